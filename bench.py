@@ -18,6 +18,9 @@ GPU, same invocation -- so that the 1 -> N ratio is read off one line.  `--weak`
 What is untimed setup: synthetic data, graph construction on the host cores (product builder,
 cached as an hnswio dump under --cache-dir), dump reload, HBM upload, exact ground truth (torch
 GEMM on the GPU: harness, not hot path).  The CPU oracle is used ONLY in the cpu_baseline leg.
+
+Same arguments, same inputs: the data are seeded and the graph is built with one host thread (--build-threads 1), so
+`--dump-outputs DIR` (the answers of the last timed step) can be compared output for output between two builds.
 """
 import argparse
 import ctypes as C
@@ -453,7 +456,9 @@ def live_traffic(args, timeout_s=120):
         return None, {"skipped": "this process is itself being profiled (rocprofv3 environment found): no nested counter runs"}
     child = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", args.config, "--data", args.data, "--steps", "3", "--warmup", "1",
              "--cache-dir", args.cache_dir, "--batches", str(args.batches), "--no-cpu-baseline", "--no-recall", "--no-concurrent",
-             "--no-boundary", "--no-traffic"]
+             "--no-boundary", "--no-traffic", "--build-threads", str(args.build_threads)]  # (the graph's cache key)
+    if args.host_build:
+        child += ["--host-build"]
     if args.n:
         child += ["--n", str(args.n)]
     if args.nq:
@@ -568,6 +573,36 @@ def boundary_timings(H, lib, index, cache_dir, base, dist_name, Q, k, ef, n, rep
     return out
 
 
+DUMP_OUTPUTS_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, answers, max_bytes=DUMP_OUTPUTS_MAX_BYTES):
+    """--dump-outputs: the answers of one step as out_dir/<name>.npy, what the caller of the path gets back: `counts` [nq] and, per
+    query, counts[i] neighbours in the [nq, k] arrays (`ids`, `dists`, and `layers` / `ranks`, the p_id, where the path returns
+    them).  The slots past counts[i] hold no answer and are written as -1 (a distance as inf).  Distances stay float32, integers
+    become float64 (exact below 2**53).  Above max_bytes in all, a fixed seeded sample of the queries is written instead, their
+    row numbers as rows.npy.  Returns the names written."""
+    counts = np.asarray(answers["counts"]).astype(np.int64)
+    out = {}
+    for name, a in answers.items():
+        a = np.asarray(a)
+        f = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        if f.ndim == 2:
+            f[np.arange(f.shape[1])[None, :] >= counts[:, None]] = np.inf if name == "dists" else -1
+        out[name] = f
+    nq = len(counts)
+    row_bytes = sum(a.nbytes for a in out.values()) / max(1, nq)
+    if nq * row_bytes > max_bytes:
+        keep = int(max_bytes // (row_bytes + 8))  # (+ 8: the row number itself)
+        rows = np.sort(np.random.default_rng(0x5EED0003).choice(nq, keep, replace=False))
+        out = {name: a[rows] for name, a in out.items()}
+        out["rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(out)
+
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -580,7 +615,8 @@ def main():
     ap.add_argument("--nq", type=int, default=0, help="override queries per GPU")
     ap.add_argument("--ef", type=int, default=0)
     ap.add_argument("--cache-dir", default=os.environ.get("HNSW_BENCH_CACHE", "/tmp/hnsw_mi355x_bench_cache"))
-    ap.add_argument("--build-threads", type=int, default=0)
+    ap.add_argument("--build-threads", type=int, default=1, help="host threads of the graph construction: 1 (default) builds the same "
+                    "graph every run, so that the same arguments give the timed steps the same inputs; 0 = all cores (32 at most)")
     ap.add_argument("--host-build", action="store_true", help="build the graph on the host cores only (default: GPU-assisted "
                     "construction: the insertions' searches on the device, window by window)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -590,6 +626,8 @@ def main():
     ap.add_argument("--no-boundary", action="store_true", help="skip the timings of the host-buffer / reference-FFI / filtered entry points")
     ap.add_argument("--dump-stats", default="", help="write the per-query kernel stats of the last step to this .npy")
     ap.add_argument("--dump-answers", default="", help="write the answers of batch 0 (all ranks' shards gathered, input order) to this .npz")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed (N > 1: gathered, input "
+                    "order) as DIR/<name>.npy, float32 / float64, 64 MB at most (dump_outputs)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend for N>1 (gloo only to exercise the multi-rank path on a 1-GPU box)")
     ap.add_argument("--weak", action="store_true", help="N > 1: a fixed number of queries per GPU (12 500 for the SIFT1M shape) "
@@ -604,6 +642,8 @@ def main():
     ap.add_argument("--batches", type=int, default=4, help="distinct query batches the steps rotate through (a step that "
                     "re-searches the batch of the previous step finds its rows in the 256 MiB Infinity Cache)")
     args = ap.parse_args(json.loads(os.environ["HNSW_BENCH_ARGV"]) if "HNSW_BENCH_ARGV" in os.environ and len(sys.argv) == 1 else None)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))  # the plain command: this process launches one rank per GPU and waits for them
@@ -693,7 +733,9 @@ def main():
 
     # ---------------------------------------------------------------- index (cached hnswio dump)
     builder = "host" if args.host_build else "gpu"
-    key = hashlib.sha1(json.dumps([args.config, n, d, cfg["dist"], cfg["M"], cfg["efc"], args.data, "v2", builder]).encode()).hexdigest()[:12]
+    # (the thread count is in the key: one thread builds the same graph every time, several threads each time another one)
+    key = hashlib.sha1(json.dumps([args.config, n, d, cfg["dist"], cfg["M"], cfg["efc"], args.data, "v2", builder,
+                                   args.build_threads]).encode()).hexdigest()[:12]
     os.makedirs(args.cache_dir, exist_ok=True)
     base = f"bench_{args.config}_{key}"
     done_marker = os.path.join(args.cache_dir, base + ".done")
@@ -813,6 +855,13 @@ def main():
     elapsed = timed(args.steps)
     ms_per_step = elapsed * 1e3 / args.steps
     qps = nq_total * args.steps / elapsed
+    if args.dump_outputs and rank == 0:  # the last timed step's answers, before any untimed step rewrites the buffers
+        if pg:  # what came back through the collective: every rank's queries, input order
+            answers = dict(zip(("ids", "dists", "counts"), xch.gathered(args.steps - 1)))
+        else:
+            answers = {"ids": out_ids, "dists": out_dists, "counts": out_counts, "layers": out_layer, "ranks": out_rank}
+        names = dump_outputs(args.dump_outputs, {name: t.cpu().numpy() for name, t in answers.items()})
+        log(f"outputs of timed step {args.steps - 1} (query batch {(args.steps - 1) % NB}) written to {args.dump_outputs}: {names}")
     timed_main_ms = list(main_ms)
     timed_kernel_ms = list(kernel_ms)
     gather_ms = None

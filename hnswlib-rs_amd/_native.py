@@ -61,7 +61,9 @@ def build_native(force=False, verbose=False):
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
             if force or not fresh():
-                r = subprocess.run(["make", "-C", CSRC_DIR, "-j%d" % max(2, os.cpu_count() or 4)], capture_output=True, text=True)
+                # at most 16 jobs (or MAX_JOBS): os.cpu_count() is the whole host's, not what this process may use
+                jobs = max(1, min(16, int(os.environ.get("MAX_JOBS") or 0) or os.cpu_count() or 4))
+                r = subprocess.run(["make", "-C", CSRC_DIR, "-j%d" % jobs], capture_output=True, text=True)
                 if verbose or r.returncode != 0:
                     print(r.stdout)
                     print(r.stderr)

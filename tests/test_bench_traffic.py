@@ -53,7 +53,8 @@ def fake_tool(tmp_path, monkeypatch):
 
 
 def _args(tmp_path):
-    return argparse.Namespace(config="random10k", data="uniform", cache_dir=str(tmp_path), batches=4, n=0, nq=0, ef=0)
+    return argparse.Namespace(config="random10k", data="uniform", cache_dir=str(tmp_path), batches=4, n=0, nq=0, ef=0,
+                              build_threads=1, host_build=False)
 
 
 def test_live_traffic_averages_the_strict_launches_and_applies_the_corrections(fake_tool, tmp_path):
