@@ -891,9 +891,10 @@ int DeviceIndex::search_device(const float* d_queries, uint64_t nq, uint64_t d, 
         if (kn.waves_per_cu > 0) per_cu = std::max(1, std::min(per_cu, kn.waves_per_cu));  // tuning hook
         uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)per_cu * (uint64_t)num_cu_, work);
         if (kn.trace_launch)  // diagnostics: what bounds the resident workgroups of this launch
-            std::fprintf(stderr, "[hnswgpu launch] %u queries, %d workgroups per CU (strict cap %d), %zu bytes of LDS each (literal heap: %u entries), table 2^%u cells, strict %d, work list %s\n",
+            std::fprintf(stderr, "[hnswgpu launch] %u queries, %d workgroups per CU (strict cap %d), %zu bytes of LDS each (literal heap: %u entries), table 2^%u cells, strict %d, work list %s, slots %d, visited set %s\n",
                          work, per_cu, strict_cap, lds, a.cand_lds, a.tbits, (int)strict_kernel,
-                         qlist ? "sorted" : "input order");
+                         qlist ? "sorted" : "input order", slots,
+                         table == TABLE_LDS_CELL16 ? "cell16" : table == TABLE_LDS_CELL32 ? "cell32" : "bitmap");
         a.queries = w.qpad.as<float>();
         a.qlist = qlist;
         a.nq = work;

@@ -1902,7 +1902,9 @@ __global__ __launch_bounds__(64, STRICT ? (S >= 16 ? 2 : S == 4 && HNSW_PIPE_ROW
         if (q == EMPTY_SLOT) break;
         const uint32_t t_start = (uint32_t)wall_clock64();
 
-        uint32_t n_dist = 0, n_expand = 0, n_ids = 0, status = 0, n_visited = 1;
+        // n_dist starts at 1: the reference evaluates the layer-0 entry point a second time (src/hnsw.rs:952); its distance
+        // is the descent's dcur here, but the work counters follow the reference (include/hnsw_mi355x.h, d_stats)
+        uint32_t n_dist = 1, n_expand = 0, n_ids = 0, status = 0, n_visited = 1;
         bool flag_tie = false;  // (A)-(C) met and not resolved here
 #if HNSW_PHASE_TIMING
         uint32_t ph[4] = {0, 0, 0, 0};
@@ -2357,7 +2359,7 @@ __global__ __launch_bounds__(64, 4) void hnsw_search_exact_kernel(DeviceIndexVie
         stage_query<METRIC>(tile, a.queries + (size_t)q * ix.row_stride, ix.row_stride, lane, ix.d);
         for (uint32_t i = (uint32_t)lane; i < a.bitmap_words; i += 64) bitmap[i] = 0u;
         __syncthreads();
-        uint32_t n_dist = 0, n_expand = 0, n_ids = 0, status = 0;
+        uint32_t n_dist = 1, n_expand = 0, n_ids = 0, status = 0;  // (1: the second evaluation of the entry point, :952)
 
         // ---- descent (src/hnsw.rs:1506-1529): done by hnsw_descend_kernel, like the main kernel's
         const PreDescent pd = a.pre[q];

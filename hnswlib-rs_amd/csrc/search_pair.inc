@@ -570,7 +570,8 @@ __global__ __launch_bounds__(64, HNSW_LB_PAIR) void hnsw_search_pair_kernel(Devi
                         if (st_v == 1u || ((bm >> half) & 1u) != 0u) atomicAdd(counters + 1, 1u);
                         if (nvis_v > (table_limit >> 1)) atomicAdd(counters + 2, 1u);
                         uint32_t* st = a.stats + (size_t)q * 8;
-                        st[0] = pd.n_dist + nvis_v - 1u; st[1] = pd.n_expand + nexp_v; st[2] = pd.n_dist - 1u + nids; st[3] = out_status;
+                        // n_dist: the descent's, the entry point once more (:952) and the nvis_v - 1 fresh ids
+                        st[0] = pd.n_dist + nvis_v; st[1] = pd.n_expand + nexp_v; st[2] = pd.n_dist - 1u + nids; st[3] = out_status;
                         st[4] = t_start; st[5] = (uint32_t)wall_clock64(); st[6] = ((bm >> half) & 1u) != 0u ? 1u : 0u;
                         st[7] = (tie_v != 0u ? 1u : 0u) | ((pd.n_expand & 0xFFu) << 8) | (pd.n_dist << 16);
 #if HNSW_PAIR_PHASES

@@ -221,8 +221,17 @@ int hnswgpu_gather_sharded_answers(const int* devices, int n_shards, const uint6
  * before returning (the visited-set overflow check needs one 4-byte read-back).
  * d_stats may be NULL, else uint32[nq*8] per query = {n_dist, n_expand, n_ids_read, status,
  * t_start, t_end (device wall clock, 10 ns ticks), used_hbm_bitmap, flags | (lists scanned by the greedy descent << 8) | (its n_dist << 16)}
- * (flags: 1 equal distances met, 2 a pop was taken from the literal candidate heap; n_dist / n_expand / n_ids_read include
- * the descent, which runs in a kernel of its own in front of the search kernel; its ids read = its n_dist - 1).
+ * (flags: 1 equal distances met, 2 a pop was taken from the literal candidate heap).  The work counters are the reference's,
+ * query by query, whichever kernel or pass answered (Hnsw::search_filter, src/hnsw.rs:1487-1580, with search_layer :922-1064):
+ *   n_dist     = calls of Distance::eval: the entry point (:1506), every id of every list the descent reads (:1518), the
+ *                layer-0 entry point once more (:952; the device reuses the descent's value but counts it) and every
+ *                neighbour not yet visited (:1026);
+ *   n_expand   = neighbour lists read: one per layer above the search layer (:1515) and one per candidate popped and not
+ *                ended by the stop rule (:981-993, :1006);
+ *   n_ids_read = the ids of those lists;
+ *   word 7 bits 8-15 / 16-31 = the descent's (:1506-1529, everything before search_layer) n_expand / n_dist; its ids read are
+ *                its n_dist - 1.  The descent runs in a kernel of its own in front of the search kernel.
+ * These are the oracle's per-query counters (orc_parallel_search_counted), which tests/test_gpu_counters.py compares them with.
  * status: 0 ok; 2 ok, but the answer depends on the reference's heap order and strict ties are off;
  * 3 ok, resolved with the literal heaps (strict ties; see DESIGN.md "ties").  ef above 1024 (the
  * register-resident result set) is served by the literal-heap kernel: correct, slower.          */

@@ -511,9 +511,11 @@ public:
     }
 
     // ---- search_filter (src/hnsw.rs:1487-1580); filter == nullptr is Hnsw::search ---------
+    // descent (may be null; needs cnt): what of *cnt the greedy descent added (:1506-1529, everything before search_layer)
     std::vector<Neighbour> search(const float* data, size_t knbn, size_t ef_arg, Counters* cnt = nullptr,
-                                  const Filter* filter = nullptr) const {
+                                  const Filter* filter = nullptr, Counters* descent = nullptr) const {
         if (!entry_point) return {};                                       // :1498-1503
+        const Counters before = cnt ? *cnt : Counters{};
         float dist_to_entry = eval(data, entry_point->v.data(), cnt);      // :1506
         std::shared_ptr<Point> pivot = entry_point;
         std::shared_ptr<Point> new_pivot;
@@ -531,6 +533,8 @@ public:
             }
             if (has_changed) pivot = new_pivot;                            // :1526-1528
         }
+        if (descent && cnt)
+            *descent = Counters{cnt->n_dist - before.n_dist, cnt->n_expand - before.n_expand, cnt->n_ids_read - before.n_ids_read};
         size_t ef = std::max(ef_arg, knbn);                                // :1531
         uint8_t l = 0;                                                     // :1534-1540
         while (get_layer_nb_point(l) == 0) l++;
@@ -549,10 +553,11 @@ public:
 
     // ---- parallel_search (src/hnsw.rs:1612-1635): per-item search, answers in input order.
     // Rayon's pool is restated as nthreads workers pulling request indices from an atomic
-    // counter (work-stealing has no observable effect on results).
+    // counter (work-stealing has no observable effect on results).  per_query (may be null):
+    // nq x 5 = {n_dist, n_expand, n_ids_read, descent n_dist, descent n_expand} of every query.
     std::vector<std::vector<Neighbour>> parallel_search(const std::vector<std::vector<float>>& datas,
                                                         size_t knbn, size_t ef, int nthreads,
-                                                        Counters* total = nullptr) const {
+                                                        Counters* total = nullptr, uint64_t* per_query = nullptr) const {
         size_t nq = datas.size();
         std::vector<std::vector<Neighbour>> answers(nq);
         if (nthreads <= 0) nthreads = (int)std::thread::hardware_concurrency();
@@ -564,7 +569,14 @@ public:
             for (;;) {
                 size_t i = next.fetch_add(1);
                 if (i >= nq) break;
-                answers[i] = search(datas[i].data(), knbn, ef, total ? &cnts[t] : nullptr);
+                if (per_query) {
+                    Counters c, dsc;
+                    answers[i] = search(datas[i].data(), knbn, ef, &c, nullptr, &dsc);
+                    store_per_query(per_query + i * 5, c, dsc);
+                    if (total) cnts[t].add(c);
+                } else {
+                    answers[i] = search(datas[i].data(), knbn, ef, total ? &cnts[t] : nullptr);
+                }
             }
         };
         std::vector<std::thread> th;
@@ -573,6 +585,10 @@ public:
         for (auto& x : th) x.join();
         if (total) for (auto& c : cnts) total->add(c);
         return answers;
+    }
+
+    static void store_per_query(uint64_t* row, const Counters& c, const Counters& dsc) {
+        row[0] = c.n_dist; row[1] = c.n_expand; row[2] = c.n_ids_read; row[3] = dsc.n_dist; row[4] = dsc.n_expand;
     }
 
     // ---- construction: insert_slice (src/hnsw.rs:1077-1215), serial ----------------------

@@ -81,17 +81,16 @@ int orc_pinning_cpu(int t) {
     return o.empty() ? -1 : o[(size_t)t % o.size()];
 }
 
-int orc_parallel_search(void* hv, const float* queries, size_t nq, size_t d, size_t k, size_t ef, int nthreads,
-                        uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank,
-                        uint32_t* out_counts, uint64_t* counters, double* elapsed_s) {
-    ORC_TRY
+static void parallel_search_impl(void* hv, const float* queries, size_t nq, size_t d, size_t k, size_t ef, int nthreads,
+                                 uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank,
+                                 uint32_t* out_counts, uint64_t* counters, uint64_t* per_query, double* elapsed_s) {
     Hnsw* h = static_cast<Hnsw*>(hv);
     if (h->data_dimension && d != h->data_dimension) throw std::runtime_error("search: dimension mismatch");
     std::vector<std::vector<float>> datas(nq);
     for (size_t i = 0; i < nq; ++i) datas[i].assign(queries + i * d, queries + (i + 1) * d);
     Counters total;
     auto t0 = std::chrono::steady_clock::now();
-    auto ans = h->parallel_search(datas, k, ef, nthreads, counters ? &total : nullptr);
+    auto ans = h->parallel_search(datas, k, ef, nthreads, counters ? &total : nullptr, per_query);
     auto t1 = std::chrono::steady_clock::now();
     if (elapsed_s) *elapsed_s = std::chrono::duration<double>(t1 - t0).count();
     for (size_t i = 0; i < nq; ++i) {
@@ -109,6 +108,26 @@ int orc_parallel_search(void* hv, const float* queries, size_t nq, size_t d, siz
         counters[1] = total.n_expand;
         counters[2] = total.n_ids_read;
     }
+}
+int orc_parallel_search(void* hv, const float* queries, size_t nq, size_t d, size_t k, size_t ef, int nthreads,
+                        uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank,
+                        uint32_t* out_counts, uint64_t* counters, double* elapsed_s) {
+    ORC_TRY
+    parallel_search_impl(hv, queries, nq, d, k, ef, nthreads, out_ids, out_dists, out_layer, out_rank, out_counts, counters,
+                         nullptr, elapsed_s);
+    return 0;
+    ORC_CATCH(-1)
+}
+// The same with the work counters of every query: per_query = uint64[nq][5] = {n_dist, n_expand, n_ids_read, the descent's
+// n_dist, the descent's n_expand} ("descent" = src/hnsw.rs:1506-1529, everything before search_layer; its ids read are its
+// n_dist - 1).  n_dist counts every Distance::eval of the search, the second one of the layer-0 entry point (:952) included.
+int orc_parallel_search_counted(void* hv, const float* queries, size_t nq, size_t d, size_t k, size_t ef, int nthreads,
+                                uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank,
+                                uint32_t* out_counts, uint64_t* per_query, double* elapsed_s) {
+    ORC_TRY
+    if (!per_query) throw std::runtime_error("orc_parallel_search_counted: per_query is NULL");
+    parallel_search_impl(hv, queries, nq, d, k, ef, nthreads, out_ids, out_dists, out_layer, out_rank, out_counts, nullptr,
+                         per_query, elapsed_s);
     return 0;
     ORC_CATCH(-1)
 }
@@ -136,10 +155,10 @@ int orc_search_filter(void* hv, const float* q, size_t d, size_t k, size_t ef, c
 // tests/filtertest.rs:155-271), on nthreads workers pulling query indices from a counter; answers in input order.
 // out_status[i] = 1 where the reference panics on query i (src/hnsw.rs:973: peek().unwrap() on an emptied heap), count 0.
 // counters (may be null): {n_dist, n_expand, n_ids_read} summed over the batch.
-int orc_parallel_search_filter(void* hv, const float* queries, size_t nq, size_t d, size_t k, size_t ef, const uint64_t* allowed,
-                               size_t n_allowed, int nthreads, uint64_t* out_ids, float* out_dists, uint8_t* out_layer,
-                               int32_t* out_rank, uint32_t* out_counts, uint8_t* out_status, uint64_t* counters, double* elapsed_s) {
-    ORC_TRY
+static void parallel_search_filter_impl(void* hv, const float* queries, size_t nq, size_t d, size_t k, size_t ef,
+                                        const uint64_t* allowed, size_t n_allowed, int nthreads, uint64_t* out_ids,
+                                        float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts,
+                                        uint8_t* out_status, uint64_t* counters, uint64_t* per_query, double* elapsed_s) {
     Hnsw* h = static_cast<Hnsw*>(hv);
     if (h->data_dimension && d != h->data_dimension) throw std::runtime_error("search: dimension mismatch");
     Hnsw::Filter f(allowed, allowed + n_allowed);
@@ -155,11 +174,14 @@ int orc_parallel_search_filter(void* hv, const float* queries, size_t nq, size_t
             if (i >= nq) break;
             std::vector<Neighbour> r;
             uint8_t st = 0;
+            Counters c, dsc;
             try {
-                r = h->search(queries + i * d, k, ef, counters ? &cnts[(size_t)t] : nullptr, &f);
+                r = h->search(queries + i * d, k, ef, &c, &f, per_query ? &dsc : nullptr);
             } catch (const std::runtime_error&) {
                 st = 1;  // (the only throw a well-formed search can meet: the reference's panic)
             }
+            if (counters) cnts[(size_t)t].add(c);
+            if (per_query) Hnsw::store_per_query(per_query + i * 5, c, dsc);  // (a panicking query: the work up to the panic)
             for (size_t j = 0; j < k; ++j) {
                 const bool have = j < r.size();
                 out_ids[i * k + j] = have ? r[j].d_id : 0;
@@ -184,6 +206,25 @@ int orc_parallel_search_filter(void* hv, const float* queries, size_t nq, size_t
         counters[1] = total.n_expand;
         counters[2] = total.n_ids_read;
     }
+}
+int orc_parallel_search_filter(void* hv, const float* queries, size_t nq, size_t d, size_t k, size_t ef, const uint64_t* allowed,
+                               size_t n_allowed, int nthreads, uint64_t* out_ids, float* out_dists, uint8_t* out_layer,
+                               int32_t* out_rank, uint32_t* out_counts, uint8_t* out_status, uint64_t* counters, double* elapsed_s) {
+    ORC_TRY
+    parallel_search_filter_impl(hv, queries, nq, d, k, ef, allowed, n_allowed, nthreads, out_ids, out_dists, out_layer, out_rank,
+                                out_counts, out_status, counters, nullptr, elapsed_s);
+    return 0;
+    ORC_CATCH(-1)
+}
+// The same with per_query = uint64[nq][5] as in orc_parallel_search_counted.
+int orc_parallel_search_filter_counted(void* hv, const float* queries, size_t nq, size_t d, size_t k, size_t ef,
+                                       const uint64_t* allowed, size_t n_allowed, int nthreads, uint64_t* out_ids,
+                                       float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts,
+                                       uint8_t* out_status, uint64_t* per_query, double* elapsed_s) {
+    ORC_TRY
+    if (!per_query) throw std::runtime_error("orc_parallel_search_filter_counted: per_query is NULL");
+    parallel_search_filter_impl(hv, queries, nq, d, k, ef, allowed, n_allowed, nthreads, out_ids, out_dists, out_layer, out_rank,
+                                out_counts, out_status, nullptr, per_query, elapsed_s);
     return 0;
     ORC_CATCH(-1)
 }

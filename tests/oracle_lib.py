@@ -55,6 +55,7 @@ def lib():
         L.orc_parallel_search.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                           C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]
+        L.orc_parallel_search_counted.argtypes = L.orc_parallel_search.argtypes
         L.orc_file_dump.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
         L.orc_load.restype = C.c_void_p
         L.orc_load.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
@@ -80,6 +81,7 @@ def lib():
         L.orc_parallel_search_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p,
                                                  C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_parallel_search_filter_counted.argtypes = L.orc_parallel_search_filter.argtypes
         L.orc_heap_retain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.orc_heap_script.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p]
@@ -93,6 +95,10 @@ def _err():
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+# columns of SearchResult.per_query (want_counters="per_query")
+PER_QUERY_FIELDS = ("n_dist", "n_expand", "n_ids_read", "descent_n_dist", "descent_n_expand")
 
 
 class SearchResult:
@@ -164,6 +170,8 @@ class OracleHnsw:
         return ids[:n], dists[:n], layers[:n], ranks[:n]
 
     def parallel_search(self, queries, k, ef, nthreads=0, want_counters=False):
+        """want_counters: True = batch totals in .counters; "per_query" = also .per_query, uint64 (nq, 5) =
+        (n_dist, n_expand, n_ids_read, descent n_dist, descent n_expand) of every query (PER_QUERY_FIELDS)."""
         queries = np.ascontiguousarray(queries, dtype=np.float32)
         nq, d = queries.shape
         ids = np.zeros((nq, k), np.uint64)
@@ -173,13 +181,22 @@ class OracleHnsw:
         counts = np.zeros(nq, np.uint32)
         counters = np.zeros(3, np.uint64)
         elapsed = C.c_double(0.0)
-        rc = lib().orc_parallel_search(self.h, _p(queries), nq, d, k, ef, nthreads, _p(ids), _p(dists), _p(layers),
-                                       _p(ranks), _p(counts), _p(counters) if want_counters else None,
-                                       C.byref(elapsed))
+        per_query = want_counters == "per_query"
+        if per_query:
+            pq = np.zeros((nq, 5), np.uint64)
+            rc = lib().orc_parallel_search_counted(self.h, _p(queries), nq, d, k, ef, nthreads, _p(ids), _p(dists), _p(layers),
+                                                   _p(ranks), _p(counts), _p(pq), C.byref(elapsed))
+        else:
+            rc = lib().orc_parallel_search(self.h, _p(queries), nq, d, k, ef, nthreads, _p(ids), _p(dists), _p(layers),
+                                           _p(ranks), _p(counts), _p(counters) if want_counters else None,
+                                           C.byref(elapsed))
         if rc != 0:
             raise RuntimeError(_err())
         res = SearchResult(ids, dists, layers, ranks, counts)
         res.elapsed_s = elapsed.value
+        if per_query:
+            res.per_query = pq
+            counters = pq[:, :3].sum(0, dtype=np.uint64)
         res.counters = dict(n_dist=int(counters[0]), n_expand=int(counters[1]), n_ids_read=int(counters[2]))
         return res
 
@@ -200,7 +217,8 @@ class OracleHnsw:
         return ids[:c], dists[:c], layers[:c], ranks[:c]
 
     def parallel_search_filter(self, queries, k, ef, allowed_ids, nthreads=0, want_counters=False):
-        """search_filter for every row of `queries` on worker threads; .status[i] == 1 where the reference panics."""
+        """search_filter for every row of `queries` on worker threads; .status[i] == 1 where the reference panics.
+        want_counters as in parallel_search (a panicking query's row holds the work up to the panic)."""
         queries = np.ascontiguousarray(queries, dtype=np.float32)
         allowed = np.ascontiguousarray(allowed_ids, dtype=np.uint64)
         nq, d = queries.shape
@@ -212,14 +230,24 @@ class OracleHnsw:
         status = np.zeros(nq, np.uint8)
         counters = np.zeros(3, np.uint64)
         elapsed = C.c_double(0.0)
-        rc = lib().orc_parallel_search_filter(C.c_void_p(self.h), _p(queries), nq, d, k, ef, _p(allowed), len(allowed), nthreads,
-                                              _p(ids), _p(dists), _p(layers), _p(ranks), _p(counts), _p(status),
-                                              _p(counters) if want_counters else None, C.byref(elapsed))
+        per_query = want_counters == "per_query"
+        if per_query:
+            pq = np.zeros((nq, 5), np.uint64)
+            rc = lib().orc_parallel_search_filter_counted(C.c_void_p(self.h), _p(queries), nq, d, k, ef, _p(allowed), len(allowed),
+                                                          nthreads, _p(ids), _p(dists), _p(layers), _p(ranks), _p(counts),
+                                                          _p(status), _p(pq), C.byref(elapsed))
+        else:
+            rc = lib().orc_parallel_search_filter(C.c_void_p(self.h), _p(queries), nq, d, k, ef, _p(allowed), len(allowed), nthreads,
+                                                  _p(ids), _p(dists), _p(layers), _p(ranks), _p(counts), _p(status),
+                                                  _p(counters) if want_counters else None, C.byref(elapsed))
         if rc != 0:
             raise RuntimeError(_err())
         res = SearchResult(ids, dists, layers, ranks, counts)
         res.status = status
         res.elapsed_s = elapsed.value
+        if per_query:
+            res.per_query = pq
+            counters = pq[:, :3].sum(0, dtype=np.uint64)
         res.counters = counters if want_counters else None
         return res
 

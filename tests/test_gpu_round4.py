@@ -120,6 +120,40 @@ def test_filtered_search_at_full_size(native, oracle, sift1m):
         assert_same(got, ref)
 
 
+def test_config2_counters_per_query_at_full_size(native, oracle, sift1m):
+    """BASELINE config 2 (10 000 clustered queries, k = 10, ef = 64, strict) on the 1M x 128 index: the device's per-query work
+    counters are the oracle's (include/hnsw_mi355x.h, d_stats), and so are the algorithmic bytes bench.py derives from them."""
+    from test_gpu_counters import check
+    h, o, stored = sift1m
+    h.upload(0)
+    k, ef, d = 10, 64, 128
+    Q = _clustered(10_000, d, 0x5EED0002)
+    res, ref = check(native, h, o, Q, k, ef, "config 2")   # (strict, then lean)
+    assert (res.st[:, 3] == 3).any()                        # the duplicates send some queries through the replay
+
+    # SURVEY.md 8(d): bytes = n_dist*d*4 + n_ids_read*4 + n_expand*8 + d*4 + k*12 per query (d unpadded)
+    def survey_bytes(n_dist, n_ids, n_expand, nq):
+        return int(n_dist.sum()) * d * 4 + int(n_ids.sum()) * 4 + int(n_expand.sum()) * 8 + nq * (d * 4 + k * 12)
+    st, pq = res.st.astype(np.int64), ref.per_query.astype(np.int64)
+    assert survey_bytes(st[:, 0], st[:, 2], st[:, 1], len(Q)) == survey_bytes(pq[:, 0], pq[:, 2], pq[:, 1], len(Q))
+
+
+def test_32_bit_visited_cells_count_like_the_oracle(native, oracle, sift1m, knob, capfd):
+    """ceil_log2(1M) = 20 id bits, ef = 10: the default table of 2^9 cells leaves 20 - 6 = 14 bits per cell, more than a 16-bit
+    cell holds -- the 32-bit-cell kernels; answers and per-query counters are the oracle's, strict and lean."""
+    from test_gpu_counters import _device_search, check
+    h, o, stored = sift1m
+    h.upload(0)
+    Q = np.concatenate([_clustered(300, 128, 0x5EED0009), stored[:100]])
+    knob("HNSWGPU_TRACE_LAUNCH", "1")
+    capfd.readouterr()
+    res = _device_search(native, h, Q, 10, 10)
+    knob("HNSWGPU_TRACE_LAUNCH", None)
+    lines = [ln for ln in capfd.readouterr().err.splitlines() if ln.startswith("[hnswgpu launch]")]
+    assert any("visited set cell32" in ln for ln in lines), lines
+    check(native, h, o, Q, 10, 10, "cell32", res=res)
+
+
 # ------------------------------------------------------------------------------------------------- SIMD-order arithmetic (opt-in)
 SIMD8_DIMS = list(range(1, 131)) + [136, 159, 160, 161, 200, 255, 256, 257, 300, 383, 384, 500, 511, 512, 640, 767, 768, 783, 784, 785, 800]
 

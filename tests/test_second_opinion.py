@@ -53,12 +53,36 @@ class _Graph:
         return self.eval(q, self.dm.get_data(self.origin[pid]))
 
 
-def _search_layer(g, q, entry, ef, layer):
+class _Work:
+    """The work of one search, counted on this walk alone: every Distance::eval, every neighbour list read and its ids, and what
+    of that the greedy descent did (src/hnsw.rs:1506-1529, everything before search_layer)."""
+
+    def __init__(self):
+        self.n_dist = self.n_expand = self.n_ids_read = self.descent_n_dist = self.descent_n_expand = 0
+
+    def row(self):
+        return [self.n_dist, self.n_expand, self.n_ids_read, self.descent_n_dist, self.descent_n_expand]
+
+
+def _read_list(w, lst):
+    if w is not None:
+        w.n_expand += 1
+        w.n_ids_read += len(lst)
+    return lst
+
+
+def _eval(w, g, q, pid):
+    if w is not None:
+        w.n_dist += 1
+    return g.dist(q, pid)
+
+
+def _search_layer(g, q, entry, ef, layer, w=None):
     """src/hnsw.rs:922-1064, filter = None.  Heaps hold (key, PointId); BinaryHeap compares keys only."""
     ret, cand = _StdBinaryHeap(), _StdBinaryHeap()
     if g.h.get_layer_nb_point(layer) == 0:           # :942-946
         return ret
-    d0 = g.dist(q, entry)                             # :952
+    d0 = _eval(w, g, q, entry)                        # :952
     visited = {entry}                                 # :955-956
     cand.push((-float(d0), entry))                    # :958-963
     ret.push((float(d0), entry))                      # :964-967
@@ -67,14 +91,14 @@ def _search_layer(g, q, entry, ef, layer):
         f = ret.d[0]                                  # peek: the root
         if -c[0] > f[0]:                              # :981
             return ret                                # :993
-        for e in g.neighbours(c[1], layer):           # :1005-1014
+        for e in _read_list(w, g.neighbours(c[1], layer)):  # :1005-1014
             if e in visited:                          # :1015
                 continue
             visited.add(e)                            # :1016
             if not ret.d:
                 return ret
             fd = ret.d[0][0]
-            de = float(g.dist(q, e))                  # :1026
+            de = float(_eval(w, g, q, e))             # :1026
             if de < fd or len(ret.d) < ef:            # :1028
                 cand.push((-de, e))                   # :1035-1036
                 ret.push((de, e))                     # :1038
@@ -83,24 +107,32 @@ def _search_layer(g, q, entry, ef, layer):
     return ret
 
 
-def _search(g, q, knbn, ef_arg):
-    """src/hnsw.rs:1487-1580, filter = None"""
+def _descend(g, q, w):
+    """src/hnsw.rs:1506-1529: the pivot of the search layer"""
     entry = g.entry
-    dist_to_entry = g.dist(q, entry)
+    dist_to_entry = _eval(w, g, q, entry)
     pivot = entry
     for layer in range(entry[0], 0, -1):              # :1510: (1..=entry_point.p_id.0).rev()
         new_pivot, changed = None, False
-        for n in g.neighbours(pivot, layer):
-            tmp = g.dist(q, n)
+        for n in _read_list(w, g.neighbours(pivot, layer)):
+            tmp = _eval(w, g, q, n)
             if tmp < dist_to_entry:
                 new_pivot, changed, dist_to_entry = n, True, tmp
         if changed:
             pivot = new_pivot
+    if w is not None:
+        w.descent_n_dist, w.descent_n_expand = w.n_dist, w.n_expand
+    return pivot
+
+
+def _search(g, q, knbn, ef_arg, w=None):
+    """src/hnsw.rs:1487-1580, filter = None"""
+    pivot = _descend(g, q, w)
     ef = max(ef_arg, knbn)                            # :1531
     layer = 0
     while g.h.get_layer_nb_point(layer) == 0:         # :1534-1540
         layer += 1
-    heap = _search_layer(g, q, pivot, ef, layer)
+    heap = _search_layer(g, q, pivot, ef, layer, w)
     srt = heap.into_sorted_vec()                      # :1544
     last = min(knbn, ef, len(srt))                    # :1547
     return [(g.origin[p], f32(d), p) for d, p in srt[:last]]
@@ -183,13 +215,13 @@ class _ReferencePanic(Exception):
     pass
 
 
-def _search_layer_filtered(g, q, entry, ef, layer, allowed):
+def _search_layer_filtered(g, q, entry, ef, layer, allowed, w=None):
     """src/hnsw.rs:922-1064 with a filter (`impl FilterT for Vec<usize>`: binary search of the origin id, src/filter.rs:11-15)"""
     ok = lambda pid: g.origin[pid] in allowed  # noqa: E731
     ret, cand = _HeapWithRetain(), _HeapWithRetain()
     if g.h.get_layer_nb_point(layer) == 0:
         return ret
-    d0 = float(g.dist(q, entry))
+    d0 = float(_eval(w, g, q, entry))
     visited = {entry}
     cand.push((-d0, entry))
     ret.push((d0, entry))                              # (the entry point goes in whether the filter allows it or not, :964-967)
@@ -200,14 +232,14 @@ def _search_layer_filtered(g, q, entry, ef, layer, allowed):
         f = ret.d[0]
         if -c[0] > f[0] and len(ret.d) >= ef:          # :981, :994-1000: no return with a filter
             ret.retain(lambda e: ok(e[1]))
-        for e in g.neighbours(c[1], layer):
+        for e in _read_list(w, g.neighbours(c[1], layer)):
             if e in visited:
                 continue
             visited.add(e)
             if not ret.d:
                 return ret                             # :1019-1024
             fd = ret.d[0][0]
-            de = float(g.dist(q, e))
+            de = float(_eval(w, g, q, e))
             if de < fd or len(ret.d) < ef:
                 cand.push((-de, e))
                 if ok(e):                              # :1040-1049
@@ -219,23 +251,13 @@ def _search_layer_filtered(g, q, entry, ef, layer, allowed):
     return ret
 
 
-def _search_filtered(g, q, knbn, ef_arg, allowed):
-    entry = g.entry
-    dist_to_entry = g.dist(q, entry)
-    pivot = entry
-    for layer in range(entry[0], 0, -1):
-        new_pivot, changed = None, False
-        for n in g.neighbours(pivot, layer):
-            tmp = g.dist(q, n)
-            if tmp < dist_to_entry:
-                new_pivot, changed, dist_to_entry = n, True, tmp
-        if changed:
-            pivot = new_pivot
+def _search_filtered(g, q, knbn, ef_arg, allowed, w=None):
+    pivot = _descend(g, q, w)
     ef = max(ef_arg, knbn)
     layer = 0
     while g.h.get_layer_nb_point(layer) == 0:
         layer += 1
-    srt = _search_layer_filtered(g, q, pivot, ef, layer, allowed).into_sorted_vec()
+    srt = _search_layer_filtered(g, q, pivot, ef, layer, allowed, w).into_sorted_vec()
     last = min(knbn, ef, len(srt))
     return [(g.origin[p], f32(d), p) for d, p in srt[:last] if g.origin[p] in allowed]   # :1549-1565
 
@@ -296,3 +318,33 @@ def test_python_transcription_against_the_oracle_under_filters_of_all_densities(
         assert np.array_equal(np.array([d_ for _, d_, _ in got], f32).view(np.uint32), ref[1].view(np.uint32)), i
         assert [p[1] for _, _, p in got] == [int(v) for v in ref[3]], i
     assert answered + panics == len(Q)
+
+
+@pytest.mark.parametrize("name,filtered", [("l2_d25", False), ("l2_dup_d16", False), ("l1_grid_d4", False),
+                                           ("l2_d25", True), ("l2_dup_d16", True), ("l1_grid_d4", True)])
+def test_python_transcription_counts_the_work_the_oracle_counts(native, oracle, name, filtered):
+    """The five per-query work counters of the oracle (n_dist, n_expand, n_ids_read and the descent's n_dist, n_expand) are what
+    this walk counts on its own: tie-free (l2_d25), tie-saturated (l2_dup_d16, l1_grid_d4) and filtered, panics included."""
+    z = np.load(os.path.join(GOLD, name + ".npz"))
+    k, ef, dist = int(z["k"]), int(z["ef"]), str(z["dist"])
+    g = _Graph(native, name, dist)
+    o = oracle.OracleHnsw.load(GOLD, name, dist)
+    Q = np.ascontiguousarray(z["queries"][:40], dtype=np.float32)
+    if filtered:
+        allowed = np.ascontiguousarray(z["filter_ids"], dtype=np.uint64)
+        ref = o.parallel_search_filter(Q, k, ef, allowed, nthreads=2, want_counters="per_query")
+        aset = set(int(v) for v in allowed)
+    else:
+        ref = o.parallel_search(Q, k, ef, nthreads=2, want_counters="per_query")
+    assert ref.per_query.shape == (len(Q), 5)
+    for i in range(len(Q)):
+        w = _Work()
+        try:
+            if filtered:
+                _search_filtered(g, Q[i], k, ef, aset, w)
+            else:
+                _search(g, Q[i], k, ef, w)
+        except _ReferencePanic:
+            assert ref.status[i] == 1, (name, i)
+        assert w.row() == [int(v) for v in ref.per_query[i]], (name, filtered, i, w.row(), ref.per_query[i].tolist())
+        assert w.n_ids_read >= w.descent_n_dist - 1 and w.descent_n_dist >= 1
