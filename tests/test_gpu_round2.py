@@ -8,6 +8,7 @@ import threading
 import numpy as np
 import pytest
 
+import f64_reference as F
 from conftest import normalized, probability, uniform
 from test_gpu_parity import assert_same, build_pair
 
@@ -288,6 +289,8 @@ def _full_size_case(native, oracle, tmp_path, knob, n, d, m, efc, k, ef, nq, n_d
     ref = o.parallel_search(Q, k, ef)
     res = h.parallel_search_flat(Q, k, ef)
     assert_same(res, ref)
+    fails = F.check_per_answer("DistL2", X, Q, res.ids, res.dists, res.counts)   # the f64 reference, answer by answer
+    assert not fails, fails[:4]
     ties = h.last_tie_count()
     # every query through the literal candidate heap (hand-over at the first pop) and, where equal distances reach the
     # answer, the literal result heap: same answers

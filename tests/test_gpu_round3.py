@@ -51,6 +51,7 @@ def test_bench_gpus_2_as_a_plain_command_gathers_the_one_gpu_answers(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------- full size
+import f64_reference as F  # noqa: E402
 from test_gpu_parity import assert_same  # noqa: E402
 from test_gpu_round2 import _clustered  # noqa: E402
 
@@ -81,6 +82,8 @@ def _full_size(native, oracle, tmp_path, knob, n, d, m, efc, dist, k, ef, nq, n_
     ref = o.parallel_search(Q, k, ef)
     res = h.parallel_search_flat(Q, k, ef)
     assert_same(res, ref)
+    fails = F.check_per_answer(dist, X, Q, res.ids, res.dists, res.counts)   # the f64 reference: row addressing, norms, id widths
+    assert not fails, fails[:4]
     ties = h.last_tie_count()
     knob("HNSWGPU_EXACT_FIRST", "1")
     assert_same(h.parallel_search_flat(Q, k, ef), ref)

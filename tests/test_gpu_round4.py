@@ -15,15 +15,29 @@ from test_gpu_round2 import _clustered  # noqa: E402
 
 
 # ------------------------------------------------------------------------------------------------- config 4 at full size
+def _sift1m_vectors():
+    """the 1M x 128 vectors of the sift1m index (regenerated where a test needs them: 512 MB are not kept around)"""
+    n, d = 1_000_000, 128
+    X = _clustered(n, d, 0x5EED0001)
+    rng = np.random.default_rng(3)
+    X[rng.choice(n, 2000, replace=False)] = X[rng.choice(n, 2000, replace=False)]  # exact duplicates under distinct ids
+    return X
+
+
+def _assert_f64_per_answer(Q, res):
+    """every returned (id, dist) within the f64 reference's bound of d(q, X[id]); unique ids; non-decreasing distances"""
+    import f64_reference as F
+    fails = F.check_per_answer("DistL2", _sift1m_vectors(), Q, res.ids, res.dists, res.counts)
+    assert not fails, fails[:4]
+
+
 @pytest.fixture(scope="module")
 def sift1m(native, oracle, tmp_path_factory):
     """BASELINE config 2 / 4's index at its real size, built once for the module: 1M x 128 clustered, M=16, ef_c=200,
     GPU-assisted construction (the product's) -> hnswio dump -> product reload and oracle reload of the same files."""
     tmp = tmp_path_factory.mktemp("sift1m")
     n, d = 1_000_000, 128
-    X = _clustered(n, d, 0x5EED0001)
-    rng = np.random.default_rng(3)
-    X[rng.choice(n, 2000, replace=False)] = X[rng.choice(n, 2000, replace=False)]  # exact duplicates under distinct ids
+    X = _sift1m_vectors()
     hb = native.Hnsw(16, n, 16, 200, "DistL2")
     hb.set_build_options(nthreads=0, gpu_device=0, gpu_window=0)
     hb.parallel_insert(X)
@@ -83,6 +97,7 @@ def test_config4_100k_queries_in_8_shards_on_1m_x_128(native, oracle, sift1m):
     got = oracle.SearchResult(cat(ids, np.uint64), cat(dists), cat(layers), cat(ranks), cat(counts, np.uint32))
     ref = o.parallel_search(Q, k, ef)
     assert_same(got, ref)
+    _assert_f64_per_answer(Q, got)
     print(f"config 4: 100 000 queries in 8 shards over {ndev} device(s) {sorted(set(devs))}: all answers == oracle")
     # the gather without a collective library (a Rust host driving the node's GPUs from one process): peer copies into device 0
     root = torch.device("cuda", 0)
@@ -130,6 +145,7 @@ def test_config2_counters_per_query_at_full_size(native, oracle, sift1m):
     Q = _clustered(10_000, d, 0x5EED0002)
     res, ref = check(native, h, o, Q, k, ef, "config 2")   # (strict, then lean)
     assert (res.st[:, 3] == 3).any()                        # the duplicates send some queries through the replay
+    _assert_f64_per_answer(Q, res)
 
     # bytes = n_dist*d*4 + n_ids_read*4 + n_expand*8 + d*4 + k*12 per query (d unpadded)
     def survey_bytes(n_dist, n_ids, n_expand, nq):
