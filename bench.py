@@ -6,18 +6,24 @@ is launched by torch.distributed.run with one rank per GPU.  A *step* is one pas
 over one batch of synthetic queries: greedy layer descent + layer-0 ef-expansion for every query
 of the batch, inputs already resident in HBM.  Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline figure needs: setup, spin-up, W warm-up steps, K timed steps, --dump-outputs,
+the line (`value`, `ms_per_step`, the timed launches' kernel times).  Everything else is measured with --full, after the
+timed steps: recall against exact brute force, strict ties off, SIMD-order arithmetic, two callers, the roofline's
+algorithmic bytes and live PMC traffic, the boundary entry points, the CPU baseline with parity against the oracle, and
+for N > 1 the exchange alone (gather_ms) and the same batch on one GPU.
+
 Workload at N=1 (BASELINE.json configs[1]): SIFT1M-shape synthetic, 1M x 128 f32, DistL2, M=16,
 ef_construction=200, ef=64, k=10, 10 000 queries.  For N>1 the workload is BASELINE.json configs[3]
 as it is stated: ONE batch of 100 000 queries (what `parallel_search` answers in one call,
 src/hnsw.rs:1612-1635) split into N contiguous blocks of 100 000 / N, the graph replicated on every
 GPU, the answers all-gathered over RCCL: the total work is fixed => "strong" scaling, and every N>1
-line carries `one_gpu_same_batch_queries_per_s` -- the same 100 000 queries in one call on rank 0's
-GPU, same invocation -- so that the 1 -> N ratio is read off one line.  `--weak` keeps the fixed
+line of a --full run carries `one_gpu_same_batch_queries_per_s` -- the same 100 000 queries in one call on
+rank 0's GPU, same invocation -- so that the 1 -> N ratio is read off one line.  `--weak` keeps the fixed
 12 500 queries per GPU of the earlier rounds (per-GPU work fixed => "weak").
 
 What is untimed setup: synthetic data, graph construction on the host cores (product builder,
-cached as an hnswio dump under --cache-dir), dump reload, HBM upload, exact ground truth (torch
-GEMM on the GPU: harness, not hot path).  The CPU oracle is used ONLY in the cpu_baseline leg.
+cached as an hnswio dump under --cache-dir), dump reload, HBM upload, exact ground truth (--full; torch
+GEMM on the GPU: harness, not hot path).  The CPU oracle is used ONLY in the cpu_baseline leg (--full).
 
 Same arguments, same inputs: the data are seeded and the graph is built with one host thread (--build-threads 1), so
 `--dump-outputs DIR` (the answers of the last timed step) can be compared output for output between two builds.
@@ -619,6 +625,11 @@ def main():
                     "graph every run, so that the same arguments give the timed steps the same inputs; 0 = all cores (32 at most)")
     ap.add_argument("--host-build", action="store_true", help="build the graph on the host cores only (default: GPU-assisted "
                     "construction: the insertions' searches on the device, window by window)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check everything beyond the headline "
+                    "figure (recall, strict ties off, SIMD-order arithmetic, two callers, roofline bytes and PMC traffic, boundary entry "
+                    "points, CPU baseline and parity; N > 1: gather_ms and the same batch on one GPU).  Off: setup, warm-up, timed "
+                    "steps, --dump-outputs and the line only")
+    # the --no-* options leave one leg out of a --full run (a plain run has none of them)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-concurrent", action="store_true", help="skip the two-caller-threads reference measurement")
     ap.add_argument("--no-recall", action="store_true", help="skip the brute-force ground truth (quick A/B runs)")
@@ -644,6 +655,9 @@ def main():
     args = ap.parse_args(json.loads(os.environ["HNSW_BENCH_ARGV"]) if "HNSW_BENCH_ARGV" in os.environ and len(sys.argv) == 1 else None)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    full = args.full
+    if not full:  # a plain run: the headline figure only (the legs below the timed steps are --full ones)
+        args.no_cpu_baseline = args.no_recall = args.no_concurrent = args.no_boundary = args.no_traffic = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))  # the plain command: this process launches one rank per GPU and waits for them
@@ -865,7 +879,7 @@ def main():
     timed_main_ms = list(main_ms)
     timed_kernel_ms = list(kernel_ms)
     gather_ms = None
-    if pg:  # untimed: a few steps with the exchange NOT overlapped and waited for, to say what one costs by itself
+    if pg and full:  # untimed: a few steps with the exchange NOT overlapped and waited for, to say what one costs by itself
         gather_marks.clear()
         for i in range(4):
             step(i, overlap=False)
@@ -877,7 +891,7 @@ def main():
     # N > 1 (one batch shared by the GPUs): the same batch -- all nq_total queries -- in ONE call on rank 0's GPU, untimed by the
     # contract's clock: what a single GPU makes of BASELINE.json configs[3], on this box, this graph, this invocation
     one_gpu_qps = None
-    if world > 1 and plan["scaling"] == "strong":
+    if full and world > 1 and plan["scaling"] == "strong":
         fence()
         if rank == 0:
             Qw = torch.from_numpy(np.ascontiguousarray(Q_all[:nq_total])).to(dev)
@@ -906,14 +920,14 @@ def main():
 
     # untimed accounting: one more step per batch for its work counters (the algorithmic bytes of that batch)
     batch_stats = []
-    for b in range(NB):
+    for b in range(NB if full else 0):
         step(b)
         fence()
         batch_stats.append(stats.cpu().numpy().astype(np.int64))
 
     # for reference: the same steps with strict ties OFF (equal distances ordered by arrival, queries flagged)
     fast_qps = None
-    if lib.hnswgpu_set_strict_ties(index.handle, 0) == 0:
+    if full and lib.hnswgpu_set_strict_ties(index.handle, 0) == 0:
         step(0)
         fast_qps = nq_total * args.steps / timed(args.steps)
         lib.hnswgpu_set_strict_ties(index.handle, 1)
@@ -921,7 +935,7 @@ def main():
     # arithmetic of every number the reference publishes, and the fair twin of the CPU baseline's "simd-order" figure
     # (hnswgpu_set_arithmetic; opt-in, never `value`; its checker is the oracle's dist_simd8: tests/test_gpu_round4.py)
     simd_qps = None
-    if lib.hnswgpu_set_arithmetic(index.handle, 1) == 0:
+    if full and lib.hnswgpu_set_arithmetic(index.handle, 1) == 0:
         try:
             step(0)
             simd_qps = nq_total * args.steps / timed(args.steps)
@@ -1021,7 +1035,8 @@ def main():
                                     "%d_queries_per_call" % len(Q): filtered_measure(torch, H, lib, index, None, n, d, k, ef, Q, 0, [1, 30])}
         except Exception as e:  # noqa: BLE001
             log(f"boundary timings skipped: {e}")
-    step(0)   # leave the strict answers of batch 0 in the output buffers for the recall / parity checks below
+    if full or args.dump_answers or args.dump_stats:
+        step(0)   # leave the strict answers of batch 0 in the output buffers for the recall / parity checks below
     fence()
     if args.dump_answers and rank == 0:  # batch 0 in input order: what the caller of parallel_search gets back
         if pg:  # (what came back through the collective, not this rank's send buffer)
@@ -1074,60 +1089,67 @@ def main():
         total = int(sb[:, 0].sum()) * d * 4 + int(sb[:, 2].sum()) * 4 + int(sb[:, 1].sum()) * 8 + nq_local * (d * 4 + k * 12)
         return total - (desc - nq_local * d * 4)  # (the search kernel stages the query row as well)
 
-    batch_bytes = [alg_bytes_of(sb) for sb in batch_stats]
-    descent_bytes = float(np.mean([alg_bytes_of(sb, "descent") for sb in batch_stats]))
-    n_dist, n_expand, n_ids = (int(sum(sb[:, c].sum() for sb in batch_stats)) / NB for c in (0, 1, 2))
     # the dominant kernel is hnsw_search_kernel (queries that need the literal heaps carry on inside it); achieved =
     # algorithmic bytes of the batches the timed steps searched / the kernel time of those launches (HIP events)
     k_ms = float(np.mean(timed_main_ms)) if timed_main_ms else float("nan")
     all_ms = float(np.mean(timed_kernel_ms)) if timed_kernel_ms else float("nan")
-    alg_bytes = float(np.mean([batch_bytes[i % NB] for i in range(args.steps)]))
-    achieved = sum(batch_bytes[i % NB] for i in range(args.steps)) / (sum(timed_main_ms) * 1e-3) / 1e9
     # A call whose first pass hands queries on (two queries per wavefront first, then the one-query kernels over the tie queries:
     # several search launches per step) is priced over ALL kernels of the call -- the second launch's bytes are in the count, so
     # its time (and, conservatively, the descent's and the host's turn-around between the launches) is too.
     several_launches = index.last_kernel_ms()[1] > 1
-    if several_launches:
-        achieved = sum(batch_bytes[i % NB] for i in range(args.steps)) / (sum(timed_kernel_ms) * 1e-3) / 1e9
-    traffic_profile = None
-    tf = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tf):
-        try:
-            tj = json.load(open(tf))
-            ent = tj.get(args.config)
-            if ent and ent.get("data") == args.data:
-                traffic_profile = ent
-        except Exception:
-            pass
+    kernel = ("hnsw_search_kernel" if not several_launches else
+              "all search launches of a call (hnsw_search_pair_kernel first, hnsw_search_kernel over what it handed on): achieved = algorithmic bytes / all_kernels_ms")
+    # the batches differ (their longest search sets a launch's length): spread of the timed launches per batch
+    by_batch = {str(b): [round(float(f(v)), 4) for f in (np.min, np.median, np.max)]
+                for b in range(NB) for v in [[m for i, m in enumerate(timed_main_ms) if i % NB == b]] if v}
     index_bytes = n * (((d + 31) // 32) * 128 + 4 * ((2 * cfg["M"] + 15) // 16) * 16 + 8)
-    all_st = np.concatenate(batch_stats)
-    roofline = {"bound": "hbm", "kernel": "hnsw_search_kernel" if not several_launches else
-                "all search launches of a call (hnsw_search_pair_kernel first, hnsw_search_kernel over what it handed on): achieved = algorithmic bytes / all_kernels_ms",
-                "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                # PMC counters cannot be collected inside this process: `traffic` is filled in below from two rocprofv3 --pmc
-                # child runs (live_traffic; N = 1), and the committed profile of an earlier box is quoted beside it
-                "traffic": None, "traffic_from_profile": traffic_profile,
-                "algorithmic_bytes_per_launch": int(alg_bytes), "kernel_ms": round(k_ms, 4),
-                "all_kernels_ms": round(all_ms, 4),
-                # in front of the search kernel on the same stream: hnsw_descend_kernel (queries padded + the greedy descent of
-                # every query, exact arithmetic) and order_desc_kernel (longest searches first)
-                "descent_and_order_kernels": {"ms": round(all_ms - k_ms, 4), "algorithmic_bytes_per_launch": int(descent_bytes),
-                                              "note": "their bytes and their time are NOT in achieved / kernel_ms: the dominant kernel is priced on its own share"},
-                "queries_resolved_with_literal_heaps": int((st[:, 3] == 3).sum()),
-                "queries_that_met_equal_distances": int((st[:, 7] & 1).sum()),
-                "launches_per_step": index.last_kernel_ms()[1], "query_batches_rotated": NB,
-                # the batches differ (their longest search sets a launch's length): spread of the timed launches per batch
-                "kernel_ms_by_batch_min_median_max": {str(b): [round(float(f(v)), 4) for f in (np.min, np.median, np.max)]
-                                                      for b in range(NB) for v in [[m for i, m in enumerate(timed_main_ms) if i % NB == b]] if v},
-                "index_bytes_in_hbm": int(index_bytes),
-                "resident_in_infinity_cache": bool(index_bytes < 256 * 2 ** 20),
-                "note": ("the whole index fits the 256 MiB Infinity Cache: the fetches behind `achieved` are served by MALL/L2, "
-                         "the fraction is against the HBM peak only by convention" if index_bytes < 256 * 2 ** 20 else
-                         "working set (vectors + lists) exceeds the Infinity Cache; batches rotate so that steps do not re-read each other's rows"),
-                "per_query": {"n_dist": n_dist / nq_local, "n_expand": n_expand / nq_local,
-                              "n_ids_read": n_ids / nq_local, "bytes": alg_bytes / nq_local,
-                              "n_dist_p50_p99_max": [int(np.percentile(all_st[:, 0], 50)), int(np.percentile(all_st[:, 0], 99)), int(all_st[:, 0].max())]}}
+    if full:
+        batch_bytes = [alg_bytes_of(sb) for sb in batch_stats]
+        descent_bytes = float(np.mean([alg_bytes_of(sb, "descent") for sb in batch_stats]))
+        n_dist, n_expand, n_ids = (int(sum(sb[:, c].sum() for sb in batch_stats)) / NB for c in (0, 1, 2))
+        alg_bytes = float(np.mean([batch_bytes[i % NB] for i in range(args.steps)]))
+        achieved = sum(batch_bytes[i % NB] for i in range(args.steps)) / (sum(timed_kernel_ms if several_launches else timed_main_ms) * 1e-3) / 1e9
+        traffic_profile = None
+        tf = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tf):
+            try:
+                tj = json.load(open(tf))
+                ent = tj.get(args.config)
+                if ent and ent.get("data") == args.data:
+                    traffic_profile = ent
+            except Exception:
+                pass
+        all_st = np.concatenate(batch_stats)
+        roofline = {"bound": "hbm", "kernel": kernel,
+                    "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                    # PMC counters cannot be collected inside this process: `traffic` is filled in below from two rocprofv3 --pmc
+                    # child runs (live_traffic; N = 1), and the committed profile of an earlier box is quoted beside it
+                    "traffic": None, "traffic_from_profile": traffic_profile,
+                    "algorithmic_bytes_per_launch": int(alg_bytes), "kernel_ms": round(k_ms, 4),
+                    "all_kernels_ms": round(all_ms, 4),
+                    # in front of the search kernel on the same stream: hnsw_descend_kernel (queries padded + the greedy descent of
+                    # every query, exact arithmetic) and order_desc_kernel (longest searches first)
+                    "descent_and_order_kernels": {"ms": round(all_ms - k_ms, 4), "algorithmic_bytes_per_launch": int(descent_bytes),
+                                                  "note": "their bytes and their time are NOT in achieved / kernel_ms: the dominant kernel is priced on its own share"},
+                    "queries_resolved_with_literal_heaps": int((st[:, 3] == 3).sum()),
+                    "queries_that_met_equal_distances": int((st[:, 7] & 1).sum())}
+    else:
+        # a plain run: the HIP-event times of the timed launches only; the algorithmic bytes need a counted step per batch (--full)
+        roofline = {"bound": "hbm", "kernel": kernel, "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None,
+                    "kernel_ms": round(k_ms, 4), "all_kernels_ms": round(all_ms, 4)}
+    roofline.update({
+        "launches_per_step": index.last_kernel_ms()[1], "query_batches_rotated": NB,
+        "kernel_ms_by_batch_min_median_max": by_batch,
+        "index_bytes_in_hbm": int(index_bytes),
+        "resident_in_infinity_cache": bool(index_bytes < 256 * 2 ** 20),
+        "note": ("the whole index fits the 256 MiB Infinity Cache: the fetches behind `achieved` are served by MALL/L2, "
+                 "the fraction is against the HBM peak only by convention" if index_bytes < 256 * 2 ** 20 else
+                 "working set (vectors + lists) exceeds the Infinity Cache; batches rotate so that steps do not re-read each other's rows")})
+    if full:
+        roofline["per_query"] = {"n_dist": n_dist / nq_local, "n_expand": n_expand / nq_local,
+                                 "n_ids_read": n_ids / nq_local, "bytes": alg_bytes / nq_local,
+                                 "n_dist_p50_p99_max": [int(np.percentile(all_st[:, 0], 50)), int(np.percentile(all_st[:, 0], 99)), int(all_st[:, 0].max())]}
 
     # ---------------------------------------------------------------- CPU baseline (oracle = checker)
     cpu_baseline = None
@@ -1145,7 +1167,7 @@ def main():
     if rank == 0:
         out = {
             "metric": "queries/sec (+ recall@10), batched HNSW search",
-            "value": round(qps, 1), "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "value": round(qps, 1), "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": full,
             "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": plan["scaling"], "vs_baseline": None,
             "dtype": "f32", "data": f"synthetic ({args.data}, seeds 0x5EED0001/0x5EED0002), graph built by the product builder ({'host cores' if args.host_build else 'GPU-assisted construction'})",
             "config": {"workload": cfg["label"], "n": n, "d": d, "distance": cfg["dist"], "M": cfg["M"],

@@ -32,7 +32,7 @@ def test_one_rank_rccl_group_runs_the_overlapped_exchange(tmp_path):
     r1, j1 = _bench(["--dump-answers", a1] + common)
     assert r1.returncode == 0 and j1 is not None, r1.stdout[-2000:] + r1.stderr[-4000:]
     assert j1["rccl"] is None and j1["config"]["exchange"] == "none"
-    r2, j2 = _bench(["--exchange", "--backend", "nccl", "--dump-answers", a2] + common)
+    r2, j2 = _bench(["--full", "--exchange", "--backend", "nccl", "--dump-answers", a2] + common)  # (--full: gather_ms)
     assert r2.returncode == 0 and j2 is not None, r2.stdout[-2000:] + r2.stderr[-4000:]
     assert j2["n_gpus"] == 1
     assert j2["rccl"]["backend"] == "nccl" and j2["rccl"]["requested"] == "nccl" and j2["rccl"]["ranks_seen"] == 1

@@ -35,7 +35,7 @@ case "$EXP" in
     run() {
       local tag=$1; shift
       echo "== $CFG $tag"
-      env HNSWGPU_TRACE_LAUNCH=1 "$@" timeout 400 python bench.py --config $CFG --steps 12 --warmup 3 --no-recall --no-boundary --no-cpu-baseline --no-traffic \
+      env HNSWGPU_TRACE_LAUNCH=1 "$@" timeout 400 python bench.py --full --config $CFG --steps 12 --warmup 3 --no-recall --no-boundary --no-cpu-baseline --no-traffic \
           --dump-stats gpurun_out/$TAG/st_$tag.npy 2> gpurun_out/$TAG/err_$tag.log | tee gpurun_out/$TAG/bench_$tag.json | line | cut -c1-220
       grep "hnswgpu launch" gpurun_out/$TAG/err_$tag.log | sort | uniq -c | sort -rn | head -2
     }
@@ -73,15 +73,15 @@ PY
     timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -3
     stamp "bench lines (CPU baseline, recall, parity at full size, boundary timings)"
     for cfg in sift1m glove25 glove25_dot mnist784 mnist784_hbm random10k; do
-      timeout 900 python bench.py --config $cfg --steps 20 --warmup 5 > $O/bench_$cfg.json 2> $O/bench_$cfg.log
+      timeout 900 python bench.py --full --config $cfg --steps 20 --warmup 5 > $O/bench_$cfg.json 2> $O/bench_$cfg.log
       echo "-- $cfg"; line < $O/bench_$cfg.json
       grep -E "built in" $O/bench_$cfg.log
     done
     stamp "config 4's batch on one GPU (100 000 queries per call)"
-    timeout 600 python bench.py --config sift1m --nq 100000 --steps 5 --warmup 2 --no-boundary --no-traffic > $O/bench_sift1m_nq100k.json 2> $O/bench_sift1m_nq100k.log
+    timeout 600 python bench.py --full --config sift1m --nq 100000 --steps 5 --warmup 2 --no-boundary --no-traffic > $O/bench_sift1m_nq100k.json 2> $O/bench_sift1m_nq100k.log
     line < $O/bench_sift1m_nq100k.json
     stamp "N = 2 as a plain command (both ranks on the one device)"
-    timeout 600 python bench.py --gpus 2 --share-device --backend nccl --steps 5 --warmup 2 --no-cpu-baseline --no-recall \
+    timeout 600 python bench.py --full --gpus 2 --share-device --backend nccl --steps 5 --warmup 2 --no-cpu-baseline --no-recall \
         2> $O/bench_sift1m_n2_shared_device.log | grep '^{' > $O/bench_sift1m_n2_shared_device.json
     python -c "
 import json

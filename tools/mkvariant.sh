@@ -3,7 +3,7 @@
 # (some experiments change structs shared by host and device code), objects kept out of the source tree.
 #   tools/mkvariant.sh NAME "-DHNSW_LB_WAVES=4 ..."   ->  hnswlib-rs_amd/lib_NAME.so
 # Run it on the GPU box side by side with the default build in ONE gpurun call (the graph differs per box):
-#   HNSW_MI355X_LIB=$PWD/hnswlib-rs_amd/lib_NAME.so python bench.py --no-cpu-baseline --no-recall | python tools/bench_line.py
+#   HNSW_MI355X_LIB=$PWD/hnswlib-rs_amd/lib_NAME.so python bench.py --full --no-cpu-baseline --no-recall | python tools/bench_line.py
 # Variant libraries are git-ignored (*.so) but travel with gpurun: delete them when done.
 # ONLY_METRICS="0 1" recompiles just those metrics' kernel units (Dist ids) and takes every other object from the
 # product build in csrc/ -- for flags that only touch device code of search_kernels.inc (minutes saved).

@@ -7,7 +7,7 @@ for spec in "$@"; do
   name=${spec%%:*}; rest=${spec#*:}; nq=${rest%%:*}; envs=${rest#*:}
   [ "$envs" = "$rest" ] && envs=X=1
   envs=$(echo "$envs" | tr ',' ' ' | sed "s#LIB=#HNSW_MI355X_LIB=$P/#")
-  env $envs timeout 300 python bench.py --config ${CFG:-sift1m} --nq $nq --steps 12 --warmup 3 --no-recall --no-boundary --no-cpu-baseline --no-traffic \
+  env $envs timeout 300 python bench.py --full --config ${CFG:-sift1m} --nq $nq --steps 12 --warmup 3 --no-recall --no-boundary --no-cpu-baseline --no-traffic \
       --dump-stats $O/st_$name.npy 2> $O/err_$name.log > $O/bench_$name.json
   echo "== $name nq=$nq $envs"
   python tools/bench_line.py < $O/bench_$name.json | cut -c1-150
