@@ -262,6 +262,56 @@ class Hnsw:
         data = np.ascontiguousarray(data, dtype=np.float32).reshape(1, -1)
         return self.parallel_search(data, knbn, ef)[0]
 
+    # ---- exhaustive exact k-NN (an extension: the reference gets its ground truth from files or a CPU loop) ----------
+    def exact_search_flat(self, datas, knbn, allowed_ids=None):
+        """The knbn nearest of ALL points (all layers) for every row of `datas`, by exhaustive search on the device, in the
+        arithmetic of the index's own search: the min(knbn, eligible) smallest by (distance as f32, origin id ascending),
+        in that order.  allowed_ids: None, or the SORTED id vector of a filter (ids naming no point are ignored; an
+        empty vector gives counts of 0).  knbn up to 4096.  Returns a BatchResult."""
+        datas = np.ascontiguousarray(datas, dtype=np.float32)
+        if datas.ndim != 2:
+            raise HnswError(N.ERR_ARG, "datas must be a (nq, d) matrix")
+        nq, d = datas.shape
+        ids = np.zeros((nq, knbn), np.uint64)
+        dists = np.zeros((nq, knbn), np.float32)
+        layers = np.zeros((nq, knbn), np.uint8)
+        ranks = np.zeros((nq, knbn), np.int32)
+        counts = np.zeros(nq, np.uint32)
+        if self._h is None:
+            return BatchResult(ids, dists, layers, ranks, counts)
+        allowed, n_allowed = None, 0
+        if allowed_ids is not None:
+            n_allowed = len(allowed_ids)
+            # (an empty filter still is a filter: a non-null pointer, zero ids)
+            allowed = np.ascontiguousarray(allowed_ids, dtype=np.uint64) if n_allowed else np.zeros(1, np.uint64)
+        _check(self._lib.hnswgpu_exact_search_batch(self._h, _p(datas), nq, d, knbn, _p(allowed), n_allowed, _p(ids), _p(dists),
+                                                    _p(layers), _p(ranks), _p(counts)))
+        return BatchResult(ids, dists, layers, ranks, counts)
+
+    def exact_search(self, datas, knbn, allowed_ids=None):
+        """exact_search_flat as Vec<Vec<Neighbour>> in input order."""
+        return self.exact_search_flat(datas, knbn, allowed_ids).to_neighbours()
+
+    def recall_flat(self, datas, knbn, ef, allowed_ids=None):
+        """The two recalls the reference's examples print (examples/ann-sift1m-128-euclidean.rs:172-186), for this index's
+        own search (filtered by allowed_ids if given) against the exact answer: (by distance, by id).
+        By distance: answers with d <= the exact knbn-th distance (the last exact one when fewer are eligible), compared
+        as f32; by id: answers whose id is among the exact ones; both over the number of exact answers."""
+        exact = self.exact_search_flat(datas, knbn, allowed_ids)
+        got = self.parallel_search_flat(datas, knbn, ef) if allowed_ids is None else \
+            self.parallel_search_filter_flat(datas, knbn, ef, allowed_ids)
+        total = int(exact.counts.sum())
+        if total == 0:
+            return 1.0, 1.0
+        by_dist = by_id = 0
+        for q in range(len(exact.counts)):
+            ce, cg = int(exact.counts[q]), int(got.counts[q])
+            if ce == 0:
+                continue
+            by_dist += int(np.count_nonzero(got.dists[q, :cg] <= exact.dists[q, ce - 1]))
+            by_id += len(np.intersect1d(got.ids[q, :cg], exact.ids[q, :ce]))
+        return by_dist / total, by_id / total
+
     # AnnT (src/api.rs:13-38)
     def search_neighbours(self, data, knbn, ef_s):
         return self.search(data, knbn, ef_s)

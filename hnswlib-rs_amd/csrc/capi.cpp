@@ -20,6 +20,7 @@
 #include "hnswio.hpp"
 #include "search_device.hpp"
 #include "worker_pool.hpp"
+#include "capi_index.hpp"
 
 using namespace hnswgpu;
 
@@ -42,47 +43,7 @@ struct JoinAll {
 static void note(const std::string& msg) { g_last_error = msg; }
 // No C++ exception may cross the C ABI (the host may be Rust, Julia or C): every entry point runs inside this guard.
 #define CAPI_GUARD_BEGIN try {
-#define CAPI_GUARD_END(ret)                                                             \
-    } catch (const std::bad_alloc&) {                                                   \
-        fail(HNSWGPU_ERR_ARG, "out of memory");                                         \
-        return ret;                                                                     \
-    } catch (const std::exception& e) {                                                 \
-        fail(HNSWGPU_ERR_FORMAT, std::string("internal error: ") + e.what());           \
-        return ret;                                                                     \
-    } catch (...) {                                                                     \
-        fail(HNSWGPU_ERR_FORMAT, "internal error");                                     \
-        return ret;                                                                     \
-    }
-
-struct hnswgpu_index {
-    // Searches take this lock shared (they are `&self` in the reference: concurrent calls on one handle are legal);
-    // whatever changes the graph or the set of replicas (insert, upload, dump of a stale flat view) takes it exclusive.
-    std::shared_mutex mu;
-    std::unique_ptr<FlatIndex> flat;        // dump-order view; rebuilt from `builder` when stale
-    std::unique_ptr<GraphBuilder> builder;  // construction state (created lazily for reloaded indexes)
-    bool flat_stale = false;
-    std::map<int, std::unique_ptr<DeviceIndex>> replicas;  // HBM replicas by HIP device ordinal
-    int primary = -1;                       // device of the single-GPU entry points
-    bool dev_stale = true;
-    int strict_ties = -1;  // -1: library default (env HNSWGPU_STRICT_TIES, else on)
-    int arithmetic = 0;    // HNSWGPU_ARITH_*
-    BuildParams params;
-
-    const FlatIndex* get_flat() {  // exclusive lock held (or the view is known to be fresh)
-        if (builder && (flat_stale || !flat)) {
-            flat.reset(new FlatIndex());
-            builder->finalize(*flat);
-            flat_stale = false;
-            dev_stale = true;
-        }
-        return flat.get();
-    }
-    bool fresh() const { return flat && !flat_stale; }
-    DeviceIndex* replica(int device) const {
-        auto it = replicas.find(device);
-        return it == replicas.end() || !it->second->ready() ? nullptr : it->second.get();
-    }
-};
+#define CAPI_GUARD_END(ret) HNSWGPU_CAPI_GUARD_END(ret)
 
 static int default_device() {
     const char* e = std::getenv("HNSWGPU_DEVICE");
@@ -127,6 +88,11 @@ static int primary_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mute
     }
     return fail(HNSWGPU_ERR_DEVICE, "index changed while a search was starting");
 }
+
+namespace hnswgpu {
+int capi_fail(int code, const std::string& msg) { return fail(code, msg); }
+int capi_primary_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mutex>& sl, DeviceIndex** out) { return primary_replica(idx, sl, out); }
+}  // namespace hnswgpu
 
 extern "C" {
 

@@ -1,0 +1,66 @@
+// capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h, for the translation units
+// that implement entry points of the C ABI (capi.cpp; exact_knn.hip).  Private: not installed, not part of the ABI.
+#pragma once
+#include <exception>
+#include <map>
+#include <new>
+#include <memory>
+#include <mutex>
+#include <shared_mutex>
+#include <string>
+
+#include "../../include/hnsw_mi355x.h"
+#include "builder.hpp"
+#include "flat_index.hpp"
+#include "search_device.hpp"
+
+struct hnswgpu_index {
+    // Searches take this lock shared (they are `&self` in the reference: concurrent calls on one handle are legal);
+    // whatever changes the graph or the set of replicas (insert, upload, dump of a stale flat view) takes it exclusive.
+    std::shared_mutex mu;
+    std::unique_ptr<hnswgpu::FlatIndex> flat;        // dump-order view; rebuilt from `builder` when stale
+    std::unique_ptr<hnswgpu::GraphBuilder> builder;  // construction state (created lazily for reloaded indexes)
+    bool flat_stale = false;
+    std::map<int, std::unique_ptr<hnswgpu::DeviceIndex>> replicas;  // HBM replicas by HIP device ordinal
+    int primary = -1;                       // device of the single-GPU entry points
+    bool dev_stale = true;
+    int strict_ties = -1;  // -1: library default (env HNSWGPU_STRICT_TIES, else on)
+    int arithmetic = 0;    // HNSWGPU_ARITH_*
+    hnswgpu::BuildParams params;
+
+    const hnswgpu::FlatIndex* get_flat() {  // exclusive lock held (or the view is known to be fresh)
+        if (builder && (flat_stale || !flat)) {
+            flat.reset(new hnswgpu::FlatIndex());
+            builder->finalize(*flat);
+            flat_stale = false;
+            dev_stale = true;
+        }
+        return flat.get();
+    }
+    bool fresh() const { return flat && !flat_stale; }
+    hnswgpu::DeviceIndex* replica(int device) const {
+        auto it = replicas.find(device);
+        return it == replicas.end() || !it->second->ready() ? nullptr : it->second.get();
+    }
+};
+
+namespace hnswgpu {
+// defined in capi.cpp, for the entry points that live in other translation units:
+// sets the calling thread's hnswgpu_last_error() message and returns `code`
+int capi_fail(int code, const std::string& msg);
+// the replica a search on the primary device uses, uploaded first where need be (`sl`: the handle's lock, held shared)
+int capi_primary_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mutex>& sl, DeviceIndex** out);
+}  // namespace hnswgpu
+
+// No C++ exception may cross the C ABI: every entry point is `try { ... HNSWGPU_CAPI_GUARD_END(ret)`
+#define HNSWGPU_CAPI_GUARD_END(ret)                                                                    \
+    } catch (const std::bad_alloc&) {                                                                   \
+        hnswgpu::capi_fail(HNSWGPU_ERR_ARG, "out of memory");                                           \
+        return ret;                                                                                     \
+    } catch (const std::exception& e) {                                                                 \
+        hnswgpu::capi_fail(HNSWGPU_ERR_FORMAT, std::string("internal error: ") + e.what());             \
+        return ret;                                                                                     \
+    } catch (...) {                                                                                     \
+        hnswgpu::capi_fail(HNSWGPU_ERR_FORMAT, "internal error");                                       \
+        return ret;                                                                                     \
+    }

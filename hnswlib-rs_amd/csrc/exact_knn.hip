@@ -1,0 +1,596 @@
+// exact_knn.hip -- exhaustive exact k-NN over every point of an uploaded index, filter included (gfx950 only):
+// hnswgpu_exact_search_batch / hnswgpu_exact_search_batch_device of include/hnsw_mi355x.h.  DESIGN.md "Exact k-NN".
+//
+//   exact_knn_prep_kernel   the queries of a chunk, zero padded and regrouped by tiles of TQ queries (element-chunk major),
+//                           DistCosine: + every query's squared norm in the crate's arithmetic
+//   exact_knn_slab_kernel   one wavefront per (tile of TQ queries, slab of rows): ONE ROW PER LANE, the row's float4 is read once
+//                           and used for the TQ queries of the tile, whose elements are wave-uniform (scalar loads: they are the
+//                           SGPR operand of the per-element instruction).  Every (query, row) pair is one left-to-right chain in
+//                           one lane, made of the search's own per-element terms (search_kernels.inc) -- bit for bit the f32 the
+//                           search computes.  Selection: per (query, slab) a sorted list of the min(k, n) smallest 64-bit keys
+//                           {distance bits, DataId rank} with a running threshold (the list's last key once it is full): after the
+//                           warm-up a row costs one 64-bit compare per query.
+//   exact_knn_merge_kernel  one wavefront per query: the slabs' lists merged (lane s holds the head of slab s), the answers written
+//
+// Keys are unique (the rank is a permutation), so every step is deterministic and a tie group is cut at position k by DataId.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <exception>
+#include <numeric>
+#include <vector>
+
+#include "capi_index.hpp"
+#include "hnswio.hpp"
+#include "search_kernels.hpp"
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wunused-function"
+#include "search_kernels.inc"  // the per-element terms and the last step of Distance::eval, shared with the search
+
+namespace hnswgpu {
+namespace {
+
+constexpr int TQ = 16;                          // queries per wavefront (one accumulator each per lane)
+constexpr uint64_t KEY_NONE = ~0ull;            // behind every key: the threshold of a list that is not full yet
+constexpr uint32_t MIN_SLAB_ROWS = 256;
+constexpr uint32_t MAX_SLABS = 64;              // the merge keeps one slab per lane
+constexpr uint64_t SCRATCH_BUDGET = 320ull << 20;  // bytes of scratch per call at most, whatever nq and n are
+constexpr uint64_t K_MAX = 4096;                // list_insert costs O(k / 64) steps per insertion: the largest knbn that was run at size
+
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(4))) const v4f* qtile_ptr_t;  // wave-uniform addresses: scalar loads
+
+struct ExactKnnArgs {
+    const float* qt;        // [tiles][nchunk][TQ] float4: element chunk c of the tile's TQ queries side by side, zero padded
+    const double* qnorm;    // [tiles * TQ] DistCosine: the queries' squared norms
+    const uint32_t* rank;   // [n] position of flat id f in ascending (DataId, flat id) order
+    const uint32_t* order;  // [n] its inverse
+    const uint32_t* allow;  // one bit per flat id, or nullptr: no filter
+    const double* nrm2;     // DistCosine: side array of the points' squared norms, or nullptr: in the rows
+    uint64_t* lists;        // [tiles][n_slabs][TQ][cap] ascending keys
+    uint32_t* lens;         // [tiles][n_slabs][TQ]
+    uint32_t nq;            // queries of this chunk
+    uint32_t nchunk;        // float4 chunks of a row that hold data: ceil(d / 4)
+    uint32_t cap;           // min(k, n)
+    uint32_t slab_rows;     // a multiple of 64
+    uint32_t n_slabs;       // <= MAX_SLABS
+    uint32_t k;
+    uint64_t* out_ids;      // the chunk's rows of the caller's arrays
+    float* out_dists;
+    uint8_t* out_layer;
+    int32_t* out_rank;
+    uint32_t* out_counts;
+};
+
+// f32 -> u32 whose unsigned order is the order of the values, every NaN behind everything (distances are >= 0: then this is the
+// bit pattern with the top bit set; the other cases keep the order total whatever a distance returns)
+__device__ __forceinline__ uint32_t dist_order_bits(float v) {
+    uint32_t b = __float_as_uint(v);
+    if (v != v) return 0xFFFFFFFFu;
+    if (b == 0x80000000u) b = 0u;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+// A key: order bits above, the DataId rank below.  Every NaN has the same order bits and comes back as the canonical quiet NaN.
+__device__ __forceinline__ uint64_t make_key(float v, uint32_t rank) { return ((uint64_t)dist_order_bits(v) << 32) | rank; }
+__device__ __forceinline__ float dist_of_key(uint64_t key) {
+    const uint32_t u = (uint32_t)(key >> 32);
+    if (u == 0xFFFFFFFFu) return __uint_as_float(0x7FC00000u);
+    return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
+}
+__device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int lane) {
+    return ((uint64_t)readlane_u((uint32_t)(v >> 32), lane) << 32) | readlane_u((uint32_t)v, lane);
+}
+__device__ __forceinline__ uint64_t first_lane_u64(uint64_t v) {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) |
+           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+}
+// the lists are private to one wavefront; what one lane stored another lane loads later
+__device__ __forceinline__ void list_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
+
+// four more elements of one (query, row) chain, left to right (round_chain's terms, one lane per row instead of a lane group)
+template <int METRIC, typename ACC>
+__device__ __forceinline__ void chain4(ACC& acc, const float4 q, const float4 x) {
+    if constexpr (METRIC == DIST_JENSENSHANNON) {
+        float ta, tb;
+        jensenshannon_terms(q.x, x.x, ta, tb); acc = acc + ta; acc = acc + tb;
+        jensenshannon_terms(q.y, x.y, ta, tb); acc = acc + ta; acc = acc + tb;
+        jensenshannon_terms(q.z, x.z, ta, tb); acc = acc + ta; acc = acc + tb;
+        jensenshannon_terms(q.w, x.w, ta, tb); acc = acc + ta; acc = acc + tb;
+    } else if constexpr (METRIC == DIST_HELLINGER) {
+        acc = acc + hellinger_term(q.x, x.x); acc = acc + hellinger_term(q.y, x.y);
+        acc = acc + hellinger_term(q.z, x.z); acc = acc + hellinger_term(q.w, x.w);
+    } else if constexpr (METRIC == DIST_JEFFREYS) {
+        acc = acc + jeffreys_term(q.x, x.x); acc = acc + jeffreys_term(q.y, x.y);
+        acc = acc + jeffreys_term(q.z, x.z); acc = acc + jeffreys_term(q.w, x.w);
+    } else {
+        const v2f lo = term2<METRIC>(v2f{q.x, q.y}, v2f{x.x, x.y});
+        const v2f hi = term2<METRIC>(v2f{q.z, q.w}, v2f{x.z, x.w});
+        acc = acc + (ACC)lo.x; acc = acc + (ACC)lo.y; acc = acc + (ACC)hi.x; acc = acc + (ACC)hi.y;
+    }
+}
+
+struct ListState {
+    uint32_t len;
+    uint64_t thr;  // KEY_NONE until the list is full, then its last key
+};
+// the keys of the lanes in `mask` go into the sorted list (all lanes take part; everything but `key` is wave-uniform)
+__device__ __attribute__((noinline)) ListState list_insert(uint64_t* list, uint32_t cap, ListState s, uint64_t key, uint64_t mask) {
+    const uint32_t lane = threadIdx.x;
+    // (arguments arrive in vector registers: say that they are wave-uniform, the loops below are scalar control flow then)
+    mask = first_lane_u64(mask);
+    cap = (uint32_t)__builtin_amdgcn_readfirstlane((int)cap);
+    s.len = (uint32_t)__builtin_amdgcn_readfirstlane((int)s.len);
+    s.thr = first_lane_u64(s.thr);
+    while (mask != 0ull) {
+        const int b = ctz64(mask);
+        mask &= mask - 1ull;
+        const uint64_t kb = readlane_u64(key, b);
+        if (!(kb < s.thr)) continue;  // an earlier key of this mask moved the threshold
+        // the entries above kb move up one slot, chunk by chunk from the tail (a chunk is loaded whole before it is stored); the
+        // one that falls off a full list is dropped.  Sorted: the entries below kb are a prefix, the walk ends in their chunk.
+        uint32_t pos = 0;
+        for (uint32_t c = (s.len + 63u) >> 6; c-- > 0u;) {
+            const uint32_t i = (c << 6) + lane;
+            const bool have = i < s.len;
+            const uint64_t v = have ? list[i] : KEY_NONE;
+            const bool below = have && v < kb;
+            const unsigned long long bm = __ballot(below);
+            if (have && !below && i + 1u < cap) list[i + 1u] = v;
+            if (bm != 0ull) { pos = (c << 6) + popc64(bm); break; }
+        }
+        if (lane == 0u) list[pos] = kb;
+        if (s.len < cap) ++s.len;
+        list_fence();
+        if (s.len == cap) s.thr = first_lane_u64(list[cap - 1u]);
+    }
+    return s;
+}
+
+template <int METRIC>
+// (the two distances that go through ln_f32 get twice the registers: their inner loop spilled at four waves per SIMD)
+__global__ __launch_bounds__(64, METRIC == DIST_JEFFREYS || METRIC == DIST_JENSENSHANNON ? 2 : 4) void exact_knn_slab_kernel(DeviceIndexView ix, ExactKnnArgs a) {
+    typedef typename std::conditional<METRIC == DIST_COSINE, double, float>::type ACC;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t slab = blockIdx.x, tile = blockIdx.y;
+    const uint32_t lo = slab * a.slab_rows;
+    const uint32_t hi = ix.n - lo < a.slab_rows ? ix.n : lo + a.slab_rows;
+    const uint32_t nvalid = a.nq - tile * (uint32_t)TQ < (uint32_t)TQ ? a.nq - tile * (uint32_t)TQ : (uint32_t)TQ;
+    const uint32_t nchunk = a.nchunk, cap = a.cap;
+    const size_t slot = ((size_t)tile * a.n_slabs + slab) * (size_t)TQ;
+    uint64_t* const lists = a.lists + slot * cap;
+    const qtile_ptr_t qc = (qtile_ptr_t)(reinterpret_cast<const v4f*>(a.qt) + (size_t)tile * nchunk * (size_t)TQ);
+    // DistCosine rows that carry their norm in their last 8 bytes: when the last data chunk is the row's last chunk, its .z/.w
+    // are those bytes, not the zero padding the sum expects (norm_fits_row: they lie behind element d - 1)
+    const bool norm_in_tail = METRIC == DIST_COSINE && a.nrm2 == nullptr && nchunk * 4u == ix.row_stride;
+    ListState st[TQ];
+#pragma unroll
+    for (int t = 0; t < TQ; ++t) st[t] = ListState{0u, KEY_NONE};
+
+    for (uint32_t r0 = lo; r0 < hi; r0 += 64u) {
+        const bool in = r0 + lane < hi;
+        const uint32_t r = in ? r0 + lane : hi - 1u;  // lanes past the slab re-read its last row
+        bool ok = in;
+        if (a.allow != nullptr) ok = in && ((a.allow[r >> 5] >> (r & 31u)) & 1u) != 0u;
+        if (__ballot(ok) == 0ull) continue;  // (wave-uniform) nothing eligible among these 64 rows
+        const float* rowf = ix.vec + (size_t)r * ix.row_stride;
+        const float4* row = reinterpret_cast<const float4*>(rowf);
+        double s2 = 0.;
+        if constexpr (METRIC == DIST_COSINE)
+            s2 = a.nrm2 != nullptr ? a.nrm2[r] : *reinterpret_cast<const double*>(rowf + ix.row_stride - 2u);
+        ACC acc[TQ];
+#pragma unroll
+        for (int t = 0; t < TQ; ++t) acc[t] = 0;
+        float4 x = row[0];
+        for (uint32_t c = 0; c < nchunk; ++c) {
+            const float4 xn = row[c + 1u < nchunk ? c + 1u : c];  // (written as a prefetch; as compiled the load sits at the head of the loop and is waited for at once)
+            if (norm_in_tail && c + 1u == nchunk) { x.z = 0.f; x.w = 0.f; }
+#pragma unroll
+            for (int t = 0; t < TQ; ++t) {
+                const v4f q = qc[(size_t)c * TQ + t];
+                chain4<METRIC, ACC>(acc[t], make_float4(q.x, q.y, q.z, q.w), x);
+            }
+            x = xn;
+        }
+        const uint32_t rk = a.rank[r];
+#pragma unroll
+        for (int t = 0; t < TQ; ++t) {
+            if ((uint32_t)t < nvalid) {
+                float v;
+                if constexpr (METRIC == DIST_COSINE) {
+                    const double s1 = ((nrm_ptr_t)a.qnorm)[tile * (uint32_t)TQ + (uint32_t)t];
+                    v = 0.f;
+                    if (s1 > 0. && s2 > 0.) {
+                        const double du = 1. - acc[t] / __builtin_sqrt(s1 * s2);
+                        v = (float)fmax(du, 0.);
+                    }
+                } else {
+                    v = dist_finish<METRIC>(acc[t]);
+                }
+                const uint64_t key = make_key(v, rk);
+                const unsigned long long m = __ballot(ok && key < st[t].thr);
+                if (m != 0ull) st[t] = list_insert(lists + (size_t)t * cap, cap, st[t], key, m);
+            }
+        }
+    }
+    if (lane < nvalid) {
+        uint32_t len = 0;
+#pragma unroll
+        for (int t = 0; t < TQ; ++t)
+            if (lane == (uint32_t)t) len = st[t].len;
+        a.lens[slot + lane] = len;
+    }
+}
+
+// one wavefront per query: lane s walks the list of slab s; the smallest head is the next answer
+__global__ __launch_bounds__(64) void exact_knn_merge_kernel(DeviceIndexView ix, ExactKnnArgs a) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t q = blockIdx.x;
+    const uint32_t tile = q / (uint32_t)TQ, t = q % (uint32_t)TQ;
+    const uint32_t k = a.k;
+    const size_t slot = ((size_t)tile * a.n_slabs + (lane < a.n_slabs ? lane : 0u)) * (size_t)TQ + t;
+    const uint64_t* list = a.lists + slot * a.cap;
+    const uint32_t len = lane < a.n_slabs ? a.lens[slot] : 0u;
+    uint32_t total = len;
+    for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o, 64);
+    const uint32_t cnt = total < k ? total : k;
+    uint32_t h = 0;
+    uint64_t cur = len > 0u ? list[0] : KEY_NONE;
+    uint64_t mine = KEY_NONE;
+    for (uint32_t j = 0; j < cnt; ++j) {
+        uint64_t m = cur;
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint64_t other = ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(m >> 32), o, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)m, o, 64);
+            m = other < m ? other : m;
+        }
+        if (cur == m) {  // keys are unique: one lane
+            ++h;
+            cur = h < len ? list[h] : KEY_NONE;
+        }
+        if (lane == (j & 63u)) mine = m;
+        if ((j & 63u) == 63u || j + 1u == cnt) {  // 64 answers at a time, one per lane
+            const uint32_t jj = (j & ~63u) + lane;
+            if (jj <= j) {
+                const uint32_t flat = a.order[(uint32_t)mine];
+                uint32_t l = 0;
+                while (l + 1 < NB_LAYER_MAX && flat >= ix.layer_offset[l + 1]) ++l;
+                const size_t o = (size_t)q * k + jj;
+                a.out_ids[o] = ix.origin_id[flat];
+                a.out_dists[o] = dist_of_key(mine);
+                if (a.out_layer) a.out_layer[o] = (uint8_t)l;
+                if (a.out_rank) a.out_rank[o] = (int32_t)(flat - ix.layer_offset[l]);
+            }
+        }
+    }
+    for (uint32_t j = cnt + lane; j < k; j += 64u) {  // slots behind the answers: zero, as the search entries leave them
+        const size_t o = (size_t)q * k + j;
+        a.out_ids[o] = 0ull;
+        a.out_dists[o] = 0.f;
+        if (a.out_layer) a.out_layer[o] = 0;
+        if (a.out_rank) a.out_rank[o] = 0;
+    }
+    if (lane == 0u) a.out_counts[q] = cnt;
+}
+
+// one thread per query slot of the chunk's tiles: the row into its tile (slots behind the last query: zeros)
+__global__ void exact_knn_prep_kernel(const float* __restrict__ src, uint32_t nq, uint32_t d, uint32_t nchunk, uint32_t n_slots,
+                                      float* __restrict__ qt, double* __restrict__ qnorm) {
+    const uint32_t qs = blockIdx.x * blockDim.x + threadIdx.x;
+    if (qs >= n_slots) return;
+    const uint32_t tile = qs / (uint32_t)TQ, t = qs % (uint32_t)TQ;
+    double s1 = 0.;  // DistCosine: f32 squares widened to f64, summed left to right (finish_staged_query)
+    for (uint32_t c = 0; c < nchunk; ++c) {
+        float e[4];
+        for (uint32_t j = 0; j < 4u; ++j) {
+            const uint32_t i = 4u * c + j;
+            e[j] = qs < nq && i < d ? src[(size_t)qs * d + i] : 0.f;
+            s1 = s1 + (double)(e[j] * e[j]);
+        }
+        reinterpret_cast<float4*>(qt)[((size_t)tile * nchunk + c) * (size_t)TQ + t] = make_float4(e[0], e[1], e[2], e[3]);
+    }
+    qnorm[qs] = s1;
+}
+
+hipError_t launch_slab(int metric, dim3 grid, hipStream_t stream, const DeviceIndexView& ix, const ExactKnnArgs& a) {
+    switch (metric) {
+        case DIST_L2: hipLaunchKernelGGL(exact_knn_slab_kernel<DIST_L2>, grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_COSINE: hipLaunchKernelGGL(exact_knn_slab_kernel<DIST_COSINE>, grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_DOT: hipLaunchKernelGGL(exact_knn_slab_kernel<DIST_DOT>, grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_L1: hipLaunchKernelGGL(exact_knn_slab_kernel<DIST_L1>, grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_HELLINGER: hipLaunchKernelGGL(exact_knn_slab_kernel<DIST_HELLINGER>, grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_JEFFREYS: hipLaunchKernelGGL(exact_knn_slab_kernel<DIST_JEFFREYS>, grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_JENSENSHANNON: hipLaunchKernelGGL(exact_knn_slab_kernel<DIST_JENSENSHANNON>, grid, dim3(64), 0, stream, ix, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+#define HIP_TRY(expr)                                                                          \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess) {                                                                \
+            err = std::string(#expr) + ": " + hipGetErrorString(e_);                           \
+            return ERR_DEVICE;                                                                 \
+        }                                                                                      \
+    } while (0)
+
+// the caller's current HIP device is left as it was found
+class OnDevice {
+public:
+    explicit OnDevice(int device) {
+        int cur = -1;
+        if (hipGetDevice(&cur) != hipSuccess) cur = -1;
+        if (cur == device) return;
+        status_ = hipSetDevice(device);
+        if (status_ == hipSuccess && cur >= 0) prev_ = cur;
+    }
+    ~OnDevice() { if (prev_ >= 0) (void)hipSetDevice(prev_); }
+    OnDevice(const OnDevice&) = delete;
+    OnDevice& operator=(const OnDevice&) = delete;
+    hipError_t status() const { return status_; }
+private:
+    int prev_ = -1;
+    hipError_t status_ = hipSuccess;
+};
+
+// What a replica keeps for this unit (DeviceIndex::extension): the DataId ranks, and scratch blocks that calls take turns with
+struct ExactState {
+    int device = -1;
+    void* d_rank = nullptr;
+    void* d_order = nullptr;
+    std::mutex mu;
+    std::vector<std::pair<void*, uint64_t>> pool;  // free scratch blocks {address, bytes}
+    ~ExactState() {
+        OnDevice on(device);
+        if (d_rank) (void)hipFree(d_rank);
+        if (d_order) (void)hipFree(d_order);
+        for (auto& b : pool) (void)hipFree(b.first);
+    }
+};
+struct ScratchLease {
+    ExactState* st;
+    void* p = nullptr;
+    uint64_t bytes = 0;
+    explicit ScratchLease(ExactState* s) : st(s) {}
+    hipError_t take(uint64_t need) {
+        {
+            std::lock_guard<std::mutex> g(st->mu);
+            if (!st->pool.empty()) { p = st->pool.back().first; bytes = st->pool.back().second; st->pool.pop_back(); }
+        }
+        if (bytes >= need) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+        const hipError_t e = hipMalloc(&p, need);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        bytes = need;
+        return hipSuccess;
+    }
+    ~ScratchLease() {
+        if (!p) return;
+        std::lock_guard<std::mutex> g(st->mu);
+        st->pool.emplace_back(p, bytes);
+    }
+};
+
+// rank[f] = position of flat id f in ascending (origin id, flat id) order, and the inverse: once per replica, on the host
+std::shared_ptr<void> make_state(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, std::string& err) {
+    const uint32_t n = dev.view().n;
+    if (origin_id.size() != n) { err = "internal error: the host view and the replica differ"; return nullptr; }
+    std::vector<uint32_t> order(n), rank(n);
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return origin_id[x] < origin_id[y]; });
+    for (uint32_t i = 0; i < n; ++i) rank[order[i]] = i;
+    std::shared_ptr<ExactState> st(new ExactState());
+    st->device = dev.device();
+    auto put = [&](void** p, const std::vector<uint32_t>& h) {
+        hipError_t e = hipMalloc(p, (size_t)n * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemcpy(*p, h.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) err = std::string("exact search: uploading the id ranks: ") + hipGetErrorString(e);
+        return e == hipSuccess;
+    };
+    if (!put(&st->d_rank, rank) || !put(&st->d_order, order)) return nullptr;
+    return st;
+}
+
+uint64_t round_up(uint64_t x, uint64_t m) { return (x + m - 1) / m * m; }
+
+// the device path: every pointer is device memory; waits for `stream` before it returns
+int exact_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* d_queries, uint64_t nq, uint64_t d,
+                 uint64_t k, const uint64_t* d_allowed, uint64_t n_allowed, bool filtered, uint64_t* d_out_ids, float* d_out_dists,
+                 uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, hipStream_t stream, std::string& err) {
+    const DeviceIndexView& v = dev.view();
+    if (nq == 0) return OK;
+    OnDevice on(dev.device());
+    HIP_TRY(on.status());
+    std::string serr;
+    std::shared_ptr<void> ext = dev.extension([&]() { return make_state(dev, origin_id, serr); });
+    if (!ext) { err = serr.empty() ? "exact search: no device state" : serr; return ERR_DEVICE; }
+    ExactState* st = static_cast<ExactState*>(ext.get());
+
+    const uint64_t n = v.n;
+    const uint64_t cap = std::min<uint64_t>(k, n);
+    const uint64_t nchunk = (d + 3) / 4;
+    const uint64_t tiles_total = (nq + TQ - 1) / TQ;
+    // slabs: enough (tile, slab) wavefronts to fill the device, never more lists than the budget holds for one tile
+    uint64_t slabs = std::min<uint64_t>(MAX_SLABS, (8192 + tiles_total - 1) / tiles_total);
+    const uint64_t allow_bytes = round_up((n + 31) / 32 * 4, 256);
+    const uint64_t fixed_bytes = allow_bytes + round_up(TQ * (nchunk * 16 + 8), 256) + 4096;  // the bitmap and one tile's queries
+    if (fixed_bytes >= SCRATCH_BUDGET) { err = "index or dimension too large for the exact search's scratch budget"; return ERR_ARG; }
+    const uint64_t list_budget = SCRATCH_BUDGET - fixed_bytes;
+    slabs = std::min(slabs, list_budget / ((uint64_t)TQ * (cap * 8 + 4)));
+    if (slabs == 0) { err = "knbn too large for the exact search's scratch budget"; return ERR_ARG; }
+    const uint64_t slab_rows = std::max<uint64_t>(MIN_SLAB_ROWS, round_up((n + slabs - 1) / slabs, 64));
+    slabs = (n + slab_rows - 1) / slab_rows;
+    // queries per chunk: whole tiles, what the budget holds, a grid the launch accepts
+    const uint64_t per_tile = round_up(nchunk * TQ * 16, 256) + round_up(TQ * 8, 256) + round_up(slabs * TQ * cap * 8, 256) + round_up(slabs * TQ * 4, 256);
+    const uint64_t chunk_tiles = std::min<uint64_t>({tiles_total, (SCRATCH_BUDGET - allow_bytes) / per_tile, 65535});
+    if (chunk_tiles == 0) { err = "knbn too large for the exact search's scratch budget"; return ERR_ARG; }
+
+    ScratchLease lease(st);
+    HIP_TRY(lease.take(allow_bytes + chunk_tiles * per_tile));
+    unsigned char* p = static_cast<unsigned char*>(lease.p);
+    uint32_t* d_allow = reinterpret_cast<uint32_t*>(p); p += allow_bytes;
+    float* d_qt = reinterpret_cast<float*>(p); p += chunk_tiles * round_up(nchunk * TQ * 16, 256);
+    double* d_qnorm = reinterpret_cast<double*>(p); p += chunk_tiles * round_up(TQ * 8, 256);
+    uint64_t* d_lists = reinterpret_cast<uint64_t*>(p); p += chunk_tiles * round_up(slabs * TQ * cap * 8, 256);
+    uint32_t* d_lens = reinterpret_cast<uint32_t*>(p);
+
+    // whatever happens, nothing of this call is still running when the scratch block goes back to the pool
+    struct Drain {
+        hipStream_t s;
+        ~Drain() { (void)hipStreamSynchronize(s); }
+    } drain{stream};
+    if (filtered) HIP_TRY(launch_allow_bitmap(stream, v.origin_id, v.n, d_allowed, n_allowed, d_allow));
+
+    for (uint64_t t0 = 0; t0 < tiles_total; t0 += chunk_tiles) {
+        const uint64_t tiles = std::min(chunk_tiles, tiles_total - t0);
+        const uint64_t q0 = t0 * TQ, cq = std::min<uint64_t>(tiles * TQ, nq - q0);
+        ExactKnnArgs a{};
+        a.qt = d_qt;
+        a.qnorm = d_qnorm;
+        a.rank = static_cast<const uint32_t*>(st->d_rank);
+        a.order = static_cast<const uint32_t*>(st->d_order);
+        a.allow = filtered ? d_allow : nullptr;
+        a.nrm2 = dev.side_norms();
+        a.lists = d_lists;
+        a.lens = d_lens;
+        a.nq = (uint32_t)cq;
+        a.nchunk = (uint32_t)nchunk;
+        a.cap = (uint32_t)cap;
+        a.slab_rows = (uint32_t)slab_rows;
+        a.n_slabs = (uint32_t)slabs;
+        a.k = (uint32_t)k;
+        a.out_ids = d_out_ids + q0 * k;
+        a.out_dists = d_out_dists + q0 * k;
+        a.out_layer = d_out_layer ? d_out_layer + q0 * k : nullptr;
+        a.out_rank = d_out_rank ? d_out_rank + q0 * k : nullptr;
+        a.out_counts = d_out_counts + q0;
+        const uint32_t n_slots = (uint32_t)(tiles * TQ);
+        hipLaunchKernelGGL(exact_knn_prep_kernel, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, d_queries + q0 * d, (uint32_t)cq,
+                           (uint32_t)d, (uint32_t)nchunk, n_slots, d_qt, d_qnorm);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch_slab(dev.dist(), dim3((uint32_t)slabs, (uint32_t)tiles), stream, v, a));
+        hipLaunchKernelGGL(exact_knn_merge_kernel, dim3((uint32_t)cq), dim3(64), 0, stream, v, a);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    return OK;
+}
+
+// the checks both entries share; the handle's lock is held (shared)
+int check_call(hnswgpu_index* idx, const void* queries, uint64_t nq, uint64_t d, uint64_t k, const void* allowed, uint64_t n_allowed,
+               const void* out_ids, const void* out_dists, const void* out_counts) {
+    const uint64_t dim = idx->builder ? idx->builder->dimension() : (idx->flat ? idx->flat->dimension : 0);
+    if (nq != 0 && (!queries || !out_ids || !out_dists || !out_counts)) return capi_fail(HNSWGPU_ERR_ARG, "null buffer");
+    if (k == 0) return capi_fail(HNSWGPU_ERR_ARG, "knbn must be > 0");
+    if (k > K_MAX) return capi_fail(HNSWGPU_ERR_ARG, "exact search: knbn above 4096");
+    if (nq > 0xFFFFFFF0ull) return capi_fail(HNSWGPU_ERR_ARG, "too many queries in one batch");
+    if (dim != 0 && d != dim) return capi_fail(HNSWGPU_ERR_ARG, "query dimension differs from the index dimension");
+    if (n_allowed != 0 && !allowed) return capi_fail(HNSWGPU_ERR_ARG, "null filter");
+    if (idx->arithmetic != HNSWGPU_ARITH_SCALAR)
+        return capi_fail(HNSWGPU_ERR_ARG, "exact search answers in the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
+    return HNSWGPU_OK;
+}
+
+// device memory of the host-buffer entry
+struct DevMem {
+    void* p = nullptr;
+    ~DevMem() { if (p) (void)hipFree(p); }
+};
+
+}  // namespace
+}  // namespace hnswgpu
+#pragma clang diagnostic pop
+
+using namespace hnswgpu;
+
+extern "C" {
+
+int hnswgpu_exact_search_batch_device(const hnswgpu_index* cidx, const float* d_queries, uint64_t nq, uint64_t d, uint64_t k,
+                                      const uint64_t* d_allowed_ids, uint64_t n_allowed, uint64_t* d_out_ids, float* d_out_dists,
+                                      uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, void* stream) {
+    try {
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return capi_fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    int rc = check_call(idx, d_queries, nq, d, k, d_allowed_ids, n_allowed, d_out_ids, d_out_dists, d_out_counts);
+    if (rc != HNSWGPU_OK) return rc;
+    DeviceIndex* dev = idx->primary >= 0 ? idx->replica(idx->primary) : nullptr;
+    if (!dev || idx->dev_stale || idx->flat_stale || !idx->flat)
+        return capi_fail(HNSWGPU_ERR_DEVICE, "index is not resident on a device: call hnswgpu_upload first");
+    std::string err;
+    rc = exact_device(*dev, idx->flat->origin_id, d_queries, nq, d, k, d_allowed_ids, n_allowed, d_allowed_ids != nullptr, d_out_ids,
+                      d_out_dists, d_out_layer, d_out_rank, d_out_counts, static_cast<hipStream_t>(stream), err);
+    if (rc != OK) return capi_fail(rc, err);
+    return HNSWGPU_OK;
+    HNSWGPU_CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+int hnswgpu_exact_search_batch(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, uint64_t k,
+                               const uint64_t* allowed_ids, uint64_t n_allowed, uint64_t* out_ids, float* out_dists,
+                               uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts) {
+    try {
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return capi_fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    int rc = check_call(idx, queries, nq, d, k, allowed_ids, n_allowed, out_ids, out_dists, out_counts);
+    if (rc != HNSWGPU_OK) return rc;
+    for (uint64_t i = 1; i < n_allowed; ++i)  // `impl FilterT for Vec<usize>` is a binary search: the vector must be sorted
+        if (allowed_ids[i - 1] > allowed_ids[i]) return capi_fail(HNSWGPU_ERR_ARG, "the id vector of a filter must be sorted ascending");
+    const bool empty = idx->builder ? idx->builder->nb_point() == 0 : (!idx->flat || idx->flat->n == 0);
+    if (empty) {  // no point: every answer is empty
+        if (nq != 0) {
+            std::memset(out_counts, 0, nq * sizeof(uint32_t));
+            std::memset(out_ids, 0, nq * k * sizeof(uint64_t));
+            std::memset(out_dists, 0, nq * k * sizeof(float));
+            if (out_layer) std::memset(out_layer, 0, nq * k);
+            if (out_rank) std::memset(out_rank, 0, nq * k * sizeof(int32_t));
+        }
+        return HNSWGPU_OK;
+    }
+    DeviceIndex* dev = nullptr;
+    rc = capi_primary_replica(idx, sl, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    if (nq == 0) return HNSWGPU_OK;
+    std::string err;
+    auto dev_fail = [&](hipError_t e, const char* what) { return capi_fail(HNSWGPU_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); };
+    OnDevice on(dev->device());
+    if (on.status() != hipSuccess) return dev_fail(on.status(), "hipSetDevice");
+    const bool filtered = allowed_ids != nullptr;
+    DevMem m_allowed, m_q, m_out;
+    hipError_t e;
+    if (filtered && n_allowed != 0) {
+        if ((e = hipMalloc(&m_allowed.p, n_allowed * sizeof(uint64_t))) != hipSuccess) { m_allowed.p = nullptr; return dev_fail(e, "hipMalloc"); }
+        if ((e = hipMemcpy(m_allowed.p, allowed_ids, n_allowed * sizeof(uint64_t), hipMemcpyHostToDevice)) != hipSuccess) return dev_fail(e, "hipMemcpy");
+    }
+    // chunks of queries: the staging of queries and answers stays within 64 MB whatever nq is
+    const uint64_t per_q = d * 4 + k * 17 + 4;
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(nq, (64ull << 20) / per_q));
+    if ((e = hipMalloc(&m_q.p, chunk * d * 4)) != hipSuccess) { m_q.p = nullptr; return dev_fail(e, "hipMalloc"); }
+    if ((e = hipMalloc(&m_out.p, chunk * (k * 17 + 4) + 64)) != hipSuccess) { m_out.p = nullptr; return dev_fail(e, "hipMalloc"); }
+    unsigned char* o = static_cast<unsigned char*>(m_out.p);
+    uint64_t* d_ids = reinterpret_cast<uint64_t*>(o);
+    float* d_dists = reinterpret_cast<float*>(o + chunk * k * 8);
+    int32_t* d_rank = reinterpret_cast<int32_t*>(o + chunk * k * 12);
+    uint32_t* d_counts = reinterpret_cast<uint32_t*>(o + chunk * k * 16);
+    uint8_t* d_layer = o + chunk * k * 16 + chunk * 4;
+    // (a filter that is empty still is a filter: a non-null pointer that is never dereferenced)
+    const uint64_t* d_allowed = filtered ? (m_allowed.p ? static_cast<const uint64_t*>(m_allowed.p) : reinterpret_cast<const uint64_t*>(m_q.p)) : nullptr;
+    for (uint64_t q0 = 0; q0 < nq; q0 += chunk) {
+        const uint64_t cq = std::min(chunk, nq - q0);
+        if ((e = hipMemcpy(m_q.p, queries + q0 * d, cq * d * 4, hipMemcpyHostToDevice)) != hipSuccess) return dev_fail(e, "hipMemcpy");
+        rc = exact_device(*dev, idx->flat->origin_id, static_cast<const float*>(m_q.p), cq, d, k, d_allowed, n_allowed, filtered, d_ids, d_dists,
+                          d_layer, d_rank, d_counts, nullptr, err);
+        if (rc != OK) return capi_fail(rc, err);
+        if ((e = hipMemcpy(out_ids + q0 * k, d_ids, cq * k * 8, hipMemcpyDeviceToHost)) != hipSuccess) return dev_fail(e, "hipMemcpy");
+        if ((e = hipMemcpy(out_dists + q0 * k, d_dists, cq * k * 4, hipMemcpyDeviceToHost)) != hipSuccess) return dev_fail(e, "hipMemcpy");
+        if (out_rank && (e = hipMemcpy(out_rank + q0 * k, d_rank, cq * k * 4, hipMemcpyDeviceToHost)) != hipSuccess) return dev_fail(e, "hipMemcpy");
+        if (out_layer && (e = hipMemcpy(out_layer + q0 * k, d_layer, cq * k, hipMemcpyDeviceToHost)) != hipSuccess) return dev_fail(e, "hipMemcpy");
+        if ((e = hipMemcpy(out_counts + q0, d_counts, cq * 4, hipMemcpyDeviceToHost)) != hipSuccess) return dev_fail(e, "hipMemcpy");
+    }
+    return HNSWGPU_OK;
+    HNSWGPU_CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+}  // extern "C"

@@ -394,6 +394,10 @@ void DeviceIndex::release() {
         free_ws_.clear();
         all_ws_.clear();
     }
+    {
+        std::lock_guard<std::mutex> g(ext_mu_);
+        ext_.reset();
+    }
     void** ptrs[] = {&d_vec_, &d_nbr0_, &d_up_ptr_, &d_up_ids_, &d_origin_, &d_nrm2_};
     for (void** p : ptrs)
         if (*p) { (void)hipFree(*p); *p = nullptr; }

@@ -161,6 +161,17 @@ public:
     void set_strict_ties(bool on) { strict_ties_.store(on); }
     bool strict_ties() const { return strict_ties_.load(); }
     CallInfo last_call() const;
+    // DistCosine: the side array of per-point squared norms (f64), or nullptr when every row carries its norm in the last
+    // 8 bytes of its own padding (norm_fits_row) -- what SearchArgs::nrm2 is given
+    const double* side_norms() const { return static_cast<const double*>(d_nrm2_); }
+    // Per-replica state of another translation unit (exact_knn.hip: the DataId ranks of the points and its scratch pool),
+    // made at first use by make() (null: failed, asked again next time) and dropped with the replica.
+    template <class MAKE>
+    std::shared_ptr<void> extension(MAKE&& make) const {
+        std::lock_guard<std::mutex> g(ext_mu_);
+        if (!ext_) ext_ = make();
+        return ext_;
+    }
 
 private:
     struct Workspace;
@@ -200,6 +211,8 @@ private:
     int kernel_metric() const;            // dist_, or its SIMD-order kernel variant
     std::atomic<int> descend_per_cu_[2] = {{0}, {0}};  // resident workgroups per CU of the descent kernel (asked once; [1]: two queries per wavefront)
     uint32_t up_deg_max_ = 0;  // longest list above the search layer
+    mutable std::mutex ext_mu_;
+    mutable std::shared_ptr<void> ext_;  // see extension()
 };
 
 int device_count();

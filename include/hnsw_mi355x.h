@@ -317,7 +317,35 @@ int hnswgpu_eval_distance_matrix(int dist, const float* queries, uint64_t nq, co
 int hnswgpu_eval_distance_matrix_arith(int dist, int arithmetic, const float* queries, uint64_t nq, const float* rows,
                                        uint64_t n, uint64_t d, uint32_t batch, float* out);
 
-/* Test entry: the lane lab.  The wave-level algorithms the search kernels are made of -- the reference's BinaryHeap (src/hnsw.rs:940,
+/* ---------------------------------------------------------------- exact k-NN ---------- */
+/* Exhaustive exact k-NN over EVERY point of the index (all layers), on the device: the ground truth a recall measurement
+ * needs (the reference's protocol: examples/ann-sift1m-128-euclidean.rs:172-186, tests/serpar.rs:305-317), and "brute force on
+ * the allowed subset" for a filtered search (tests/filtertest.rs).  The reference has no such function; the contract is:
+ *   distance  the f32 Distance<f32>::eval the index's search computes for that pair (HNSWGPU_ARITH_SCALAR: same summation
+ *             order, no contraction, f64 sums of DistCosine, the same ln); all seven distances.  An index set to
+ *             HNSWGPU_ARITH_SIMD8 is refused with HNSWGPU_ERR_ARG -- the call never answers in the other arithmetic.
+ *   answer    per query the min(k, #eligible) points of smallest key (distance as f32 value, origin id ascending, then
+ *             dump order), written in that order; out_counts[q] = that number; slots behind it are zero.  The answer is a
+ *             function of (vectors, ids, distance, query) alone -- not of the graph, insertion or dump order.  A NaN
+ *             distance orders behind every number and is returned as the canonical quiet NaN.
+ *   filter    allowed_ids == NULL: every point is eligible.  Else the SORTED id vector of `impl FilterT for Vec<usize>`
+ *             (unsorted: HNSWGPU_ERR_ARG); ids naming no point are ignored; an empty vector gives counts of 0.
+ *   k         1 .. 4096 (larger: HNSWGPU_ERR_ARG -- the selection costs O(k / 64) steps per insertion, and 4096 is the largest k
+ *             that was run at size); k > nb_point is fine.
+ * Same outputs as hnswgpu_search_batch (out_layer / out_rank may be NULL).  Scratch memory is a fixed budget: the nq x n
+ * distance matrix is never formed, long batches are cut into chunks of queries.  Takes the handle's lock shared, like a
+ * search.  Host buffers; uploads the index on first use like hnswgpu_search_batch.                                    */
+int hnswgpu_exact_search_batch(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, uint64_t k,
+                               const uint64_t* allowed_ids, uint64_t n_allowed, uint64_t* out_ids, float* out_dists,
+                               uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts);
+/* The same on device-resident buffers (d_allowed_ids too; NULL = no filter), launched on HIP stream `stream` and waited
+ * for.  The index must be uploaded (else HNSWGPU_ERR_DEVICE).  The sortedness of d_allowed_ids is the caller's promise. */
+int hnswgpu_exact_search_batch_device(const hnswgpu_index* idx, const float* d_queries, uint64_t nq, uint64_t d, uint64_t k,
+                                      const uint64_t* d_allowed_ids, uint64_t n_allowed, uint64_t* d_out_ids,
+                                      float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank,
+                                      uint32_t* d_out_counts, void* stream);
+
+/* Test entry: the lane lab. The wave-level algorithms the search kernels are made of -- the reference's BinaryHeap (src/hnsw.rs:940,
  * :958-973, :1035-1053, :1544; std's push / pop / into_sorted_vec) as a memory heap and as a register heap, the sorted result set
  * with its accept rule (:1028-1053), the exact visited table (:955-956, :1016-1017) -- run on `device` by ONE wavefront from a
  * script: ops[n_ops][4] = {op, a, b, c}, lanes[n_lane_sets][64][2] = {f32 bits, id} (the lane vectors of the batch operations).

@@ -8,6 +8,7 @@
 #   ab TAG CFG ENV=V[,ENV=V] ... the same short bench under several environments (knobs, variant libraries), base first and last
 #   profile TAG [bench args]     rocprofv3 kernel trace + the PMC passes (tools/profile_round.sh) + summary
 #   record ROUND                 the round's record: suite, bench lines of every config, N=2 plain command, profiles
+#   exact_rate OUTDIR [args]     tools/exact_knn_rate.py: rate of the exhaustive exact k-NN entry + its two comparators -> OUTDIR/rate.json
 #   sh 'command'                 anything else, verbatim
 set -u
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
@@ -96,11 +97,18 @@ print(j['value'], j['n_gpus'], j['scaling'], j['config']['queries_total'], j['on
       rm -rf $O/prof_$cfg
     done
     ;;
+  exact_rate)
+    O=$1; shift
+    mkdir -p "$O"
+    stamp "exact k-NN rate $*"
+    timeout 900 python tools/exact_knn_rate.py "$@" > "$O/rate.json" 2> "$O/rate.log"
+    cat "$O/rate.json"; tail -5 "$O/rate.log"
+    ;;
   sh)
     stamp "$*"
     bash -c "$*"
     ;;
   *)
-    echo "usage: tools/gpu_call.sh suite|bench|ab|profile|record|sh ..."; exit 2 ;;
+    echo "usage: tools/gpu_call.sh suite|bench|ab|profile|record|exact_rate|sh ..."; exit 2 ;;
 esac
 stamp done
