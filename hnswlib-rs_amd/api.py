@@ -245,6 +245,46 @@ class Hnsw:
                                                        _p(dists), _p(layers), _p(ranks), _p(counts), _p(status)))
         return BatchResult(ids, dists, layers, ranks, counts, status)
 
+    def parallel_search_filters_flat(self, datas, knbn, ef, filters, filter_of=None):
+        """Hnsw::search_filter(datas[q], knbn, ef, Some(&filters[filter_of[q]])) for every row q: a set of filters for the batch,
+        each query naming its own.  filters: a sequence of SORTED id arrays (an empty one allows nothing); filter_of: one index
+        into it per query, or None for one filter per query in order (len(filters) == nq).  Rows on which the reference panics
+        come back with count 0 and status 1."""
+        datas = np.ascontiguousarray(datas, dtype=np.float32)
+        if datas.ndim != 2:
+            raise HnswError(N.ERR_ARG, "datas must be a (nq, d) matrix")
+        nq, d = datas.shape
+        filters = [np.ascontiguousarray(f, dtype=np.uint64).reshape(-1) for f in filters]
+        if filter_of is None:
+            if len(filters) != nq:
+                raise HnswError(N.ERR_ARG, f"filter_of=None means one filter per query: {len(filters)} filters for {nq} queries")
+            filter_of = np.arange(nq, dtype=np.uint32)
+        else:
+            fo = np.asarray(filter_of)
+            if fo.shape != (nq,):
+                raise HnswError(N.ERR_ARG, "filter_of must hold one filter index per query")
+            if nq and (fo.min() < 0 or fo.max() > 0xFFFFFFFF):
+                raise HnswError(N.ERR_ARG, "filter_of holds an index that names no filter")
+            filter_of = np.ascontiguousarray(fo, dtype=np.uint32)
+        offsets = np.zeros(len(filters) + 1, np.uint64)
+        if filters:
+            np.cumsum([len(f) for f in filters], out=offsets[1:])
+        flat = np.concatenate(filters) if filters else np.zeros(0, np.uint64)
+        if len(flat) == 0:
+            flat = np.zeros(1, np.uint64)  # (never read: every filter is empty)
+        ids = np.zeros((nq, knbn), np.uint64)
+        dists = np.zeros((nq, knbn), np.float32)
+        layers = np.zeros((nq, knbn), np.uint8)
+        ranks = np.zeros((nq, knbn), np.int32)
+        counts = np.zeros(nq, np.uint32)
+        status = np.zeros(nq, np.uint8)
+        if self._h is None:  # empty index => empty answers (src/hnsw.rs:1498-1503)
+            return BatchResult(ids, dists, layers, ranks, counts, status)
+        _check(self._lib.hnswgpu_search_batch_filter_set(self._h, _p(datas), nq, d, knbn, ef, _p(flat), _p(offsets), len(filters),
+                                                         _p(filter_of), _p(ids), _p(dists), _p(layers), _p(ranks), _p(counts),
+                                                         _p(status)))
+        return BatchResult(ids, dists, layers, ranks, counts, status)
+
     def search_filter(self, data, knbn, ef, allowed_ids):
         """Vec<Neighbour> of Hnsw::search_filter with a sorted id vector; raises where the reference panics."""
         data = np.ascontiguousarray(data, dtype=np.float32).reshape(1, -1)

@@ -667,6 +667,103 @@ int hnswgpu_search_batch_filtered_device(const hnswgpu_index* cidx, const float*
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
+// ---- filter set: every query of the batch under a filter of its own choice (search_device.hpp: FilterSet)
+// Weak references: the host-only build of this file (tools/asan_host_suite.sh links it against stand-ins for the device) has no
+// search_device.hip behind it and answers "no device" -- after the argument checks, which are the same everywhere.
+extern "C++" {
+namespace hnswgpu {
+__attribute__((weak)) int search_filter_set_device(DeviceIndex&, const float*, uint64_t, uint64_t, uint64_t, uint64_t, const FilterSet&, uint64_t*,
+                                                   float*, uint8_t*, int32_t*, uint32_t*, uint32_t*, void*, CallInfo*, std::string&);
+__attribute__((weak)) int search_filter_set_host(DeviceIndex&, const float*, uint64_t, uint64_t, uint64_t, uint64_t, const FilterSet&, uint64_t*,
+                                                 float*, uint8_t*, int32_t*, uint32_t*, uint8_t*, CallInfo*, std::string&);
+}  // namespace hnswgpu
+}  // extern "C++"
+static const char* const kNoFilterSetDevice = "no HIP device visible (a gfx950 GPU is required; there is no CPU fallback)";
+
+int hnswgpu_search_batch_filter_set(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef,
+                                    const uint64_t* filter_ids, const uint64_t* filter_offsets, uint64_t n_filters,
+                                    const uint32_t* filter_of, uint64_t* out_ids, float* out_dists, uint8_t* out_layer,
+                                    int32_t* out_rank, uint32_t* out_counts, uint8_t* out_status) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    if (nq != 0 && (!queries || !out_ids || !out_dists || !out_counts)) return fail(HNSWGPU_ERR_ARG, "null buffer");
+    if (nq != 0 && !filter_of) return fail(HNSWGPU_ERR_ARG, "null filter_of: every query names its filter");
+    if (n_filters != 0 && !filter_offsets) return fail(HNSWGPU_ERR_ARG, "null filter_offsets");
+    if (n_filters == 0 && nq != 0) return fail(HNSWGPU_ERR_ARG, "a filter set without filters: n_filters is 0 (an unfiltered batch is hnswgpu_search_batch)");
+    if (n_filters > 0xFFFFFFFFull) return fail(HNSWGPU_ERR_ARG, "too many filters: filter_of is 32 bits wide");
+    if (n_filters != 0) {
+        if (filter_offsets[0] != 0) return fail(HNSWGPU_ERR_ARG, "filter_offsets must start at 0");
+        for (uint64_t f = 0; f < n_filters; ++f)
+            if (filter_offsets[f] > filter_offsets[f + 1])
+                return fail(HNSWGPU_ERR_ARG, "filter_offsets must ascend: filter_offsets[" + std::to_string(f + 1) + "] is below its predecessor");
+        if (filter_offsets[n_filters] != 0 && !filter_ids) return fail(HNSWGPU_ERR_ARG, "null filter_ids");
+        for (uint64_t f = 0; f < n_filters; ++f)  // `impl FilterT for Vec<usize>` is a binary search: every vector must be sorted
+            for (uint64_t i = filter_offsets[f] + 1; i < filter_offsets[f + 1]; ++i)
+                if (filter_ids[i - 1] > filter_ids[i])
+                    return fail(HNSWGPU_ERR_ARG, "the id vector of filter " + std::to_string(f) + " is not sorted ascending");
+    }
+    for (uint64_t q = 0; q < nq; ++q)
+        if (filter_of[q] >= n_filters)
+            return fail(HNSWGPU_ERR_ARG, "filter_of[" + std::to_string(q) + "] = " + std::to_string(filter_of[q]) + " names no filter (n_filters = " +
+                        std::to_string(n_filters) + ")");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    const bool empty = idx->builder ? idx->builder->nb_point() == 0 : (!idx->flat || idx->flat->n == 0);
+    if (empty) {  // empty index => every answer is empty (src/hnsw.rs:1498-1503)
+        if (out_counts) std::memset(out_counts, 0, nq * sizeof(uint32_t));
+        if (out_status) std::memset(out_status, 0, nq);
+        return HNSWGPU_OK;
+    }
+    if (nq == 0) return HNSWGPU_OK;
+    if (!hnswgpu::search_filter_set_host) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    int rc = primary_replica(idx, sl, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    CallInfo info;
+    const FilterSet set{filter_ids, filter_offsets, n_filters, filter_of};
+    rc = hnswgpu::search_filter_set_host(*dev, queries, nq, d, k, ef, set, out_ids, out_dists, out_layer, out_rank, out_counts, out_status, &info, err);
+    if (rc != OK) return fail(rc, err);
+    if (info.panics != 0 && !out_status)
+        return fail(HNSWGPU_ERR_REF_PANIC, "the reference panics on " + std::to_string(info.panics) +
+                    " of these queries (return_points.peek().unwrap() on a heap the filter emptied, src/hnsw.rs:973); "
+                    "pass out_status to learn which");
+    return HNSWGPU_OK;
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswgpu_search_batch_filter_set_device(const hnswgpu_index* cidx, const float* d_queries, uint64_t nq, uint64_t d, uint64_t k,
+                                           uint64_t ef, const uint64_t* d_filter_ids, const uint64_t* d_filter_offsets,
+                                           uint64_t n_filters, const uint32_t* d_filter_of, uint64_t* d_out_ids, float* d_out_dists,
+                                           uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, uint32_t* d_stats,
+                                           void* stream, uint32_t* n_panics) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (n_panics) *n_panics = 0;
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    if (nq != 0 && (!d_queries || !d_out_ids || !d_out_dists || !d_out_counts)) return fail(HNSWGPU_ERR_ARG, "null buffer");
+    if (nq != 0 && !d_filter_of) return fail(HNSWGPU_ERR_ARG, "null filter_of: every query names its filter");
+    if (n_filters != 0 && !d_filter_offsets) return fail(HNSWGPU_ERR_ARG, "null filter_offsets");
+    if (n_filters == 0 && nq != 0) return fail(HNSWGPU_ERR_ARG, "a filter set without filters: n_filters is 0 (an unfiltered batch is hnswgpu_search_batch_device)");
+    if (n_filters > 0xFFFFFFFFull) return fail(HNSWGPU_ERR_ARG, "too many filters: filter_of is 32 bits wide");
+    if (nq == 0) return HNSWGPU_OK;
+    if (!hnswgpu::search_filter_set_device) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    DeviceIndex* dev = idx->primary >= 0 ? idx->replica(idx->primary) : nullptr;
+    if (!dev || idx->dev_stale || idx->flat_stale)
+        return fail(HNSWGPU_ERR_DEVICE, "index is not resident on a device: call hnswgpu_upload first");
+    std::string err;
+    CallInfo info;
+    // (filters that are all empty need no id array: hand over a non-null pointer that is never dereferenced)
+    const FilterSet set{d_filter_ids ? d_filter_ids : reinterpret_cast<const uint64_t*>(d_queries), d_filter_offsets, n_filters, d_filter_of};
+    int rc = hnswgpu::search_filter_set_device(*dev, d_queries, nq, d, k, ef, set, d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts,
+                                               d_stats, stream, &info, err);
+    if (rc != OK) return fail(rc, err);
+    if (n_panics) *n_panics = info.panics;
+    return HNSWGPU_OK;
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
 static DeviceIndex* any_replica(hnswgpu_index* idx) {
     if (idx->primary >= 0 && idx->replica(idx->primary)) return idx->replica(idx->primary);
     return nullptr;

@@ -58,6 +58,10 @@ Knobs read_knobs() {
     k.pair_search = num("HNSWGPU_PAIR_SEARCH", -1);
     k.pair_tbits_delta = num("HNSWGPU_PAIR_TBITS_DELTA", 0);
     k.pair_wg_per_cu = num("HNSWGPU_PAIR_WG_PER_CU", -1);
+    if (const char* e = std::getenv("HNSWGPU_FILTER_SET_MB")) {  // MiB, fractions allowed (the tests bound a launch to two small bitmaps)
+        const double mb = std::atof(e);
+        k.filter_set_bytes = mb > 0. ? (int64_t)std::min(mb * 1048576., 64. * 1073741824.) : 0;
+    }
     return k;
 }
 std::atomic<const Knobs*> g_knobs{nullptr};
@@ -227,7 +231,7 @@ void pinned_free(void* p) {
 }
 
 struct DeviceIndex::Workspace {
-    DevBuf qpad, tie, pre, order, retry[2], stats, bitmap, heaps, cand, oplog, allow, allowed_ids;
+    DevBuf qpad, tie, pre, order, retry[2], stats, bitmap, heaps, cand, oplog, allow, allowed_ids, slot_of, set_offsets, set_of;
     PinnedBuf pin_in, pin_out;
     void* d_ctrl = nullptr;   // work counter + counters
     void* h_ctrl = nullptr;   // pinned host copy (read back once per launch)
@@ -244,7 +248,7 @@ struct DeviceIndex::Workspace {
         return OK;
     }
     ~Workspace() {
-        for (DevBuf* b : {&qpad, &tie, &pre, &order, &retry[0], &retry[1], &stats, &bitmap, &heaps, &cand, &oplog, &allow, &allowed_ids})
+        for (DevBuf* b : {&qpad, &tie, &pre, &order, &retry[0], &retry[1], &stats, &bitmap, &heaps, &cand, &oplog, &allow, &allowed_ids, &slot_of, &set_offsets, &set_of})
             b->free();
         pin_in.free();
         pin_out.free();
@@ -535,7 +539,7 @@ int DeviceIndex::upload(const FlatIndex& x, int device, std::string& err) {
 int DeviceIndex::run_exact(Workspace& w, const float* d_qpad, const uint32_t* d_qlist, uint32_t nq, uint64_t k, uint64_t ef,
                            const uint32_t* d_allow, uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer,
                            int32_t* d_out_rank, uint32_t* d_out_counts, uint32_t* stats, void* stream_v, uint32_t* panics,
-                           std::string& err, OutLayout layout) {
+                           std::string& err, OutLayout layout, const uint32_t* d_slot_of) {
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     const uint32_t tile_bytes = tile_bytes_for(kernel_metric(), v_.row_stride);
     const uint32_t bitmap_words = (v_.n + 31) / 32;
@@ -596,6 +600,8 @@ int DeviceIndex::run_exact(Workspace& w, const float* d_qpad, const uint32_t* d_
         x.heap_stride = heap_stride;
         x.cand_cap = (uint32_t)std::min<uint64_t>(cand_cap, 0xFFFFFFFFull);
         x.allow = d_allow;
+        x.slot_of = d_slot_of;  // filter set: d_allow holds one bitmap of bitmap_words words per slot
+        x.allow_stride = bitmap_words;
         HIP_TRY(hipMemsetAsync(w.d_ctrl, 0, 16, stream));
         HIP_TRY(ks.launch_exact(ns, grid, lds, stream, v_, a, x));
         volatile uint32_t* ctrl = static_cast<volatile uint32_t*>(w.h_ctrl);
@@ -610,10 +616,91 @@ int DeviceIndex::run_exact(Workspace& w, const float* d_qpad, const uint32_t* d_
     return OK;
 }
 
-int DeviceIndex::search_device(const float* d_queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef_arg,
+int DeviceIndex::search_device(const float* d_queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef,
                                uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank,
-                               uint32_t* d_out_counts, uint32_t* d_stats, void* stream_v, const uint64_t* d_allowed,
-                               uint64_t n_allowed, CallInfo* info_out, std::string& err, const RowFeed* feed, OutLayout layout) {
+                               uint32_t* d_out_counts, uint32_t* d_stats, void* stream, const uint64_t* d_allowed,
+                               uint64_t n_allowed, CallInfo* info, std::string& err, const RowFeed* feed, OutLayout layout) {
+    return search_device_impl(d_queries, nq, d, k, ef, d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts, d_stats, stream,
+                              d_allowed, n_allowed, nullptr, info, err, feed, layout);
+}
+int search_filter_set_device(DeviceIndex& ix, const float* d_queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef, const FilterSet& d_set,
+                             uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts,
+                             uint32_t* d_stats, void* stream, CallInfo* info, std::string& err) {
+    return ix.search_device_impl(d_queries, nq, d, k, ef, d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts, d_stats, stream,
+                                 nullptr, 0, &d_set, info, err, nullptr, OutLayout{});
+}
+
+// A filter-set search behind the descent: the bitmaps of the set are built group by group -- as many consecutive filters as the
+// budget (HNSWGPU_FILTER_SET_MB, 256 MiB) holds bitmaps -- and the literal kernel searches every query under the slot of its own
+// filter.  One group (the usual case: ~2 000 filters at 1M points): one launch over all queries, slot_of = filter_of.  More:
+// per group, filter_group_kernel lists the group's queries and their slots and run_exact searches that list; a query belongs to
+// exactly one group, its answer lands in its own rows.
+// The search must never see a filter_of entry >= n_filters (it would read past the bitmaps): filter_of_check_kernel counts them,
+// and the count is read back -- while the descent and the first group's bitmaps are still running -- before anything is searched.
+int DeviceIndex::filter_set_search(Workspace& w, const FilterSet& fs, uint32_t nq, uint64_t k, uint64_t ef, uint64_t* d_out_ids,
+                                   float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, uint32_t* stats,
+                                   void* stream_v, uint32_t* panics, std::string& err, OutLayout layout) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    constexpr uint64_t MAX_FILTER_SET_WAVES = 1ull << 31;  // allow_bitmap_set_kernel: four wavefronts per workgroup, 2^29 workgroups
+    const uint32_t words = (v_.n + 31) / 32;
+    const uint64_t slot_bytes = (uint64_t)words * sizeof(uint32_t);
+    const int64_t knob = knobs().filter_set_bytes;
+    const uint64_t budget = knob >= 0 ? (uint64_t)knob : 256ull << 20;
+    if (budget < slot_bytes) {
+        err = "HNSWGPU_FILTER_SET_MB is smaller than one filter's bitmap (" + std::to_string(slot_bytes) + " bytes for this index)";
+        return ERR_ARG;
+    }
+    const uint64_t per_group = std::min<uint64_t>({budget / slot_bytes, fs.n_filters, MAX_FILTER_SET_WAVES / ((v_.n + 63u) / 64u) - 1});
+    uint32_t* d_ctrl = static_cast<uint32_t*>(w.d_ctrl);  // words 0-3 are run_exact's; 8: bad filter_of entries, 9: queries of a group
+    volatile uint32_t* h_ctrl = static_cast<volatile uint32_t*>(w.h_ctrl);
+    HIP_TRY(hipMemsetAsync(d_ctrl + 8, 0, 8, stream));
+    HIP_TRY(launch_filter_of_check(stream, fs.filter_of, nq, fs.n_filters, d_ctrl + 8));
+    HIP_TRY(w.allow.ensure(per_group * slot_bytes));
+    HIP_TRY(launch_allow_bitmap_set(stream, v_.origin_id, v_.n, fs.ids, fs.offsets, 0, (uint32_t)per_group, w.allow.as<uint32_t>()));
+    HIP_TRY(hipMemcpyAsync(w.h_ctrl, w.d_ctrl, 64, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(wait_stream(stream));
+    if (h_ctrl[8] != 0) {
+        err = std::to_string(h_ctrl[8]) + " entries of filter_of name no filter of the set (>= n_filters = " + std::to_string(fs.n_filters) + ")";
+        return ERR_ARG;
+    }
+    uint32_t panics_total = 0;
+    if (per_group >= fs.n_filters) {
+        int rc = run_exact(w, w.qpad.as<float>(), nullptr, nq, k, ef, w.allow.as<uint32_t>(), d_out_ids, d_out_dists, d_out_layer, d_out_rank,
+                           d_out_counts, stats, stream, &panics_total, err, layout, fs.filter_of);
+        if (rc != OK) return rc;
+    } else {
+        HIP_TRY(w.retry[1].ensure((uint64_t)nq * sizeof(uint32_t)));
+        HIP_TRY(w.slot_of.ensure((uint64_t)nq * sizeof(uint32_t)));
+        for (uint64_t f0 = 0; f0 < fs.n_filters; f0 += per_group) {
+            const uint32_t n_slots = (uint32_t)std::min<uint64_t>(per_group, fs.n_filters - f0);
+            // (the previous group's search has been waited for: its bitmaps, its list and its slots are free)
+            if (f0 != 0)
+                HIP_TRY(launch_allow_bitmap_set(stream, v_.origin_id, v_.n, fs.ids, fs.offsets, (uint32_t)f0, n_slots, w.allow.as<uint32_t>()));
+            HIP_TRY(hipMemsetAsync(d_ctrl + 9, 0, 4, stream));
+            HIP_TRY(launch_filter_group(stream, fs.filter_of, nq, (uint32_t)f0, n_slots, w.retry[1].as<uint32_t>(), w.slot_of.as<uint32_t>(), d_ctrl + 9));
+            HIP_TRY(hipMemcpyAsync(w.h_ctrl, w.d_ctrl, 64, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(wait_stream(stream));
+            const uint32_t members = h_ctrl[9];
+            if (members == 0) continue;
+            if (knobs().trace_launch)
+                std::fprintf(stderr, "[hnswgpu launch] filter set: filters %llu..%llu, %u queries\n", (unsigned long long)f0,
+                             (unsigned long long)(f0 + n_slots - 1), members);
+            uint32_t group_panics = 0;
+            int rc = run_exact(w, w.qpad.as<float>(), w.retry[1].as<uint32_t>(), members, k, ef, w.allow.as<uint32_t>(), d_out_ids, d_out_dists,
+                               d_out_layer, d_out_rank, d_out_counts, stats, stream, &group_panics, err, layout, w.slot_of.as<uint32_t>());
+            if (rc != OK) return rc;
+            panics_total += group_panics;
+        }
+    }
+    if (panics) *panics = panics_total;
+    return OK;
+}
+
+int DeviceIndex::search_device_impl(const float* d_queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef_arg,
+                                    uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank,
+                                    uint32_t* d_out_counts, uint32_t* d_stats, void* stream_v, const uint64_t* d_allowed,
+                                    uint64_t n_allowed, const FilterSet* d_set, CallInfo* info_out, std::string& err, const RowFeed* feed,
+                                    OutLayout layout) {
     if (!ready_) { err = "index is not resident on a device: call hnswgpu_upload first"; return ERR_DEVICE; }
     if (d != v_.d) { err = "query dimension differs from the index dimension"; return ERR_ARG; }
     CallInfo info{};
@@ -628,7 +715,11 @@ int DeviceIndex::search_device(const float* d_queries, uint64_t nq, uint64_t d, 
     const uint64_t ef = std::max(ef_arg, k);  // src/hnsw.rs:1531
     if (ef > 0x7FFFFFF0ull) { err = "ef too large"; return ERR_ARG; }
     if (nq > 0xFFFFFFF0ull) { err = "too many queries in one batch"; return ERR_ARG; }
-    const bool filtered = d_allowed != nullptr || n_allowed != 0;
+    const bool filtered = d_allowed != nullptr || n_allowed != 0 || d_set != nullptr;
+    if (d_set && (d_set->n_filters == 0 || d_set->n_filters > 0xFFFFFFFFull || !d_set->offsets || !d_set->filter_of)) {
+        err = "a filter set holds 1 .. 2^32 - 1 filters, with their offsets and one filter index per query";
+        return ERR_ARG;
+    }
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     DeviceGuard on_device(device_);
     HIP_TRY(on_device.status());
@@ -688,14 +779,16 @@ int DeviceIndex::search_device(const float* d_queries, uint64_t nq, uint64_t d, 
     // ---- filtered search, and ef beyond the register-resident result set (64 x 16 entries): literal heaps in memory
     if (filtered || ef > 1024) {
         const uint32_t* d_allow = nullptr;
-        if (filtered) {
+        if (filtered && !d_set) {
             HIP_TRY(w.allow.ensure((uint64_t)((v_.n + 31) / 32) * sizeof(uint32_t)));
             HIP_TRY(launch_allow_bitmap(stream, v_.origin_id, v_.n, d_allowed, n_allowed, w.allow.as<uint32_t>()));
             d_allow = w.allow.as<uint32_t>();
         }
         HIP_TRY(hipEventRecord(w.ev_ks, stream));
-        int rc = run_exact(w, w.qpad.as<float>(), nullptr, (uint32_t)nq, k, ef, d_allow, d_out_ids, d_out_dists, d_out_layer, d_out_rank,
-                           d_out_counts, stats, stream, &info.panics, err, layout);
+        int rc = d_set ? filter_set_search(w, *d_set, (uint32_t)nq, k, ef, d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts, stats,
+                                           stream, &info.panics, err, layout)
+                       : run_exact(w, w.qpad.as<float>(), nullptr, (uint32_t)nq, k, ef, d_allow, d_out_ids, d_out_dists, d_out_layer, d_out_rank,
+                                   d_out_counts, stats, stream, &info.panics, err, layout);
         if (rc != OK) return rc;
         HIP_TRY(hipEventRecord(w.ev_stop, stream));
         HIP_TRY(wait_event(w.ev_stop));
@@ -1085,6 +1178,11 @@ struct HostCall {
 int DeviceIndex::search_host_staged(const float* queries, const float* const* rows, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef,
                                     const uint64_t* allowed, uint64_t n_allowed, bool filtered, bool want_status, const AnswerSink& sink,
                                     CallInfo* info, std::string& err) {
+    return search_host_staged_impl(queries, rows, nq, d, k, ef, allowed, n_allowed, filtered, nullptr, want_status, sink, info, err);
+}
+int DeviceIndex::search_host_staged_impl(const float* queries, const float* const* rows, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef,
+                                         const uint64_t* allowed, uint64_t n_allowed, bool filtered, const FilterSet* set, bool want_status,
+                                         const AnswerSink& sink, CallInfo* info, std::string& err) {
     if (!ready_) { err = "index is not resident on a device: call hnswgpu_upload first"; return ERR_DEVICE; }
     if (nq == 0) { if (info) *info = CallInfo{}; return OK; }
     HostCall::InFlight in_flight;  // (how long this call's helpers may spin depends on how many calls there are: HostCall::relax)
@@ -1142,6 +1240,18 @@ int DeviceIndex::search_host_staged(const float* queries, const float* const* ro
         if (n_allowed) HIP_TRY(hipMemcpyAsync(w.allowed_ids.p, allowed, n_allowed * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
         dallowed = w.allowed_ids.as<uint64_t>();
     }
+    FilterSet dset{};  // the caller's filter set (host memory, validated by the entry point) copied to the device
+    if (set) {
+        const uint64_t n_ids = set->offsets[set->n_filters];
+        HIP_TRY(w.allowed_ids.ensure(std::max<uint64_t>(1, n_ids) * sizeof(uint64_t)));
+        HIP_TRY(w.set_offsets.ensure((set->n_filters + 1) * sizeof(uint64_t)));
+        HIP_TRY(w.set_of.ensure(nq * sizeof(uint32_t)));
+        if (n_ids) HIP_TRY(hipMemcpyAsync(w.allowed_ids.p, set->ids, n_ids * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(w.set_offsets.p, set->offsets, (set->n_filters + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(w.set_of.p, set->filter_of, nq * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        dset = FilterSet{w.allowed_ids.as<uint64_t>(), w.set_offsets.as<uint64_t>(), set->n_filters, w.set_of.as<uint32_t>()};
+    }
+    const FilterSet* d_set = set ? &dset : nullptr;
     // how many threads, how the work is cut: ~64 KB per gather task, a few chunks (every chunk is a launch of the descent kernel)
     const uint64_t total_bytes = q_bytes + o_ans_end;
     // (measured, tools/host_call_sweep.py: 2 chunks beat 4 and 1 -- every chunk is a launch of the descent kernel, whose reads across
@@ -1191,14 +1301,14 @@ int DeviceIndex::search_host_staged(const float* queries, const float* const* ro
             // the caller: the device side of the call (its launches wait for the chunks), then its share of the unpacking
             const auto t_search = std::chrono::steady_clock::now();
             if (in_place)
-                rc = search_device(static_cast<const float*>(w.pin_in.dev), nq, d, k, ef, reinterpret_cast<uint64_t*>(in_sink(direct.ids)),
-                                   reinterpret_cast<float*>(in_sink(direct.dists)), nullptr, nullptr, reinterpret_cast<uint32_t*>(in_sink(direct.counts)),
-                                   nullptr, stream, dallowed, filtered ? n_allowed : 0, info, err, &feed, direct.layout);
+                rc = search_device_impl(static_cast<const float*>(w.pin_in.dev), nq, d, k, ef, reinterpret_cast<uint64_t*>(in_sink(direct.ids)),
+                                        reinterpret_cast<float*>(in_sink(direct.dists)), nullptr, nullptr, reinterpret_cast<uint32_t*>(in_sink(direct.counts)),
+                                        nullptr, stream, dallowed, filtered ? n_allowed : 0, d_set, info, err, &feed, direct.layout);
             else
-                rc = search_device(static_cast<const float*>(w.pin_in.dev), nq, d, k, ef, reinterpret_cast<uint64_t*>(dout + o_ids),
-                                   reinterpret_cast<float*>(dout + o_dists), dout + o_layer, reinterpret_cast<int32_t*>(dout + o_rank),
-                                   reinterpret_cast<uint32_t*>(dout + o_cnt), want_status ? reinterpret_cast<uint32_t*>(dout + o_stat) : nullptr,
-                                   stream, dallowed, filtered ? n_allowed : 0, info, err, &feed);
+                rc = search_device_impl(static_cast<const float*>(w.pin_in.dev), nq, d, k, ef, reinterpret_cast<uint64_t*>(dout + o_ids),
+                                        reinterpret_cast<float*>(dout + o_dists), dout + o_layer, reinterpret_cast<int32_t*>(dout + o_rank),
+                                        reinterpret_cast<uint32_t*>(dout + o_cnt), want_status ? reinterpret_cast<uint32_t*>(dout + o_stat) : nullptr,
+                                        stream, dallowed, filtered ? n_allowed : 0, d_set, info, err, &feed, OutLayout{});
             us_search = since(t_search);
             // (search_device returns with the stream idle: the answers are in the arena -- or the call failed, and whatever
             // it left in flight is waited for by `drain`; the gather is then finished by nobody, which is fine)
@@ -1235,6 +1345,19 @@ int DeviceIndex::search_host(const float* queries, uint64_t nq, uint64_t d, uint
                              float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts,
                              const uint64_t* allowed, uint64_t n_allowed, bool filtered, uint8_t* out_status,
                              CallInfo* info, std::string& err) {
+    return search_host_impl(queries, nq, d, k, ef, out_ids, out_dists, out_layer, out_rank, out_counts, allowed, n_allowed, filtered, nullptr,
+                            out_status, info, err);
+}
+int search_filter_set_host(DeviceIndex& ix, const float* queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef, const FilterSet& set,
+                           uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts,
+                           uint8_t* out_status, CallInfo* info, std::string& err) {
+    return ix.search_host_impl(queries, nq, d, k, ef, out_ids, out_dists, out_layer, out_rank, out_counts, nullptr, 0, false, &set, out_status,
+                               info, err);
+}
+int DeviceIndex::search_host_impl(const float* queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef, uint64_t* out_ids,
+                                  float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts,
+                                  const uint64_t* allowed, uint64_t n_allowed, bool filtered, const FilterSet* set, uint8_t* out_status,
+                                  CallInfo* info, std::string& err) {
     if (nq != 0 && (!queries || !out_ids || !out_dists || !out_counts)) { err = "null buffer"; return ERR_ARG; }
     struct Out {
         uint64_t k;
@@ -1251,7 +1374,7 @@ int DeviceIndex::search_host(const float* queries, uint64_t nq, uint64_t d, uint
                         if (o.status && a.status) std::memcpy(o.status + b, a.status + b, e - b);
                     },
                     &o};
-    return search_host_staged(queries, nullptr, nq, d, k, ef, allowed, n_allowed, filtered, out_status != nullptr, sink, info, err);
+    return search_host_staged_impl(queries, nullptr, nq, d, k, ef, allowed, n_allowed, filtered, set, out_status != nullptr, sink, info, err);
 }
 
 

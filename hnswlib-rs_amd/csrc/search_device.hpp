@@ -34,6 +34,7 @@ struct Knobs {
                                  // (unset: strict DistCosine / DistDot batches of >= 40 000 queries on rows of one 128-byte line)
     int pair_tbits_delta = 0;    // HNSWGPU_PAIR_TBITS_DELTA: the pair kernel's visited tables, in powers of two relative to the one-query kernels'
     int pair_wg_per_cu = -1;     // HNSWGPU_PAIR_WG_PER_CU: cap on its resident workgroups per CU
+    int64_t filter_set_bytes = -1;  // HNSWGPU_FILTER_SET_MB (MiB, may be a fraction): bound on the bitmaps one launch of a filter-set search holds (unset: 256 MiB)
 };
 const Knobs& knobs();
 void reload_knobs();
@@ -79,6 +80,29 @@ struct OutLayout {
 // use.  nullptr when the runtime refuses (no device, limits): the caller falls back to ordinary memory and an unpacking pass.
 void* pinned_alloc(size_t bytes, void** dev);
 void pinned_free(void* p);
+
+// A set of filters for one batch, in CSR form: filter f is the SORTED id vector ids[offsets[f] .. offsets[f + 1]) (offsets[0] == 0,
+// ascending, n_filters + 1 of them; an empty range allows nothing), and query q is searched under filter filter_of[q] < n_filters.
+struct FilterSet {
+    const uint64_t* ids;
+    const uint64_t* offsets;
+    uint64_t n_filters;
+    const uint32_t* filter_of;  // [nq]
+};
+class DeviceIndex;
+// Hnsw::search_filter(data_q, knbn, ef, Some(&filters[filter_of[q]])) for every query q of a batch (search_device.hip).  capi.cpp
+// refers to these two weakly: a host-only build of the C ABI (the sanitizer build, whose source list is fixed) links without
+// them and answers "no device", what every device entry answers there.
+// Every buffer in device memory: like DeviceIndex::search_device with a filter.  The arrays cannot be read on the host, so a kernel
+// counts the entries of filter_of that are >= n_filters and the call returns ERR_ARG, nothing written, before the search is launched;
+// the offsets and the sortedness of the vectors are the caller's promise.
+int search_filter_set_device(DeviceIndex& ix, const float* d_queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef, const FilterSet& d_set,
+                             uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts,
+                             uint32_t* d_stats, void* stream, CallInfo* info, std::string& err);
+// Host buffers (the set too, already validated): like DeviceIndex::search_host.
+int search_filter_set_host(DeviceIndex& ix, const float* queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef, const FilterSet& set,
+                           uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts,
+                           uint8_t* out_status, CallInfo* info, std::string& err);
 
 class DeviceIndex {
 public:
@@ -174,6 +198,10 @@ public:
     }
 
 private:
+    friend int search_filter_set_device(DeviceIndex&, const float*, uint64_t, uint64_t, uint64_t, uint64_t, const FilterSet&, uint64_t*, float*,
+                                        uint8_t*, int32_t*, uint32_t*, uint32_t*, void*, CallInfo*, std::string&);
+    friend int search_filter_set_host(DeviceIndex&, const float*, uint64_t, uint64_t, uint64_t, uint64_t, const FilterSet&, uint64_t*, float*,
+                                      uint8_t*, int32_t*, uint32_t*, uint8_t*, CallInfo*, std::string&);
     struct Workspace;
     class Lease;
     Workspace* acquire(std::string& err);
@@ -182,7 +210,22 @@ private:
     int run_exact(Workspace& w, const float* d_qpad, const uint32_t* d_qlist, uint32_t nq, uint64_t k, uint64_t ef,
                   const uint32_t* d_allow, uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer,
                   int32_t* d_out_rank, uint32_t* d_out_counts, uint32_t* stats, void* stream, uint32_t* panics,
-                  std::string& err, OutLayout layout);
+                  std::string& err, OutLayout layout, const uint32_t* d_slot_of = nullptr);
+    // what search_device / search_host_staged / search_host and their filter-set counterparts share: d_set / set == nullptr is the
+    // public call of that name
+    int search_device_impl(const float* d_queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef, uint64_t* d_out_ids,
+                           float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, uint32_t* d_stats,
+                           void* stream, const uint64_t* d_allowed, uint64_t n_allowed, const FilterSet* d_set, CallInfo* info,
+                           std::string& err, const RowFeed* feed, OutLayout layout);
+    int filter_set_search(Workspace& w, const FilterSet& d_set, uint32_t nq, uint64_t k, uint64_t ef, uint64_t* d_out_ids, float* d_out_dists,
+                          uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, uint32_t* stats, void* stream, uint32_t* panics,
+                          std::string& err, OutLayout layout);
+    int search_host_staged_impl(const float* queries, const float* const* rows, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef,
+                                const uint64_t* allowed, uint64_t n_allowed, bool filtered, const FilterSet* set, bool want_status,
+                                const AnswerSink& sink, CallInfo* info, std::string& err);
+    int search_host_impl(const float* queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef, uint64_t* out_ids, float* out_dists,
+                         uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts, const uint64_t* allowed, uint64_t n_allowed,
+                         bool filtered, const FilterSet* set, uint8_t* out_status, CallInfo* info, std::string& err);
 
     DeviceIndexView v_{};
     bool ready_ = false;

@@ -97,6 +97,9 @@ struct ExactArgs {
     uint32_t r_lds_cap;     // entries of return_points kept in LDS
     uint32_t cand_lds;      // entries of candidate_points kept in LDS
     const uint32_t* allow;  // filtered search: one bit per flat id (nullptr = Hnsw::search, no filter)
+    const uint32_t* slot_of;  // filter set: [nq_total] query q is searched under the bitmap at allow + slot_of[q] * allow_stride
+                              // (nullptr: one filter for the whole launch, the bitmap at allow)
+    uint32_t allow_stride;    // words per bitmap slot: ceil(n / 32)
 };
 
 // the snapshot's neighbour lists during construction: one fixed-stride array per layer (builder ids, EMPTY padded)
@@ -232,6 +235,14 @@ template <> const KernelSet& kernels_for<KM_DOT_SIMD8>();
 template <> const KernelSet& kernels_for<KM_L1_SIMD8>();
 // metric-independent helpers (instantiated once, in part 2 of the L2 units)
 hipError_t launch_allow_bitmap(hipStream_t stream, const uint64_t* origin_id, uint32_t n, const uint64_t* ids, uint64_t m, uint32_t* allow);
+// filter set (CSR: ids, offsets): the bitmaps of filters f0 .. f0 + n_slots - 1 into slots of ceil(n / 32) words each
+hipError_t launch_allow_bitmap_set(hipStream_t stream, const uint64_t* origin_id, uint32_t n, const uint64_t* ids, const uint64_t* offsets,
+                                   uint32_t f0, uint32_t n_slots, uint32_t* allow);
+// *bad += the entries of filter_of[0..nq) that are >= n_filters
+hipError_t launch_filter_of_check(hipStream_t stream, const uint32_t* filter_of, uint32_t nq, uint64_t n_filters, uint32_t* bad);
+// the queries whose filter is one of f0 .. f0 + n_slots - 1: appended to qlist (*count of them), slot_of[q] = filter_of[q] - f0
+hipError_t launch_filter_group(hipStream_t stream, const uint32_t* filter_of, uint32_t nq, uint32_t f0, uint32_t n_slots, uint32_t* qlist,
+                               uint32_t* slot_of, uint32_t* count);
 // DistCosine: every point's squared norm (the crate's arithmetic) into out[n] -- or, out == nullptr, into the last 8 bytes of
 // each row's padding (norm_fits_row)
 hipError_t launch_row_sq_norms(hipStream_t stream, float* vec, double* out, uint32_t n, uint32_t d, uint32_t row_stride);

@@ -2315,7 +2315,8 @@ __global__ __launch_bounds__(64, 4) void hnsw_search_exact_kernel(DeviceIndexVie
     const HeapMem R{lds_heaps, glb, r_lds};
     const HeapMem Cq{lds_heaps + r_lds, glb + (a.ef + 2u), x.cand_lds};
     const bool filtered = x.allow != nullptr;
-    auto allowed = [&](uint32_t flat) __attribute__((always_inline)) -> bool { return (x.allow[flat >> 5] >> (flat & 31u)) & 1u; };
+    const uint32_t* allow = x.allow;  // this query's bitmap: x.allow, or, with a filter set, slot slot_of[q] behind it (chosen below)
+    auto allowed = [&](uint32_t flat) __attribute__((always_inline)) -> bool { return (allow[flat >> 5] >> (flat & 31u)) & 1u; };
     // push + "pop when len > ef" of src/hnsw.rs:1038, :1051-1053 (without a push the length cannot exceed ef)
     auto r_push_capped = [&](uint32_t& len, hent_t item) __attribute__((always_inline)) {
         if constexpr (NS > 0) {
@@ -2355,6 +2356,7 @@ __global__ __launch_bounds__(64, 4) void hnsw_search_exact_kernel(DeviceIndexVie
         wi = readlane_u(wi, 0);
         if (wi >= a.nq) break;
         const uint32_t q = a.qlist ? a.qlist[wi] : wi;
+        if (x.slot_of != nullptr) allow = x.allow + (size_t)x.slot_of[q] * x.allow_stride;  // filter set: the bitmap of this query's filter
         const uint32_t t_start = (uint32_t)wall_clock64();
         stage_query<METRIC>(tile, a.queries + (size_t)q * ix.row_stride, ix.row_stride, lane, ix.d);
         for (uint32_t i = (uint32_t)lane; i < a.bitmap_words; i += 64) bitmap[i] = 0u;
@@ -2843,6 +2845,66 @@ __global__ void allow_bitmap_kernel(const uint64_t* __restrict__ origin_id, uint
     if ((threadIdx.x & 63u) == 0u && f < n) {
         allow[f >> 5] = (uint32_t)b;
         if (f + 32u < ((n + 31u) & ~31u)) allow[(f >> 5) + 1u] = (uint32_t)(b >> 32);
+    }
+}
+
+// The bitmaps of a group of filters of a filter set in one launch: slot s = filter f0 + s, the sorted id vector
+// ids[offsets[f0 + s] .. offsets[f0 + s + 1]) (CSR), its bitmap in words [s W, (s + 1) W) of `allow`, W = ceil(n / 32); bits past
+// n are zero.  One wavefront per (slot, 64 flat ids): allow_bitmap_kernel's binary search inside that filter's range.  W may be
+// odd, so a slot's last word abuts the next slot's first: the second word of a wave is written only where the slot has one.
+__global__ void allow_bitmap_set_kernel(const uint64_t* __restrict__ origin_id, uint32_t n, const uint64_t* __restrict__ ids,
+                                        const uint64_t* __restrict__ offsets, uint32_t f0, uint32_t n_slots, uint32_t* __restrict__ allow) {
+    const uint32_t waves_per_slot = (n + 63u) >> 6, words = (n + 31u) >> 5;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (wave >= (uint64_t)n_slots * waves_per_slot) return;  // (whole waves leave: the ballot below sees 64 lanes or none)
+    const uint32_t slot = (uint32_t)(wave / waves_per_slot);
+    const uint32_t f = (uint32_t)(wave % waves_per_slot) * 64u + (threadIdx.x & 63u);
+    bool ok = false;
+    if (f < n) {
+        const uint64_t key = origin_id[f];
+        const uint64_t end = offsets[(uint64_t)f0 + slot + 1u];
+        uint64_t lo = offsets[(uint64_t)f0 + slot], hi = end;
+        while (lo < hi) {
+            const uint64_t mid = lo + ((hi - lo) >> 1);
+            const uint64_t v = ids[mid];
+            if (v < key) lo = mid + 1;
+            else hi = mid;
+        }
+        ok = lo < end && ids[lo] == key;
+    }
+    const unsigned long long b = __ballot(ok);
+    if ((threadIdx.x & 63u) == 0u) {  // (f < n: the wave exists only for f < 64 waves_per_slot, and its first id is in range)
+        uint32_t* out = allow + (size_t)slot * words;
+        out[f >> 5] = (uint32_t)b;
+        if ((f >> 5) + 1u < words) out[(f >> 5) + 1u] = (uint32_t)(b >> 32);
+    }
+}
+
+// How many entries of filter_of[0..nq) name no filter of the set (>= n_filters): added to *bad.  The search kernel indexes the
+// bitmaps with these values, so the call reads the count back and refuses before it launches the search.
+__global__ void filter_of_check_kernel(const uint32_t* __restrict__ filter_of, uint32_t nq, uint64_t n_filters, uint32_t* __restrict__ bad) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long m = __ballot(q < nq && (uint64_t)filter_of[q < nq ? q : 0u] >= n_filters);
+    if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(bad, (uint32_t)__popcll(m));
+}
+
+// The queries of one group of a filter set: every q with f0 <= filter_of[q] < f0 + n_slots is appended to qlist (count in
+// *count; the order among wavefronts is the order of their atomics -- it only decides which workgroup searches which query) and
+// slot_of[q] = filter_of[q] - f0.
+__global__ void filter_group_kernel(const uint32_t* __restrict__ filter_of, uint32_t nq, uint32_t f0, uint32_t n_slots,
+                                    uint32_t* __restrict__ qlist, uint32_t* __restrict__ slot_of, uint32_t* __restrict__ count) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t f = q < nq ? filter_of[q] : 0u;
+    const bool in = q < nq && f >= f0 && f - f0 < n_slots;
+    const unsigned long long m = __ballot(in);
+    if (m == 0ull) return;
+    uint32_t base = 0;
+    if (lane == 0u) base = atomicAdd(count, (uint32_t)__popcll(m));
+    base = readlane_u(base, 0);
+    if (in) {
+        qlist[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = q;
+        slot_of[q] = f - f0;
     }
 }
 

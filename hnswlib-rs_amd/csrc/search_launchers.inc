@@ -161,6 +161,21 @@ hipError_t launch_allow_bitmap(hipStream_t stream, const uint64_t* origin_id, ui
     hipLaunchKernelGGL(allow_bitmap_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, origin_id, n, ids, m, allow);
     return hipGetLastError();
 }
+hipError_t launch_allow_bitmap_set(hipStream_t stream, const uint64_t* origin_id, uint32_t n, const uint64_t* ids, const uint64_t* offsets,
+                                   uint32_t f0, uint32_t n_slots, uint32_t* allow) {
+    const uint64_t waves = (uint64_t)n_slots * ((n + 63u) >> 6);  // (the caller keeps this below 2^31: MAX_FILTER_SET_WAVES)
+    hipLaunchKernelGGL(allow_bitmap_set_kernel, dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, stream, origin_id, n, ids, offsets, f0, n_slots, allow);
+    return hipGetLastError();
+}
+hipError_t launch_filter_of_check(hipStream_t stream, const uint32_t* filter_of, uint32_t nq, uint64_t n_filters, uint32_t* bad) {
+    hipLaunchKernelGGL(filter_of_check_kernel, dim3((nq + 255) / 256), dim3(256), 0, stream, filter_of, nq, n_filters, bad);
+    return hipGetLastError();
+}
+hipError_t launch_filter_group(hipStream_t stream, const uint32_t* filter_of, uint32_t nq, uint32_t f0, uint32_t n_slots, uint32_t* qlist,
+                               uint32_t* slot_of, uint32_t* count) {
+    hipLaunchKernelGGL(filter_group_kernel, dim3((nq + 255) / 256), dim3(256), 0, stream, filter_of, nq, f0, n_slots, qlist, slot_of, count);
+    return hipGetLastError();
+}
 hipError_t launch_scatter_lists(hipStream_t stream, const uint32_t* upd, uint32_t n_upd, uint32_t rec_words, const BuildLists& lists) {
     hipLaunchKernelGGL(scatter_lists_kernel, dim3((n_upd + 3) / 4), dim3(256), 0, stream, upd, n_upd, rec_words, lists);
     return hipGetLastError();

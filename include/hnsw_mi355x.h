@@ -187,6 +187,24 @@ int hnswgpu_search_batch_filtered(const hnswgpu_index* idx, const float* queries
                                   float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts,
                                   uint8_t* out_status);
 
+/* A SET of filters for one batch, each query naming its own: query q is answered exactly as
+ * Hnsw::search_filter(data_q, knbn, ef, Some(&filters[filter_of[q]])) -- ids, f32 distance bits, p_ids, counts, and the status of a
+ * query on which the reference panics.  The vectors are given in CSR form: filter f is filter_ids[filter_offsets[f] ..
+ * filter_offsets[f + 1]), sorted ascending like the vector of hnswgpu_search_batch_filtered; filter_offsets has n_filters + 1
+ * entries, starts at 0 and ascends; filter_of[0..nq) < n_filters.  An empty vector is a filter that allows nothing.  There is no
+ * "no filter" value: a query without a filter belongs in hnswgpu_search_batch.  HNSWGPU_ERR_ARG (the message names what is wrong):
+ * a null buffer, n_filters == 0 with nq > 0, offsets that do not start at 0 or that descend, a vector that is not sorted (the
+ * filter is named), a filter_of[q] >= n_filters.  out_status / HNSWGPU_ERR_REF_PANIC: as hnswgpu_search_batch_filtered.
+ * The device holds one bitmap of ceil(nb_point / 32) words per filter; the bitmaps of one launch are bounded by
+ * HNSWGPU_FILTER_SET_MB (MiB, default 256: ~2 000 filters at 1M points).  A larger set is served in groups of consecutive
+ * filters -- bitmaps built, the group's queries listed, that list searched -- every query exactly once, the answers in the
+ * caller's rows by q.  A bound below one bitmap is HNSWGPU_ERR_ARG.  One filter named by every query costs what
+ * hnswgpu_search_batch_filtered costs, and answers the same.                                                              */
+int hnswgpu_search_batch_filter_set(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, uint64_t k,
+                                    uint64_t ef, const uint64_t* filter_ids, const uint64_t* filter_offsets,
+                                    uint64_t n_filters, const uint32_t* filter_of, uint64_t* out_ids, float* out_dists,
+                                    uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts, uint8_t* out_status);
+
 /* Hnsw::parallel_search with the batch sharded over several GPUs of THIS process (BASELINE config 4 without Python or
  * a collective library): the graph is replicated on every device named in devices[0..n_shards) (uploaded on first use),
  * shard s = the s-th contiguous balanced block of queries (nq / n_shards each, the first nq % n_shards one more), one
@@ -246,6 +264,18 @@ int hnswgpu_search_batch_filtered_device(const hnswgpu_index* idx, const float* 
                                          uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer,
                                          int32_t* d_out_rank, uint32_t* d_out_counts, uint32_t* d_stats, void* stream,
                                          uint32_t* n_panics);
+/* hnswgpu_search_batch_filter_set with every buffer in HBM (ids, offsets and filter_of too); d_stats, stream and n_panics as in
+ * hnswgpu_search_batch_filtered_device.  The arrays cannot be read on the host: a kernel counts the entries of d_filter_of that
+ * are >= n_filters, and if there are any the call returns HNSWGPU_ERR_ARG BEFORE the search is launched -- no output is written,
+ * the handle stays usable.  That d_filter_offsets starts at 0, ascends and ends inside d_filter_ids, and that every vector is
+ * sorted, is the caller's promise (as the sortedness is in hnswgpu_search_batch_filtered_device).  The call waits on `stream` once
+ * more than the one-filter call (the count), and once per group when the set exceeds HNSWGPU_FILTER_SET_MB.                */
+int hnswgpu_search_batch_filter_set_device(const hnswgpu_index* idx, const float* d_queries, uint64_t nq, uint64_t d,
+                                           uint64_t k, uint64_t ef, const uint64_t* d_filter_ids,
+                                           const uint64_t* d_filter_offsets, uint64_t n_filters, const uint32_t* d_filter_of,
+                                           uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer,
+                                           int32_t* d_out_rank, uint32_t* d_out_counts, uint32_t* d_stats, void* stream,
+                                           uint32_t* n_panics);
 /* The same call, not waited for: hnswgpu_search_batch_device_begin returns at once with a ticket (a worker thread of
  * the library issues the launches on `stream` and waits for them), hnswgpu_search_batch_end waits for that call, returns
  * its status (its message is then hnswgpu_last_error() of the caller's thread) and releases the ticket.  Two batches in
@@ -274,7 +304,7 @@ int hnswgpu_set_strict_ties(hnswgpu_index* idx, int on);
 int hnswgpu_last_tie_count(const hnswgpu_index* idx, uint32_t* ties);
 
 /* The HNSWGPU_* tuning and test hooks (HNSWGPU_HASH_BITS, _NO_SCHED, _NO_INKERNEL, _STRICT_WG_PER_CU, _CAND_LDS, _WAVES_PER_CU,
- * _EXACT_FIRST, _TRACE_LAUNCH, _TRACE_HOST, _HOST_THREADS, _HOST_CHUNKS, _FFI_UNPACK) are read from the environment ONCE per
+ * _EXACT_FIRST, _TRACE_LAUNCH, _TRACE_HOST, _HOST_THREADS, _HOST_CHUNKS, _FFI_UNPACK, _FILTER_SET_MB) are read from the environment ONCE per
  * process, at the library's first search -- never on the launch path.  A caller that changes them afterwards (the tests do)
  * says so with this call.  Always HNSWGPU_OK.                                                                          */
 int hnswgpu_reload_env(void);
