@@ -1,7 +1,10 @@
 """Exhaustive exact k-NN on the device (Hnsw.exact_search_flat -> hnswgpu_exact_search_batch, csrc/exact_knn.hip).
 The expected answer never comes from the code under test: D = oracle_lib.dist_matrix(metric, Q, X) (the CPU oracle's
 Distance::eval), order = np.lexsort((origin_ids, D[q]))[:k]; every comparison is exact (ids, f32 bit patterns, counts, p_ids)
-unless it says otherwise.  The f64 reference (tests/f64_reference.py) checks the same answers sharing nothing with the oracle."""
+unless it says otherwise.  The f64 reference (tests/f64_reference.py) checks the same answers sharing nothing with the oracle.
+Every input here is benign (uniform, normalised, probability vectors) and every index is built.  Hostile values -- subnormals,
+magnitudes mixed over 2^-60 .. 2^60, overflowing sums, +inf tie groups, NaN distances -- and repeated origin ids live in
+tests/test_gpu_exact_knn_hostile.py, on indexes loaded from hand-written dumps (tests/dump_writer.py): the builder refuses such rows."""
 import ctypes as C
 import os
 import threading
