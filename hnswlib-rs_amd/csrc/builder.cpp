@@ -301,7 +301,10 @@ GraphBuilder::GraphBuilder(const BuildParams& p) : p_(p) {
     max_layer_ = (unsigned)std::min<uint64_t>(NB_LAYER_MAX, p.max_layer);  // src/hnsw.rs:778
     if (max_layer_ == 0) max_layer_ = 1;
     double f = std::min(1.0, std::max(0.2, p.level_scale_factor));          // src/hnsw.rs:884-904
-    scale_ = f / std::log((double)p.max_nb_connection);                      // src/hnsw.rs:327
+    // 1 / ln(M) first (src/hnsw.rs:327), then times the factor (:378): two roundings, as the reference does them -- f / ln(M)
+    // differs in the last bit for most factors (0.6 with M = 10), and the scale is dumped
+    scale_ = 1.0 / std::log((double)p.max_nb_connection);
+    scale_ *= f;
     for (auto& a : layer_inserted_) a.store(0);
     layer_rank_next_.fill(0);
 }

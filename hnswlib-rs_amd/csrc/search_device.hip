@@ -58,6 +58,8 @@ Knobs read_knobs() {
     k.pair_search = num("HNSWGPU_PAIR_SEARCH", -1);
     k.pair_tbits_delta = num("HNSWGPU_PAIR_TBITS_DELTA", 0);
     k.pair_wg_per_cu = num("HNSWGPU_PAIR_WG_PER_CU", -1);
+    k.build_wg = num("HNSWGPU_BUILD_WG", -1);
+    k.build_hash_bits = num("HNSWGPU_BUILD_HASH_BITS", -1);
     if (const char* e = std::getenv("HNSWGPU_FILTER_SET_MB")) {  // MiB, fractions allowed (the tests bound a launch to two small bitmaps)
         const double mb = std::atof(e);
         k.filter_set_bytes = mb > 0. ? (int64_t)std::min(mb * 1048576., 64. * 1073741824.) : 0;
@@ -1509,7 +1511,9 @@ public:
         if (slots_per_lane == 8) slots_per_lane = 16;
         // visited table: ef_c x degree cells (the construction search visits about that many points), 16-bit cells
         const uint32_t idbits = std::max<uint32_t>(1u, ceil_log2(n_));
-        uint32_t tbits = std::min<uint32_t>(14u, std::max<uint32_t>(8u, ceil_log2((uint64_t)ef_c_ * std::min<uint32_t>(bl_.stride[0], 64u))));
+        const Knobs& kn = knobs();
+        const uint32_t want_bits = kn.build_hash_bits > 0 ? (uint32_t)kn.build_hash_bits : ceil_log2((uint64_t)ef_c_ * std::min<uint32_t>(bl_.stride[0], 64u));
+        uint32_t tbits = std::min<uint32_t>(14u, std::max<uint32_t>(8u, want_bits));
         tbits = std::max(3u, std::min(tbits, idbits + 3u));
         while (idbits - (tbits - 3u) > 13u && tbits < 16u) ++tbits;  // (16-bit cells keep at most 13 id bits)
         if (idbits - (tbits - 3u) > 13u) { err = "GPU-assisted construction: index too large for the 16-bit visited cells"; return ERR_ARG; }
@@ -1522,7 +1526,8 @@ public:
         int per_cu = 0;
         HIP_TRY(ks.build_occupancy(slots_per_lane, lds, &per_cu));
         if (per_cu < 1) per_cu = 1;
-        const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)per_cu * (uint64_t)num_cu_, count);
+        uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)per_cu * (uint64_t)num_cu_, count);
+        if (kn.build_wg > 0) grid = std::min<uint32_t>(grid, (uint32_t)kn.build_wg);
         a.bitmap_words = (uint32_t)((n_ + 31) / 32);
         HIP_TRY(bitmap_.ensure((uint64_t)grid * a.bitmap_words * sizeof(uint32_t)));
         a.bitmap = bitmap_.as<uint32_t>();
@@ -1579,7 +1584,8 @@ public:
             sa.work_counter = static_cast<uint32_t*>(d_ctrl_);
             HIP_TRY(hipMemset(d_ctrl_, 0, 8));
             const size_t sel_lds = a.tile_bytes + IDS_BYTES + (size_t)sel_stride * 8u;
-            const uint32_t sgrid = (uint32_t)std::min<uint64_t>((uint64_t)num_cu_ * 24u, slots);
+            uint32_t sgrid = (uint32_t)std::min<uint64_t>((uint64_t)num_cu_ * 24u, slots);
+            if (kn.build_wg > 0) sgrid = std::min<uint32_t>(sgrid, (uint32_t)kn.build_wg);
             HIP_TRY(ks.launch_build_select(sgrid, sel_lds, nullptr, sa));
             // (a kernel that faults is reported by the synchronising copies below at the latest; asked here so that the
             // message names the kernel, and before sel_n is trusted)

@@ -34,6 +34,8 @@ struct Knobs {
                                  // (unset: strict DistCosine / DistDot batches of >= 40 000 queries on rows of one 128-byte line)
     int pair_tbits_delta = 0;    // HNSWGPU_PAIR_TBITS_DELTA: the pair kernel's visited tables, in powers of two relative to the one-query kernels'
     int pair_wg_per_cu = -1;     // HNSWGPU_PAIR_WG_PER_CU: cap on its resident workgroups per CU
+    int build_wg = -1;           // HNSWGPU_BUILD_WG (test hook): cap on the workgroups of the two construction kernels, so that one wavefront handles many points of a window
+    int build_hash_bits = -1;    // HNSWGPU_BUILD_HASH_BITS (test hook): the construction search's visited-table size (clamped like the default)
     int64_t filter_set_bytes = -1;  // HNSWGPU_FILTER_SET_MB (MiB, may be a fraction): bound on the bitmaps one launch of a filter-set search holds (unset: 256 MiB)
 };
 const Knobs& knobs();

@@ -453,14 +453,21 @@ public:
     static bool hnsw_filter(const Filter& f, size_t id) { return std::binary_search(f.begin(), f.end(), id); }
 
     // ---- search_layer (src/hnsw.rs:922-1064); filter == nullptr is the unfiltered branch --
+    // n_visited (may be null): how many points the search marked as visited (the entry point included)
     RustBinaryHeap search_layer(const float* point, std::shared_ptr<Point> entry, size_t ef,
-                                uint8_t layer, Counters* cnt, const Filter* filter = nullptr) const {
+                                uint8_t layer, Counters* cnt, const Filter* filter = nullptr, size_t* n_visited = nullptr) const {
         RustBinaryHeap return_points;                                      // :940
+        if (n_visited) *n_visited = 0;
         if (points_by_layer[layer].empty()) return return_points;          // :942-946
         if (entry->p_id.rank < 0) return return_points;                    // :947-950
         float dist_to_entry_point = eval(point, entry->v.data(), cnt);     // :952
         std::unordered_map<PointId, std::shared_ptr<Point>, PointIdHash> visited;  // :955
         visited.emplace(entry->p_id, entry);                               // :956
+        struct ReportVisited {  // (the search returns from three places)
+            size_t* out;
+            const std::unordered_map<PointId, std::shared_ptr<Point>, PointIdHash>& set;
+            ~ReportVisited() { if (out) *out = set.size(); }
+        } report_visited{n_visited, visited};
         RustBinaryHeap candidate_points;                                   // :958
         candidate_points.push(std::make_shared<PointWithOrder>(entry, -dist_to_entry_point));
         return_points.push(std::make_shared<PointWithOrder>(entry, dist_to_entry_point));
@@ -648,6 +655,137 @@ public:
         check_entry_point(new_point);                                           // :1212
     }
 
+    // ---- insert_window: the protocol of a GPU-assisted build (the product's builder.cpp: insert_batch_gpu and
+    // apply_window_point; its hnsw_build_search_kernel / hnsw_build_select_kernel), restated from this file's own routines.
+    // The `count` points of a window do not see each other's searches:
+    //   phase 1 (frozen): every point is generated in input order (levels and p_ids as `insert` draws them), then the
+    //     searches of insert (src/hnsw.rs:1110-1197) run for each of them against the graph as it stood when the window
+    //     began -- lists, entry point and its level, and which layers held a point.  Nothing is linked during this phase,
+    //     so the live lists ARE the frozen ones.  A layer counts as populated for a point if it held a point when the
+    //     window began or if it is the point's own level (generate_new_point pushed it first, :516).  Above the point's
+    //     level: ef = 1 per populated layer, the hit is kept, and it becomes the next entry only when nearer (:1146-1150).
+    //     From min(level, frozen entry level) down: ef_construction, and the nearest candidate -- what select_neighbours
+    //     keeps first -- is the next layer's entry (:1201-1203).
+    //   phase 2 (live, input order): the hits are pushed (:1140-1144); a layer above the frozen entry level yields the
+    //     frozen entry point alone, if populated; select_neighbours runs on the phase-1 candidates (with extend_candidates
+    //     it reads the LIVE lists, as the product's host path does); lists sorted and stored (:1195-1197); reverse update
+    //     (:1210); check_entry_point (:1212).
+    // With one point per call this is `insert`.
+    struct WindowStats {
+        uint64_t windows = 0;              // insert_window calls so far
+        uint64_t points = 0;               // points they inserted
+        uint64_t max_visited = 0;          // most points one phase-1 search_layer marked visited
+        uint64_t above_entry = 0;          // points whose level exceeds the frozen entry point's
+        uint64_t skipped_unpopulated = 0;  // (point, layer) pairs that gave nothing because the frozen graph had no point there
+        uint64_t max_candidates = 0;       // longest candidate list of a phase-1 ef_construction search
+        uint64_t max_kept = 0;             // most neighbours the heuristic kept (before any keep_pruned fill)
+        uint64_t selections_pruned = 0;    // select_neighbours calls with more candidates than asked for
+        uint64_t selected_ties = 0;        // selected lists that hold the same f32 distance twice: their order is the heap's, and
+                                           // the product's lean construction search does not claim it
+    };
+    WindowStats window_stats;
+
+    void insert_window(const float* data, size_t count, size_t d, const size_t* ids) {
+        if (count == 0) return;
+        if (data_dimension == 0) data_dimension = d;
+        if (d != data_dimension) throw std::runtime_error("insert_window: dimension mismatch");
+        const std::shared_ptr<Point> frozen_entry = entry_point;
+        if (!frozen_entry && count > 1) throw std::runtime_error("insert_window: a window of several points needs a graph to search in");
+        const int frozen_level = frozen_entry ? (int)frozen_entry->p_id.layer : -1;
+        bool populated[NB_LAYER_MAX];
+        for (size_t l = 0; l < NB_LAYER_MAX; ++l) populated[l] = get_layer_nb_point(l) > 0;
+        struct Found {
+            std::shared_ptr<Point> point;
+            std::vector<PWO> hits;              // per layer above the point's level: the ef = 1 hit, or null
+            std::vector<RustBinaryHeap> cands;  // per layer from min(level, frozen entry level) down: search_layer's heap
+        };
+        std::vector<Found> found(count);
+        // ---- phase 1
+        for (size_t i = 0; i < count; ++i) {
+            const float* v = data + i * d;
+            const size_t level = layer_g.generate();  // generate_new_point (src/hnsw.rs:503-531)
+            PointId p_id{(uint8_t)level, (int32_t)points_by_layer[level].size()};
+            Found& f = found[i];
+            f.point = std::make_shared<Point>(v, d, ids ? ids[i] : i, p_id);
+            points_by_layer[level].push_back(f.point);
+            nb_point += 1;
+            f.hits.assign(NB_LAYER_MAX, nullptr);
+            f.cands.resize(NB_LAYER_MAX);
+            if (!frozen_entry) continue;
+            if ((int)level > frozen_level) window_stats.above_entry++;
+            std::shared_ptr<Point> enter = frozen_entry;
+            float dist_to_entry = eval(v, enter->v.data(), nullptr);            // :1110-1112
+            size_t n_visited = 0;
+            for (int l = frozen_level; l >= (int)level + 1; --l) {                // :1114-1155
+                if (!populated[l]) { window_stats.skipped_unpopulated++; continue; }  // :942-946
+                RustBinaryHeap sorted_points = search_layer(v, enter, 1, (uint8_t)l, nullptr, nullptr, &n_visited);
+                window_stats.max_visited = std::max<uint64_t>(window_stats.max_visited, n_visited);
+                if (sorted_points.len() > 1) throw std::runtime_error("in insert_window : search_layer returned > 1 points");
+                PWO ep;
+                if (sorted_points.pop(ep)) {
+                    f.hits[l] = ep;
+                    if (ep->dist_to_ref < dist_to_entry) {                        // :1146-1150
+                        enter = ep->point_ref;
+                        dist_to_entry = ep->dist_to_ref;
+                    }
+                }
+            }
+            for (int l = (int)level; l > frozen_level; --l)                       // above the frozen entry point: phase 2
+                if (l != (int)level && !populated[l]) window_stats.skipped_unpopulated++;
+            for (int l = std::min((int)level, frozen_level); l >= 0; --l) {       // :1158-1205
+                if (!populated[l] && l != (int)level) { window_stats.skipped_unpopulated++; continue; }
+                f.cands[l] = search_layer(v, enter, ef_construction, (uint8_t)l, nullptr, nullptr, &n_visited);
+                window_stats.max_visited = std::max<uint64_t>(window_stats.max_visited, n_visited);
+                window_stats.max_candidates = std::max<uint64_t>(window_stats.max_candidates, f.cands[l].len());
+                const PWO* nearest = nullptr;
+                for (const PWO& c : f.cands[l].data)
+                    if (!nearest || pwo_lt(c, *nearest)) nearest = &c;
+                if (nearest) enter = (*nearest)->point_ref;                       // :1201-1203
+            }
+        }
+        // ---- phase 2
+        for (size_t i = 0; i < count; ++i) {
+            Found& f = found[i];
+            const std::shared_ptr<Point>& new_point = f.point;
+            const float* v = new_point->v.data();
+            const int level = new_point->p_id.layer;
+            if (!frozen_entry) {                                                  // :1106-1109
+                check_entry_point(new_point);
+                continue;
+            }
+            for (int l = frozen_level; l >= level + 1; --l)                       // :1140-1144
+                if (f.hits[l] && new_point->neighbours[l].size() < (size_t)(uint8_t)max_nb_connection)
+                    new_point->neighbours[l].push_back(f.hits[l]);
+            for (int l = level; l >= 0; --l) {
+                RustBinaryHeap sorted_points;
+                if (l > frozen_level) {
+                    // search_layer from the frozen entry point in a layer above it: that point alone, if the layer has a point
+                    if (l == level || populated[l])
+                        sorted_points.push(std::make_shared<PointWithOrder>(frozen_entry, eval(v, frozen_entry->v.data(), nullptr)));
+                } else {
+                    sorted_points = std::move(f.cands[l]);
+                }
+                sorted_points = from_positive_to_negative(sorted_points);          // :1173
+                if (sorted_points.is_empty()) continue;
+                const size_t nb_conn = l == 0 ? 2 * max_nb_connection : max_nb_connection;
+                const bool extend_c = l == 0 ? extend_candidates : false;
+                if (sorted_points.len() > nb_conn) window_stats.selections_pruned++;
+                std::vector<PWO> neighbours;
+                size_t kept = 0;
+                select_neighbours(v, sorted_points, nb_conn, extend_c, (uint8_t)l, keep_pruned, neighbours, &kept);
+                window_stats.max_kept = std::max<uint64_t>(window_stats.max_kept, kept);
+                sort_unstable(neighbours);                                         // :1195
+                for (size_t j = 1; j < neighbours.size(); ++j)
+                    if (neighbours[j]->dist_to_ref == neighbours[j - 1]->dist_to_ref) { window_stats.selected_ties++; break; }
+                new_point->neighbours[l] = neighbours;                             // :1197
+            }
+            reverse_update_neighborhood_simple(new_point);                         // :1210
+            check_entry_point(new_point);                                          // :1212
+        }
+        window_stats.windows += 1;
+        window_stats.points += count;
+    }
+
     // neighbour list of flat point (for dumps and graph comparison)
     static void sort_unstable(std::vector<PWO>& v) {
         // Rust sort_unstable by Ord (distance only); for tie-free lists any sort agrees.
@@ -700,8 +838,9 @@ private:
     // src/hnsw.rs:1299-1421 (Navarro heuristic).  `candidates` holds negated distances.
     void select_neighbours(const float* data, RustBinaryHeap& candidates, size_t nb_neighbours_asked,
                            bool extend_candidates_asked, uint8_t layer, bool keep_pruned_,
-                           std::vector<PWO>& neighbours_vec) {
+                           std::vector<PWO>& neighbours_vec, size_t* kept_by_heuristic = nullptr) {
         neighbours_vec.clear();
+        if (kept_by_heuristic) *kept_by_heuristic = 0;  // (stays 0 where the heuristic does not run)
         bool extend = false;
         if (candidates.len() <= nb_neighbours_asked) {
             if (!extend_candidates_asked) {
@@ -745,6 +884,7 @@ private:
                 discarded_points.push(std::make_shared<PointWithOrder>(e_p->point_ref, e_p->dist_to_ref));
             }
         }
+        if (kept_by_heuristic) *kept_by_heuristic = neighbours_vec.size();
         if (keep_pruned_) {
             while (!discarded_points.is_empty() && neighbours_vec.size() < nb_neighbours_asked) {
                 PWO best;

@@ -50,6 +50,22 @@ int orc_insert_batch(void* hv, const float* data, size_t n, size_t d, const size
     ORC_CATCH(-1)
 }
 
+// Hnsw::insert_window (hnsw_oracle.hpp): one window of a GPU-assisted build -- searches against the graph as it is now for
+// all n points, then the points linked in order.
+int orc_insert_window(void* hv, const float* data, size_t n, size_t d, const size_t* ids) {
+    ORC_TRY
+    static_cast<Hnsw*>(hv)->insert_window(data, n, d, ids);
+    return 0;
+    ORC_CATCH(-1)
+}
+// out[9] = {windows, points, max_visited, above_entry, skipped_unpopulated, max_candidates, max_kept, selections_pruned, selected_ties}
+void orc_window_stats(void* hv, uint64_t* out) {
+    const Hnsw::WindowStats& s = static_cast<Hnsw*>(hv)->window_stats;
+    const uint64_t v[9] = {s.windows, s.points, s.max_visited, s.above_entry, s.skipped_unpopulated, s.max_candidates, s.max_kept, s.selections_pruned,
+                           s.selected_ties};
+    std::memcpy(out, v, sizeof v);
+}
+
 // Hnsw::search (src/hnsw.rs:1597).  Outputs hold up to k entries; *count = number returned.
 int orc_search(void* hv, const float* q, size_t d, size_t k, size_t ef, uint64_t* out_ids, float* out_dists,
                uint8_t* out_layer, int32_t* out_rank, uint32_t* count) {

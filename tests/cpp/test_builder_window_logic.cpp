@@ -7,7 +7,10 @@
 //   1. window = 1 reproduces the serial insertion: dumps byte-identical;
 //   2. growing windows on several threads: a well-formed graph of the right size that finds its own points;
 //   3. a backend that fails at its third window: the call succeeds, says so (last_warning) and every point is linked;
-//   4. a backend that cannot serve the build at all (check fails): error, index unchanged.
+//   4. a backend that cannot serve the build at all (check fails): error, index unchanged;
+//   5. windows of 200 points on one thread, select_neighbours on the host and then on the "device": the input vectors (raw
+//      f32) and both dumps are written for tests/test_cpp_mirror.py, which builds the same windows with the oracle's
+//      insert_window and requires the same bytes.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -297,6 +300,25 @@ int main(int argc, char** argv) {
         if (b.insert_batch_gpu(x.data(), 100, d, nullptr, 2, dev, 0, err) != ERR_DEVICE || b.nb_point() != 0) {
             std::printf("refusing backend: nb_point %llu, err '%s'\n", (unsigned long long)b.nb_point(), err.c_str());
             return 1;
+        }
+    }
+    // ---- 5. real windows, deterministic (one thread): dumps and inputs for the comparison with the oracle's windowed insertion
+    for (int pass = 0; pass < 2; ++pass) {
+        const uint64_t n = 2000;
+        const std::vector<float> x = data_set(n, d, 15);
+        GraphBuilder b(params());
+        HostMockBackend dev;
+        dev.do_select = pass == 1;
+        if (b.insert_batch_gpu(x.data(), n, d, nullptr, 1, dev, 200, err) != OK) { std::printf("window 200: %s\n", err.c_str()); return 1; }
+        if (!b.last_warning().empty()) { std::printf("window 200: unexpected warning %s\n", b.last_warning().c_str()); return 1; }
+        if (dev.windows != 5) { std::printf("window 200: %d windows for %llu points\n", dev.windows, (unsigned long long)n); return 1; }
+        FlatIndex f;
+        b.finalize(f);
+        if (write_dump(f, dir, pass == 0 ? "window200_host_select" : "window200_device_select", err) != OK) { std::printf("dump: %s\n", err.c_str()); return 1; }
+        if (pass == 0) {
+            std::ofstream raw(dir + "/window200.f32", std::ios::binary);
+            raw.write(reinterpret_cast<const char*>(x.data()), (std::streamsize)(x.size() * sizeof(float)));
+            if (!raw) { std::printf("window 200: cannot write the input vectors\n"); return 1; }
         }
     }
     std::printf("window logic OK\n");

@@ -50,6 +50,9 @@ def lib():
         L.orc_get_dimension.restype = C.c_size_t
         L.orc_get_dimension.argtypes = [C.c_void_p]
         L.orc_insert_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+        L.orc_insert_window.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+        L.orc_window_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.orc_window_stats.restype = None
         L.orc_search.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_parallel_search.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
@@ -99,6 +102,11 @@ def _p(a):
 
 # columns of SearchResult.per_query (want_counters="per_query")
 PER_QUERY_FIELDS = ("n_dist", "n_expand", "n_ids_read", "descent_n_dist", "descent_n_expand")
+
+
+# fields of OracleHnsw.window_stats()
+WINDOW_STAT_FIELDS = ("windows", "points", "max_visited", "above_entry", "skipped_unpopulated", "max_candidates", "max_kept",
+                      "selections_pruned", "selected_ties")
 
 
 class SearchResult:
@@ -155,6 +163,24 @@ class OracleHnsw:
             idp = _p(ids)
         if lib().orc_insert_batch(self.h, _p(data), n, d, idp) != 0:
             raise RuntimeError(_err())
+
+    def insert_window(self, data, ids=None):
+        """One window of a GPU-assisted build (Hnsw::insert_window in oracle/hnsw_oracle.hpp): the searches of every row against
+        the graph as it is now, then the rows linked in input order."""
+        data = np.ascontiguousarray(data, dtype=np.float32)
+        n, d = data.shape
+        idp = None
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.uint64)
+            idp = _p(ids)
+        if lib().orc_insert_window(self.h, _p(data), n, d, idp) != 0:
+            raise RuntimeError(_err())
+
+    def window_stats(self):
+        """What the insert_window calls so far met (WINDOW_STAT_FIELDS), as a dict."""
+        out = np.zeros(len(WINDOW_STAT_FIELDS), np.uint64)
+        lib().orc_window_stats(self.h, _p(out))
+        return {k: int(v) for k, v in zip(WINDOW_STAT_FIELDS, out)}
 
     def search(self, q, k, ef):
         q = np.ascontiguousarray(q, dtype=np.float32)

@@ -195,3 +195,21 @@ def test_gpu_insert_without_a_device_leaves_the_index_unchanged(native, tmp_path
     g.set_build_options(gpu_device=bad_device, gpu_window=0)
     with pytest.raises(native.HnswError):
         g.parallel_insert(X)
+
+
+def test_a_modified_level_scale_is_rounded_as_the_reference_rounds_it(native, oracle, tmp_path):
+    """LayerGenerator::new computes 1 / ln(M) (src/hnsw.rs:327) and modify_level_scale multiplies that by the factor (:378): two
+    roundings.  factor / ln(M) is another double for most factors (0.6 with M = 10; 0.5 hides it), and the scale is written into
+    the dump: a serial build with such a factor must still equal the oracle's byte for byte."""
+    X = uniform(300, 10, 1)
+    o = oracle.OracleHnsw(10, 300, 16, 40, "DistL1")
+    o.modify_level_scale(0.6)
+    o.insert_batch(X)
+    o.file_dump(tmp_path, "orc")
+    h = native.Hnsw(10, 300, 16, 40, "DistL1")
+    h.modify_level_scale(0.6)
+    h.set_build_options(nthreads=1)
+    h.parallel_insert(X)
+    h.file_dump(tmp_path, "host")
+    for ext in (".hnsw.graph", ".hnsw.data"):
+        assert open(tmp_path / ("orc" + ext), "rb").read() == open(tmp_path / ("host" + ext), "rb").read(), ext

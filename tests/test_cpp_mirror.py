@@ -83,18 +83,47 @@ def _window_logic_sources():
     return [os.path.join(ROOT, "tests", "cpp", "test_builder_window_logic.cpp"), os.path.join(csrc, "builder.cpp"), os.path.join(csrc, "hnswio.cpp")]
 
 
-def test_gpu_assisted_construction_host_side_against_a_mock_device(tmp_path):
-    """GraphBuilder::insert_batch_gpu with the device replaced by a CPU mock that keeps the frozen snapshot and searches it with
-    the builder's own semantics: window 1 == the serial insertion (dumps byte-identical), growing windows on several threads,
-    a backend that fails at its third window (the host builder finishes, the call says so), a backend that refuses (index
-    unchanged).  The device side of the same protocol is GPU-tested (tests/test_gpu_round2.py, tests/test_gpu_round3.py)."""
+@pytest.fixture(scope="module")
+def window_logic_run(tmp_path_factory):
+    """tests/cpp/test_builder_window_logic.cpp built and run once: (the finished process, the directory of its dumps)."""
+    tmp_path = tmp_path_factory.mktemp("window_logic")
     exe = tmp_path / "test_builder_window_logic"
     subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-pthread", "-I", os.path.join(ROOT, "hnswlib-rs_amd", "csrc"),
                     *_window_logic_sources(), "-o", str(exe)], check=True, capture_output=True)
     out = tmp_path / "dumps"
     out.mkdir()
-    r = subprocess.run([str(exe), str(out)], capture_output=True, text=True, timeout=600)
+    return subprocess.run([str(exe), str(out)], capture_output=True, text=True, timeout=600), out
+
+
+def test_gpu_assisted_construction_host_side_against_a_mock_device(window_logic_run):
+    """GraphBuilder::insert_batch_gpu with the device replaced by a CPU mock that keeps the frozen snapshot and searches it with
+    the builder's own semantics: window 1 == the serial insertion (dumps byte-identical), growing windows on several threads,
+    a backend that fails at its third window (the host builder finishes, the call says so), a backend that refuses (index
+    unchanged).  The device side of the same protocol is GPU-tested (tests/test_gpu_round2.py, tests/test_gpu_round3.py,
+    tests/test_gpu_build_windows.py)."""
+    r, _ = window_logic_run
     assert r.returncode == 0 and "window logic OK" in r.stdout, r.stdout + r.stderr
+
+
+def test_oracle_windowed_insertion_equals_the_host_side_of_the_product(window_logic_run, oracle):
+    """The oracle's insert_window (the model that judges the device in tests/test_gpu_build_windows.py) against the product's
+    host side of the same protocol, without a GPU: section 5 of the C++ test builds 2000 points on one thread in windows of
+    200 over the mock device, with select_neighbours on the host and then on the mock; the oracle, given the same vectors and
+    the same window schedule, must dump the same bytes as both."""
+    import numpy as np
+    from test_gpu_build_windows import build_windowed_oracle
+    r, out = window_logic_run
+    assert r.returncode == 0, r.stdout + r.stderr
+    X = np.fromfile(out / "window200.f32", dtype=np.float32).reshape(2000, 10)
+    o = oracle.OracleHnsw(8, 2000, 16, 40, "DistL2")
+    sizes = build_windowed_oracle(o, X, 200)
+    assert sizes == [200, 200, 200, 200, 176]
+    o.file_dump(out, "window200_oracle")
+    for name in ("window200_host_select", "window200_device_select"):
+        for ext in (".hnsw.graph", ".hnsw.data"):
+            assert open(out / (name + ext), "rb").read() == open(out / ("window200_oracle" + ext), "rb").read(), (name, ext)
+    st = o.window_stats()
+    assert st["windows"] == 5 and st["points"] == 976 and st["selections_pruned"] > 0, st
 
 
 def test_gpu_assisted_construction_host_side_is_clean_under_thread_sanitizer(tmp_path):

@@ -240,3 +240,22 @@ def test_builder_graph_against_f64(native, oracle, name, n, opts):
     fails = F.check_graph(h, X, "DistL2", m, oracle.levels(m, n), stats=stats)
     assert not fails, (name, fails[:6])
     assert stats["edges"] > n * m // 2 and stats["owners_named"] == n, stats
+
+
+@pytest.mark.parametrize("metric,d,data", [("DistCosine", 25, "uniform"), ("DistCosine", 32, "uniform"), ("DistDot", 16, "normalized"),
+                                           ("DistJensenShannon", 12, "probability")])
+def test_builder_graph_against_f64_other_metrics(native, oracle, metric, d, data):
+    """The same check of the multi-threaded, large-window GPU-assisted build beyond DistL2: DistCosine with the norm in the row's
+    padding (d = 25) and in an array beside the row (d = 32), DistDot on normalized rows, DistJensenShannon on probability vectors.
+    That path cannot be compared bit for bit (the host threads link a window's points in no fixed order); one thread and real
+    windows are compared byte for byte in tests/test_gpu_build_windows.py."""
+    n, m = 5000, 16
+    X = {"uniform": uniform, "normalized": normalized, "probability": probability}[data](n, d, 7)
+    h = native.Hnsw(m, n, 16, 200, metric)
+    h.set_build_options(fast_arithmetic=False, nthreads=8, gpu_device=0, gpu_window=4096)
+    h.parallel_insert(X)
+    assert h.get_nb_point() == n
+    stats = {}
+    fails = F.check_graph(h, X, metric, m, oracle.levels(m, n), stats=stats)
+    assert not fails, (metric, d, fails[:6])
+    assert stats["edges"] > n * m // 2 and stats["owners_named"] == n, stats

@@ -333,3 +333,29 @@ def test_two_transcriptions_of_std_binary_heap_agree(oracle, seed):
     rest = h.into_sorted_vec()
     assert [t for _, t in popped] == list(pt) and np.array_equal(np.array([v for v, _ in popped], np.float32), pv)
     assert [t for _, t in rest] == list(st) and np.array_equal(np.array([v for v, _ in rest], np.float32), sv)
+
+
+@pytest.mark.parametrize("dist,d,keep_pruned,extend", [("DistL2", 16, False, False), ("DistCosine", 25, True, False),
+                                                       ("DistJeffreys", 12, False, True)])
+def test_insert_window_of_one_point_is_insert(oracle, tmp_path, dist, d, keep_pruned, extend):
+    """The windowed insertion that models a GPU-assisted build (Hnsw::insert_window, oracle/hnsw_oracle.hpp) with one point per
+    call, from the first point on, is the serial insertion: the dumps are byte-identical."""
+    from conftest import probability, uniform
+    n = 700
+    X = probability(n, d, 23) if dist == "DistJeffreys" else uniform(n, d, 23)
+    dumps = []
+    for windowed in (False, True):
+        o = oracle.OracleHnsw(8, n, 16, 50, dist)
+        o.set_keeping_pruned(keep_pruned)
+        o.set_extend_candidates(extend)
+        if windowed:
+            for i in range(n):
+                o.insert_window(X[i:i + 1], np.array([i], np.uint64))
+            st = o.window_stats()
+            assert st["windows"] == n and st["points"] == n and st["max_candidates"] == 50 and st["selections_pruned"] > 0, st
+        else:
+            o.insert_batch(X)
+        name = "windowed" if windowed else "serial"
+        o.file_dump(tmp_path, name)
+        dumps.append([open(tmp_path / (name + ext), "rb").read() for ext in (".hnsw.graph", ".hnsw.data")])
+    assert dumps[0] == dumps[1]
