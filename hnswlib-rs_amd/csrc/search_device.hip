@@ -533,27 +533,131 @@ int DeviceIndex::upload(const FlatIndex& x, int device, std::string& err) {
     return OK;
 }
 
-// Literal search (hnsw_search_exact_kernel) of the queries in d_qlist (nullptr: all nq), optionally filtered.
+// Where a call's answers go (device addresses; layer / rank may be null).  stats: [nq][8] as SearchArgs::stats -- the caller's, or
+// null on the way in: search_device_impl then names the workspace's.
+struct DeviceIndex::AnswerBufs {
+    uint64_t* ids; float* dists; uint8_t* layer; int32_t* rank; uint32_t* counts;
+    uint32_t* stats;
+    OutLayout layout;
+};
+// The call's filter: none, one sorted id vector for every query of the batch (device memory), or a FilterSet.
+struct DeviceIndex::CallFilter {
+    const uint64_t* d_allowed; uint64_t n_allowed;
+    const FilterSet* d_set;
+    bool filtered() const { return d_allowed != nullptr || n_allowed != 0 || d_set != nullptr; }
+};
+
+namespace {
+// The control words of a call: Workspace::d_ctrl (16 words, zeroed by the first descent launch) and h_ctrl, the pinned host copy
+// they are read back into.  Word 0 is the work counter of the persistent grid, the counters start at word 1 (SearchArgs::
+// overflow_count); words 0-3 are zeroed again in front of every launch behind a call's first.  What a counter means depends on
+// the kernel that ran last.
+constexpr uint32_t CTRL_WORK = 0, CTRL_COUNTERS = 1;
+constexpr size_t CTRL_LAUNCH_BYTES = 16;
+// hnsw_search_kernel and hnsw_search_pair_kernel: queries to search again (retry_out: the table full and no bitmap slice / handed
+// back by the pair pass), queries that moved to the HBM bitmap inside the launch, queries that would overflow a table of half the
+// size, ties not resolved in the launch (tie_list; cumulative over relaunches), ties resolved with the literal heaps inside it
+enum : uint32_t { SC_RETRY = 1, SC_TO_BITMAP = 2, SC_HALF_OVERFLOW = 3, SC_FLAGGED = 4, SC_LITERAL = 5 };
+// hnsw_search_exact_kernel, the literal kernel: internal failures, queries on which the reference panics, queries whose candidate
+// heap outgrew this launch's scratch (retry_out)
+enum : uint32_t { XC_INTERNAL = 1, XC_PANICS = 2, XC_RETRY = 3 };
+// the filter-set kernels (words 0-3 stay the literal kernel's): entries of filter_of that name no filter (filter_of_check_kernel),
+// queries of the group (filter_group_kernel)
+enum : uint32_t { FC_BAD_FILTER_OF = 8, FC_GROUP_QUERIES = 9 };
+constexpr size_t SC_BYTES = 24, XC_BYTES = 16, FC_BYTES = 64;  // what is read back behind each
+}  // namespace
+
+// One search call behind its argument checks (search_device_impl): what its steps share and what they hand to each other.
+struct DeviceIndex::SearchCall {
+    DeviceIndex& ix; const DeviceIndexView& v; Workspace& w;
+    const hipStream_t stream; const AnswerBufs& out; std::string& err;
+    const uint64_t nq, k, ef;  // ef: already max(ef_arg, k)
+    const int metric; const KernelSet& ks;  // the replica's kernel_metric() when the call began, its kernels
+    const uint32_t tile_bytes; const bool strict_ties;
+    const Knobs& kn;           // (the environment was read once: search_device.hpp)
+    CallInfo info{};
+    // the search launches so far
+    uint32_t work;                    // queries still to search ...
+    const uint32_t* qlist = nullptr;  // ... and their list (nullptr: all of them, input order)
+    int pingpong = 0;                 // the w.retry[] the next launch lists its leftovers in
+    uint32_t launches = 0, stop_recorded_after = ~0u;  // (ev_stop lies behind launch number stop_recorded_after)
+    uint32_t n_flagged = 0, n_literal = 0;
+    bool all_done = false;
+    hipEvent_t main_end;              // ev_ks .. main_end is what the call reports as its main search: ev_ke, the end of the first search launch
+    // the visited tables of the one-query kernels (plan)
+    int slots = 1, table = TABLE_LDS_CELL16;
+    uint32_t idbits = 0, tbits = 0, tbits_first = 0;
+    bool grown = false, env_forced = false;
+    SearchCall(DeviceIndex& ix_, Workspace& w_, hipStream_t stream_, const AnswerBufs& out_, uint64_t nq_, uint64_t k_, uint64_t ef_, std::string& err_)
+        : ix(ix_), v(ix_.v_), w(w_), stream(stream_), out(out_), err(err_), nq(nq_), k(k_), ef(ef_), metric(ix_.kernel_metric()),
+          ks(kernel_set(metric)), tile_bytes(tile_bytes_for(metric, ix_.v_.row_stride)), strict_ties(ix_.strict_ties_.load()), kn(knobs()),
+          work((uint32_t)nq_), main_end(w_.ev_ke) {}
+    volatile const uint32_t* ctrl() const { return static_cast<volatile uint32_t*>(w.h_ctrl); }
+    uint32_t* d_ctrl() const { return static_cast<uint32_t*>(w.d_ctrl); }
+    struct LaunchShape { size_t lds; int per_cu, strict_cap; bool strict_kernel; };
+    hipError_t read_ctrl(size_t bytes, bool record_stop);
+    SearchArgs search_args(const uint32_t* list, uint32_t n) const;
+    void table_feedback();
+    int descend(const float* d_queries, const RowFeed* feed);
+    int run_exact(const uint32_t* d_qlist, uint32_t n, const uint32_t* d_allow, uint32_t* panics, const uint32_t* d_slot_of = nullptr);
+    int filter_set_search(const FilterSet& fs);
+    int literal_call(const CallFilter& filter);
+    int plan(), pair_pass(), shape_launch(SearchArgs& a, LaunchShape& s), relaunch_loop(), rerun_ties();
+};
+
+// The first `bytes` of the control words back on the host; ev_stop behind the copy where the launch may have been the call's last.
+hipError_t DeviceIndex::SearchCall::read_ctrl(size_t bytes, bool record_stop) {
+    hipError_t e = hipMemcpyAsync(w.h_ctrl, w.d_ctrl, bytes, hipMemcpyDeviceToHost, stream);  // pinned: a true asynchronous copy
+    if (e == hipSuccess && record_stop) {
+        e = hipEventRecord(w.ev_stop, stream);  // the end of the call unless another launch follows (the usual case: one wait)
+        stop_recorded_after = launches;
+    }
+    return e == hipSuccess ? wait_stream(stream) : e;
+}
+
+// What every launch of a search kernel is told: the `n` queries of `list`, where the answers go.  Table, bitmap slices, retry and tie
+// lists and the literal heaps' scratch are the launching path's to add; what it leaves alone stays zero.
+SearchArgs DeviceIndex::SearchCall::search_args(const uint32_t* list, uint32_t n) const {
+    SearchArgs a{};
+    a.queries = w.qpad.as<float>(); a.qlist = list; a.nq = n;
+    a.k = (uint32_t)k; a.ef = (uint32_t)ef;
+    a.tile_bytes = tile_bytes;
+    a.nrm2 = static_cast<const double*>(ix.d_nrm2_);
+    a.pre = w.pre.as<PreDescent>();
+    a.work_counter = d_ctrl() + CTRL_WORK;
+    a.overflow_count = d_ctrl() + CTRL_COUNTERS;
+    a.out_ids = out.ids; a.out_dists = out.dists; a.out_layer = out.layer; a.out_rank = out.rank; a.out_counts = out.counts;
+    a.id_stride = out.layout.id_stride; a.dist_stride = out.layout.dist_stride; a.count_stride = out.layout.count_stride;
+    a.stats = out.stats;
+    return a;
+}
+
+// Table sizing feedback for the next batch: grow when more than ~1 query in 8 had to move to the
+// HBM bitmap, shrink when a half-size table would have overflowed for fewer than 1 in 32.
+void DeviceIndex::SearchCall::table_feedback() {
+    uint32_t next = tbits_first;
+    if ((uint64_t)ctrl()[SC_TO_BITMAP] * 8 > nq && tbits_first < 14u) next = tbits_first + 1;
+    else if ((uint64_t)ctrl()[SC_HALF_OVERFLOW] * 32 < nq && tbits_first > 8u) next = tbits_first - 1;
+    std::lock_guard<std::mutex> g(ix.meta_mu_);
+    ix.adapt_ef_ = ef;
+    ix.adapt_tbits_ = next;
+}
+
+// Literal search (hnsw_search_exact_kernel) of the queries in d_qlist (nullptr: all n), optionally filtered; *panics (may be null)
+// grows by the queries on which the reference panics.
 // Resident workgroups are what this kernel lives on (a query is one long chain of round trips), so a workgroup gets the LDS
 // that lets the register limit decide (~10 KB: the top ~1 000 entries of the candidate heap) and 1 MB of candidate scratch; a
 // query whose candidate heap outgrows that is listed by the kernel and searched again by a second, narrow launch with room
 // for every point.
-int DeviceIndex::run_exact(Workspace& w, const float* d_qpad, const uint32_t* d_qlist, uint32_t nq, uint64_t k, uint64_t ef,
-                           const uint32_t* d_allow, uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer,
-                           int32_t* d_out_rank, uint32_t* d_out_counts, uint32_t* stats, void* stream_v, uint32_t* panics,
-                           std::string& err, OutLayout layout, const uint32_t* d_slot_of) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    const uint32_t tile_bytes = tile_bytes_for(kernel_metric(), v_.row_stride);
-    const uint32_t bitmap_words = (v_.n + 31) / 32;
+int DeviceIndex::SearchCall::run_exact(const uint32_t* d_qlist, uint32_t n, const uint32_t* d_allow, uint32_t* panics, const uint32_t* d_slot_of) {
+    const uint32_t bitmap_words = (v.n + 31) / 32;
     const uint64_t bm_slice = (uint64_t)bitmap_words * sizeof(uint32_t);
     const int ns = ef <= 64 ? 1 : ef <= 128 ? 2 : 0;  // return_points in VGPRs when it fits (push+pop fused when full)
-    const KernelSet& ks = kernel_set(kernel_metric());
-    uint32_t panics_total = 0;
-    uint32_t work = nq;
-    const uint32_t* qlist = d_qlist;
-    for (int pass = 0; pass < 2 && work > 0; ++pass) {
+    uint32_t left = n;
+    const uint32_t* list = d_qlist;
+    for (int pass = 0; pass < 2 && left > 0; ++pass) {
         // pass 0: many workgroups with a bounded candidate heap; pass 1: the queries that outgrew it, every point has room
-        const uint64_t cand_cap = pass == 0 ? std::min<uint64_t>(v_.n, 1ull << 17) : v_.n;
+        const uint64_t cand_cap = pass == 0 ? std::min<uint64_t>(v.n, 1ull << 17) : v.n;
         const uint64_t heap_stride = ef + 2 + cand_cap;
         const uint64_t per_block = bm_slice + heap_stride * sizeof(hent_t);
         ExactArgs x{};
@@ -566,55 +670,33 @@ int DeviceIndex::run_exact(Workspace& w, const float* d_qpad, const uint32_t* d_
         int per_cu = 0;
         HIP_TRY(ks.exact_occupancy(ns, lds, &per_cu));
         per_cu = std::max(1, per_cu);
-        uint32_t grid = (uint32_t)std::min<uint64_t>(work, std::max<uint64_t>(1, (16ull << 30) / per_block));
-        grid = std::min<uint32_t>(grid, (uint32_t)num_cu_ * (uint32_t)per_cu);
+        uint32_t grid = (uint32_t)std::min<uint64_t>(left, std::max<uint64_t>(1, (16ull << 30) / per_block));
+        grid = std::min<uint32_t>(grid, (uint32_t)ix.num_cu_ * (uint32_t)per_cu);
         HIP_TRY(w.bitmap.ensure((uint64_t)grid * bm_slice));
         HIP_TRY(w.heaps.ensure((uint64_t)grid * heap_stride * sizeof(hent_t)));
-        HIP_TRY(w.retry[0].ensure((uint64_t)nq * sizeof(uint32_t)));
-        if (knobs().trace_launch)
+        HIP_TRY(w.retry[0].ensure((uint64_t)n * sizeof(uint32_t)));
+        if (kn.trace_launch)
             std::fprintf(stderr, "[hnswgpu launch] literal kernel, pass %d: %u queries on %u workgroups (%d per CU), %zu bytes of LDS each "
-                         "(candidate heap: %u entries in LDS, %llu in all)\n", pass, work, grid, per_cu, lds, x.cand_lds, (unsigned long long)cand_cap);
-        SearchArgs a{};
-        a.queries = d_qpad;
-        a.qlist = qlist;
-        a.nq = work;
-        a.k = (uint32_t)k;
-        a.ef = (uint32_t)ef;
-        a.tile_bytes = tile_bytes;
-        a.work_counter = static_cast<uint32_t*>(w.d_ctrl);
-        a.overflow_count = static_cast<uint32_t*>(w.d_ctrl) + 1;
+                         "(candidate heap: %u entries in LDS, %llu in all)\n", pass, left, grid, per_cu, lds, x.cand_lds, (unsigned long long)cand_cap);
+        SearchArgs a = search_args(list, left);
         a.retry_out = pass == 0 ? w.retry[0].as<uint32_t>() : nullptr;
         a.bitmap = w.bitmap.as<uint32_t>();
         a.bitmap_words = bitmap_words;
         a.bitmap_blocks = grid;
-        a.nrm2 = static_cast<const double*>(d_nrm2_);
-        a.out_ids = d_out_ids;
-        a.out_dists = d_out_dists;
-        a.out_layer = d_out_layer;
-        a.out_rank = d_out_rank;
-        a.out_counts = d_out_counts;
-        a.id_stride = layout.id_stride;
-        a.dist_stride = layout.dist_stride;
-        a.count_stride = layout.count_stride;
-        a.stats = stats;
-        a.pre = w.pre.as<PreDescent>();
         x.heaps = w.heaps.as<hent_t>();
         x.heap_stride = heap_stride;
         x.cand_cap = (uint32_t)std::min<uint64_t>(cand_cap, 0xFFFFFFFFull);
         x.allow = d_allow;
         x.slot_of = d_slot_of;  // filter set: d_allow holds one bitmap of bitmap_words words per slot
         x.allow_stride = bitmap_words;
-        HIP_TRY(hipMemsetAsync(w.d_ctrl, 0, 16, stream));
-        HIP_TRY(ks.launch_exact(ns, grid, lds, stream, v_, a, x));
-        volatile uint32_t* ctrl = static_cast<volatile uint32_t*>(w.h_ctrl);
-        HIP_TRY(hipMemcpyAsync(w.h_ctrl, w.d_ctrl, 16, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(wait_stream(stream));
-        if (ctrl[1] != 0) { err = "internal error in the literal search kernel (a refused point inside return_points, or a candidate heap beyond every point)"; return ERR_DEVICE; }
-        panics_total += ctrl[2];
-        work = ctrl[3];
-        qlist = w.retry[0].as<uint32_t>();
+        HIP_TRY(hipMemsetAsync(w.d_ctrl, 0, CTRL_LAUNCH_BYTES, stream));
+        HIP_TRY(ks.launch_exact(ns, grid, lds, stream, v, a, x));
+        HIP_TRY(read_ctrl(XC_BYTES, false));
+        if (ctrl()[XC_INTERNAL] != 0) { err = "internal error in the literal search kernel (a refused point inside return_points, or a candidate heap beyond every point)"; return ERR_DEVICE; }
+        if (panics) *panics += ctrl()[XC_PANICS];
+        left = ctrl()[XC_RETRY];
+        list = w.retry[0].as<uint32_t>();
     }
-    if (panics) *panics = panics_total;
     return OK;
 }
 
@@ -622,14 +704,15 @@ int DeviceIndex::search_device(const float* d_queries, uint64_t nq, uint64_t d, 
                                uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank,
                                uint32_t* d_out_counts, uint32_t* d_stats, void* stream, const uint64_t* d_allowed,
                                uint64_t n_allowed, CallInfo* info, std::string& err, const RowFeed* feed, OutLayout layout) {
-    return search_device_impl(d_queries, nq, d, k, ef, d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts, d_stats, stream,
-                              d_allowed, n_allowed, nullptr, info, err, feed, layout);
+    return search_device_impl(d_queries, nq, d, k, ef, AnswerBufs{d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts, d_stats, layout},
+                              stream, CallFilter{d_allowed, n_allowed, nullptr}, info, err, feed);
 }
 int search_filter_set_device(DeviceIndex& ix, const float* d_queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef, const FilterSet& d_set,
                              uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts,
                              uint32_t* d_stats, void* stream, CallInfo* info, std::string& err) {
-    return ix.search_device_impl(d_queries, nq, d, k, ef, d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts, d_stats, stream,
-                                 nullptr, 0, &d_set, info, err, nullptr, OutLayout{});
+    return ix.search_device_impl(d_queries, nq, d, k, ef,
+                                 DeviceIndex::AnswerBufs{d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts, d_stats, OutLayout{}}, stream,
+                                 DeviceIndex::CallFilter{nullptr, 0, &d_set}, info, err, nullptr);
 }
 
 // A filter-set search behind the descent: the bitmaps of the set are built group by group -- as many consecutive filters as the
@@ -639,85 +722,66 @@ int search_filter_set_device(DeviceIndex& ix, const float* d_queries, uint64_t n
 // exactly one group, its answer lands in its own rows.
 // The search must never see a filter_of entry >= n_filters (it would read past the bitmaps): filter_of_check_kernel counts them,
 // and the count is read back -- while the descent and the first group's bitmaps are still running -- before anything is searched.
-int DeviceIndex::filter_set_search(Workspace& w, const FilterSet& fs, uint32_t nq, uint64_t k, uint64_t ef, uint64_t* d_out_ids,
-                                   float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, uint32_t* stats,
-                                   void* stream_v, uint32_t* panics, std::string& err, OutLayout layout) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+int DeviceIndex::SearchCall::filter_set_search(const FilterSet& fs) {
     constexpr uint64_t MAX_FILTER_SET_WAVES = 1ull << 31;  // allow_bitmap_set_kernel: four wavefronts per workgroup, 2^29 workgroups
-    const uint32_t words = (v_.n + 31) / 32;
+    const uint32_t words = (v.n + 31) / 32;
     const uint64_t slot_bytes = (uint64_t)words * sizeof(uint32_t);
-    const int64_t knob = knobs().filter_set_bytes;
+    const int64_t knob = kn.filter_set_bytes;
     const uint64_t budget = knob >= 0 ? (uint64_t)knob : 256ull << 20;
     if (budget < slot_bytes) {
         err = "HNSWGPU_FILTER_SET_MB is smaller than one filter's bitmap (" + std::to_string(slot_bytes) + " bytes for this index)";
         return ERR_ARG;
     }
-    const uint64_t per_group = std::min<uint64_t>({budget / slot_bytes, fs.n_filters, MAX_FILTER_SET_WAVES / ((v_.n + 63u) / 64u) - 1});
-    uint32_t* d_ctrl = static_cast<uint32_t*>(w.d_ctrl);  // words 0-3 are run_exact's; 8: bad filter_of entries, 9: queries of a group
-    volatile uint32_t* h_ctrl = static_cast<volatile uint32_t*>(w.h_ctrl);
-    HIP_TRY(hipMemsetAsync(d_ctrl + 8, 0, 8, stream));
-    HIP_TRY(launch_filter_of_check(stream, fs.filter_of, nq, fs.n_filters, d_ctrl + 8));
+    const uint64_t per_group = std::min<uint64_t>({budget / slot_bytes, fs.n_filters, MAX_FILTER_SET_WAVES / ((v.n + 63u) / 64u) - 1});
+    HIP_TRY(hipMemsetAsync(d_ctrl() + FC_BAD_FILTER_OF, 0, 8, stream));  // (and FC_GROUP_QUERIES behind it)
+    HIP_TRY(launch_filter_of_check(stream, fs.filter_of, (uint32_t)nq, fs.n_filters, d_ctrl() + FC_BAD_FILTER_OF));
     HIP_TRY(w.allow.ensure(per_group * slot_bytes));
-    HIP_TRY(launch_allow_bitmap_set(stream, v_.origin_id, v_.n, fs.ids, fs.offsets, 0, (uint32_t)per_group, w.allow.as<uint32_t>()));
-    HIP_TRY(hipMemcpyAsync(w.h_ctrl, w.d_ctrl, 64, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(wait_stream(stream));
-    if (h_ctrl[8] != 0) {
-        err = std::to_string(h_ctrl[8]) + " entries of filter_of name no filter of the set (>= n_filters = " + std::to_string(fs.n_filters) + ")";
+    HIP_TRY(launch_allow_bitmap_set(stream, v.origin_id, v.n, fs.ids, fs.offsets, 0, (uint32_t)per_group, w.allow.as<uint32_t>()));
+    HIP_TRY(read_ctrl(FC_BYTES, false));
+    if (ctrl()[FC_BAD_FILTER_OF] != 0) {
+        err = std::to_string(ctrl()[FC_BAD_FILTER_OF]) + " entries of filter_of name no filter of the set (>= n_filters = " + std::to_string(fs.n_filters) + ")";
         return ERR_ARG;
     }
-    uint32_t panics_total = 0;
-    if (per_group >= fs.n_filters) {
-        int rc = run_exact(w, w.qpad.as<float>(), nullptr, nq, k, ef, w.allow.as<uint32_t>(), d_out_ids, d_out_dists, d_out_layer, d_out_rank,
-                           d_out_counts, stats, stream, &panics_total, err, layout, fs.filter_of);
+    if (per_group >= fs.n_filters) return run_exact(nullptr, (uint32_t)nq, w.allow.as<uint32_t>(), &info.panics, fs.filter_of);
+    HIP_TRY(w.retry[1].ensure(nq * sizeof(uint32_t)));
+    HIP_TRY(w.slot_of.ensure(nq * sizeof(uint32_t)));
+    for (uint64_t f0 = 0; f0 < fs.n_filters; f0 += per_group) {
+        const uint32_t n_slots = (uint32_t)std::min<uint64_t>(per_group, fs.n_filters - f0);
+        // (the previous group's search has been waited for: its bitmaps, its list and its slots are free)
+        if (f0 != 0)
+            HIP_TRY(launch_allow_bitmap_set(stream, v.origin_id, v.n, fs.ids, fs.offsets, (uint32_t)f0, n_slots, w.allow.as<uint32_t>()));
+        HIP_TRY(hipMemsetAsync(d_ctrl() + FC_GROUP_QUERIES, 0, 4, stream));
+        HIP_TRY(launch_filter_group(stream, fs.filter_of, (uint32_t)nq, (uint32_t)f0, n_slots, w.retry[1].as<uint32_t>(), w.slot_of.as<uint32_t>(),
+                                    d_ctrl() + FC_GROUP_QUERIES));
+        HIP_TRY(read_ctrl(FC_BYTES, false));
+        const uint32_t members = ctrl()[FC_GROUP_QUERIES];
+        if (members == 0) continue;
+        if (kn.trace_launch)
+            std::fprintf(stderr, "[hnswgpu launch] filter set: filters %llu..%llu, %u queries\n", (unsigned long long)f0,
+                         (unsigned long long)(f0 + n_slots - 1), members);
+        int rc = run_exact(w.retry[1].as<uint32_t>(), members, w.allow.as<uint32_t>(), &info.panics, w.slot_of.as<uint32_t>());
         if (rc != OK) return rc;
-    } else {
-        HIP_TRY(w.retry[1].ensure((uint64_t)nq * sizeof(uint32_t)));
-        HIP_TRY(w.slot_of.ensure((uint64_t)nq * sizeof(uint32_t)));
-        for (uint64_t f0 = 0; f0 < fs.n_filters; f0 += per_group) {
-            const uint32_t n_slots = (uint32_t)std::min<uint64_t>(per_group, fs.n_filters - f0);
-            // (the previous group's search has been waited for: its bitmaps, its list and its slots are free)
-            if (f0 != 0)
-                HIP_TRY(launch_allow_bitmap_set(stream, v_.origin_id, v_.n, fs.ids, fs.offsets, (uint32_t)f0, n_slots, w.allow.as<uint32_t>()));
-            HIP_TRY(hipMemsetAsync(d_ctrl + 9, 0, 4, stream));
-            HIP_TRY(launch_filter_group(stream, fs.filter_of, nq, (uint32_t)f0, n_slots, w.retry[1].as<uint32_t>(), w.slot_of.as<uint32_t>(), d_ctrl + 9));
-            HIP_TRY(hipMemcpyAsync(w.h_ctrl, w.d_ctrl, 64, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(wait_stream(stream));
-            const uint32_t members = h_ctrl[9];
-            if (members == 0) continue;
-            if (knobs().trace_launch)
-                std::fprintf(stderr, "[hnswgpu launch] filter set: filters %llu..%llu, %u queries\n", (unsigned long long)f0,
-                             (unsigned long long)(f0 + n_slots - 1), members);
-            uint32_t group_panics = 0;
-            int rc = run_exact(w, w.qpad.as<float>(), w.retry[1].as<uint32_t>(), members, k, ef, w.allow.as<uint32_t>(), d_out_ids, d_out_dists,
-                               d_out_layer, d_out_rank, d_out_counts, stats, stream, &group_panics, err, layout, w.slot_of.as<uint32_t>());
-            if (rc != OK) return rc;
-            panics_total += group_panics;
-        }
     }
-    if (panics) *panics = panics_total;
     return OK;
 }
 
-int DeviceIndex::search_device_impl(const float* d_queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef_arg,
-                                    uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank,
-                                    uint32_t* d_out_counts, uint32_t* d_stats, void* stream_v, const uint64_t* d_allowed,
-                                    uint64_t n_allowed, const FilterSet* d_set, CallInfo* info_out, std::string& err, const RowFeed* feed,
-                                    OutLayout layout) {
+// A batched search on device-resident buffers: the argument checks and the call's workspace, then its steps in order.
+int DeviceIndex::search_device_impl(const float* d_queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef_arg, const AnswerBufs& out_arg,
+                                    void* stream_v, const CallFilter& filter, CallInfo* info_out, std::string& err, const RowFeed* feed) {
     if (!ready_) { err = "index is not resident on a device: call hnswgpu_upload first"; return ERR_DEVICE; }
     if (d != v_.d) { err = "query dimension differs from the index dimension"; return ERR_ARG; }
-    CallInfo info{};
-    auto publish = [&]() {
+    auto publish = [&](const CallInfo& info) {
         if (info_out) *info_out = info;
         std::lock_guard<std::mutex> g(meta_mu_);
         last_ = info;
     };
-    if (nq == 0) { publish(); return OK; }
-    if (!d_queries || !d_out_ids || !d_out_dists || !d_out_counts) { err = "null buffer"; return ERR_ARG; }
+    if (nq == 0) { publish(CallInfo{}); return OK; }
+    if (!d_queries || !out_arg.ids || !out_arg.dists || !out_arg.counts) { err = "null buffer"; return ERR_ARG; }
     if (k == 0) { err = "knbn must be > 0"; return ERR_ARG; }
     const uint64_t ef = std::max(ef_arg, k);  // src/hnsw.rs:1531
     if (ef > 0x7FFFFFF0ull) { err = "ef too large"; return ERR_ARG; }
     if (nq > 0xFFFFFFF0ull) { err = "too many queries in one batch"; return ERR_ARG; }
-    const bool filtered = d_allowed != nullptr || n_allowed != 0 || d_set != nullptr;
+    const FilterSet* d_set = filter.d_set;
     if (d_set && (d_set->n_filters == 0 || d_set->n_filters > 0xFFFFFFFFull || !d_set->offsets || !d_set->filter_of)) {
         err = "a filter set holds 1 .. 2^32 - 1 filters, with their offsets and one filter index per query";
         return ERR_ARG;
@@ -736,285 +800,247 @@ int DeviceIndex::search_device_impl(const float* d_queries, uint64_t nq, uint64_
         ~DrainOnError() { if (!done) (void)hipStreamSynchronize(s); }
     } drain{stream};
 
+    AnswerBufs out = out_arg;
     HIP_TRY(w.qpad.ensure(nq * v_.row_stride * sizeof(float)));
-    if (!d_stats) HIP_TRY(w.stats.ensure(nq * 8 * sizeof(uint32_t)));
-    uint32_t* stats = d_stats ? d_stats : w.stats.as<uint32_t>();
-    const bool strict_ties = strict_ties_.load();
-
+    if (!out.stats) {
+        HIP_TRY(w.stats.ensure(nq * 8 * sizeof(uint32_t)));
+        out.stats = w.stats.as<uint32_t>();
+    }
     HIP_TRY(w.pre.ensure(nq * sizeof(PreDescent)));
-    const uint32_t tile_bytes = tile_bytes_for(kernel_metric(), v_.row_stride);
-    // (the call's events ride on its kernels: ev_start = start of the first descent launch, ev_ks / ev_ke = the first search launch)
-    // first kernel of the call: rows padded to the row stride, the greedy descent of every query (pre[]), counters zeroed
-    {
-        const KernelSet& ks = kernel_set(kernel_metric());
-        // two queries per wavefront where every list above the search layer fits a half's 16 row slots (hnsw_descend_pair_kernel)
-        const bool pair = up_deg_max_ <= 16u && kernel_metric() < KM_SIMD8_FIRST && !knobs().no_pair_descent;
-        const size_t descend_lds = (pair ? 2u : 1u) * (size_t)tile_bytes + IDS_BYTES;
-        int per_cu = descend_per_cu_[pair].load();
-        if (per_cu <= 0) {
-            HIP_TRY(ks.descend_occupancy(descend_lds, pair, &per_cu));
-            per_cu = std::max(1, per_cu);
-            descend_per_cu_[pair].store(per_cu);
-        }
-        // one launch -- or, when the rows are still being gathered into pinned memory, one per chunk: the device reads chunk i
-        // across PCIe while the host fills chunk i + 1 (a few chunks: every launch costs a few microseconds of stream time)
-        const uint64_t chunk = feed ? std::max<uint64_t>(1, feed->chunk_rows) : nq;
-        for (uint64_t lo = 0; lo < nq; lo += chunk) {
-            const uint64_t hi = std::min(nq, lo + chunk);
-            if (feed) feed->fill(feed->ctx, lo, hi);
-            DescendArgs da{};
-            da.src = d_queries + lo * v_.d;
-            da.qpad = w.qpad.as<float>() + lo * v_.row_stride;
-            da.pre = w.pre.as<PreDescent>() + lo;
-            da.nq = (uint32_t)(hi - lo);
-            da.tile_bytes = tile_bytes;
-            da.nrm2 = static_cast<const double*>(d_nrm2_);
-            da.ctrl = lo == 0 ? static_cast<uint32_t*>(w.d_ctrl) : nullptr;
-            da.ctrl_words = 16;
-            da.pair = pair ? 1u : 0u;
-            const uint64_t waves = pair ? (hi - lo + 1) / 2 : hi - lo;
-            HIP_TRY(ks.launch_descend((uint32_t)std::min<uint64_t>(waves, (uint64_t)per_cu * (uint64_t)num_cu_), stream, v_, da,
-                                      LaunchEvents{lo == 0 ? w.ev_start : nullptr, nullptr}));
-        }
-    }
-
+    SearchCall c(*this, w, stream, out, nq, k, ef, err);
+    int rc = c.descend(d_queries, feed);
+    if (rc != OK) return rc;
     // ---- filtered search, and ef beyond the register-resident result set (64 x 16 entries): literal heaps in memory
-    if (filtered || ef > 1024) {
-        const uint32_t* d_allow = nullptr;
-        if (filtered && !d_set) {
-            HIP_TRY(w.allow.ensure((uint64_t)((v_.n + 31) / 32) * sizeof(uint32_t)));
-            HIP_TRY(launch_allow_bitmap(stream, v_.origin_id, v_.n, d_allowed, n_allowed, w.allow.as<uint32_t>()));
-            d_allow = w.allow.as<uint32_t>();
-        }
-        HIP_TRY(hipEventRecord(w.ev_ks, stream));
-        int rc = d_set ? filter_set_search(w, *d_set, (uint32_t)nq, k, ef, d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts, stats,
-                                           stream, &info.panics, err, layout)
-                       : run_exact(w, w.qpad.as<float>(), nullptr, (uint32_t)nq, k, ef, d_allow, d_out_ids, d_out_dists, d_out_layer, d_out_rank,
-                                   d_out_counts, stats, stream, &info.panics, err, layout);
-        if (rc != OK) return rc;
-        HIP_TRY(hipEventRecord(w.ev_stop, stream));
-        HIP_TRY(wait_event(w.ev_stop));
-        float ms = 0.f, ms_main = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, w.ev_start, w.ev_stop));
-        HIP_TRY(hipEventElapsedTime(&ms_main, w.ev_ks, w.ev_stop));
-        info.ms = ms;
-        info.main_ms = ms_main;
-        info.launches = 1;
-        publish();
-        drain.done = true;
-        return OK;
+    if (filter.filtered() || ef > 1024) {
+        rc = c.literal_call(filter);
+    } else if ((rc = c.plan()) == OK && (rc = c.pair_pass()) == OK && (rc = c.relaunch_loop()) == OK) {
+        rc = c.rerun_ties();
     }
+    if (rc != OK) return rc;
+    float ms = 0.f, ms_main = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, w.ev_start, w.ev_stop));
+    HIP_TRY(hipEventElapsedTime(&ms_main, w.ev_ks, c.main_end));  // (not the literal path: first launch of the search kernel alone)
+    c.info.ms = ms; c.info.main_ms = ms_main; c.info.launches = c.launches;
+    publish(c.info);
+    drain.done = true;
+    return OK;
+}
 
+// (the call's events ride on its kernels: ev_start = start of the first descent launch, ev_ks / ev_ke = the first search launch)
+// first kernel of the call: rows padded to the row stride, the greedy descent of every query (pre[]), counters zeroed
+int DeviceIndex::SearchCall::descend(const float* d_queries, const RowFeed* feed) {
+    // two queries per wavefront where every list above the search layer fits a half's 16 row slots (hnsw_descend_pair_kernel)
+    const bool pair = ix.up_deg_max_ <= 16u && metric < KM_SIMD8_FIRST && !kn.no_pair_descent;
+    const size_t descend_lds = (pair ? 2u : 1u) * (size_t)tile_bytes + IDS_BYTES;
+    int per_cu = ix.descend_per_cu_[pair].load();
+    if (per_cu <= 0) {
+        HIP_TRY(ks.descend_occupancy(descend_lds, pair, &per_cu));
+        per_cu = std::max(1, per_cu);
+        ix.descend_per_cu_[pair].store(per_cu);
+    }
+    // one launch -- or, when the rows are still being gathered into pinned memory, one per chunk: the device reads chunk i
+    // across PCIe while the host fills chunk i + 1 (a few chunks: every launch costs a few microseconds of stream time)
+    const uint64_t chunk = feed ? std::max<uint64_t>(1, feed->chunk_rows) : nq;
+    for (uint64_t lo = 0; lo < nq; lo += chunk) {
+        const uint64_t hi = std::min(nq, lo + chunk);
+        if (feed) feed->fill(feed->ctx, lo, hi);
+        DescendArgs da{};
+        da.src = d_queries + lo * v.d;
+        da.qpad = w.qpad.as<float>() + lo * v.row_stride;
+        da.pre = w.pre.as<PreDescent>() + lo;
+        da.nq = (uint32_t)(hi - lo);
+        da.tile_bytes = tile_bytes;
+        da.nrm2 = static_cast<const double*>(ix.d_nrm2_);
+        da.ctrl = lo == 0 ? d_ctrl() : nullptr;
+        da.ctrl_words = 16;
+        da.pair = pair ? 1u : 0u;
+        const uint64_t waves = pair ? (hi - lo + 1) / 2 : hi - lo;
+        HIP_TRY(ks.launch_descend((uint32_t)std::min<uint64_t>(waves, (uint64_t)per_cu * (uint64_t)ix.num_cu_), stream, v, da,
+                                  LaunchEvents{lo == 0 ? w.ev_start : nullptr, nullptr}));
+    }
+    return OK;
+}
+
+// The whole call through the literal kernel, under the call's filter if it has one.  It reports one launch, which lasts from ev_ks
+// to ev_stop: every pass and the bitmaps of a filter set included.
+int DeviceIndex::SearchCall::literal_call(const CallFilter& filter) {
+    const uint32_t* d_allow = nullptr;
+    if (filter.filtered() && !filter.d_set) {
+        HIP_TRY(w.allow.ensure((uint64_t)((v.n + 31) / 32) * sizeof(uint32_t)));
+        HIP_TRY(launch_allow_bitmap(stream, v.origin_id, v.n, filter.d_allowed, filter.n_allowed, w.allow.as<uint32_t>()));
+        d_allow = w.allow.as<uint32_t>();
+    }
+    HIP_TRY(hipEventRecord(w.ev_ks, stream));
+    int rc = filter.d_set ? filter_set_search(*filter.d_set) : run_exact(nullptr, (uint32_t)nq, d_allow, &info.panics);
+    if (rc != OK) return rc;
+    HIP_TRY(hipEventRecord(w.ev_stop, stream));
+    HIP_TRY(wait_event(w.ev_stop));
+    main_end = w.ev_stop;
+    launches = 1;
+    return OK;
+}
+
+// What the one-query kernels (and the pair pass in front of them) start from: result slots, the visited tables' size, the work list.
+int DeviceIndex::SearchCall::plan() {
     HIP_TRY(w.tie.ensure(nq * sizeof(uint32_t)));
     HIP_TRY(w.retry[0].ensure(nq * sizeof(uint32_t)));
     HIP_TRY(w.retry[1].ensure(nq * sizeof(uint32_t)));
-
-    int slots = 1;
     while ((uint64_t)slots * 64 < ef) slots *= 2;
     if (slots == 8) slots = 16;  // kernels are instantiated for 1, 2, 4 and 16 result slots per lane
     // Lists of more than 64 ids (M > 32: none of BASELINE's configs) need a loop over the batches of a list; only the
     // 16-slot kernels carry it -- in the others the single batch is a compile-time fact, worth 1.5-4 % to every search.
-    if (v_.deg_stride > 64u) slots = 16;
-
+    if (v.deg_stride > 64u) slots = 16;
     // Visited-set sizing.  LDS per wavefront is what bounds occupancy, so the table is sized for the
     // typical query (ef x degree cells, ~2.4x the median number of visited points, measured); the few
     // per cent of queries that outgrow it move to the HBM bitmap inside the same launch.
-    const uint32_t idbits = std::max<uint32_t>(1u, ceil_log2(v_.n));
-    const uint64_t expect = ef * std::min<uint64_t>(v_.deg_stride, 64);
-    uint32_t tbits = std::min<uint32_t>(14u, std::max<uint32_t>(8u, ceil_log2(expect)));
+    idbits = std::max<uint32_t>(1u, ceil_log2(v.n));
+    const uint64_t expect = ef * std::min<uint64_t>(v.deg_stride, 64);
+    tbits = std::min<uint32_t>(14u, std::max<uint32_t>(8u, ceil_log2(expect)));
     {   // ... then follows what the previous batches with the same ef measured
-        std::lock_guard<std::mutex> g(meta_mu_);
-        if (adapt_ef_ == ef && adapt_tbits_ != 0) tbits = adapt_tbits_;
+        std::lock_guard<std::mutex> g(ix.meta_mu_);
+        if (ix.adapt_ef_ == ef && ix.adapt_tbits_ != 0) tbits = ix.adapt_tbits_;
     }
-    bool env_forced = false;
-    const Knobs& kn = knobs();  // (the environment was read once: search_device.hpp)
     if (kn.hash_bits >= 6 && kn.hash_bits <= 14) { tbits = (uint32_t)kn.hash_bits; env_forced = true; }  // tuning / test hook: initial table size
-    const uint32_t tbits_first = tbits;
-    const size_t lds_fixed = tile_bytes + IDS_BYTES;
-    int table = TABLE_LDS_CELL16;
-    bool grown = false;
+    tbits_first = tbits;
 
     // Batch scheduling: the searches run in descending order of the distance to the layer-0 entry point (the descent's
     // result), long searches first (DESIGN.md "scheduling").  Small batches skip it (one launch less, lowest latency).
     const bool scheduled = nq >= 256 && !kn.no_sched;
     if (scheduled) {
         HIP_TRY(w.order.ensure(nq * sizeof(uint32_t)));
-        HIP_TRY(kernel_set(kernel_metric()).launch_order(stream, w.pre.as<PreDescent>(), (uint32_t)nq, w.order.as<uint32_t>()));
+        HIP_TRY(ks.launch_order(stream, w.pre.as<PreDescent>(), (uint32_t)nq, w.order.as<uint32_t>()));
     }
-    uint32_t launches = 0, stop_recorded_after = ~0u;
-    uint32_t work = (uint32_t)nq;
-    uint32_t n_flagged = 0, n_literal = 0;
-    const uint32_t* qlist = scheduled ? w.order.as<uint32_t>() : nullptr;
-    int pingpong = 0;
-    bool all_done = false;
-    // ---- first pass with two queries per wavefront (hnsw_search_pair_kernel, search_pair.inc) where the index and the call allow it:
-    // ef <= 128 (4 result slots x 32 lanes), lists of <= 64 ids, 16-bit-cell tables, scalar arithmetic.  It answers every query that
-    // meets none of the three places where equal distances make the reference's answer depend on its heaps' order (DESIGN.md section
-    // 6); those come back on the retry list and go through the one-query kernels below (strict calls; lean calls flag them like the
-    // lean kernel does).  A visited set that outgrows its LDS table moves to an HBM bitmap slice inside the launch.
-    // Default (no HNSWGPU_PAIR_SEARCH): where it was measured to pay -- strict calls of tens of thousands of queries on short rows with
-    // DistCosine or DistDot (config 3 at 100 000 per call: 9.75 M against 7.93 M queries/s, config 3': 10.30 M against 9.45 M; both
-    // cross over at ~30 000 per call; at 10 000 the second launch for the tie queries costs more than the pass gains, rows of several
-    // 128-byte lines gain nothing: profiles/r06_pair_search/README.md).
-    const bool pair_auto = (kernel_metric() == DIST_COSINE || kernel_metric() == DIST_DOT) && v_.row_stride <= 32u && strict_ties &&
-                           nq >= PAIR_SEARCH_AUTO_MIN_QUERIES;
-    if (kn.pair_search > 0 || (kn.pair_search < 0 && pair_auto)) {
-        const int tbp = (int)tbits + kn.pair_tbits_delta;
-        const uint32_t tb = (uint32_t)std::max(6, std::min<int>(tbp, (int)std::min(14u, idbits + 3u)));
-        const bool ok = ef <= 128 && v_.deg_stride <= 64u && kernel_metric() < KM_SIMD8_FIRST && nq >= 512 && idbits >= tb - 3u && idbits - (tb - 3u) <= 13u &&
-                        idbits - (tb - 3u) >= 1u;
-        if (ok) {
-            const KernelSet& ks = kernel_set(kernel_metric());
-            SearchArgs a{};
-            a.tbits = tb;
+    qlist = scheduled ? w.order.as<uint32_t>() : nullptr;
+    return OK;
+}
+
+// ---- first pass with two queries per wavefront (hnsw_search_pair_kernel, search_pair.inc) where the index and the call allow it:
+// ef <= 128 (4 result slots x 32 lanes), lists of <= 64 ids, 16-bit-cell tables, scalar arithmetic.  It answers every query that
+// meets none of the three places where equal distances make the reference's answer depend on its heaps' order (DESIGN.md section
+// 6); those come back on the retry list and go through the one-query kernels below (strict calls; lean calls flag them like the
+// lean kernel does).  A visited set that outgrows its LDS table moves to an HBM bitmap slice inside the launch.
+// Default (no HNSWGPU_PAIR_SEARCH): where it was measured to pay -- strict calls of tens of thousands of queries on short rows with
+// DistCosine or DistDot (config 3 at 100 000 per call: 9.75 M against 7.93 M queries/s, config 3': 10.30 M against 9.45 M; both
+// cross over at ~30 000 per call; at 10 000 the second launch for the tie queries costs more than the pass gains, rows of several
+// 128-byte lines gain nothing: profiles/r06_pair_search/README.md).
+int DeviceIndex::SearchCall::pair_pass() {
+    const bool pair_auto = (metric == DIST_COSINE || metric == DIST_DOT) && v.row_stride <= 32u && strict_ties && nq >= PAIR_SEARCH_AUTO_MIN_QUERIES;
+    if (!(kn.pair_search > 0 || (kn.pair_search < 0 && pair_auto))) return OK;
+    const int tbp = (int)tbits + kn.pair_tbits_delta;
+    const uint32_t tb = (uint32_t)std::max(6, std::min<int>(tbp, (int)std::min(14u, idbits + 3u)));
+    const bool ok = ef <= 128 && v.deg_stride <= 64u && metric < KM_SIMD8_FIRST && nq >= 512 && idbits >= tb - 3u && idbits - (tb - 3u) <= 13u &&
+                    idbits - (tb - 3u) >= 1u;
+    if (!ok) return OK;
+    const size_t lds = pair_lds_bytes(tile_bytes, tb, (uint32_t)ef);
+    int per_cu = 0;
+    HIP_TRY(ks.pair_occupancy(lds, &per_cu));
+    if (per_cu < 1) return OK;
+    if (kn.pair_wg_per_cu > 0) per_cu = std::min(per_cu, kn.pair_wg_per_cu);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)per_cu * (uint64_t)ix.num_cu_, (nq + 1) / 2);  // (pairs of queries)
+    if (kn.trace_launch)
+        std::fprintf(stderr, "[hnswgpu launch] pair pass: %u queries, %d workgroups per CU, %zu bytes of LDS each, tables 2^%u cells\n",
+                     work, per_cu, lds, tb);
+    SearchArgs a = search_args(qlist, work);
+    a.tbits = tb;
+    a.restbits = idbits - (tb - 3u);
+    a.idbits = idbits;
+    a.retry_out = w.retry[pingpong].as<uint32_t>();
+    a.tie_list = w.tie.as<uint32_t>();
+    a.pair_ties_to_retry = strict_ties ? 1u : 0u;
+    {   // HBM bitmaps for the halves whose table fills up: two slices per workgroup, within the 4 GiB budget
+        a.bitmap_words = (v.n + 31) / 32;
+        const uint64_t slice = (uint64_t)a.bitmap_words * sizeof(uint32_t);
+        const uint64_t blocks = std::min<uint64_t>(2ull * grid, std::max<uint64_t>(2, (4ull << 30) / slice));
+        HIP_TRY(w.bitmap.ensure(blocks * slice));
+        a.bitmap = w.bitmap.as<uint32_t>();
+        a.bitmap_blocks = (uint32_t)blocks;
+    }
+    HIP_TRY(ks.launch_pair(grid, lds, stream, v, a, LaunchEvents{w.ev_ks, w.ev_ke}));
+    ++launches;
+    HIP_TRY(read_ctrl(SC_BYTES, true));
+    n_flagged = ctrl()[SC_FLAGGED];
+    info.pair_retries = ctrl()[SC_RETRY];
+    if (table != TABLE_GLOBAL_BITMAP && !env_forced) table_feedback();
+    all_done = ctrl()[SC_RETRY] == 0;
+    if (!all_done) {
+        work = ctrl()[SC_RETRY];
+        qlist = w.retry[pingpong].as<uint32_t>();
+        pingpong ^= 1;
+    }
+    return OK;
+}
+
+// LDS, visited table and resident workgroups of one launch of the one-query kernels: sets the table's kind (`table`) and the
+// fields of `a` that size the workgroup's LDS.
+int DeviceIndex::SearchCall::shape_launch(SearchArgs& a, LaunchShape& s) {
+    s.lds = tile_bytes + IDS_BYTES;
+    if (table != TABLE_GLOBAL_BITMAP) {
+        // buckets of 8 cells: the id's top (tb - 3) bits select the bucket, the cell keeps the other restbits bits
+        // next to a 2-bit bucket displacement and the valid bit (16-bit cells: restbits <= 13)
+        uint32_t tb = std::max(3u, std::min(tbits, idbits + 3u));
+        if (idbits - (tb - 3u) <= 13u) {
+            table = TABLE_LDS_CELL16;
             a.restbits = idbits - (tb - 3u);
-            a.idbits = idbits;
-            a.tile_bytes = tile_bytes;
-            a.nrm2 = static_cast<const double*>(d_nrm2_);
-            const size_t lds = pair_lds_bytes(tile_bytes, tb, (uint32_t)ef);
-            int per_cu = 0;
-            HIP_TRY(ks.pair_occupancy(lds, &per_cu));
-            if (per_cu >= 1) {
-                if (kn.pair_wg_per_cu > 0) per_cu = std::min(per_cu, kn.pair_wg_per_cu);
-                const uint64_t npairs = (nq + 1) / 2;
-                const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)per_cu * (uint64_t)num_cu_, npairs);
-                if (kn.trace_launch)
-                    std::fprintf(stderr, "[hnswgpu launch] pair pass: %u queries, %d workgroups per CU, %zu bytes of LDS each, tables 2^%u cells\n",
-                                 work, per_cu, lds, tb);
-                a.queries = w.qpad.as<float>();
-                a.qlist = qlist;
-                a.nq = work;
-                a.k = (uint32_t)k;
-                a.ef = (uint32_t)ef;
-                a.work_counter = static_cast<uint32_t*>(w.d_ctrl);
-                a.overflow_count = static_cast<uint32_t*>(w.d_ctrl) + 1;
-                a.retry_out = w.retry[pingpong].as<uint32_t>();
-                a.out_ids = d_out_ids;
-                a.out_dists = d_out_dists;
-                a.out_layer = d_out_layer;
-                a.out_rank = d_out_rank;
-                a.out_counts = d_out_counts;
-                a.id_stride = layout.id_stride;
-                a.dist_stride = layout.dist_stride;
-                a.count_stride = layout.count_stride;
-                a.stats = stats;
-                a.pre = w.pre.as<PreDescent>();
-                a.tie_list = w.tie.as<uint32_t>();
-                a.pair_ties_to_retry = strict_ties ? 1u : 0u;
-                {   // HBM bitmaps for the halves whose table fills up: two slices per workgroup, within the 4 GiB budget
-                    a.bitmap_words = (v_.n + 31) / 32;
-                    const uint64_t slice = (uint64_t)a.bitmap_words * sizeof(uint32_t);
-                    const uint64_t blocks = std::min<uint64_t>(2ull * grid, std::max<uint64_t>(2, (4ull << 30) / slice));
-                    HIP_TRY(w.bitmap.ensure(blocks * slice));
-                    a.bitmap = w.bitmap.as<uint32_t>();
-                    a.bitmap_blocks = (uint32_t)blocks;
-                }
-                HIP_TRY(ks.launch_pair(grid, lds, stream, v_, a, LaunchEvents{w.ev_ks, w.ev_ke}));
-                ++launches;
-                volatile uint32_t* ctrl = static_cast<volatile uint32_t*>(w.h_ctrl);
-                HIP_TRY(hipMemcpyAsync(w.h_ctrl, w.d_ctrl, 24, hipMemcpyDeviceToHost, stream));
-                HIP_TRY(hipEventRecord(w.ev_stop, stream));
-                stop_recorded_after = launches;
-                HIP_TRY(wait_stream(stream));
-                n_flagged = ctrl[4];
-                info.pair_retries = ctrl[1];
-                if (table != TABLE_GLOBAL_BITMAP && !env_forced) {  // table sizing feedback, as below
-                    uint32_t next = tbits_first;
-                    if ((uint64_t)ctrl[2] * 8 > nq && tbits_first < 14u) next = tbits_first + 1;
-                    else if ((uint64_t)ctrl[3] * 32 < nq && tbits_first > 8u) next = tbits_first - 1;
-                    std::lock_guard<std::mutex> g(meta_mu_);
-                    adapt_ef_ = ef;
-                    adapt_tbits_ = next;
-                }
-                if (ctrl[1] == 0) {
-                    all_done = true;
-                } else {
-                    work = ctrl[1];
-                    qlist = w.retry[pingpong].as<uint32_t>();
-                    pingpong ^= 1;
-                }
-            }
+            s.lds += (size_t)2 << tb;
+        } else {
+            table = TABLE_LDS_CELL32;
+            s.lds += (size_t)4 << tb;
         }
+        a.tbits = tb;
     }
+    a.idbits = idbits;
+    s.strict_kernel = strict_ties && table != TABLE_GLOBAL_BITMAP && !kn.no_inkernel;
+    if (slots <= (s.strict_kernel ? HNSW_MERGE_SMAX : HNSW_MERGE_LEAN_SMAX)) {  // merge_list's scatter buffer
+        a.merge_entries = (uint32_t)slots * 64u + 64u;
+        s.lds += (size_t)a.merge_entries * sizeof(hent_t);
+    }
+    s.per_cu = 0;
+    s.strict_cap = STRICT_WG_PER_CU;
+    if (kn.strict_wg_per_cu > 0) s.strict_cap = kn.strict_wg_per_cu;  // tuning hook (reported by HNSWGPU_TRACE_LAUNCH)
+    if (s.strict_kernel) {
+        // top levels of the (lazy) literal candidate heap, for the few pops that need it: 512 entries when that costs no
+        // resident wave (the strict kernel sits at 4 waves per SIMD by its registers, which leaves ~10 KB of LDS per
+        // wave), else 256 -- a replay touches the heap ~800 times per query, every level out of LDS is an L2 round trip
+        a.cand_lds = 256;
+        if (kn.cand_lds >= 0) {
+            a.cand_lds = (uint32_t)std::min(4096, kn.cand_lds);  // tuning hook
+        } else {
+            int occ256 = 0, occ512 = 0;
+            HIP_TRY(ks.occupancy(slots, table, true, s.lds + 256 * sizeof(hent_t), &occ256));
+            HIP_TRY(ks.occupancy(slots, table, true, s.lds + 512 * sizeof(hent_t), &occ512));
+            if (std::min(occ512, s.strict_cap) >= std::min(occ256, s.strict_cap)) a.cand_lds = 512;
+        }
+        s.lds += (size_t)a.cand_lds * sizeof(hent_t);
+    }
+    HIP_TRY(ks.occupancy(slots, table, s.strict_kernel, s.lds, &s.per_cu));
+    if (s.per_cu < 1) s.per_cu = 1;
+    // A strict launch ends with its longest search -- normally one that replayed its heap-operation log -- and a fifth wave
+    // per SIMD slows every expansion of it: with the descent out of the kernel the strict kernel needs 89 VGPRs and would
+    // fit 20 workgroups per CU; measured (config 2, one box) 7.63 M queries/s at 20, 8.49 M at 16.  The lean kernel gains
+    // from its 20 (9.7 M) and keeps them.
+    if (s.strict_kernel) s.per_cu = std::min(s.per_cu, s.strict_cap);
+    if (kn.waves_per_cu > 0) s.per_cu = std::max(1, std::min(s.per_cu, kn.waves_per_cu));  // tuning hook
+    return OK;
+}
+
+// The one-query kernels on what is left of the batch, launched again for as long as a launch hands queries back: first with
+// larger tables, then with the visited sets in HBM bitmaps.
+int DeviceIndex::SearchCall::relaunch_loop() {
     while (!all_done) {
-        SearchArgs a{};
-        size_t lds = lds_fixed;
-        if (table != TABLE_GLOBAL_BITMAP) {
-            // buckets of 8 cells: the id's top (tb - 3) bits select the bucket, the cell keeps the other restbits bits
-            // next to a 2-bit bucket displacement and the valid bit (16-bit cells: restbits <= 13)
-            uint32_t tb = std::max(3u, std::min(tbits, idbits + 3u));
-            if (idbits - (tb - 3u) <= 13u) {
-                table = TABLE_LDS_CELL16;
-                a.restbits = idbits - (tb - 3u);
-                lds += (size_t)2 << tb;
-            } else {
-                table = TABLE_LDS_CELL32;
-                lds += (size_t)4 << tb;
-            }
-            a.tbits = tb;
-        }
-        a.tile_bytes = tile_bytes;
-        a.nrm2 = static_cast<const double*>(d_nrm2_);
-        a.idbits = idbits;
-        const KernelSet& ks = kernel_set(kernel_metric());
-        const bool strict_kernel = strict_ties && table != TABLE_GLOBAL_BITMAP && !kn.no_inkernel;
-        if (slots <= (strict_kernel ? HNSW_MERGE_SMAX : HNSW_MERGE_LEAN_SMAX)) {  // merge_list's scatter buffer
-            a.merge_entries = (uint32_t)slots * 64u + 64u;
-            lds += (size_t)a.merge_entries * sizeof(hent_t);
-        }
-        int per_cu = 0;
-        int strict_cap = STRICT_WG_PER_CU;
-        if (kn.strict_wg_per_cu > 0) strict_cap = kn.strict_wg_per_cu;  // tuning hook (reported by HNSWGPU_TRACE_LAUNCH)
-        if (strict_kernel) {
-            // top levels of the (lazy) literal candidate heap, for the few pops that need it: 512 entries when that costs no
-            // resident wave (the strict kernel sits at 4 waves per SIMD by its registers, which leaves ~10 KB of LDS per
-            // wave), else 256 -- a replay touches the heap ~800 times per query, every level out of LDS is an L2 round trip
-            a.cand_lds = 256;
-            if (kn.cand_lds >= 0) {
-                a.cand_lds = (uint32_t)std::min(4096, kn.cand_lds);  // tuning hook
-            } else {
-                int occ256 = 0, occ512 = 0;
-                HIP_TRY(ks.occupancy(slots, table, true, lds + 256 * sizeof(hent_t), &occ256));
-                HIP_TRY(ks.occupancy(slots, table, true, lds + 512 * sizeof(hent_t), &occ512));
-                if (std::min(occ512, strict_cap) >= std::min(occ256, strict_cap)) a.cand_lds = 512;
-            }
-            lds += (size_t)a.cand_lds * sizeof(hent_t);
-        }
-        HIP_TRY(ks.occupancy(slots, table, strict_kernel, lds, &per_cu));
-        if (per_cu < 1) per_cu = 1;
-        // A strict launch ends with its longest search -- normally one that replayed its heap-operation log -- and a fifth wave
-        // per SIMD slows every expansion of it: with the descent out of the kernel the strict kernel needs 89 VGPRs and would
-        // fit 20 workgroups per CU; measured (config 2, one box) 7.63 M queries/s at 20, 8.49 M at 16.  The lean kernel gains
-        // from its 20 (9.7 M) and keeps them.
-        if (strict_kernel) per_cu = std::min(per_cu, strict_cap);
-        if (kn.waves_per_cu > 0) per_cu = std::max(1, std::min(per_cu, kn.waves_per_cu));  // tuning hook
-        uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)per_cu * (uint64_t)num_cu_, work);
+        SearchArgs a = search_args(qlist, work);
+        LaunchShape s{};
+        int rc = shape_launch(a, s);
+        if (rc != OK) return rc;
+        uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)s.per_cu * (uint64_t)ix.num_cu_, work);
         if (kn.trace_launch)  // diagnostics: what bounds the resident workgroups of this launch
             std::fprintf(stderr, "[hnswgpu launch] %u queries, %d workgroups per CU (strict cap %d), %zu bytes of LDS each (literal heap: %u entries), table 2^%u cells, strict %d, work list %s, slots %d, visited set %s\n",
-                         work, per_cu, strict_cap, lds, a.cand_lds, a.tbits, (int)strict_kernel,
+                         work, s.per_cu, s.strict_cap, s.lds, a.cand_lds, a.tbits, (int)s.strict_kernel,
                          qlist ? "sorted" : "input order", slots,
                          table == TABLE_LDS_CELL16 ? "cell16" : table == TABLE_LDS_CELL32 ? "cell32" : "bitmap");
-        a.queries = w.qpad.as<float>();
-        a.qlist = qlist;
-        a.nq = work;
-        a.k = (uint32_t)k;
-        a.ef = (uint32_t)ef;
-        a.work_counter = static_cast<uint32_t*>(w.d_ctrl);
-        a.overflow_count = static_cast<uint32_t*>(w.d_ctrl) + 1;
         a.retry_out = w.retry[pingpong].as<uint32_t>();
-        a.out_ids = d_out_ids;
-        a.out_dists = d_out_dists;
-        a.out_layer = d_out_layer;
-        a.out_rank = d_out_rank;
-        a.out_counts = d_out_counts;
-        a.id_stride = layout.id_stride;
-        a.dist_stride = layout.dist_stride;
-        a.count_stride = layout.count_stride;
-        a.stats = stats;
-        a.pre = w.pre.as<PreDescent>();
         {
             // HBM bitmaps for the in-launch fallback: one slice per workgroup, within a 4 GiB budget
-            a.bitmap_words = (v_.n + 31) / 32;
+            a.bitmap_words = (v.n + 31) / 32;
             const uint64_t slice = (uint64_t)a.bitmap_words * sizeof(uint32_t);
             uint64_t blocks = std::min<uint64_t>(grid, std::max<uint64_t>(1, (4ull << 30) / slice));
             if (table == TABLE_GLOBAL_BITMAP) grid = (uint32_t)blocks;  // every workgroup needs one
@@ -1023,7 +1049,7 @@ int DeviceIndex::search_device_impl(const float* d_queries, uint64_t nq, uint64_
             a.bitmap_blocks = (uint32_t)blocks;
         }
         a.tie_list = w.tie.as<uint32_t>();
-        if (strict_kernel) {
+        if (s.strict_kernel) {
             // per-workgroup scratch: the heap-operation log, and the part of the literal candidate heap beyond LDS
             const uint32_t cap = 4096;
             const uint64_t need = (uint64_t)grid * cap * sizeof(hent_t);
@@ -1036,30 +1062,17 @@ int DeviceIndex::search_device_impl(const float* d_queries, uint64_t nq, uint64_
             if (kn.exact_first >= 0) a.exact_first = kn.exact_first != 0 ? 1u : 0u;  // test hook
         }
         // (the first launch finds the counters zeroed by the descent kernel; the flagged list spans relaunches)
-        if (launches != 0) HIP_TRY(hipMemsetAsync(w.d_ctrl, 0, 16, stream));
-        HIP_TRY(ks.launch_search(slots, table, strict_kernel, grid, lds, stream, v_, a,
+        if (launches != 0) HIP_TRY(hipMemsetAsync(w.d_ctrl, 0, CTRL_LAUNCH_BYTES, stream));
+        HIP_TRY(ks.launch_search(slots, table, s.strict_kernel, grid, s.lds, stream, v, a,
                                  launches == 0 ? LaunchEvents{w.ev_ks, w.ev_ke} : LaunchEvents{}));
         ++launches;
-        volatile uint32_t* ctrl = static_cast<volatile uint32_t*>(w.h_ctrl);  // pinned: a true asynchronous copy
-        HIP_TRY(hipMemcpyAsync(w.h_ctrl, w.d_ctrl, 24, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipEventRecord(w.ev_stop, stream));  // the end of the call unless another launch follows (the usual case: one wait)
-        stop_recorded_after = launches;
-        HIP_TRY(wait_stream(stream));
-        n_flagged = ctrl[4];     // not resolved in the launch (cumulative over relaunches)
-        n_literal += ctrl[5];    // resolved with the literal heaps inside the launch
-        if (launches == 1 && table != TABLE_GLOBAL_BITMAP && !env_forced && nq >= 256) {
-            // Table sizing feedback for the next batch: grow when more than ~1 query in 8 had to move to the
-            // HBM bitmap, shrink when a half-size table would have overflowed for fewer than 1 in 32.
-            uint32_t next = tbits_first;
-            if ((uint64_t)ctrl[2] * 8 > nq && tbits_first < 14u) next = tbits_first + 1;
-            else if ((uint64_t)ctrl[3] * 32 < nq && tbits_first > 8u) next = tbits_first - 1;
-            std::lock_guard<std::mutex> g(meta_mu_);
-            adapt_ef_ = ef;
-            adapt_tbits_ = next;
-        }
-        if (ctrl[1] == 0) break;
+        HIP_TRY(read_ctrl(SC_BYTES, true));
+        n_flagged = ctrl()[SC_FLAGGED];     // not resolved in the launch (cumulative over relaunches)
+        n_literal += ctrl()[SC_LITERAL];    // resolved with the literal heaps inside the launch
+        if (launches == 1 && table != TABLE_GLOBAL_BITMAP && !env_forced && nq >= 256) table_feedback();
+        if (ctrl()[SC_RETRY] == 0) break;
         // some queries visited more points than the table holds and had no bitmap slice: rerun only those
-        work = ctrl[1];
+        work = ctrl()[SC_RETRY];
         qlist = w.retry[pingpong].as<uint32_t>();
         pingpong ^= 1;
         if (table == TABLE_GLOBAL_BITMAP) { err = "internal error: bitmap visited set reported an overflow"; return ERR_DEVICE; }
@@ -1070,11 +1083,15 @@ int DeviceIndex::search_device_impl(const float* d_queries, uint64_t nq, uint64_
             table = TABLE_GLOBAL_BITMAP;
         }
     }
+    return OK;
+}
+
+// Behind the last launch: the queries still flagged through the literal kernel (strict calls), and ev_stop behind them.
+int DeviceIndex::SearchCall::rerun_ties() {
     info.ties = n_flagged + n_literal;
     if (strict_ties && n_flagged > 0) {
         // the flagged queries again, with both heaps literal from the first operation on
-        int rc = run_exact(w, w.qpad.as<float>(), w.tie.as<uint32_t>(), n_flagged, k, ef, nullptr, d_out_ids, d_out_dists, d_out_layer,
-                           d_out_rank, d_out_counts, stats, stream, nullptr, err, layout);
+        int rc = run_exact(w.tie.as<uint32_t>(), n_flagged, nullptr, nullptr);
         if (rc != OK) return rc;
         ++launches;
     }
@@ -1082,14 +1099,6 @@ int DeviceIndex::search_device_impl(const float* d_queries, uint64_t nq, uint64_
         HIP_TRY(hipEventRecord(w.ev_stop, stream));
         HIP_TRY(wait_event(w.ev_stop));
     }
-    float ms = 0.f, ms_main = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, w.ev_start, w.ev_stop));
-    HIP_TRY(hipEventElapsedTime(&ms_main, w.ev_ks, w.ev_ke));  // first launch of the search kernel alone
-    info.ms = ms;
-    info.main_ms = ms_main;
-    info.launches = launches;
-    publish();
-    drain.done = true;
     return OK;
 }
 
@@ -1253,7 +1262,6 @@ int DeviceIndex::search_host_staged_impl(const float* queries, const float* cons
         HIP_TRY(hipMemcpyAsync(w.set_of.p, set->filter_of, nq * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
         dset = FilterSet{w.allowed_ids.as<uint64_t>(), w.set_offsets.as<uint64_t>(), set->n_filters, w.set_of.as<uint32_t>()};
     }
-    const FilterSet* d_set = set ? &dset : nullptr;
     // how many threads, how the work is cut: ~64 KB per gather task, a few chunks (every chunk is a launch of the descent kernel)
     const uint64_t total_bytes = q_bytes + o_ans_end;
     // (measured, tools/host_call_sweep.py: 2 chunks beat 4 and 1 -- every chunk is a launch of the descent kernel, whose reads across
@@ -1294,6 +1302,13 @@ int DeviceIndex::search_host_staged_impl(const float* queries, const float* cons
                      h.us_gather += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
                  },
                  &hc, hc.chunk_rows};
+    // where the kernels write: into the sink's own records, or into the arena the sink unpacks
+    const AnswerBufs out = in_place ? AnswerBufs{reinterpret_cast<uint64_t*>(in_sink(direct.ids)), reinterpret_cast<float*>(in_sink(direct.dists)), nullptr, nullptr,
+                                                 reinterpret_cast<uint32_t*>(in_sink(direct.counts)), nullptr, direct.layout}
+                                    : AnswerBufs{reinterpret_cast<uint64_t*>(dout + o_ids), reinterpret_cast<float*>(dout + o_dists), dout + o_layer,
+                                                 reinterpret_cast<int32_t*>(dout + o_rank), reinterpret_cast<uint32_t*>(dout + o_cnt),
+                                                 want_status ? reinterpret_cast<uint32_t*>(dout + o_stat) : nullptr, OutLayout{}};
+    const CallFilter filter{dallowed, filtered ? n_allowed : 0, set ? &dset : nullptr};
     int rc = OK;
     double us_search = 0.;
     const std::thread::id caller = std::this_thread::get_id();
@@ -1302,15 +1317,7 @@ int DeviceIndex::search_host_staged_impl(const float* queries, const float* cons
         if (std::this_thread::get_id() == caller && !main_taken.exchange(true)) {
             // the caller: the device side of the call (its launches wait for the chunks), then its share of the unpacking
             const auto t_search = std::chrono::steady_clock::now();
-            if (in_place)
-                rc = search_device_impl(static_cast<const float*>(w.pin_in.dev), nq, d, k, ef, reinterpret_cast<uint64_t*>(in_sink(direct.ids)),
-                                        reinterpret_cast<float*>(in_sink(direct.dists)), nullptr, nullptr, reinterpret_cast<uint32_t*>(in_sink(direct.counts)),
-                                        nullptr, stream, dallowed, filtered ? n_allowed : 0, d_set, info, err, &feed, direct.layout);
-            else
-                rc = search_device_impl(static_cast<const float*>(w.pin_in.dev), nq, d, k, ef, reinterpret_cast<uint64_t*>(dout + o_ids),
-                                        reinterpret_cast<float*>(dout + o_dists), dout + o_layer, reinterpret_cast<int32_t*>(dout + o_rank),
-                                        reinterpret_cast<uint32_t*>(dout + o_cnt), want_status ? reinterpret_cast<uint32_t*>(dout + o_stat) : nullptr,
-                                        stream, dallowed, filtered ? n_allowed : 0, d_set, info, err, &feed, OutLayout{});
+            rc = search_device_impl(static_cast<const float*>(w.pin_in.dev), nq, d, k, ef, out, stream, filter, info, err, &feed);
             us_search = since(t_search);
             // (search_device returns with the stream idle: the answers are in the arena -- or the call failed, and whatever
             // it left in flight is waited for by `drain`; the gather is then finished by nobody, which is fine)

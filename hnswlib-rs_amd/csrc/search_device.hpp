@@ -209,19 +209,11 @@ private:
     Workspace* acquire(std::string& err);
     void release_ws(Workspace* w);
     void release();
-    int run_exact(Workspace& w, const float* d_qpad, const uint32_t* d_qlist, uint32_t nq, uint64_t k, uint64_t ef,
-                  const uint32_t* d_allow, uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer,
-                  int32_t* d_out_rank, uint32_t* d_out_counts, uint32_t* stats, void* stream, uint32_t* panics,
-                  std::string& err, OutLayout layout, const uint32_t* d_slot_of = nullptr);
-    // what search_device / search_host_staged / search_host and their filter-set counterparts share: d_set / set == nullptr is the
-    // public call of that name
-    int search_device_impl(const float* d_queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef, uint64_t* d_out_ids,
-                           float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, uint32_t* d_stats,
-                           void* stream, const uint64_t* d_allowed, uint64_t n_allowed, const FilterSet* d_set, CallInfo* info,
-                           std::string& err, const RowFeed* feed, OutLayout layout);
-    int filter_set_search(Workspace& w, const FilterSet& d_set, uint32_t nq, uint64_t k, uint64_t ef, uint64_t* d_out_ids, float* d_out_dists,
-                          uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, uint32_t* stats, void* stream, uint32_t* panics,
-                          std::string& err, OutLayout layout);
+    // what search_device / search_host_staged / search_host and their filter-set counterparts share (search_device.hip): where a
+    // call's answers go, its filter (none, one id vector, a FilterSet), and the steps of one call with what they hand to each other
+    struct AnswerBufs; struct CallFilter; struct SearchCall;
+    int search_device_impl(const float* d_queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef, const AnswerBufs& out, void* stream,
+                           const CallFilter& filter, CallInfo* info, std::string& err, const RowFeed* feed);
     int search_host_staged_impl(const float* queries, const float* const* rows, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef,
                                 const uint64_t* allowed, uint64_t n_allowed, bool filtered, const FilterSet* set, bool want_status,
                                 const AnswerSink& sink, CallInfo* info, std::string& err);
