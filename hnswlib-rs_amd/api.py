@@ -24,6 +24,49 @@ from . import _native as N
 Neighbour = namedtuple("Neighbour", ["d_id", "distance", "p_id"])  # p_id = (layer, rank)
 
 
+def _recall(got, exact):
+    """(by distance, by id) of the answers `got` against the exact answers `exact` (Hnsw.recall_flat has the definition)"""
+    total = int(exact.counts.sum())
+    if total == 0:
+        return 1.0, 1.0
+    by_dist = by_id = 0
+    for q in range(len(exact.counts)):
+        ce, cg = int(exact.counts[q]), int(got.counts[q])
+        if ce == 0:
+            continue
+        by_dist += int(np.count_nonzero(got.dists[q, :cg] <= exact.dists[q, ce - 1]))
+        by_id += len(np.intersect1d(got.ids[q, :cg], exact.ids[q, :ce]))
+    return by_dist / total, by_id / total
+
+
+def _pack_filter_set(datas, filters, filter_of):
+    """The arguments of the filter-set calls, checked and packed: the (nq, d) f32 matrix, the filters' ids behind one another
+    with their CSR offsets, one u32 filter index per query (filter_of=None: one filter per query in order)."""
+    datas = np.ascontiguousarray(datas, dtype=np.float32)
+    if datas.ndim != 2:
+        raise HnswError(N.ERR_ARG, "datas must be a (nq, d) matrix")
+    nq, d = datas.shape
+    filters = [np.ascontiguousarray(f, dtype=np.uint64).reshape(-1) for f in filters]
+    if filter_of is None:
+        if len(filters) != nq:
+            raise HnswError(N.ERR_ARG, f"filter_of=None means one filter per query: {len(filters)} filters for {nq} queries")
+        filter_of = np.arange(nq, dtype=np.uint32)
+    else:
+        fo = np.asarray(filter_of)
+        if fo.shape != (nq,):
+            raise HnswError(N.ERR_ARG, "filter_of must hold one filter index per query")
+        if nq and (fo.min() < 0 or fo.max() > 0xFFFFFFFF):
+            raise HnswError(N.ERR_ARG, "filter_of holds an index that names no filter")
+        filter_of = np.ascontiguousarray(fo, dtype=np.uint32)
+    offsets = np.zeros(len(filters) + 1, np.uint64)
+    if filters:
+        np.cumsum([len(f) for f in filters], out=offsets[1:])
+    flat = np.concatenate(filters) if filters else np.zeros(0, np.uint64)
+    if len(flat) == 0:
+        flat = np.zeros(1, np.uint64)  # (never read: every filter is empty)
+    return datas, flat, offsets, filter_of
+
+
 class HnswError(RuntimeError):
     """anyhow::Error analogue: carries the status code of the failing C-ABI call."""
 
@@ -250,28 +293,8 @@ class Hnsw:
         each query naming its own.  filters: a sequence of SORTED id arrays (an empty one allows nothing); filter_of: one index
         into it per query, or None for one filter per query in order (len(filters) == nq).  Rows on which the reference panics
         come back with count 0 and status 1."""
-        datas = np.ascontiguousarray(datas, dtype=np.float32)
-        if datas.ndim != 2:
-            raise HnswError(N.ERR_ARG, "datas must be a (nq, d) matrix")
+        datas, flat, offsets, filter_of = _pack_filter_set(datas, filters, filter_of)
         nq, d = datas.shape
-        filters = [np.ascontiguousarray(f, dtype=np.uint64).reshape(-1) for f in filters]
-        if filter_of is None:
-            if len(filters) != nq:
-                raise HnswError(N.ERR_ARG, f"filter_of=None means one filter per query: {len(filters)} filters for {nq} queries")
-            filter_of = np.arange(nq, dtype=np.uint32)
-        else:
-            fo = np.asarray(filter_of)
-            if fo.shape != (nq,):
-                raise HnswError(N.ERR_ARG, "filter_of must hold one filter index per query")
-            if nq and (fo.min() < 0 or fo.max() > 0xFFFFFFFF):
-                raise HnswError(N.ERR_ARG, "filter_of holds an index that names no filter")
-            filter_of = np.ascontiguousarray(fo, dtype=np.uint32)
-        offsets = np.zeros(len(filters) + 1, np.uint64)
-        if filters:
-            np.cumsum([len(f) for f in filters], out=offsets[1:])
-        flat = np.concatenate(filters) if filters else np.zeros(0, np.uint64)
-        if len(flat) == 0:
-            flat = np.zeros(1, np.uint64)  # (never read: every filter is empty)
         ids = np.zeros((nq, knbn), np.uint64)
         dists = np.zeros((nq, knbn), np.float32)
         layers = np.zeros((nq, knbn), np.uint8)
@@ -280,7 +303,7 @@ class Hnsw:
         status = np.zeros(nq, np.uint8)
         if self._h is None:  # empty index => empty answers (src/hnsw.rs:1498-1503)
             return BatchResult(ids, dists, layers, ranks, counts, status)
-        _check(self._lib.hnswgpu_search_batch_filter_set(self._h, _p(datas), nq, d, knbn, ef, _p(flat), _p(offsets), len(filters),
+        _check(self._lib.hnswgpu_search_batch_filter_set(self._h, _p(datas), nq, d, knbn, ef, _p(flat), _p(offsets), len(offsets) - 1,
                                                          _p(filter_of), _p(ids), _p(dists), _p(layers), _p(ranks), _p(counts),
                                                          _p(status)))
         return BatchResult(ids, dists, layers, ranks, counts, status)
@@ -332,6 +355,26 @@ class Hnsw:
         """exact_search_flat as Vec<Vec<Neighbour>> in input order."""
         return self.exact_search_flat(datas, knbn, allowed_ids).to_neighbours()
 
+    def exact_search_filters_flat(self, datas, knbn, filters, filter_of=None):
+        """exact_search_flat for a set of filters, each query naming its own: row q is exact_search_flat(datas[q], knbn,
+        filters[filter_of[q]]) -- the ground truth of parallel_search_filters_flat, whose `filters` / `filter_of` these are."""
+        datas, flat, offsets, filter_of = _pack_filter_set(datas, filters, filter_of)
+        nq, d = datas.shape
+        ids = np.zeros((nq, knbn), np.uint64)
+        dists = np.zeros((nq, knbn), np.float32)
+        layers = np.zeros((nq, knbn), np.uint8)
+        ranks = np.zeros((nq, knbn), np.int32)
+        counts = np.zeros(nq, np.uint32)
+        if self._h is None:
+            return BatchResult(ids, dists, layers, ranks, counts)
+        _check(self._lib.hnswgpu_exact_search_batch_filter_set(self._h, _p(datas), nq, d, knbn, _p(flat), _p(offsets), len(offsets) - 1,
+                                                               _p(filter_of), _p(ids), _p(dists), _p(layers), _p(ranks), _p(counts)))
+        return BatchResult(ids, dists, layers, ranks, counts)
+
+    def exact_search_filters(self, datas, knbn, filters, filter_of=None):
+        """exact_search_filters_flat as Vec<Vec<Neighbour>> in input order."""
+        return self.exact_search_filters_flat(datas, knbn, filters, filter_of).to_neighbours()
+
     def recall_flat(self, datas, knbn, ef, allowed_ids=None):
         """The two recalls the reference's examples print (examples/ann-sift1m-128-euclidean.rs:172-186), for this index's
         own search (filtered by allowed_ids if given) against the exact answer: (by distance, by id).
@@ -340,17 +383,15 @@ class Hnsw:
         exact = self.exact_search_flat(datas, knbn, allowed_ids)
         got = self.parallel_search_flat(datas, knbn, ef) if allowed_ids is None else \
             self.parallel_search_filter_flat(datas, knbn, ef, allowed_ids)
-        total = int(exact.counts.sum())
-        if total == 0:
-            return 1.0, 1.0
-        by_dist = by_id = 0
-        for q in range(len(exact.counts)):
-            ce, cg = int(exact.counts[q]), int(got.counts[q])
-            if ce == 0:
-                continue
-            by_dist += int(np.count_nonzero(got.dists[q, :cg] <= exact.dists[q, ce - 1]))
-            by_id += len(np.intersect1d(got.ids[q, :cg], exact.ids[q, :ce]))
-        return by_dist / total, by_id / total
+        return _recall(got, exact)
+
+    def recall_filters_flat(self, datas, knbn, ef, filters, filter_of=None):
+        """recall_flat for a set of filters, each query naming its own: parallel_search_filters_flat against
+        exact_search_filters_flat, (by distance, by id).  A row on which the reference panics (status 1, count 0) has found
+        nothing."""
+        exact = self.exact_search_filters_flat(datas, knbn, filters, filter_of)
+        got = self.parallel_search_filters_flat(datas, knbn, ef, filters, filter_of)
+        return _recall(got, exact)
 
     # AnnT (src/api.rs:13-38)
     def search_neighbours(self, data, knbn, ef_s):

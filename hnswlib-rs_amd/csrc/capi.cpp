@@ -764,6 +764,117 @@ int hnswgpu_search_batch_filter_set_device(const hnswgpu_index* cidx, const floa
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
+// ---- exact k-NN under a filter set: the ground truth of hnswgpu_search_batch_filter_set (exact_knn.hip holds the device side)
+extern "C++" {
+namespace hnswgpu {
+__attribute__((weak)) int exact_filter_set_host(const DeviceIndex&, const std::vector<uint64_t>&, const float*, uint64_t, uint64_t, uint64_t,
+                                                const FilterSet&, uint64_t*, float*, uint8_t*, int32_t*, uint32_t*, std::string&);
+__attribute__((weak)) int exact_filter_set_device(const DeviceIndex&, const std::vector<uint64_t>&, const float*, uint64_t, uint64_t, uint64_t,
+                                                  const FilterSet&, uint64_t*, float*, uint8_t*, int32_t*, uint32_t*, void*, std::string&);
+}  // namespace hnswgpu
+}  // extern "C++"
+// what both entries can check of the set without reading it, then (behind the host entry's reading checks) the checks of
+// hnswgpu_exact_search_batch: k, d, the arithmetic.  The handle's lock is held (shared) for the second part.
+static int exact_filter_set_shape(const void* queries, uint64_t nq, const void* filter_offsets, uint64_t n_filters, const void* filter_of,
+                                  const void* out_ids, const void* out_dists, const void* out_counts, const char* unfiltered) {
+    if (nq != 0 && (!queries || !out_ids || !out_dists || !out_counts)) return fail(HNSWGPU_ERR_ARG, "null buffer");
+    if (nq != 0 && !filter_of) return fail(HNSWGPU_ERR_ARG, "null filter_of: every query names its filter");
+    if (n_filters != 0 && !filter_offsets) return fail(HNSWGPU_ERR_ARG, "null filter_offsets");
+    if (n_filters == 0 && nq != 0)
+        return fail(HNSWGPU_ERR_ARG, std::string("a filter set without filters: n_filters is 0 (an unfiltered batch is ") + unfiltered + ")");
+    if (n_filters > 0xFFFFFFFFull) return fail(HNSWGPU_ERR_ARG, "too many filters: filter_of is 32 bits wide");
+    return HNSWGPU_OK;
+}
+static int exact_filter_set_call(const hnswgpu_index* idx, uint64_t nq, uint64_t d, uint64_t k) {
+    const uint64_t dim = idx->builder ? idx->builder->dimension() : (idx->flat ? idx->flat->dimension : 0);
+    if (k == 0) return fail(HNSWGPU_ERR_ARG, "knbn must be > 0");
+    if (k > 4096) return fail(HNSWGPU_ERR_ARG, "exact search: knbn above 4096");
+    if (nq > 0xFFFFFFF0ull) return fail(HNSWGPU_ERR_ARG, "too many queries in one batch");
+    if (dim != 0 && d != dim) return fail(HNSWGPU_ERR_ARG, "query dimension differs from the index dimension");
+    if (idx->arithmetic != HNSWGPU_ARITH_SCALAR)
+        return fail(HNSWGPU_ERR_ARG, "exact search answers in the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
+    return HNSWGPU_OK;
+}
+
+int hnswgpu_exact_search_batch_filter_set(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, uint64_t k,
+                                          const uint64_t* filter_ids, const uint64_t* filter_offsets, uint64_t n_filters,
+                                          const uint32_t* filter_of, uint64_t* out_ids, float* out_dists, uint8_t* out_layer,
+                                          int32_t* out_rank, uint32_t* out_counts) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    int rc = exact_filter_set_shape(queries, nq, filter_offsets, n_filters, filter_of, out_ids, out_dists, out_counts, "hnswgpu_exact_search_batch");
+    if (rc != HNSWGPU_OK) return rc;
+    if (n_filters != 0) {
+        if (filter_offsets[0] != 0) return fail(HNSWGPU_ERR_ARG, "filter_offsets must start at 0");
+        for (uint64_t f = 0; f < n_filters; ++f)
+            if (filter_offsets[f] > filter_offsets[f + 1])
+                return fail(HNSWGPU_ERR_ARG, "filter_offsets must ascend: filter_offsets[" + std::to_string(f + 1) + "] is below its predecessor");
+        if (filter_offsets[n_filters] != 0 && !filter_ids) return fail(HNSWGPU_ERR_ARG, "null filter_ids");
+        for (uint64_t f = 0; f < n_filters; ++f)  // `impl FilterT for Vec<usize>` is a binary search: every vector must be sorted
+            for (uint64_t i = filter_offsets[f] + 1; i < filter_offsets[f + 1]; ++i)
+                if (filter_ids[i - 1] > filter_ids[i])
+                    return fail(HNSWGPU_ERR_ARG, "the id vector of filter " + std::to_string(f) + " is not sorted ascending");
+    }
+    for (uint64_t q = 0; q < nq; ++q)
+        if (filter_of[q] >= n_filters)
+            return fail(HNSWGPU_ERR_ARG, "filter_of[" + std::to_string(q) + "] = " + std::to_string(filter_of[q]) + " names no filter (n_filters = " +
+                        std::to_string(n_filters) + ")");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    rc = exact_filter_set_call(idx, nq, d, k);
+    if (rc != HNSWGPU_OK) return rc;
+    const bool empty = idx->builder ? idx->builder->nb_point() == 0 : (!idx->flat || idx->flat->n == 0);
+    if (empty) {  // no point: every answer is empty
+        if (nq != 0) {
+            std::memset(out_counts, 0, nq * sizeof(uint32_t));
+            std::memset(out_ids, 0, nq * k * sizeof(uint64_t));
+            std::memset(out_dists, 0, nq * k * sizeof(float));
+            if (out_layer) std::memset(out_layer, 0, nq * k);
+            if (out_rank) std::memset(out_rank, 0, nq * k * sizeof(int32_t));
+        }
+        return HNSWGPU_OK;
+    }
+    if (nq == 0) return HNSWGPU_OK;
+    if (!hnswgpu::exact_filter_set_host) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = primary_replica(idx, sl, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    const FilterSet set{filter_ids, filter_offsets, n_filters, filter_of};
+    rc = hnswgpu::exact_filter_set_host(*dev, idx->flat->origin_id, queries, nq, d, k, set, out_ids, out_dists, out_layer, out_rank, out_counts, err);
+    if (rc != OK) return fail(rc, err);
+    return HNSWGPU_OK;
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswgpu_exact_search_batch_filter_set_device(const hnswgpu_index* cidx, const float* d_queries, uint64_t nq, uint64_t d, uint64_t k,
+                                                 const uint64_t* d_filter_ids, const uint64_t* d_filter_offsets, uint64_t n_filters,
+                                                 const uint32_t* d_filter_of, uint64_t* d_out_ids, float* d_out_dists,
+                                                 uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, void* stream) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    int rc = exact_filter_set_shape(d_queries, nq, d_filter_offsets, n_filters, d_filter_of, d_out_ids, d_out_dists, d_out_counts,
+                                    "hnswgpu_exact_search_batch_device");
+    if (rc != HNSWGPU_OK) return rc;
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    rc = exact_filter_set_call(idx, nq, d, k);
+    if (rc != HNSWGPU_OK) return rc;
+    if (nq == 0) return HNSWGPU_OK;
+    if (!hnswgpu::exact_filter_set_device) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = idx->primary >= 0 ? idx->replica(idx->primary) : nullptr;
+    if (!dev || idx->dev_stale || idx->flat_stale || !idx->flat)
+        return fail(HNSWGPU_ERR_DEVICE, "index is not resident on a device: call hnswgpu_upload first");
+    std::string err;
+    // (filters that are all empty need no id array: hand over a non-null pointer that is never dereferenced)
+    const FilterSet set{d_filter_ids ? d_filter_ids : reinterpret_cast<const uint64_t*>(d_queries), d_filter_offsets, n_filters, d_filter_of};
+    rc = hnswgpu::exact_filter_set_device(*dev, idx->flat->origin_id, d_queries, nq, d, k, set, d_out_ids, d_out_dists, d_out_layer, d_out_rank,
+                                          d_out_counts, stream, err);
+    if (rc != OK) return fail(rc, err);
+    return HNSWGPU_OK;
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
 static DeviceIndex* any_replica(hnswgpu_index* idx) {
     if (idx->primary >= 0 && idx->replica(idx->primary)) return idx->replica(idx->primary);
     return nullptr;

@@ -8,6 +8,7 @@
 #include <mutex>
 #include <shared_mutex>
 #include <string>
+#include <vector>
 
 #include "../../include/hnsw_mi355x.h"
 #include "builder.hpp"
@@ -50,6 +51,15 @@ namespace hnswgpu {
 int capi_fail(int code, const std::string& msg);
 // the replica a search on the primary device uses, uploaded first where need be (`sl`: the handle's lock, held shared)
 int capi_primary_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mutex>& sl, DeviceIndex** out);
+// the device side of hnswgpu_exact_search_batch_filter_set(_device), defined in exact_knn.hip: the exact k-NN of every query q
+// under filter filter_of[q] of the set (the arguments have been checked).  capi.cpp refers to these two weakly, like the search's
+// own filter-set pair (search_device.hpp): a host-only build of the C ABI links without them and answers "no device".
+int exact_filter_set_host(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* queries, uint64_t nq, uint64_t d,
+                          uint64_t k, const FilterSet& set, uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank,
+                          uint32_t* out_counts, std::string& err);
+int exact_filter_set_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* d_queries, uint64_t nq, uint64_t d,
+                            uint64_t k, const FilterSet& d_set, uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer,
+                            int32_t* d_out_rank, uint32_t* d_out_counts, void* stream, std::string& err);
 }  // namespace hnswgpu
 
 // No C++ exception may cross the C ABI: every entry point is `try { ... HNSWGPU_CAPI_GUARD_END(ret)`

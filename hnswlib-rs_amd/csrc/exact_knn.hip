@@ -1,5 +1,7 @@
 // exact_knn.hip -- exhaustive exact k-NN over every point of an uploaded index, filter included (gfx950 only):
-// hnswgpu_exact_search_batch / hnswgpu_exact_search_batch_device of include/hnsw_mi355x.h.  DESIGN.md "Exact k-NN".
+// hnswgpu_exact_search_batch / hnswgpu_exact_search_batch_device of include/hnsw_mi355x.h, and the device side of
+// hnswgpu_exact_search_batch_filter_set / _device (a set of filters, each query naming its own; the entries are in capi.cpp).
+// DESIGN.md "Exact k-NN".
 //
 //   exact_knn_prep_kernel   the queries of a chunk, zero padded and regrouped by tiles of TQ queries (element-chunk major),
 //                           DistCosine: + every query's squared norm in the crate's arithmetic
@@ -12,7 +14,12 @@
 //                           warm-up a row costs one 64-bit compare per query.
 //   exact_knn_merge_kernel  one wavefront per query: the slabs' lists merged (lane s holds the head of slab s), the answers written
 //
-// Keys are unique (the rank is a permutation), so every step is deterministic and a tie group is cut at position k by DataId.
+// Filter set: the slab kernel's SET variant keeps a 16-bit eligibility mask per lane (bit t: the row's bit in the bitmap of the
+// filter that query t of the tile names), so a tile may mix filters; the prep and merge kernels reach a query through an optional
+// list (a group's queries tiled densely, wherever they sit in the batch).
+//
+// Keys are unique (the rank is a permutation), so every step is deterministic and a tie group is cut at position k by DataId --
+// and a query's answer does not depend on which tile, group or chunk it is served in.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,6 +47,7 @@ constexpr uint64_t K_MAX = 4096;                // list_insert costs O(k / 64) s
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(4))) const v4f* qtile_ptr_t;  // wave-uniform addresses: scalar loads
+typedef __attribute__((address_space(4))) const uint32_t* uword_ptr_t;
 
 struct ExactKnnArgs {
     const float* qt;        // [tiles][nchunk][TQ] float4: element chunk c of the tile's TQ queries side by side, zero padded
@@ -61,6 +69,9 @@ struct ExactKnnArgs {
     uint8_t* out_layer;
     int32_t* out_rank;
     uint32_t* out_counts;
+    // (behind everything the kernels of the one-filter call read: their code does not move)
+    const uint32_t* qlist;  // tile slot -> row of the caller's arrays, or nullptr: the slot's own number
+    const uint32_t* tword;  // [tiles * TQ] filter set: first word of the slot's bitmap in `allow` (prep kernel)
 };
 
 // f32 -> u32 whose unsigned order is the order of the values, every NaN behind everything (distances are >= 0: then this is the
@@ -147,7 +158,9 @@ __device__ __attribute__((noinline)) ListState list_insert(uint64_t* list, uint3
     return s;
 }
 
-template <int METRIC>
+// SET: `allow` holds one bitmap of ceil(n / 32) words per filter of the group and every query of the tile names its own
+// (a.tword); else one bitmap (or none) for all
+template <int METRIC, bool SET>
 // (the two distances that go through ln_f32 get twice the registers: their inner loop spilled at four waves per SIMD)
 __global__ __launch_bounds__(64, METRIC == DIST_JEFFREYS || METRIC == DIST_JENSENSHANNON ? 2 : 4) void exact_knn_slab_kernel(DeviceIndexView ix, ExactKnnArgs a) {
     typedef typename std::conditional<METRIC == DIST_COSINE, double, float>::type ACC;
@@ -166,13 +179,43 @@ __global__ __launch_bounds__(64, METRIC == DIST_JEFFREYS || METRIC == DIST_JENSE
     ListState st[TQ];
 #pragma unroll
     for (int t = 0; t < TQ; ++t) st[t] = ListState{0u, KEY_NONE};
+    // filter set: where the bitmap of each query's filter starts (wave-uniform: scalar registers); the slots behind the last
+    // query of a part-filled tile never insert
+    uint32_t tword[TQ];
+    bool one_filter = true;  // every query of the tile names the same filter: one word per step serves all
+    if constexpr (SET) {
+#pragma unroll
+        for (int t = 0; t < TQ; ++t) {
+            tword[t] = ((uword_ptr_t)a.tword)[tile * (uint32_t)TQ + (uint32_t)t];
+            one_filter = one_filter && ((uint32_t)t >= nvalid || tword[t] == tword[0]);
+        }
+    }
+    const uint32_t valid_bits = (1u << nvalid) - 1u;
 
     for (uint32_t r0 = lo; r0 < hi; r0 += 64u) {
         const bool in = r0 + lane < hi;
         const uint32_t r = in ? r0 + lane : hi - 1u;  // lanes past the slab re-read its last row
         bool ok = in;
-        if (a.allow != nullptr) ok = in && ((a.allow[r >> 5] >> (r & 31u)) & 1u) != 0u;
-        if (__ballot(ok) == 0ull) continue;  // (wave-uniform) nothing eligible among these 64 rows
+        uint32_t elig = 0u;  // SET: bit t = this row is eligible for query t
+        if constexpr (SET) {
+            const uint32_t* const w = a.allow + (r >> 5);
+            const uint32_t sh = r & 31u;
+            if (one_filter) {
+                elig = ((w[tword[0]] >> sh) & 1u) != 0u ? valid_bits : 0u;
+            } else {
+                uint32_t word[TQ];  // one word per query, all loads issued before any is used
+#pragma unroll
+                for (int t = 0; t < TQ; ++t) word[t] = w[tword[t]];
+#pragma unroll
+                for (int t = 0; t < TQ; ++t) elig |= ((word[t] >> sh) & 1u) << t;
+                elig &= valid_bits;
+            }
+            if (!in) elig = 0u;
+            ok = elig != 0u;
+        } else {
+            if (a.allow != nullptr) ok = in && ((a.allow[r >> 5] >> (r & 31u)) & 1u) != 0u;
+        }
+        if (__ballot(ok) == 0ull) continue;  // (wave-uniform) nothing eligible for any query among these 64 rows
         const float* rowf = ix.vec + (size_t)r * ix.row_stride;
         const float4* row = reinterpret_cast<const float4*>(rowf);
         double s2 = 0.;
@@ -208,7 +251,8 @@ __global__ __launch_bounds__(64, METRIC == DIST_JEFFREYS || METRIC == DIST_JENSE
                     v = dist_finish<METRIC>(acc[t]);
                 }
                 const uint64_t key = make_key(v, rk);
-                const unsigned long long m = __ballot(ok && key < st[t].thr);
+                const bool mine = SET ? ((elig >> t) & 1u) != 0u : ok;
+                const unsigned long long m = __ballot(mine && key < st[t].thr);
                 if (m != 0ull) st[t] = list_insert(lists + (size_t)t * cap, cap, st[t], key, m);
             }
         }
@@ -225,8 +269,9 @@ __global__ __launch_bounds__(64, METRIC == DIST_JEFFREYS || METRIC == DIST_JENSE
 // one wavefront per query: lane s walks the list of slab s; the smallest head is the next answer
 __global__ __launch_bounds__(64) void exact_knn_merge_kernel(DeviceIndexView ix, ExactKnnArgs a) {
     const uint32_t lane = threadIdx.x;
-    const uint32_t q = blockIdx.x;
-    const uint32_t tile = q / (uint32_t)TQ, t = q % (uint32_t)TQ;
+    const uint32_t qs = blockIdx.x;  // the query's slot in the chunk's tiles; q: its row in the caller's arrays
+    const uint32_t q = a.qlist != nullptr ? a.qlist[qs] : qs;
+    const uint32_t tile = qs / (uint32_t)TQ, t = qs % (uint32_t)TQ;
     const uint32_t k = a.k;
     const size_t slot = ((size_t)tile * a.n_slabs + (lane < a.n_slabs ? lane : 0u)) * (size_t)TQ + t;
     const uint64_t* list = a.lists + slot * a.cap;
@@ -272,18 +317,23 @@ __global__ __launch_bounds__(64) void exact_knn_merge_kernel(DeviceIndexView ix,
     if (lane == 0u) a.out_counts[q] = cnt;
 }
 
-// one thread per query slot of the chunk's tiles: the row into its tile (slots behind the last query: zeros)
+// one thread per query slot of the chunk's tiles: the row into its tile (slots behind the last query: zeros).  Slot qs holds row
+// qlist[qs] of src (qlist == nullptr: row qs).  Filter set (tword != nullptr): the first word of the bitmap that row's filter has
+// in the group's bitmaps, slot_of[row] * words -- the caller bounds the bitmaps of a group to 2^32 words.
 __global__ void exact_knn_prep_kernel(const float* __restrict__ src, uint32_t nq, uint32_t d, uint32_t nchunk, uint32_t n_slots,
-                                      float* __restrict__ qt, double* __restrict__ qnorm) {
+                                      float* __restrict__ qt, double* __restrict__ qnorm, const uint32_t* __restrict__ qlist,
+                                      const uint32_t* __restrict__ slot_of, uint32_t words, uint32_t* __restrict__ tword) {
     const uint32_t qs = blockIdx.x * blockDim.x + threadIdx.x;
     if (qs >= n_slots) return;
     const uint32_t tile = qs / (uint32_t)TQ, t = qs % (uint32_t)TQ;
+    const uint32_t q = qs < nq && qlist != nullptr ? qlist[qs] : qs;
+    if (tword != nullptr) tword[qs] = qs < nq ? slot_of[q] * words : 0u;
     double s1 = 0.;  // DistCosine: f32 squares widened to f64, summed left to right (finish_staged_query)
     for (uint32_t c = 0; c < nchunk; ++c) {
         float e[4];
         for (uint32_t j = 0; j < 4u; ++j) {
             const uint32_t i = 4u * c + j;
-            e[j] = qs < nq && i < d ? src[(size_t)qs * d + i] : 0.f;
+            e[j] = qs < nq && i < d ? src[(size_t)q * d + i] : 0.f;
             s1 = s1 + (double)(e[j] * e[j]);
         }
         reinterpret_cast<float4*>(qt)[((size_t)tile * nchunk + c) * (size_t)TQ + t] = make_float4(e[0], e[1], e[2], e[3]);
@@ -291,18 +341,22 @@ __global__ void exact_knn_prep_kernel(const float* __restrict__ src, uint32_t nq
     qnorm[qs] = s1;
 }
 
-hipError_t launch_slab(int metric, dim3 grid, hipStream_t stream, const DeviceIndexView& ix, const ExactKnnArgs& a) {
+template <bool SET>
+hipError_t launch_slab_of(int metric, dim3 grid, hipStream_t stream, const DeviceIndexView& ix, const ExactKnnArgs& a) {
     switch (metric) {
-        case DIST_L2: hipLaunchKernelGGL(exact_knn_slab_kernel<DIST_L2>, grid, dim3(64), 0, stream, ix, a); break;
-        case DIST_COSINE: hipLaunchKernelGGL(exact_knn_slab_kernel<DIST_COSINE>, grid, dim3(64), 0, stream, ix, a); break;
-        case DIST_DOT: hipLaunchKernelGGL(exact_knn_slab_kernel<DIST_DOT>, grid, dim3(64), 0, stream, ix, a); break;
-        case DIST_L1: hipLaunchKernelGGL(exact_knn_slab_kernel<DIST_L1>, grid, dim3(64), 0, stream, ix, a); break;
-        case DIST_HELLINGER: hipLaunchKernelGGL(exact_knn_slab_kernel<DIST_HELLINGER>, grid, dim3(64), 0, stream, ix, a); break;
-        case DIST_JEFFREYS: hipLaunchKernelGGL(exact_knn_slab_kernel<DIST_JEFFREYS>, grid, dim3(64), 0, stream, ix, a); break;
-        case DIST_JENSENSHANNON: hipLaunchKernelGGL(exact_knn_slab_kernel<DIST_JENSENSHANNON>, grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_L2: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_L2, SET>), grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_COSINE: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_COSINE, SET>), grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_DOT: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_DOT, SET>), grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_L1: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_L1, SET>), grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_HELLINGER: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_HELLINGER, SET>), grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_JEFFREYS: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_JEFFREYS, SET>), grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_JENSENSHANNON: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_JENSENSHANNON, SET>), grid, dim3(64), 0, stream, ix, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+hipError_t launch_slab(int metric, bool set, dim3 grid, hipStream_t stream, const DeviceIndexView& ix, const ExactKnnArgs& a) {
+    return set ? launch_slab_of<true>(metric, grid, stream, ix, a) : launch_slab_of<false>(metric, grid, stream, ix, a);
 }
 
 #define HIP_TRY(expr)                                                                          \
@@ -395,10 +449,20 @@ std::shared_ptr<void> make_state(const DeviceIndex& dev, const std::vector<uint6
 
 uint64_t round_up(uint64_t x, uint64_t m) { return (x + m - 1) / m * m; }
 
-// the device path: every pointer is device memory; waits for `stream` before it returns
+// A filter set behind a call (device pointers), and the knob that bounds the bitmaps one launch holds
+struct SetCall {
+    const FilterSet* fs;
+    uint64_t bitmap_budget;  // HNSWGPU_FILTER_SET_MB in bytes
+};
+constexpr uint64_t MAX_FILTER_SET_WAVES = 1ull << 31;  // allow_bitmap_set_kernel: four wavefronts per workgroup, 2^29 workgroups
+
+// the device path: every pointer is device memory; waits for `stream` before it returns.
+// set == nullptr: no filter, or one for the batch (d_allowed).  Else query q is answered under filter fs->filter_of[q]: the
+// bitmaps are built group by group -- as many consecutive filters as the bound and this unit's scratch budget hold -- and per group
+// its queries are listed (launch_filter_group), tiled densely and searched; one group (the usual case): all queries in batch order.
 int exact_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* d_queries, uint64_t nq, uint64_t d,
-                 uint64_t k, const uint64_t* d_allowed, uint64_t n_allowed, bool filtered, uint64_t* d_out_ids, float* d_out_dists,
-                 uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, hipStream_t stream, std::string& err) {
+                 uint64_t k, const uint64_t* d_allowed, uint64_t n_allowed, bool filtered, const SetCall* set, uint64_t* d_out_ids,
+                 float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, hipStream_t stream, std::string& err) {
     const DeviceIndexView& v = dev.view();
     if (nq == 0) return OK;
     OnDevice on(dev.device());
@@ -414,65 +478,133 @@ int exact_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id,
     const uint64_t tiles_total = (nq + TQ - 1) / TQ;
     // slabs: enough (tile, slab) wavefronts to fill the device, never more lists than the budget holds for one tile
     uint64_t slabs = std::min<uint64_t>(MAX_SLABS, (8192 + tiles_total - 1) / tiles_total);
-    const uint64_t allow_bytes = round_up((n + 31) / 32 * 4, 256);
-    const uint64_t fixed_bytes = allow_bytes + round_up(TQ * (nchunk * 16 + 8), 256) + 4096;  // the bitmap and one tile's queries
-    if (fixed_bytes >= SCRATCH_BUDGET) { err = "index or dimension too large for the exact search's scratch budget"; return ERR_ARG; }
+    const uint64_t words = (n + 31) / 32, slot_bytes = words * 4;
+    // in front of the tiles: the bitmap -- or, for a filter set, the bitmaps of a group (at most half of the budget), two words of
+    // counters and, when there is more than one group, the list of a group's queries and every query's slot
+    uint64_t per_group = 1, groups = 1, ctrl_bytes = 0, qlist_bytes = 0;
+    if (set) {
+        if (set->bitmap_budget < slot_bytes) {
+            err = "HNSWGPU_FILTER_SET_MB is smaller than one filter's bitmap (" + std::to_string(slot_bytes) + " bytes for this index)";
+            return ERR_ARG;
+        }
+        per_group = std::min<uint64_t>({set->bitmap_budget / slot_bytes, (SCRATCH_BUDGET / 2) / slot_bytes, set->fs->n_filters,
+                                        MAX_FILTER_SET_WAVES / ((n + 63) / 64) - 1});
+        if (per_group == 0) { err = "index too large for the exact search's scratch budget"; return ERR_ARG; }
+        groups = (set->fs->n_filters + per_group - 1) / per_group;
+        ctrl_bytes = 256;
+        if (groups > 1) qlist_bytes = round_up(nq * 4, 256);
+    }
+    const uint64_t allow_bytes = round_up(per_group * slot_bytes, 256) + ctrl_bytes + 2 * qlist_bytes;
+    const uint64_t fixed_bytes = allow_bytes + round_up(TQ * (nchunk * 16 + 8), 256) + 4096;  // the bitmap(s) and one tile's queries
+    if (fixed_bytes >= SCRATCH_BUDGET) { err = "index, batch or dimension too large for the exact search's scratch budget"; return ERR_ARG; }
     const uint64_t list_budget = SCRATCH_BUDGET - fixed_bytes;
     slabs = std::min(slabs, list_budget / ((uint64_t)TQ * (cap * 8 + 4)));
     if (slabs == 0) { err = "knbn too large for the exact search's scratch budget"; return ERR_ARG; }
     const uint64_t slab_rows = std::max<uint64_t>(MIN_SLAB_ROWS, round_up((n + slabs - 1) / slabs, 64));
     slabs = (n + slab_rows - 1) / slab_rows;
     // queries per chunk: whole tiles, what the budget holds, a grid the launch accepts
-    const uint64_t per_tile = round_up(nchunk * TQ * 16, 256) + round_up(TQ * 8, 256) + round_up(slabs * TQ * cap * 8, 256) + round_up(slabs * TQ * 4, 256);
+    const uint64_t tword_bytes = set ? round_up(TQ * 4, 256) : 0;
+    const uint64_t per_tile = round_up(nchunk * TQ * 16, 256) + round_up(TQ * 8, 256) + round_up(slabs * TQ * cap * 8, 256) + round_up(slabs * TQ * 4, 256) + tword_bytes;
     const uint64_t chunk_tiles = std::min<uint64_t>({tiles_total, (SCRATCH_BUDGET - allow_bytes) / per_tile, 65535});
     if (chunk_tiles == 0) { err = "knbn too large for the exact search's scratch budget"; return ERR_ARG; }
 
     ScratchLease lease(st);
     HIP_TRY(lease.take(allow_bytes + chunk_tiles * per_tile));
     unsigned char* p = static_cast<unsigned char*>(lease.p);
-    uint32_t* d_allow = reinterpret_cast<uint32_t*>(p); p += allow_bytes;
+    uint32_t* d_allow = reinterpret_cast<uint32_t*>(p); p += round_up(per_group * slot_bytes, 256);
+    uint32_t* d_ctrl = reinterpret_cast<uint32_t*>(p); p += ctrl_bytes;  // [0] entries of filter_of that name no filter, [1] queries of the group
+    uint32_t* d_qlist = reinterpret_cast<uint32_t*>(p); p += qlist_bytes;
+    uint32_t* d_slot_of = reinterpret_cast<uint32_t*>(p); p += qlist_bytes;
     float* d_qt = reinterpret_cast<float*>(p); p += chunk_tiles * round_up(nchunk * TQ * 16, 256);
     double* d_qnorm = reinterpret_cast<double*>(p); p += chunk_tiles * round_up(TQ * 8, 256);
     uint64_t* d_lists = reinterpret_cast<uint64_t*>(p); p += chunk_tiles * round_up(slabs * TQ * cap * 8, 256);
-    uint32_t* d_lens = reinterpret_cast<uint32_t*>(p);
+    uint32_t* d_lens = reinterpret_cast<uint32_t*>(p); p += chunk_tiles * round_up(slabs * TQ * 4, 256);
+    uint32_t* d_tword = set ? reinterpret_cast<uint32_t*>(p) : nullptr;
 
     // whatever happens, nothing of this call is still running when the scratch block goes back to the pool
     struct Drain {
         hipStream_t s;
         ~Drain() { (void)hipStreamSynchronize(s); }
     } drain{stream};
-    if (filtered) HIP_TRY(launch_allow_bitmap(stream, v.origin_id, v.n, d_allowed, n_allowed, d_allow));
 
-    for (uint64_t t0 = 0; t0 < tiles_total; t0 += chunk_tiles) {
-        const uint64_t tiles = std::min(chunk_tiles, tiles_total - t0);
-        const uint64_t q0 = t0 * TQ, cq = std::min<uint64_t>(tiles * TQ, nq - q0);
-        ExactKnnArgs a{};
-        a.qt = d_qt;
-        a.qnorm = d_qnorm;
-        a.rank = static_cast<const uint32_t*>(st->d_rank);
-        a.order = static_cast<const uint32_t*>(st->d_order);
-        a.allow = filtered ? d_allow : nullptr;
-        a.nrm2 = dev.side_norms();
-        a.lists = d_lists;
-        a.lens = d_lens;
-        a.nq = (uint32_t)cq;
-        a.nchunk = (uint32_t)nchunk;
-        a.cap = (uint32_t)cap;
-        a.slab_rows = (uint32_t)slab_rows;
-        a.n_slabs = (uint32_t)slabs;
-        a.k = (uint32_t)k;
-        a.out_ids = d_out_ids + q0 * k;
-        a.out_dists = d_out_dists + q0 * k;
-        a.out_layer = d_out_layer ? d_out_layer + q0 * k : nullptr;
-        a.out_rank = d_out_rank ? d_out_rank + q0 * k : nullptr;
-        a.out_counts = d_out_counts + q0;
-        const uint32_t n_slots = (uint32_t)(tiles * TQ);
-        hipLaunchKernelGGL(exact_knn_prep_kernel, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, d_queries + q0 * d, (uint32_t)cq,
-                           (uint32_t)d, (uint32_t)nchunk, n_slots, d_qt, d_qnorm);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(launch_slab(dev.dist(), dim3((uint32_t)slabs, (uint32_t)tiles), stream, v, a));
-        hipLaunchKernelGGL(exact_knn_merge_kernel, dim3((uint32_t)cq), dim3(64), 0, stream, v, a);
-        HIP_TRY(hipGetLastError());
+    // `count` queries in chunks of whole tiles: slot i of the tiles is query qlist[i] (nullptr: query i) of the batch, searched
+    // under the bitmap slot_of[that query] of the group (filter set only)
+    auto run = [&](const uint32_t* qlist, uint64_t count, const uint32_t* slot_of) -> int {
+        const uint64_t tiles_all = (count + TQ - 1) / TQ;
+        for (uint64_t t0 = 0; t0 < tiles_all; t0 += chunk_tiles) {
+            const uint64_t tiles = std::min(chunk_tiles, tiles_all - t0);
+            const uint64_t q0 = t0 * TQ, cq = std::min<uint64_t>(tiles * TQ, count - q0);
+            const uint64_t row0 = qlist ? 0 : q0;  // a list names rows of the whole batch; without one the chunk's rows start at q0
+            ExactKnnArgs a{};
+            a.qt = d_qt;
+            a.qnorm = d_qnorm;
+            a.rank = static_cast<const uint32_t*>(st->d_rank);
+            a.order = static_cast<const uint32_t*>(st->d_order);
+            a.allow = filtered || set ? d_allow : nullptr;
+            a.nrm2 = dev.side_norms();
+            a.lists = d_lists;
+            a.lens = d_lens;
+            a.nq = (uint32_t)cq;
+            a.nchunk = (uint32_t)nchunk;
+            a.cap = (uint32_t)cap;
+            a.slab_rows = (uint32_t)slab_rows;
+            a.n_slabs = (uint32_t)slabs;
+            a.k = (uint32_t)k;
+            a.out_ids = d_out_ids + row0 * k;
+            a.out_dists = d_out_dists + row0 * k;
+            a.out_layer = d_out_layer ? d_out_layer + row0 * k : nullptr;
+            a.out_rank = d_out_rank ? d_out_rank + row0 * k : nullptr;
+            a.out_counts = d_out_counts + row0;
+            a.qlist = qlist ? qlist + q0 : nullptr;
+            a.tword = d_tword;
+            const uint32_t n_slots = (uint32_t)(tiles * TQ);
+            hipLaunchKernelGGL(exact_knn_prep_kernel, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, d_queries + row0 * d, (uint32_t)cq,
+                               (uint32_t)d, (uint32_t)nchunk, n_slots, d_qt, d_qnorm, a.qlist, slot_of ? slot_of + row0 : nullptr, (uint32_t)words, d_tword);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(launch_slab(dev.dist(), set != nullptr, dim3((uint32_t)slabs, (uint32_t)tiles), stream, v, a));
+            hipLaunchKernelGGL(exact_knn_merge_kernel, dim3((uint32_t)cq), dim3(64), 0, stream, v, a);
+            HIP_TRY(hipGetLastError());
+        }
+        return OK;
+    };
+
+    if (!set) {
+        if (filtered) HIP_TRY(launch_allow_bitmap(stream, v.origin_id, v.n, d_allowed, n_allowed, d_allow));
+        const int rc = run(nullptr, nq, nullptr);
+        if (rc != OK) return rc;
+        HIP_TRY(hipStreamSynchronize(stream));
+        return OK;
+    }
+    // The slab kernel indexes the bitmaps with filter_of's values: the entries that name no filter are counted, and the count is
+    // read back (while the first group's bitmaps are being built) before anything is searched or written.
+    const FilterSet& fs = *set->fs;
+    uint32_t h_ctrl[2] = {0u, 0u};
+    HIP_TRY(hipMemsetAsync(d_ctrl, 0, 8, stream));
+    HIP_TRY(launch_filter_of_check(stream, fs.filter_of, (uint32_t)nq, fs.n_filters, d_ctrl));
+    HIP_TRY(launch_allow_bitmap_set(stream, v.origin_id, v.n, fs.ids, fs.offsets, 0, (uint32_t)per_group, d_allow));
+    HIP_TRY(hipMemcpyAsync(h_ctrl, d_ctrl, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (h_ctrl[0] != 0) {
+        err = std::to_string(h_ctrl[0]) + " entries of filter_of name no filter of the set (>= n_filters = " + std::to_string(fs.n_filters) + ")";
+        return ERR_ARG;
+    }
+    if (groups == 1) {
+        const int rc = run(nullptr, nq, fs.filter_of);
+        if (rc != OK) return rc;
+    } else {
+        for (uint64_t f0 = 0; f0 < fs.n_filters; f0 += per_group) {
+            const uint32_t n_slots = (uint32_t)std::min<uint64_t>(per_group, fs.n_filters - f0);
+            // (the stream is in order: the previous group's search is behind its bitmaps, its list and its slots)
+            if (f0 != 0) HIP_TRY(launch_allow_bitmap_set(stream, v.origin_id, v.n, fs.ids, fs.offsets, (uint32_t)f0, n_slots, d_allow));
+            HIP_TRY(hipMemsetAsync(d_ctrl + 1, 0, 4, stream));
+            HIP_TRY(launch_filter_group(stream, fs.filter_of, (uint32_t)nq, (uint32_t)f0, n_slots, d_qlist, d_slot_of, d_ctrl + 1));
+            HIP_TRY(hipMemcpyAsync(h_ctrl, d_ctrl, 8, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            const uint32_t members = h_ctrl[1];
+            if (members == 0) continue;  // a group without queries launches nothing
+            const int rc = run(d_qlist, members, d_slot_of);
+            if (rc != OK) return rc;
+        }
     }
     HIP_TRY(hipStreamSynchronize(stream));
     return OK;
@@ -499,7 +631,67 @@ struct DevMem {
     ~DevMem() { if (p) (void)hipFree(p); }
 };
 
+uint64_t filter_set_budget() {
+    const int64_t knob = knobs().filter_set_bytes;
+    return knob >= 0 ? (uint64_t)knob : 256ull << 20;
+}
+
 }  // namespace
+
+// The device side of hnswgpu_exact_search_batch_filter_set(_device); capi.cpp holds the entries and every argument check, and
+// refers to these two weakly (capi_index.hpp).
+int exact_filter_set_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* d_queries, uint64_t nq, uint64_t d,
+                            uint64_t k, const FilterSet& d_set, uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer,
+                            int32_t* d_out_rank, uint32_t* d_out_counts, void* stream, std::string& err) {
+    const SetCall set{&d_set, filter_set_budget()};
+    return exact_device(dev, origin_id, d_queries, nq, d, k, nullptr, 0, false, &set, d_out_ids, d_out_dists, d_out_layer, d_out_rank,
+                        d_out_counts, static_cast<hipStream_t>(stream), err);
+}
+
+// host buffers: the set goes to the device once; queries and answers are staged in chunks of at most 64 MB, each chunk one call
+// of the device path (under its own rows of filter_of)
+int exact_filter_set_host(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* queries, uint64_t nq, uint64_t d,
+                          uint64_t k, const FilterSet& set, uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank,
+                          uint32_t* out_counts, std::string& err) {
+    if (nq == 0) return OK;
+    OnDevice on(dev.device());
+    HIP_TRY(on.status());
+    const uint64_t n_ids = set.offsets[set.n_filters];
+    const uint64_t per_q = d * 4 + k * 17 + 4 + 4;
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(nq, (64ull << 20) / per_q));
+    DevMem m_ids, m_off, m_of, m_q, m_out;
+    HIP_TRY(hipMalloc(&m_ids.p, std::max<uint64_t>(1, n_ids) * sizeof(uint64_t)));  // (filters that are all empty: never read)
+    HIP_TRY(hipMalloc(&m_off.p, (set.n_filters + 1) * sizeof(uint64_t)));
+    HIP_TRY(hipMalloc(&m_of.p, chunk * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&m_q.p, chunk * d * 4));
+    HIP_TRY(hipMalloc(&m_out.p, chunk * (k * 17 + 4) + 64));
+    if (n_ids != 0) HIP_TRY(hipMemcpy(m_ids.p, set.ids, n_ids * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m_off.p, set.offsets, (set.n_filters + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+    unsigned char* o = static_cast<unsigned char*>(m_out.p);
+    uint64_t* d_ids = reinterpret_cast<uint64_t*>(o);
+    float* d_dists = reinterpret_cast<float*>(o + chunk * k * 8);
+    int32_t* d_rank = reinterpret_cast<int32_t*>(o + chunk * k * 12);
+    uint32_t* d_counts = reinterpret_cast<uint32_t*>(o + chunk * k * 16);
+    uint8_t* d_layer = o + chunk * k * 16 + chunk * 4;
+    const FilterSet d_set{static_cast<const uint64_t*>(m_ids.p), static_cast<const uint64_t*>(m_off.p), set.n_filters,
+                          static_cast<const uint32_t*>(m_of.p)};
+    const SetCall call{&d_set, filter_set_budget()};
+    for (uint64_t q0 = 0; q0 < nq; q0 += chunk) {
+        const uint64_t cq = std::min(chunk, nq - q0);
+        HIP_TRY(hipMemcpy(m_q.p, queries + q0 * d, cq * d * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(m_of.p, set.filter_of + q0, cq * sizeof(uint32_t), hipMemcpyHostToDevice));
+        const int rc = exact_device(dev, origin_id, static_cast<const float*>(m_q.p), cq, d, k, nullptr, 0, false, &call, d_ids, d_dists, d_layer,
+                                    d_rank, d_counts, nullptr, err);
+        if (rc != OK) return rc;
+        HIP_TRY(hipMemcpy(out_ids + q0 * k, d_ids, cq * k * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out_dists + q0 * k, d_dists, cq * k * 4, hipMemcpyDeviceToHost));
+        if (out_rank) HIP_TRY(hipMemcpy(out_rank + q0 * k, d_rank, cq * k * 4, hipMemcpyDeviceToHost));
+        if (out_layer) HIP_TRY(hipMemcpy(out_layer + q0 * k, d_layer, cq * k, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out_counts + q0, d_counts, cq * 4, hipMemcpyDeviceToHost));
+    }
+    return OK;
+}
+
 }  // namespace hnswgpu
 #pragma clang diagnostic pop
 
@@ -520,7 +712,7 @@ int hnswgpu_exact_search_batch_device(const hnswgpu_index* cidx, const float* d_
     if (!dev || idx->dev_stale || idx->flat_stale || !idx->flat)
         return capi_fail(HNSWGPU_ERR_DEVICE, "index is not resident on a device: call hnswgpu_upload first");
     std::string err;
-    rc = exact_device(*dev, idx->flat->origin_id, d_queries, nq, d, k, d_allowed_ids, n_allowed, d_allowed_ids != nullptr, d_out_ids,
+    rc = exact_device(*dev, idx->flat->origin_id, d_queries, nq, d, k, d_allowed_ids, n_allowed, d_allowed_ids != nullptr, nullptr, d_out_ids,
                       d_out_dists, d_out_layer, d_out_rank, d_out_counts, static_cast<hipStream_t>(stream), err);
     if (rc != OK) return capi_fail(rc, err);
     return HNSWGPU_OK;
@@ -580,7 +772,7 @@ int hnswgpu_exact_search_batch(const hnswgpu_index* cidx, const float* queries, 
     for (uint64_t q0 = 0; q0 < nq; q0 += chunk) {
         const uint64_t cq = std::min(chunk, nq - q0);
         if ((e = hipMemcpy(m_q.p, queries + q0 * d, cq * d * 4, hipMemcpyHostToDevice)) != hipSuccess) return dev_fail(e, "hipMemcpy");
-        rc = exact_device(*dev, idx->flat->origin_id, static_cast<const float*>(m_q.p), cq, d, k, d_allowed, n_allowed, filtered, d_ids, d_dists,
+        rc = exact_device(*dev, idx->flat->origin_id, static_cast<const float*>(m_q.p), cq, d, k, d_allowed, n_allowed, filtered, nullptr, d_ids, d_dists,
                           d_layer, d_rank, d_counts, nullptr, err);
         if (rc != OK) return capi_fail(rc, err);
         if ((e = hipMemcpy(out_ids + q0 * k, d_ids, cq * k * 8, hipMemcpyDeviceToHost)) != hipSuccess) return dev_fail(e, "hipMemcpy");

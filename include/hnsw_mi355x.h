@@ -374,6 +374,30 @@ int hnswgpu_exact_search_batch_device(const hnswgpu_index* idx, const float* d_q
                                       const uint64_t* d_allowed_ids, uint64_t n_allowed, uint64_t* d_out_ids,
                                       float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank,
                                       uint32_t* d_out_counts, void* stream);
+/* The exact answers for a SET of filters, each query naming its own: the ground truth of hnswgpu_search_batch_filter_set.  Row q
+ * is exactly what hnswgpu_exact_search_batch returns for query q alone with allowed_ids = filter filter_of[q] -- ids and their
+ * order, f32 distance bits (NaN and +-0 as there), p_ids, counts, zeros behind the answers.  The set is given as in
+ * hnswgpu_search_batch_filter_set (CSR filter_ids / filter_offsets[0 .. n_filters], every vector sorted; filter_of[0..nq) <
+ * n_filters) and checked the same way, each HNSWGPU_ERR_ARG with a message that names the offender; then k, d and the arithmetic
+ * as in hnswgpu_exact_search_batch.  Ids naming no point are ignored, an empty vector gives count 0.  No out_status: an
+ * exhaustive search has no panic case.  A tile of 16 queries may mix filters (every lane keeps one eligibility bit per query), so
+ * one filter per query costs no more vector work than one filter for all.  The bitmaps one launch holds are bounded by
+ * HNSWGPU_FILTER_SET_MB as in the search (and by half of this call's 320 MB of scratch); a larger set is served in groups of
+ * consecutive filters, every query exactly once; a bound below one bitmap is HNSWGPU_ERR_ARG.  Keys (distance, id rank) are
+ * unique, so an answer does NOT depend on how the queries are grouped into tiles, groups or chunks.                          */
+int hnswgpu_exact_search_batch_filter_set(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, uint64_t k,
+                                          const uint64_t* filter_ids, const uint64_t* filter_offsets, uint64_t n_filters,
+                                          const uint32_t* filter_of, uint64_t* out_ids, float* out_dists, uint8_t* out_layer,
+                                          int32_t* out_rank, uint32_t* out_counts);
+/* The same with every buffer in HBM (ids, offsets and filter_of too), on `stream`, waited for.  The arrays cannot be read on the
+ * host: a kernel counts the entries of d_filter_of that are >= n_filters, and if there are any the call returns HNSWGPU_ERR_ARG
+ * BEFORE anything is searched -- no output is written, the handle stays usable.  Offsets and sortedness are the caller's promise,
+ * as in hnswgpu_search_batch_filter_set_device.  The index must be uploaded (else HNSWGPU_ERR_DEVICE).                       */
+int hnswgpu_exact_search_batch_filter_set_device(const hnswgpu_index* idx, const float* d_queries, uint64_t nq, uint64_t d,
+                                                 uint64_t k, const uint64_t* d_filter_ids, const uint64_t* d_filter_offsets,
+                                                 uint64_t n_filters, const uint32_t* d_filter_of, uint64_t* d_out_ids,
+                                                 float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank,
+                                                 uint32_t* d_out_counts, void* stream);
 
 /* Test entry: the lane lab. The wave-level algorithms the search kernels are made of -- the reference's BinaryHeap (src/hnsw.rs:940,
  * :958-973, :1035-1053, :1544; std's push / pop / into_sorted_vec) as a memory heap and as a register heap, the sorted result set

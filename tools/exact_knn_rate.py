@@ -5,7 +5,14 @@ with two comparators measured on the same box and inputs:
       small enough to finish -- the new entry (host buffers, like (a)) is timed on the same queries;
   (b) bench.py's ground_truth (torch GEMM shortlist + f64 re-evaluation): context only -- not exact, not the index's arithmetic.
     tools/gpu_call.sh exact_rate OUTDIR [--shapes sift1m,glove25,mnist784] [--nq 10000]      -> OUTDIR/rate.json
-One JSON line per shape on stdout, progress on stderr.  Warm-up calls first, then the median and the spread of `--repeats` calls."""
+One JSON line per shape on stdout, progress on stderr.  Warm-up calls first, then the median and the spread of `--repeats` calls.
+
+Filter-set mode (--filter-set): hnswgpu_exact_search_batch_filter_set through Hnsw.exact_search_filters_flat on the first shape,
+with --filters F filters of --selectivity LO[,HI] (fractions of the points, spread evenly from LO to HI) named by the queries
+--naming random | same (every query names filter 0) | own (query q names filter q: F = nq), against the host loop it replaces
+(one Hnsw.exact_search_flat per filter on that filter's queries) and against the one-filter call with filter 0 for every query.
+--package-root DIR measures the package of another checkout (the parent commit, built there): what that package lacks -- the set
+call before it existed -- is left out of the line, so both commits are timed by the same code on the same inputs."""
 import argparse
 import ctypes as C
 import json
@@ -17,6 +24,8 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--package-root" in sys.argv:
+    ROOT = os.path.abspath(sys.argv[sys.argv.index("--package-root") + 1])
 sys.path.insert(0, ROOT)
 
 SHAPES = {  # BASELINE configs 2, 3, 5
@@ -65,6 +74,54 @@ def timed(fn, warmup, repeats):
     return statistics.median(ts), min(ts), max(ts)
 
 
+def filter_set_mode(a):
+    import torch
+    torch.cuda.init()
+    import hnsw_rs_amd as H
+    H.build_native()
+    name = a.shapes.split(",")[0]
+    s = SHAPES[name]
+    n, d, dist, k, nq = s["n"], s["d"], s["dist"], a.k, a.nq
+    sel = [float(x) for x in a.selectivity.split(",")]
+    nf = nq if a.naming == "own" else a.filters
+    fracs = np.linspace(sel[0], sel[-1], nf)
+    rng = np.random.default_rng(7)
+    X, Q = clustered(n, d, 1), clustered(nq, d, 2)
+    h = H.Hnsw(8, n, 16, 16, dist)
+    h.set_build_options(nthreads=0, gpu_device=0, gpu_window=0)
+    t0 = time.perf_counter()
+    h.parallel_insert(X)
+    h.upload(0)
+    print(f"== {name}: built and uploaded in {time.perf_counter() - t0:.1f} s", file=sys.stderr)
+    filters = [np.flatnonzero(rng.random(n) < f).astype(np.uint64) for f in fracs]   # origin ids are the row numbers
+    filter_of = {"random": rng.integers(0, nf, nq), "same": np.zeros(nq, np.int64), "own": np.arange(nq)}[a.naming].astype(np.uint32)
+    out = dict(mode="filter_set", shape=name, n=n, d=d, dist=dist, nq=nq, k=k, filters=nf, selectivity=[float(fracs[0]), float(fracs[-1])],
+               naming=a.naming, repeats=a.repeats, warmup=a.warmup, package_root=ROOT)
+
+    def loop():   # what a caller had to do before: one call per filter with the queries that name it
+        res = {}
+        for f in np.unique(filter_of):
+            qs = np.flatnonzero(filter_of == f)
+            res[int(f)] = (qs, h.exact_search_flat(Q[qs], k, filters[int(f)]))
+        return res
+    med, lo, hi = timed(lambda: h.exact_search_flat(Q, k, filters[0]), a.warmup, a.repeats)
+    out["one_filter_call_filter0_s"] = dict(median=med, min=lo, max=hi)
+    med, lo, hi = timed(loop, min(a.warmup, 1), a.repeats)
+    out["host_loop_s"] = dict(median=med, min=lo, max=hi, calls=int(len(np.unique(filter_of))))
+    if hasattr(h, "exact_search_filters_flat"):
+        med, lo, hi = timed(lambda: h.exact_search_filters_flat(Q, k, filters, filter_of), a.warmup, a.repeats)
+        out["set_call_s"] = dict(median=med, min=lo, max=hi)
+        out["host_loop_over_set_call"] = out["host_loop_s"]["median"] / med
+        got, same = h.exact_search_filters_flat(Q, k, filters, filter_of), True
+        for f, (qs, r) in loop().items():   # equal work: the set call's rows are the loop's
+            same = same and np.array_equal(got.ids[qs], r.ids) and np.array_equal(got.dists[qs].view(np.uint32), r.dists.view(np.uint32)) \
+                and np.array_equal(got.counts[qs], r.counts)
+        out["same_answers_as_host_loop"] = bool(same)
+    print(json.dumps(out), flush=True)
+    if out.get("same_answers_as_host_loop") is False:
+        sys.exit(1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="sift1m,glove25,mnist784")
@@ -74,7 +131,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--no-torch-comparator", action="store_true")
+    ap.add_argument("--filter-set", action="store_true")
+    ap.add_argument("--filters", type=int, default=64)
+    ap.add_argument("--selectivity", default="0.01,0.5")
+    ap.add_argument("--naming", choices=("random", "same", "own"), default="random")
+    ap.add_argument("--package-root", default=None)
     a = ap.parse_args()
+    if a.filter_set:
+        return filter_set_mode(a)
     import torch
     torch.cuda.init()
     import hnsw_rs_amd as H

@@ -1,16 +1,20 @@
 #!/usr/bin/env python3
 """Per-kernel register / scratch / occupancy table of one kernel translation unit (cross-compiles, no GPU needed):
-    tools/kres.py METRIC PART [extra -D flags ...]      e.g.  tools/kres.py 0 0"""
+    tools/kres.py METRIC PART [extra -D flags ...]      e.g.  tools/kres.py 0 0
+    tools/kres.py exact [extra -D flags ...]            the kernels of exact_knn.hip (every instantiation of the slab kernel)"""
 import os
 import re
 import subprocess
 import sys
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-metric, part, extra = sys.argv[1], sys.argv[2], sys.argv[3:]
-cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-pthread", "--offload-arch=gfx950",
-       "-fhip-fp32-correctly-rounded-divide-sqrt", *extra, f"-DHNSW_THIS_METRIC={metric}", f"-DHNSW_PART={part}",
-       "-Rpass-analysis=kernel-resource-usage", "-c", "search_kernels_tu.hip", "-o", f"/tmp/kres_{metric}_{part}.o"]
+flags = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-pthread", "--offload-arch=gfx950",
+         "-fhip-fp32-correctly-rounded-divide-sqrt", "-Rpass-analysis=kernel-resource-usage"]
+if sys.argv[1] == "exact":
+    cmd = [*flags, *sys.argv[2:], "-c", "exact_knn.hip", "-o", "/tmp/kres_exact.o"]
+else:
+    metric, part, extra = sys.argv[1], sys.argv[2], sys.argv[3:]
+    cmd = [*flags, *extra, f"-DHNSW_THIS_METRIC={metric}", f"-DHNSW_PART={part}", "-c", "search_kernels_tu.hip", "-o", f"/tmp/kres_{metric}_{part}.o"]
 p = subprocess.run(cmd, cwd=os.path.join(root, "hnswlib-rs_amd", "csrc"), capture_output=True, text=True)
 rows, cur = [], {}
 for line in p.stderr.splitlines():
