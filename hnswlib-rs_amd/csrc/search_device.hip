@@ -64,6 +64,10 @@ Knobs read_knobs() {
         const double mb = std::atof(e);
         k.filter_set_bytes = mb > 0. ? (int64_t)std::min(mb * 1048576., 64. * 1073741824.) : 0;
     }
+    k.bitmap_slices = num("HNSWGPU_BITMAP_SLICES", -1);
+    if (k.bitmap_slices < 1) k.bitmap_slices = -1;  // (a launch needs one slice at least)
+    k.literal_cand_cap = num("HNSWGPU_LITERAL_CAND_CAP", -1);
+    k.literal_cand_cap = k.literal_cand_cap < 1 ? -1 : std::max(64, k.literal_cand_cap);  // (one batch of neighbours at least)
     return k;
 }
 std::atomic<const Knobs*> g_knobs{nullptr};
@@ -557,6 +561,7 @@ constexpr size_t CTRL_LAUNCH_BYTES = 16;
 // hnsw_search_kernel and hnsw_search_pair_kernel: queries to search again (retry_out: the table full and no bitmap slice / handed
 // back by the pair pass), queries that moved to the HBM bitmap inside the launch, queries that would overflow a table of half the
 // size, ties not resolved in the launch (tie_list; cumulative over relaunches), ties resolved with the literal heaps inside it
+// (cumulative over relaunches as well)
 enum : uint32_t { SC_RETRY = 1, SC_TO_BITMAP = 2, SC_HALF_OVERFLOW = 3, SC_FLAGGED = 4, SC_LITERAL = 5 };
 // hnsw_search_exact_kernel, the literal kernel: internal failures, queries on which the reference panics, queries whose candidate
 // heap outgrew this launch's scratch (retry_out)
@@ -657,7 +662,8 @@ int DeviceIndex::SearchCall::run_exact(const uint32_t* d_qlist, uint32_t n, cons
     const uint32_t* list = d_qlist;
     for (int pass = 0; pass < 2 && left > 0; ++pass) {
         // pass 0: many workgroups with a bounded candidate heap; pass 1: the queries that outgrew it, every point has room
-        const uint64_t cand_cap = pass == 0 ? std::min<uint64_t>(v.n, 1ull << 17) : v.n;
+        uint64_t cand_cap = pass == 0 ? std::min<uint64_t>(v.n, 1ull << 17) : v.n;
+        if (pass == 0 && kn.literal_cand_cap > 0) cand_cap = std::min<uint64_t>(cand_cap, (uint64_t)kn.literal_cand_cap);  // test hook
         const uint64_t heap_stride = ef + 2 + cand_cap;
         const uint64_t per_block = bm_slice + heap_stride * sizeof(hent_t);
         ExactArgs x{};
@@ -950,7 +956,8 @@ int DeviceIndex::SearchCall::pair_pass() {
     {   // HBM bitmaps for the halves whose table fills up: two slices per workgroup, within the 4 GiB budget
         a.bitmap_words = (v.n + 31) / 32;
         const uint64_t slice = (uint64_t)a.bitmap_words * sizeof(uint32_t);
-        const uint64_t blocks = std::min<uint64_t>(2ull * grid, std::max<uint64_t>(2, (4ull << 30) / slice));
+        const uint64_t budget = kn.bitmap_slices > 0 ? (uint64_t)kn.bitmap_slices : (4ull << 30) / slice;  // (test hook: a cap in slices)
+        const uint64_t blocks = std::min<uint64_t>(2ull * grid, std::max<uint64_t>(2, budget));
         HIP_TRY(w.bitmap.ensure(blocks * slice));
         a.bitmap = w.bitmap.as<uint32_t>();
         a.bitmap_blocks = (uint32_t)blocks;
@@ -1042,7 +1049,8 @@ int DeviceIndex::SearchCall::relaunch_loop() {
             // HBM bitmaps for the in-launch fallback: one slice per workgroup, within a 4 GiB budget
             a.bitmap_words = (v.n + 31) / 32;
             const uint64_t slice = (uint64_t)a.bitmap_words * sizeof(uint32_t);
-            uint64_t blocks = std::min<uint64_t>(grid, std::max<uint64_t>(1, (4ull << 30) / slice));
+            const uint64_t budget = kn.bitmap_slices > 0 ? (uint64_t)kn.bitmap_slices : (4ull << 30) / slice;  // (test hook: a cap in slices)
+            uint64_t blocks = std::min<uint64_t>(grid, std::max<uint64_t>(1, budget));
             if (table == TABLE_GLOBAL_BITMAP) grid = (uint32_t)blocks;  // every workgroup needs one
             HIP_TRY(w.bitmap.ensure(blocks * slice));
             a.bitmap = w.bitmap.as<uint32_t>();
@@ -1068,7 +1076,7 @@ int DeviceIndex::SearchCall::relaunch_loop() {
         ++launches;
         HIP_TRY(read_ctrl(SC_BYTES, true));
         n_flagged = ctrl()[SC_FLAGGED];     // not resolved in the launch (cumulative over relaunches)
-        n_literal += ctrl()[SC_LITERAL];    // resolved with the literal heaps inside the launch
+        n_literal = ctrl()[SC_LITERAL];     // resolved with the literal heaps inside a launch (word 5 is not zeroed between launches: cumulative too)
         if (launches == 1 && table != TABLE_GLOBAL_BITMAP && !env_forced && nq >= 256) table_feedback();
         if (ctrl()[SC_RETRY] == 0) break;
         // some queries visited more points than the table holds and had no bitmap slice: rerun only those

@@ -37,6 +37,10 @@ struct Knobs {
     int build_wg = -1;           // HNSWGPU_BUILD_WG (test hook): cap on the workgroups of the two construction kernels, so that one wavefront handles many points of a window
     int build_hash_bits = -1;    // HNSWGPU_BUILD_HASH_BITS (test hook): the construction search's visited-table size (clamped like the default)
     int64_t filter_set_bytes = -1;  // HNSWGPU_FILTER_SET_MB (MiB, may be a fraction): bound on the bitmaps one launch of a filter-set search holds (unset: 256 MiB)
+    int bitmap_slices = -1;      // HNSWGPU_BITMAP_SLICES (test hook): cap on the HBM visited-bitmap slices of a search launch, in place of what 4 GiB hold (1 ..; the
+                                 // pair pass keeps its floor of 2) -- workgroups without a slice hand their overflowing queries back, and the call relaunches
+    int literal_cand_cap = -1;   // HNSWGPU_LITERAL_CAND_CAP (test hook): cap on the candidate-heap capacity of the literal kernel's FIRST pass (64 ..; unset:
+                                 // min(n, 2^17)) -- queries that outgrow it go through its second pass, which has room for every point
 };
 const Knobs& knobs();
 void reload_knobs();

@@ -1696,7 +1696,7 @@ __device__ __attribute__((noinline)) void finish_query(const void* kargs, QueryE
     const uint32_t feedback = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.feedback);
     const uint32_t k = ka->a.k;
     uint32_t* const counters = ka->a.overflow_count;
-    if (out_status == 3u && lane == 0) atomicAdd(counters + 4, 1u);  // ctrl[5]: answered with the literal heaps
+    if (out_status == 3u && status != 1u && lane == 0) atomicAdd(counters + 4, 1u);  // ctrl[5]: answered with the literal heaps (not: given up after a replay, searched again)
     if (status == 2u) {  // flagged: (A)-(C) met and not resolved in this launch
         uint32_t* const tie_list = ka->a.tie_list;
         if (tie_list != nullptr && lane == 0) tie_list[atomicAdd(counters + 3, 1u)] = q;

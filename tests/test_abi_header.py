@@ -80,3 +80,15 @@ def test_every_exported_symbol_has_a_parsed_prototype(native):
     # and the package's own copy of the header (what a relocated package binds from) is the tree's
     pkg = os.path.join(os.path.dirname(native.LIB_PATH), "hnsw_mi355x.h")
     assert os.path.exists(pkg) and open(pkg).read() == open(HEADER).read()
+
+
+def test_the_relaunch_test_hooks_are_documented_as_such():
+    """HNSWGPU_BITMAP_SLICES / HNSWGPU_LITERAL_CAND_CAP: named where hnswgpu_reload_env lists the hooks it re-reads, and marked
+    "test hook" in the knob list (their parsing, clamping and reloading need a device: tests/test_gpu_relaunch.py)"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "hnsw_mi355x.h")).read()
+    comment = header[:header.index("int hnswgpu_reload_env(void);")].rsplit("/*", 1)[1]
+    knobs = open(os.path.join(root, "INTEGRATION.md"), encoding="utf-8").read()
+    for name in ("HNSWGPU_BITMAP_SLICES", "HNSWGPU_LITERAL_CAND_CAP"):
+        assert name in comment, name
+        assert f"`{name}=" in knobs and "test hook" in knobs[knobs.index(f"`{name}="):][:80], name
