@@ -1,7 +1,7 @@
 // lane_lab.inc -- included at the end of search_kernels.inc by the one translation unit that carries the metric-independent helpers.
 // =======================================================================================
 // Lane lab: the wave-level algorithms of the search kernels -- the memory heap (heap_push / heap_push_batch / heap_pop / heap_pop3 /
-// heap_sift_down_range), the register heap (RegHeap), the result set (r_insert, merge_list) and the 16-bit-cell visited table
+// heap_push_lds / heap_pop_lds / heap_sift_down_range), the register heap (RegHeap), the result set (r_insert, merge_list) and the 16-bit-cell visited table
 // (cell16_test / cell16_insert / visit_cell16) -- run from a SCRIPT by one wavefront; every observable result and the final state
 // come back.  tests/test_gpu_lane_lab.py fuzzes these very functions against the oracle's BinaryHeap (src/hnsw.rs:283-297 orders
 // its entries), a sequential accept rule (src/hnsw.rs:1028-1053) and a Python set; the Python models of rounds 3-4 only generate
@@ -24,7 +24,9 @@ __device__ __forceinline__ void lab_load_lanes(const uint32_t* lanes, uint32_t s
     de = __uint_as_float(lanes[((size_t)set * 64u + (uint32_t)lane) * 2u]);
     idc = lanes[((size_t)set * 64u + (uint32_t)lane) * 2u + 1u];
 }
-// mode 0: BinaryHeap in memory (top p0 entries in LDS, the rest in the global slice); p1: pops through heap_pop (0) / heap_pop3 (1)
+// mode 0: BinaryHeap in memory (top p0 entries in LDS, the rest in the global slice); p1: pops through heap_pop (0) / heap_pop3 (1) /
+// heap_pop_lds (2; 3: the form a replayed pop uses, whose root is neither read nor reported); p2 = 2: pushes through heap_push_lds.
+// The LDS-only operations need the whole heap in LDS: the host refuses a script whose heap would outgrow p0 entries with them.
 __device__ void lab_memheap(const LaneLabArgs& A, LabEmit& E, hent_t* lds, int lane) {
     const HeapMem H{lds, A.scratch, A.p0};
     uint32_t len = 0;
@@ -33,11 +35,18 @@ __device__ void lab_memheap(const LaneLabArgs& A, LabEmit& E, hent_t* lds, int l
         if (op == LAB_PUSH) {  // p2 != 0: without the parent probe (the form a log replay uses)
             if (len < A.scratch_cap) {
                 if (A.p2 == 0u) heap_push(H, len, ((hent_t)a << 32) | b, lane);
-                else heap_push<false>(H, len, ((hent_t)a << 32) | b, lane);
+                else if (A.p2 == 1u) heap_push<false>(H, len, ((hent_t)a << 32) | b, lane);
+                else if (len < A.p0) heap_push_lds(lds, len, ((hent_t)a << 32) | b, lane);
             }
         } else if (op == LAB_POP) {
             if (len == 0u) { E.put_h(~0ull, lane); continue; }
-            E.put_h(A.p1 == 0u ? heap_pop(H, len, lane) : heap_pop3(H, len, lane), lane);
+            if (A.p1 >= 2u) {
+                if (len > A.p0) continue;
+                if (A.p1 == 2u) E.put_h(heap_pop_lds<true>(lds, len, lane), lane);
+                else (void)heap_pop_lds<false>(lds, len, lane);
+            } else {
+                E.put_h(A.p1 == 0u ? heap_pop(H, len, lane) : heap_pop3(H, len, lane), lane);
+            }
         } else if (op == LAB_PUSH_LANES) {  // BinaryHeap::push of {-de, idc} for the lanes of the mask, lowest lane first
             float de;
             uint32_t idc;

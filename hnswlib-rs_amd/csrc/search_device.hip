@@ -311,7 +311,8 @@ int device_count() {
 int lane_lab_device(int device, uint32_t mode, uint32_t p0, uint32_t p1, uint32_t p2, const uint32_t* ops, uint32_t n_ops,
                     const uint32_t* lanes, uint32_t n_lane_sets, uint32_t* out, uint32_t out_words, std::string& err) {
     if (mode > 3u || out_words < 1u) { err = "bad lane-lab mode"; return ERR_ARG; }
-    if (mode == 0u && p0 > 1024u) { err = "lane lab: at most 1024 heap entries in LDS"; return ERR_ARG; }
+    if (mode == 0u && p0 > 4096u) { err = "lane lab: at most 4096 heap entries in LDS"; return ERR_ARG; }
+    if (mode == 0u && (p1 > 3u || p2 > 2u)) { err = "lane lab: unknown heap operation"; return ERR_ARG; }
     if ((mode == 1u || mode == 2u) && p0 != 1u && p0 != 2u && p0 != 4u) { err = "lane lab: 1, 2 or 4 slots per lane"; return ERR_ARG; }
     if (mode == 2u && (p1 == 0u || p1 > 64u * p0)) { err = "lane lab: ef beyond the result set"; return ERR_ARG; }
     if (mode == 3u && (p0 < 4u || p0 > 12u || p2 > 13u || p1 > 31u || p1 + 3u < p0 || p1 - (p0 - 3u) != p2)) { err = "lane lab: table geometry"; return ERR_ARG; }
@@ -324,6 +325,21 @@ int lane_lab_device(int device, uint32_t mode, uint32_t p0, uint32_t p1, uint32_
         if ((op == LAB_PUSH_LANES || op == LAB_MERGE || op == LAB_BATCH) && c >= n_lane_sets) {
             err = "lane lab: op " + std::to_string(i) + " names lane set " + std::to_string(c) + " of " + std::to_string(n_lane_sets);
             return ERR_ARG;
+        }
+    }
+    // the LDS-only heap operations (p1 >= 2, p2 == 2) address LDS alone: a script whose heap would outgrow the p0 entries
+    // kept there is refused (a pop of an empty heap is reported by the kernel and changes nothing)
+    if (mode == 0u && (p1 >= 2u || p2 == 2u)) {
+        uint64_t len = 0;
+        for (uint32_t i = 0; i < n_ops; ++i) {
+            const uint32_t op = ops[4u * i];
+            if (op == LAB_PUSH) len += 1;
+            else if (op == LAB_PUSH_LANES) len += (uint64_t)__builtin_popcount(ops[4u * i + 1u]) + (uint64_t)__builtin_popcount(ops[4u * i + 2u]);
+            else if (op == LAB_POP && len > 0) len -= 1;
+            if (len > p0) {
+                err = "lane lab: op " + std::to_string(i) + " grows the heap to " + std::to_string(len) + " entries, the LDS-only operations hold " + std::to_string(p0);
+                return ERR_ARG;
+            }
         }
     }
     DeviceGuard on_device(device);
@@ -348,7 +364,7 @@ int lane_lab_device(int device, uint32_t mode, uint32_t p0, uint32_t p1, uint32_
     a.scratch_cap = scratch_cap;
     a.out = d_out.as<uint32_t>();
     a.out_cap = out_words;
-    HIP_TRY(launch_lane_lab(nullptr, 16384, a));
+    HIP_TRY(launch_lane_lab(nullptr, std::max<size_t>(16384, mode == 0u ? (size_t)p0 * sizeof(hent_t) : 0), a));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, d_out.p, (size_t)out_words * 4, hipMemcpyDeviceToHost));
     return OK;

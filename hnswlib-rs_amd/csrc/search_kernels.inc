@@ -1033,6 +1033,90 @@ __device__ __forceinline__ hent_t heap_pop3(const HeapMem& H, uint32_t& len, int
     return root;
 }
 
+// ---- The same two operations for a heap that lies in LDS as a whole (every index touched is below the heap's lds_cap: the
+// caller checks len, pushes to come included, against it).  The replay of a heap-operation log runs on these when the literal
+// candidate heap fits: plain ds reads and writes -- no per-lane choice between LDS and the global slice, no wait for global
+// stores --, one store per push, and a pop that walks only the rounds its length needs.
+// BinaryHeap::push without the parent probe: lane j >= 1 reads ancestor j of the new position, the ancestors the item passes
+// (it stops on <=) move down one step and the item takes the place of the last of them: ONE predicated store.
+__device__ __forceinline__ void heap_push_lds(hent_t* h, uint32_t& len, hent_t item, int lane) {
+    const uint32_t pos1 = len + 1u;  // 1-based index of the new position; its ancestor j is pos1 >> j
+    len += 1;
+    // (lane predicates are folded into the arithmetic: a mask held in scalar registers is a pair of them for the whole replay)
+    const uint32_t p1 = pos1 >> (lane < 31 ? lane : 31);  // pos1 < 2^31: lanes >= 31 hold 0 = no ancestor; lane 0 holds pos1 itself
+    const hent_t e = h[(p1 > 1u ? p1 : 1u) - 1u];        // (lane 0 and the lanes past the root read some entry: not looked at)
+    // the first lane >= 1 that is past the root or holds an ancestor the item does not pass (lane 31 is past the root: stop != 0)
+    const unsigned long long stop = __ballot(p1 == 0u || hkey(item) <= hkey(e)) & ~1ull;
+    const uint32_t moved = (uint32_t)ctz64(stop) - 1u;  // ancestors 1..moved move down one step
+    // lane j in 1..moved: ancestor j goes to the place of ancestor j - 1; lane moved + 1: the item goes to the place of ancestor `moved`
+    const uint32_t jm1 = (uint32_t)lane - 1u;
+    if (jm1 <= moved) h[(pos1 >> (jm1 & 31u)) - 1u] = jm1 == moved ? item : e;
+    wave_lds_fence();
+}
+
+// BinaryHeap::pop (swap-remove the root with the last element, sift_down_to_bottom(0), sift_up) in rounds of five levels, as
+// heap_pop3 -- the 63 lanes hold the subtree below the node reached so far, every lane compares its two children, the
+// greater-child walk (right child on <=) is five scalar bit tests -- but as a loop that runs while the walk has not met the
+// bottom: one round below 64 entries, two below 2 048, three below 65 536.  Nothing is kept from round to round: on a root path
+// of a heap the keys never rise, so the path nodes that `last` is <= to -- those move up one step, `last` comes to lie on the
+// deepest of them (sift_up stops there) -- are the path's top part, and each round stores its own moves; a round that holds a
+// path node `last` is greater than is the last one.  (Keys are never NaN: the reference's order panics on one.)
+// ROOT = false: the popped root is neither read out nor returned (a replayed pop throws it away).
+template <bool ROOT>
+__device__ __forceinline__ hent_t heap_pop_lds(hent_t* h, uint32_t& len, int lane) {
+    const hent_t last = h[len - 1u];
+    len -= 1;
+    if (len == 0u) return last;
+    const uint32_t end = len;
+    // lane L holds the node with 1-based index L + 1 of the 63-node subtree rooted (lane 0) at the round's start
+    const uint32_t L1 = (uint32_t)lane + 1u;
+    const uint32_t t = 31u - (uint32_t)__clz((int)L1);
+    // (lane predicates folded into the arithmetic, as in heap_push_lds: lane 63 holds no node -- its index lies past every heap --,
+    // and the lanes of the round's last level, 31..62, have their children in the next round -- theirs lie past every heap)
+    const uint32_t off = lane < 63 ? L1 - (1u << t) - 1u : 0x40000000u;
+    const uint32_t coff = lane <= 30 ? 1u : 0x40000000u;
+    const uint32_t cl = ((2u * (uint32_t)lane + 1u) & 63u) << 2;  // ds_bpermute address of the lane of the left child
+    hent_t root = 0ull;
+    uint32_t p1 = 1u;  // 1-based index of the round's root
+    for (;;) {
+        const uint32_t idx = (p1 << t) + off;  // (< 2^22 for heaps below 65 536 entries)
+        const hent_t ent = h[idx < end ? idx : 0u];
+        if constexpr (ROOT) {
+            if (p1 == 1u) root = readlane_h(ent, 0);
+        }
+        const int khi = (int)(uint32_t)(ent >> 32);
+        const float kl = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((int)cl, khi));
+        const float kr = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((int)cl + 4, khi));
+        // lanes 0..30 have their children in the round: left child at 2 idx + 1, right child at 2 idx + 2
+        const uint32_t lc = 2u * idx + coff;
+        const unsigned long long hm = __ballot(lc < end);
+        const unsigned long long pm = __ballot(lc + 1u < end && kl <= kr);
+        uint32_t cur = 0;
+        unsigned long long bits = 0ull;
+        bool more = false;
+        for (int step = 0; step < 5; ++step) {
+            if (((hm >> cur) & 1ull) == 0ull) break;
+            cur = 2u * cur + 1u + (uint32_t)((pm >> cur) & 1ull);
+            bits |= 1ull << cur;
+            if (step == 4) more = true;  // five levels walked and not at the bottom yet
+        }
+        const bool on_path = ((bits >> lane) & 1ull) != 0ull;
+        const unsigned long long up = __ballot(on_path && hkey(last) <= hkey(ent));
+        if (on_path && ((up >> lane) & 1ull) != 0ull) h[(idx - 1u) >> 1] = ent;
+        if (up == bits && more) {  // every path node of the round moved up: the next round starts at the deepest one
+            p1 = readlane_u(idx, (int)cur) + 1u;
+            wave_lds_fence();
+            continue;
+        }
+        // `last` lies on the deepest path node it is <= to; none in this round: on the round's root (the deepest so far)
+        const int lstar = up != 0ull ? 63 - __clzll((long long)up) : 0;
+        if (lane == lstar) h[idx] = last;
+        break;
+    }
+    wave_lds_fence();
+    return root;
+}
+
 // sift_down_range(0, end) of into_sorted_vec: descend along the greater child, stop as soon as elt >= child
 __device__ __forceinline__ void heap_sift_down_range(const HeapMem& H, uint32_t end, int lane) {
     const hent_t elt = hload(H, 0u);
@@ -1566,25 +1650,48 @@ __device__ HNSW_COLD LiteralPop literal_candidate_pop(const void* kargs, uint32_
     out.n_ops = to - from + 1u;
     out.t_pops = 0;
 #endif
+    // a chunk of the log (<= 64 entries) whose pushes leave the heap within its LDS part is replayed with the LDS-only
+    // operations (the heap only grows by pushes: no index of the chunk then reaches the global slice); so is the final pop
+    const auto lds_fits = [&](uint32_t len) { return len <= Cq.lds_cap && len <= cand_cap; };
     hfence();  // the log's stores have landed (entry 0 is the entry point's push, :958-963)
     bool ok = true;
     for (uint32_t base = from; base < to && ok; base += 64) {
         const uint32_t li = base + (uint32_t)lane;
         const hent_t mine = li < to ? __hip_atomic_load(oplog + li, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
         const uint32_t cntb = to - base < 64u ? to - base : 64u;
-        for (uint32_t t = 0; t < cntb; ++t) {
-            const hent_t e = readlane_h(mine, (int)t);
-            if (e == LOG_EXPAND) {
+        // the chunk's entries classified once, all lanes at a time: a bit per marker (= pop), and every push's {-key, id} ready
+        // in its lane -- the serial part below tests a bit and reads a lane
+        const unsigned long long markers = ~__ballot(mine != LOG_EXPAND);  // (lanes past the chunk's end hold 0: no marker)
+        const uint32_t pushes = cntb - popc64(markers);
+        const hent_t item = hmake(-hkey(mine), hid(mine));
+        if (lds_fits(lenC + pushes)) {
+            for (uint32_t t = 0; t < cntb; ++t) {
+                if (((markers >> t) & 1ull) != 0ull) {
 #if HNSW_PHASE_TIMING == 2
-                const unsigned long long tp0 = clock64();
+                    const unsigned long long tp0 = clock64();
 #endif
-                (void)heap_pop3(Cq, lenC, lane);
+                    (void)heap_pop_lds<false>(Cq.lds, lenC, lane);
 #if HNSW_PHASE_TIMING == 2
-                out.t_pops += (uint32_t)(clock64() - tp0);
+                    out.t_pops += (uint32_t)(clock64() - tp0);
 #endif
-            } else {
-                if (lenC >= cand_cap) { ok = false; break; }
-                heap_push<false>(Cq, lenC, hmake(-hkey(e), hid(e)), lane);
+                } else {
+                    heap_push_lds(Cq.lds, lenC, readlane_h(item, (int)t), lane);
+                }
+            }
+        } else {
+            for (uint32_t t = 0; t < cntb; ++t) {
+                if (((markers >> t) & 1ull) != 0ull) {
+#if HNSW_PHASE_TIMING == 2
+                    const unsigned long long tp0 = clock64();
+#endif
+                    (void)heap_pop3(Cq, lenC, lane);
+#if HNSW_PHASE_TIMING == 2
+                    out.t_pops += (uint32_t)(clock64() - tp0);
+#endif
+                } else {
+                    if (lenC >= cand_cap) { ok = false; break; }
+                    heap_push<false>(Cq, lenC, readlane_h(item, (int)t), lane);
+                }
             }
         }
     }
@@ -1593,7 +1700,7 @@ __device__ HNSW_COLD LiteralPop literal_candidate_pop(const void* kargs, uint32_
         if (lenC == 0u) {
             out.rc = 1;
         } else {
-            out.ce = heap_pop3(Cq, lenC, lane);
+            out.ce = lds_fits(lenC) ? heap_pop_lds<true>(Cq.lds, lenC, lane) : heap_pop3(Cq, lenC, lane);
             out.rc = 0;
         }
     }
