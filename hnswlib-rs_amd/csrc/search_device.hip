@@ -68,6 +68,8 @@ Knobs read_knobs() {
     if (k.bitmap_slices < 1) k.bitmap_slices = -1;  // (a launch needs one slice at least)
     k.literal_cand_cap = num("HNSWGPU_LITERAL_CAND_CAP", -1);
     k.literal_cand_cap = k.literal_cand_cap < 1 ? -1 : std::max(64, k.literal_cand_cap);  // (one batch of neighbours at least)
+    k.max_wg = num("HNSWGPU_MAX_WG", -1);
+    if (k.max_wg < 1) k.max_wg = -1;  // (a launch needs one workgroup at least)
     return k;
 }
 std::atomic<const Knobs*> g_knobs{nullptr};
@@ -615,6 +617,8 @@ struct DeviceIndex::SearchCall {
           work((uint32_t)nq_), main_end(w_.ev_ke) {}
     volatile const uint32_t* ctrl() const { return static_cast<volatile uint32_t*>(w.h_ctrl); }
     uint32_t* d_ctrl() const { return static_cast<uint32_t*>(w.d_ctrl); }
+    // the workgroups of a persistent launch behind every other bound: HNSWGPU_MAX_WG (test hook) caps them
+    uint32_t capped(uint64_t grid) const { return (uint32_t)(kn.max_wg > 0 ? std::min<uint64_t>(grid, (uint64_t)kn.max_wg) : grid); }
     struct LaunchShape { size_t lds; int per_cu, strict_cap; bool strict_kernel; };
     hipError_t read_ctrl(size_t bytes, bool record_stop);
     SearchArgs search_args(const uint32_t* list, uint32_t n) const;
@@ -693,7 +697,7 @@ int DeviceIndex::SearchCall::run_exact(const uint32_t* d_qlist, uint32_t n, cons
         HIP_TRY(ks.exact_occupancy(ns, lds, &per_cu));
         per_cu = std::max(1, per_cu);
         uint32_t grid = (uint32_t)std::min<uint64_t>(left, std::max<uint64_t>(1, (16ull << 30) / per_block));
-        grid = std::min<uint32_t>(grid, (uint32_t)ix.num_cu_ * (uint32_t)per_cu);
+        grid = capped(std::min<uint32_t>(grid, (uint32_t)ix.num_cu_ * (uint32_t)per_cu));
         HIP_TRY(w.bitmap.ensure((uint64_t)grid * bm_slice));
         HIP_TRY(w.heaps.ensure((uint64_t)grid * heap_stride * sizeof(hent_t)));
         HIP_TRY(w.retry[0].ensure((uint64_t)n * sizeof(uint32_t)));
@@ -877,8 +881,11 @@ int DeviceIndex::SearchCall::descend(const float* d_queries, const RowFeed* feed
         da.ctrl_words = 16;
         da.pair = pair ? 1u : 0u;
         const uint64_t waves = pair ? (hi - lo + 1) / 2 : hi - lo;
-        HIP_TRY(ks.launch_descend((uint32_t)std::min<uint64_t>(waves, (uint64_t)per_cu * (uint64_t)ix.num_cu_), stream, v, da,
-                                  LaunchEvents{lo == 0 ? w.ev_start : nullptr, nullptr}));
+        const uint32_t grid = capped(std::min<uint64_t>(waves, (uint64_t)per_cu * (uint64_t)ix.num_cu_));
+        if (kn.trace_launch)  // (a line of its own kind: the "[hnswgpu launch]" lines are the search launches)
+            std::fprintf(stderr, "[hnswgpu descent] %llu queries, %d workgroups per CU, two per wavefront %d, %u workgroups\n",
+                         (unsigned long long)(hi - lo), per_cu, (int)pair, grid);
+        HIP_TRY(ks.launch_descend(grid, stream, v, da, LaunchEvents{lo == 0 ? w.ev_start : nullptr, nullptr}));
     }
     return OK;
 }
@@ -958,10 +965,10 @@ int DeviceIndex::SearchCall::pair_pass() {
     HIP_TRY(ks.pair_occupancy(lds, &per_cu));
     if (per_cu < 1) return OK;
     if (kn.pair_wg_per_cu > 0) per_cu = std::min(per_cu, kn.pair_wg_per_cu);
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)per_cu * (uint64_t)ix.num_cu_, (nq + 1) / 2);  // (pairs of queries)
+    const uint32_t grid = capped(std::min<uint64_t>((uint64_t)per_cu * (uint64_t)ix.num_cu_, (nq + 1) / 2));  // (pairs of queries)
     if (kn.trace_launch)
-        std::fprintf(stderr, "[hnswgpu launch] pair pass: %u queries, %d workgroups per CU, %zu bytes of LDS each, tables 2^%u cells\n",
-                     work, per_cu, lds, tb);
+        std::fprintf(stderr, "[hnswgpu launch] pair pass: %u queries, %d workgroups per CU, %zu bytes of LDS each, tables 2^%u cells, %u workgroups\n",
+                     work, per_cu, lds, tb, grid);
     SearchArgs a = search_args(qlist, work);
     a.tbits = tb;
     a.restbits = idbits - (tb - 3u);
@@ -1054,12 +1061,7 @@ int DeviceIndex::SearchCall::relaunch_loop() {
         LaunchShape s{};
         int rc = shape_launch(a, s);
         if (rc != OK) return rc;
-        uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)s.per_cu * (uint64_t)ix.num_cu_, work);
-        if (kn.trace_launch)  // diagnostics: what bounds the resident workgroups of this launch
-            std::fprintf(stderr, "[hnswgpu launch] %u queries, %d workgroups per CU (strict cap %d), %zu bytes of LDS each (literal heap: %u entries), table 2^%u cells, strict %d, work list %s, slots %d, visited set %s\n",
-                         work, s.per_cu, s.strict_cap, s.lds, a.cand_lds, a.tbits, (int)s.strict_kernel,
-                         qlist ? "sorted" : "input order", slots,
-                         table == TABLE_LDS_CELL16 ? "cell16" : table == TABLE_LDS_CELL32 ? "cell32" : "bitmap");
+        uint32_t grid = capped(std::min<uint64_t>((uint64_t)s.per_cu * (uint64_t)ix.num_cu_, work));
         a.retry_out = w.retry[pingpong].as<uint32_t>();
         {
             // HBM bitmaps for the in-launch fallback: one slice per workgroup, within a 4 GiB budget
@@ -1072,6 +1074,11 @@ int DeviceIndex::SearchCall::relaunch_loop() {
             a.bitmap = w.bitmap.as<uint32_t>();
             a.bitmap_blocks = (uint32_t)blocks;
         }
+        if (kn.trace_launch)  // diagnostics: what bounds the resident workgroups of this launch
+            std::fprintf(stderr, "[hnswgpu launch] %u queries, %d workgroups per CU (strict cap %d), %zu bytes of LDS each (literal heap: %u entries), table 2^%u cells, strict %d, work list %s, slots %d, visited set %s, %u workgroups\n",
+                         work, s.per_cu, s.strict_cap, s.lds, a.cand_lds, a.tbits, (int)s.strict_kernel,
+                         qlist ? "sorted" : "input order", slots,
+                         table == TABLE_LDS_CELL16 ? "cell16" : table == TABLE_LDS_CELL32 ? "cell32" : "bitmap", grid);
         a.tie_list = w.tie.as<uint32_t>();
         if (s.strict_kernel) {
             // per-workgroup scratch: the heap-operation log, and the part of the literal candidate heap beyond LDS

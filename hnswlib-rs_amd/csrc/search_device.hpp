@@ -41,6 +41,8 @@ struct Knobs {
                                  // pair pass keeps its floor of 2) -- workgroups without a slice hand their overflowing queries back, and the call relaunches
     int literal_cand_cap = -1;   // HNSWGPU_LITERAL_CAND_CAP (test hook): cap on the candidate-heap capacity of the literal kernel's FIRST pass (64 ..; unset:
                                  // min(n, 2^17)) -- queries that outgrow it go through its second pass, which has room for every point
+    int max_wg = -1;             // HNSWGPU_MAX_WG (test hook): absolute cap on the workgroups of every persistent launch of a search call (descent, pair pass,
+                                 // one-query kernels, literal kernel), applied behind every other bound (1 ..) -- a workgroup then answers many queries in turn
 };
 const Knobs& knobs();
 void reload_knobs();

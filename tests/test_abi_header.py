@@ -92,3 +92,19 @@ def test_the_relaunch_test_hooks_are_documented_as_such():
     for name in ("HNSWGPU_BITMAP_SLICES", "HNSWGPU_LITERAL_CAND_CAP"):
         assert name in comment, name
         assert f"`{name}=" in knobs and "test hook" in knobs[knobs.index(f"`{name}="):][:80], name
+
+
+def test_the_workgroup_cap_test_hook_is_documented_as_such():
+    """HNSWGPU_MAX_WG: held to the rule of the two relaunch hooks -- named where hnswgpu_reload_env lists the hooks it re-reads,
+    marked "test hook" in the knob list -- and named where DESIGN.md describes the persistent grid (its parsing, reloading and
+    effect need a device: tests/test_gpu_workgroup_reuse.py)"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "hnsw_mi355x.h")).read()
+    comment = header[:header.index("int hnswgpu_reload_env(void);")].rsplit("/*", 1)[1]
+    knobs = open(os.path.join(root, "INTEGRATION.md"), encoding="utf-8").read()
+    name = "HNSWGPU_MAX_WG"
+    assert name in comment
+    assert f"`{name}=" in knobs and "test hook" in knobs[knobs.index(f"`{name}="):][:80]
+    design = open(os.path.join(root, "DESIGN.md"), encoding="utf-8").read()
+    grid = design[design.index("persistent grid (`occupancy"):]
+    assert f"`{name}` (test hook)" in grid[:1500]

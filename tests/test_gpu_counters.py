@@ -189,8 +189,11 @@ def shapes_pair(native, oracle, tmp_path_factory):
     return _pair(native, oracle, tmp_path_factory.mktemp("shapes"), X, 12, 60, "DistL2", "sh")
 
 
-@pytest.mark.parametrize("k,ef,slots", [(10, 10, 1), (10, 64, 1), (10, 65, 2), (10, 128, 2), (10, 129, 4), (10, 256, 4),
-                                        (10, 257, 16), (100, 1000, 16), (40, 20, 1)])   # (40, 20): k > ef, ef = max(ef, k)
+RESULT_SET_SHAPES = [(10, 10, 1), (10, 64, 1), (10, 65, 2), (10, 128, 2), (10, 129, 4), (10, 256, 4),   # k, ef, slots per lane
+                     (10, 257, 16), (100, 1000, 16), (40, 20, 1)]                                        # (40, 20): k > ef, ef = max(ef, k)
+
+
+@pytest.mark.parametrize("k,ef,slots", RESULT_SET_SHAPES)
 def test_counters_at_every_result_set_shape(native, shapes_pair, knob, capfd, k, ef, slots):
     o, h = shapes_pair
     Q = uniform(200, 8, 72)

@@ -60,6 +60,19 @@ def _forced_bits(ref, lo=6, hi=12):
     return b
 
 
+def _split_bits(ref, need, lo=6, hi=12):
+    """a first table of 2^b cells that some queries outgrow INSIDE a launch and some do not (_forced_bits sizes the table after the
+    next, 2^(b + 2)), from the oracle's counters: a query that visits more than 0.75 x 2^b points at layer 0 moves to its bitmap
+    slice, one that stays 64 ids (a batch) below that never does (gather_batch's first check).  Asserts `need` queries of each kind;
+    returns b and the two sets."""
+    vis = _visited(ref)
+    sets = {b: (vis > 0.75 * 2 ** b, vis + 64 <= 0.75 * 2 ** b) for b in range(lo, hi + 1)}
+    b = max(sets, key=lambda t: min(sets[t][0].sum(), sets[t][1].sum()))
+    moved, stayed = sets[b]
+    assert moved.sum() >= need and stayed.sum() >= need, (b, int(moved.sum()), int(stayed.sum()), np.percentile(vis, [0, 5, 50, 95, 100]))
+    return b, moved, stayed
+
+
 _QUERIES = re.compile(r"\] (?:pair pass: |literal kernel, pass \d: )?(\d+) queries")
 
 
