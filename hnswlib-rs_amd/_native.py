@@ -22,9 +22,9 @@ _PKG_HEADER = os.path.join(PKG_DIR, "hnsw_mi355x.h")
 HEADER_PATH = _TREE_HEADER if os.path.exists(_TREE_HEADER) else _PKG_HEADER
 # The header is the one description of the C ABI; structures, prototypes and codes below are READ FROM IT (._cheader).
 HEADER = _cheader.load(HEADER_PATH)
-OK, ERR_ARG, ERR_IO, ERR_FORMAT, ERR_DISTANCE, ERR_TYPE, ERR_DEVICE, ERR_EMPTY, ERR_REF_PANIC = (
+OK, ERR_ARG, ERR_IO, ERR_FORMAT, ERR_DISTANCE, ERR_TYPE, ERR_DEVICE, ERR_EMPTY, ERR_REF_PANIC, ERR_CAPACITY = (
     HEADER.constants["HNSWGPU_" + n] for n in ("OK", "ERR_ARG", "ERR_IO", "ERR_FORMAT", "ERR_DISTANCE", "ERR_TYPE", "ERR_DEVICE",
-                                               "ERR_EMPTY", "ERR_REF_PANIC"))
+                                               "ERR_EMPTY", "ERR_REF_PANIC", "ERR_CAPACITY"))
 DIST = {"DistL2": HEADER.constants["HNSWGPU_DIST_L2"], "DistCosine": HEADER.constants["HNSWGPU_DIST_COSINE"],
         "DistDot": HEADER.constants["HNSWGPU_DIST_DOT"], "DistL1": HEADER.constants["HNSWGPU_DIST_L1"],
         "DistHellinger": HEADER.constants["HNSWGPU_DIST_HELLINGER"], "DistJeffreys": HEADER.constants["HNSWGPU_DIST_JEFFREYS"],

@@ -101,6 +101,30 @@ class BatchResult:
         return out
 
 
+class RangeResult:
+    """The answers of a range search in CSR form: query q owns the slots offsets[q] .. offsets[q + 1] of ids, dists, layers and
+    ranks, ascending by (distance, origin id)."""
+
+    def __init__(self, offsets, ids, dists, layers, ranks):
+        self.offsets, self.ids, self.dists, self.layers, self.ranks = offsets, ids, dists, layers, ranks
+
+    @property
+    def counts(self):
+        return np.diff(self.offsets)
+
+    def of(self, q):
+        """(ids, dists, layers, ranks) of query q: views, not copies"""
+        a, b = int(self.offsets[q]), int(self.offsets[q + 1])
+        return self.ids[a:b], self.dists[a:b], self.layers[a:b], self.ranks[a:b]
+
+    def to_neighbours(self):
+        out = []
+        for q in range(len(self.offsets) - 1):
+            ids, dists, layers, ranks = self.of(q)
+            out.append([Neighbour(int(ids[j]), float(dists[j]), (int(layers[j]), int(ranks[j]))) for j in range(len(ids))])
+        return out
+
+
 class Hnsw:
     """Hnsw<f32, D>: owns a hnswgpu_index handle (flat host graph + its HBM replica)."""
 
@@ -374,6 +398,48 @@ class Hnsw:
     def exact_search_filters(self, datas, knbn, filters, filter_of=None):
         """exact_search_filters_flat as Vec<Vec<Neighbour>> in input order."""
         return self.exact_search_filters_flat(datas, knbn, filters, filter_of).to_neighbours()
+
+    # ---- exhaustive exact range search (an extension, like the exact k-NN) ------------------------------------------
+    def exact_range_search_flat(self, datas, radius, allowed_ids=None):
+        """Every point within `radius` (a scalar, or one value per row of `datas`) of every row of `datas`, by exhaustive
+        search on the device in the arithmetic of the index's own search: the eligible points with distance <= radius as
+        f32 values, ascending by (distance, origin id).  allowed_ids as in exact_search_flat.  Returns a RangeResult.
+        One call with a guessed capacity, one more with the exact total when the guess was too small."""
+        datas = np.ascontiguousarray(datas, dtype=np.float32)
+        if datas.ndim != 2:
+            raise HnswError(N.ERR_ARG, "datas must be a (nq, d) matrix")
+        nq, d = datas.shape
+        radii = np.asarray(radius, dtype=np.float32)
+        if radii.ndim == 0:
+            radii = np.full(nq, radii, np.float32)
+        if radii.shape != (nq,):
+            raise HnswError(N.ERR_ARG, "radius must be a scalar or hold one radius per query")
+        radii = np.ascontiguousarray(radii)
+        offsets = np.zeros(nq + 1, np.uint64)
+
+        def empty(cap):
+            return np.zeros(cap, np.uint64), np.zeros(cap, np.float32), np.zeros(cap, np.uint8), np.zeros(cap, np.int32)
+        if self._h is None:
+            return RangeResult(offsets, *empty(0))
+        allowed, n_allowed = None, 0
+        if allowed_ids is not None:
+            n_allowed = len(allowed_ids)
+            allowed = np.ascontiguousarray(allowed_ids, dtype=np.uint64) if n_allowed else np.zeros(1, np.uint64)
+        cap = max(1024, 32 * nq)
+        for attempt in range(2):
+            ids, dists, layers, ranks = empty(cap)
+            rc = self._lib.hnswgpu_exact_range_search_batch(self._h, _p(datas), nq, d, _p(radii), _p(allowed), n_allowed, cap, _p(offsets),
+                                                            _p(ids), _p(dists), _p(layers), _p(ranks))
+            if rc != N.ERR_CAPACITY or attempt == 1:
+                break
+            cap = int(offsets[nq])
+        _check(rc)
+        total = int(offsets[nq])
+        return RangeResult(offsets, ids[:total], dists[:total], layers[:total], ranks[:total])
+
+    def exact_range_search(self, datas, radius, allowed_ids=None):
+        """exact_range_search_flat as Vec<Vec<Neighbour>> in input order."""
+        return self.exact_range_search_flat(datas, radius, allowed_ids).to_neighbours()
 
     def recall_flat(self, datas, knbn, ef, allowed_ids=None):
         """The two recalls the reference's examples print (examples/ann-sift1m-128-euclidean.rs:172-186), for this index's

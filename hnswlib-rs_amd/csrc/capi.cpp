@@ -875,6 +875,80 @@ int hnswgpu_exact_search_batch_filter_set_device(const hnswgpu_index* cidx, cons
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
+// ---- exact range search: every eligible point within a query's radius (exact_knn.hip holds the device side)
+extern "C++" {
+namespace hnswgpu {
+__attribute__((weak)) int exact_range_host(const DeviceIndex&, const std::vector<uint64_t>&, const float*, uint64_t, uint64_t, const float*,
+                                           const uint64_t*, uint64_t, uint64_t, uint64_t*, uint64_t*, float*, uint8_t*, int32_t*, std::string&);
+__attribute__((weak)) int exact_range_device(const DeviceIndex&, const std::vector<uint64_t>&, const float*, uint64_t, uint64_t, const float*,
+                                             const uint64_t*, uint64_t, uint64_t, uint64_t*, uint64_t*, float*, uint8_t*, int32_t*, void*, std::string&);
+}  // namespace hnswgpu
+}  // extern "C++"
+// the checks both entries share; the handle's lock is held (shared)
+static int exact_range_call(const hnswgpu_index* idx, const void* queries, uint64_t nq, uint64_t d, const void* radii, const void* allowed,
+                            uint64_t n_allowed, uint64_t cap, const void* out_offsets, const void* out_ids, const void* out_dists) {
+    const uint64_t dim = idx->builder ? idx->builder->dimension() : (idx->flat ? idx->flat->dimension : 0);
+    if (!out_offsets) return fail(HNSWGPU_ERR_ARG, "null out_offsets: the offsets are written by every call");
+    if (nq != 0 && !queries) return fail(HNSWGPU_ERR_ARG, "null queries");
+    if (nq != 0 && !radii) return fail(HNSWGPU_ERR_ARG, "null radii: every query names its radius");
+    if (cap != 0 && (!out_ids || !out_dists)) return fail(HNSWGPU_ERR_ARG, "cap > 0 with null out_ids or out_dists (the count-only call is cap == 0)");
+    if (nq > 0xFFFFFFF0ull) return fail(HNSWGPU_ERR_ARG, "too many queries in one batch");
+    if (dim != 0 && d != dim) return fail(HNSWGPU_ERR_ARG, "query dimension differs from the index dimension");
+    if (n_allowed != 0 && !allowed) return fail(HNSWGPU_ERR_ARG, "null filter");
+    if (idx->arithmetic != HNSWGPU_ARITH_SCALAR)
+        return fail(HNSWGPU_ERR_ARG, "exact range search answers in the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
+    return HNSWGPU_OK;
+}
+
+int hnswgpu_exact_range_search_batch(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, const float* radii,
+                                     const uint64_t* allowed_ids, uint64_t n_allowed, uint64_t cap, uint64_t* out_offsets, uint64_t* out_ids,
+                                     float* out_dists, uint8_t* out_layer, int32_t* out_rank) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    int rc = exact_range_call(idx, queries, nq, d, radii, allowed_ids, n_allowed, cap, out_offsets, out_ids, out_dists);
+    if (rc != HNSWGPU_OK) return rc;
+    for (uint64_t i = 1; i < n_allowed; ++i)  // `impl FilterT for Vec<usize>` is a binary search: the vector must be sorted
+        if (allowed_ids[i - 1] > allowed_ids[i]) return fail(HNSWGPU_ERR_ARG, "the id vector of a filter must be sorted ascending");
+    const bool empty = idx->builder ? idx->builder->nb_point() == 0 : (!idx->flat || idx->flat->n == 0);
+    if (empty || nq == 0) {  // no point, or no query: every answer is empty
+        std::memset(out_offsets, 0, (nq + 1) * sizeof(uint64_t));
+        return HNSWGPU_OK;
+    }
+    if (!hnswgpu::exact_range_host) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = primary_replica(idx, sl, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    rc = hnswgpu::exact_range_host(*dev, idx->flat->origin_id, queries, nq, d, radii, allowed_ids, n_allowed, cap, out_offsets, out_ids, out_dists,
+                                   out_layer, out_rank, err);
+    if (rc != OK) return fail(rc, err);
+    return HNSWGPU_OK;
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswgpu_exact_range_search_batch_device(const hnswgpu_index* cidx, const float* d_queries, uint64_t nq, uint64_t d, const float* d_radii,
+                                            const uint64_t* d_allowed_ids, uint64_t n_allowed, uint64_t cap, uint64_t* d_out_offsets,
+                                            uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, void* stream) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    int rc = exact_range_call(idx, d_queries, nq, d, d_radii, d_allowed_ids, n_allowed, cap, d_out_offsets, d_out_ids, d_out_dists);
+    if (rc != HNSWGPU_OK) return rc;
+    if (!hnswgpu::exact_range_device) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = idx->primary >= 0 ? idx->replica(idx->primary) : nullptr;
+    if (!dev || idx->dev_stale || idx->flat_stale || !idx->flat)
+        return fail(HNSWGPU_ERR_DEVICE, "index is not resident on a device: call hnswgpu_upload first");
+    std::string err;
+    rc = hnswgpu::exact_range_device(*dev, idx->flat->origin_id, d_queries, nq, d, d_radii, d_allowed_ids, n_allowed, cap, d_out_offsets, d_out_ids,
+                                     d_out_dists, d_out_layer, d_out_rank, stream, err);
+    if (rc != OK) return fail(rc, err);
+    return HNSWGPU_OK;
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
 static DeviceIndex* any_replica(hnswgpu_index* idx) {
     if (idx->primary >= 0 && idx->replica(idx->primary)) return idx->replica(idx->primary);
     return nullptr;

@@ -60,6 +60,14 @@ int exact_filter_set_host(const DeviceIndex& dev, const std::vector<uint64_t>& o
 int exact_filter_set_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* d_queries, uint64_t nq, uint64_t d,
                             uint64_t k, const FilterSet& d_set, uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer,
                             int32_t* d_out_rank, uint32_t* d_out_counts, void* stream, std::string& err);
+// the device side of hnswgpu_exact_range_search_batch(_device), defined in exact_knn.hip and referred to weakly in the same way.
+// They return HNSWGPU_ERR_CAPACITY, the offsets complete and no out slot written, when the answers need more than cap slots.
+int exact_range_host(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* queries, uint64_t nq, uint64_t d,
+                     const float* radii, const uint64_t* allowed, uint64_t n_allowed, uint64_t cap, uint64_t* out_offsets, uint64_t* out_ids,
+                     float* out_dists, uint8_t* out_layer, int32_t* out_rank, std::string& err);
+int exact_range_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* d_queries, uint64_t nq, uint64_t d,
+                       const float* d_radii, const uint64_t* d_allowed, uint64_t n_allowed, uint64_t cap, uint64_t* d_out_offsets,
+                       uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, void* stream, std::string& err);
 }  // namespace hnswgpu
 
 // No C++ exception may cross the C ABI: every entry point is `try { ... HNSWGPU_CAPI_GUARD_END(ret)`

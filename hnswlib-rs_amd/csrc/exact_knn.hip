@@ -20,7 +20,18 @@
 //
 // Keys are unique (the rank is a permutation), so every step is deterministic and a tie group is cut at position k by DataId --
 // and a query's answer does not depend on which tile, group or chunk it is served in.
+//
+// Range search (the device side of hnswgpu_exact_range_search_batch / _device; the entries are in capi.cpp): every eligible row
+// with dist <= the query's radius, in the same key order.  DESIGN.md "Exact range search".
+//   exact_range_slab_kernel    the slab kernel's tile and chain without the lists.  Count pass: a ballot and a popcount per
+//                              (query, 64 rows) into a counter per (query, slab).  Fill pass: the same loop, the hitting lanes
+//                              write their keys, compacted by the ballot's prefix, at the (query, slab) base.
+//   exact_range_scan_kernel    the counters, query major and slab minor, into the CSR offsets and into each slab's base
+//   (rocPRIM)                  every query's segment of keys sorted ascending
+//   exact_range_decode_kernel  keys into ids, distances and p_ids
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_segmented_radix_sort.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
 
 #include <algorithm>
 #include <cstring>
@@ -636,6 +647,423 @@ uint64_t filter_set_budget() {
     return knob >= 0 ? (uint64_t)knob : 256ull << 20;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- range search
+constexpr uint64_t RANGE_HITS_PER_PASS = 8ull << 20;  // answers one fill pass holds at most (HNSWGPU_RANGE_HITS_PER_PASS), or one query's
+constexpr uint64_t RANGE_TILE_BUDGET = 64ull << 20;   // bytes of tiled queries and counters per chunk of tiles
+
+typedef __attribute__((address_space(4))) const float* ufloat_ptr_t;
+typedef __attribute__((address_space(4))) const uint64_t* uquad_ptr_t;
+
+struct ExactRangeArgs {
+    const float* qt;        // as ExactKnnArgs
+    const double* qnorm;
+    const float* radius;    // [nq] the chunk's radii
+    const uint32_t* rank;
+    const uint32_t* allow;
+    const double* nrm2;
+    uint32_t* cnt;          // [nq][n_slabs]; count pass: the hits of (query, slab), written.  Fill pass: the hits of the query in the slabs
+                            // before this one, read (nullptr: one slab)
+    const uint64_t* offs;   // fill pass: [nq] where each query's answer starts among the batch's answers
+    uint64_t* keys;         // fill pass: the chunk's keys, slot 0 being answer key_base of the batch; nullptr: count pass
+    uint64_t key_base;
+    uint32_t key_cap;       // slots behind keys
+    uint32_t nq;
+    uint32_t nchunk;
+    uint32_t slab_rows;
+    uint32_t n_slabs;
+};
+
+// At most this many waves per SIMD: without the lists the loop needs 40 VGPRs and eight waves would fit, but every wavefront
+// streams its tile's queries through the scalar cache (8 KB per tile at d = 128), and with more tiles resident than the cache
+// holds the scalar loads the loop waits for slow down: 1M x 128 DistL2, 10 000 queries, count pass 238 ms uncapped, 189 ms at
+// five, 161 ms at four (the k-NN kernel's 88 VGPRs give it five).
+#ifndef HNSW_RANGE_MAX_WAVES
+#define HNSW_RANGE_MAX_WAVES 4
+#endif
+// exact_knn_slab_kernel's loop; per query of the tile the radius and the counter (fill pass: the next slot) are wave-uniform
+template <int METRIC>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(
+    METRIC == DIST_JEFFREYS || METRIC == DIST_JENSENSHANNON ? 2 : (HNSW_RANGE_MAX_WAVES < 4 ? HNSW_RANGE_MAX_WAVES : 4), HNSW_RANGE_MAX_WAVES)))
+void exact_range_slab_kernel(DeviceIndexView ix, ExactRangeArgs a) {
+    typedef typename std::conditional<METRIC == DIST_COSINE, double, float>::type ACC;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t slab = blockIdx.x, tile = blockIdx.y;
+    const uint32_t lo = slab * a.slab_rows;
+    const uint32_t hi = ix.n - lo < a.slab_rows ? ix.n : lo + a.slab_rows;
+    const uint32_t nvalid = a.nq - tile * (uint32_t)TQ < (uint32_t)TQ ? a.nq - tile * (uint32_t)TQ : (uint32_t)TQ;
+    const uint32_t nchunk = a.nchunk;
+    const qtile_ptr_t qc = (qtile_ptr_t)(reinterpret_cast<const v4f*>(a.qt) + (size_t)tile * nchunk * (size_t)TQ);
+    const bool norm_in_tail = METRIC == DIST_COSINE && a.nrm2 == nullptr && nchunk * 4u == ix.row_stride;
+    const bool fill = a.keys != nullptr;
+    float rad[TQ];
+    uint32_t pos[TQ];  // count pass: the hits so far; fill pass: the slot of the next hit
+#pragma unroll
+    for (int t = 0; t < TQ; ++t) {
+        const uint32_t qs = tile * (uint32_t)TQ + ((uint32_t)t < nvalid ? (uint32_t)t : 0u);  // (the slots behind the last query are never counted)
+        rad[t] = ((ufloat_ptr_t)a.radius)[qs];
+        pos[t] = 0u;
+        if (fill) {
+            pos[t] = (uint32_t)(((uquad_ptr_t)a.offs)[qs] - a.key_base);
+            if (a.cnt != nullptr) pos[t] += ((uword_ptr_t)a.cnt)[(size_t)qs * a.n_slabs + slab];
+        }
+    }
+
+    for (uint32_t r0 = lo; r0 < hi; r0 += 64u) {
+        const bool in = r0 + lane < hi;
+        const uint32_t r = in ? r0 + lane : hi - 1u;  // lanes past the slab re-read its last row
+        bool ok = in;
+        if (a.allow != nullptr) ok = in && ((a.allow[r >> 5] >> (r & 31u)) & 1u) != 0u;
+        if (__ballot(ok) == 0ull) continue;  // (wave-uniform) nothing eligible among these 64 rows
+        const float* rowf = ix.vec + (size_t)r * ix.row_stride;
+        const float4* row = reinterpret_cast<const float4*>(rowf);
+        double s2 = 0.;
+        if constexpr (METRIC == DIST_COSINE)
+            s2 = a.nrm2 != nullptr ? a.nrm2[r] : *reinterpret_cast<const double*>(rowf + ix.row_stride - 2u);
+        ACC acc[TQ];
+#pragma unroll
+        for (int t = 0; t < TQ; ++t) acc[t] = 0;
+        float4 x = row[0];
+        for (uint32_t c = 0; c < nchunk; ++c) {
+            const float4 xn = row[c + 1u < nchunk ? c + 1u : c];
+            if (norm_in_tail && c + 1u == nchunk) { x.z = 0.f; x.w = 0.f; }
+#pragma unroll
+            for (int t = 0; t < TQ; ++t) {
+                const v4f q = qc[(size_t)c * TQ + t];
+                chain4<METRIC, ACC>(acc[t], make_float4(q.x, q.y, q.z, q.w), x);
+            }
+            x = xn;
+        }
+        const uint32_t rk = fill ? a.rank[r] : 0u;
+#pragma unroll
+        for (int t = 0; t < TQ; ++t) {
+            if ((uint32_t)t < nvalid) {
+                float v;
+                if constexpr (METRIC == DIST_COSINE) {
+                    const double s1 = ((nrm_ptr_t)a.qnorm)[tile * (uint32_t)TQ + (uint32_t)t];
+                    v = 0.f;
+                    if (s1 > 0. && s2 > 0.) {
+                        const double du = 1. - acc[t] / __builtin_sqrt(s1 * s2);
+                        v = (float)fmax(du, 0.);
+                    }
+                } else {
+                    v = dist_finish<METRIC>(acc[t]);
+                }
+                const bool hit = ok && v <= rad[t];  // (a NaN on either side: no hit)
+                const unsigned long long m = __ballot(hit);
+                if (m != 0ull) {
+                    if (fill && hit) {
+                        const uint32_t p = pos[t] + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                        if (p < a.key_cap) a.keys[p] = make_key(v, rk);
+                    }
+                    pos[t] += popc64(m);
+                }
+            }
+        }
+    }
+    if (!fill && lane < nvalid) {
+        uint32_t c = 0;
+#pragma unroll
+        for (int t = 0; t < TQ; ++t)
+            if (lane == (uint32_t)t) c = pos[t];
+        a.cnt[(size_t)(tile * (uint32_t)TQ + lane) * a.n_slabs + slab] = c;
+    }
+}
+
+// one workgroup: the counters of a chunk, query major and slab minor, into offs[q + 1] = offs[0] + the hits of queries 0 .. q, and
+// in place every counter into the hits of its query in the slabs before it.  offs[0]: set to `base` (set_base), else what the
+// previous chunk left there.
+__global__ __launch_bounds__(1024) void exact_range_scan_kernel(uint32_t* __restrict__ cnt, uint32_t nq, uint32_t n_slabs, uint64_t* __restrict__ offs,
+                                                               bool set_base, uint64_t base) {
+    __shared__ uint64_t part[1024];
+    const uint32_t t = threadIdx.x;
+    const uint32_t per = (nq + 1023u) / 1024u;
+    const uint32_t q0 = t * per < nq ? t * per : nq, q1 = nq - q0 < per ? nq : q0 + per;
+    uint64_t sum = 0;
+    for (uint32_t q = q0; q < q1; ++q)
+        for (uint32_t s = 0; s < n_slabs; ++s) sum += cnt[(size_t)q * n_slabs + s];
+    part[t] = sum;
+    __syncthreads();
+    if (t == 0u) {
+        uint64_t run = set_base ? base : offs[0];
+        if (set_base) offs[0] = base;
+        for (uint32_t i = 0; i < 1024u; ++i) { const uint64_t p = part[i]; part[i] = run; run += p; }
+    }
+    __syncthreads();
+    uint64_t run = part[t];
+    for (uint32_t q = q0; q < q1; ++q) {
+        uint32_t in_query = 0;
+        for (uint32_t s = 0; s < n_slabs; ++s) {
+            const uint32_t c = cnt[(size_t)q * n_slabs + s];
+            cnt[(size_t)q * n_slabs + s] = in_query;
+            in_query += c;
+        }
+        run += in_query;
+        offs[q + 1u] = run;
+    }
+}
+
+// one thread per sorted key: the answer it stands for (exact_knn_merge_kernel's decoding; a -0 distance comes back as +0)
+__global__ __launch_bounds__(256) void exact_range_decode_kernel(DeviceIndexView ix, const uint64_t* __restrict__ keys, uint32_t count,
+                                                                const uint32_t* __restrict__ order, uint64_t* __restrict__ out_ids,
+                                                                float* __restrict__ out_dists, uint8_t* __restrict__ out_layer,
+                                                                int32_t* __restrict__ out_rank) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= count) return;
+    const uint64_t key = keys[j];
+    const uint32_t rk = (uint32_t)key < ix.n ? (uint32_t)key : 0u;  // (a rank, whatever the slot holds)
+    const uint32_t flat = order[rk];
+    uint32_t l = 0;
+    while (l + 1 < NB_LAYER_MAX && flat >= ix.layer_offset[l + 1]) ++l;
+    out_ids[j] = ix.origin_id[flat];
+    out_dists[j] = dist_of_key(key);
+    if (out_layer) out_layer[j] = (uint8_t)l;
+    if (out_rank) out_rank[j] = (int32_t)(flat - ix.layer_offset[l]);
+}
+
+hipError_t launch_range_slab(int metric, dim3 grid, hipStream_t stream, const DeviceIndexView& ix, const ExactRangeArgs& a) {
+    switch (metric) {
+        case DIST_L2: hipLaunchKernelGGL((exact_range_slab_kernel<DIST_L2>), grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_COSINE: hipLaunchKernelGGL((exact_range_slab_kernel<DIST_COSINE>), grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_DOT: hipLaunchKernelGGL((exact_range_slab_kernel<DIST_DOT>), grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_L1: hipLaunchKernelGGL((exact_range_slab_kernel<DIST_L1>), grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_HELLINGER: hipLaunchKernelGGL((exact_range_slab_kernel<DIST_HELLINGER>), grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_JEFFREYS: hipLaunchKernelGGL((exact_range_slab_kernel<DIST_JEFFREYS>), grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_JENSENSHANNON: hipLaunchKernelGGL((exact_range_slab_kernel<DIST_JENSENSHANNON>), grid, dim3(64), 0, stream, ix, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// an answer's position among the batch's answers -> its slot in the chunk's keys (the segment bounds of the sort)
+struct RangeSlot {
+    uint64_t base;
+    __host__ __device__ unsigned int operator()(uint64_t v) const { return (unsigned int)(v - base); }
+};
+typedef rocprim::transform_iterator<const uint64_t*, RangeSlot, unsigned int> range_slot_iter_t;
+hipError_t sort_segments(void* temp, size_t& temp_bytes, uint64_t* keys_in, uint64_t* keys_out, uint32_t count, uint32_t segments,
+                         const uint64_t* d_offs, uint64_t base, hipStream_t stream) {
+    const range_slot_iter_t begin(d_offs, RangeSlot{base});
+    return rocprim::segmented_radix_sort_keys(temp, temp_bytes, keys_in, keys_out, count, segments, begin, begin + 1, 0u, 64u, stream);
+}
+
+// the fill pass's plan: the consecutive queries [qa, qb) of [qa, q_end) whose answers fit `budget` slots, at most max_q of them and
+// one at least (a single query may hit every point).  offs: the CSR offsets of the batch, on the host.
+uint64_t range_chunk_end(const uint64_t* offs, uint64_t qa, uint64_t q_end, uint64_t budget, uint64_t max_q) {
+    uint64_t qb = qa + 1;
+    while (qb < q_end && qb - qa < max_q && offs[qb + 1] - offs[qa] <= budget) ++qb;
+    return qb;
+}
+
+// A call's buffers: plain host memory (host) or device memory; `allowed` is device memory either way
+struct RangeCall {
+    bool host;
+    const float* queries;
+    const float* radii;
+    const uint64_t* d_allowed;
+    uint64_t n_allowed;
+    bool filtered;
+    uint64_t cap;
+    uint64_t* offsets;
+    uint64_t* ids;
+    float* dists;
+    uint8_t* layer;
+    int32_t* rank;
+};
+
+// Both entries.  Count pass over every query (host buffers: in blocks of at most 64 MB of queries), the offsets complete on the
+// caller's side; then, when the total fits cap, the fill pass chunk by chunk of the plan: keys, sort, decode -- into the caller's
+// arrays (device) or into a staging area that is copied out (host).  Waits for `stream` before it returns.
+int exact_range(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const RangeCall& io, uint64_t nq, uint64_t d, hipStream_t stream,
+                std::string& err) {
+    const DeviceIndexView& v = dev.view();
+    OnDevice on(dev.device());
+    HIP_TRY(on.status());
+    if (nq == 0) {
+        if (io.host) { io.offsets[0] = 0; return OK; }
+        HIP_TRY(hipMemsetAsync(io.offsets, 0, 8, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return OK;
+    }
+    if (v.n == 0) {  // no point: every answer is empty
+        if (io.host) { std::memset(io.offsets, 0, (nq + 1) * 8); return OK; }
+        HIP_TRY(hipMemsetAsync(io.offsets, 0, (nq + 1) * 8, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return OK;
+    }
+    std::string serr;
+    std::shared_ptr<void> ext = dev.extension([&]() { return make_state(dev, origin_id, serr); });
+    if (!ext) { err = serr.empty() ? "exact range search: no device state" : serr; return ERR_DEVICE; }
+    ExactState* st = static_cast<ExactState*>(ext.get());
+
+    const uint64_t n = v.n;
+    const uint64_t nchunk = (d + 3) / 4;
+    const uint64_t tiles_total = (nq + TQ - 1) / TQ;
+    uint64_t slabs = std::min<uint64_t>(MAX_SLABS, (8192 + tiles_total - 1) / tiles_total);
+    const uint64_t slab_rows = std::max<uint64_t>(MIN_SLAB_ROWS, round_up((n + slabs - 1) / slabs, 64));
+    slabs = (n + slab_rows - 1) / slab_rows;
+    // more than one slab: fewer than 8192 tiles, the batch's counters are 1 MB at most and stay for the fill pass; one slab: a
+    // query's base is its offset, the counters are a chunk's
+    const bool keep = slabs > 1;
+    const uint64_t words = (n + 31) / 32;
+    const uint64_t allow_bytes = io.filtered ? round_up(words * 4, 256) : 0;
+    const uint64_t tile_bytes = round_up(nchunk * TQ * 16, 256) + round_up(TQ * 8, 256);
+    const uint64_t per_tile = tile_bytes + (keep ? 0 : TQ * 4);
+    const uint64_t block_q = io.host ? std::max<uint64_t>(1, std::min<uint64_t>(nq, (64ull << 20) / (d * 4 + 12))) : nq;
+    const uint64_t chunk_tiles = std::min<uint64_t>({(block_q + TQ - 1) / TQ, std::max<uint64_t>(1, RANGE_TILE_BUDGET / per_tile), 65535});
+    const uint64_t cnt_bytes = round_up(keep ? nq * slabs * 4 : chunk_tiles * TQ * 4, 256);
+    const int64_t knob = knobs().range_hits_per_pass;
+    const uint64_t budget = knob > 0 ? (uint64_t)knob : RANGE_HITS_PER_PASS;
+    const uint64_t max_fill_q = std::min<uint64_t>(block_q, chunk_tiles * TQ);
+    // the keys of one fill pass: the budget, or one query's answer where that is larger -- never more than the caller has room for
+    const uint64_t all_pairs = nq > 0xFFFFFFFFull / n ? 0xFFFFFFFFull : nq * n;
+    const uint64_t key_cap = std::min<uint64_t>({std::max(budget, n), all_pairs, io.cap});
+    if (key_cap > 0xFFFFFFF0ull) { err = "index too large for the exact range search"; return ERR_ARG; }
+    size_t temp_bytes = 0;
+    if (key_cap != 0)
+        HIP_TRY(sort_segments(nullptr, temp_bytes, nullptr, nullptr, (uint32_t)key_cap, (uint32_t)max_fill_q, nullptr, 0, stream));
+    const uint64_t keys_bytes = round_up(key_cap * 8, 256);
+    const uint64_t stage_bytes = io.host ? round_up(key_cap * 8, 256) + 2 * round_up(key_cap * 4, 256) + round_up(key_cap, 256) : 0;
+
+    ScratchLease lease(st);
+    HIP_TRY(lease.take(allow_bytes + chunk_tiles * tile_bytes + cnt_bytes + 2 * keys_bytes + round_up(temp_bytes, 256) + stage_bytes + 256));
+    unsigned char* p = static_cast<unsigned char*>(lease.p);
+    uint32_t* d_allow = io.filtered ? reinterpret_cast<uint32_t*>(p) : nullptr; p += allow_bytes;
+    float* d_qt = reinterpret_cast<float*>(p); p += chunk_tiles * round_up(nchunk * TQ * 16, 256);
+    double* d_qnorm = reinterpret_cast<double*>(p); p += chunk_tiles * round_up(TQ * 8, 256);
+    uint32_t* d_cnt = reinterpret_cast<uint32_t*>(p); p += cnt_bytes;
+    uint64_t* d_keys_a = reinterpret_cast<uint64_t*>(p); p += keys_bytes;
+    uint64_t* d_keys_b = reinterpret_cast<uint64_t*>(p); p += keys_bytes;
+    void* d_temp = p; p += round_up(temp_bytes, 256);
+    uint64_t* s_ids = reinterpret_cast<uint64_t*>(p); p += io.host ? round_up(key_cap * 8, 256) : 0;
+    float* s_dists = reinterpret_cast<float*>(p); p += io.host ? round_up(key_cap * 4, 256) : 0;
+    int32_t* s_rank = reinterpret_cast<int32_t*>(p); p += io.host ? round_up(key_cap * 4, 256) : 0;
+    uint8_t* s_layer = p;
+
+    DevMem m_q, m_rad, m_off;
+    if (io.host) {
+        HIP_TRY(hipMalloc(&m_q.p, block_q * d * 4));
+        HIP_TRY(hipMalloc(&m_rad.p, block_q * 4));
+        HIP_TRY(hipMalloc(&m_off.p, (block_q + 1) * 8));
+    }
+    // the offsets on the host: the caller's array, or a copy of it (the plan of the fill pass is made here)
+    std::vector<uint64_t> off_copy;
+    if (!io.host) off_copy.resize(nq + 1);
+    uint64_t* const h_off = io.host ? io.offsets : off_copy.data();
+    h_off[0] = 0;
+
+    struct Drain {
+        hipStream_t s;
+        ~Drain() { (void)hipStreamSynchronize(s); }
+    } drain{stream};
+
+    if (io.filtered) HIP_TRY(launch_allow_bitmap(stream, v.origin_id, v.n, io.d_allowed, io.n_allowed, d_allow));
+    ExactRangeArgs a{};
+    a.qt = d_qt;
+    a.qnorm = d_qnorm;
+    a.rank = static_cast<const uint32_t*>(st->d_rank);
+    a.allow = d_allow;
+    a.nrm2 = dev.side_norms();
+    a.nchunk = (uint32_t)nchunk;
+    a.slab_rows = (uint32_t)slab_rows;
+    a.n_slabs = (uint32_t)slabs;
+    // queries [q0, q0 + cq) of a block into the tiles
+    auto prep = [&](const float* dq, uint64_t cq) -> int {
+        const uint32_t n_slots = (uint32_t)((cq + TQ - 1) / TQ * TQ);
+        hipLaunchKernelGGL(exact_knn_prep_kernel, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, dq, (uint32_t)cq, (uint32_t)d, (uint32_t)nchunk,
+                           n_slots, d_qt, d_qnorm, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0u, (uint32_t*)nullptr);
+        HIP_TRY(hipGetLastError());
+        return OK;
+    };
+    const bool one_block = block_q >= nq;
+    // where block [b0, b0 + bq) has its queries, radii and offsets on the device
+    const float* dq = io.queries;
+    const float* dr = io.radii;
+    uint64_t* doff = io.offsets;
+    auto stage_block = [&](uint64_t b0, uint64_t bq) -> int {
+        if (!io.host) return OK;
+        HIP_TRY(hipMemcpyAsync(m_q.p, io.queries + b0 * d, bq * d * 4, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(m_rad.p, io.radii + b0, bq * 4, hipMemcpyHostToDevice, stream));
+        dq = static_cast<const float*>(m_q.p);
+        dr = static_cast<const float*>(m_rad.p);
+        doff = static_cast<uint64_t*>(m_off.p);
+        return OK;
+    };
+
+    // ---- the count pass
+    for (uint64_t b0 = 0; b0 < nq; b0 += block_q) {
+        const uint64_t bq = std::min(block_q, nq - b0);
+        int rc = stage_block(b0, bq);
+        if (rc != OK) return rc;
+        for (uint64_t q0 = 0; q0 < bq; q0 += chunk_tiles * TQ) {
+            const uint64_t cq = std::min<uint64_t>(chunk_tiles * TQ, bq - q0);
+            if ((rc = prep(dq + q0 * d, cq)) != OK) return rc;
+            a.radius = dr + q0;
+            a.cnt = d_cnt + (keep ? (b0 + q0) * slabs : 0);
+            a.offs = nullptr;
+            a.keys = nullptr;
+            a.nq = (uint32_t)cq;
+            HIP_TRY(launch_range_slab(dev.dist(), dim3((uint32_t)slabs, (uint32_t)((cq + TQ - 1) / TQ)), stream, v, a));
+            hipLaunchKernelGGL(exact_range_scan_kernel, dim3(1), dim3(1024), 0, stream, a.cnt, (uint32_t)cq, (uint32_t)slabs, doff + q0, q0 == 0,
+                               h_off[b0]);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(h_off + b0 + 1, doff + 1, bq * 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    const uint64_t total = h_off[nq];
+    if (total > io.cap) {
+        err = "the answers need " + std::to_string(total) + " slots, cap is " + std::to_string(io.cap);
+        return HNSWGPU_ERR_CAPACITY;
+    }
+    if (total == 0 || io.ids == nullptr) return OK;
+
+    // ---- the fill pass
+    for (uint64_t b0 = 0; b0 < nq; b0 += block_q) {
+        const uint64_t bq = std::min(block_q, nq - b0);
+        if (h_off[b0 + bq] == h_off[b0]) continue;  // a block of empty answers
+        if (!one_block) {
+            const int rc = stage_block(b0, bq);
+            if (rc != OK) return rc;
+            HIP_TRY(hipMemcpyAsync(doff, h_off + b0, (bq + 1) * 8, hipMemcpyHostToDevice, stream));
+        }
+        for (uint64_t qa = b0, qb; qa < b0 + bq; qa = qb) {
+            qb = range_chunk_end(h_off, qa, b0 + bq, budget, max_fill_q);
+            const uint64_t hits = h_off[qb] - h_off[qa], cq = qb - qa;
+            if (hits == 0) continue;
+            if (hits > key_cap) { err = "internal error: a fill pass of " + std::to_string(hits) + " answers"; return ERR_DEVICE; }
+            const int rc = prep(dq + (qa - b0) * d, cq);
+            if (rc != OK) return rc;
+            a.radius = dr + (qa - b0);
+            a.cnt = keep ? d_cnt + qa * slabs : nullptr;
+            a.offs = doff + (qa - b0);
+            a.keys = d_keys_a;
+            a.key_base = h_off[qa];
+            a.key_cap = (uint32_t)hits;
+            a.nq = (uint32_t)cq;
+            HIP_TRY(launch_range_slab(dev.dist(), dim3((uint32_t)slabs, (uint32_t)((cq + TQ - 1) / TQ)), stream, v, a));
+            size_t need = 0;
+            HIP_TRY(sort_segments(nullptr, need, d_keys_a, d_keys_b, (uint32_t)hits, (uint32_t)cq, a.offs, a.key_base, stream));
+            if (need > temp_bytes) { err = "internal error: the sort's temporary storage"; return ERR_DEVICE; }
+            HIP_TRY(sort_segments(d_temp, need, d_keys_a, d_keys_b, (uint32_t)hits, (uint32_t)cq, a.offs, a.key_base, stream));
+            const uint64_t o = h_off[qa];
+            hipLaunchKernelGGL(exact_range_decode_kernel, dim3((uint32_t)((hits + 255) / 256)), dim3(256), 0, stream, v, d_keys_b, (uint32_t)hits,
+                               static_cast<const uint32_t*>(st->d_order), io.host ? s_ids : io.ids + o, io.host ? s_dists : io.dists + o,
+                               io.host ? (io.layer ? s_layer : nullptr) : (io.layer ? io.layer + o : nullptr),
+                               io.host ? (io.rank ? s_rank : nullptr) : (io.rank ? io.rank + o : nullptr));
+            HIP_TRY(hipGetLastError());
+            if (io.host) {
+                HIP_TRY(hipMemcpyAsync(io.ids + o, s_ids, hits * 8, hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipMemcpyAsync(io.dists + o, s_dists, hits * 4, hipMemcpyDeviceToHost, stream));
+                if (io.rank) HIP_TRY(hipMemcpyAsync(io.rank + o, s_rank, hits * 4, hipMemcpyDeviceToHost, stream));
+                if (io.layer) HIP_TRY(hipMemcpyAsync(io.layer + o, s_layer, hits, hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipStreamSynchronize(stream));  // the staging area is the next pass's
+            }
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    return OK;
+}
+
 }  // namespace
 
 // The device side of hnswgpu_exact_search_batch_filter_set(_device); capi.cpp holds the entries and every argument check, and
@@ -690,6 +1118,32 @@ int exact_filter_set_host(const DeviceIndex& dev, const std::vector<uint64_t>& o
         HIP_TRY(hipMemcpy(out_counts + q0, d_counts, cq * 4, hipMemcpyDeviceToHost));
     }
     return OK;
+}
+
+// The device side of hnswgpu_exact_range_search_batch(_device); capi.cpp holds the entries and every argument check, and refers
+// to these two weakly (capi_index.hpp).
+int exact_range_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* d_queries, uint64_t nq, uint64_t d,
+                       const float* d_radii, const uint64_t* d_allowed, uint64_t n_allowed, uint64_t cap, uint64_t* d_out_offsets,
+                       uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, void* stream, std::string& err) {
+    // (a filter that is empty still is a filter: a non-null pointer that is never dereferenced)
+    const RangeCall io{false, d_queries, d_radii, d_allowed, n_allowed, d_allowed != nullptr, cap, d_out_offsets, d_out_ids, d_out_dists,
+                       d_out_layer, d_out_rank};
+    return exact_range(dev, origin_id, io, nq, d, static_cast<hipStream_t>(stream), err);
+}
+
+int exact_range_host(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* queries, uint64_t nq, uint64_t d,
+                     const float* radii, const uint64_t* allowed, uint64_t n_allowed, uint64_t cap, uint64_t* out_offsets, uint64_t* out_ids,
+                     float* out_dists, uint8_t* out_layer, int32_t* out_rank, std::string& err) {
+    OnDevice on(dev.device());
+    HIP_TRY(on.status());
+    DevMem m_allowed;
+    if (allowed != nullptr) {
+        HIP_TRY(hipMalloc(&m_allowed.p, std::max<uint64_t>(1, n_allowed) * sizeof(uint64_t)));
+        if (n_allowed != 0) HIP_TRY(hipMemcpy(m_allowed.p, allowed, n_allowed * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    const RangeCall io{true, queries, radii, static_cast<const uint64_t*>(m_allowed.p), n_allowed, allowed != nullptr, cap, out_offsets, out_ids,
+                       out_dists, out_layer, out_rank};
+    return exact_range(dev, origin_id, io, nq, d, nullptr, err);
 }
 
 }  // namespace hnswgpu

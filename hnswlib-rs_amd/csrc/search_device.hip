@@ -70,6 +70,10 @@ Knobs read_knobs() {
     k.literal_cand_cap = k.literal_cand_cap < 1 ? -1 : std::max(64, k.literal_cand_cap);  // (one batch of neighbours at least)
     k.max_wg = num("HNSWGPU_MAX_WG", -1);
     if (k.max_wg < 1) k.max_wg = -1;  // (a launch needs one workgroup at least)
+    if (const char* e = std::getenv("HNSWGPU_RANGE_HITS_PER_PASS")) {
+        const long long v = std::atoll(e);
+        k.range_hits_per_pass = v < 1 ? -1 : (int64_t)std::min<long long>(v, 1ll << 31);
+    }
     return k;
 }
 std::atomic<const Knobs*> g_knobs{nullptr};

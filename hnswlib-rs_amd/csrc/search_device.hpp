@@ -43,6 +43,8 @@ struct Knobs {
                                  // min(n, 2^17)) -- queries that outgrow it go through its second pass, which has room for every point
     int max_wg = -1;             // HNSWGPU_MAX_WG (test hook): absolute cap on the workgroups of every persistent launch of a search call (descent, pair pass,
                                  // one-query kernels, literal kernel), applied behind every other bound (1 ..) -- a workgroup then answers many queries in turn
+    int64_t range_hits_per_pass = -1;  // HNSWGPU_RANGE_HITS_PER_PASS (test hook): the answers one fill pass of the exact range search holds (1 .. 2^31; unset: 8 Mi) --
+                                 // a small batch's chunk plan then takes several turns; a query with more answers still gets a pass of its own
 };
 const Knobs& knobs();
 void reload_knobs();

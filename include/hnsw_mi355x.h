@@ -40,8 +40,10 @@ enum {
     HNSWGPU_ERR_TYPE = 5,     /* dump's element type is not "f32"                         */
     HNSWGPU_ERR_DEVICE = 6,   /* HIP error, or no gfx950 device / index not uploaded      */
     HNSWGPU_ERR_EMPTY = 7,    /* operation needs a non-empty index                        */
-    HNSWGPU_ERR_REF_PANIC = 8 /* filtered search: the reference panics on some of the queries
+    HNSWGPU_ERR_REF_PANIC = 8, /* filtered search: the reference panics on some of the queries
                                  (src/hnsw.rs:973) and no per-query status array was given  */
+    HNSWGPU_ERR_CAPACITY = 9  /* exact range search: the answers need more slots than `cap`;
+                                 the offsets are complete, no out slot was written          */
 };
 
 /* metric selector == short type name of the anndists distance */
@@ -305,7 +307,7 @@ int hnswgpu_last_tie_count(const hnswgpu_index* idx, uint32_t* ties);
 
 /* The HNSWGPU_* tuning and test hooks (HNSWGPU_HASH_BITS, _NO_SCHED, _NO_INKERNEL, _STRICT_WG_PER_CU, _CAND_LDS, _WAVES_PER_CU,
  * _EXACT_FIRST, _TRACE_LAUNCH, _TRACE_HOST, _HOST_THREADS, _HOST_CHUNKS, _FFI_UNPACK, _FILTER_SET_MB; the test hooks
- * HNSWGPU_BITMAP_SLICES, HNSWGPU_LITERAL_CAND_CAP and HNSWGPU_MAX_WG) are read from the environment ONCE per
+ * HNSWGPU_BITMAP_SLICES, HNSWGPU_LITERAL_CAND_CAP, HNSWGPU_MAX_WG and HNSWGPU_RANGE_HITS_PER_PASS) are read from the environment ONCE per
  * process, at the library's first search -- never on the launch path.  A caller that changes them afterwards (the tests do)
  * says so with this call.  Always HNSWGPU_OK.                                                                          */
 int hnswgpu_reload_env(void);
@@ -399,6 +401,48 @@ int hnswgpu_exact_search_batch_filter_set_device(const hnswgpu_index* idx, const
                                                  uint64_t n_filters, const uint32_t* d_filter_of, uint64_t* d_out_ids,
                                                  float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank,
                                                  uint32_t* d_out_counts, void* stream);
+
+/* ---------------------------------------------------------------- exact range search --- */
+/* Every point within a query's radius, by exhaustive search on the device: the other basic query of a vector index
+ * (deduplication, clustering radius, thresholded matching).  There is no k: the answer's size depends on the data, nothing is
+ * selected, and the output is variable-length (CSR).  The reference has no such function; the contract is:
+ *   distance  as in hnswgpu_exact_search_batch: the f32 the index's search computes for the pair in HNSWGPU_ARITH_SCALAR, all
+ *             seven distances; an index set to HNSWGPU_ARITH_SIMD8 is refused with HNSWGPU_ERR_ARG.
+ *   match     point p is in query q's answer iff p is eligible and dist(q, p) <= radii[q] as an IEEE f32 comparison of values.
+ *             So a NaN distance never matches and a NaN radius matches nothing; a negative radius matches nothing (distances
+ *             are >= 0); -0.0 and +0.0 match a distance of +-0; +inf matches every eligible point whose distance is not NaN,
+ *             +inf distances included.
+ *   order     ascending by the exact k-NN key: the distance's value with -0 folded into +0, then origin id, then dump order.
+ *             For any k the first k entries of a query's answer are the exact k-NN answer restricted to the ball.
+ *   output    CSR.  out_offsets[0 .. nq] is u64 and out_offsets[0] = 0; query q owns the slots out_offsets[q] .. out_offsets[q + 1]
+ *             of out_ids (origin ids), out_dists (f32; a -0 distance comes back as +0), out_layer and out_rank (the point's own
+ *             p_id; both may be NULL).
+ *   capacity  cap = the number of slots behind the four out arrays.  out_offsets is ALWAYS written completely, so
+ *             out_offsets[nq] is the total.  total <= cap: the answers are written, HNSWGPU_OK.  Otherwise NO out slot is touched
+ *             and the call returns HNSWGPU_ERR_CAPACITY; hnswgpu_last_error() names the total needed.  cap == 0 with NULL out
+ *             arrays is the count-only call: it evaluates every pair once and never runs the fill pass.  cap > 0 with a NULL
+ *             out_ids or out_dists is HNSWGPU_ERR_ARG.
+ *   filter    allowed_ids == NULL: every point is eligible.  Else the SORTED id vector, as in hnswgpu_exact_search_batch:
+ *             unsorted is HNSWGPU_ERR_ARG (host entry), ids naming no point are ignored, an empty vector gives empty answers.
+ *   radii     one f32 per query.
+ *   The answer is a function of (vectors, ids, distance, query, radius) alone: not of the graph, not of the dump order beyond the
+ *   last tie-break, not of how the queries are grouped into tiles or chunks.  An empty index: every answer is empty, HNSWGPU_OK.
+ * Two passes over the same pair evaluations (count, then fill), a sort of every query's keys, a decoding pass.  Scratch memory
+ * is a fixed budget: neither the nq x n matrix nor the whole answer is held on the device by the host entry -- the fill pass
+ * serves consecutive queries whose answers fit 8 Mi slots (or one query, however many points it hits; the test hook
+ * HNSWGPU_RANGE_HITS_PER_PASS sets another number) and the host entry copies each pass's answers out.  Takes the handle's lock
+ * shared, like a search.  Host buffers; uploads the index on first use.                                                       */
+int hnswgpu_exact_range_search_batch(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d,
+                                     const float* radii, const uint64_t* allowed_ids, uint64_t n_allowed, uint64_t cap,
+                                     uint64_t* out_offsets, uint64_t* out_ids, float* out_dists, uint8_t* out_layer,
+                                     int32_t* out_rank);
+/* The same on device-resident buffers (radii, filter and offsets too), on HIP stream `stream`, waited for; the same capacity rule
+ * (the out arrays hold cap slots in HBM and are written in place).  The index must be uploaded (else HNSWGPU_ERR_DEVICE).  The
+ * sortedness of d_allowed_ids is the caller's promise.  The offsets are read back once (the fill pass is planned on the host).  */
+int hnswgpu_exact_range_search_batch_device(const hnswgpu_index* idx, const float* d_queries, uint64_t nq, uint64_t d,
+                                            const float* d_radii, const uint64_t* d_allowed_ids, uint64_t n_allowed,
+                                            uint64_t cap, uint64_t* d_out_offsets, uint64_t* d_out_ids, float* d_out_dists,
+                                            uint8_t* d_out_layer, int32_t* d_out_rank, void* stream);
 
 /* Test entry: the lane lab. The wave-level algorithms the search kernels are made of -- the reference's BinaryHeap (src/hnsw.rs:940,
  * :958-973, :1035-1053, :1544; std's push / pop / into_sorted_vec) as a memory heap and as a register heap, the sorted result set
