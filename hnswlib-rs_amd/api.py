@@ -441,6 +441,52 @@ class Hnsw:
         """exact_range_search_flat as Vec<Vec<Neighbour>> in input order."""
         return self.exact_range_search_flat(datas, radius, allowed_ids).to_neighbours()
 
+    # ---- queries by stored point: the k-NN graph of the indexed points (an extension) --------------------------------
+    def _graph_call(self, entry, knbn, point_ids, *middle):
+        """one of the two graph entries: point_ids (DataIds; None = every point, row i being the point at position i of the
+        ascending (DataId, dump order) order), the entry's own arguments, the five output arrays"""
+        pts = None
+        if point_ids is not None:
+            pts = np.ascontiguousarray(point_ids, dtype=np.uint64).reshape(-1)
+        np_ = self.get_nb_point() if pts is None else len(pts)
+        ids = np.zeros((np_, knbn), np.uint64)
+        dists = np.zeros((np_, knbn), np.float32)
+        layers = np.zeros((np_, knbn), np.uint8)
+        ranks = np.zeros((np_, knbn), np.int32)
+        counts = np.zeros(np_, np.uint32)
+        if self._h is None:
+            if np_ != 0:
+                raise HnswError(N.ERR_ARG, f"{np_} of the {np_} point_ids name no point of the index")
+            return BatchResult(ids, dists, layers, ranks, counts)
+        if pts is not None and np_ == 0:
+            pts = np.zeros(1, np.uint64)  # (no point named still is a list of points: a non-null pointer, zero ids)
+        _check(entry(self._h, _p(pts), np_, knbn, *middle, _p(ids), _p(dists), _p(layers), _p(ranks), _p(counts)))
+        return BatchResult(ids, dists, layers, ranks, counts)
+
+    def knn_graph_flat(self, knbn, ef, point_ids=None):
+        """The approximate k-NN graph: for every named point (DataIds; None = every point of the index) its knbn neighbours
+        by the index's own search -- the answer of parallel_search_flat(the point's stored vector, knbn + 1, ef) without the
+        entry that is the point itself (by p_id: exact copies and other points of its DataId stay), or without its last entry
+        when the point is not in its own answer.  The stored vectors never leave the device.  An id that no point carries
+        raises (ERR_ARG); an id that several points carry names the first in dump order.  Returns a BatchResult."""
+        return self._graph_call(self._lib.hnswgpu_graph_search_batch, knbn, point_ids, ef)
+
+    def exact_knn_graph_flat(self, knbn, point_ids=None, allowed_ids=None):
+        """The exact k-NN graph: for every named point the min(knbn, candidates) smallest by (distance as f32, origin id,
+        dump order) among all OTHER points -- or, with allowed_ids (the SORTED id vector of a filter, as in exact_search_flat),
+        among the allowed points other than itself.  The point is excluded by identity: its exact copies come back at distance
+        0.  knbn up to 4096.  Returns a BatchResult."""
+        allowed, n_allowed = None, 0
+        if allowed_ids is not None:
+            n_allowed = len(allowed_ids)
+            allowed = np.ascontiguousarray(allowed_ids, dtype=np.uint64) if n_allowed else np.zeros(1, np.uint64)
+        return self._graph_call(self._lib.hnswgpu_exact_graph_batch, knbn, point_ids, _p(allowed), n_allowed)
+
+    def knn_graph_recall(self, knbn, ef, point_ids=None):
+        """The recall by id of knn_graph_flat against exact_knn_graph_flat over the named points: the share of the exact
+        graph's edges whose id the approximate graph has in the same row."""
+        return _recall(self.knn_graph_flat(knbn, ef, point_ids), self.exact_knn_graph_flat(knbn, point_ids))[1]
+
     def recall_flat(self, datas, knbn, ef, allowed_ids=None):
         """The two recalls the reference's examples print (examples/ann-sift1m-128-euclidean.rs:172-186), for this index's
         own search (filtered by allowed_ids if given) against the exact answer: (by distance, by id).

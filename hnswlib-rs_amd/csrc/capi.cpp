@@ -949,6 +949,124 @@ int hnswgpu_exact_range_search_batch_device(const hnswgpu_index* cidx, const flo
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
+// ---- queries by stored point: the k-NN graph of the indexed points, approximate and exact (exact_knn.hip holds the device side)
+extern "C++" {
+namespace hnswgpu {
+__attribute__((weak)) int graph_search(DeviceIndex&, const std::vector<uint64_t>&, bool, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*, float*,
+                                       uint8_t*, int32_t*, uint32_t*, void*, std::string&);
+__attribute__((weak)) int exact_graph(const DeviceIndex&, const std::vector<uint64_t>&, bool, const uint64_t*, uint64_t, uint64_t, const uint64_t*, uint64_t,
+                                      uint64_t*, float*, uint8_t*, int32_t*, uint32_t*, void*, std::string&);
+}  // namespace hnswgpu
+}  // extern "C++"
+// the checks all four entries share; the handle's lock is held (shared).  exact: the exact call's own limits behind them.
+static int graph_call(const hnswgpu_index* idx, const void* point_ids, uint64_t np, uint64_t k, bool exact, const void* allowed, uint64_t n_allowed,
+                      const void* out_ids, const void* out_dists, const void* out_counts) {
+    const uint64_t n = idx->builder ? idx->builder->nb_point() : (idx->flat ? idx->flat->n : 0);
+    if (np != 0 && (!out_ids || !out_dists || !out_counts)) return fail(HNSWGPU_ERR_ARG, "null buffer");
+    if (!point_ids && np != n)
+        return fail(HNSWGPU_ERR_ARG, "point_ids is NULL (every point): np must be nb_point = " + std::to_string(n) + ", not " + std::to_string(np));
+    if (k == 0) return fail(HNSWGPU_ERR_ARG, "knbn must be > 0");
+    if (np > 0xFFFFFFF0ull) return fail(HNSWGPU_ERR_ARG, "too many points in one batch");
+    if (!exact) return HNSWGPU_OK;
+    if (k > 4096) return fail(HNSWGPU_ERR_ARG, "exact graph: knbn above 4096");
+    if (n_allowed != 0 && !allowed) return fail(HNSWGPU_ERR_ARG, "null filter");
+    if (idx->arithmetic != HNSWGPU_ARITH_SCALAR)
+        return fail(HNSWGPU_ERR_ARG, "exact graph answers in the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
+    return HNSWGPU_OK;
+}
+// what the host entries do behind the checks: an empty index names no point; else the replica, uploaded on first use
+static int graph_host_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mutex>& sl, uint64_t np, bool have_device_side, DeviceIndex** dev) {
+    *dev = nullptr;
+    if (np == 0) return HNSWGPU_OK;
+    const bool empty = idx->builder ? idx->builder->nb_point() == 0 : (!idx->flat || idx->flat->n == 0);
+    if (empty) return fail(HNSWGPU_ERR_ARG, std::to_string(np) + " of the " + std::to_string(np) + " point_ids name no point of the index");
+    if (!have_device_side) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    return primary_replica(idx, sl, dev);
+}
+
+int hnswgpu_graph_search_batch(const hnswgpu_index* cidx, const uint64_t* point_ids, uint64_t np, uint64_t k, uint64_t ef, uint64_t* out_ids,
+                               float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    int rc = graph_call(idx, point_ids, np, k, false, nullptr, 0, out_ids, out_dists, out_counts);
+    if (rc != HNSWGPU_OK) return rc;
+    DeviceIndex* dev = nullptr;
+    rc = graph_host_replica(idx, sl, np, hnswgpu::graph_search != nullptr, &dev);
+    if (rc != HNSWGPU_OK || !dev) return rc;
+    std::string err;
+    rc = hnswgpu::graph_search(*dev, idx->flat->origin_id, true, point_ids, np, k, ef, out_ids, out_dists, out_layer, out_rank, out_counts, nullptr, err);
+    if (rc != OK) return fail(rc, err);
+    return HNSWGPU_OK;
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswgpu_graph_search_batch_device(const hnswgpu_index* cidx, const uint64_t* d_point_ids, uint64_t np, uint64_t k, uint64_t ef,
+                                      uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts,
+                                      void* stream) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    int rc = graph_call(idx, d_point_ids, np, k, false, nullptr, 0, d_out_ids, d_out_dists, d_out_counts);
+    if (rc != HNSWGPU_OK) return rc;
+    if (np == 0) return HNSWGPU_OK;
+    if (!hnswgpu::graph_search) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = idx->primary >= 0 ? idx->replica(idx->primary) : nullptr;
+    if (!dev || idx->dev_stale || idx->flat_stale || !idx->flat)
+        return fail(HNSWGPU_ERR_DEVICE, "index is not resident on a device: call hnswgpu_upload first");
+    std::string err;
+    rc = hnswgpu::graph_search(*dev, idx->flat->origin_id, false, d_point_ids, np, k, ef, d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts,
+                               stream, err);
+    if (rc != OK) return fail(rc, err);
+    return HNSWGPU_OK;
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+int hnswgpu_exact_graph_batch(const hnswgpu_index* cidx, const uint64_t* point_ids, uint64_t np, uint64_t k, const uint64_t* allowed_ids,
+                              uint64_t n_allowed, uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    int rc = graph_call(idx, point_ids, np, k, true, allowed_ids, n_allowed, out_ids, out_dists, out_counts);
+    if (rc != HNSWGPU_OK) return rc;
+    for (uint64_t i = 1; i < n_allowed; ++i)  // `impl FilterT for Vec<usize>` is a binary search: the vector must be sorted
+        if (allowed_ids[i - 1] > allowed_ids[i]) return fail(HNSWGPU_ERR_ARG, "the id vector of a filter must be sorted ascending");
+    DeviceIndex* dev = nullptr;
+    rc = graph_host_replica(idx, sl, np, hnswgpu::exact_graph != nullptr, &dev);
+    if (rc != HNSWGPU_OK || !dev) return rc;
+    std::string err;
+    rc = hnswgpu::exact_graph(*dev, idx->flat->origin_id, true, point_ids, np, k, allowed_ids, n_allowed, out_ids, out_dists, out_layer, out_rank, out_counts,
+                              nullptr, err);
+    if (rc != OK) return fail(rc, err);
+    return HNSWGPU_OK;
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswgpu_exact_graph_batch_device(const hnswgpu_index* cidx, const uint64_t* d_point_ids, uint64_t np, uint64_t k, const uint64_t* d_allowed_ids,
+                                     uint64_t n_allowed, uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank,
+                                     uint32_t* d_out_counts, void* stream) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    int rc = graph_call(idx, d_point_ids, np, k, true, d_allowed_ids, n_allowed, d_out_ids, d_out_dists, d_out_counts);
+    if (rc != HNSWGPU_OK) return rc;
+    if (np == 0) return HNSWGPU_OK;
+    if (!hnswgpu::exact_graph) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = idx->primary >= 0 ? idx->replica(idx->primary) : nullptr;
+    if (!dev || idx->dev_stale || idx->flat_stale || !idx->flat)
+        return fail(HNSWGPU_ERR_DEVICE, "index is not resident on a device: call hnswgpu_upload first");
+    std::string err;
+    rc = hnswgpu::exact_graph(*dev, idx->flat->origin_id, false, d_point_ids, np, k, d_allowed_ids, n_allowed, d_out_ids, d_out_dists, d_out_layer,
+                              d_out_rank, d_out_counts, stream, err);
+    if (rc != OK) return fail(rc, err);
+    return HNSWGPU_OK;
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
 static DeviceIndex* any_replica(hnswgpu_index* idx) {
     if (idx->primary >= 0 && idx->replica(idx->primary)) return idx->replica(idx->primary);
     return nullptr;

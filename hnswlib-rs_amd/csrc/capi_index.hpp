@@ -68,6 +68,15 @@ int exact_range_host(const DeviceIndex& dev, const std::vector<uint64_t>& origin
 int exact_range_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* d_queries, uint64_t nq, uint64_t d,
                        const float* d_radii, const uint64_t* d_allowed, uint64_t n_allowed, uint64_t cap, uint64_t* d_out_offsets,
                        uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, void* stream, std::string& err);
+// the device side of hnswgpu_graph_search_batch(_device) and hnswgpu_exact_graph_batch(_device), defined in exact_knn.hip and
+// referred to weakly in the same way.  host: every buffer (point_ids and allowed too) is plain host memory; else device memory
+// and `stream` is the caller's.  point_ids == nullptr: every point (np == the number of points, checked by the caller).  They
+// return ERR_ARG, nothing searched and no out slot written, when an id of point_ids names no point.
+int graph_search(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, bool host, const uint64_t* point_ids, uint64_t np, uint64_t k, uint64_t ef,
+                 uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts, void* stream, std::string& err);
+int exact_graph(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, bool host, const uint64_t* point_ids, uint64_t np, uint64_t k,
+                const uint64_t* allowed, uint64_t n_allowed, uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank,
+                uint32_t* out_counts, void* stream, std::string& err);
 }  // namespace hnswgpu
 
 // No C++ exception may cross the C ABI: every entry point is `try { ... HNSWGPU_CAPI_GUARD_END(ret)`

@@ -29,6 +29,11 @@
 //   exact_range_scan_kernel    the counters, query major and slab minor, into the CSR offsets and into each slab's base
 //   (rocPRIM)                  every query's segment of keys sorted ascending
 //   exact_range_decode_kernel  keys into ids, distances and p_ids
+//
+// Queries by stored point (the device side of hnswgpu_graph_search_batch / hnswgpu_exact_graph_batch and their _device forms; the
+// entries are in capi.cpp): the k-NN graph of the indexed points, the point itself left out by identity.  DESIGN.md "Queries by
+// stored point".  Exact: exact_knn_prep_rows_kernel tiles the rows themselves and the slab kernel's SELF variant skips each
+// query's own rank.  Approximate: graph_gather_kernel, the batched search with knbn = k + 1, graph_compact_kernel.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
@@ -83,6 +88,7 @@ struct ExactKnnArgs {
     // (behind everything the kernels of the one-filter call read: their code does not move)
     const uint32_t* qlist;  // tile slot -> row of the caller's arrays, or nullptr: the slot's own number
     const uint32_t* tword;  // [tiles * TQ] filter set: first word of the slot's bitmap in `allow` (prep kernel)
+    const uint32_t* self_rank;  // [tiles * TQ] k-NN graph: the slot's query is the stored point of this DataId rank (prep kernel), never its own answer
 };
 
 // f32 -> u32 whose unsigned order is the order of the values, every NaN behind everything (distances are >= 0: then this is the
@@ -170,8 +176,10 @@ __device__ __attribute__((noinline)) ListState list_insert(uint64_t* list, uint3
 }
 
 // SET: `allow` holds one bitmap of ceil(n / 32) words per filter of the group and every query of the tile names its own
-// (a.tword); else one bitmap (or none) for all
-template <int METRIC, bool SET>
+// (a.tword); else one bitmap (or none) for all.
+// SELF (k-NN graph): every query of the tile is a stored point, named by its DataId rank (a.self_rank), and that one row -- the
+// point itself, not its copies and not the other points of its DataId -- is never inserted into the query's lists.
+template <int METRIC, bool SET, bool SELF>
 // (the two distances that go through ln_f32 get twice the registers: their inner loop spilled at four waves per SIMD)
 __global__ __launch_bounds__(64, METRIC == DIST_JEFFREYS || METRIC == DIST_JENSENSHANNON ? 2 : 4) void exact_knn_slab_kernel(DeviceIndexView ix, ExactKnnArgs a) {
     typedef typename std::conditional<METRIC == DIST_COSINE, double, float>::type ACC;
@@ -202,6 +210,13 @@ __global__ __launch_bounds__(64, METRIC == DIST_JEFFREYS || METRIC == DIST_JENSE
         }
     }
     const uint32_t valid_bits = (1u << nvalid) - 1u;
+    // the tile's own ranks are wave-uniform: one scalar load of 64 bytes, 16 scalar registers for the kernel's life (the compare
+    // below then has a scalar operand and costs no vector register)
+    uint32_t self[TQ];
+    if constexpr (SELF) {
+#pragma unroll
+        for (int t = 0; t < TQ; ++t) self[t] = ((uword_ptr_t)a.self_rank)[tile * (uint32_t)TQ + (uint32_t)t];
+    }
 
     for (uint32_t r0 = lo; r0 < hi; r0 += 64u) {
         const bool in = r0 + lane < hi;
@@ -262,7 +277,8 @@ __global__ __launch_bounds__(64, METRIC == DIST_JEFFREYS || METRIC == DIST_JENSE
                     v = dist_finish<METRIC>(acc[t]);
                 }
                 const uint64_t key = make_key(v, rk);
-                const bool mine = SET ? ((elig >> t) & 1u) != 0u : ok;
+                bool mine = SET ? ((elig >> t) & 1u) != 0u : ok;
+                if constexpr (SELF) mine = mine && rk != self[t];
                 const unsigned long long m = __ballot(mine && key < st[t].thr);
                 if (m != 0ull) st[t] = list_insert(lists + (size_t)t * cap, cap, st[t], key, m);
             }
@@ -352,22 +368,48 @@ __global__ void exact_knn_prep_kernel(const float* __restrict__ src, uint32_t nq
     qnorm[qs] = s1;
 }
 
-template <bool SET>
+// k-NN graph: the same tiles from the index's own rows -- slot qs holds the stored point flat[qs], its first d elements (what lies
+// behind them in the padded row, a DistCosine norm included, never reaches the tile), the squared norm summed as above, so the
+// bits are those of the point's vector brought as a query -- and the slot's own DataId rank (slots behind the last: no rank)
+__global__ void exact_knn_prep_rows_kernel(DeviceIndexView ix, const uint32_t* __restrict__ flat, const uint32_t* __restrict__ rank, uint32_t nq,
+                                           uint32_t nchunk, uint32_t n_slots, float* __restrict__ qt, double* __restrict__ qnorm,
+                                           uint32_t* __restrict__ self_rank) {
+    const uint32_t qs = blockIdx.x * blockDim.x + threadIdx.x;
+    if (qs >= n_slots) return;
+    const uint32_t tile = qs / (uint32_t)TQ, t = qs % (uint32_t)TQ;
+    const uint32_t f = qs < nq ? flat[qs] : 0u;
+    const float* src = ix.vec + (size_t)f * ix.row_stride;
+    double s1 = 0.;
+    for (uint32_t c = 0; c < nchunk; ++c) {
+        float e[4];
+        for (uint32_t j = 0; j < 4u; ++j) {
+            const uint32_t i = 4u * c + j;
+            e[j] = qs < nq && i < ix.d ? src[i] : 0.f;
+            s1 = s1 + (double)(e[j] * e[j]);
+        }
+        reinterpret_cast<float4*>(qt)[((size_t)tile * nchunk + c) * (size_t)TQ + t] = make_float4(e[0], e[1], e[2], e[3]);
+    }
+    qnorm[qs] = s1;
+    self_rank[qs] = qs < nq ? rank[f] : 0xFFFFFFFFu;
+}
+
+template <bool SET, bool SELF>
 hipError_t launch_slab_of(int metric, dim3 grid, hipStream_t stream, const DeviceIndexView& ix, const ExactKnnArgs& a) {
     switch (metric) {
-        case DIST_L2: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_L2, SET>), grid, dim3(64), 0, stream, ix, a); break;
-        case DIST_COSINE: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_COSINE, SET>), grid, dim3(64), 0, stream, ix, a); break;
-        case DIST_DOT: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_DOT, SET>), grid, dim3(64), 0, stream, ix, a); break;
-        case DIST_L1: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_L1, SET>), grid, dim3(64), 0, stream, ix, a); break;
-        case DIST_HELLINGER: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_HELLINGER, SET>), grid, dim3(64), 0, stream, ix, a); break;
-        case DIST_JEFFREYS: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_JEFFREYS, SET>), grid, dim3(64), 0, stream, ix, a); break;
-        case DIST_JENSENSHANNON: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_JENSENSHANNON, SET>), grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_L2: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_L2, SET, SELF>), grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_COSINE: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_COSINE, SET, SELF>), grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_DOT: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_DOT, SET, SELF>), grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_L1: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_L1, SET, SELF>), grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_HELLINGER: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_HELLINGER, SET, SELF>), grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_JEFFREYS: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_JEFFREYS, SET, SELF>), grid, dim3(64), 0, stream, ix, a); break;
+        case DIST_JENSENSHANNON: hipLaunchKernelGGL((exact_knn_slab_kernel<DIST_JENSENSHANNON, SET, SELF>), grid, dim3(64), 0, stream, ix, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
-hipError_t launch_slab(int metric, bool set, dim3 grid, hipStream_t stream, const DeviceIndexView& ix, const ExactKnnArgs& a) {
-    return set ? launch_slab_of<true>(metric, grid, stream, ix, a) : launch_slab_of<false>(metric, grid, stream, ix, a);
+hipError_t launch_slab(int metric, bool set, bool self, dim3 grid, hipStream_t stream, const DeviceIndexView& ix, const ExactKnnArgs& a) {
+    if (self) return launch_slab_of<false, true>(metric, grid, stream, ix, a);  // (the graph calls take one filter or none)
+    return set ? launch_slab_of<true, false>(metric, grid, stream, ix, a) : launch_slab_of<false, false>(metric, grid, stream, ix, a);
 }
 
 #define HIP_TRY(expr)                                                                          \
@@ -471,9 +513,12 @@ constexpr uint64_t MAX_FILTER_SET_WAVES = 1ull << 31;  // allow_bitmap_set_kerne
 // set == nullptr: no filter, or one for the batch (d_allowed).  Else query q is answered under filter fs->filter_of[q]: the
 // bitmaps are built group by group -- as many consecutive filters as the bound and this unit's scratch budget hold -- and per group
 // its queries are listed (launch_filter_group), tiled densely and searched; one group (the usual case): all queries in batch order.
+// d_self != nullptr (k-NN graph; no set): query q is the stored point of flat id d_self[q], d_queries is not read, and the point
+// itself is no candidate of its own row.
 int exact_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* d_queries, uint64_t nq, uint64_t d,
                  uint64_t k, const uint64_t* d_allowed, uint64_t n_allowed, bool filtered, const SetCall* set, uint64_t* d_out_ids,
-                 float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, hipStream_t stream, std::string& err) {
+                 float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, hipStream_t stream, std::string& err,
+                 const uint32_t* d_self = nullptr) {
     const DeviceIndexView& v = dev.view();
     if (nq == 0) return OK;
     OnDevice on(dev.device());
@@ -515,7 +560,9 @@ int exact_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id,
     slabs = (n + slab_rows - 1) / slab_rows;
     // queries per chunk: whole tiles, what the budget holds, a grid the launch accepts
     const uint64_t tword_bytes = set ? round_up(TQ * 4, 256) : 0;
-    const uint64_t per_tile = round_up(nchunk * TQ * 16, 256) + round_up(TQ * 8, 256) + round_up(slabs * TQ * cap * 8, 256) + round_up(slabs * TQ * 4, 256) + tword_bytes;
+    const uint64_t self_bytes = d_self ? round_up(TQ * 4, 256) : 0;
+    const uint64_t per_tile = round_up(nchunk * TQ * 16, 256) + round_up(TQ * 8, 256) + round_up(slabs * TQ * cap * 8, 256) + round_up(slabs * TQ * 4, 256) +
+                              tword_bytes + self_bytes;
     const uint64_t chunk_tiles = std::min<uint64_t>({tiles_total, (SCRATCH_BUDGET - allow_bytes) / per_tile, 65535});
     if (chunk_tiles == 0) { err = "knbn too large for the exact search's scratch budget"; return ERR_ARG; }
 
@@ -530,7 +577,8 @@ int exact_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id,
     double* d_qnorm = reinterpret_cast<double*>(p); p += chunk_tiles * round_up(TQ * 8, 256);
     uint64_t* d_lists = reinterpret_cast<uint64_t*>(p); p += chunk_tiles * round_up(slabs * TQ * cap * 8, 256);
     uint32_t* d_lens = reinterpret_cast<uint32_t*>(p); p += chunk_tiles * round_up(slabs * TQ * 4, 256);
-    uint32_t* d_tword = set ? reinterpret_cast<uint32_t*>(p) : nullptr;
+    uint32_t* d_tword = set ? reinterpret_cast<uint32_t*>(p) : nullptr; p += chunk_tiles * tword_bytes;
+    uint32_t* d_self_rank = d_self ? reinterpret_cast<uint32_t*>(p) : nullptr;
 
     // whatever happens, nothing of this call is still running when the scratch block goes back to the pool
     struct Drain {
@@ -568,11 +616,16 @@ int exact_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id,
             a.out_counts = d_out_counts + row0;
             a.qlist = qlist ? qlist + q0 : nullptr;
             a.tword = d_tword;
+            a.self_rank = d_self_rank;
             const uint32_t n_slots = (uint32_t)(tiles * TQ);
-            hipLaunchKernelGGL(exact_knn_prep_kernel, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, d_queries + row0 * d, (uint32_t)cq,
-                               (uint32_t)d, (uint32_t)nchunk, n_slots, d_qt, d_qnorm, a.qlist, slot_of ? slot_of + row0 : nullptr, (uint32_t)words, d_tword);
+            if (d_self)
+                hipLaunchKernelGGL(exact_knn_prep_rows_kernel, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, v, d_self + row0, a.rank, (uint32_t)cq,
+                                   (uint32_t)nchunk, n_slots, d_qt, d_qnorm, d_self_rank);
+            else
+                hipLaunchKernelGGL(exact_knn_prep_kernel, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, d_queries + row0 * d, (uint32_t)cq,
+                                   (uint32_t)d, (uint32_t)nchunk, n_slots, d_qt, d_qnorm, a.qlist, slot_of ? slot_of + row0 : nullptr, (uint32_t)words, d_tword);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(launch_slab(dev.dist(), set != nullptr, dim3((uint32_t)slabs, (uint32_t)tiles), stream, v, a));
+            HIP_TRY(launch_slab(dev.dist(), set != nullptr, d_self != nullptr, dim3((uint32_t)slabs, (uint32_t)tiles), stream, v, a));
             hipLaunchKernelGGL(exact_knn_merge_kernel, dim3((uint32_t)cq), dim3(64), 0, stream, v, a);
             HIP_TRY(hipGetLastError());
         }
@@ -1064,6 +1117,150 @@ int exact_range(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, 
     return OK;
 }
 
+// ------------------------------------------------------------------------------------------------------------------ k-NN graph
+// Queries by stored point (the device side of hnswgpu_graph_search_batch / hnswgpu_exact_graph_batch and their _device forms; the
+// entries are in capi.cpp).  DESIGN.md "Queries by stored point".
+//   graph_resolve_kernel   DataIds into flat ids: a binary search over origin_id[order[.]], the first point of a repeated id
+//   graph_gather_kernel    the first d elements of the named rows into a dense query matrix (approximate graph)
+//   graph_compact_kernel   the search's (k + 1)-wide answers into the caller's k-wide rows, the point's own entry dropped
+constexpr uint64_t GRAPH_SCRATCH = 256ull << 20;  // bytes of gathered queries and staged answers per chunk of points at most
+
+// one thread per named point.  ids == nullptr: every point, row i being position i of the ascending (DataId, dump order) order.
+// An id that no point carries is counted in *n_unknown (its slot gets flat id 0 and is never used: the call fails).
+__global__ __launch_bounds__(256) void graph_resolve_kernel(const uint64_t* __restrict__ origin_id, const uint32_t* __restrict__ order, uint32_t n,
+                                                           const uint64_t* __restrict__ ids, uint32_t np, uint32_t* __restrict__ flat,
+                                                           uint32_t* __restrict__ n_unknown) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= np) return;
+    if (ids == nullptr) { flat[i] = order[i]; return; }  // (the caller has checked np == n)
+    const uint64_t id = ids[i];
+    uint32_t lo = 0, hi = n;  // the first position whose id is >= id
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (origin_id[order[mid]] < id) lo = mid + 1u; else hi = mid;
+    }
+    uint32_t f = 0;
+    if (lo < n && origin_id[order[lo]] == id) f = order[lo];
+    else atomicAdd(n_unknown, 1u);
+    flat[i] = f;
+}
+
+// one thread per element of the query matrix: q[i][j] = element j < d of the row of point flat[i].  The row's padding -- zeros, or
+// a DistCosine norm in its last 8 bytes -- stays behind.
+__global__ __launch_bounds__(256) void graph_gather_kernel(DeviceIndexView ix, const uint32_t* __restrict__ flat, uint64_t total, float* __restrict__ q) {
+    const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (e >= total) return;
+    const uint64_t i = e / ix.d;
+    const uint32_t j = (uint32_t)(e - i * ix.d);
+    q[e] = ix.vec[(size_t)flat[i] * ix.row_stride + j];
+}
+
+struct GraphRows {  // answers, row major
+    uint64_t* ids;
+    float* dists;
+    uint8_t* layer;   // the caller's may be nullptr; the staged ones never are
+    int32_t* rank;
+    uint32_t* counts;
+};
+// one wavefront per row: the search's answer for the stored vector of point flat[row] with knbn = k + 1 (src) into the k-wide
+// row of dst.  The entry whose p_id is the point's own is removed; when there is none and the answer is full, its last entry.
+// The slots behind what remains are zeroed.
+__global__ __launch_bounds__(64) void graph_compact_kernel(DeviceIndexView ix, const uint32_t* __restrict__ flat, GraphRows src, GraphRows dst, uint32_t k) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t row = blockIdx.x;
+    const uint32_t k1 = k + 1u;
+    const uint32_t cnt = src.counts[row] < k1 ? src.counts[row] : k1;
+    const uint32_t own = flat[row];
+    const size_t s0 = (size_t)row * k1, d0 = (size_t)row * k;
+    uint32_t pos = 0xFFFFFFFFu;  // where the point's own entry is (a p_id names one point: at most one entry)
+    for (uint32_t j = lane; j < cnt; j += 64u)
+        if (ix.layer_offset[src.layer[s0 + j] < NB_LAYER_MAX ? src.layer[s0 + j] : NB_LAYER_MAX] + (uint32_t)src.rank[s0 + j] == own) pos = j;
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t other = (uint32_t)__shfl_xor((int)pos, o, 64);
+        pos = other < pos ? other : pos;
+    }
+    const uint32_t left = pos != 0xFFFFFFFFu ? cnt - 1u : (cnt < k ? cnt : k);
+    for (uint32_t j = lane; j < k; j += 64u) {
+        const bool have = j < left;
+        const size_t s = s0 + (j < pos ? j : j + 1u);
+        dst.ids[d0 + j] = have ? src.ids[s] : 0ull;
+        dst.dists[d0 + j] = have ? src.dists[s] : 0.f;
+        if (dst.layer) dst.layer[d0 + j] = have ? src.layer[s] : (uint8_t)0;
+        if (dst.rank) dst.rank[d0 + j] = have ? src.rank[s] : 0;
+    }
+    if (lane == 0u) dst.counts[row] = left;
+}
+
+// A graph call's buffers: plain host memory (host) or device memory, point_ids and allowed too
+struct GraphCall {
+    bool host;
+    const uint64_t* point_ids;  // nullptr: every point
+    uint64_t np, k;
+    uint64_t* ids;
+    float* dists;
+    uint8_t* layer;
+    int32_t* rank;
+    uint32_t* counts;
+};
+
+// the named points as flat ids in device memory (m_flat; word 0 of m_ctrl counts the unknown ids).  Returns ERR_ARG, nothing
+// searched and no output written, when an id names no point.
+int graph_resolve(const DeviceIndexView& v, const ExactState* st, const GraphCall& io, DevMem& m_flat, hipStream_t stream, std::string& err) {
+    DevMem m_ids, m_ctrl;
+    HIP_TRY(hipMalloc(&m_flat.p, io.np * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&m_ctrl.p, 256));
+    const uint64_t* d_ids = io.point_ids;
+    if (io.host && io.point_ids != nullptr) {
+        HIP_TRY(hipMalloc(&m_ids.p, io.np * sizeof(uint64_t)));
+        HIP_TRY(hipMemcpyAsync(m_ids.p, io.point_ids, io.np * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        d_ids = static_cast<const uint64_t*>(m_ids.p);
+    }
+    uint32_t unknown = 0;
+    HIP_TRY(hipMemsetAsync(m_ctrl.p, 0, 4, stream));
+    hipLaunchKernelGGL(graph_resolve_kernel, dim3((uint32_t)((io.np + 255) / 256)), dim3(256), 0, stream, v.origin_id, static_cast<const uint32_t*>(st->d_order),
+                       v.n, d_ids, (uint32_t)io.np, static_cast<uint32_t*>(m_flat.p), static_cast<uint32_t*>(m_ctrl.p));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&unknown, m_ctrl.p, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (unknown != 0) {
+        err = std::to_string(unknown) + " of the " + std::to_string(io.np) + " point_ids name no point of the index";
+        return ERR_ARG;
+    }
+    return OK;
+}
+
+// device staging of a chunk's k-wide answers (host calls), and their way out
+struct GraphStage {
+    DevMem mem;
+    GraphRows rows{};
+    hipError_t alloc(uint64_t chunk, uint64_t k) {
+        const hipError_t e = hipMalloc(&mem.p, round_up(chunk * k * 8, 256) + 2 * round_up(chunk * k * 4, 256) + round_up(chunk * 4, 256) + round_up(chunk * k, 256));
+        if (e != hipSuccess) { mem.p = nullptr; return e; }
+        unsigned char* p = static_cast<unsigned char*>(mem.p);
+        rows.ids = reinterpret_cast<uint64_t*>(p); p += round_up(chunk * k * 8, 256);
+        rows.dists = reinterpret_cast<float*>(p); p += round_up(chunk * k * 4, 256);
+        rows.rank = reinterpret_cast<int32_t*>(p); p += round_up(chunk * k * 4, 256);
+        rows.counts = reinterpret_cast<uint32_t*>(p); p += round_up(chunk * 4, 256);
+        rows.layer = p;
+        return hipSuccess;
+    }
+    hipError_t copy_out(const GraphCall& io, uint64_t c0, uint64_t cq, hipStream_t stream) const {
+        const uint64_t k = io.k;
+        hipError_t e = hipMemcpyAsync(io.ids + c0 * k, rows.ids, cq * k * 8, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(io.dists + c0 * k, rows.dists, cq * k * 4, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess && io.rank) e = hipMemcpyAsync(io.rank + c0 * k, rows.rank, cq * k * 4, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess && io.layer) e = hipMemcpyAsync(io.layer + c0 * k, rows.layer, cq * k, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(io.counts + c0, rows.counts, cq * 4, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);  // the staging area is the next chunk's
+        return e;
+    }
+};
+// rows [c0, c0 + ..) of a device call's own arrays
+GraphRows graph_rows_at(const GraphCall& io, uint64_t c0) {
+    return GraphRows{io.ids + c0 * io.k, io.dists + c0 * io.k, io.layer ? io.layer + c0 * io.k : nullptr, io.rank ? io.rank + c0 * io.k : nullptr,
+                     io.counts + c0};
+}
+
 }  // namespace
 
 // The device side of hnswgpu_exact_search_batch_filter_set(_device); capi.cpp holds the entries and every argument check, and
@@ -1144,6 +1341,109 @@ int exact_range_host(const DeviceIndex& dev, const std::vector<uint64_t>& origin
     const RangeCall io{true, queries, radii, static_cast<const uint64_t*>(m_allowed.p), n_allowed, allowed != nullptr, cap, out_offsets, out_ids,
                        out_dists, out_layer, out_rank};
     return exact_range(dev, origin_id, io, nq, d, nullptr, err);
+}
+
+// The device side of hnswgpu_graph_search_batch(_device) and hnswgpu_exact_graph_batch(_device); capi.cpp holds the entries and
+// every argument check that needs no device, and refers to these two weakly (capi_index.hpp).  host: every buffer is plain host
+// memory, else device memory.  Both wait for `stream` before they return.
+
+// Approximate graph: chunk by chunk of at most HNSWGPU_GRAPH_CHUNK points (unset: what GRAPH_SCRATCH holds), the points' vectors
+// gathered on the device, searched by the batched search itself with knbn = k + 1, and compacted into the caller's rows.
+int graph_search(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, bool host, const uint64_t* point_ids, uint64_t np, uint64_t k, uint64_t ef,
+                 uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts, void* stream_v, std::string& err) {
+    if (np == 0) return OK;
+    const DeviceIndexView& v = dev.view();
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    OnDevice on(dev.device());
+    HIP_TRY(on.status());
+    std::string serr;
+    std::shared_ptr<void> ext = dev.extension([&]() { return make_state(dev, origin_id, serr); });
+    if (!ext) { err = serr.empty() ? "graph search: no device state" : serr; return ERR_DEVICE; }
+    const ExactState* st = static_cast<const ExactState*>(ext.get());
+    const GraphCall io{host, point_ids, np, k, out_ids, out_dists, out_layer, out_rank, out_counts};
+    struct Drain {
+        hipStream_t s;
+        ~Drain() { (void)hipStreamSynchronize(s); }
+    };
+    DevMem m_flat, m_scr;
+    GraphStage stage;
+    Drain drain{stream};  // (destroyed first: nothing of this call is running when its memory is freed)
+    int rc = graph_resolve(v, st, io, m_flat, stream, err);
+    if (rc != OK) return rc;
+    const uint32_t* d_flat = static_cast<const uint32_t*>(m_flat.p);
+
+    const uint64_t d = v.d, k1 = k + 1;
+    const uint64_t per_point = d * 4 + k1 * 17 + 4 + (host ? k * 17 + 4 : 0);
+    const int64_t knob = knobs().graph_chunk;
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>({np, GRAPH_SCRATCH / per_point, knob > 0 ? (uint64_t)knob : np}));
+    HIP_TRY(hipMalloc(&m_scr.p, round_up(chunk * d * 4, 256) + round_up(chunk * k1 * 8, 256) + 2 * round_up(chunk * k1 * 4, 256) + round_up(chunk * 4, 256) +
+                                    round_up(chunk * k1, 256)));
+    unsigned char* p = static_cast<unsigned char*>(m_scr.p);
+    float* d_q = reinterpret_cast<float*>(p); p += round_up(chunk * d * 4, 256);
+    GraphRows wide{};
+    wide.ids = reinterpret_cast<uint64_t*>(p); p += round_up(chunk * k1 * 8, 256);
+    wide.dists = reinterpret_cast<float*>(p); p += round_up(chunk * k1 * 4, 256);
+    wide.rank = reinterpret_cast<int32_t*>(p); p += round_up(chunk * k1 * 4, 256);
+    wide.counts = reinterpret_cast<uint32_t*>(p); p += round_up(chunk * 4, 256);
+    wide.layer = p;
+    if (host) HIP_TRY(stage.alloc(chunk, k));
+
+    for (uint64_t c0 = 0; c0 < np; c0 += chunk) {
+        const uint64_t cq = std::min(chunk, np - c0);
+        hipLaunchKernelGGL(graph_gather_kernel, dim3((uint32_t)((cq * d + 255) / 256)), dim3(256), 0, stream, v, d_flat + c0, cq * d, d_q);
+        HIP_TRY(hipGetLastError());
+        rc = dev.search_device(d_q, cq, d, k1, ef, wide.ids, wide.dists, wide.layer, wide.rank, wide.counts, nullptr, stream, nullptr, 0, nullptr, err);
+        if (rc != OK) return rc;
+        hipLaunchKernelGGL(graph_compact_kernel, dim3((uint32_t)cq), dim3(64), 0, stream, v, d_flat + c0, wide, host ? stage.rows : graph_rows_at(io, c0),
+                           (uint32_t)k);
+        HIP_TRY(hipGetLastError());
+        if (host) HIP_TRY(stage.copy_out(io, c0, cq, stream));
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    return OK;
+}
+
+// Exact graph: the exact k-NN's own chunk loop over tiles built from the rows themselves, the slab kernel's SELF variant
+int exact_graph(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, bool host, const uint64_t* point_ids, uint64_t np, uint64_t k,
+                const uint64_t* allowed, uint64_t n_allowed, uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank,
+                uint32_t* out_counts, void* stream_v, std::string& err) {
+    if (np == 0) return OK;
+    const DeviceIndexView& v = dev.view();
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    OnDevice on(dev.device());
+    HIP_TRY(on.status());
+    std::string serr;
+    std::shared_ptr<void> ext = dev.extension([&]() { return make_state(dev, origin_id, serr); });
+    if (!ext) { err = serr.empty() ? "exact graph: no device state" : serr; return ERR_DEVICE; }
+    const ExactState* st = static_cast<const ExactState*>(ext.get());
+    const GraphCall io{host, point_ids, np, k, out_ids, out_dists, out_layer, out_rank, out_counts};
+    DevMem m_flat, m_allowed;
+    GraphStage stage;
+    int rc = graph_resolve(v, st, io, m_flat, stream, err);  // (waits for the stream)
+    if (rc != OK) return rc;
+    const uint32_t* d_flat = static_cast<const uint32_t*>(m_flat.p);
+    const bool filtered = allowed != nullptr;
+    if (!host)
+        return exact_device(dev, origin_id, nullptr, np, v.d, k, allowed, n_allowed, filtered, nullptr, out_ids, out_dists, out_layer, out_rank, out_counts,
+                            stream, err, d_flat);
+    // (a filter that is empty still is a filter: a non-null pointer that is never dereferenced)
+    const uint64_t* d_allowed = filtered ? reinterpret_cast<const uint64_t*>(m_flat.p) : nullptr;
+    if (filtered && n_allowed != 0) {
+        HIP_TRY(hipMalloc(&m_allowed.p, n_allowed * sizeof(uint64_t)));
+        HIP_TRY(hipMemcpy(m_allowed.p, allowed, n_allowed * sizeof(uint64_t), hipMemcpyHostToDevice));
+        d_allowed = static_cast<const uint64_t*>(m_allowed.p);
+    }
+    // chunks of points: the staged answers stay within 64 MB whatever np is
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(np, (64ull << 20) / (k * 17 + 4)));
+    HIP_TRY(stage.alloc(chunk, k));
+    for (uint64_t c0 = 0; c0 < np; c0 += chunk) {
+        const uint64_t cq = std::min(chunk, np - c0);
+        rc = exact_device(dev, origin_id, nullptr, cq, v.d, k, d_allowed, n_allowed, filtered, nullptr, stage.rows.ids, stage.rows.dists, stage.rows.layer,
+                          stage.rows.rank, stage.rows.counts, stream, err, d_flat + c0);
+        if (rc != OK) return rc;
+        HIP_TRY(stage.copy_out(io, c0, cq, stream));
+    }
+    return OK;
 }
 
 }  // namespace hnswgpu

@@ -45,6 +45,8 @@ struct Knobs {
                                  // one-query kernels, literal kernel), applied behind every other bound (1 ..) -- a workgroup then answers many queries in turn
     int64_t range_hits_per_pass = -1;  // HNSWGPU_RANGE_HITS_PER_PASS (test hook): the answers one fill pass of the exact range search holds (1 .. 2^31; unset: 8 Mi) --
                                  // a small batch's chunk plan then takes several turns; a query with more answers still gets a pass of its own
+    int64_t graph_chunk = -1;    // HNSWGPU_GRAPH_CHUNK (test hook): the points one chunk of hnswgpu_graph_search_batch gathers and searches at most (1 ..; unset: what
+                                 // its 256 MiB of queries and staged answers hold)
 };
 const Knobs& knobs();
 void reload_knobs();

@@ -307,8 +307,8 @@ int hnswgpu_last_tie_count(const hnswgpu_index* idx, uint32_t* ties);
 
 /* The HNSWGPU_* tuning and test hooks (HNSWGPU_HASH_BITS, _NO_SCHED, _NO_INKERNEL, _STRICT_WG_PER_CU, _CAND_LDS, _WAVES_PER_CU,
  * _EXACT_FIRST, _TRACE_LAUNCH, _TRACE_HOST, _HOST_THREADS, _HOST_CHUNKS, _FFI_UNPACK, _FILTER_SET_MB; the test hooks
- * HNSWGPU_BITMAP_SLICES, HNSWGPU_LITERAL_CAND_CAP, HNSWGPU_MAX_WG and HNSWGPU_RANGE_HITS_PER_PASS) are read from the environment ONCE per
- * process, at the library's first search -- never on the launch path.  A caller that changes them afterwards (the tests do)
+ * HNSWGPU_BITMAP_SLICES, HNSWGPU_LITERAL_CAND_CAP, HNSWGPU_MAX_WG, HNSWGPU_RANGE_HITS_PER_PASS and HNSWGPU_GRAPH_CHUNK) are read from the
+ * environment ONCE per process, at the library's first search -- never on the launch path.  A caller that changes them afterwards (the tests do)
  * says so with this call.  Always HNSWGPU_OK.                                                                          */
 int hnswgpu_reload_env(void);
 
@@ -443,6 +443,56 @@ int hnswgpu_exact_range_search_batch_device(const hnswgpu_index* idx, const floa
                                             const float* d_radii, const uint64_t* d_allowed_ids, uint64_t n_allowed,
                                             uint64_t cap, uint64_t* d_out_offsets, uint64_t* d_out_ids, float* d_out_dists,
                                             uint8_t* d_out_layer, int32_t* d_out_rank, void* stream);
+
+/* ---------------------------------------------------------------- queries by stored point: the k-NN graph --- */
+/* The neighbours of points that are ALREADY IN THE INDEX: asked for one point, "more like this"; asked for every point, the
+ * k-nearest-neighbour graph of the data set (what embedders, graph clustering and duplicate detection start from).  The stored
+ * vectors are the queries and never leave the device, and "without the point itself" is defined by IDENTITY -- the point's own
+ * p_id -- not by its DataId and not by distance 0: exact copies of a point and other points that carry its DataId are
+ * neighbours like any other.  The reference has no such function; the contract is:
+ *   points    point_ids[0 .. np) are DataIds.  An id that several points carry names the FIRST of them in dump order.  The same id
+ *             may occur more than once; every occurrence gets its own row.  An id that no point carries: HNSWGPU_ERR_ARG, the
+ *             message gives the number of such ids -- BEFORE any out slot is written and before anything is searched (the ids are
+ *             resolved on the device, a binary search per id, and the count is read back first).
+ *             point_ids == NULL: every point.  np must then be hnswgpu_nb_point (else HNSWGPU_ERR_ARG), and row i is the point at
+ *             position i of the ascending (DataId, dump order) order -- with ids 0 .. n-1, row i is the point of id i.
+ *   output    as hnswgpu_search_batch: np x k row major, out_counts[i] entries in row i, the slots behind them zero; out_layer /
+ *             out_rank (the neighbours' p_ids) may be NULL.  k >= 1 (else HNSWGPU_ERR_ARG).
+ *
+ * hnswgpu_graph_search_batch -- the approximate graph, by the index's own search.  Row i is defined in four steps:
+ *   1. the answer hnswgpu_search_batch_device gives for the stored vector of point p_i (its first d elements) read as a query,
+ *      with knbn = k + 1 and this ef, under the index's arithmetic and tie setting: bit for bit the reference's `search`;
+ *   2. the entry whose p_id (layer, rank) is p_i's own is removed;
+ *   3. if no entry is the point's own (it can be missing: the search is approximate, and k + 1 exact copies may crowd it out) and
+ *      the answer has k + 1 entries, its last entry is removed;
+ *   4. out_counts[i] is what remains (at most k).
+ * Nothing else about the search changes.  The points are served in chunks of at most HNSWGPU_GRAPH_CHUNK (a test hook; unset:
+ * as many as keep the gathered queries and the (k + 1)-wide staged answers within 256 MiB): gathered, searched, compacted.
+ *
+ * hnswgpu_exact_graph_batch -- the exact graph, by exhaustive search as in hnswgpu_exact_search_batch (same distance, same key,
+ * same scratch budget).  Row i is the min(k, #candidates) points of smallest key (distance as f32 value, origin id ascending,
+ * then dump order) among the candidates: every point other than p_i itself, or, with a filter (allowed_ids: the SORTED id vector
+ * as in hnswgpu_exact_search_batch; unsorted: HNSWGPU_ERR_ARG from the host entry), the allowed points other than p_i itself.  A
+ * queried point need not be allowed; an allowed queried point is still no candidate of its own row.  The distance bits are those
+ * hnswgpu_exact_search_batch returns for the point's vector brought as a query.  An index of one point: count 0.  k is 1 .. 4096
+ * and an index set to HNSWGPU_ARITH_SIMD8 is refused, both HNSWGPU_ERR_ARG, as there.
+ *
+ * Out of scope, all of it: using dist(p, q) == dist(q, p) to halve the exact graph's work; filter sets; k above 4096; sharding
+ * over several GPUs; a symmetrised or CSR graph; the SIMD-order arithmetic for the exact call.
+ * Host buffers; upload the index on first use like hnswgpu_search_batch; take the handle's lock shared, like a search.      */
+int hnswgpu_graph_search_batch(const hnswgpu_index* idx, const uint64_t* point_ids, uint64_t np, uint64_t k, uint64_t ef,
+                               uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts);
+int hnswgpu_exact_graph_batch(const hnswgpu_index* idx, const uint64_t* point_ids, uint64_t np, uint64_t k,
+                              const uint64_t* allowed_ids, uint64_t n_allowed, uint64_t* out_ids, float* out_dists,
+                              uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts);
+/* The same with point_ids, the filter and the outputs in device memory, on HIP stream `stream`, waited for.  The index must be
+ * uploaded (else HNSWGPU_ERR_DEVICE).  The sortedness of d_allowed_ids is the caller's promise.                              */
+int hnswgpu_graph_search_batch_device(const hnswgpu_index* idx, const uint64_t* d_point_ids, uint64_t np, uint64_t k, uint64_t ef,
+                                      uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank,
+                                      uint32_t* d_out_counts, void* stream);
+int hnswgpu_exact_graph_batch_device(const hnswgpu_index* idx, const uint64_t* d_point_ids, uint64_t np, uint64_t k,
+                                     const uint64_t* d_allowed_ids, uint64_t n_allowed, uint64_t* d_out_ids, float* d_out_dists,
+                                     uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, void* stream);
 
 /* Test entry: the lane lab. The wave-level algorithms the search kernels are made of -- the reference's BinaryHeap (src/hnsw.rs:940,
  * :958-973, :1035-1053, :1544; std's push / pop / into_sorted_vec) as a memory heap and as a register heap, the sorted result set
