@@ -103,10 +103,13 @@ class BatchResult:
 
 class RangeResult:
     """The answers of a range search in CSR form: query q owns the slots offsets[q] .. offsets[q + 1] of ids, dists, layers and
-    ranks, ascending by (distance, origin id)."""
+    ranks, ascending by (distance, origin id).  An approximate range search (Hnsw.range_search_flat) also gives, per query, .ef
+    (the ef at which it settled) and .flags (bit 0: saturated -- the result set was full and inside the ball at ef_max); its answers
+    are in the search's own order."""
 
-    def __init__(self, offsets, ids, dists, layers, ranks):
+    def __init__(self, offsets, ids, dists, layers, ranks, ef=None, flags=None):
         self.offsets, self.ids, self.dists, self.layers, self.ranks = offsets, ids, dists, layers, ranks
+        self.ef, self.flags = ef, flags
 
     @property
     def counts(self):
@@ -440,6 +443,64 @@ class Hnsw:
     def exact_range_search(self, datas, radius, allowed_ids=None):
         """exact_range_search_flat as Vec<Vec<Neighbour>> in input order."""
         return self.exact_range_search_flat(datas, radius, allowed_ids).to_neighbours()
+
+    # ---- approximate range search through the graph (an extension) --------------------------------------------------
+    def range_search_flat(self, datas, radius, ef_first, ef_max, allowed_ids=None):
+        """Every point within `radius` (a scalar, or one value per row of `datas`) that the index's own search finds: per query
+        the search with knbn = ef = ef_first, 2 ef_first, ... (clamped to ef_max), restarted until its result set reaches past the
+        ball, returns fewer than ef entries or ef_max is reached; the answer is the prefix with distance <= radius of that one
+        search, bit for bit (ids, f32 distances, p_ids, the search's order).  allowed_ids: the SORTED id vector of a filter
+        (then ef_first >= 2).  Returns a RangeResult with .ef and .flags (bit 0: saturated, raise ef_max).  One call with a
+        guessed capacity, one more with the exact total when the guess was too small."""
+        datas = np.ascontiguousarray(datas, dtype=np.float32)
+        if datas.ndim != 2:
+            raise HnswError(N.ERR_ARG, "datas must be a (nq, d) matrix")
+        nq, d = datas.shape
+        radii = np.asarray(radius, dtype=np.float32)
+        if radii.ndim == 0:
+            radii = np.full(nq, radii, np.float32)
+        if radii.shape != (nq,):
+            raise HnswError(N.ERR_ARG, "radius must be a scalar or hold one radius per query")
+        radii = np.ascontiguousarray(radii)
+        offsets = np.zeros(nq + 1, np.uint64)
+        ef, flags = np.zeros(nq, np.uint32), np.zeros(nq, np.uint8)
+
+        def empty(cap):
+            return np.zeros(cap, np.uint64), np.zeros(cap, np.float32), np.zeros(cap, np.uint8), np.zeros(cap, np.int32)
+        allowed, n_allowed = None, 0
+        if allowed_ids is not None:
+            n_allowed = len(allowed_ids)
+            allowed = np.ascontiguousarray(allowed_ids, dtype=np.uint64) if n_allowed else np.zeros(1, np.uint64)
+        if self._h is None:
+            if not 1 <= ef_first <= ef_max <= 4096 or (allowed is not None and ef_first < 2):
+                raise HnswError(N.ERR_ARG, "1 <= ef_first <= ef_max <= 4096 (ef_first >= 2 with a filter)")
+            return RangeResult(offsets, *empty(0), ef, flags)
+        cap = max(1024, 32 * nq)
+        for attempt in range(2):
+            ids, dists, layers, ranks = empty(cap)
+            rc = self._lib.hnswgpu_range_search_batch(self._h, _p(datas), nq, d, _p(radii), ef_first, ef_max, _p(allowed), n_allowed, cap,
+                                                      _p(offsets), _p(ids), _p(dists), _p(layers), _p(ranks), _p(ef), _p(flags))
+            if rc != N.ERR_CAPACITY or attempt == 1:
+                break
+            cap = int(offsets[nq])
+        _check(rc)
+        total = int(offsets[nq])
+        return RangeResult(offsets, ids[:total], dists[:total], layers[:total], ranks[:total], ef, flags)
+
+    def range_search(self, datas, radius, ef_first, ef_max, allowed_ids=None):
+        """range_search_flat as Vec<Vec<Neighbour>> in input order."""
+        return self.range_search_flat(datas, radius, ef_first, ef_max, allowed_ids).to_neighbours()
+
+    def range_recall_flat(self, datas, radius, ef_first, ef_max, allowed_ids=None):
+        """(recall by id, share of saturated queries) of range_search_flat against exact_range_search_flat: the hits found (ids
+        of a query's answer that are in its exact answer) over the hits that exist; 1.0 when none exists."""
+        got = self.range_search_flat(datas, radius, ef_first, ef_max, allowed_ids)
+        exact = self.exact_range_search_flat(datas, radius, allowed_ids)
+        nq = len(exact.offsets) - 1
+        found = sum(len(np.intersect1d(got.of(q)[0], exact.of(q)[0])) for q in range(nq))
+        total = int(exact.offsets[nq])
+        saturated = float(np.count_nonzero(got.flags & 1)) / nq if nq else 0.0
+        return (found / total if total else 1.0), saturated
 
     # ---- queries by stored point: the k-NN graph of the indexed points (an extension) --------------------------------
     def _graph_call(self, entry, knbn, point_ids, *middle):

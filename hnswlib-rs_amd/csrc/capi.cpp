@@ -1067,6 +1067,93 @@ int hnswgpu_exact_graph_batch_device(const hnswgpu_index* cidx, const uint64_t* 
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
+// ---- approximate range search: the graph's answers cut at a radius, ef doubled until the result set reaches past the ball
+// (range_search.hip holds the device side)
+extern "C++" {
+namespace hnswgpu {
+__attribute__((weak)) int range_search_host(DeviceIndex&, const RangeSearchArgs&, std::string&);
+__attribute__((weak)) int range_search_device(DeviceIndex*, const RangeSearchArgs&, void*, std::string&);
+}  // namespace hnswgpu
+}  // extern "C++"
+// the checks both entries share; the handle's lock is held (shared)
+static int range_search_call(const hnswgpu_index* idx, const RangeSearchArgs& a) {
+    const uint64_t dim = idx->builder ? idx->builder->dimension() : (idx->flat ? idx->flat->dimension : 0);
+    if (!a.out_offsets) return fail(HNSWGPU_ERR_ARG, "null out_offsets: the offsets are written by every call");
+    if (a.nq != 0 && !a.queries) return fail(HNSWGPU_ERR_ARG, "null queries");
+    if (a.nq != 0 && !a.radii) return fail(HNSWGPU_ERR_ARG, "null radii: every query names its radius");
+    if (a.ef_first < 1) return fail(HNSWGPU_ERR_ARG, "ef_first must be >= 1");
+    if (a.ef_first > a.ef_max) return fail(HNSWGPU_ERR_ARG, "ef_first is above ef_max");
+    if (a.ef_max > 4096) return fail(HNSWGPU_ERR_ARG, "range search: ef_max above 4096");
+    if (a.n_allowed != 0 && !a.allowed) return fail(HNSWGPU_ERR_ARG, "null filter");
+    if (a.filtered && a.ef_first < 2)
+        return fail(HNSWGPU_ERR_ARG, "range search with a filter: ef_first must be >= 2 (the reference panics at ef == 1, src/hnsw.rs:973)");
+    if (a.cap != 0 && (!a.out_ids || !a.out_dists))
+        return fail(HNSWGPU_ERR_ARG, "cap > 0 with null out_ids or out_dists (the count-only call is cap == 0)");
+    if (a.nq > 0xFFFFFFF0ull) return fail(HNSWGPU_ERR_ARG, "too many queries in one batch");
+    if (dim != 0 && a.d != dim) return fail(HNSWGPU_ERR_ARG, "query dimension differs from the index dimension");
+    return HNSWGPU_OK;
+}
+
+int hnswgpu_range_search_batch(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, const float* radii, uint64_t ef_first,
+                               uint64_t ef_max, const uint64_t* allowed_ids, uint64_t n_allowed, uint64_t cap, uint64_t* out_offsets, uint64_t* out_ids,
+                               float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_ef, uint8_t* out_flags) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    const RangeSearchArgs a{queries, radii, nq, d, ef_first, ef_max, allowed_ids, n_allowed, allowed_ids != nullptr, cap, out_offsets, out_ids, out_dists,
+                            out_layer, out_rank, out_ef, out_flags};
+    int rc = range_search_call(idx, a);
+    if (rc != HNSWGPU_OK) return rc;
+    for (uint64_t i = 1; i < n_allowed; ++i)  // `impl FilterT for Vec<usize>` is a binary search: the vector must be sorted
+        if (allowed_ids[i - 1] > allowed_ids[i]) return fail(HNSWGPU_ERR_ARG, "the id vector of a filter must be sorted ascending");
+    const bool empty = idx->builder ? idx->builder->nb_point() == 0 : (!idx->flat || idx->flat->n == 0);
+    if (empty || nq == 0) {  // no point, or no query: every answer is empty
+        std::memset(out_offsets, 0, (nq + 1) * sizeof(uint64_t));
+        if (out_ef && nq != 0) std::memset(out_ef, 0, nq * sizeof(uint32_t));
+        if (out_flags && nq != 0) std::memset(out_flags, 0, nq);
+        return HNSWGPU_OK;
+    }
+    if (!hnswgpu::range_search_host) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = primary_replica(idx, sl, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    rc = hnswgpu::range_search_host(*dev, a, err);
+    if (rc != OK) return fail(rc, err);
+    return HNSWGPU_OK;
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswgpu_range_search_batch_device(const hnswgpu_index* cidx, const float* d_queries, uint64_t nq, uint64_t d, const float* d_radii,
+                                      uint64_t ef_first, uint64_t ef_max, const uint64_t* d_allowed_ids, uint64_t n_allowed, uint64_t cap,
+                                      uint64_t* d_out_offsets, uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank,
+                                      uint32_t* d_out_ef, uint8_t* d_out_flags, void* stream) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    const RangeSearchArgs a{d_queries, d_radii, nq, d, ef_first, ef_max, d_allowed_ids, n_allowed, d_allowed_ids != nullptr, cap, d_out_offsets, d_out_ids,
+                            d_out_dists, d_out_layer, d_out_rank, d_out_ef, d_out_flags};
+    int rc = range_search_call(idx, a);
+    if (rc != HNSWGPU_OK) return rc;
+    if (!hnswgpu::range_search_device) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    std::string err;
+    const bool empty = idx->builder ? idx->builder->nb_point() == 0 : (!idx->flat || idx->flat->n == 0);
+    if (empty || nq == 0) {  // no point, or no query: the offsets are zeroed on the caller's stream
+        rc = hnswgpu::range_search_device(nullptr, a, stream, err);
+        if (rc != OK) return fail(rc, err);
+        return HNSWGPU_OK;
+    }
+    DeviceIndex* dev = idx->primary >= 0 ? idx->replica(idx->primary) : nullptr;
+    if (!dev || idx->dev_stale || idx->flat_stale || !idx->flat)
+        return fail(HNSWGPU_ERR_DEVICE, "index is not resident on a device: call hnswgpu_upload first");
+    rc = hnswgpu::range_search_device(dev, a, stream, err);
+    if (rc != OK) return fail(rc, err);
+    return HNSWGPU_OK;
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
 static DeviceIndex* any_replica(hnswgpu_index* idx) {
     if (idx->primary >= 0 && idx->replica(idx->primary)) return idx->replica(idx->primary);
     return nullptr;

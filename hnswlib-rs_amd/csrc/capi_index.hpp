@@ -1,5 +1,5 @@
 // capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h, for the translation units
-// that implement entry points of the C ABI (capi.cpp; exact_knn.hip).  Private: not installed, not part of the ABI.
+// that implement entry points of the C ABI (capi.cpp; exact_knn.hip; range_search.hip).  Private: not installed, not part of the ABI.
 #pragma once
 #include <exception>
 #include <map>
@@ -77,6 +77,28 @@ int graph_search(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, bool 
 int exact_graph(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, bool host, const uint64_t* point_ids, uint64_t np, uint64_t k,
                 const uint64_t* allowed, uint64_t n_allowed, uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank,
                 uint32_t* out_counts, void* stream, std::string& err);
+// the device side of hnswgpu_range_search_batch(_device), defined in range_search.hip and referred to weakly in the same way: the
+// rounds of every group of queries through DeviceIndex::search_device (the arguments have been checked).  filtered: d_allowed /
+// allowed is a filter even when it is empty.  dev == nullptr (device entry on an empty index): the offsets are zeroed.  They return
+// HNSWGPU_ERR_CAPACITY, the offsets complete, when the answers need more than cap slots.
+struct RangeSearchArgs {
+    const float* queries;  // nq x d
+    const float* radii;    // [nq]
+    uint64_t nq, d, ef_first, ef_max;
+    const uint64_t* allowed;
+    uint64_t n_allowed;
+    bool filtered;
+    uint64_t cap;
+    uint64_t* out_offsets;  // [nq + 1]
+    uint64_t* out_ids;      // cap slots each; all four nullptr: the count-only call
+    float* out_dists;
+    uint8_t* out_layer;
+    int32_t* out_rank;
+    uint32_t* out_ef;       // [nq], may be nullptr
+    uint8_t* out_flags;     // [nq], may be nullptr
+};
+int range_search_host(DeviceIndex& dev, const RangeSearchArgs& a, std::string& err);
+int range_search_device(DeviceIndex* dev, const RangeSearchArgs& d_a, void* stream, std::string& err);
 }  // namespace hnswgpu
 
 // No C++ exception may cross the C ABI: every entry point is `try { ... HNSWGPU_CAPI_GUARD_END(ret)`

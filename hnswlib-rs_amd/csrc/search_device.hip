@@ -78,6 +78,10 @@ Knobs read_knobs() {
         const long long v = std::atoll(e);
         k.graph_chunk = v < 1 ? -1 : (int64_t)std::min<long long>(v, 1ll << 31);
     }
+    if (const char* e = std::getenv("HNSWGPU_RANGE_CHUNK")) {
+        const long long v = std::atoll(e);
+        k.range_chunk = v < 1 ? -1 : (int64_t)std::min<long long>(v, 1ll << 31);
+    }
     return k;
 }
 std::atomic<const Knobs*> g_knobs{nullptr};

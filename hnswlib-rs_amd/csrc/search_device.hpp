@@ -47,6 +47,8 @@ struct Knobs {
                                  // a small batch's chunk plan then takes several turns; a query with more answers still gets a pass of its own
     int64_t graph_chunk = -1;    // HNSWGPU_GRAPH_CHUNK (test hook): the points one chunk of hnswgpu_graph_search_batch gathers and searches at most (1 ..; unset: what
                                  // its 256 MiB of queries and staged answers hold)
+    int64_t range_chunk = -1;    // HNSWGPU_RANGE_CHUNK (test hook): the queries one group of hnswgpu_range_search_batch serves at most (1 ..; unset: as many as
+                                 // keep a round's staged answers and the group's held answers within 256 MiB each)
 };
 const Knobs& knobs();
 void reload_knobs();

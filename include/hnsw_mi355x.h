@@ -42,8 +42,9 @@ enum {
     HNSWGPU_ERR_EMPTY = 7,    /* operation needs a non-empty index                        */
     HNSWGPU_ERR_REF_PANIC = 8, /* filtered search: the reference panics on some of the queries
                                  (src/hnsw.rs:973) and no per-query status array was given  */
-    HNSWGPU_ERR_CAPACITY = 9  /* exact range search: the answers need more slots than `cap`;
-                                 the offsets are complete, no out slot was written          */
+    HNSWGPU_ERR_CAPACITY = 9  /* range search: the answers need more slots than `cap`; the offsets
+                                 are complete; exact call: no out slot was written; approximate
+                                 call (hnswgpu_range_search_batch): the out slots are unspecified */
 };
 
 /* metric selector == short type name of the anndists distance */
@@ -307,7 +308,7 @@ int hnswgpu_last_tie_count(const hnswgpu_index* idx, uint32_t* ties);
 
 /* The HNSWGPU_* tuning and test hooks (HNSWGPU_HASH_BITS, _NO_SCHED, _NO_INKERNEL, _STRICT_WG_PER_CU, _CAND_LDS, _WAVES_PER_CU,
  * _EXACT_FIRST, _TRACE_LAUNCH, _TRACE_HOST, _HOST_THREADS, _HOST_CHUNKS, _FFI_UNPACK, _FILTER_SET_MB; the test hooks
- * HNSWGPU_BITMAP_SLICES, HNSWGPU_LITERAL_CAND_CAP, HNSWGPU_MAX_WG, HNSWGPU_RANGE_HITS_PER_PASS and HNSWGPU_GRAPH_CHUNK) are read from the
+ * HNSWGPU_BITMAP_SLICES, HNSWGPU_LITERAL_CAND_CAP, HNSWGPU_MAX_WG, HNSWGPU_RANGE_HITS_PER_PASS, HNSWGPU_GRAPH_CHUNK and HNSWGPU_RANGE_CHUNK) are read from the
  * environment ONCE per process, at the library's first search -- never on the launch path.  A caller that changes them afterwards (the tests do)
  * says so with this call.  Always HNSWGPU_OK.                                                                          */
 int hnswgpu_reload_env(void);
@@ -443,6 +444,54 @@ int hnswgpu_exact_range_search_batch_device(const hnswgpu_index* idx, const floa
                                             const float* d_radii, const uint64_t* d_allowed_ids, uint64_t n_allowed,
                                             uint64_t cap, uint64_t* d_out_offsets, uint64_t* d_out_ids, float* d_out_dists,
                                             uint8_t* d_out_layer, int32_t* d_out_rank, void* stream);
+
+/* ---------------------------------------------------------------- approximate range search --- */
+/* Every point within a query's radius that the GRAPH finds: the range query at the cost of a search, not of a scan over every row
+ * (hnswgpu_exact_range_search_batch is its ground truth).  The reference has no such function; the contract is defined step by step
+ * through the index's own search, so that every answer is one call of the reference's `search`, bit for bit.
+ * Let the ef sequence be e_0 = ef_first, e_{j+1} = min(2 e_j, ef_max).  Query q is defined in rounds j = 0, 1, ...:
+ *   1. A_j is the answer hnswgpu_search_batch_device gives for q with knbn = e_j and ef = e_j -- with a filter (allowed_ids !=
+ *      NULL), the answer of hnswgpu_search_batch_filtered_device under allowed_ids -- in the index's arithmetic (scalar or SIMD
+ *      order) and tie setting: the reference's search / search_filter, its whole final result set, ascending.  c_j is its count.
+ *   2. m_j is the length of the longest prefix of A_j whose distances satisfy dist <= radii[q] as an IEEE f32 comparison of
+ *      values.  A NaN or negative radius gives 0; -0.0 and +0.0 match a distance of +-0; +inf matches every distance that is
+ *      not NaN.
+ *   3. q is SETTLED in the first round where one of these holds: (a) m_j < c_j: the result set reached past the ball;
+ *      (b) c_j < e_j: the search returned everything it can reach; (c) e_j == ef_max.
+ *   4. q's answer is the first m_j entries of that A_j in the search's own order: ids, f32 distance bits and p_ids as the search
+ *      wrote them.  out_ef[q] = e_j.  out_flags[q] bit 0 (SATURATED) is set iff q settled with m_j == c_j == e_j -- under rule
+ *      (c) only: the ball may hold more, the caller raises ef_max.  out_ef and out_flags may be NULL.
+ * Nothing else about the search changes.  A settled query is never searched again; an unsettled one is searched again FROM
+ * SCRATCH at the next ef -- there is no continuation, which is what keeps every row equal to one call of the reference.
+ *   arguments 1 <= ef_first <= ef_max <= 4096, else HNSWGPU_ERR_ARG (above 1024 the literal-heap kernel serves the round, as in
+ *             hnswgpu_search_batch_device).  With a filter ef_first >= 2: the only input on which the reference panics needs
+ *             ef == 1 (src/hnsw.rs:973), so this call has no panic status.  The filter is the SORTED id vector of
+ *             hnswgpu_search_batch_filtered (unsorted: HNSWGPU_ERR_ARG from the host entry); an empty vector (a non-NULL
+ *             pointer, n_allowed == 0) allows nothing.  nq == 0 or an empty index: HNSWGPU_OK, all offsets zero.
+ *   output    CSR as in hnswgpu_exact_range_search_batch: out_offsets[0 .. nq] is u64 and is ALWAYS written completely; cap = the
+ *             slots behind the four out arrays (out_layer / out_rank may be NULL); cap == 0 with NULL out arrays is the
+ *             count-only call, which holds no answers; cap > 0 with a NULL out_ids or out_dists is HNSWGPU_ERR_ARG.
+ *   capacity  total > cap: HNSWGPU_ERR_CAPACITY, hnswgpu_last_error() names the total -- and, UNLIKE the exact call, the contents
+ *             of the out arrays are then unspecified: the batch is served group by group, the total is not known before the last
+ *             group, and from the group that overflows onward the call only counts.
+ *   memory    the batch is served in groups of consecutive queries, each group running all its rounds before the next starts.  A
+ *             group holds at most HNSWGPU_RANGE_CHUNK queries (a test hook); unset, as many as keep the staged answers of a round
+ *             and the group's held answers (each at most group x ef_max x 17 bytes) and its gathered queries within 256 MiB
+ *             each.  Device memory is a fixed budget that does not depend on nq, for both entries.
+ * Takes the handle's lock shared and is legal from several host threads at once.  Host buffers; uploads the index on first use.
+ * Out of scope: filter sets, queries by stored point, sharding over GPUs, tickets (_begin / _end), any slack or ratio in the
+ * stop rule, continuing a search instead of restarting it.                                                                  */
+int hnswgpu_range_search_batch(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, const float* radii,
+                               uint64_t ef_first, uint64_t ef_max, const uint64_t* allowed_ids, uint64_t n_allowed, uint64_t cap,
+                               uint64_t* out_offsets, uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank,
+                               uint32_t* out_ef, uint8_t* out_flags);
+/* The same with every buffer in HBM (radii, filter, offsets, ef and flags too), on HIP stream `stream`, waited for; the out arrays
+ * hold cap slots and are written in place.  The index must be uploaded (else HNSWGPU_ERR_DEVICE).  The sortedness of
+ * d_allowed_ids is the caller's promise.  One word is read back per round and group: the host sizes the next launch.        */
+int hnswgpu_range_search_batch_device(const hnswgpu_index* idx, const float* d_queries, uint64_t nq, uint64_t d, const float* d_radii,
+                                      uint64_t ef_first, uint64_t ef_max, const uint64_t* d_allowed_ids, uint64_t n_allowed,
+                                      uint64_t cap, uint64_t* d_out_offsets, uint64_t* d_out_ids, float* d_out_dists,
+                                      uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_ef, uint8_t* d_out_flags, void* stream);
 
 /* ---------------------------------------------------------------- queries by stored point: the k-NN graph --- */
 /* The neighbours of points that are ALREADY IN THE INDEX: asked for one point, "more like this"; asked for every point, the
