@@ -593,6 +593,21 @@ class Hnsw:
         """Extension: "simd8" = distances of the following searches summed in the order of the crate's simdeez_f build."""
         _check(self._lib.hnswgpu_set_arithmetic(self._h, ARITH[arithmetic]))
 
+    def set_storage(self, storage="f32"):
+        """Extension: how the replicas hold the vectors in HBM.  "f16" = rows stored as IEEE binary16 (half the bytes) where every
+        stored element is representable (round_to_f16 the data BEFORE building: the library only verifies); the answers of every
+        search are those of the same index at "f32", bit for bit.  Raises HnswError(ERR_ARG) naming the first offending point."""
+        _check(self._lib.hnswgpu_set_storage(self._h, STORAGE[storage]))
+
+    def get_storage(self):
+        return STORAGE_NAME[self._lib.hnswgpu_get_storage(self._h)]
+
+    def device_bytes(self, device=0):
+        """Bytes of the replica resident on `device` (upload first; a change of storage or an insert makes it stale)."""
+        n = C.c_uint64()
+        _check(self._lib.hnswgpu_device_bytes(self._h, int(device), C.byref(n)))
+        return n.value
+
     def last_tie_count(self):
         n = C.c_uint32()
         _check(self._lib.hnswgpu_last_tie_count(self._h, C.byref(n)))
@@ -687,15 +702,38 @@ def load_description(graph_file_path):
 
 
 ARITH = {"scalar": N.HEADER.constants["HNSWGPU_ARITH_SCALAR"], "simd8": N.HEADER.constants["HNSWGPU_ARITH_SIMD8"]}
+STORAGE = {"f32": N.HEADER.constants["HNSWGPU_STORAGE_F32"], "f16": N.HEADER.constants["HNSWGPU_STORAGE_F16"]}
+STORAGE_NAME = {v: k for k, v in STORAGE.items()}
 
 
-def eval_distance_matrix(dist, queries, rows, batch, arithmetic="scalar"):
+def round_to_f16(x):
+    """x rounded to the nearest IEEE binary16 and widened back: contiguous f32 that Hnsw.set_storage("f16") accepts."""
+    with np.errstate(over="ignore"):
+        return np.ascontiguousarray(np.asarray(x, dtype=np.float32).astype(np.float16).astype(np.float32))
+
+
+def f16_representable(x):
+    """(number of elements of x that binary16 cannot hold exactly -- NaN counts --, flat index of the first or None)."""
+    a = np.ascontiguousarray(x, dtype=np.float32)
+    first = C.c_uint64(0)
+    bad = N.lib().hnswgpu_f16_representable(_p(a), a.size, C.byref(first))
+    return bad, (first.value if bad else None)
+
+
+def eval_distance_matrix(dist, queries, rows, batch, arithmetic="scalar", storage="f32"):
     """out[q][r] = Distance<f32>::eval(queries[q], rows[r]) on the device, by the search kernel's own distance routine with
     the rows taken in batches of `batch` (1..64) -- the lane-group branches the search takes for that many neighbours.
-    arithmetic: "scalar" (the crate's default build) or "simd8" (the summation order of its simdeez_f build)."""
+    arithmetic: "scalar" (the crate's default build) or "simd8" (the summation order of its simdeez_f build).
+    storage: "f16" = the rows (representable ones only) narrowed to binary16 before the kernel reads them (scalar arithmetic)."""
     q = np.ascontiguousarray(queries, dtype=np.float32)
     r = np.ascontiguousarray(rows, dtype=np.float32)
     out = np.zeros((q.shape[0], r.shape[0]), np.float32)
+    if storage != "f32":
+        if arithmetic != "scalar":
+            raise HnswError(N.ERR_ARG, "half-precision rows are read in the scalar arithmetic only")
+        _check(N.lib().hnswgpu_eval_distance_matrix_storage(N.DIST[dist], STORAGE[storage], _p(q), q.shape[0], _p(r), r.shape[0], q.shape[1],
+                                                            batch, _p(out)))
+        return out
     _check(N.lib().hnswgpu_eval_distance_matrix_arith(N.DIST[dist], ARITH[arithmetic], _p(q), q.shape[0], _p(r), r.shape[0], q.shape[1],
                                                       batch, _p(out)))
     return out

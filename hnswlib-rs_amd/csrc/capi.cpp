@@ -62,6 +62,7 @@ static int ensure_device(hnswgpu_index* idx, int device) {
     if (!idx->replica(device)) {
         std::unique_ptr<DeviceIndex> dev(new DeviceIndex());
         std::string err;
+        dev->set_storage(idx->storage);
         int rc = dev->upload(*f, device, err);
         if (rc != OK) return fail(rc, err);
         if (idx->strict_ties >= 0) dev->set_strict_ties(idx->strict_ties != 0);
@@ -89,9 +90,29 @@ static int primary_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mute
     return fail(HNSWGPU_ERR_DEVICE, "index changed while a search was starting");
 }
 
+// primary_replica for the entries that read rows outside the search path.  Their argument checks refused an F16 index under the
+// shared lock, but primary_replica gives that lock up while it uploads: a hnswgpu_set_storage(F16) in between makes the replica a
+// half one, which those kernels would read as f32, past its end.  So the replica itself is asked.
+static int primary_f32_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mutex>& sl, DeviceIndex** out) {
+    int rc = primary_replica(idx, sl, out);
+    if (rc != HNSWGPU_OK) return rc;
+    if ((*out)->storage() != STORAGE_F32) {
+        *out = nullptr;
+        return fail(HNSWGPU_ERR_ARG, "this call reads f32 rows only: the index was set to HNSWGPU_STORAGE_F16 while the call was starting "
+                                     "(hnswgpu_set_storage(idx, HNSWGPU_STORAGE_F32) first)");
+    }
+    return HNSWGPU_OK;
+}
+
 namespace hnswgpu {
 int capi_fail(int code, const std::string& msg) { return fail(code, msg); }
+int capi_primary_f32_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mutex>& sl, DeviceIndex** out) { return primary_f32_replica(idx, sl, out); }
 int capi_primary_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mutex>& sl, DeviceIndex** out) { return primary_replica(idx, sl, out); }
+int capi_refuse_f16(const hnswgpu_index* idx, const char* what) {
+    if (idx->storage != HNSWGPU_STORAGE_F16) return HNSWGPU_OK;
+    return fail(HNSWGPU_ERR_ARG, std::string(what) + " reads f32 rows only: the index is set to HNSWGPU_STORAGE_F16 "
+                                 "(hnswgpu_set_storage(idx, HNSWGPU_STORAGE_F32) first)");
+}
 }  // namespace hnswgpu
 
 extern "C" {
@@ -212,6 +233,11 @@ int hnswgpu_build(const float* data, uint64_t n, uint64_t d, const uint64_t* ids
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
+static uint64_t idx_nb_point(const hnswgpu_index* idx) { return idx->builder ? idx->builder->nb_point() : (idx->flat ? idx->flat->n : 0); }
+static std::string unrepresentable_message(uint64_t bad, uint64_t data_id, uint64_t dim) {
+    return "HNSWGPU_STORAGE_F16: " + std::to_string(bad) + " vector elements are not representable as binary16 (NaN, or (f32)(f16)x != x); "
+           "the first is dimension " + std::to_string(dim) + " of the point with DataId " + std::to_string(data_id);
+}
 // Hnsw::insert / parallel_insert on ANY handle, reloaded ones included (HnswIo::load_hnsw returns a fully insertable
 // Hnsw).  Exclusive lock held by the caller.
 static int insert_points(hnswgpu_index* idx, const float* data, uint64_t n, uint64_t d, const uint64_t* ids, int nthreads,
@@ -220,6 +246,16 @@ static int insert_points(hnswgpu_index* idx, const float* data, uint64_t n, uint
         if (!idx->flat) return fail(HNSWGPU_ERR_EMPTY, "handle holds no index");
         idx->builder.reset(new GraphBuilder(*idx->flat, false));  // continue the reloaded graph (builder.hpp)
         idx->params = idx->builder->params();
+    }
+    // an F16 index: the NEW vectors first -- one element that a half cannot hold refuses the whole call.  (Rows of another dimension
+    // than the index's are the builder's to refuse, below: an element index counted with the caller's d would name the wrong one.)
+    const uint64_t dim = idx->builder->dimension();
+    if (idx->storage == HNSWGPU_STORAGE_F16 && d != 0 && (dim == 0 || d == dim)) {
+        uint64_t first = 0;
+        const uint64_t bad = f16_count_unrepresentable(data, n * d, &first);
+        if (bad != 0)
+            return fail(HNSWGPU_ERR_ARG, unrepresentable_message(bad, ids ? ids[first / d] : idx_nb_point(idx) + first / d, first % d) +
+                                         "; nothing was inserted");
     }
     std::string err;
     int rc;
@@ -418,6 +454,7 @@ static int ensure_devices(hnswgpu_index* idx, const int* devices, int n) {
         auto upload_one = [&](size_t i) {
             try {
                 fresh[i].reset(new DeviceIndex());
+                fresh[i]->set_storage(idx->storage);
                 rcs[i] = fresh[i]->upload(*f, missing[i], errs[i]);
             } catch (const std::exception& e) {
                 rcs[i] = ERR_DEVICE;
@@ -793,7 +830,7 @@ static int exact_filter_set_call(const hnswgpu_index* idx, uint64_t nq, uint64_t
     if (dim != 0 && d != dim) return fail(HNSWGPU_ERR_ARG, "query dimension differs from the index dimension");
     if (idx->arithmetic != HNSWGPU_ARITH_SCALAR)
         return fail(HNSWGPU_ERR_ARG, "exact search answers in the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
-    return HNSWGPU_OK;
+    return capi_refuse_f16(idx, "exact search");
 }
 
 int hnswgpu_exact_search_batch_filter_set(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, uint64_t k,
@@ -837,7 +874,7 @@ int hnswgpu_exact_search_batch_filter_set(const hnswgpu_index* cidx, const float
     if (nq == 0) return HNSWGPU_OK;
     if (!hnswgpu::exact_filter_set_host) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     DeviceIndex* dev = nullptr;
-    rc = primary_replica(idx, sl, &dev);
+    rc = primary_f32_replica(idx, sl, &dev);
     if (rc != HNSWGPU_OK) return rc;
     std::string err;
     const FilterSet set{filter_ids, filter_offsets, n_filters, filter_of};
@@ -897,7 +934,7 @@ static int exact_range_call(const hnswgpu_index* idx, const void* queries, uint6
     if (n_allowed != 0 && !allowed) return fail(HNSWGPU_ERR_ARG, "null filter");
     if (idx->arithmetic != HNSWGPU_ARITH_SCALAR)
         return fail(HNSWGPU_ERR_ARG, "exact range search answers in the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
-    return HNSWGPU_OK;
+    return capi_refuse_f16(idx, "exact range search");
 }
 
 int hnswgpu_exact_range_search_batch(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, const float* radii,
@@ -918,7 +955,7 @@ int hnswgpu_exact_range_search_batch(const hnswgpu_index* cidx, const float* que
     }
     if (!hnswgpu::exact_range_host) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     DeviceIndex* dev = nullptr;
-    rc = primary_replica(idx, sl, &dev);
+    rc = primary_f32_replica(idx, sl, &dev);
     if (rc != HNSWGPU_OK) return rc;
     std::string err;
     rc = hnswgpu::exact_range_host(*dev, idx->flat->origin_id, queries, nq, d, radii, allowed_ids, n_allowed, cap, out_offsets, out_ids, out_dists,
@@ -967,12 +1004,12 @@ static int graph_call(const hnswgpu_index* idx, const void* point_ids, uint64_t 
         return fail(HNSWGPU_ERR_ARG, "point_ids is NULL (every point): np must be nb_point = " + std::to_string(n) + ", not " + std::to_string(np));
     if (k == 0) return fail(HNSWGPU_ERR_ARG, "knbn must be > 0");
     if (np > 0xFFFFFFF0ull) return fail(HNSWGPU_ERR_ARG, "too many points in one batch");
-    if (!exact) return HNSWGPU_OK;
+    if (!exact) return capi_refuse_f16(idx, "the graph search (its gather kernel copies stored rows)");
     if (k > 4096) return fail(HNSWGPU_ERR_ARG, "exact graph: knbn above 4096");
     if (n_allowed != 0 && !allowed) return fail(HNSWGPU_ERR_ARG, "null filter");
     if (idx->arithmetic != HNSWGPU_ARITH_SCALAR)
         return fail(HNSWGPU_ERR_ARG, "exact graph answers in the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
-    return HNSWGPU_OK;
+    return capi_refuse_f16(idx, "exact graph");
 }
 // what the host entries do behind the checks: an empty index names no point; else the replica, uploaded on first use
 static int graph_host_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mutex>& sl, uint64_t np, bool have_device_side, DeviceIndex** dev) {
@@ -981,7 +1018,7 @@ static int graph_host_replica(hnswgpu_index* idx, std::shared_lock<std::shared_m
     const bool empty = idx->builder ? idx->builder->nb_point() == 0 : (!idx->flat || idx->flat->n == 0);
     if (empty) return fail(HNSWGPU_ERR_ARG, std::to_string(np) + " of the " + std::to_string(np) + " point_ids name no point of the index");
     if (!have_device_side) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    return primary_replica(idx, sl, dev);
+    return primary_f32_replica(idx, sl, dev);
 }
 
 int hnswgpu_graph_search_batch(const hnswgpu_index* cidx, const uint64_t* point_ids, uint64_t np, uint64_t k, uint64_t ef, uint64_t* out_ids,
@@ -1182,8 +1219,58 @@ int hnswgpu_set_arithmetic(hnswgpu_index* idx, int arithmetic) {
     if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
     if (arithmetic != HNSWGPU_ARITH_SCALAR && arithmetic != HNSWGPU_ARITH_SIMD8) return fail(HNSWGPU_ERR_ARG, "unknown arithmetic");
     std::unique_lock<std::shared_mutex> g(idx->mu);
+    if (arithmetic == HNSWGPU_ARITH_SIMD8 && idx->storage == HNSWGPU_STORAGE_F16)
+        return fail(HNSWGPU_ERR_ARG, "HNSWGPU_ARITH_SIMD8 reads f32 rows only: the index is set to HNSWGPU_STORAGE_F16");
     idx->arithmetic = arithmetic;
     for (auto& kv : idx->replicas) kv.second->set_arithmetic(arithmetic);
+    return HNSWGPU_OK;
+}
+int hnswgpu_set_storage(hnswgpu_index* idx, int storage) {
+    CAPI_GUARD_BEGIN
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    if (storage != HNSWGPU_STORAGE_F32 && storage != HNSWGPU_STORAGE_F16) return fail(HNSWGPU_ERR_ARG, "unknown storage");
+    std::unique_lock<std::shared_mutex> g(idx->mu);
+    if (storage == idx->storage) return HNSWGPU_OK;
+    if (storage == HNSWGPU_STORAGE_F16) {
+        if (!idx->builder && !idx->flat) return fail(HNSWGPU_ERR_EMPTY, "handle holds no index");
+        const int dist = idx->builder ? idx->params.dist : idx->flat->dist;
+        if (dist != DIST_L2 && dist != DIST_COSINE && dist != DIST_DOT && dist != DIST_L1)
+            return fail(HNSWGPU_ERR_ARG, "HNSWGPU_STORAGE_F16 serves DistL2, DistCosine, DistDot and DistL1 only");
+        if (idx->arithmetic == HNSWGPU_ARITH_SIMD8)
+            return fail(HNSWGPU_ERR_ARG, "HNSWGPU_STORAGE_F16 is read in the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
+        // the caller rounds, the library only verifies: every stored vector, on the host
+        const FlatIndex* f = idx->get_flat();
+        if (f && f->n != 0) {
+            uint64_t first = 0;
+            const uint64_t bad = f16_count_unrepresentable(f->vectors.data(), f->n * f->dimension, &first);
+            if (bad != 0)
+                return fail(HNSWGPU_ERR_ARG, unrepresentable_message(bad, f->origin_id[first / f->dimension], first % f->dimension) +
+                                             "; the index keeps its storage");
+        }
+    }
+    idx->storage = storage;
+    idx->dev_stale = true;  // like an insert: the next upload, explicit or in front of a search, makes replicas of the new kind
+    return HNSWGPU_OK;
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+int hnswgpu_get_storage(const hnswgpu_index* cidx) {
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> g(idx->mu);
+    return idx->storage;
+}
+uint64_t hnswgpu_f16_representable(const float* x, uint64_t n, uint64_t* first_bad) {
+    if (!x || n == 0) return 0;
+    return f16_count_unrepresentable(x, n, first_bad);
+}
+int hnswgpu_device_bytes(const hnswgpu_index* cidx, int device, uint64_t* bytes) {
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx || !bytes) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> g(idx->mu);
+    if (device < 0) device = idx->primary;
+    DeviceIndex* dev = idx->dev_stale || idx->flat_stale ? nullptr : idx->replica(device);
+    if (!dev) return fail(HNSWGPU_ERR_DEVICE, "index is not resident on that device (hnswgpu_upload first)");
+    *bytes = dev->bytes();
     return HNSWGPU_OK;
 }
 int hnswgpu_set_strict_ties(hnswgpu_index* idx, int on) {
@@ -1233,6 +1320,37 @@ int hnswgpu_eval_distance_matrix_arith(int dist, int arithmetic, const float* qu
     if (!queries || !rows || !out || dist < 0 || dist >= DIST_COUNT) return fail(HNSWGPU_ERR_ARG, "bad argument");
     std::string err;
     int rc = eval_distance_matrix_device(dist, queries, nq, rows, n, d, batch, false, out, err, arithmetic);
+    if (rc != OK) return fail(rc, err);
+    return HNSWGPU_OK;
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+// Referred to weakly, like the filter-set, exact, range and graph entries: the host-only build of the C ABI (the sanitizer build, whose
+// stand-in for search_device.hip defines the device entries that existed when it was written, eval_distance_matrix_device among
+// them) links without it and answers "no device".
+extern "C++" {
+namespace hnswgpu {
+__attribute__((weak)) int eval_distance_matrix_storage_device(int, int, const float*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, float*,
+                                                              std::string&);
+}  // namespace hnswgpu
+}  // extern "C++"
+int hnswgpu_eval_distance_matrix_storage(int dist, int storage, const float* queries, uint64_t nq, const float* rows, uint64_t n,
+                                         uint64_t d, uint32_t batch, float* out) {
+    CAPI_GUARD_BEGIN
+    if (!queries || !rows || !out || dist < 0 || dist >= DIST_COUNT) return fail(HNSWGPU_ERR_ARG, "bad argument");
+    if (storage != HNSWGPU_STORAGE_F32 && storage != HNSWGPU_STORAGE_F16) return fail(HNSWGPU_ERR_ARG, "unknown storage");
+    if (storage == HNSWGPU_STORAGE_F16) {  // (the one place these two are checked: the device side converts what it is handed)
+        if (dist != DIST_L2 && dist != DIST_COSINE && dist != DIST_DOT && dist != DIST_L1)
+            return fail(HNSWGPU_ERR_ARG, "HNSWGPU_STORAGE_F16 serves DistL2, DistCosine, DistDot and DistL1 only");
+        uint64_t first = 0;
+        const uint64_t bad = d ? f16_count_unrepresentable(rows, n * d, &first) : 0;
+        if (bad != 0)
+            return fail(HNSWGPU_ERR_ARG, std::to_string(bad) + " row elements are not representable as binary16; the first is element " +
+                                         std::to_string(first % d) + " of row " + std::to_string(first / d));
+    }
+    if (!hnswgpu::eval_distance_matrix_storage_device) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    std::string err;
+    int rc = hnswgpu::eval_distance_matrix_storage_device(dist, storage, queries, nq, rows, n, d, batch, out, err);
     if (rc != OK) return fail(rc, err);
     return HNSWGPU_OK;
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)

@@ -27,6 +27,7 @@ struct hnswgpu_index {
     bool dev_stale = true;
     int strict_ties = -1;  // -1: library default (env HNSWGPU_STRICT_TIES, else on)
     int arithmetic = 0;    // HNSWGPU_ARITH_*
+    int storage = 0;       // HNSWGPU_STORAGE_*: how the replicas hold the rows (handed to each one before its upload)
     hnswgpu::BuildParams params;
 
     const hnswgpu::FlatIndex* get_flat() {  // exclusive lock held (or the view is known to be fresh)
@@ -51,6 +52,12 @@ namespace hnswgpu {
 int capi_fail(int code, const std::string& msg);
 // the replica a search on the primary device uses, uploaded first where need be (`sl`: the handle's lock, held shared)
 int capi_primary_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mutex>& sl, DeviceIndex** out);
+// the same for the entries that read rows outside the search path: HNSWGPU_ERR_ARG when the replica turns out to be a half one (the
+// index's storage was changed while the lock was given up for the upload)
+int capi_primary_f32_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mutex>& sl, DeviceIndex** out);
+// HNSWGPU_OK, or -- the index is set to HNSWGPU_STORAGE_F16 -- HNSWGPU_ERR_ARG with a message that names `what`: the calls that
+// read rows outside the search path (exact k-NN / range / graph, the stored-point queries) exist for f32 rows only
+int capi_refuse_f16(const hnswgpu_index* idx, const char* what);
 // the device side of hnswgpu_exact_search_batch_filter_set(_device), defined in exact_knn.hip: the exact k-NN of every query q
 // under filter filter_of[q] of the set (the arguments have been checked).  capi.cpp refers to these two weakly, like the search's
 // own filter-set pair (search_device.hpp): a host-only build of the C ABI links without them and answers "no device".

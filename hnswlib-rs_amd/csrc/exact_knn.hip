@@ -686,7 +686,7 @@ int check_call(hnswgpu_index* idx, const void* queries, uint64_t nq, uint64_t d,
     if (n_allowed != 0 && !allowed) return capi_fail(HNSWGPU_ERR_ARG, "null filter");
     if (idx->arithmetic != HNSWGPU_ARITH_SCALAR)
         return capi_fail(HNSWGPU_ERR_ARG, "exact search answers in the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
-    return HNSWGPU_OK;
+    return capi_refuse_f16(idx, "exact search");
 }
 
 // device memory of the host-buffer entry
@@ -1496,7 +1496,7 @@ int hnswgpu_exact_search_batch(const hnswgpu_index* cidx, const float* queries, 
         return HNSWGPU_OK;
     }
     DeviceIndex* dev = nullptr;
-    rc = capi_primary_replica(idx, sl, &dev);
+    rc = capi_primary_f32_replica(idx, sl, &dev);
     if (rc != HNSWGPU_OK) return rc;
     if (nq == 0) return HNSWGPU_OK;
     std::string err;

@@ -153,6 +153,16 @@ private:
 constexpr uint64_t PAIR_SEARCH_AUTO_MIN_QUERIES = 40000;  // hnsw_search_pair_kernel as the first pass of a strict DistCosine / DistDot batch (rows of one 128-byte line) of at least this many queries
 constexpr int STRICT_WG_PER_CU = 16;  // resident workgroups per CU of a strict launch: four waves per SIMD (see search_device)
 
+// DistCosine's squared norm of one stored vector, the arithmetic of row_sq_norms_kernel on the host
+double row_sq_norm_host(const float* r, uint64_t d) {
+    double s2 = 0.;
+    for (uint64_t c = 0; c < d; ++c) {
+        const float sq = r[c] * r[c];
+        s2 = s2 + (double)sq;
+    }
+    return s2;
+}
+
 uint32_t ceil_log2(uint64_t x) {
     uint32_t b = 0;
     while ((1ull << b) < x) ++b;
@@ -171,6 +181,10 @@ const KernelSet& kernel_set(int metric) {
         case KM_COSINE_SIMD8: return kernels_for<KM_COSINE_SIMD8>();
         case KM_DOT_SIMD8: return kernels_for<KM_DOT_SIMD8>();
         case KM_L1_SIMD8: return kernels_for<KM_L1_SIMD8>();
+        case KM_L2_F16: return kernels_for<KM_L2_F16>();
+        case KM_COSINE_F16: return kernels_for<KM_COSINE_F16>();
+        case KM_DOT_F16: return kernels_for<KM_DOT_F16>();
+        case KM_L1_F16: return kernels_for<KM_L1_F16>();
         default: return kernels_for<DIST_L1>();
     }
 }
@@ -445,6 +459,7 @@ void DeviceIndex::release() {
 }
 
 int DeviceIndex::kernel_metric() const {
+    if (storage_ == STORAGE_F16) return f16_kernel_metric(dist_);  // (upload() refused the metrics without one)
     if (arith_.load() == ARITH_SIMD8) {
         const int km = simd8_kernel_metric(dist_);
         if (km >= 0) return km;
@@ -462,6 +477,8 @@ int DeviceIndex::upload(const FlatIndex& x, int device, std::string& err) {
     if (x.n == 0 || x.entry_flat == NO_POINT) { err = "cannot upload an empty index"; return ERR_EMPTY; }
     // bit 31 of a flat id is the EXPANDED flag of the result set
     if (x.n >= 0x80000000ull) { err = "index too large for the device path (2^31 points or more)"; return ERR_ARG; }
+    const bool half_rows = storage_ == STORAGE_F16;
+    if (half_rows && f16_kernel_metric(x.dist) < 0) { err = "half-precision storage serves DistL2, DistCosine, DistDot and DistL1 only"; return ERR_ARG; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { err = "no HIP device visible (a gfx950 GPU is required; there is no CPU fallback)"; return ERR_DEVICE; }
     if (device < 0 || device >= ndev) { err = "bad device ordinal"; return ERR_ARG; }
@@ -488,7 +505,18 @@ int DeviceIndex::upload(const FlatIndex& x, int device, std::string& err) {
     for (unsigned l = 0; l <= NB_LAYER_MAX; ++l) v.layer_offset[l] = (uint32_t)x.layer_offset[l];
 
     // vectors, padded rows
-    {
+    if (half_rows) {  // binary16, converted here: row_stride ELEMENTS per row (64-byte lines), zero padded
+        std::vector<uint16_t> pad((size_t)n * v.row_stride, (uint16_t)0);
+        for (uint64_t f = 0; f < n; ++f)
+            for (uint64_t c = 0; c < d; ++c)
+                if (!f16_exact_bits(x.vectors[f * d + c], &pad[f * v.row_stride + c])) {
+                    err = "half-precision storage: a vector element is not representable as binary16";
+                    return ERR_ARG;
+                }
+        HIP_TRY(hipMalloc(&d_vec_, pad.size() * sizeof(uint16_t)));
+        HIP_TRY(hipMemcpy(d_vec_, pad.data(), pad.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        bytes_ += pad.size() * sizeof(uint16_t);
+    } else {
         std::vector<float> pad((size_t)n * v.row_stride, 0.f);
         for (uint64_t f = 0; f < n; ++f) std::memcpy(pad.data() + f * v.row_stride, x.vectors.data() + f * d, d * sizeof(float));
         HIP_TRY(hipMalloc(&d_vec_, pad.size() * sizeof(float)));
@@ -542,7 +570,15 @@ int DeviceIndex::upload(const FlatIndex& x, int device, std::string& err) {
     HIP_TRY(hipMalloc(&d_origin_, n * sizeof(uint64_t)));
     HIP_TRY(hipMemcpy(d_origin_, x.origin_id.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
     bytes_ += n * sizeof(uint64_t);
-    if (x.dist == DIST_COSINE) {  // DistCosine's per-point sum of squares, once: inside the row when its padding has room
+    if (x.dist == DIST_COSINE && half_rows) {
+        // half rows never carry their norm: always the side array, summed here as row_sq_norms_kernel sums it (f32 squares widened
+        // to f64, left to right; this unit is compiled without contraction too) -- equal inputs, equal bits
+        std::vector<double> nrm((size_t)n);
+        for (uint64_t f = 0; f < n; ++f) nrm[f] = row_sq_norm_host(x.vectors.data() + f * d, d);
+        HIP_TRY(hipMalloc(&d_nrm2_, n * sizeof(double)));
+        HIP_TRY(hipMemcpy(d_nrm2_, nrm.data(), n * sizeof(double), hipMemcpyHostToDevice));
+        bytes_ += n * sizeof(double);
+    } else if (x.dist == DIST_COSINE) {  // DistCosine's per-point sum of squares, once: inside the row when its padding has room
         if (!norm_fits_row(x.dist, v.d, v.row_stride)) {
             HIP_TRY(hipMalloc(&d_nrm2_, n * sizeof(double)));
             bytes_ += n * sizeof(double);
@@ -1685,10 +1721,27 @@ std::unique_ptr<BuildSearchBackend> make_device_build_backend(int device) {
     return std::unique_ptr<BuildSearchBackend>(new DeviceBuildBackend(device));
 }
 
+namespace {
+int eval_distance_matrix_impl(int dist, const float* queries, uint64_t nq, const float* rows, uint64_t n, uint64_t d,
+                              uint32_t nf, bool pairs, float* out, std::string& err, int arithmetic, int storage);
+}
 int eval_distance_matrix_device(int dist, const float* queries, uint64_t nq, const float* rows, uint64_t n, uint64_t d,
                                 uint32_t nf, bool pairs, float* out, std::string& err, int arithmetic) {
+    return eval_distance_matrix_impl(dist, queries, nq, rows, n, d, nf, pairs, out, err, arithmetic, STORAGE_F32);
+}
+int eval_distance_matrix_storage_device(int dist, int storage, const float* queries, uint64_t nq, const float* rows, uint64_t n, uint64_t d,
+                                        uint32_t nf, float* out, std::string& err) {
+    return eval_distance_matrix_impl(dist, queries, nq, rows, n, d, nf, false, out, err, ARITH_SCALAR, storage);
+}
+namespace {
+int eval_distance_matrix_impl(int dist, const float* queries, uint64_t nq, const float* rows, uint64_t n, uint64_t d,
+                              uint32_t nf, bool pairs, float* out, std::string& err, int arithmetic, int storage) {
     if (nq == 0 || n == 0) return OK;
-    int km = dist;
+    // half rows (eval_distance_matrix_storage_device): scalar arithmetic, one of the four metrics, every element representable --
+    // the C ABI's entry has checked all of it
+    const bool half_rows = storage == STORAGE_F16;
+    int km = half_rows ? f16_kernel_metric(dist) : dist;
+    if (km < 0) { err = "half-precision storage serves DistL2, DistCosine, DistDot and DistL1 only"; return ERR_ARG; }  // (never an f32 kernel on half rows)
     if (arithmetic == ARITH_SIMD8) {
         km = simd8_kernel_metric(dist);
         if (km < 0) { err = "this distance has no SIMD-order variant"; return ERR_ARG; }
@@ -1699,25 +1752,40 @@ int eval_distance_matrix_device(int dist, const float* queries, uint64_t nq, con
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { err = "no HIP device visible"; return ERR_DEVICE; }
     const uint32_t rs = (uint32_t)((d + 31) / 32 * 32);
-    std::vector<float> pq((size_t)nq * rs, 0.f), pr((size_t)n * rs, 0.f);
+    const size_t elem = half_rows ? sizeof(uint16_t) : sizeof(float);  // of a stored row
+    std::vector<float> pq((size_t)nq * rs, 0.f);
+    std::vector<unsigned char> pr((size_t)n * rs * elem, (unsigned char)0);
     for (uint64_t i = 0; i < nq; ++i) std::memcpy(pq.data() + i * rs, queries + i * d, d * sizeof(float));
-    for (uint64_t i = 0; i < n; ++i) std::memcpy(pr.data() + i * rs, rows + i * d, d * sizeof(float));
+    for (uint64_t i = 0; i < n; ++i) {
+        if (half_rows) {
+            uint16_t* dst = reinterpret_cast<uint16_t*>(pr.data()) + i * rs;
+            for (uint64_t c = 0; c < d; ++c) (void)f16_exact_bits(rows[i * d + c], dst + c);
+        } else {
+            std::memcpy(pr.data() + i * rs * elem, rows + i * d, d * sizeof(float));
+        }
+    }
     DevBuf dq, dr, dn, dout;
     struct Free { DevBuf *a, *b, *c, *e; ~Free() { a->free(); b->free(); c->free(); e->free(); } } guard{&dq, &dr, &dn, &dout};
     const uint64_t n_out = pairs ? n : nq * n;
     HIP_TRY(dq.ensure(pq.size() * sizeof(float)));
-    HIP_TRY(dr.ensure(pr.size() * sizeof(float)));
+    HIP_TRY(dr.ensure(pr.size()));
     HIP_TRY(dout.ensure(n_out * sizeof(float)));
     HIP_TRY(hipMemcpy(dq.p, pq.data(), pq.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dr.p, pr.data(), pr.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (dist == DIST_COSINE) {  // the layout the search uses for this dimension: norm in the row, or beside it
+    HIP_TRY(hipMemcpy(dr.p, pr.data(), pr.size(), hipMemcpyHostToDevice));
+    if (dist == DIST_COSINE && half_rows) {  // as DeviceIndex::upload: the norms beside the rows, summed on the host
+        std::vector<double> nrm((size_t)n);
+        for (uint64_t i = 0; i < n; ++i) nrm[i] = row_sq_norm_host(rows + i * d, d);
+        HIP_TRY(dn.ensure(n * sizeof(double)));
+        HIP_TRY(hipMemcpy(dn.p, nrm.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    } else if (dist == DIST_COSINE) {  // the layout the search uses for this dimension: norm in the row, or beside it
         if (!norm_fits_row(dist, (uint32_t)d, rs)) HIP_TRY(dn.ensure(n * sizeof(double)));
         HIP_TRY(launch_row_sq_norms(nullptr, dr.as<float>(), dn.as<double>(), (uint32_t)n, (uint32_t)d, rs));
     }
     if (pairs) {
         for (uint64_t q0 = 0; q0 < n; q0 += 32768) {  // gridDim.y is limited to 65535
             const uint32_t cnt = (uint32_t)std::min<uint64_t>(32768, n - q0);
-            HIP_TRY(kernel_set(km).launch_eval_matrix(nullptr, dq.as<float>() + q0 * rs, cnt, dr.as<float>() + q0 * rs, cnt,
+            const float* rows_q0 = reinterpret_cast<const float*>(dr.as<unsigned char>() + q0 * rs * elem);
+            HIP_TRY(kernel_set(km).launch_eval_matrix(nullptr, dq.as<float>() + q0 * rs, cnt, rows_q0, cnt,
                                                       dn.p ? dn.as<double>() + q0 : nullptr, dout.as<float>() + q0, rs, (uint32_t)d, 1, true));
         }
     } else {
@@ -1727,5 +1795,6 @@ int eval_distance_matrix_device(int dist, const float* queries, uint64_t nq, con
     HIP_TRY(hipMemcpy(out, dout.p, n_out * sizeof(float), hipMemcpyDeviceToHost));
     return OK;
 }
+}  // namespace
 
 }  // namespace hnswgpu

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 #include "builder.hpp"
+#include "f16_storage.hpp"
 #include "flat_index.hpp"
 
 namespace hnswgpu {
@@ -55,7 +56,8 @@ void reload_knobs();
 
 // Plain-pointer view handed to the kernels by value.
 struct DeviceIndexView {
-    const float* vec;          // [n][row_stride] f32, rows zero-padded to 128-byte lines
+    const float* vec;          // [n][row_stride] f32, rows zero-padded to 128-byte lines -- or, on a STORAGE_F16 replica, as many
+                               // binary16 elements behind the same pointer (64-byte lines; only the *_F16 kernels read them)
     const uint32_t* nbr0;      // [n][deg_stride] flat ids of the SEARCH layer's lists, padded with NO_POINT
     const uint32_t* up_ptr;    // [n_up_layers][n+1] CSR offsets of the lists at layers >= 1
     const uint32_t* up_ids;    // concatenated lists of layers 1..n_up_layers (list order = file order)
@@ -125,6 +127,12 @@ public:
     DeviceIndex(const DeviceIndex&) = delete;
     DeviceIndex& operator=(const DeviceIndex&) = delete;
 
+    // How the next upload() stores the rows: STORAGE_F32 (default), or STORAGE_F16 -- binary16 rows converted on the host (no f32
+    // copy of the matrix ever reaches the device), DistL2 / DistCosine / DistDot / DistL1 only, every element representable (else
+    // upload() returns ERR_ARG; the C ABI has verified it before).  The search then runs the KM_*_F16 kernels: the same arithmetic
+    // on the same f32 values, so the same answers bit for bit.  Whatever reads view().vec outside the search path must ask storage().
+    void set_storage(int s) { storage_ = s == STORAGE_F16 ? STORAGE_F16 : STORAGE_F32; }
+    int storage() const { return storage_; }
     int upload(const FlatIndex& x, int device, std::string& err);
     bool ready() const { return ready_; }
     int device() const { return device_; }
@@ -237,6 +245,7 @@ private:
     bool ready_ = false;
     int device_ = -1;
     int dist_ = DIST_L2;
+    int storage_ = STORAGE_F32;   // of the rows at d_vec_ (fixed by upload())
     int num_cu_ = 0;
     uint64_t bytes_ = 0;
     // the replica (read-only after upload)
@@ -257,7 +266,7 @@ private:
     CallInfo last_{};
     std::atomic<bool> strict_ties_{true};
     std::atomic<int> arith_{0};
-    int kernel_metric() const;            // dist_, or its SIMD-order kernel variant
+    int kernel_metric() const;            // dist_, or its SIMD-order / half-storage kernel variant
     std::atomic<int> descend_per_cu_[2] = {{0}, {0}};  // resident workgroups per CU of the descent kernel (asked once; [1]: two queries per wavefront)
     uint32_t up_deg_max_ = 0;  // longest list above the search layer
     mutable std::mutex ext_mu_;
@@ -278,8 +287,13 @@ std::unique_ptr<BuildSearchBackend> make_device_build_backend(int device);
 // Distance<f32>::eval on the device through the search kernel's own distance routine: out[q][r] = dist(queries[q],
 // rows[r]), rows evaluated in batches of `nf` (1..64) -- the lane-group branches the search takes for nf neighbours.
 // pairs: nq == n and out[i] = dist(queries[i], rows[i]) (nf ignored).
+// eval_distance_matrix_storage_device (matrix mode, scalar arithmetic; capi.cpp refers to it weakly, like the filter-set pair above),
+// storage == STORAGE_F16: `rows` (every element representable, else ERR_ARG) are narrowed to binary16 on the host and read by the
+// half-storage kernels, as a STORAGE_F16 replica's are (scalar arithmetic, DistL2 / DistCosine / DistDot / DistL1).
 int eval_distance_matrix_device(int dist, const float* queries, uint64_t nq, const float* rows, uint64_t n, uint64_t d,
                                 uint32_t nf, bool pairs, float* out, std::string& err, int arithmetic = 0);
+int eval_distance_matrix_storage_device(int dist, int storage, const float* queries, uint64_t nq, const float* rows, uint64_t n, uint64_t d,
+                                        uint32_t nf, float* out, std::string& err);
 
 // The lane lab (search_kernels.hpp, lane_lab.inc): runs a script of wave-level operations of the search kernels on `device`
 // (host buffers in, host buffer out; out[0] = words produced).  Test entry.

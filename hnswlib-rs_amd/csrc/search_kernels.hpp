@@ -19,9 +19,20 @@ constexpr int TABLE_GLOBAL_BITMAP = 2;
 // (hnswgpu_set_arithmetic; search_kernels.inc, group_dist_simd8).  Only the search-path kernels exist for them.
 constexpr int KM_SIMD8_FIRST = 7;
 constexpr int KM_L2_SIMD8 = 7, KM_COSINE_SIMD8 = 8, KM_DOT_SIMD8 = 9, KM_L1_SIMD8 = 10;
-constexpr int KM_COUNT = 11;
+// ... and the half-storage family: the base metric's scalar arithmetic, unchanged, on a replica whose rows are stored as binary16
+// and widened (exactly) by the kernel's row loads (hnswgpu_set_storage; search_kernels.inc, round_load).  Search-path kernels only.
+constexpr int KM_F16_FIRST = 11;
+constexpr int KM_L2_F16 = 11, KM_COSINE_F16 = 12, KM_DOT_F16 = 13, KM_L1_F16 = 14;
+constexpr int KM_COUNT = 15;
 inline int simd8_kernel_metric(int dist) {  // -1: the metric has no SIMD-order variant (the probability distances)
     return dist == DIST_L2 ? KM_L2_SIMD8 : dist == DIST_COSINE ? KM_COSINE_SIMD8 : dist == DIST_DOT ? KM_DOT_SIMD8 : dist == DIST_L1 ? KM_L1_SIMD8 : -1;
+}
+
+inline int f16_kernel_metric(int dist) {  // -1: the metric is not served from half rows (the probability distances)
+    return dist == DIST_L2 ? KM_L2_F16 : dist == DIST_COSINE ? KM_COSINE_F16 : dist == DIST_DOT ? KM_DOT_F16 : dist == DIST_L1 ? KM_L1_F16 : -1;
+}
+constexpr int f16_base_metric(int km) {  // the Dist id whose arithmetic a half-storage id runs
+    return km == KM_L2_F16 ? DIST_L2 : km == KM_COSINE_F16 ? DIST_COSINE : km == KM_DOT_F16 ? DIST_DOT : DIST_L1;
 }
 
 constexpr uint32_t IDS_BYTES = 64 * 4;  // LDS: the compacted ids of one batch of neighbours
@@ -213,7 +224,7 @@ struct KernelSet {
 #endif
 // LDS in front of the id buffer: the query row; DistCosine keeps the query's squared norm (f64) behind it
 inline uint32_t tile_bytes_for(int metric, uint32_t row_stride) {
-    return ((row_stride * 4u + 15u) & ~15u) + (metric == DIST_COSINE || metric == KM_COSINE_SIMD8 ? 16u : 0u);
+    return ((row_stride * 4u + 15u) & ~15u) + (metric == DIST_COSINE || metric == KM_COSINE_SIMD8 || metric == KM_COSINE_F16 ? 16u : 0u);
 }
 // LDS of a hnsw_search_pair_kernel workgroup: two query rows, two id buffers, two visited tables of 2^tb 16-bit cells, two mirrors of
 // the result array (ef entries), the candidates and the cr list of a round
@@ -233,6 +244,10 @@ template <> const KernelSet& kernels_for<KM_L2_SIMD8>();
 template <> const KernelSet& kernels_for<KM_COSINE_SIMD8>();
 template <> const KernelSet& kernels_for<KM_DOT_SIMD8>();
 template <> const KernelSet& kernels_for<KM_L1_SIMD8>();
+template <> const KernelSet& kernels_for<KM_L2_F16>();
+template <> const KernelSet& kernels_for<KM_COSINE_F16>();
+template <> const KernelSet& kernels_for<KM_DOT_F16>();
+template <> const KernelSet& kernels_for<KM_L1_F16>();
 // metric-independent helpers (instantiated once, in part 2 of the L2 units)
 hipError_t launch_allow_bitmap(hipStream_t stream, const uint64_t* origin_id, uint32_t n, const uint64_t* ids, uint64_t m, uint32_t* allow);
 // filter set (CSR: ids, offsets): the bitmaps of filters f0 .. f0 + n_slots - 1 into slots of ceil(n / 32) words each

@@ -128,7 +128,7 @@ __device__ __forceinline__ void finish_staged_query(float4* tile, uint32_t row_s
         if (lane == 0) *reinterpret_cast<float*>(tile + (row_stride >> 2)) = s1;
         __syncthreads();
     }
-    if constexpr (METRIC == DIST_COSINE) {
+    if constexpr (METRIC == DIST_COSINE || METRIC == KM_COSINE_F16) {  // (half rows: the query side is f32 all the same)
         double s1 = 0.;
         for (uint32_t c = 0; c < (row_stride >> 2); ++c) {
             const float4 v = tile[c];
@@ -216,10 +216,25 @@ __device__ __forceinline__ void chain_add2(float& acc, const float4 ta, const fl
 // the two words to the group's first lane and replaces them by the zero padding the sum expects.
 // between(): work that does not depend on the rows, run after this round's loads are issued and before they are used
 struct NoOverlap { __device__ __forceinline__ void operator()() const {} };
+// ROW: the element type of the stored rows -- float, or _Float16 on a half-storage replica (KM_*_F16).  A chunk is four elements
+// either way (16 or 8 bytes); the lane <-> chunk map, the rounds and everything behind round_load are the same.
+typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
+template <typename ROW> struct row_chunk { typedef float4 type; };
+template <> struct row_chunk<_Float16> { typedef half4_t type; };
 template <int G, int NU>
 __device__ __forceinline__ void round_load(float4 (&x)[NU], const float4* __restrict__ row) {
 #pragma unroll
     for (int u = 0; u < NU; ++u) x[u] = row[u * G];
+}
+// half rows: 8 bytes per chunk and lane, widened into the same float4 (binary16 -> binary32 is exact, subnormals included:
+// v_cvt_f32_f16 under the default mode, which keeps f16 denormals) -- the chain then sees the values an f32 replica holds
+template <int G, int NU>
+__device__ __forceinline__ void round_load(float4 (&x)[NU], const half4_t* __restrict__ row) {
+    half4_t h[NU];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) h[u] = row[u * G];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) x[u] = make_float4((float)h[u].x, (float)h[u].y, (float)h[u].z, (float)h[u].w);
 }
 template <int METRIC, int G, int NU, typename ACC>
 __device__ __forceinline__ void round_chain(ACC& acc, float4 (&x)[NU], const float4* qp, bool norm_tail, bool last_lane, double& s2) {
@@ -258,9 +273,9 @@ __device__ __forceinline__ void round_chain(ACC& acc, float4 (&x)[NU], const flo
         }
     }
 }
-template <int METRIC, int G, int NU, typename ACC, typename BETWEEN>
-__device__ __forceinline__ void group_round(ACC& acc, const float4* __restrict__ row, const float4* qp, bool norm_tail, bool last_lane,
-                                            double& s2, BETWEEN&& between, bool run_between) {
+template <int METRIC, int G, int NU, typename ACC, typename ROW = float, typename BETWEEN>
+__device__ __forceinline__ void group_round(ACC& acc, const typename row_chunk<ROW>::type* __restrict__ row, const float4* qp, bool norm_tail,
+                                            bool last_lane, double& s2, BETWEEN&& between, bool run_between) {
     float4 x[NU];
     round_load<G, NU>(x, row);
     if (run_between) between();
@@ -277,19 +292,21 @@ __device__ __forceinline__ void group_round(ACC& acc, const float4* __restrict__
 // three waves per SIMD; the 16-slot kernel is at its 256 registers already).
 // row_dist: the distance from the query at `qlds` (per lane: a wavefront may hold two queries, hnsw_search_pair_kernel) to row `id`,
 // computed by the G lanes of the row's group; the value is valid in the group's first lane (g == 0)
-template <int METRIC, int G, bool DEEP = false, bool PIPE = false, typename BETWEEN>
+template <int METRIC, int G, bool DEEP = false, bool PIPE = false, typename ROW = float, typename BETWEEN>
 __device__ __forceinline__ float row_dist(const float* __restrict__ vec, uint32_t row_stride, nrm_ptr_t nrm2, const float4* qlds,
                                           uint32_t id, uint32_t g, BETWEEN&& between, bool run_between) {
     typedef typename std::conditional<METRIC == DIST_COSINE, double, float>::type ACC;
-    const uint32_t nchunk = row_stride >> 2;  // float4 chunks per row: a multiple of 8
-    const float4* row = reinterpret_cast<const float4*>(vec + (size_t)id * row_stride) + g;
+    typedef typename row_chunk<ROW>::type chunk_t;
+    const uint32_t nchunk = row_stride >> 2;  // four-element chunks per row: a multiple of 8
+    // (half rows: `vec` names binary16 elements, row_stride of them per row -- the row's address halves, nothing else moves)
+    const chunk_t* row = reinterpret_cast<const chunk_t*>(reinterpret_cast<const ROW*>(vec) + (size_t)id * row_stride) + g;
     const float4* qp = qlds + g;
     // DistCosine: the point's squared norm comes from nrm2[] -- or, when that is null, from the last 8 bytes of the row
     // itself (rows whose zero padding has room for it: no second fetch, the bytes arrive with the row's last sector)
     double s2 = 0.;
     bool in_row = false;
     if constexpr (METRIC == DIST_COSINE) {
-        in_row = nrm2 == nullptr;
+        in_row = std::is_same<ROW, float>::value && nrm2 == nullptr;  // (half rows never carry their norm)
         if (!in_row) s2 = nrm2[id];
     }
     const bool last_lane = g == (uint32_t)(G - 1);
@@ -300,7 +317,7 @@ __device__ __forceinline__ float row_dist(const float* __restrict__ vec, uint32_
     uint32_t base = 0;
     if constexpr (DEEP && G == 2) {
         for (; base + 16u * (uint32_t)G <= nchunk; base += 16u * (uint32_t)G)
-            group_round<METRIC, G, 16, ACC>(acc, row + base, qp + base, in_row && base + 16u * (uint32_t)G == nchunk, last_lane, s2, between,
+            group_round<METRIC, G, 16, ACC, ROW>(acc, row + base, qp + base, in_row && base + 16u * (uint32_t)G == nchunk, last_lane, s2, between,
                                             run_between && base == 0u);
     }
     if constexpr (PIPE) {
@@ -324,17 +341,17 @@ __device__ __forceinline__ float row_dist(const float* __restrict__ vec, uint32_
         }
     } else {
         for (; base + 8u * (uint32_t)G <= nchunk; base += 8u * (uint32_t)G)
-            group_round<METRIC, G, 8, ACC>(acc, row + base, qp + base, in_row && base + 8u * (uint32_t)G == nchunk, last_lane, s2, between,
+            group_round<METRIC, G, 8, ACC, ROW>(acc, row + base, qp + base, in_row && base + 8u * (uint32_t)G == nchunk, last_lane, s2, between,
                                            run_between && base == 0u);
     }
     if (base + 4u * (uint32_t)G <= nchunk) {
-        group_round<METRIC, G, 4, ACC>(acc, row + base, qp + base, in_row && base + 4u * (uint32_t)G == nchunk, last_lane, s2, between,
+        group_round<METRIC, G, 4, ACC, ROW>(acc, row + base, qp + base, in_row && base + 4u * (uint32_t)G == nchunk, last_lane, s2, between,
                                        run_between && base == 0u);
         base += 4u * (uint32_t)G;
     }
     if constexpr (G == 4) {
         if (base + 2u * (uint32_t)G <= nchunk) {
-            group_round<METRIC, G, 2, ACC>(acc, row + base, qp + base, in_row && base + 2u * (uint32_t)G == nchunk, last_lane, s2, between,
+            group_round<METRIC, G, 2, ACC, ROW>(acc, row + base, qp + base, in_row && base + 2u * (uint32_t)G == nchunk, last_lane, s2, between,
                                            run_between && base == 0u);
             base += 2u * (uint32_t)G;
         }
@@ -352,7 +369,7 @@ __device__ __forceinline__ float row_dist(const float* __restrict__ vec, uint32_
     }
     return v;
 }
-template <int METRIC, int G, bool DEEP = false, bool PIPE = false, typename BETWEEN>
+template <int METRIC, int G, bool DEEP = false, bool PIPE = false, typename ROW = float, typename BETWEEN>
 __device__ __forceinline__ float group_dist(const float* __restrict__ vec, uint32_t row_stride, nrm_ptr_t nrm2, const float4* qlds,
                                             const uint32_t* ids_lds, uint32_t s0, uint32_t nf, int lane, float result, BETWEEN&& between,
                                             bool run_between) {
@@ -361,7 +378,7 @@ __device__ __forceinline__ float group_dist(const float* __restrict__ vec, uint3
     const uint32_t r = s0 + (uint32_t)lane / (uint32_t)G;
     // lanes past the last row re-read row s0 (same cache lines as the lanes that own it: free)
     const uint32_t id = ids_lds[r < nf ? r : s0];
-    float v = row_dist<METRIC, G, DEEP, PIPE>(vec, row_stride, nrm2, qlds, id, g, between, run_between);
+    float v = row_dist<METRIC, G, DEEP, PIPE, ROW>(vec, row_stride, nrm2, qlds, id, g, between, run_between);
     v = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((int)((((uint32_t)lane - s0) * (uint32_t)G) & 63u) << 2, __builtin_bit_cast(int, v)));
     if ((uint32_t)lane >= s0 && (uint32_t)lane < s0 + ROWS && (uint32_t)lane < nf) result = v;
     return result;
@@ -477,7 +494,18 @@ __device__ __forceinline__ float batch_dist(const float* __restrict__ vec, uint3
                                             const float4* qlds, const uint32_t* ids_lds, uint32_t nf, int lane, BETWEEN&& between) {
     float result = INFINITY;
     uint32_t s0 = 0;
-    if constexpr (METRIC >= KM_SIMD8_FIRST) {  // the crate's simdeez_f summation order: its own routine, 16 rows per round
+    if constexpr (METRIC >= KM_F16_FIRST) {  // half rows: the base metric's routine on binary16 rows (DistCosine's norms always beside them)
+        (void)d;
+        while (s0 < nf) {
+            if (nf - s0 <= 16u) {
+                result = group_dist<f16_base_metric(METRIC), 4, false, PIPE, _Float16>(vec, row_stride, nrm2, qlds, ids_lds, s0, nf, lane, result, between, s0 == 0u);
+                s0 += 16u;
+            } else {
+                result = group_dist<f16_base_metric(METRIC), 2, DEEP, PIPE, _Float16>(vec, row_stride, nrm2, qlds, ids_lds, s0, nf, lane, result, between, s0 == 0u);
+                s0 += 32u;
+            }
+        }
+    } else if constexpr (METRIC >= KM_SIMD8_FIRST) {  // the crate's simdeez_f summation order: its own routine, 16 rows per round
         while (s0 < nf) {
             result = group_dist_simd8<METRIC>(vec, row_stride, d, nrm2 == nullptr, qlds, ids_lds, s0, nf, lane, result, between, s0 == 0u);
             s0 += 16u;
@@ -1968,8 +1996,17 @@ __device__ __forceinline__ bool final_order_ambiguous(const float (&rd)[S], uint
     return bad != 0ull || r_dist_at<S>(rd, kk - 1u) == taint_w;
 }
 
+// waves per SIMD the search kernel is built for.  One half-storage instantiation gets a wave less than its f32 twin: DistL1 on half
+// rows, S = 2, 32-bit cells, lean does not fit the 96 VGPRs that five waves leave -- there the compiler spilled the lane's
+// lanemask_lt constant and reloaded it inside the expansion loop; built for four it takes 105 registers and no scratch
 template <int METRIC, int S, int TABLE, bool STRICT>
-__global__ __launch_bounds__(64, STRICT ? (S >= 16 ? 2 : S == 4 && HNSW_PIPE_ROWS != 0 ? 3 : HNSW_LB_WAVES_STRICT) : (S >= 16 ? 4 : HNSW_LB_WAVES)) void hnsw_search_kernel(DeviceIndexView ix, SearchArgs a) {
+constexpr int search_lb_waves() {
+    if (STRICT) return S >= 16 ? 2 : S == 4 && HNSW_PIPE_ROWS != 0 ? 3 : HNSW_LB_WAVES_STRICT;
+    if (METRIC == KM_L1_F16 && S == 2 && TABLE == TABLE_LDS_CELL32) return HNSW_LB_WAVES < 4 ? HNSW_LB_WAVES : 4;
+    return S >= 16 ? 4 : HNSW_LB_WAVES;
+}
+template <int METRIC, int S, int TABLE, bool STRICT>
+__global__ __launch_bounds__(64, (search_lb_waves<METRIC, S, TABLE, STRICT>())) void hnsw_search_kernel(DeviceIndexView ix, SearchArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     // (the out-of-line parts of the kernel read their arguments from here)
     const void* const kargs = (const void*)__builtin_amdgcn_kernarg_segment_ptr();

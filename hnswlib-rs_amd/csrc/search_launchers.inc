@@ -123,7 +123,7 @@ hipError_t launch_eval_matrix(hipStream_t stream, const float* queries, uint32_t
                        queries, rows, nrm2, out, n_rows, row_stride, nf, tile_bytes, pairs ? 1u : 0u, d);
     return hipGetLastError();
 }
-#if HNSW_THIS_METRIC < 7  // construction runs in the scalar arithmetic only: no build kernels for the SIMD-order variants
+#if HNSW_THIS_METRIC < 7  // construction runs in the scalar arithmetic on f32 rows only: no build kernels for the SIMD-order and half-storage variants
 using BuildFn = void (*)(BuildArgs);
 BuildFn pick_build(int slots) {
     switch (slots) {

@@ -332,6 +332,42 @@ int hnswgpu_reload_env(void);
 #define HNSWGPU_ARITH_SIMD8 1
 int hnswgpu_set_arithmetic(hnswgpu_index* idx, int arithmetic);
 
+/* How the replicas of an index hold its vectors in HBM.  The index itself stays an Hnsw<f32, D> (the dump stays t_name "f32",
+ * construction runs on f32, queries are f32 with any values); only the device copy of the rows narrows, and only when that loses
+ * nothing:
+ *   HNSWGPU_STORAGE_F32 (default, also after hnswgpu_load_dump / hnswgpu_build): n x row_stride f32, rows of 128-byte lines.
+ *   HNSWGPU_STORAGE_F16:  n x row_stride IEEE binary16 (64-byte lines), converted on the host at upload -- half the bytes of the rows
+ *                         and half the row traffic of a search.  The search kernels widen each element back (binary16 -> binary32
+ *                         is exact) and run the unchanged arithmetic, so EVERY search-path answer equals the same call on the same
+ *                         index at F32: ids, f32 distance bits, p_ids, counts, the per-query work counters, hnswgpu_last_tie_count
+ *                         and the filtered search's panic status, under strict ties and lean.
+ * An f32 x is REPRESENTABLE iff it is not NaN and (f32)(f16)x has the bits of x: +-0, the f16 subnormals, everything up to
+ * +-65504 that needs no more than 11 significant bits, +-inf.  hnswgpu_f16_representable returns the number of elements of
+ * x[0..n) that are not, and the index of the first in *first_bad (may be NULL); it is the host routine the scans below use.
+ * hnswgpu_set_storage(F16) scans the index's vectors on the host (the caller rounds, the library only verifies): the first
+ * element that is not representable fails the call with HNSWGPU_ERR_ARG -- the message names the point's DataId, the dimension and
+ * the number of offending elements -- and the index keeps its previous storage.  Also HNSWGPU_ERR_ARG: a metric other than DistL2 /
+ * DistCosine / DistDot / DistL1; F16 on an index set to HNSWGPU_ARITH_SIMD8 (and hnswgpu_set_arithmetic(SIMD8) on an F16 index);
+ * an unknown storage value.  Switching back to F32 is always allowed.
+ * A change of storage marks every replica stale, like an insert: the next upload, explicit or the lazy one in front of a search,
+ * makes replicas of the new kind.
+ * Inserts on an F16 index (hnswgpu_insert, hnswgpu_insert_gpu, insert_f32, parallel_insert_f32) check the NEW vectors first: one
+ * element that is not representable refuses the whole call with HNSWGPU_ERR_ARG and nothing is inserted (the two FFI symbols
+ * have no status: the message is in hnswgpu_last_error).  The build itself runs on f32, host or GPU-assisted, unchanged.
+ * Served from an F16 replica: hnswgpu_search_batch(_device), _device_begin / _end, _sharded(_device), _filtered(_device),
+ * _filter_set(_device), hnswgpu_range_search_batch(_device), search_neighbours_f32 / parallel_search_neighbours_f32;
+ * hnswgpu_file_dump still writes f32.  The calls that read rows outside the search path -- hnswgpu_exact_search_batch*,
+ * hnswgpu_exact_range_search_batch*, hnswgpu_exact_graph_batch*, hnswgpu_graph_search_batch* (its gather kernel copies rows) --
+ * return HNSWGPU_ERR_ARG on an F16 index before touching any output; the message says to set F32.
+ * hnswgpu_get_storage: the index's storage.  hnswgpu_device_bytes: the bytes of the replica on `device` (< 0: the primary one),
+ * HNSWGPU_ERR_DEVICE when the index is not resident (or stale) there.                                                            */
+#define HNSWGPU_STORAGE_F32 0
+#define HNSWGPU_STORAGE_F16 1
+int hnswgpu_set_storage(hnswgpu_index* idx, int storage);
+int hnswgpu_get_storage(const hnswgpu_index* idx);
+uint64_t hnswgpu_f16_representable(const float* x, uint64_t n, uint64_t* first_bad);
+int hnswgpu_device_bytes(const hnswgpu_index* idx, int device, uint64_t* bytes);
+
 /* Timing of the kernels of the last search call on this index, measured with HIP events on
  * the launch stream: total milliseconds and number of launches (retries included).        */
 int hnswgpu_last_kernel_ms(const hnswgpu_index* idx, double* ms, uint32_t* launches);
@@ -350,6 +386,10 @@ int hnswgpu_eval_distance_matrix(int dist, const float* queries, uint64_t nq, co
 /* the same in the given arithmetic (HNSWGPU_ARITH_*)                                                                  */
 int hnswgpu_eval_distance_matrix_arith(int dist, int arithmetic, const float* queries, uint64_t nq, const float* rows,
                                        uint64_t n, uint64_t d, uint32_t batch, float* out);
+/* the same (scalar arithmetic) with `rows` held as the given storage (HNSWGPU_STORAGE_*): F16 narrows them on the host before the
+ * kernel reads them, as a replica's are -- every element of rows must be representable, else HNSWGPU_ERR_ARG                      */
+int hnswgpu_eval_distance_matrix_storage(int dist, int storage, const float* queries, uint64_t nq, const float* rows,
+                                         uint64_t n, uint64_t d, uint32_t batch, float* out);
 
 /* ---------------------------------------------------------------- exact k-NN ---------- */
 /* Exhaustive exact k-NN over EVERY point of the index (all layers), on the device: the ground truth a recall measurement

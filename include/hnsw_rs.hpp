@@ -94,6 +94,10 @@ public:
     void set_strict_ties(bool on) { check(hnswgpu_set_strict_ties(idx_, on)); }
     // distances of the following searches summed like the crate's simdeez_f build (true) or its default build (false)
     void set_simd_order_arithmetic(bool on) { check(hnswgpu_set_arithmetic(idx_, on ? HNSWGPU_ARITH_SIMD8 : HNSWGPU_ARITH_SCALAR)); }
+    // the replicas hold the vectors as IEEE binary16 (true: half the bytes; every stored element must be representable, the caller
+    // rounds and the library verifies) or as f32 (false, the default); the answers of every search are the same bit for bit
+    void set_storage(bool half_precision) { check(hnswgpu_set_storage(idx_, half_precision ? HNSWGPU_STORAGE_F16 : HNSWGPU_STORAGE_F32)); }
+    bool half_precision_storage() const { return hnswgpu_get_storage(idx_) == HNSWGPU_STORAGE_F16; }
 
     // search(&[T], knbn, ef) -> Vec<Neighbour>
     std::vector<Neighbour> search(const std::vector<float>& data, size_t knbn, size_t ef) const {
