@@ -128,6 +128,32 @@ class RangeResult:
         return out
 
 
+class GraphCsrResult:
+    """An undirected k-NN graph of the indexed points in CSR form (Hnsw.symmetric_knn_graph_flat).  Vertices are POSITIONS in the
+    ascending (DataId, dump order) order -- DataIds may repeat, positions do not.  Row i owns the slots offsets[i] .. offsets[i + 1]
+    of pos (the neighbours' positions), ids (their DataIds), dists (the stored f32 distances), layers and ranks (their p_ids),
+    ascending by (distance, position)."""
+
+    def __init__(self, offsets, pos, ids, dists, layers, ranks):
+        self.offsets, self.pos, self.ids, self.dists, self.layers, self.ranks = offsets, pos, ids, dists, layers, ranks
+
+    @property
+    def counts(self):
+        return np.diff(self.offsets)
+
+    def of(self, i):
+        """(pos, ids, dists, layers, ranks) of row i: views, not copies"""
+        a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+        return self.pos[a:b], self.ids[a:b], self.dists[a:b], self.layers[a:b], self.ranks[a:b]
+
+    def to_neighbours(self):
+        out = []
+        for i in range(len(self.offsets) - 1):
+            _pos, ids, dists, layers, ranks = self.of(i)
+            out.append([Neighbour(int(ids[j]), float(dists[j]), (int(layers[j]), int(ranks[j]))) for j in range(len(ids))])
+        return out
+
+
 class Hnsw:
     """Hnsw<f32, D>: owns a hnswgpu_index handle (flat host graph + its HBM replica)."""
 
@@ -542,6 +568,44 @@ class Hnsw:
             n_allowed = len(allowed_ids)
             allowed = np.ascontiguousarray(allowed_ids, dtype=np.uint64) if n_allowed else np.zeros(1, np.uint64)
         return self._graph_call(self._lib.hnswgpu_exact_graph_batch, knbn, point_ids, _p(allowed), n_allowed)
+
+    # ---- the k-NN graph of the indexed points made undirected, in CSR (an extension) ----------------------------------
+    def symmetric_knn_graph_flat(self, knbn, ef=None, mode="union"):
+        """The k-NN graph of every indexed point made undirected on the device.  The directed graph is exact_knn_graph_flat(knbn)
+        (ef=None) or knn_graph_flat(knbn, ef), every point, bit for bit; mode "union": row i holds j iff either names the other,
+        "mutual": iff both do.  An entry's distance is the stored f32 of its own row's edge when there is one, else of the other
+        row's (for DistJeffreys and DistJensenShannon the two directions differ in their bits).  Returns a GraphCsrResult.  One
+        call with a guessed capacity, one more with the exact total when the guess was too small."""
+        modes = {"union": N.HEADER.constants["HNSWGPU_SYM_UNION"], "mutual": N.HEADER.constants["HNSWGPU_SYM_MUTUAL"]}
+        if mode not in modes:
+            raise HnswError(N.ERR_ARG, f"mode must be 'union' or 'mutual', not {mode!r}")
+        if ef is not None and ef < 1:
+            raise HnswError(N.ERR_ARG, "ef must be >= 1 (ef=None: the exact graph)")
+        n = self.get_nb_point()
+        offsets = np.zeros(n + 1, np.uint64)
+
+        def empty(cap):
+            return (np.zeros(cap, np.uint32), np.zeros(cap, np.uint64), np.zeros(cap, np.float32), np.zeros(cap, np.uint8),
+                    np.zeros(cap, np.int32))
+        if self._h is None:
+            if knbn < 1:
+                raise HnswError(N.ERR_ARG, "knbn must be > 0")
+            return GraphCsrResult(offsets, *empty(0))
+        cap = max(1024, 2 * n * min(knbn, max(n - 1, 1)) if modes[mode] == 0 else n * min(knbn, max(n - 1, 1)))
+        for attempt in range(2):
+            pos, ids, dists, layers, ranks = empty(cap)
+            rc = self._lib.hnswgpu_symmetric_graph(self._h, knbn, 0 if ef is None else ef, modes[mode], cap, _p(offsets), _p(pos), _p(ids),
+                                                   _p(dists), _p(layers), _p(ranks))
+            if rc != N.ERR_CAPACITY or attempt == 1:
+                break
+            cap = int(offsets[n])
+        _check(rc)
+        total = int(offsets[n])
+        return GraphCsrResult(offsets, pos[:total], ids[:total], dists[:total], layers[:total], ranks[:total])
+
+    def symmetric_knn_graph(self, knbn, ef=None, mode="union"):
+        """symmetric_knn_graph_flat as Vec<Vec<Neighbour>>, row i being the point at position i."""
+        return self.symmetric_knn_graph_flat(knbn, ef, mode).to_neighbours()
 
     def knn_graph_recall(self, knbn, ef, point_ids=None):
         """The recall by id of knn_graph_flat against exact_knn_graph_flat over the named points: the share of the exact

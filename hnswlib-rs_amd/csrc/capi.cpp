@@ -1191,6 +1191,83 @@ int hnswgpu_range_search_batch_device(const hnswgpu_index* cidx, const float* d_
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
+// ---- the k-NN graph of the indexed points made undirected, in CSR (symmetric_graph.hip holds the device side)
+extern "C++" {
+namespace hnswgpu {
+__attribute__((weak)) int symmetric_graph(DeviceIndex*, const std::vector<uint64_t>&, const SymGraphArgs&, bool, void*, std::string&);
+}  // namespace hnswgpu
+}  // extern "C++"
+// the checks both entries share; the handle's lock is held (shared).  What the source call of D refuses is refused here.
+static int symmetric_graph_call(const hnswgpu_index* idx, const SymGraphArgs& a) {
+    const uint64_t n = idx->builder ? idx->builder->nb_point() : (idx->flat ? idx->flat->n : 0);
+    if (!a.out_offsets) return fail(HNSWGPU_ERR_ARG, "null out_offsets: the offsets are written by every call");
+    if (a.k == 0) return fail(HNSWGPU_ERR_ARG, "knbn must be > 0");
+    if (a.mode != HNSWGPU_SYM_UNION && a.mode != HNSWGPU_SYM_MUTUAL)
+        return fail(HNSWGPU_ERR_ARG, "unknown mode " + std::to_string(a.mode) + ": HNSWGPU_SYM_UNION or HNSWGPU_SYM_MUTUAL");
+    if (a.cap != 0 && (!a.out_pos || !a.out_dists))
+        return fail(HNSWGPU_ERR_ARG, "cap > 0 with null out_pos or out_dists (the count-only call is cap == 0)");
+    if (n != 0 && a.k > (1ull << 30) / n)
+        return fail(HNSWGPU_ERR_ARG, "symmetric graph: nb_point x knbn = " + std::to_string(n) + " x " + std::to_string(a.k) +
+                                         (a.k <= ~0ull / n ? " = " + std::to_string(n * a.k) : std::string()) + " slots, above 2^30 = 1073741824");
+    if (a.ef != 0) return capi_refuse_f16(idx, "the graph search (its gather kernel copies stored rows)");
+    if (a.k > 4096) return fail(HNSWGPU_ERR_ARG, "exact graph: knbn above 4096");
+    if (idx->arithmetic != HNSWGPU_ARITH_SCALAR)
+        return fail(HNSWGPU_ERR_ARG, "exact graph answers in the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
+    return capi_refuse_f16(idx, "exact graph");
+}
+
+int hnswgpu_symmetric_graph(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t cap, uint64_t* out_offsets, uint32_t* out_pos,
+                            uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    const SymGraphArgs a{k, ef, mode, cap, out_offsets, out_pos, out_ids, out_dists, out_layer, out_rank};
+    int rc = symmetric_graph_call(idx, a);
+    if (rc != HNSWGPU_OK) return rc;
+    const uint64_t n = idx->builder ? idx->builder->nb_point() : (idx->flat ? idx->flat->n : 0);
+    if (n <= 1) {  // no point, or one: no edge
+        std::memset(out_offsets, 0, (n + 1) * sizeof(uint64_t));
+        return HNSWGPU_OK;
+    }
+    if (!hnswgpu::symmetric_graph) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = primary_f32_replica(idx, sl, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    rc = hnswgpu::symmetric_graph(dev, idx->flat->origin_id, a, true, nullptr, err);
+    if (rc != OK) return fail(rc, err);
+    return HNSWGPU_OK;
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswgpu_symmetric_graph_device(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t cap, uint64_t* d_out_offsets,
+                                   uint32_t* d_out_pos, uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, void* stream) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    const SymGraphArgs a{k, ef, mode, cap, d_out_offsets, d_out_pos, d_out_ids, d_out_dists, d_out_layer, d_out_rank};
+    int rc = symmetric_graph_call(idx, a);
+    if (rc != HNSWGPU_OK) return rc;
+    if (!hnswgpu::symmetric_graph) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    std::string err;
+    static const std::vector<uint64_t> no_ids;
+    const bool empty = idx->builder ? idx->builder->nb_point() == 0 : (!idx->flat || idx->flat->n == 0);
+    if (empty) {  // no point: the one offset is zeroed on the caller's stream
+        rc = hnswgpu::symmetric_graph(nullptr, no_ids, a, false, stream, err);
+        if (rc != OK) return fail(rc, err);
+        return HNSWGPU_OK;
+    }
+    DeviceIndex* dev = idx->primary >= 0 ? idx->replica(idx->primary) : nullptr;
+    if (!dev || idx->dev_stale || idx->flat_stale || !idx->flat)
+        return fail(HNSWGPU_ERR_DEVICE, "index is not resident on a device: call hnswgpu_upload first");
+    rc = hnswgpu::symmetric_graph(dev, idx->flat->origin_id, a, false, stream, err);
+    if (rc != OK) return fail(rc, err);
+    return HNSWGPU_OK;
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
 static DeviceIndex* any_replica(hnswgpu_index* idx) {
     if (idx->primary >= 0 && idx->replica(idx->primary)) return idx->replica(idx->primary);
     return nullptr;

@@ -1,5 +1,5 @@
 // capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h, for the translation units
-// that implement entry points of the C ABI (capi.cpp; exact_knn.hip; range_search.hip).  Private: not installed, not part of the ABI.
+// that implement entry points of the C ABI (capi.cpp; exact_knn.hip; range_search.hip; symmetric_graph.hip).  Private: not installed, not part of the ABI.
 #pragma once
 #include <exception>
 #include <map>
@@ -106,6 +106,23 @@ struct RangeSearchArgs {
 };
 int range_search_host(DeviceIndex& dev, const RangeSearchArgs& a, std::string& err);
 int range_search_device(DeviceIndex* dev, const RangeSearchArgs& d_a, void* stream, std::string& err);
+// the device side of hnswgpu_symmetric_graph(_device), defined in symmetric_graph.hip and referred to weakly in the same way: the
+// directed graph of every point through exact_graph (ef == 0) or graph_search, made undirected (the arguments have been checked).
+// host: the out arrays are plain host memory; else device memory and `stream` is the caller's.  Returns HNSWGPU_ERR_CAPACITY, the
+// offsets complete and no out slot written, when the answer needs more than cap slots.  dev == nullptr (device entry on an empty
+// index): the one offset is zeroed.
+struct SymGraphArgs {
+    uint64_t k, ef;
+    uint32_t mode;          // HNSWGPU_SYM_*
+    uint64_t cap;
+    uint64_t* out_offsets;  // [n + 1]
+    uint32_t* out_pos;      // cap slots each; out_pos == nullptr: the count-only call
+    uint64_t* out_ids;      // may be nullptr
+    float* out_dists;
+    uint8_t* out_layer;     // may be nullptr
+    int32_t* out_rank;      // may be nullptr
+};
+int symmetric_graph(DeviceIndex* dev, const std::vector<uint64_t>& origin_id, const SymGraphArgs& a, bool host, void* stream, std::string& err);
 }  // namespace hnswgpu
 
 // No C++ exception may cross the C ABI: every entry point is `try { ... HNSWGPU_CAPI_GUARD_END(ret)`

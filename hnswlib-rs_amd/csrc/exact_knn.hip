@@ -45,6 +45,7 @@
 #include <vector>
 
 #include "capi_index.hpp"
+#include "graph_internal.hpp"
 #include "hnswio.hpp"
 #include "search_kernels.hpp"
 #pragma clang diagnostic push
@@ -91,14 +92,7 @@ struct ExactKnnArgs {
     const uint32_t* self_rank;  // [tiles * TQ] k-NN graph: the slot's query is the stored point of this DataId rank (prep kernel), never its own answer
 };
 
-// f32 -> u32 whose unsigned order is the order of the values, every NaN behind everything (distances are >= 0: then this is the
-// bit pattern with the top bit set; the other cases keep the order total whatever a distance returns)
-__device__ __forceinline__ uint32_t dist_order_bits(float v) {
-    uint32_t b = __float_as_uint(v);
-    if (v != v) return 0xFFFFFFFFu;
-    if (b == 0x80000000u) b = 0u;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
+// (dist_order_bits, the order of a key's upper half, is in graph_internal.hpp: symmetric_graph.hip builds the same keys)
 // A key: order bits above, the DataId rank below.  Every NaN has the same order bits and comes back as the canonical quiet NaN.
 __device__ __forceinline__ uint64_t make_key(float v, uint32_t rank) { return ((uint64_t)dist_order_bits(v) << 32) | rank; }
 __device__ __forceinline__ float dist_of_key(uint64_t key) {
@@ -1443,6 +1437,20 @@ int exact_graph(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, 
         if (rc != OK) return rc;
         HIP_TRY(stage.copy_out(io, c0, cq, stream));
     }
+    return OK;
+}
+
+// The DataId ranks of the replica's state, for symmetric_graph.hip (graph_internal.hpp): made on first use, like every call here does
+int graph_order(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, GraphOrder& out, std::string& err) {
+    OnDevice on(dev.device());
+    HIP_TRY(on.status());
+    std::string serr;
+    std::shared_ptr<void> ext = dev.extension([&]() { return make_state(dev, origin_id, serr); });
+    if (!ext) { err = serr.empty() ? "symmetric graph: no device state" : serr; return ERR_DEVICE; }
+    const ExactState* st = static_cast<const ExactState*>(ext.get());
+    out.keep = ext;
+    out.d_rank = static_cast<const uint32_t*>(st->d_rank);
+    out.d_order = static_cast<const uint32_t*>(st->d_order);
     return OK;
 }
 

@@ -567,7 +567,7 @@ int hnswgpu_range_search_batch_device(const hnswgpu_index* idx, const float* d_q
  * and an index set to HNSWGPU_ARITH_SIMD8 is refused, both HNSWGPU_ERR_ARG, as there.
  *
  * Out of scope, all of it: using dist(p, q) == dist(q, p) to halve the exact graph's work; filter sets; k above 4096; sharding
- * over several GPUs; a symmetrised or CSR graph; the SIMD-order arithmetic for the exact call.
+ * over several GPUs; the SIMD-order arithmetic for the exact call.  (The graph made undirected, in CSR: hnswgpu_symmetric_graph.)
  * Host buffers; upload the index on first use like hnswgpu_search_batch; take the handle's lock shared, like a search.      */
 int hnswgpu_graph_search_batch(const hnswgpu_index* idx, const uint64_t* point_ids, uint64_t np, uint64_t k, uint64_t ef,
                                uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts);
@@ -582,6 +582,62 @@ int hnswgpu_graph_search_batch_device(const hnswgpu_index* idx, const uint64_t* 
 int hnswgpu_exact_graph_batch_device(const hnswgpu_index* idx, const uint64_t* d_point_ids, uint64_t np, uint64_t k,
                                      const uint64_t* d_allowed_ids, uint64_t n_allowed, uint64_t* d_out_ids, float* d_out_dists,
                                      uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, void* stream);
+
+/* ---------------------------------------------------------------- the symmetrised k-NN graph, in CSR --- */
+/* The k-NN graph of the indexed points made UNDIRECTED on the device: what embedders (annembed, UMAP-style), spectral methods,
+ * connected components and mutual-neighbour outlier tests turn the directed graph into before anything else.  A k-NN graph is
+ * directed -- j in kNN(i) does not give i in kNN(j) -- and the rows of the undirected one are ragged (a hub is named by up to
+ * n - 1 others), so the answer is CSR, not n x k.  The reference has no such function; the contract is defined through the two
+ * graph calls above:
+ *   rows      row i, i in 0 .. n = hnswgpu_nb_point, is the point at position i of the ascending (DataId, dump order) order:
+ *             exactly the row numbering of the graph calls with point_ids == NULL.  POSITIONS, not DataIds, are the vertex names
+ *             (DataIds may repeat): out_pos carries each neighbour's position; out_ids, out_layer and out_rank carry its DataId
+ *             and p_id, as everywhere else.
+ *   D         the directed graph.  ef == 0: row i of D is row i of hnswgpu_exact_graph_batch(idx, NULL, n, k, NULL, 0, ...);
+ *             ef >= 1: row i of hnswgpu_graph_search_batch(idx, NULL, n, k, ef, ...) -- bit for bit: the neighbours' p_ids, their
+ *             order, their f32 distance bits, the counts.  A neighbour's position is the position of the point that has its p_id.
+ *             What those calls refuse this call refuses the same way, HNSWGPU_ERR_ARG before any output is written: k == 0; for
+ *             ef == 0, k above 4096 and an index set to HNSWGPU_ARITH_SIMD8; an index set to HNSWGPU_STORAGE_F16.
+ *   answer    write i -> j for "j is an entry of row i of D", with distance d(i->j).
+ *             HNSWGPU_SYM_UNION:  row i holds j iff i -> j or  j -> i.
+ *             HNSWGPU_SYM_MUTUAL: row i holds j iff i -> j and j -> i.
+ *             j != i always (D never holds a point in its own row); a pair appears once per row, however it arose.  Any other
+ *             mode is HNSWGPU_ERR_ARG.
+ *   distance  of entry j in row i: d(i->j) when i -> j, otherwise (UNION only) d(j->i) -- the STORED f32 bits of D, never a
+ *             recomputation.  For DistL2, DistL1, DistDot, DistCosine and DistHellinger the two directions are the same
+ *             arithmetic and entry (i, j) equals entry (j, i) in its bits.  DistJeffreys (ln(a/b) against ln(b/a)) and
+ *             DistJensenShannon (its two terms added in the other order) are NOT symmetric in their bits: for those two, rows i
+ *             and j may carry different bits for the same pair.  That is the contract.
+ *   order     within a row ascending by the exact k-NN key built from the entry's distance: the distance as an f32 value with -0
+ *             folded into +0 and NaN last, then the neighbour's position (= DataId, then dump order).  The distance itself comes
+ *             back as stored (a -0 stays -0).
+ *   output    CSR.  out_offsets[0 .. n] is u64 and is ALWAYS written completely, so out_offsets[n] is the total; row i owns the
+ *             slots out_offsets[i] .. out_offsets[i + 1] of out_pos, out_ids, out_dists, out_layer and out_rank (out_ids,
+ *             out_layer and out_rank may each be NULL).
+ *   capacity  cap = the number of slots behind the out arrays.  total <= cap: the answers are written, HNSWGPU_OK.  Otherwise NO
+ *             out slot is touched and the call returns HNSWGPU_ERR_CAPACITY; hnswgpu_last_error() names the total needed.
+ *             cap == 0 with NULL out arrays is the count-only call.  cap > 0 with a NULL out_pos or out_dists is HNSWGPU_ERR_ARG.
+ *             An empty index or n == 1: all offsets zero, HNSWGPU_OK.
+ *   memory    there is NO fixed scratch budget here: a sorted edge list of the whole graph is the product.  The work is O(n k) on
+ *             the device.  With S = n k: D is staged (17 S + 4 n bytes, besides what its own call takes) and released once it is
+ *             expanded into 2 S edge records of 12 bytes, held twice by the sort (48 S bytes, plus rocPRIM's temporary storage);
+ *             the answer's total <= 2 S entries then take 20 bytes each (sort keys twice, distance bits) -- at most 88 S bytes
+ *             and rocPRIM's temporary storage at the peak.  n k above 2^30 is HNSWGPU_ERR_ARG; the message gives the product.
+ * The answer is a function of D alone (no float atomics, no write whose place depends on timing): two calls give the same bytes.
+ * Takes the handle's lock shared, like a search, and is legal from several host threads at once.  Host buffers; uploads the index
+ * on first use.
+ * Out of scope: a filter or filter set; a subset of points; weights other than the stored distances (no kernel functions, no
+ * perplexity); sharding over GPUs; F16 storage; connected components.                                                        */
+#define HNSWGPU_SYM_UNION 0
+#define HNSWGPU_SYM_MUTUAL 1
+int hnswgpu_symmetric_graph(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t cap,
+                            uint64_t* out_offsets, uint32_t* out_pos, uint64_t* out_ids, float* out_dists, uint8_t* out_layer,
+                            int32_t* out_rank);
+/* The same with every out array in HBM (the offsets too), on HIP stream `stream`, waited for; the out arrays hold cap slots and are
+ * written in place.  The index must be uploaded (else HNSWGPU_ERR_DEVICE).  Only the total is read back.                      */
+int hnswgpu_symmetric_graph_device(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t cap,
+                                   uint64_t* d_out_offsets, uint32_t* d_out_pos, uint64_t* d_out_ids, float* d_out_dists,
+                                   uint8_t* d_out_layer, int32_t* d_out_rank, void* stream);
 
 /* Test entry: the lane lab. The wave-level algorithms the search kernels are made of -- the reference's BinaryHeap (src/hnsw.rs:940,
  * :958-973, :1035-1053, :1544; std's push / pop / into_sorted_vec) as a memory heap and as a register heap, the sorted result set

@@ -125,6 +125,37 @@ public:
         check(hnswgpu_file_dump(idx_, path.c_str(), file_basename.c_str()));
         return file_basename;
     }
+    // The k-NN graph of the indexed points made undirected (an extension: hnswgpu_symmetric_graph), in CSR.  Vertices are POSITIONS
+    // in the ascending (DataId, dump order) order; row i owns the slots offsets[i] .. offsets[i + 1] of pos (the neighbours'
+    // positions) and neighbours (their DataIds, the stored f32 distances, their p_ids), ascending by (distance, position).
+    struct GraphCsr {
+        std::vector<uint64_t> offsets;
+        std::vector<uint32_t> pos;
+        std::vector<Neighbour> neighbours;
+    };
+    // ef == 0: from the exact graph, else from the approximate graph at this ef.  mutual: an edge only if both endpoints name the
+    // other (HNSWGPU_SYM_MUTUAL), else if either does (HNSWGPU_SYM_UNION).  One counting call, one filling call.
+    GraphCsr symmetric_knn_graph(size_t knbn, size_t ef = 0, bool mutual = false) const {
+        GraphCsr g;
+        const size_t n = get_nb_point();
+        g.offsets.assign(n + 1, 0);
+        if (!idx_) return g;
+        const uint32_t mode = mutual ? HNSWGPU_SYM_MUTUAL : HNSWGPU_SYM_UNION;
+        const int rc = hnswgpu_symmetric_graph(idx_, knbn, ef, mode, 0, g.offsets.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
+        if (rc != HNSWGPU_ERR_CAPACITY) check(rc);
+        const size_t total = g.offsets[n];
+        if (total == 0) return g;
+        std::vector<uint64_t> ids(total);
+        std::vector<float> dists(total);
+        std::vector<uint8_t> layers(total);
+        std::vector<int32_t> ranks(total);
+        g.pos.resize(total);
+        check(hnswgpu_symmetric_graph(idx_, knbn, ef, mode, total, g.offsets.data(), g.pos.data(), ids.data(), dists.data(), layers.data(),
+                                      ranks.data()));
+        g.neighbours.reserve(total);
+        for (size_t e = 0; e < total; ++e) g.neighbours.push_back(Neighbour{(size_t)ids[e], dists[e], PointId{layers[e], ranks[e]}});
+        return g;
+    }
     hnswgpu_index* handle() const { return idx_; }
 
 private:
