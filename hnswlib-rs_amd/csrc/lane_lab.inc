@@ -99,7 +99,7 @@ __device__ void lab_regheap(const LaneLabArgs& A, LabEmit& E, int lane) {
 // accept step for a whole list (merge_list when the set is full, one at a time otherwise or when merge_list declines)
 template <int S>
 __device__ void lab_rset(const LaneLabArgs& A, LabEmit& E, hent_t* merge_buf, int lane) {
-    struct { uint32_t ef; } a{A.p1};  // (merge_list_body.inc names the launch argument)
+    const uint32_t ef = A.p1;  // (the name merge_list_body.inc and the search kernel use)
     float rd[S];
     uint32_t ri[S];
 #pragma unroll
@@ -120,15 +120,15 @@ __device__ void lab_rset(const LaneLabArgs& A, LabEmit& E, hent_t* merge_buf, in
     for (uint32_t i = 0; i < A.n_ops; ++i) {
         const uint32_t op = A.ops[4u * i], x = A.ops[4u * i + 1u], y = A.ops[4u * i + 2u], c = A.ops[4u * i + 3u];
         if (op == LAB_INSERT) {
-            const bool tie = r_insert<S>(rd, ri, len, a.ef, __uint_as_float(x), y, lane);
+            const bool tie = r_insert<S>(rd, ri, len, ef, __uint_as_float(x), y, lane);
             E.put(tie ? 1u : 0u, lane);
         } else if (op == LAB_MERGE) {
             lab_load_lanes(A.lanes, c, lane, de, idc);
             const unsigned long long fm = ((unsigned long long)y << 32) | x;
             float worst = len > 0u ? r_worst<S>(rd, len) : INFINITY;
-            unsigned long long cand = fm & __ballot(len < a.ef || de < worst);
+            unsigned long long cand = fm & __ballot(len < ef || de < worst);
             uint32_t taken = 2u;  // 2: merge_list not tried
-            if (len == a.ef && cand != 0ull) {
+            if (len == ef && cand != 0ull) {
                 taken = merge_list(cand) ? 1u : 0u;
                 if (taken == 1u) cand = 0ull;
             }
@@ -139,8 +139,8 @@ __device__ void lab_rset(const LaneLabArgs& A, LabEmit& E, hent_t* merge_buf, in
             while (cand != 0ull) {
                 const int jl = ctz64(cand);
                 const float xd = readlane_f(de, jl);
-                if (xd < worst || len < a.ef) {
-                    (void)r_insert<S>(rd, ri, len, a.ef, xd, readlane_u(idc, jl), lane);
+                if (xd < worst || len < ef) {
+                    (void)r_insert<S>(rd, ri, len, ef, xd, readlane_u(idc, jl), lane);
                     worst = r_worst<S>(rd, len);
                 }
                 cand &= cand - 1ull;

@@ -1,7 +1,7 @@
 // merge_list_body.inc -- the body of merge_list, the accept rule for a whole neighbour list at once (DESIGN.md section 4.4;
 // src/hnsw.rs:1028-1053).  Textually included, so that the code under test is the code that runs: by hnsw_search_kernel's
 // `merge_list` lambda (search_kernels.inc) and by the lane lab's wrapper (lane_lab_kernel, tests/test_gpu_lane_lab.py).
-// Expects in scope: S, rd[S], ri[S], a.ef, de, idc (the candidates: lanes of de / idc, ascending lane = list order), cand (the
+// Expects in scope: S, rd[S], ri[S], ef, de, idc (the candidates: lanes of de / idc, ascending lane = list order), cand (the
 // candidate lanes, consumed), merge_buf (LDS, 64 S + 64 entries), lane.  Leaves `acc` (the lanes accepted) and `tie_here` (one of
 // them met an equal distance); returns true from the enclosing function when nothing is accepted, false -- nothing changed -- when
 // equal entries end up on both sides of the cut at ef; falls through with rd / ri rebuilt otherwise.
@@ -10,7 +10,7 @@
 #pragma unroll
             for (int s = 0; s < S; ++s) {
                 const uint32_t lo = (uint32_t)s * 64u;
-                slotmask[s] = a.ef >= lo + 64u ? ~0ull : (a.ef > lo ? (1ull << (a.ef - lo)) - 1ull : 0ull);
+                slotmask[s] = ef >= lo + 64u ? ~0ull : (ef > lo ? (1ull << (ef - lo)) - 1ull : 0ull);
             }
             unsigned long long acc = 0ull;
             bool tie_here = false;
@@ -30,7 +30,7 @@
                     eqm |= __ballot(rd[s] == xd) & slotmask[s];
                 }
                 const uint32_t cb = popc64(__ballot(de <= xd) & acc);
-                if (cr + cb >= a.ef) continue;  // not nearer than the farthest entry at its turn
+                if (cr + cb >= ef) continue;  // not nearer than the farthest entry at its turn
                 if ((eqm | (__ballot(de == xd) & acc)) != 0ull) tie_here = true;
 #pragma unroll
                 for (int s = 0; s < S; ++s) shift[s] += xd < rd[s] ? 1u : 0u;
@@ -49,12 +49,12 @@
             hent_t mine[S];
 #pragma unroll
             for (int s = 0; s < S; ++s) mine[s] = merge_buf[(uint32_t)s * 64u + (uint32_t)lane];
-            const hent_t out0 = merge_buf[a.ef];  // the nearest entry that leaves (ef + popc(acc) entries were written)
+            const hent_t out0 = merge_buf[ef];  // the nearest entry that leaves (ef + popc(acc) entries were written)
             wave_lds_fence();
             float w_new = 0.f;
 #pragma unroll
             for (int s = 0; s < S; ++s)
-                if (((a.ef - 1u) >> 6) == (uint32_t)s) w_new = readlane_f(hkey(mine[s]), (int)((a.ef - 1u) & 63u));
+                if (((ef - 1u) >> 6) == (uint32_t)s) w_new = readlane_f(hkey(mine[s]), (int)((ef - 1u) & 63u));
             if (hkey(out0) == w_new) return false;
 #pragma unroll
             for (int s = 0; s < S; ++s)

@@ -46,11 +46,13 @@ Knobs read_knobs() {
     k.no_sched = flag("HNSWGPU_NO_SCHED");
     k.no_pair_descent = flag("HNSWGPU_NO_PAIR_DESCENT");
     k.no_inkernel = flag("HNSWGPU_NO_INKERNEL");
+    k.no_shape = flag("HNSWGPU_NO_SHAPE");
     k.strict_wg_per_cu = num("HNSWGPU_STRICT_WG_PER_CU", -1);
     k.cand_lds = num("HNSWGPU_CAND_LDS", -1);
     k.waves_per_cu = num("HNSWGPU_WAVES_PER_CU", -1);
     k.exact_first = num("HNSWGPU_EXACT_FIRST", -1);
     k.trace_launch = flag("HNSWGPU_TRACE_LAUNCH");
+    k.trace_shape = num("HNSWGPU_TRACE_LAUNCH", 0) >= 2;
     k.trace_host = flag("HNSWGPU_TRACE_HOST");
     k.host_threads = num("HNSWGPU_HOST_THREADS", -1);
     k.host_chunks = num("HNSWGPU_HOST_CHUNKS", -1);
@@ -493,6 +495,10 @@ int DeviceIndex::upload(const FlatIndex& x, int device, std::string& err) {
     bytes_ = 0;
     descend_per_cu_[0].store(0);
     descend_per_cu_[1].store(0);
+    {
+        std::lock_guard<std::mutex> g(meta_mu_);
+        search_per_cu_.clear();
+    }
 
     const uint64_t n = x.n, d = x.dimension;
     DeviceIndexView v{};
@@ -667,7 +673,8 @@ struct DeviceIndex::SearchCall {
     uint32_t* d_ctrl() const { return static_cast<uint32_t*>(w.d_ctrl); }
     // the workgroups of a persistent launch behind every other bound: HNSWGPU_MAX_WG (test hook) caps them
     uint32_t capped(uint64_t grid) const { return (uint32_t)(kn.max_wg > 0 ? std::min<uint64_t>(grid, (uint64_t)kn.max_wg) : grid); }
-    struct LaunchShape { size_t lds; int per_cu, strict_cap; bool strict_kernel; };
+    struct LaunchShape { size_t lds; int per_cu, strict_cap; bool strict_kernel; int shape; };
+    hipError_t search_occupancy(int shape, bool strict, size_t lds, int* per_cu);
     hipError_t read_ctrl(size_t bytes, bool record_stop);
     SearchArgs search_args(const uint32_t* list, uint32_t n) const;
     void table_feedback();
@@ -1048,6 +1055,25 @@ int DeviceIndex::SearchCall::pair_pass() {
     return OK;
 }
 
+// Resident workgroups per CU of a one-query kernel: the runtime's answer depends on (kernel, LDS bytes) only, so the replica keeps
+// it -- a search launch otherwise asks three times, on the host, between the order kernel's launch and its own.
+hipError_t DeviceIndex::SearchCall::search_occupancy(int shape, bool strict, size_t lds, int* per_cu) {
+    // (slots 1 / 2 / 4 / 16, three table kinds, two shapes, strict or lean; the LDS of a workgroup is far below 2^20 bytes)
+    const uint64_t key = ((uint64_t)metric << 40) | ((uint64_t)slots << 32) | ((uint64_t)table << 28) | ((uint64_t)shape << 24) |
+                         ((uint64_t)(strict ? 1 : 0) << 20) | (uint64_t)lds;
+    if (lds < (1u << 20)) {
+        std::lock_guard<std::mutex> g(ix.meta_mu_);
+        for (const auto& e : ix.search_per_cu_)
+            if (e.first == key) { *per_cu = e.second; return hipSuccess; }
+    }
+    const hipError_t rc = ks.occupancy(slots, table, shape, strict, lds, per_cu);
+    if (rc == hipSuccess && lds < (1u << 20)) {
+        std::lock_guard<std::mutex> g(ix.meta_mu_);
+        if (ix.search_per_cu_.size() < 64) ix.search_per_cu_.emplace_back(key, *per_cu);
+    }
+    return rc;
+}
+
 // LDS, visited table and resident workgroups of one launch of the one-query kernels: sets the table's kind (`table`) and the
 // fields of `a` that size the workgroup's LDS.
 int DeviceIndex::SearchCall::shape_launch(SearchArgs& a, LaunchShape& s) {
@@ -1068,6 +1094,9 @@ int DeviceIndex::SearchCall::shape_launch(SearchArgs& a, LaunchShape& s) {
     }
     a.idbits = idbits;
     s.strict_kernel = strict_ties && table != TABLE_GLOBAL_BITMAP && !kn.no_inkernel;
+    // the kernel that knows its row stride and ef, where the replica and the call have that shape and it was built (HNSWGPU_NO_SHAPE:
+    // never -- the A/B switch and test hook; answers and work counters are the same either way)
+    s.shape = !kn.no_shape && v.row_stride == 128u && ef == 64u * (uint64_t)slots && shape_r128_ef_built(metric, slots, table) ? SHAPE_R128_EF : SHAPE_ANY;
     if (slots <= (s.strict_kernel ? HNSW_MERGE_SMAX : HNSW_MERGE_LEAN_SMAX)) {  // merge_list's scatter buffer
         a.merge_entries = (uint32_t)slots * 64u + 64u;
         s.lds += (size_t)a.merge_entries * sizeof(hent_t);
@@ -1084,13 +1113,13 @@ int DeviceIndex::SearchCall::shape_launch(SearchArgs& a, LaunchShape& s) {
             a.cand_lds = (uint32_t)std::min(4096, kn.cand_lds);  // tuning hook
         } else {
             int occ256 = 0, occ512 = 0;
-            HIP_TRY(ks.occupancy(slots, table, true, s.lds + 256 * sizeof(hent_t), &occ256));
-            HIP_TRY(ks.occupancy(slots, table, true, s.lds + 512 * sizeof(hent_t), &occ512));
+            HIP_TRY(search_occupancy(s.shape, true, s.lds + 256 * sizeof(hent_t), &occ256));
+            HIP_TRY(search_occupancy(s.shape, true, s.lds + 512 * sizeof(hent_t), &occ512));
             if (std::min(occ512, s.strict_cap) >= std::min(occ256, s.strict_cap)) a.cand_lds = 512;
         }
         s.lds += (size_t)a.cand_lds * sizeof(hent_t);
     }
-    HIP_TRY(ks.occupancy(slots, table, s.strict_kernel, s.lds, &s.per_cu));
+    HIP_TRY(search_occupancy(s.shape, s.strict_kernel, s.lds, &s.per_cu));
     if (s.per_cu < 1) s.per_cu = 1;
     // A strict launch ends with its longest search -- normally one that replayed its heap-operation log -- and a fifth wave
     // per SIMD slows every expansion of it: with the descent out of the kernel the strict kernel needs 89 VGPRs and would
@@ -1127,6 +1156,10 @@ int DeviceIndex::SearchCall::relaunch_loop() {
                          work, s.per_cu, s.strict_cap, s.lds, a.cand_lds, a.tbits, (int)s.strict_kernel,
                          qlist ? "sorted" : "input order", slots,
                          table == TABLE_LDS_CELL16 ? "cell16" : table == TABLE_LDS_CELL32 ? "cell32" : "bitmap", grid);
+        // (a line of its own kind, at the trace's second level: level 1 stays one line per launch, which is what its readers count)
+        if (kn.trace_shape)
+            std::fprintf(stderr, "[hnswgpu shape] %u queries on %s: row stride %u, ef %llu, slots %d, %u workgroups\n", work,
+                         s.shape == SHAPE_R128_EF ? "SHAPE_R128_EF" : "SHAPE_ANY", v.row_stride, (unsigned long long)ef, slots, grid);
         a.tie_list = w.tie.as<uint32_t>();
         if (s.strict_kernel) {
             // per-workgroup scratch: the heap-operation log, and the part of the literal candidate heap beyond LDS
@@ -1142,7 +1175,7 @@ int DeviceIndex::SearchCall::relaunch_loop() {
         }
         // (the first launch finds the counters zeroed by the descent kernel; the flagged list spans relaunches)
         if (launches != 0) HIP_TRY(hipMemsetAsync(w.d_ctrl, 0, CTRL_LAUNCH_BYTES, stream));
-        HIP_TRY(ks.launch_search(slots, table, s.strict_kernel, grid, s.lds, stream, v, a,
+        HIP_TRY(ks.launch_search(slots, table, s.shape, s.strict_kernel, grid, s.lds, stream, v, a,
                                  launches == 0 ? LaunchEvents{w.ev_ks, w.ev_ke} : LaunchEvents{}));
         ++launches;
         HIP_TRY(read_ctrl(SC_BYTES, true));

@@ -6,6 +6,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 #include "builder.hpp"
 #include "f16_storage.hpp"
@@ -22,11 +23,14 @@ struct Knobs {
     bool no_sched = false;       // HNSWGPU_NO_SCHED: searches in input order
     bool no_pair_descent = false;  // HNSWGPU_NO_PAIR_DESCENT: one query per wavefront in the descent kernel whatever the index
     bool no_inkernel = false;    // HNSWGPU_NO_INKERNEL: strict ties resolved by the literal kernel only
+    bool no_shape = false;       // HNSWGPU_NO_SHAPE: every search launch on the kernel that takes row stride and ef at run time (SHAPE_ANY), also where
+                                 // the fixed-shape kernel applies (A/B switch and test hook: the answers are the same)
     int strict_wg_per_cu = -1;   // HNSWGPU_STRICT_WG_PER_CU
     int cand_lds = -1;           // HNSWGPU_CAND_LDS
     int waves_per_cu = -1;       // HNSWGPU_WAVES_PER_CU
     int exact_first = -1;        // HNSWGPU_EXACT_FIRST (test hook)
-    bool trace_launch = false;   // HNSWGPU_TRACE_LAUNCH
+    bool trace_launch = false;   // HNSWGPU_TRACE_LAUNCH: one line per kernel launch of a search call
+    bool trace_shape = false;    // HNSWGPU_TRACE_LAUNCH=2 (or more): also a "[hnswgpu shape]" line behind the line of every launch of the one-query kernels
     bool trace_host = false;     // HNSWGPU_TRACE_HOST
     int host_threads = -1;       // HNSWGPU_HOST_THREADS
     int host_chunks = -1;        // HNSWGPU_HOST_CHUNKS
@@ -268,6 +272,7 @@ private:
     std::atomic<int> arith_{0};
     int kernel_metric() const;            // dist_, or its SIMD-order / half-storage kernel variant
     std::atomic<int> descend_per_cu_[2] = {{0}, {0}};  // resident workgroups per CU of the descent kernel (asked once; [1]: two queries per wavefront)
+    std::vector<std::pair<uint64_t, int>> search_per_cu_;  // ... of the one-query search kernels, per (kernel, LDS bytes): asked once each (under meta_mu_)
     uint32_t up_deg_max_ = 0;  // longest list above the search layer
     mutable std::mutex ext_mu_;
     mutable std::shared_ptr<void> ext_;  // see extension()

@@ -14,6 +14,15 @@ constexpr uint32_t EMPTY_SLOT = 0xFFFFFFFFu;
 constexpr int TABLE_LDS_CELL16 = 0;
 constexpr int TABLE_LDS_CELL32 = 1;
 constexpr int TABLE_GLOBAL_BITMAP = 2;
+// shapes of the one-query search kernel: what the launch's row stride and ef are to the compiler
+constexpr int SHAPE_ANY = 0;      // run-time values (every index, every call)
+constexpr int SHAPE_R128_EF = 1;  // rows of 128 elements and ef == 64 S (a full result array) as compile-time facts: the row loop of the
+                                  // distance routine is one fixed round, the slot masks and `len == ef` compares of the accept rule fold
+                                  // away.  d itself stays a run-time value (the scalar routines never read it): 97 <= d <= 128
+// the instantiations of SHAPE_R128_EF: DistL2 on f32 rows, 64 or 128 results, 16-bit-cell tables, strict and lean
+constexpr bool shape_r128_ef_built(int metric, int slots, int table) {
+    return metric == DIST_L2 && (slots == 1 || slots == 2) && table == TABLE_LDS_CELL16;
+}
 
 // kernel "metric" ids beyond the Dist ids of flat_index.hpp: the same distance summed in the crate's simdeez_f order
 // (hnswgpu_set_arithmetic; search_kernels.inc, group_dist_simd8).  Only the search-path kernels exist for them.
@@ -190,9 +199,10 @@ struct LaunchEvents {
 struct KernelSet {
     // search kernel: S in {1,2,4,16} result slots per lane, visited-table kind, strict (decisions that depend on the
     // reference's heap order are resolved with literal heaps inside the launch) or lean (such queries are only flagged)
-    hipError_t (*launch_search)(int slots, int table, bool strict, uint32_t grid, size_t lds, hipStream_t stream,
+    // shape: SHAPE_ANY, or SHAPE_R128_EF where shape_r128_ef_built() and the launch has that shape (the caller checks both)
+    hipError_t (*launch_search)(int slots, int table, int shape, bool strict, uint32_t grid, size_t lds, hipStream_t stream,
                                 const DeviceIndexView& ix, const SearchArgs& a, LaunchEvents ev);
-    hipError_t (*occupancy)(int slots, int table, bool strict, size_t lds, int* per_cu);
+    hipError_t (*occupancy)(int slots, int table, int shape, bool strict, size_t lds, int* per_cu);
     // two queries per wavefront (hnsw_search_pair_kernel: ef <= 128, lists of <= 64 ids, 16-bit-cell tables, scalar arithmetic)
     hipError_t (*launch_pair)(uint32_t grid, size_t lds, hipStream_t stream, const DeviceIndexView& ix, const SearchArgs& a, LaunchEvents ev);
     hipError_t (*pair_occupancy)(size_t lds, int* per_cu);

@@ -292,11 +292,13 @@ __device__ __forceinline__ void group_round(ACC& acc, const typename row_chunk<R
 // three waves per SIMD; the 16-slot kernel is at its 256 registers already).
 // row_dist: the distance from the query at `qlds` (per lane: a wavefront may hold two queries, hnsw_search_pair_kernel) to row `id`,
 // computed by the G lanes of the row's group; the value is valid in the group's first lane (g == 0)
-template <int METRIC, int G, bool DEEP = false, bool PIPE = false, typename ROW = float, typename BETWEEN>
-__device__ __forceinline__ float row_dist(const float* __restrict__ vec, uint32_t row_stride, nrm_ptr_t nrm2, const float4* qlds,
+// RS: the row stride as a compile-time fact (0: the run-time argument) -- the rounds below are then decided by the compiler
+template <int METRIC, int G, bool DEEP = false, bool PIPE = false, typename ROW = float, int RS = 0, typename BETWEEN>
+__device__ __forceinline__ float row_dist(const float* __restrict__ vec, uint32_t row_stride_arg, nrm_ptr_t nrm2, const float4* qlds,
                                           uint32_t id, uint32_t g, BETWEEN&& between, bool run_between) {
     typedef typename std::conditional<METRIC == DIST_COSINE, double, float>::type ACC;
     typedef typename row_chunk<ROW>::type chunk_t;
+    const uint32_t row_stride = RS != 0 ? (uint32_t)RS : row_stride_arg;
     const uint32_t nchunk = row_stride >> 2;  // four-element chunks per row: a multiple of 8
     // (half rows: `vec` names binary16 elements, row_stride of them per row -- the row's address halves, nothing else moves)
     const chunk_t* row = reinterpret_cast<const chunk_t*>(reinterpret_cast<const ROW*>(vec) + (size_t)id * row_stride) + g;
@@ -369,7 +371,7 @@ __device__ __forceinline__ float row_dist(const float* __restrict__ vec, uint32_
     }
     return v;
 }
-template <int METRIC, int G, bool DEEP = false, bool PIPE = false, typename ROW = float, typename BETWEEN>
+template <int METRIC, int G, bool DEEP = false, bool PIPE = false, typename ROW = float, int RS = 0, typename BETWEEN>
 __device__ __forceinline__ float group_dist(const float* __restrict__ vec, uint32_t row_stride, nrm_ptr_t nrm2, const float4* qlds,
                                             const uint32_t* ids_lds, uint32_t s0, uint32_t nf, int lane, float result, BETWEEN&& between,
                                             bool run_between) {
@@ -378,7 +380,7 @@ __device__ __forceinline__ float group_dist(const float* __restrict__ vec, uint3
     const uint32_t r = s0 + (uint32_t)lane / (uint32_t)G;
     // lanes past the last row re-read row s0 (same cache lines as the lanes that own it: free)
     const uint32_t id = ids_lds[r < nf ? r : s0];
-    float v = row_dist<METRIC, G, DEEP, PIPE, ROW>(vec, row_stride, nrm2, qlds, id, g, between, run_between);
+    float v = row_dist<METRIC, G, DEEP, PIPE, ROW, RS>(vec, row_stride, nrm2, qlds, id, g, between, run_between);
     v = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((int)((((uint32_t)lane - s0) * (uint32_t)G) & 63u) << 2, __builtin_bit_cast(int, v)));
     if ((uint32_t)lane >= s0 && (uint32_t)lane < s0 + ROWS && (uint32_t)lane < nf) result = v;
     return result;
@@ -489,7 +491,7 @@ __device__ __forceinline__ float group_dist_simd8(const float* __restrict__ vec,
 
 // between(): runs ONCE, while the first row loads of the batch are in flight (the search puts the insertion of the batch's ids
 // into the visited table there: work that does not need the rows, behind an HBM round trip that has to be waited for anyway)
-template <int METRIC, bool DEEP = false, bool PIPE = false, typename BETWEEN>
+template <int METRIC, bool DEEP = false, bool PIPE = false, int RS = 0, typename BETWEEN>
 __device__ __forceinline__ float batch_dist(const float* __restrict__ vec, uint32_t row_stride, uint32_t d, nrm_ptr_t nrm2,
                                             const float4* qlds, const uint32_t* ids_lds, uint32_t nf, int lane, BETWEEN&& between) {
     float result = INFINITY;
@@ -498,10 +500,10 @@ __device__ __forceinline__ float batch_dist(const float* __restrict__ vec, uint3
         (void)d;
         while (s0 < nf) {
             if (nf - s0 <= 16u) {
-                result = group_dist<f16_base_metric(METRIC), 4, false, PIPE, _Float16>(vec, row_stride, nrm2, qlds, ids_lds, s0, nf, lane, result, between, s0 == 0u);
+                result = group_dist<f16_base_metric(METRIC), 4, false, PIPE, _Float16, RS>(vec, row_stride, nrm2, qlds, ids_lds, s0, nf, lane, result, between, s0 == 0u);
                 s0 += 16u;
             } else {
-                result = group_dist<f16_base_metric(METRIC), 2, DEEP, PIPE, _Float16>(vec, row_stride, nrm2, qlds, ids_lds, s0, nf, lane, result, between, s0 == 0u);
+                result = group_dist<f16_base_metric(METRIC), 2, DEEP, PIPE, _Float16, RS>(vec, row_stride, nrm2, qlds, ids_lds, s0, nf, lane, result, between, s0 == 0u);
                 s0 += 32u;
             }
         }
@@ -514,10 +516,10 @@ __device__ __forceinline__ float batch_dist(const float* __restrict__ vec, uint3
         (void)d;
         while (s0 < nf) {
             if (nf - s0 <= 16u) {
-                result = group_dist<METRIC, 4, false, PIPE>(vec, row_stride, nrm2, qlds, ids_lds, s0, nf, lane, result, between, s0 == 0u);
+                result = group_dist<METRIC, 4, false, PIPE, float, RS>(vec, row_stride, nrm2, qlds, ids_lds, s0, nf, lane, result, between, s0 == 0u);
                 s0 += 16u;
             } else {
-                result = group_dist<METRIC, 2, DEEP, PIPE>(vec, row_stride, nrm2, qlds, ids_lds, s0, nf, lane, result, between, s0 == 0u);
+                result = group_dist<METRIC, 2, DEEP, PIPE, float, RS>(vec, row_stride, nrm2, qlds, ids_lds, s0, nf, lane, result, between, s0 == 0u);
                 s0 += 32u;
             }
         }
@@ -2005,8 +2007,13 @@ constexpr int search_lb_waves() {
     if (METRIC == KM_L1_F16 && S == 2 && TABLE == TABLE_LDS_CELL32) return HNSW_LB_WAVES < 4 ? HNSW_LB_WAVES : 4;
     return S >= 16 ? 4 : HNSW_LB_WAVES;
 }
-template <int METRIC, int S, int TABLE, bool STRICT>
+// SHAPE (search_kernels.hpp): SHAPE_ANY takes the row stride and ef from the launch's arguments; SHAPE_R128_EF knows them -- rows of 128
+// elements, ef == 64 S -- and the host launches it only where both hold (DeviceIndex::SearchCall::shape_launch).  One text of the
+// loop either way: the two values are chosen here and handed down (batch_dist's RS, merge_list_body.inc's `ef`).
+template <int METRIC, int S, int TABLE, int SHAPE, bool STRICT>
 __global__ __launch_bounds__(64, (search_lb_waves<METRIC, S, TABLE, STRICT>())) void hnsw_search_kernel(DeviceIndexView ix, SearchArgs a) {
+    constexpr int RS = SHAPE == SHAPE_R128_EF ? 128 : 0;
+    const uint32_t ef = SHAPE == SHAPE_R128_EF ? 64u * (uint32_t)S : a.ef;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     // (the out-of-line parts of the kernel read their arguments from here)
     const void* const kargs = (const void*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -2118,7 +2125,7 @@ __global__ __launch_bounds__(64, (search_lb_waves<METRIC, S, TABLE, STRICT>())) 
             idc = (uint32_t)lane < nf ? ids_lds[lane] : 0u;
             PH_T(gt1);
             int irc = 1;
-            de = batch_dist<METRIC, HNSW_DEEP_G2 != 0 && STRICT && S <= 2, HNSW_PIPE_ROWS != 0 && STRICT && S == 4>(ix.vec, ix.row_stride, ix.d, nrm2, tile, ids_lds, nf, lane, [&]() __attribute__((always_inline)) {
+            de = batch_dist<METRIC, HNSW_DEEP_G2 != 0 && STRICT && S <= 2, HNSW_PIPE_ROWS != 0 && STRICT && S == 4, RS>(ix.vec, ix.row_stride, ix.d, nrm2, tile, ids_lds, nf, lane, [&]() __attribute__((always_inline)) {
                 if constexpr (TABLE == TABLE_LDS_CELL16) {
                     if (to_insert) irc = cell16_insert(table, a.tbits, a.restbits, pr);
                 }
@@ -2335,20 +2342,20 @@ __global__ __launch_bounds__(64, (search_lb_waves<METRIC, S, TABLE, STRICT>())) 
                 // accept rule applied sequentially in list order (:1028-1053)
                 float worst = r_worst<S>(rd, len);
                 unsigned long long cand = nf >= 64u ? ~0ull : (1ull << nf) - 1ull;  // (lanes < nf)
-                if (len >= a.ef) cand &= __ballot(de < worst);
+                if (len >= ef) cand &= __ballot(de < worst);
                 if constexpr ((S == 1 || (S <= HNSW_MERGE_SMAX && (STRICT || S <= HNSW_MERGE_LEAN_SMAX))) && HNSW_MERGE_LISTS != 0) {
-                    if (len == a.ef && popc64(cand) >= (uint32_t)HNSW_MERGE_LISTS && merge_list(cand)) cand = 0ull;
+                    if (len == ef && popc64(cand) >= (uint32_t)HNSW_MERGE_LISTS && merge_list(cand)) cand = 0ull;
                 }
                 while (cand != 0ull) {
                     const int jl = ctz64(cand);
                     const float xd = readlane_f(de, jl);
-                    if (xd < worst || len < a.ef) {
+                    if (xd < worst || len < ef) {
                         const uint32_t xi = readlane_u(idc, jl);
                         pend_mask |= 1ull << jl;  // (the log: stored by log_flush)
-                        const bool was_full = len == a.ef;
+                        const bool was_full = len == ef;
                         uint32_t last_if = 0u;  // the entry this insertion pushes out of return_points
-                        if (was_full) last_if = r_id_flag_at<S>(ri, a.ef - 1u);
-                        if (r_insert<S>(rd, ri, len, a.ef, xd, xi, lane)) tie_any = true;
+                        if (was_full) last_if = r_id_flag_at<S>(ri, ef - 1u);
+                        if (r_insert<S>(rd, ri, len, ef, xd, xi, lane)) tie_any = true;
                         const float nw = r_worst<S>(rd, len);
                         if (was_full) {
                             if (nw == worst) {  // one of >= 2 equal farthest entries left: which one is the heap's choice

@@ -2,12 +2,12 @@
 // compiled once per metric and part; each part instantiates a third of the kernels).
 namespace hnswgpu {
 // the pieces the parts hand to each other: specialised per metric, defined in exactly one part
-template <int METRIC> hipError_t launch_search_strict(int slots, int table, uint32_t grid, size_t lds, hipStream_t stream,
+template <int METRIC> hipError_t launch_search_strict(int slots, int table, int shape, uint32_t grid, size_t lds, hipStream_t stream,
                                                       const DeviceIndexView& ix, const SearchArgs& a, LaunchEvents ev);
-template <int METRIC> hipError_t occupancy_strict(int slots, int table, size_t lds, int* per_cu);
-template <int METRIC> hipError_t launch_search_lean(int slots, int table, uint32_t grid, size_t lds, hipStream_t stream,
+template <int METRIC> hipError_t occupancy_strict(int slots, int table, int shape, size_t lds, int* per_cu);
+template <int METRIC> hipError_t launch_search_lean(int slots, int table, int shape, uint32_t grid, size_t lds, hipStream_t stream,
                                                     const DeviceIndexView& ix, const SearchArgs& a, LaunchEvents ev);
-template <int METRIC> hipError_t occupancy_lean(int slots, int table, size_t lds, int* per_cu);
+template <int METRIC> hipError_t occupancy_lean(int slots, int table, int shape, size_t lds, int* per_cu);
 template <int METRIC> hipError_t launch_search_pair(uint32_t grid, size_t lds, hipStream_t stream, const DeviceIndexView& ix, const SearchArgs& a, LaunchEvents ev);
 template <int METRIC> hipError_t occupancy_pair(size_t lds, int* per_cu);
 
@@ -15,10 +15,10 @@ namespace {
 constexpr int M = HNSW_THIS_METRIC;
 using KernelFn = void (*)(DeviceIndexView, SearchArgs);
 }  // namespace
-template <> hipError_t launch_search_strict<M>(int, int, uint32_t, size_t, hipStream_t, const DeviceIndexView&, const SearchArgs&, LaunchEvents);
-template <> hipError_t occupancy_strict<M>(int, int, size_t, int*);
-template <> hipError_t launch_search_lean<M>(int, int, uint32_t, size_t, hipStream_t, const DeviceIndexView&, const SearchArgs&, LaunchEvents);
-template <> hipError_t occupancy_lean<M>(int, int, size_t, int*);
+template <> hipError_t launch_search_strict<M>(int, int, int, uint32_t, size_t, hipStream_t, const DeviceIndexView&, const SearchArgs&, LaunchEvents);
+template <> hipError_t occupancy_strict<M>(int, int, int, size_t, int*);
+template <> hipError_t launch_search_lean<M>(int, int, int, uint32_t, size_t, hipStream_t, const DeviceIndexView&, const SearchArgs&, LaunchEvents);
+template <> hipError_t occupancy_lean<M>(int, int, int, size_t, int*);
 template <> hipError_t launch_search_pair<M>(uint32_t, size_t, hipStream_t, const DeviceIndexView&, const SearchArgs&, LaunchEvents);
 template <> hipError_t occupancy_pair<M>(size_t, int*);
 
@@ -28,13 +28,20 @@ constexpr bool STRICT = HNSW_PART == 0;
 template <int TABLE>
 KernelFn pick_slots(int slots) {
     switch (slots) {
-        case 1: return hnsw_search_kernel<M, 1, TABLE, STRICT>;
-        case 2: return hnsw_search_kernel<M, 2, TABLE, STRICT>;
-        case 4: return hnsw_search_kernel<M, 4, TABLE, STRICT>;
-        default: return hnsw_search_kernel<M, 16, TABLE, STRICT>;
+        case 1: return hnsw_search_kernel<M, 1, TABLE, SHAPE_ANY, STRICT>;
+        case 2: return hnsw_search_kernel<M, 2, TABLE, SHAPE_ANY, STRICT>;
+        case 4: return hnsw_search_kernel<M, 4, TABLE, SHAPE_ANY, STRICT>;
+        default: return hnsw_search_kernel<M, 16, TABLE, SHAPE_ANY, STRICT>;
     }
 }
-KernelFn pick(int slots, int table) {
+// the fixed shape exists where shape_r128_ef_built() says so; asked for anywhere else: nullptr, the launch fails (no silent SHAPE_ANY)
+template <int S>
+KernelFn pick_r128_ef() {
+    if constexpr (shape_r128_ef_built(M, S, TABLE_LDS_CELL16)) return hnsw_search_kernel<M, S, TABLE_LDS_CELL16, SHAPE_R128_EF, STRICT>;
+    else return nullptr;
+}
+KernelFn pick(int slots, int table, int shape) {
+    if (shape == SHAPE_R128_EF) return table != TABLE_LDS_CELL16 ? nullptr : slots == 1 ? pick_r128_ef<1>() : slots == 2 ? pick_r128_ef<2>() : nullptr;
 #if HNSW_PART == 1
     if (table == TABLE_GLOBAL_BITMAP) return pick_slots<TABLE_GLOBAL_BITMAP>(slots);  // lean only: the host never asks for a strict one
 #endif
@@ -42,22 +49,30 @@ KernelFn pick(int slots, int table) {
 }
 }  // namespace
 #if HNSW_PART == 0
-template <> hipError_t launch_search_strict<M>(int slots, int table, uint32_t grid, size_t lds, hipStream_t stream,
+template <> hipError_t launch_search_strict<M>(int slots, int table, int shape, uint32_t grid, size_t lds, hipStream_t stream,
                                                const DeviceIndexView& ix, const SearchArgs& a, LaunchEvents ev) {
-    hipExtLaunchKernelGGL(pick(slots, table), dim3(grid), dim3(64), (uint32_t)lds, stream, ev.start, ev.stop, 0, ix, a);
+    const KernelFn fn = pick(slots, table, shape);
+    if (fn == nullptr) return hipErrorInvalidDeviceFunction;
+    hipExtLaunchKernelGGL(fn, dim3(grid), dim3(64), (uint32_t)lds, stream, ev.start, ev.stop, 0, ix, a);
     return hipGetLastError();
 }
-template <> hipError_t occupancy_strict<M>(int slots, int table, size_t lds, int* per_cu) {
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, pick(slots, table), 64, lds);
+template <> hipError_t occupancy_strict<M>(int slots, int table, int shape, size_t lds, int* per_cu) {
+    const KernelFn fn = pick(slots, table, shape);
+    if (fn == nullptr) return hipErrorInvalidDeviceFunction;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, fn, 64, lds);
 }
 #else
-template <> hipError_t launch_search_lean<M>(int slots, int table, uint32_t grid, size_t lds, hipStream_t stream,
+template <> hipError_t launch_search_lean<M>(int slots, int table, int shape, uint32_t grid, size_t lds, hipStream_t stream,
                                              const DeviceIndexView& ix, const SearchArgs& a, LaunchEvents ev) {
-    hipExtLaunchKernelGGL(pick(slots, table), dim3(grid), dim3(64), (uint32_t)lds, stream, ev.start, ev.stop, 0, ix, a);
+    const KernelFn fn = pick(slots, table, shape);
+    if (fn == nullptr) return hipErrorInvalidDeviceFunction;
+    hipExtLaunchKernelGGL(fn, dim3(grid), dim3(64), (uint32_t)lds, stream, ev.start, ev.stop, 0, ix, a);
     return hipGetLastError();
 }
-template <> hipError_t occupancy_lean<M>(int slots, int table, size_t lds, int* per_cu) {
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, pick(slots, table), 64, lds);
+template <> hipError_t occupancy_lean<M>(int slots, int table, int shape, size_t lds, int* per_cu) {
+    const KernelFn fn = pick(slots, table, shape);
+    if (fn == nullptr) return hipErrorInvalidDeviceFunction;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, fn, 64, lds);
 }
 // (the pair kernel lives in the lean unit)
 #if HNSW_THIS_METRIC < 7
@@ -78,14 +93,14 @@ template <> hipError_t occupancy_pair<M>(size_t, int*) { return hipErrorNotSuppo
 #if HNSW_PART == 2
 namespace {
 // the HBM-bitmap kernels exist in their lean form only
-hipError_t launch_search(int slots, int table, bool strict, uint32_t grid, size_t lds, hipStream_t stream,
+hipError_t launch_search(int slots, int table, int shape, bool strict, uint32_t grid, size_t lds, hipStream_t stream,
                          const DeviceIndexView& ix, const SearchArgs& a, LaunchEvents ev) {
-    return strict && table != TABLE_GLOBAL_BITMAP ? launch_search_strict<M>(slots, table, grid, lds, stream, ix, a, ev)
-                                                  : launch_search_lean<M>(slots, table, grid, lds, stream, ix, a, ev);
+    return strict && table != TABLE_GLOBAL_BITMAP ? launch_search_strict<M>(slots, table, shape, grid, lds, stream, ix, a, ev)
+                                                  : launch_search_lean<M>(slots, table, shape, grid, lds, stream, ix, a, ev);
 }
-hipError_t occupancy(int slots, int table, bool strict, size_t lds, int* per_cu) {
-    return strict && table != TABLE_GLOBAL_BITMAP ? occupancy_strict<M>(slots, table, lds, per_cu)
-                                                  : occupancy_lean<M>(slots, table, lds, per_cu);
+hipError_t occupancy(int slots, int table, int shape, bool strict, size_t lds, int* per_cu) {
+    return strict && table != TABLE_GLOBAL_BITMAP ? occupancy_strict<M>(slots, table, shape, lds, per_cu)
+                                                  : occupancy_lean<M>(slots, table, shape, lds, per_cu);
 }
 hipError_t launch_pair(uint32_t grid, size_t lds, hipStream_t stream, const DeviceIndexView& ix, const SearchArgs& a, LaunchEvents ev) {
     return launch_search_pair<M>(grid, lds, stream, ix, a, ev);
