@@ -104,8 +104,65 @@ static int primary_f32_replica(hnswgpu_index* idx, std::shared_lock<std::shared_
     return HNSWGPU_OK;
 }
 
+// ---- what the batched entries share: a new pair of entries is written by calling these.  Where they read the index the handle's
+// lock is held.
+static uint64_t index_nb_point(const hnswgpu_index* idx) { return idx->builder ? idx->builder->nb_point() : (idx->flat ? idx->flat->n : 0); }
+static uint64_t index_dimension(const hnswgpu_index* idx) { return idx->builder ? idx->builder->dimension() : (idx->flat ? idx->flat->dimension : 0); }
+static bool index_empty(const hnswgpu_index* idx) { return index_nb_point(idx) == 0; }
+// the end of an entry: the device side's status and message handed on
+static int finish(int rc, const std::string& err) { return rc != OK ? fail(rc, err) : HNSWGPU_OK; }
+// the replica a _device entry works on: the caller's buffers live on a device already, so nothing is uploaded from here.
+// need_flat: the call reads the host view too (its DataIds)
+static int resident_replica(const hnswgpu_index* idx, bool need_flat, DeviceIndex** dev) {
+    *dev = idx->primary >= 0 ? idx->replica(idx->primary) : nullptr;
+    if (!*dev || idx->dev_stale || idx->flat_stale || (need_flat && !idx->flat))
+        return fail(HNSWGPU_ERR_DEVICE, "index is not resident on a device: call hnswgpu_upload first");
+    return HNSWGPU_OK;
+}
+// one filter for the batch, in host memory: `impl FilterT for Vec<usize>` is a binary search, so the vector must be sorted
+static int check_sorted_filter(const uint64_t* ids, uint64_t n) {
+    for (uint64_t i = 1; i < n; ++i)
+        if (ids[i - 1] > ids[i]) return fail(HNSWGPU_ERR_ARG, "the id vector of a filter must be sorted ascending");
+    return HNSWGPU_OK;
+}
+// the limits of an exact k-NN call, one filter or a set of them (which hands in no `allowed`)
+static int check_exact_call(const hnswgpu_index* idx, const void* queries, uint64_t nq, uint64_t d, uint64_t k, const void* allowed, uint64_t n_allowed,
+                            const void* out_ids, const void* out_dists, const void* out_counts) {
+    const uint64_t dim = index_dimension(idx);
+    if (nq != 0 && (!queries || !out_ids || !out_dists || !out_counts)) return fail(HNSWGPU_ERR_ARG, "null buffer");
+    if (k == 0) return fail(HNSWGPU_ERR_ARG, "knbn must be > 0");
+    // (list_insert of exact_knn.hip costs O(k / 64) steps per insertion: 4096 is the largest knbn that was run at size)
+    if (k > 4096) return fail(HNSWGPU_ERR_ARG, "exact search: knbn above 4096");
+    if (nq > 0xFFFFFFF0ull) return fail(HNSWGPU_ERR_ARG, "too many queries in one batch");
+    if (dim != 0 && d != dim) return fail(HNSWGPU_ERR_ARG, "query dimension differs from the index dimension");
+    if (n_allowed != 0 && !allowed) return fail(HNSWGPU_ERR_ARG, "null filter");
+    if (idx->arithmetic != HNSWGPU_ARITH_SCALAR)
+        return fail(HNSWGPU_ERR_ARG, "exact search answers in the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
+    return capi_refuse_f16(idx, "exact search");
+}
+// a k-NN answer on an index without a point: every count 0, every slot zeroed
+static void zero_knn_answers(uint64_t nq, uint64_t k, uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts) {
+    if (nq == 0) return;
+    std::memset(out_counts, 0, nq * sizeof(uint32_t));
+    std::memset(out_ids, 0, nq * k * sizeof(uint64_t));
+    std::memset(out_dists, 0, nq * k * sizeof(float));
+    if (out_layer) std::memset(out_layer, 0, nq * k);
+    if (out_rank) std::memset(out_rank, 0, nq * k * sizeof(int32_t));
+}
+
 namespace hnswgpu {
 int capi_fail(int code, const std::string& msg) { return fail(code, msg); }
+int capi_finish(int rc, const std::string& err) { return finish(rc, err); }
+bool capi_index_empty(const hnswgpu_index* idx) { return index_empty(idx); }
+int capi_resident_replica(const hnswgpu_index* idx, bool need_flat, DeviceIndex** dev) { return resident_replica(idx, need_flat, dev); }
+int capi_check_sorted_filter(const uint64_t* ids, uint64_t n) { return check_sorted_filter(ids, n); }
+int capi_check_exact_call(const hnswgpu_index* idx, const void* queries, uint64_t nq, uint64_t d, uint64_t k, const void* allowed, uint64_t n_allowed,
+                          const void* out_ids, const void* out_dists, const void* out_counts) {
+    return check_exact_call(idx, queries, nq, d, k, allowed, n_allowed, out_ids, out_dists, out_counts);
+}
+void capi_zero_knn_answers(uint64_t nq, uint64_t k, uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts) {
+    zero_knn_answers(nq, k, out_ids, out_dists, out_layer, out_rank, out_counts);
+}
 int capi_primary_f32_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mutex>& sl, DeviceIndex** out) { return primary_f32_replica(idx, sl, out); }
 int capi_primary_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mutex>& sl, DeviceIndex** out) { return primary_replica(idx, sl, out); }
 int capi_refuse_f16(const hnswgpu_index* idx, const char* what) {
@@ -141,9 +198,7 @@ int hnswgpu_file_dump(const hnswgpu_index* cidx, const char* dir, const char* ba
     const FlatIndex* f = idx->get_flat();
     if (!f) return fail(HNSWGPU_ERR_EMPTY, "entry point not initialized");
     std::string err;
-    int rc = write_dump(*f, dir, basename, err);
-    if (rc != OK) return fail(rc, err);
-    return HNSWGPU_OK;
+    return finish(write_dump(*f, dir, basename, err), err);
     CAPI_GUARD_END(HNSWGPU_ERR_IO)
 }
 
@@ -233,7 +288,6 @@ int hnswgpu_build(const float* data, uint64_t n, uint64_t d, const uint64_t* ids
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
-static uint64_t idx_nb_point(const hnswgpu_index* idx) { return idx->builder ? idx->builder->nb_point() : (idx->flat ? idx->flat->n : 0); }
 static std::string unrepresentable_message(uint64_t bad, uint64_t data_id, uint64_t dim) {
     return "HNSWGPU_STORAGE_F16: " + std::to_string(bad) + " vector elements are not representable as binary16 (NaN, or (f32)(f16)x != x); "
            "the first is dimension " + std::to_string(dim) + " of the point with DataId " + std::to_string(data_id);
@@ -254,7 +308,7 @@ static int insert_points(hnswgpu_index* idx, const float* data, uint64_t n, uint
         uint64_t first = 0;
         const uint64_t bad = f16_count_unrepresentable(data, n * d, &first);
         if (bad != 0)
-            return fail(HNSWGPU_ERR_ARG, unrepresentable_message(bad, ids ? ids[first / d] : idx_nb_point(idx) + first / d, first % d) +
+            return fail(HNSWGPU_ERR_ARG, unrepresentable_message(bad, ids ? ids[first / d] : index_nb_point(idx) + first / d, first % d) +
                                          "; nothing was inserted");
     }
     std::string err;
@@ -295,8 +349,7 @@ uint64_t hnswgpu_nb_point(const hnswgpu_index* cidx) {
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (!idx) return 0;
     std::shared_lock<std::shared_mutex> g(idx->mu);
-    if (idx->builder) return idx->builder->nb_point();
-    return idx->flat ? idx->flat->n : 0;
+    return index_nb_point(idx);
     CAPI_GUARD_END(0)
 }
 uint64_t hnswgpu_dimension(const hnswgpu_index* cidx) {
@@ -304,8 +357,7 @@ uint64_t hnswgpu_dimension(const hnswgpu_index* cidx) {
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (!idx) return 0;
     std::shared_lock<std::shared_mutex> g(idx->mu);
-    if (idx->builder) return idx->builder->dimension();
-    return idx->flat ? idx->flat->dimension : 0;
+    return index_dimension(idx);
     CAPI_GUARD_END(0)
 }
 int hnswgpu_dist(const hnswgpu_index* cidx) {
@@ -387,8 +439,7 @@ static int search_host_common(const hnswgpu_index* cidx, const float* queries, u
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
     std::shared_lock<std::shared_mutex> sl(idx->mu);
-    const bool empty = idx->builder ? idx->builder->nb_point() == 0 : (!idx->flat || idx->flat->n == 0);
-    if (empty) {  // empty index => every answer is empty (src/hnsw.rs:1498-1503)
+    if (index_empty(idx)) {  // empty index => every answer is empty (src/hnsw.rs:1498-1503)
         if (out_counts) std::memset(out_counts, 0, nq * sizeof(uint32_t));
         if (out_status) std::memset(out_status, 0, nq);
         if (panics) *panics = 0;
@@ -420,10 +471,10 @@ int hnswgpu_search_batch_filtered(const hnswgpu_index* cidx, const float* querie
                                   uint8_t* out_status) {
     CAPI_GUARD_BEGIN
     if (n_allowed && !allowed_ids) return fail(HNSWGPU_ERR_ARG, "null filter");
-    for (uint64_t i = 1; i < n_allowed; ++i)  // `impl FilterT for Vec<usize>` is a binary search: the vector must be sorted
-        if (allowed_ids[i - 1] > allowed_ids[i]) return fail(HNSWGPU_ERR_ARG, "the id vector of a filter must be sorted ascending");
+    int rc = check_sorted_filter(allowed_ids, n_allowed);
+    if (rc != HNSWGPU_OK) return rc;
     uint32_t panics = 0;
-    int rc = search_host_common(cidx, queries, nq, d, k, ef, allowed_ids, n_allowed, true, out_ids, out_dists, out_layer, out_rank,
+    rc = search_host_common(cidx, queries, nq, d, k, ef, allowed_ids, n_allowed, true, out_ids, out_dists, out_layer, out_rank,
                                 out_counts, out_status, &panics);
     if (rc != HNSWGPU_OK) return rc;
     if (panics != 0 && !out_status)
@@ -485,7 +536,7 @@ static int sharded_prepare(hnswgpu_index* idx, const int* devices, int n_shards,
     *empty = false;
     {   // replicas on every device named (exclusive: uploads change the handle)
         std::unique_lock<std::shared_mutex> xl(idx->mu);
-        if (idx->builder ? idx->builder->nb_point() == 0 : (!idx->flat || idx->flat->n == 0)) { *empty = true; return HNSWGPU_OK; }
+        if (index_empty(idx)) { *empty = true; return HNSWGPU_OK; }
         int rc = ensure_devices(idx, devices, n_shards);
         if (rc != HNSWGPU_OK) return rc;
     }
@@ -595,9 +646,7 @@ int hnswgpu_lane_lab(int device, uint32_t mode, uint32_t p0, uint32_t p1, uint32
     CAPI_GUARD_BEGIN
     if ((n_ops && !ops) || (n_lane_sets && !lanes) || !out) return fail(HNSWGPU_ERR_ARG, "null buffer");
     std::string err;
-    int rc = lane_lab_device(device, mode, p0, p1, p2, ops, n_ops, lanes, n_lane_sets, out, out_words, err);
-    if (rc != OK) return fail(rc, err);
-    return HNSWGPU_OK;
+    return finish(lane_lab_device(device, mode, p0, p1, p2, ops, n_ops, lanes, n_lane_sets, out, out_words, err), err);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
@@ -615,10 +664,8 @@ int hnswgpu_gather_sharded_answers(const int* devices, int n_shards, const uint6
     }
     if (total && (!root_ids || !root_dists || !root_counts)) return fail(HNSWGPU_ERR_ARG, "null buffer");
     std::string err;
-    int rc = hnswgpu::gather_sharded_answers(devices, n_shards, nq_shard, k, d_ids, d_dists, d_layer, d_rank, d_counts, root_device,
-                                             root_ids, root_dists, root_layer, root_rank, root_counts, root_stream, err);
-    if (rc != OK) return fail(rc, err);
-    return HNSWGPU_OK;
+    return finish(hnswgpu::gather_sharded_answers(devices, n_shards, nq_shard, k, d_ids, d_dists, d_layer, d_rank, d_counts, root_device,
+                                             root_ids, root_dists, root_layer, root_rank, root_counts, root_stream, err), err);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
@@ -629,12 +676,12 @@ static int search_device_common(const hnswgpu_index* cidx, const float* d_querie
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
     std::shared_lock<std::shared_mutex> sl(idx->mu);
-    DeviceIndex* dev = idx->primary >= 0 ? idx->replica(idx->primary) : nullptr;
-    if (!dev || idx->dev_stale || idx->flat_stale)
-        return fail(HNSWGPU_ERR_DEVICE, "index is not resident on a device: call hnswgpu_upload first");
+    DeviceIndex* dev = nullptr;
+    int rc = resident_replica(idx, false, &dev);
+    if (rc != HNSWGPU_OK) return rc;
     std::string err;
     CallInfo info;
-    int rc = dev->search_device(d_queries, nq, d, k, ef, d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts, d_stats,
+    rc = dev->search_device(d_queries, nq, d, k, ef, d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts, d_stats,
                                 stream, d_allowed, n_allowed, &info, err);
     if (rc != OK) return fail(rc, err);
     if (panics) *panics = info.panics;
@@ -717,18 +764,20 @@ __attribute__((weak)) int search_filter_set_host(DeviceIndex&, const float*, uin
 }  // extern "C++"
 static const char* const kNoFilterSetDevice = "no HIP device visible (a gfx950 GPU is required; there is no CPU fallback)";
 
-int hnswgpu_search_batch_filter_set(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef,
-                                    const uint64_t* filter_ids, const uint64_t* filter_offsets, uint64_t n_filters,
-                                    const uint32_t* filter_of, uint64_t* out_ids, float* out_dists, uint8_t* out_layer,
-                                    int32_t* out_rank, uint32_t* out_counts, uint8_t* out_status) {
-    CAPI_GUARD_BEGIN
-    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
-    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+// what both entries of a filter-set pair can check of the set without reading it (unfiltered: the sibling the message points to)
+static int check_filter_set_shape(const void* queries, uint64_t nq, const void* filter_offsets, uint64_t n_filters, const void* filter_of,
+                                  const void* out_ids, const void* out_dists, const void* out_counts, const char* unfiltered) {
     if (nq != 0 && (!queries || !out_ids || !out_dists || !out_counts)) return fail(HNSWGPU_ERR_ARG, "null buffer");
     if (nq != 0 && !filter_of) return fail(HNSWGPU_ERR_ARG, "null filter_of: every query names its filter");
     if (n_filters != 0 && !filter_offsets) return fail(HNSWGPU_ERR_ARG, "null filter_offsets");
-    if (n_filters == 0 && nq != 0) return fail(HNSWGPU_ERR_ARG, "a filter set without filters: n_filters is 0 (an unfiltered batch is hnswgpu_search_batch)");
+    if (n_filters == 0 && nq != 0)
+        return fail(HNSWGPU_ERR_ARG, std::string("a filter set without filters: n_filters is 0 (an unfiltered batch is ") + unfiltered + ")");
     if (n_filters > 0xFFFFFFFFull) return fail(HNSWGPU_ERR_ARG, "too many filters: filter_of is 32 bits wide");
+    return HNSWGPU_OK;
+}
+// ... and what only a host entry can, behind the shape: the set itself
+static int check_filter_set_contents(const uint64_t* filter_ids, const uint64_t* filter_offsets, uint64_t n_filters, const uint32_t* filter_of,
+                                     uint64_t nq) {
     if (n_filters != 0) {
         if (filter_offsets[0] != 0) return fail(HNSWGPU_ERR_ARG, "filter_offsets must start at 0");
         for (uint64_t f = 0; f < n_filters; ++f)
@@ -744,9 +793,22 @@ int hnswgpu_search_batch_filter_set(const hnswgpu_index* cidx, const float* quer
         if (filter_of[q] >= n_filters)
             return fail(HNSWGPU_ERR_ARG, "filter_of[" + std::to_string(q) + "] = " + std::to_string(filter_of[q]) + " names no filter (n_filters = " +
                         std::to_string(n_filters) + ")");
+    return HNSWGPU_OK;
+}
+
+int hnswgpu_search_batch_filter_set(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef,
+                                    const uint64_t* filter_ids, const uint64_t* filter_offsets, uint64_t n_filters,
+                                    const uint32_t* filter_of, uint64_t* out_ids, float* out_dists, uint8_t* out_layer,
+                                    int32_t* out_rank, uint32_t* out_counts, uint8_t* out_status) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    int rc = check_filter_set_shape(queries, nq, filter_offsets, n_filters, filter_of, out_ids, out_dists, out_counts, "hnswgpu_search_batch");
+    if (rc != HNSWGPU_OK) return rc;
+    rc = check_filter_set_contents(filter_ids, filter_offsets, n_filters, filter_of, nq);
+    if (rc != HNSWGPU_OK) return rc;
     std::shared_lock<std::shared_mutex> sl(idx->mu);
-    const bool empty = idx->builder ? idx->builder->nb_point() == 0 : (!idx->flat || idx->flat->n == 0);
-    if (empty) {  // empty index => every answer is empty (src/hnsw.rs:1498-1503)
+    if (index_empty(idx)) {  // empty index => every answer is empty (src/hnsw.rs:1498-1503)
         if (out_counts) std::memset(out_counts, 0, nq * sizeof(uint32_t));
         if (out_status) std::memset(out_status, 0, nq);
         return HNSWGPU_OK;
@@ -754,7 +816,7 @@ int hnswgpu_search_batch_filter_set(const hnswgpu_index* cidx, const float* quer
     if (nq == 0) return HNSWGPU_OK;
     if (!hnswgpu::search_filter_set_host) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     DeviceIndex* dev = nullptr;
-    int rc = primary_replica(idx, sl, &dev);
+    rc = primary_replica(idx, sl, &dev);
     if (rc != HNSWGPU_OK) return rc;
     std::string err;
     CallInfo info;
@@ -778,23 +840,21 @@ int hnswgpu_search_batch_filter_set_device(const hnswgpu_index* cidx, const floa
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (n_panics) *n_panics = 0;
     if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    if (nq != 0 && (!d_queries || !d_out_ids || !d_out_dists || !d_out_counts)) return fail(HNSWGPU_ERR_ARG, "null buffer");
-    if (nq != 0 && !d_filter_of) return fail(HNSWGPU_ERR_ARG, "null filter_of: every query names its filter");
-    if (n_filters != 0 && !d_filter_offsets) return fail(HNSWGPU_ERR_ARG, "null filter_offsets");
-    if (n_filters == 0 && nq != 0) return fail(HNSWGPU_ERR_ARG, "a filter set without filters: n_filters is 0 (an unfiltered batch is hnswgpu_search_batch_device)");
-    if (n_filters > 0xFFFFFFFFull) return fail(HNSWGPU_ERR_ARG, "too many filters: filter_of is 32 bits wide");
+    int rc = check_filter_set_shape(d_queries, nq, d_filter_offsets, n_filters, d_filter_of, d_out_ids, d_out_dists, d_out_counts,
+                                    "hnswgpu_search_batch_device");
+    if (rc != HNSWGPU_OK) return rc;
     if (nq == 0) return HNSWGPU_OK;
     if (!hnswgpu::search_filter_set_device) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     std::shared_lock<std::shared_mutex> sl(idx->mu);
-    DeviceIndex* dev = idx->primary >= 0 ? idx->replica(idx->primary) : nullptr;
-    if (!dev || idx->dev_stale || idx->flat_stale)
-        return fail(HNSWGPU_ERR_DEVICE, "index is not resident on a device: call hnswgpu_upload first");
+    DeviceIndex* dev = nullptr;
+    rc = resident_replica(idx, false, &dev);
+    if (rc != HNSWGPU_OK) return rc;
     std::string err;
     CallInfo info;
     // (filters that are all empty need no id array: hand over a non-null pointer that is never dereferenced)
     const FilterSet set{d_filter_ids ? d_filter_ids : reinterpret_cast<const uint64_t*>(d_queries), d_filter_offsets, n_filters, d_filter_of};
-    int rc = hnswgpu::search_filter_set_device(*dev, d_queries, nq, d, k, ef, set, d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts,
-                                               d_stats, stream, &info, err);
+    rc = hnswgpu::search_filter_set_device(*dev, d_queries, nq, d, k, ef, set, d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts,
+                                           d_stats, stream, &info, err);
     if (rc != OK) return fail(rc, err);
     if (n_panics) *n_panics = info.panics;
     return HNSWGPU_OK;
@@ -810,28 +870,6 @@ __attribute__((weak)) int exact_filter_set_device(const DeviceIndex&, const std:
                                                   const FilterSet&, uint64_t*, float*, uint8_t*, int32_t*, uint32_t*, void*, std::string&);
 }  // namespace hnswgpu
 }  // extern "C++"
-// what both entries can check of the set without reading it, then (behind the host entry's reading checks) the checks of
-// hnswgpu_exact_search_batch: k, d, the arithmetic.  The handle's lock is held (shared) for the second part.
-static int exact_filter_set_shape(const void* queries, uint64_t nq, const void* filter_offsets, uint64_t n_filters, const void* filter_of,
-                                  const void* out_ids, const void* out_dists, const void* out_counts, const char* unfiltered) {
-    if (nq != 0 && (!queries || !out_ids || !out_dists || !out_counts)) return fail(HNSWGPU_ERR_ARG, "null buffer");
-    if (nq != 0 && !filter_of) return fail(HNSWGPU_ERR_ARG, "null filter_of: every query names its filter");
-    if (n_filters != 0 && !filter_offsets) return fail(HNSWGPU_ERR_ARG, "null filter_offsets");
-    if (n_filters == 0 && nq != 0)
-        return fail(HNSWGPU_ERR_ARG, std::string("a filter set without filters: n_filters is 0 (an unfiltered batch is ") + unfiltered + ")");
-    if (n_filters > 0xFFFFFFFFull) return fail(HNSWGPU_ERR_ARG, "too many filters: filter_of is 32 bits wide");
-    return HNSWGPU_OK;
-}
-static int exact_filter_set_call(const hnswgpu_index* idx, uint64_t nq, uint64_t d, uint64_t k) {
-    const uint64_t dim = idx->builder ? idx->builder->dimension() : (idx->flat ? idx->flat->dimension : 0);
-    if (k == 0) return fail(HNSWGPU_ERR_ARG, "knbn must be > 0");
-    if (k > 4096) return fail(HNSWGPU_ERR_ARG, "exact search: knbn above 4096");
-    if (nq > 0xFFFFFFF0ull) return fail(HNSWGPU_ERR_ARG, "too many queries in one batch");
-    if (dim != 0 && d != dim) return fail(HNSWGPU_ERR_ARG, "query dimension differs from the index dimension");
-    if (idx->arithmetic != HNSWGPU_ARITH_SCALAR)
-        return fail(HNSWGPU_ERR_ARG, "exact search answers in the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
-    return capi_refuse_f16(idx, "exact search");
-}
 
 int hnswgpu_exact_search_batch_filter_set(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, uint64_t k,
                                           const uint64_t* filter_ids, const uint64_t* filter_offsets, uint64_t n_filters,
@@ -840,35 +878,15 @@ int hnswgpu_exact_search_batch_filter_set(const hnswgpu_index* cidx, const float
     CAPI_GUARD_BEGIN
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    int rc = exact_filter_set_shape(queries, nq, filter_offsets, n_filters, filter_of, out_ids, out_dists, out_counts, "hnswgpu_exact_search_batch");
+    int rc = check_filter_set_shape(queries, nq, filter_offsets, n_filters, filter_of, out_ids, out_dists, out_counts, "hnswgpu_exact_search_batch");
     if (rc != HNSWGPU_OK) return rc;
-    if (n_filters != 0) {
-        if (filter_offsets[0] != 0) return fail(HNSWGPU_ERR_ARG, "filter_offsets must start at 0");
-        for (uint64_t f = 0; f < n_filters; ++f)
-            if (filter_offsets[f] > filter_offsets[f + 1])
-                return fail(HNSWGPU_ERR_ARG, "filter_offsets must ascend: filter_offsets[" + std::to_string(f + 1) + "] is below its predecessor");
-        if (filter_offsets[n_filters] != 0 && !filter_ids) return fail(HNSWGPU_ERR_ARG, "null filter_ids");
-        for (uint64_t f = 0; f < n_filters; ++f)  // `impl FilterT for Vec<usize>` is a binary search: every vector must be sorted
-            for (uint64_t i = filter_offsets[f] + 1; i < filter_offsets[f + 1]; ++i)
-                if (filter_ids[i - 1] > filter_ids[i])
-                    return fail(HNSWGPU_ERR_ARG, "the id vector of filter " + std::to_string(f) + " is not sorted ascending");
-    }
-    for (uint64_t q = 0; q < nq; ++q)
-        if (filter_of[q] >= n_filters)
-            return fail(HNSWGPU_ERR_ARG, "filter_of[" + std::to_string(q) + "] = " + std::to_string(filter_of[q]) + " names no filter (n_filters = " +
-                        std::to_string(n_filters) + ")");
+    rc = check_filter_set_contents(filter_ids, filter_offsets, n_filters, filter_of, nq);
+    if (rc != HNSWGPU_OK) return rc;
     std::shared_lock<std::shared_mutex> sl(idx->mu);
-    rc = exact_filter_set_call(idx, nq, d, k);
+    rc = check_exact_call(idx, queries, nq, d, k, nullptr, 0, out_ids, out_dists, out_counts);
     if (rc != HNSWGPU_OK) return rc;
-    const bool empty = idx->builder ? idx->builder->nb_point() == 0 : (!idx->flat || idx->flat->n == 0);
-    if (empty) {  // no point: every answer is empty
-        if (nq != 0) {
-            std::memset(out_counts, 0, nq * sizeof(uint32_t));
-            std::memset(out_ids, 0, nq * k * sizeof(uint64_t));
-            std::memset(out_dists, 0, nq * k * sizeof(float));
-            if (out_layer) std::memset(out_layer, 0, nq * k);
-            if (out_rank) std::memset(out_rank, 0, nq * k * sizeof(int32_t));
-        }
+    if (index_empty(idx)) {  // no point: every answer is empty
+        zero_knn_answers(nq, k, out_ids, out_dists, out_layer, out_rank, out_counts);
         return HNSWGPU_OK;
     }
     if (nq == 0) return HNSWGPU_OK;
@@ -878,9 +896,8 @@ int hnswgpu_exact_search_batch_filter_set(const hnswgpu_index* cidx, const float
     if (rc != HNSWGPU_OK) return rc;
     std::string err;
     const FilterSet set{filter_ids, filter_offsets, n_filters, filter_of};
-    rc = hnswgpu::exact_filter_set_host(*dev, idx->flat->origin_id, queries, nq, d, k, set, out_ids, out_dists, out_layer, out_rank, out_counts, err);
-    if (rc != OK) return fail(rc, err);
-    return HNSWGPU_OK;
+    return finish(hnswgpu::exact_filter_set_host(*dev, idx->flat->origin_id, queries, nq, d, k, set, out_ids, out_dists, out_layer, out_rank, out_counts, err),
+                  err);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
@@ -891,24 +908,23 @@ int hnswgpu_exact_search_batch_filter_set_device(const hnswgpu_index* cidx, cons
     CAPI_GUARD_BEGIN
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    int rc = exact_filter_set_shape(d_queries, nq, d_filter_offsets, n_filters, d_filter_of, d_out_ids, d_out_dists, d_out_counts,
+    int rc = check_filter_set_shape(d_queries, nq, d_filter_offsets, n_filters, d_filter_of, d_out_ids, d_out_dists, d_out_counts,
                                     "hnswgpu_exact_search_batch_device");
     if (rc != HNSWGPU_OK) return rc;
     std::shared_lock<std::shared_mutex> sl(idx->mu);
-    rc = exact_filter_set_call(idx, nq, d, k);
+    rc = check_exact_call(idx, d_queries, nq, d, k, nullptr, 0, d_out_ids, d_out_dists, d_out_counts);
     if (rc != HNSWGPU_OK) return rc;
     if (nq == 0) return HNSWGPU_OK;
     if (!hnswgpu::exact_filter_set_device) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    DeviceIndex* dev = idx->primary >= 0 ? idx->replica(idx->primary) : nullptr;
-    if (!dev || idx->dev_stale || idx->flat_stale || !idx->flat)
-        return fail(HNSWGPU_ERR_DEVICE, "index is not resident on a device: call hnswgpu_upload first");
+    DeviceIndex* dev = nullptr;
+    rc = resident_replica(idx, true, &dev);
+    if (rc != HNSWGPU_OK) return rc;
     std::string err;
     // (filters that are all empty need no id array: hand over a non-null pointer that is never dereferenced)
     const FilterSet set{d_filter_ids ? d_filter_ids : reinterpret_cast<const uint64_t*>(d_queries), d_filter_offsets, n_filters, d_filter_of};
-    rc = hnswgpu::exact_filter_set_device(*dev, idx->flat->origin_id, d_queries, nq, d, k, set, d_out_ids, d_out_dists, d_out_layer, d_out_rank,
-                                          d_out_counts, stream, err);
-    if (rc != OK) return fail(rc, err);
-    return HNSWGPU_OK;
+    return finish(hnswgpu::exact_filter_set_device(*dev, idx->flat->origin_id, d_queries, nq, d, k, set, d_out_ids, d_out_dists, d_out_layer, d_out_rank,
+                                                   d_out_counts, stream, err),
+                  err);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
@@ -924,7 +940,7 @@ __attribute__((weak)) int exact_range_device(const DeviceIndex&, const std::vect
 // the checks both entries share; the handle's lock is held (shared)
 static int exact_range_call(const hnswgpu_index* idx, const void* queries, uint64_t nq, uint64_t d, const void* radii, const void* allowed,
                             uint64_t n_allowed, uint64_t cap, const void* out_offsets, const void* out_ids, const void* out_dists) {
-    const uint64_t dim = idx->builder ? idx->builder->dimension() : (idx->flat ? idx->flat->dimension : 0);
+    const uint64_t dim = index_dimension(idx);
     if (!out_offsets) return fail(HNSWGPU_ERR_ARG, "null out_offsets: the offsets are written by every call");
     if (nq != 0 && !queries) return fail(HNSWGPU_ERR_ARG, "null queries");
     if (nq != 0 && !radii) return fail(HNSWGPU_ERR_ARG, "null radii: every query names its radius");
@@ -946,10 +962,9 @@ int hnswgpu_exact_range_search_batch(const hnswgpu_index* cidx, const float* que
     std::shared_lock<std::shared_mutex> sl(idx->mu);
     int rc = exact_range_call(idx, queries, nq, d, radii, allowed_ids, n_allowed, cap, out_offsets, out_ids, out_dists);
     if (rc != HNSWGPU_OK) return rc;
-    for (uint64_t i = 1; i < n_allowed; ++i)  // `impl FilterT for Vec<usize>` is a binary search: the vector must be sorted
-        if (allowed_ids[i - 1] > allowed_ids[i]) return fail(HNSWGPU_ERR_ARG, "the id vector of a filter must be sorted ascending");
-    const bool empty = idx->builder ? idx->builder->nb_point() == 0 : (!idx->flat || idx->flat->n == 0);
-    if (empty || nq == 0) {  // no point, or no query: every answer is empty
+    rc = check_sorted_filter(allowed_ids, n_allowed);
+    if (rc != HNSWGPU_OK) return rc;
+    if (index_empty(idx) || nq == 0) {  // no point, or no query: every answer is empty
         std::memset(out_offsets, 0, (nq + 1) * sizeof(uint64_t));
         return HNSWGPU_OK;
     }
@@ -958,10 +973,9 @@ int hnswgpu_exact_range_search_batch(const hnswgpu_index* cidx, const float* que
     rc = primary_f32_replica(idx, sl, &dev);
     if (rc != HNSWGPU_OK) return rc;
     std::string err;
-    rc = hnswgpu::exact_range_host(*dev, idx->flat->origin_id, queries, nq, d, radii, allowed_ids, n_allowed, cap, out_offsets, out_ids, out_dists,
-                                   out_layer, out_rank, err);
-    if (rc != OK) return fail(rc, err);
-    return HNSWGPU_OK;
+    return finish(hnswgpu::exact_range_host(*dev, idx->flat->origin_id, queries, nq, d, radii, allowed_ids, n_allowed, cap, out_offsets, out_ids, out_dists,
+                                            out_layer, out_rank, err),
+                  err);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
@@ -975,14 +989,13 @@ int hnswgpu_exact_range_search_batch_device(const hnswgpu_index* cidx, const flo
     int rc = exact_range_call(idx, d_queries, nq, d, d_radii, d_allowed_ids, n_allowed, cap, d_out_offsets, d_out_ids, d_out_dists);
     if (rc != HNSWGPU_OK) return rc;
     if (!hnswgpu::exact_range_device) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    DeviceIndex* dev = idx->primary >= 0 ? idx->replica(idx->primary) : nullptr;
-    if (!dev || idx->dev_stale || idx->flat_stale || !idx->flat)
-        return fail(HNSWGPU_ERR_DEVICE, "index is not resident on a device: call hnswgpu_upload first");
+    DeviceIndex* dev = nullptr;
+    rc = resident_replica(idx, true, &dev);
+    if (rc != HNSWGPU_OK) return rc;
     std::string err;
-    rc = hnswgpu::exact_range_device(*dev, idx->flat->origin_id, d_queries, nq, d, d_radii, d_allowed_ids, n_allowed, cap, d_out_offsets, d_out_ids,
-                                     d_out_dists, d_out_layer, d_out_rank, stream, err);
-    if (rc != OK) return fail(rc, err);
-    return HNSWGPU_OK;
+    return finish(hnswgpu::exact_range_device(*dev, idx->flat->origin_id, d_queries, nq, d, d_radii, d_allowed_ids, n_allowed, cap, d_out_offsets, d_out_ids,
+                                              d_out_dists, d_out_layer, d_out_rank, stream, err),
+                  err);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
@@ -998,7 +1011,7 @@ __attribute__((weak)) int exact_graph(const DeviceIndex&, const std::vector<uint
 // the checks all four entries share; the handle's lock is held (shared).  exact: the exact call's own limits behind them.
 static int graph_call(const hnswgpu_index* idx, const void* point_ids, uint64_t np, uint64_t k, bool exact, const void* allowed, uint64_t n_allowed,
                       const void* out_ids, const void* out_dists, const void* out_counts) {
-    const uint64_t n = idx->builder ? idx->builder->nb_point() : (idx->flat ? idx->flat->n : 0);
+    const uint64_t n = index_nb_point(idx);
     if (np != 0 && (!out_ids || !out_dists || !out_counts)) return fail(HNSWGPU_ERR_ARG, "null buffer");
     if (!point_ids && np != n)
         return fail(HNSWGPU_ERR_ARG, "point_ids is NULL (every point): np must be nb_point = " + std::to_string(n) + ", not " + std::to_string(np));
@@ -1015,10 +1028,16 @@ static int graph_call(const hnswgpu_index* idx, const void* point_ids, uint64_t 
 static int graph_host_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mutex>& sl, uint64_t np, bool have_device_side, DeviceIndex** dev) {
     *dev = nullptr;
     if (np == 0) return HNSWGPU_OK;
-    const bool empty = idx->builder ? idx->builder->nb_point() == 0 : (!idx->flat || idx->flat->n == 0);
-    if (empty) return fail(HNSWGPU_ERR_ARG, std::to_string(np) + " of the " + std::to_string(np) + " point_ids name no point of the index");
+    if (index_empty(idx)) return fail(HNSWGPU_ERR_ARG, std::to_string(np) + " of the " + std::to_string(np) + " point_ids name no point of the index");
     if (!have_device_side) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     return primary_f32_replica(idx, sl, dev);
+}
+// ... and the device entries: no point asks nothing of a device; else the replica has to be there
+static int graph_device_replica(const hnswgpu_index* idx, uint64_t np, bool have_device_side, DeviceIndex** dev) {
+    *dev = nullptr;
+    if (np == 0) return HNSWGPU_OK;
+    if (!have_device_side) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    return resident_replica(idx, true, dev);
 }
 
 int hnswgpu_graph_search_batch(const hnswgpu_index* cidx, const uint64_t* point_ids, uint64_t np, uint64_t k, uint64_t ef, uint64_t* out_ids,
@@ -1033,9 +1052,8 @@ int hnswgpu_graph_search_batch(const hnswgpu_index* cidx, const uint64_t* point_
     rc = graph_host_replica(idx, sl, np, hnswgpu::graph_search != nullptr, &dev);
     if (rc != HNSWGPU_OK || !dev) return rc;
     std::string err;
-    rc = hnswgpu::graph_search(*dev, idx->flat->origin_id, true, point_ids, np, k, ef, out_ids, out_dists, out_layer, out_rank, out_counts, nullptr, err);
-    if (rc != OK) return fail(rc, err);
-    return HNSWGPU_OK;
+    return finish(hnswgpu::graph_search(*dev, idx->flat->origin_id, true, point_ids, np, k, ef, out_ids, out_dists, out_layer, out_rank, out_counts, nullptr, err),
+                  err);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
@@ -1048,16 +1066,13 @@ int hnswgpu_graph_search_batch_device(const hnswgpu_index* cidx, const uint64_t*
     std::shared_lock<std::shared_mutex> sl(idx->mu);
     int rc = graph_call(idx, d_point_ids, np, k, false, nullptr, 0, d_out_ids, d_out_dists, d_out_counts);
     if (rc != HNSWGPU_OK) return rc;
-    if (np == 0) return HNSWGPU_OK;
-    if (!hnswgpu::graph_search) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    DeviceIndex* dev = idx->primary >= 0 ? idx->replica(idx->primary) : nullptr;
-    if (!dev || idx->dev_stale || idx->flat_stale || !idx->flat)
-        return fail(HNSWGPU_ERR_DEVICE, "index is not resident on a device: call hnswgpu_upload first");
+    DeviceIndex* dev = nullptr;
+    rc = graph_device_replica(idx, np, hnswgpu::graph_search != nullptr, &dev);
+    if (rc != HNSWGPU_OK || !dev) return rc;
     std::string err;
-    rc = hnswgpu::graph_search(*dev, idx->flat->origin_id, false, d_point_ids, np, k, ef, d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts,
-                               stream, err);
-    if (rc != OK) return fail(rc, err);
-    return HNSWGPU_OK;
+    return finish(hnswgpu::graph_search(*dev, idx->flat->origin_id, false, d_point_ids, np, k, ef, d_out_ids, d_out_dists, d_out_layer, d_out_rank,
+                                        d_out_counts, stream, err),
+                  err);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
@@ -1069,16 +1084,15 @@ int hnswgpu_exact_graph_batch(const hnswgpu_index* cidx, const uint64_t* point_i
     std::shared_lock<std::shared_mutex> sl(idx->mu);
     int rc = graph_call(idx, point_ids, np, k, true, allowed_ids, n_allowed, out_ids, out_dists, out_counts);
     if (rc != HNSWGPU_OK) return rc;
-    for (uint64_t i = 1; i < n_allowed; ++i)  // `impl FilterT for Vec<usize>` is a binary search: the vector must be sorted
-        if (allowed_ids[i - 1] > allowed_ids[i]) return fail(HNSWGPU_ERR_ARG, "the id vector of a filter must be sorted ascending");
+    rc = check_sorted_filter(allowed_ids, n_allowed);
+    if (rc != HNSWGPU_OK) return rc;
     DeviceIndex* dev = nullptr;
     rc = graph_host_replica(idx, sl, np, hnswgpu::exact_graph != nullptr, &dev);
     if (rc != HNSWGPU_OK || !dev) return rc;
     std::string err;
-    rc = hnswgpu::exact_graph(*dev, idx->flat->origin_id, true, point_ids, np, k, allowed_ids, n_allowed, out_ids, out_dists, out_layer, out_rank, out_counts,
-                              nullptr, err);
-    if (rc != OK) return fail(rc, err);
-    return HNSWGPU_OK;
+    return finish(hnswgpu::exact_graph(*dev, idx->flat->origin_id, true, point_ids, np, k, allowed_ids, n_allowed, out_ids, out_dists, out_layer, out_rank,
+                                       out_counts, nullptr, err),
+                  err);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
@@ -1091,16 +1105,13 @@ int hnswgpu_exact_graph_batch_device(const hnswgpu_index* cidx, const uint64_t* 
     std::shared_lock<std::shared_mutex> sl(idx->mu);
     int rc = graph_call(idx, d_point_ids, np, k, true, d_allowed_ids, n_allowed, d_out_ids, d_out_dists, d_out_counts);
     if (rc != HNSWGPU_OK) return rc;
-    if (np == 0) return HNSWGPU_OK;
-    if (!hnswgpu::exact_graph) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    DeviceIndex* dev = idx->primary >= 0 ? idx->replica(idx->primary) : nullptr;
-    if (!dev || idx->dev_stale || idx->flat_stale || !idx->flat)
-        return fail(HNSWGPU_ERR_DEVICE, "index is not resident on a device: call hnswgpu_upload first");
+    DeviceIndex* dev = nullptr;
+    rc = graph_device_replica(idx, np, hnswgpu::exact_graph != nullptr, &dev);
+    if (rc != HNSWGPU_OK || !dev) return rc;
     std::string err;
-    rc = hnswgpu::exact_graph(*dev, idx->flat->origin_id, false, d_point_ids, np, k, d_allowed_ids, n_allowed, d_out_ids, d_out_dists, d_out_layer,
-                              d_out_rank, d_out_counts, stream, err);
-    if (rc != OK) return fail(rc, err);
-    return HNSWGPU_OK;
+    return finish(hnswgpu::exact_graph(*dev, idx->flat->origin_id, false, d_point_ids, np, k, d_allowed_ids, n_allowed, d_out_ids, d_out_dists, d_out_layer,
+                                       d_out_rank, d_out_counts, stream, err),
+                  err);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
@@ -1114,7 +1125,7 @@ __attribute__((weak)) int range_search_device(DeviceIndex*, const RangeSearchArg
 }  // extern "C++"
 // the checks both entries share; the handle's lock is held (shared)
 static int range_search_call(const hnswgpu_index* idx, const RangeSearchArgs& a) {
-    const uint64_t dim = idx->builder ? idx->builder->dimension() : (idx->flat ? idx->flat->dimension : 0);
+    const uint64_t dim = index_dimension(idx);
     if (!a.out_offsets) return fail(HNSWGPU_ERR_ARG, "null out_offsets: the offsets are written by every call");
     if (a.nq != 0 && !a.queries) return fail(HNSWGPU_ERR_ARG, "null queries");
     if (a.nq != 0 && !a.radii) return fail(HNSWGPU_ERR_ARG, "null radii: every query names its radius");
@@ -1142,10 +1153,9 @@ int hnswgpu_range_search_batch(const hnswgpu_index* cidx, const float* queries, 
                             out_layer, out_rank, out_ef, out_flags};
     int rc = range_search_call(idx, a);
     if (rc != HNSWGPU_OK) return rc;
-    for (uint64_t i = 1; i < n_allowed; ++i)  // `impl FilterT for Vec<usize>` is a binary search: the vector must be sorted
-        if (allowed_ids[i - 1] > allowed_ids[i]) return fail(HNSWGPU_ERR_ARG, "the id vector of a filter must be sorted ascending");
-    const bool empty = idx->builder ? idx->builder->nb_point() == 0 : (!idx->flat || idx->flat->n == 0);
-    if (empty || nq == 0) {  // no point, or no query: every answer is empty
+    rc = check_sorted_filter(allowed_ids, n_allowed);
+    if (rc != HNSWGPU_OK) return rc;
+    if (index_empty(idx) || nq == 0) {  // no point, or no query: every answer is empty
         std::memset(out_offsets, 0, (nq + 1) * sizeof(uint64_t));
         if (out_ef && nq != 0) std::memset(out_ef, 0, nq * sizeof(uint32_t));
         if (out_flags && nq != 0) std::memset(out_flags, 0, nq);
@@ -1156,9 +1166,7 @@ int hnswgpu_range_search_batch(const hnswgpu_index* cidx, const float* queries, 
     rc = primary_replica(idx, sl, &dev);
     if (rc != HNSWGPU_OK) return rc;
     std::string err;
-    rc = hnswgpu::range_search_host(*dev, a, err);
-    if (rc != OK) return fail(rc, err);
-    return HNSWGPU_OK;
+    return finish(hnswgpu::range_search_host(*dev, a, err), err);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
@@ -1176,18 +1184,12 @@ int hnswgpu_range_search_batch_device(const hnswgpu_index* cidx, const float* d_
     if (rc != HNSWGPU_OK) return rc;
     if (!hnswgpu::range_search_device) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     std::string err;
-    const bool empty = idx->builder ? idx->builder->nb_point() == 0 : (!idx->flat || idx->flat->n == 0);
-    if (empty || nq == 0) {  // no point, or no query: the offsets are zeroed on the caller's stream
-        rc = hnswgpu::range_search_device(nullptr, a, stream, err);
-        if (rc != OK) return fail(rc, err);
-        return HNSWGPU_OK;
+    DeviceIndex* dev = nullptr;  // (stays so where there is no point, or no query: the offsets are zeroed on the caller's stream)
+    if (!index_empty(idx) && nq != 0) {
+        rc = resident_replica(idx, true, &dev);
+        if (rc != HNSWGPU_OK) return rc;
     }
-    DeviceIndex* dev = idx->primary >= 0 ? idx->replica(idx->primary) : nullptr;
-    if (!dev || idx->dev_stale || idx->flat_stale || !idx->flat)
-        return fail(HNSWGPU_ERR_DEVICE, "index is not resident on a device: call hnswgpu_upload first");
-    rc = hnswgpu::range_search_device(dev, a, stream, err);
-    if (rc != OK) return fail(rc, err);
-    return HNSWGPU_OK;
+    return finish(hnswgpu::range_search_device(dev, a, stream, err), err);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
@@ -1199,7 +1201,7 @@ __attribute__((weak)) int symmetric_graph(DeviceIndex*, const std::vector<uint64
 }  // extern "C++"
 // the checks both entries share; the handle's lock is held (shared).  What the source call of D refuses is refused here.
 static int symmetric_graph_call(const hnswgpu_index* idx, const SymGraphArgs& a) {
-    const uint64_t n = idx->builder ? idx->builder->nb_point() : (idx->flat ? idx->flat->n : 0);
+    const uint64_t n = index_nb_point(idx);
     if (!a.out_offsets) return fail(HNSWGPU_ERR_ARG, "null out_offsets: the offsets are written by every call");
     if (a.k == 0) return fail(HNSWGPU_ERR_ARG, "knbn must be > 0");
     if (a.mode != HNSWGPU_SYM_UNION && a.mode != HNSWGPU_SYM_MUTUAL)
@@ -1225,7 +1227,7 @@ int hnswgpu_symmetric_graph(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, 
     const SymGraphArgs a{k, ef, mode, cap, out_offsets, out_pos, out_ids, out_dists, out_layer, out_rank};
     int rc = symmetric_graph_call(idx, a);
     if (rc != HNSWGPU_OK) return rc;
-    const uint64_t n = idx->builder ? idx->builder->nb_point() : (idx->flat ? idx->flat->n : 0);
+    const uint64_t n = index_nb_point(idx);
     if (n <= 1) {  // no point, or one: no edge
         std::memset(out_offsets, 0, (n + 1) * sizeof(uint64_t));
         return HNSWGPU_OK;
@@ -1235,9 +1237,7 @@ int hnswgpu_symmetric_graph(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, 
     rc = primary_f32_replica(idx, sl, &dev);
     if (rc != HNSWGPU_OK) return rc;
     std::string err;
-    rc = hnswgpu::symmetric_graph(dev, idx->flat->origin_id, a, true, nullptr, err);
-    if (rc != OK) return fail(rc, err);
-    return HNSWGPU_OK;
+    return finish(hnswgpu::symmetric_graph(dev, idx->flat->origin_id, a, true, nullptr, err), err);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
@@ -1253,18 +1253,12 @@ int hnswgpu_symmetric_graph_device(const hnswgpu_index* cidx, uint64_t k, uint64
     if (!hnswgpu::symmetric_graph) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     std::string err;
     static const std::vector<uint64_t> no_ids;
-    const bool empty = idx->builder ? idx->builder->nb_point() == 0 : (!idx->flat || idx->flat->n == 0);
-    if (empty) {  // no point: the one offset is zeroed on the caller's stream
-        rc = hnswgpu::symmetric_graph(nullptr, no_ids, a, false, stream, err);
-        if (rc != OK) return fail(rc, err);
-        return HNSWGPU_OK;
-    }
-    DeviceIndex* dev = idx->primary >= 0 ? idx->replica(idx->primary) : nullptr;
-    if (!dev || idx->dev_stale || idx->flat_stale || !idx->flat)
-        return fail(HNSWGPU_ERR_DEVICE, "index is not resident on a device: call hnswgpu_upload first");
-    rc = hnswgpu::symmetric_graph(dev, idx->flat->origin_id, a, false, stream, err);
-    if (rc != OK) return fail(rc, err);
-    return HNSWGPU_OK;
+    if (index_empty(idx))  // no point: the one offset is zeroed on the caller's stream
+        return finish(hnswgpu::symmetric_graph(nullptr, no_ids, a, false, stream, err), err);
+    DeviceIndex* dev = nullptr;
+    rc = resident_replica(idx, true, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    return finish(hnswgpu::symmetric_graph(dev, idx->flat->origin_id, a, false, stream, err), err);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
@@ -1375,9 +1369,7 @@ int hnswgpu_eval_distances(int dist, const float* a, const float* b, uint64_t n,
     CAPI_GUARD_BEGIN
     if (!a || !b || !out || dist < 0 || dist >= DIST_COUNT) return fail(HNSWGPU_ERR_ARG, "bad argument");
     std::string err;
-    int rc = eval_distance_matrix_device(dist, a, n, b, n, d, 1, true, out, err);
-    if (rc != OK) return fail(rc, err);
-    return HNSWGPU_OK;
+    return finish(eval_distance_matrix_device(dist, a, n, b, n, d, 1, true, out, err), err);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 int hnswgpu_eval_distance_matrix(int dist, const float* queries, uint64_t nq, const float* rows, uint64_t n, uint64_t d,
@@ -1385,9 +1377,7 @@ int hnswgpu_eval_distance_matrix(int dist, const float* queries, uint64_t nq, co
     CAPI_GUARD_BEGIN
     if (!queries || !rows || !out || dist < 0 || dist >= DIST_COUNT) return fail(HNSWGPU_ERR_ARG, "bad argument");
     std::string err;
-    int rc = eval_distance_matrix_device(dist, queries, nq, rows, n, d, batch, false, out, err);
-    if (rc != OK) return fail(rc, err);
-    return HNSWGPU_OK;
+    return finish(eval_distance_matrix_device(dist, queries, nq, rows, n, d, batch, false, out, err), err);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
@@ -1396,9 +1386,7 @@ int hnswgpu_eval_distance_matrix_arith(int dist, int arithmetic, const float* qu
     CAPI_GUARD_BEGIN
     if (!queries || !rows || !out || dist < 0 || dist >= DIST_COUNT) return fail(HNSWGPU_ERR_ARG, "bad argument");
     std::string err;
-    int rc = eval_distance_matrix_device(dist, queries, nq, rows, n, d, batch, false, out, err, arithmetic);
-    if (rc != OK) return fail(rc, err);
-    return HNSWGPU_OK;
+    return finish(eval_distance_matrix_device(dist, queries, nq, rows, n, d, batch, false, out, err, arithmetic), err);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
@@ -1427,9 +1415,7 @@ int hnswgpu_eval_distance_matrix_storage(int dist, int storage, const float* que
     }
     if (!hnswgpu::eval_distance_matrix_storage_device) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     std::string err;
-    int rc = hnswgpu::eval_distance_matrix_storage_device(dist, storage, queries, nq, rows, n, d, batch, out, err);
-    if (rc != OK) return fail(rc, err);
-    return HNSWGPU_OK;
+    return finish(hnswgpu::eval_distance_matrix_storage_device(dist, storage, queries, nq, rows, n, d, batch, out, err), err);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 

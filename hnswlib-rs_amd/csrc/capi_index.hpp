@@ -1,5 +1,9 @@
 // capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h, for the translation units
 // that implement entry points of the C ABI (capi.cpp; exact_knn.hip; range_search.hip; symmetric_graph.hip).  Private: not installed, not part of the ABI.
+// The checks that entries share (empty index, resident replica, sorted filter, the shape and contents of a filter set, the limits of
+// an exact call, the zeroed k-NN answer, the tail) live once, in capi.cpp; what an entry outside capi.cpp needs of them is declared
+// below as capi_*.  A new pair of entries calls them.  The HIP host helpers of the .hip units (HIP_TRY, DeviceGuard, DevMem,
+// round_up) are in hip_host.hpp, which this header -- compiled by plain g++ too -- does not include.
 #pragma once
 #include <exception>
 #include <map>
@@ -58,6 +62,21 @@ int capi_primary_f32_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mu
 // HNSWGPU_OK, or -- the index is set to HNSWGPU_STORAGE_F16 -- HNSWGPU_ERR_ARG with a message that names `what`: the calls that
 // read rows outside the search path (exact k-NN / range / graph, the stored-point queries) exist for f32 rows only
 int capi_refuse_f16(const hnswgpu_index* idx, const char* what);
+// the shared checks of capi.cpp that hnswgpu_exact_search_batch(_device) -- defined in exact_knn.hip -- call too.  The handle's lock
+// is held where the index is read.
+// the end of an entry: HNSWGPU_OK, or `rc` with `err` as the thread's message
+int capi_finish(int rc, const std::string& err);
+bool capi_index_empty(const hnswgpu_index* idx);
+// the primary replica as it is (nothing is uploaded), or HNSWGPU_ERR_DEVICE "index is not resident on a device ...";
+// need_flat: the host view has to be there too
+int capi_resident_replica(const hnswgpu_index* idx, bool need_flat, DeviceIndex** dev);
+// HNSWGPU_ERR_ARG unless ids[0..n) (host memory) ascend
+int capi_check_sorted_filter(const uint64_t* ids, uint64_t n);
+// the limits of an exact k-NN call: buffers, knbn, nq, d, the filter pointer, the arithmetic, the storage -- in this order
+int capi_check_exact_call(const hnswgpu_index* idx, const void* queries, uint64_t nq, uint64_t d, uint64_t k, const void* allowed, uint64_t n_allowed,
+                          const void* out_ids, const void* out_dists, const void* out_counts);
+// the k-NN answer of an index without a point: counts, ids, dists and (where given) layer and rank of nq rows zeroed
+void capi_zero_knn_answers(uint64_t nq, uint64_t k, uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts);
 // the device side of hnswgpu_exact_search_batch_filter_set(_device), defined in exact_knn.hip: the exact k-NN of every query q
 // under filter filter_of[q] of the set (the arguments have been checked).  capi.cpp refers to these two weakly, like the search's
 // own filter-set pair (search_device.hpp): a host-only build of the C ABI links without them and answers "no device".

@@ -46,6 +46,7 @@
 
 #include "capi_index.hpp"
 #include "graph_internal.hpp"
+#include "hip_host.hpp"
 #include "hnswio.hpp"
 #include "search_kernels.hpp"
 #pragma clang diagnostic push
@@ -60,7 +61,6 @@ constexpr uint64_t KEY_NONE = ~0ull;            // behind every key: the thresho
 constexpr uint32_t MIN_SLAB_ROWS = 256;
 constexpr uint32_t MAX_SLABS = 64;              // the merge keeps one slab per lane
 constexpr uint64_t SCRATCH_BUDGET = 320ull << 20;  // bytes of scratch per call at most, whatever nq and n are
-constexpr uint64_t K_MAX = 4096;                // list_insert costs O(k / 64) steps per insertion: the largest knbn that was run at size
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(4))) const v4f* qtile_ptr_t;  // wave-uniform addresses: scalar loads
@@ -406,34 +406,6 @@ hipError_t launch_slab(int metric, bool set, bool self, dim3 grid, hipStream_t s
     return set ? launch_slab_of<true, false>(metric, grid, stream, ix, a) : launch_slab_of<false, false>(metric, grid, stream, ix, a);
 }
 
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            err = std::string(#expr) + ": " + hipGetErrorString(e_);                           \
-            return ERR_DEVICE;                                                                 \
-        }                                                                                      \
-    } while (0)
-
-// the caller's current HIP device is left as it was found
-class OnDevice {
-public:
-    explicit OnDevice(int device) {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-        if (cur == device) return;
-        status_ = hipSetDevice(device);
-        if (status_ == hipSuccess && cur >= 0) prev_ = cur;
-    }
-    ~OnDevice() { if (prev_ >= 0) (void)hipSetDevice(prev_); }
-    OnDevice(const OnDevice&) = delete;
-    OnDevice& operator=(const OnDevice&) = delete;
-    hipError_t status() const { return status_; }
-private:
-    int prev_ = -1;
-    hipError_t status_ = hipSuccess;
-};
-
 // What a replica keeps for this unit (DeviceIndex::extension): the DataId ranks, and scratch blocks that calls take turns with
 struct ExactState {
     int device = -1;
@@ -442,7 +414,7 @@ struct ExactState {
     std::mutex mu;
     std::vector<std::pair<void*, uint64_t>> pool;  // free scratch blocks {address, bytes}
     ~ExactState() {
-        OnDevice on(device);
+        DeviceGuard on(device);
         if (d_rank) (void)hipFree(d_rank);
         if (d_order) (void)hipFree(d_order);
         for (auto& b : pool) (void)hipFree(b.first);
@@ -494,8 +466,6 @@ std::shared_ptr<void> make_state(const DeviceIndex& dev, const std::vector<uint6
     return st;
 }
 
-uint64_t round_up(uint64_t x, uint64_t m) { return (x + m - 1) / m * m; }
-
 // A filter set behind a call (device pointers), and the knob that bounds the bitmaps one launch holds
 struct SetCall {
     const FilterSet* fs;
@@ -515,7 +485,7 @@ int exact_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id,
                  const uint32_t* d_self = nullptr) {
     const DeviceIndexView& v = dev.view();
     if (nq == 0) return OK;
-    OnDevice on(dev.device());
+    DeviceGuard on(dev.device());
     HIP_TRY(on.status());
     std::string serr;
     std::shared_ptr<void> ext = dev.extension([&]() { return make_state(dev, origin_id, serr); });
@@ -667,27 +637,6 @@ int exact_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id,
     HIP_TRY(hipStreamSynchronize(stream));
     return OK;
 }
-
-// the checks both entries share; the handle's lock is held (shared)
-int check_call(hnswgpu_index* idx, const void* queries, uint64_t nq, uint64_t d, uint64_t k, const void* allowed, uint64_t n_allowed,
-               const void* out_ids, const void* out_dists, const void* out_counts) {
-    const uint64_t dim = idx->builder ? idx->builder->dimension() : (idx->flat ? idx->flat->dimension : 0);
-    if (nq != 0 && (!queries || !out_ids || !out_dists || !out_counts)) return capi_fail(HNSWGPU_ERR_ARG, "null buffer");
-    if (k == 0) return capi_fail(HNSWGPU_ERR_ARG, "knbn must be > 0");
-    if (k > K_MAX) return capi_fail(HNSWGPU_ERR_ARG, "exact search: knbn above 4096");
-    if (nq > 0xFFFFFFF0ull) return capi_fail(HNSWGPU_ERR_ARG, "too many queries in one batch");
-    if (dim != 0 && d != dim) return capi_fail(HNSWGPU_ERR_ARG, "query dimension differs from the index dimension");
-    if (n_allowed != 0 && !allowed) return capi_fail(HNSWGPU_ERR_ARG, "null filter");
-    if (idx->arithmetic != HNSWGPU_ARITH_SCALAR)
-        return capi_fail(HNSWGPU_ERR_ARG, "exact search answers in the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
-    return capi_refuse_f16(idx, "exact search");
-}
-
-// device memory of the host-buffer entry
-struct DevMem {
-    void* p = nullptr;
-    ~DevMem() { if (p) (void)hipFree(p); }
-};
 
 uint64_t filter_set_budget() {
     const int64_t knob = knobs().filter_set_bytes;
@@ -923,7 +872,7 @@ struct RangeCall {
 int exact_range(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const RangeCall& io, uint64_t nq, uint64_t d, hipStream_t stream,
                 std::string& err) {
     const DeviceIndexView& v = dev.view();
-    OnDevice on(dev.device());
+    DeviceGuard on(dev.device());
     HIP_TRY(on.status());
     if (nq == 0) {
         if (io.host) { io.offsets[0] = 0; return OK; }
@@ -1190,11 +1139,7 @@ struct GraphCall {
     bool host;
     const uint64_t* point_ids;  // nullptr: every point
     uint64_t np, k;
-    uint64_t* ids;
-    float* dists;
-    uint8_t* layer;
-    int32_t* rank;
-    uint32_t* counts;
+    GraphRows out;              // np rows of k slots
 };
 
 // the named points as flat ids in device memory (m_flat; word 0 of m_ctrl counts the unknown ids).  Returns ERR_ARG, nothing
@@ -1223,8 +1168,13 @@ int graph_resolve(const DeviceIndexView& v, const ExactState* st, const GraphCal
     return OK;
 }
 
-// device staging of a chunk's k-wide answers (host calls), and their way out
-struct GraphStage {
+// rows [c0, c0 + ..) of k-wide answers
+GraphRows rows_at(const GraphRows& r, uint64_t c0, uint64_t k) {
+    return GraphRows{r.ids + c0 * k, r.dists + c0 * k, r.layer ? r.layer + c0 * k : nullptr, r.rank ? r.rank + c0 * k : nullptr, r.counts + c0};
+}
+// The one device staging of this unit for a chunk of k-NN answers, k slots a row: ids, dists, rank, counts and layer in one block,
+// each 256-aligned -- and the way of a chunk's first cq rows out to host rows
+struct AnswerStage {
     DevMem mem;
     GraphRows rows{};
     hipError_t alloc(uint64_t chunk, uint64_t k) {
@@ -1238,21 +1188,56 @@ struct GraphStage {
         rows.layer = p;
         return hipSuccess;
     }
-    hipError_t copy_out(const GraphCall& io, uint64_t c0, uint64_t cq, hipStream_t stream) const {
-        const uint64_t k = io.k;
-        hipError_t e = hipMemcpyAsync(io.ids + c0 * k, rows.ids, cq * k * 8, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(io.dists + c0 * k, rows.dists, cq * k * 4, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess && io.rank) e = hipMemcpyAsync(io.rank + c0 * k, rows.rank, cq * k * 4, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess && io.layer) e = hipMemcpyAsync(io.layer + c0 * k, rows.layer, cq * k, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(io.counts + c0, rows.counts, cq * 4, hipMemcpyDeviceToHost, stream);
+    hipError_t copy_out(const GraphRows& dst, uint64_t cq, uint64_t k, hipStream_t stream) const {  // (dst.layer, dst.rank may be nullptr)
+        hipError_t e = hipMemcpyAsync(dst.ids, rows.ids, cq * k * 8, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dst.dists, rows.dists, cq * k * 4, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess && dst.rank) e = hipMemcpyAsync(dst.rank, rows.rank, cq * k * 4, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess && dst.layer) e = hipMemcpyAsync(dst.layer, rows.layer, cq * k, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dst.counts, rows.counts, cq * 4, hipMemcpyDeviceToHost, stream);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);  // the staging area is the next chunk's
         return e;
     }
 };
-// rows [c0, c0 + ..) of a device call's own arrays
-GraphRows graph_rows_at(const GraphCall& io, uint64_t c0) {
-    return GraphRows{io.ids + c0 * io.k, io.dists + c0 * io.k, io.layer ? io.layer + c0 * io.k : nullptr, io.rank ? io.rank + c0 * io.k : nullptr,
-                     io.counts + c0};
+
+// Host buffers of an exact k-NN call: queries and answers are staged in chunks of at most 64 MB, each chunk one call of the device
+// path on the null stream.  d_set == nullptr: no filter, or one for the batch (d_allowed, on the device).  Else d_set's ids and offsets
+// are on the device, and every chunk brings its own rows of filter_of (host memory) along.
+int exact_host_chunks(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* queries, uint64_t nq, uint64_t d, uint64_t k,
+                      const uint64_t* d_allowed, uint64_t n_allowed, bool filtered, const FilterSet* d_set, const uint32_t* filter_of,
+                      const GraphRows& out, std::string& err) {
+    const uint64_t per_q = d * 4 + k * 17 + 4 + (d_set ? 4 : 0);
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(nq, (64ull << 20) / per_q));
+    DevMem m_q, m_of;
+    AnswerStage stage;
+    HIP_TRY(hipMalloc(&m_q.p, chunk * d * 4));
+    if (d_set) HIP_TRY(hipMalloc(&m_of.p, chunk * sizeof(uint32_t)));
+    HIP_TRY(stage.alloc(chunk, k));
+    const FilterSet chunk_set{d_set ? d_set->ids : nullptr, d_set ? d_set->offsets : nullptr, d_set ? d_set->n_filters : 0, static_cast<const uint32_t*>(m_of.p)};
+    const SetCall call{&chunk_set, filter_set_budget()};
+    for (uint64_t q0 = 0; q0 < nq; q0 += chunk) {
+        const uint64_t cq = std::min(chunk, nq - q0);
+        HIP_TRY(hipMemcpy(m_q.p, queries + q0 * d, cq * d * 4, hipMemcpyHostToDevice));
+        if (d_set) HIP_TRY(hipMemcpy(m_of.p, filter_of + q0, cq * sizeof(uint32_t), hipMemcpyHostToDevice));
+        const int rc = exact_device(dev, origin_id, static_cast<const float*>(m_q.p), cq, d, k, d_allowed, n_allowed, filtered, d_set ? &call : nullptr,
+                                    stage.rows.ids, stage.rows.dists, stage.rows.layer, stage.rows.rank, stage.rows.counts, nullptr, err);
+        if (rc != OK) return rc;
+        HIP_TRY(stage.copy_out(rows_at(out, q0, k), cq, k, nullptr));
+    }
+    return OK;
+}
+// the host side of hnswgpu_exact_search_batch: the filter, when there is one, goes to the device once
+int exact_host(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* queries, uint64_t nq, uint64_t d, uint64_t k,
+               const uint64_t* allowed, uint64_t n_allowed, const GraphRows& out, std::string& err) {
+    if (nq == 0) return OK;
+    DeviceGuard on(dev.device());
+    HIP_TRY(on.status());
+    DevMem m_allowed;  // (a filter that is empty still is a filter: a non-null pointer that is never dereferenced)
+    if (allowed != nullptr) {
+        HIP_TRY(hipMalloc(&m_allowed.p, std::max<uint64_t>(1, n_allowed) * sizeof(uint64_t)));
+        if (n_allowed != 0) HIP_TRY(hipMemcpy(m_allowed.p, allowed, n_allowed * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    return exact_host_chunks(dev, origin_id, queries, nq, d, k, static_cast<const uint64_t*>(m_allowed.p), n_allowed, allowed != nullptr, nullptr, nullptr,
+                             out, err);
 }
 
 }  // namespace
@@ -1267,48 +1252,22 @@ int exact_filter_set_device(const DeviceIndex& dev, const std::vector<uint64_t>&
                         d_out_counts, static_cast<hipStream_t>(stream), err);
 }
 
-// host buffers: the set goes to the device once; queries and answers are staged in chunks of at most 64 MB, each chunk one call
-// of the device path (under its own rows of filter_of)
+// host buffers: the set goes to the device once; queries and answers go chunk by chunk (exact_host_chunks)
 int exact_filter_set_host(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* queries, uint64_t nq, uint64_t d,
                           uint64_t k, const FilterSet& set, uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank,
                           uint32_t* out_counts, std::string& err) {
     if (nq == 0) return OK;
-    OnDevice on(dev.device());
+    DeviceGuard on(dev.device());
     HIP_TRY(on.status());
     const uint64_t n_ids = set.offsets[set.n_filters];
-    const uint64_t per_q = d * 4 + k * 17 + 4 + 4;
-    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(nq, (64ull << 20) / per_q));
-    DevMem m_ids, m_off, m_of, m_q, m_out;
+    DevMem m_ids, m_off;
     HIP_TRY(hipMalloc(&m_ids.p, std::max<uint64_t>(1, n_ids) * sizeof(uint64_t)));  // (filters that are all empty: never read)
     HIP_TRY(hipMalloc(&m_off.p, (set.n_filters + 1) * sizeof(uint64_t)));
-    HIP_TRY(hipMalloc(&m_of.p, chunk * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&m_q.p, chunk * d * 4));
-    HIP_TRY(hipMalloc(&m_out.p, chunk * (k * 17 + 4) + 64));
     if (n_ids != 0) HIP_TRY(hipMemcpy(m_ids.p, set.ids, n_ids * sizeof(uint64_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(m_off.p, set.offsets, (set.n_filters + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-    unsigned char* o = static_cast<unsigned char*>(m_out.p);
-    uint64_t* d_ids = reinterpret_cast<uint64_t*>(o);
-    float* d_dists = reinterpret_cast<float*>(o + chunk * k * 8);
-    int32_t* d_rank = reinterpret_cast<int32_t*>(o + chunk * k * 12);
-    uint32_t* d_counts = reinterpret_cast<uint32_t*>(o + chunk * k * 16);
-    uint8_t* d_layer = o + chunk * k * 16 + chunk * 4;
-    const FilterSet d_set{static_cast<const uint64_t*>(m_ids.p), static_cast<const uint64_t*>(m_off.p), set.n_filters,
-                          static_cast<const uint32_t*>(m_of.p)};
-    const SetCall call{&d_set, filter_set_budget()};
-    for (uint64_t q0 = 0; q0 < nq; q0 += chunk) {
-        const uint64_t cq = std::min(chunk, nq - q0);
-        HIP_TRY(hipMemcpy(m_q.p, queries + q0 * d, cq * d * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(m_of.p, set.filter_of + q0, cq * sizeof(uint32_t), hipMemcpyHostToDevice));
-        const int rc = exact_device(dev, origin_id, static_cast<const float*>(m_q.p), cq, d, k, nullptr, 0, false, &call, d_ids, d_dists, d_layer,
-                                    d_rank, d_counts, nullptr, err);
-        if (rc != OK) return rc;
-        HIP_TRY(hipMemcpy(out_ids + q0 * k, d_ids, cq * k * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_dists + q0 * k, d_dists, cq * k * 4, hipMemcpyDeviceToHost));
-        if (out_rank) HIP_TRY(hipMemcpy(out_rank + q0 * k, d_rank, cq * k * 4, hipMemcpyDeviceToHost));
-        if (out_layer) HIP_TRY(hipMemcpy(out_layer + q0 * k, d_layer, cq * k, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_counts + q0, d_counts, cq * 4, hipMemcpyDeviceToHost));
-    }
-    return OK;
+    const FilterSet d_set{static_cast<const uint64_t*>(m_ids.p), static_cast<const uint64_t*>(m_off.p), set.n_filters, nullptr};
+    return exact_host_chunks(dev, origin_id, queries, nq, d, k, nullptr, 0, false, &d_set, set.filter_of,
+                             GraphRows{out_ids, out_dists, out_layer, out_rank, out_counts}, err);
 }
 
 // The device side of hnswgpu_exact_range_search_batch(_device); capi.cpp holds the entries and every argument check, and refers
@@ -1325,7 +1284,7 @@ int exact_range_device(const DeviceIndex& dev, const std::vector<uint64_t>& orig
 int exact_range_host(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* queries, uint64_t nq, uint64_t d,
                      const float* radii, const uint64_t* allowed, uint64_t n_allowed, uint64_t cap, uint64_t* out_offsets, uint64_t* out_ids,
                      float* out_dists, uint8_t* out_layer, int32_t* out_rank, std::string& err) {
-    OnDevice on(dev.device());
+    DeviceGuard on(dev.device());
     HIP_TRY(on.status());
     DevMem m_allowed;
     if (allowed != nullptr) {
@@ -1348,19 +1307,19 @@ int graph_search(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, bool 
     if (np == 0) return OK;
     const DeviceIndexView& v = dev.view();
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    OnDevice on(dev.device());
+    DeviceGuard on(dev.device());
     HIP_TRY(on.status());
     std::string serr;
     std::shared_ptr<void> ext = dev.extension([&]() { return make_state(dev, origin_id, serr); });
     if (!ext) { err = serr.empty() ? "graph search: no device state" : serr; return ERR_DEVICE; }
     const ExactState* st = static_cast<const ExactState*>(ext.get());
-    const GraphCall io{host, point_ids, np, k, out_ids, out_dists, out_layer, out_rank, out_counts};
+    const GraphCall io{host, point_ids, np, k, {out_ids, out_dists, out_layer, out_rank, out_counts}};
     struct Drain {
         hipStream_t s;
         ~Drain() { (void)hipStreamSynchronize(s); }
     };
-    DevMem m_flat, m_scr;
-    GraphStage stage;
+    DevMem m_flat, m_q;
+    AnswerStage wide, stage;  // the search's (k + 1)-wide answers; a host call's k-wide ones
     Drain drain{stream};  // (destroyed first: nothing of this call is running when its memory is freed)
     int rc = graph_resolve(v, st, io, m_flat, stream, err);
     if (rc != OK) return rc;
@@ -1370,28 +1329,22 @@ int graph_search(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, bool 
     const uint64_t per_point = d * 4 + k1 * 17 + 4 + (host ? k * 17 + 4 : 0);
     const int64_t knob = knobs().graph_chunk;
     const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>({np, GRAPH_SCRATCH / per_point, knob > 0 ? (uint64_t)knob : np}));
-    HIP_TRY(hipMalloc(&m_scr.p, round_up(chunk * d * 4, 256) + round_up(chunk * k1 * 8, 256) + 2 * round_up(chunk * k1 * 4, 256) + round_up(chunk * 4, 256) +
-                                    round_up(chunk * k1, 256)));
-    unsigned char* p = static_cast<unsigned char*>(m_scr.p);
-    float* d_q = reinterpret_cast<float*>(p); p += round_up(chunk * d * 4, 256);
-    GraphRows wide{};
-    wide.ids = reinterpret_cast<uint64_t*>(p); p += round_up(chunk * k1 * 8, 256);
-    wide.dists = reinterpret_cast<float*>(p); p += round_up(chunk * k1 * 4, 256);
-    wide.rank = reinterpret_cast<int32_t*>(p); p += round_up(chunk * k1 * 4, 256);
-    wide.counts = reinterpret_cast<uint32_t*>(p); p += round_up(chunk * 4, 256);
-    wide.layer = p;
+    HIP_TRY(hipMalloc(&m_q.p, chunk * d * 4));
+    float* d_q = static_cast<float*>(m_q.p);
+    HIP_TRY(wide.alloc(chunk, k1));
     if (host) HIP_TRY(stage.alloc(chunk, k));
 
     for (uint64_t c0 = 0; c0 < np; c0 += chunk) {
         const uint64_t cq = std::min(chunk, np - c0);
         hipLaunchKernelGGL(graph_gather_kernel, dim3((uint32_t)((cq * d + 255) / 256)), dim3(256), 0, stream, v, d_flat + c0, cq * d, d_q);
         HIP_TRY(hipGetLastError());
-        rc = dev.search_device(d_q, cq, d, k1, ef, wide.ids, wide.dists, wide.layer, wide.rank, wide.counts, nullptr, stream, nullptr, 0, nullptr, err);
+        rc = dev.search_device(d_q, cq, d, k1, ef, wide.rows.ids, wide.rows.dists, wide.rows.layer, wide.rows.rank, wide.rows.counts, nullptr, stream, nullptr, 0,
+                               nullptr, err);
         if (rc != OK) return rc;
-        hipLaunchKernelGGL(graph_compact_kernel, dim3((uint32_t)cq), dim3(64), 0, stream, v, d_flat + c0, wide, host ? stage.rows : graph_rows_at(io, c0),
-                           (uint32_t)k);
+        hipLaunchKernelGGL(graph_compact_kernel, dim3((uint32_t)cq), dim3(64), 0, stream, v, d_flat + c0, wide.rows,
+                           host ? stage.rows : rows_at(io.out, c0, k), (uint32_t)k);
         HIP_TRY(hipGetLastError());
-        if (host) HIP_TRY(stage.copy_out(io, c0, cq, stream));
+        if (host) HIP_TRY(stage.copy_out(rows_at(io.out, c0, k), cq, k, stream));
     }
     HIP_TRY(hipStreamSynchronize(stream));
     return OK;
@@ -1404,15 +1357,15 @@ int exact_graph(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, 
     if (np == 0) return OK;
     const DeviceIndexView& v = dev.view();
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    OnDevice on(dev.device());
+    DeviceGuard on(dev.device());
     HIP_TRY(on.status());
     std::string serr;
     std::shared_ptr<void> ext = dev.extension([&]() { return make_state(dev, origin_id, serr); });
     if (!ext) { err = serr.empty() ? "exact graph: no device state" : serr; return ERR_DEVICE; }
     const ExactState* st = static_cast<const ExactState*>(ext.get());
-    const GraphCall io{host, point_ids, np, k, out_ids, out_dists, out_layer, out_rank, out_counts};
+    const GraphCall io{host, point_ids, np, k, {out_ids, out_dists, out_layer, out_rank, out_counts}};
     DevMem m_flat, m_allowed;
-    GraphStage stage;
+    AnswerStage stage;
     int rc = graph_resolve(v, st, io, m_flat, stream, err);  // (waits for the stream)
     if (rc != OK) return rc;
     const uint32_t* d_flat = static_cast<const uint32_t*>(m_flat.p);
@@ -1435,14 +1388,14 @@ int exact_graph(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, 
         rc = exact_device(dev, origin_id, nullptr, cq, v.d, k, d_allowed, n_allowed, filtered, nullptr, stage.rows.ids, stage.rows.dists, stage.rows.layer,
                           stage.rows.rank, stage.rows.counts, stream, err, d_flat + c0);
         if (rc != OK) return rc;
-        HIP_TRY(stage.copy_out(io, c0, cq, stream));
+        HIP_TRY(stage.copy_out(rows_at(io.out, c0, k), cq, k, stream));
     }
     return OK;
 }
 
 // The DataId ranks of the replica's state, for symmetric_graph.hip (graph_internal.hpp): made on first use, like every call here does
 int graph_order(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, GraphOrder& out, std::string& err) {
-    OnDevice on(dev.device());
+    DeviceGuard on(dev.device());
     HIP_TRY(on.status());
     std::string serr;
     std::shared_ptr<void> ext = dev.extension([&]() { return make_state(dev, origin_id, serr); });
@@ -1468,16 +1421,15 @@ int hnswgpu_exact_search_batch_device(const hnswgpu_index* cidx, const float* d_
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (!idx) return capi_fail(HNSWGPU_ERR_ARG, "null argument");
     std::shared_lock<std::shared_mutex> sl(idx->mu);
-    int rc = check_call(idx, d_queries, nq, d, k, d_allowed_ids, n_allowed, d_out_ids, d_out_dists, d_out_counts);
+    int rc = capi_check_exact_call(idx, d_queries, nq, d, k, d_allowed_ids, n_allowed, d_out_ids, d_out_dists, d_out_counts);
     if (rc != HNSWGPU_OK) return rc;
-    DeviceIndex* dev = idx->primary >= 0 ? idx->replica(idx->primary) : nullptr;
-    if (!dev || idx->dev_stale || idx->flat_stale || !idx->flat)
-        return capi_fail(HNSWGPU_ERR_DEVICE, "index is not resident on a device: call hnswgpu_upload first");
+    DeviceIndex* dev = nullptr;
+    rc = capi_resident_replica(idx, true, &dev);
+    if (rc != HNSWGPU_OK) return rc;
     std::string err;
-    rc = exact_device(*dev, idx->flat->origin_id, d_queries, nq, d, k, d_allowed_ids, n_allowed, d_allowed_ids != nullptr, nullptr, d_out_ids,
-                      d_out_dists, d_out_layer, d_out_rank, d_out_counts, static_cast<hipStream_t>(stream), err);
-    if (rc != OK) return capi_fail(rc, err);
-    return HNSWGPU_OK;
+    return capi_finish(exact_device(*dev, idx->flat->origin_id, d_queries, nq, d, k, d_allowed_ids, n_allowed, d_allowed_ids != nullptr, nullptr, d_out_ids,
+                                    d_out_dists, d_out_layer, d_out_rank, d_out_counts, static_cast<hipStream_t>(stream), err),
+                       err);
     HNSWGPU_CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
@@ -1488,62 +1440,21 @@ int hnswgpu_exact_search_batch(const hnswgpu_index* cidx, const float* queries, 
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (!idx) return capi_fail(HNSWGPU_ERR_ARG, "null argument");
     std::shared_lock<std::shared_mutex> sl(idx->mu);
-    int rc = check_call(idx, queries, nq, d, k, allowed_ids, n_allowed, out_ids, out_dists, out_counts);
+    int rc = capi_check_exact_call(idx, queries, nq, d, k, allowed_ids, n_allowed, out_ids, out_dists, out_counts);
     if (rc != HNSWGPU_OK) return rc;
-    for (uint64_t i = 1; i < n_allowed; ++i)  // `impl FilterT for Vec<usize>` is a binary search: the vector must be sorted
-        if (allowed_ids[i - 1] > allowed_ids[i]) return capi_fail(HNSWGPU_ERR_ARG, "the id vector of a filter must be sorted ascending");
-    const bool empty = idx->builder ? idx->builder->nb_point() == 0 : (!idx->flat || idx->flat->n == 0);
-    if (empty) {  // no point: every answer is empty
-        if (nq != 0) {
-            std::memset(out_counts, 0, nq * sizeof(uint32_t));
-            std::memset(out_ids, 0, nq * k * sizeof(uint64_t));
-            std::memset(out_dists, 0, nq * k * sizeof(float));
-            if (out_layer) std::memset(out_layer, 0, nq * k);
-            if (out_rank) std::memset(out_rank, 0, nq * k * sizeof(int32_t));
-        }
+    rc = capi_check_sorted_filter(allowed_ids, n_allowed);
+    if (rc != HNSWGPU_OK) return rc;
+    if (capi_index_empty(idx)) {  // no point: every answer is empty
+        capi_zero_knn_answers(nq, k, out_ids, out_dists, out_layer, out_rank, out_counts);
         return HNSWGPU_OK;
     }
     DeviceIndex* dev = nullptr;
     rc = capi_primary_f32_replica(idx, sl, &dev);
     if (rc != HNSWGPU_OK) return rc;
-    if (nq == 0) return HNSWGPU_OK;
     std::string err;
-    auto dev_fail = [&](hipError_t e, const char* what) { return capi_fail(HNSWGPU_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); };
-    OnDevice on(dev->device());
-    if (on.status() != hipSuccess) return dev_fail(on.status(), "hipSetDevice");
-    const bool filtered = allowed_ids != nullptr;
-    DevMem m_allowed, m_q, m_out;
-    hipError_t e;
-    if (filtered && n_allowed != 0) {
-        if ((e = hipMalloc(&m_allowed.p, n_allowed * sizeof(uint64_t))) != hipSuccess) { m_allowed.p = nullptr; return dev_fail(e, "hipMalloc"); }
-        if ((e = hipMemcpy(m_allowed.p, allowed_ids, n_allowed * sizeof(uint64_t), hipMemcpyHostToDevice)) != hipSuccess) return dev_fail(e, "hipMemcpy");
-    }
-    // chunks of queries: the staging of queries and answers stays within 64 MB whatever nq is
-    const uint64_t per_q = d * 4 + k * 17 + 4;
-    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(nq, (64ull << 20) / per_q));
-    if ((e = hipMalloc(&m_q.p, chunk * d * 4)) != hipSuccess) { m_q.p = nullptr; return dev_fail(e, "hipMalloc"); }
-    if ((e = hipMalloc(&m_out.p, chunk * (k * 17 + 4) + 64)) != hipSuccess) { m_out.p = nullptr; return dev_fail(e, "hipMalloc"); }
-    unsigned char* o = static_cast<unsigned char*>(m_out.p);
-    uint64_t* d_ids = reinterpret_cast<uint64_t*>(o);
-    float* d_dists = reinterpret_cast<float*>(o + chunk * k * 8);
-    int32_t* d_rank = reinterpret_cast<int32_t*>(o + chunk * k * 12);
-    uint32_t* d_counts = reinterpret_cast<uint32_t*>(o + chunk * k * 16);
-    uint8_t* d_layer = o + chunk * k * 16 + chunk * 4;
-    // (a filter that is empty still is a filter: a non-null pointer that is never dereferenced)
-    const uint64_t* d_allowed = filtered ? (m_allowed.p ? static_cast<const uint64_t*>(m_allowed.p) : reinterpret_cast<const uint64_t*>(m_q.p)) : nullptr;
-    for (uint64_t q0 = 0; q0 < nq; q0 += chunk) {
-        const uint64_t cq = std::min(chunk, nq - q0);
-        if ((e = hipMemcpy(m_q.p, queries + q0 * d, cq * d * 4, hipMemcpyHostToDevice)) != hipSuccess) return dev_fail(e, "hipMemcpy");
-        rc = exact_device(*dev, idx->flat->origin_id, static_cast<const float*>(m_q.p), cq, d, k, d_allowed, n_allowed, filtered, nullptr, d_ids, d_dists,
-                          d_layer, d_rank, d_counts, nullptr, err);
-        if (rc != OK) return capi_fail(rc, err);
-        if ((e = hipMemcpy(out_ids + q0 * k, d_ids, cq * k * 8, hipMemcpyDeviceToHost)) != hipSuccess) return dev_fail(e, "hipMemcpy");
-        if ((e = hipMemcpy(out_dists + q0 * k, d_dists, cq * k * 4, hipMemcpyDeviceToHost)) != hipSuccess) return dev_fail(e, "hipMemcpy");
-        if (out_rank && (e = hipMemcpy(out_rank + q0 * k, d_rank, cq * k * 4, hipMemcpyDeviceToHost)) != hipSuccess) return dev_fail(e, "hipMemcpy");
-        if (out_layer && (e = hipMemcpy(out_layer + q0 * k, d_layer, cq * k, hipMemcpyDeviceToHost)) != hipSuccess) return dev_fail(e, "hipMemcpy");
-        if ((e = hipMemcpy(out_counts + q0, d_counts, cq * 4, hipMemcpyDeviceToHost)) != hipSuccess) return dev_fail(e, "hipMemcpy");
-    }
-    return HNSWGPU_OK;
+    return capi_finish(exact_host(*dev, idx->flat->origin_id, queries, nq, d, k, allowed_ids, n_allowed,
+                                  GraphRows{out_ids, out_dists, out_layer, out_rank, out_counts}, err),
+                       err);
     HNSWGPU_CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 

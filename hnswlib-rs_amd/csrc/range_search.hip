@@ -21,6 +21,7 @@
 #include <string>
 
 #include "capi_index.hpp"
+#include "hip_host.hpp"
 #include "hnswio.hpp"
 
 namespace hnswgpu {
@@ -29,39 +30,6 @@ namespace {
 constexpr uint64_t RANGE_BUDGET = 256ull << 20;  // bytes of staged answers, of held answers and of gathered queries per group at most
 constexpr uint64_t ENTRY_BYTES = 17;             // id, distance, rank, layer
 constexpr uint32_t ROWS_PER_WG = 4;              // wavefronts of a workgroup of the row kernels
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            err = std::string(#expr) + ": " + hipGetErrorString(e_);                           \
-            return ERR_DEVICE;                                                                 \
-        }                                                                                      \
-    } while (0)
-
-// the caller's current HIP device is left as it was found
-class OnDevice {
-public:
-    explicit OnDevice(int device) {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-        if (cur == device) return;
-        status_ = hipSetDevice(device);
-        if (status_ == hipSuccess && cur >= 0) prev_ = cur;
-    }
-    ~OnDevice() { if (prev_ >= 0) (void)hipSetDevice(prev_); }
-    OnDevice(const OnDevice&) = delete;
-    OnDevice& operator=(const OnDevice&) = delete;
-    hipError_t status() const { return status_; }
-private:
-    int prev_ = -1;
-    hipError_t status_ = hipSuccess;
-};
-struct DevMem {
-    void* p = nullptr;
-    ~DevMem() { if (p) (void)hipFree(p); }
-};
-uint64_t round_up(uint64_t x, uint64_t m) { return (x + m - 1) / m * m; }
 
 // answers entry by entry: staged rows of a round (row r, entry j at r e + j), held answers, CSR slots
 struct RangeSlots {
@@ -206,7 +174,7 @@ uint64_t range_group_size(uint64_t nq, uint64_t d, uint64_t ef_max) {
 // both entries.  host: every buffer of `a` but the filter is plain host memory (the filter has been copied); else device memory.
 int range_search(DeviceIndex& dev, const RangeSearchArgs& a, bool host, hipStream_t stream, std::string& err) {
     const uint64_t nq = a.nq, d = a.d;
-    OnDevice on(dev.device());
+    DeviceGuard on(dev.device());
     HIP_TRY(on.status());
     struct Drain {
         hipStream_t s;
@@ -341,7 +309,7 @@ int range_search_device(DeviceIndex* dev, const RangeSearchArgs& d_a, void* stre
 }
 
 int range_search_host(DeviceIndex& dev, const RangeSearchArgs& a, std::string& err) {
-    OnDevice on(dev.device());
+    DeviceGuard on(dev.device());
     HIP_TRY(on.status());
     DevMem m_allowed;
     RangeSearchArgs b = a;

@@ -30,6 +30,7 @@
 #include <thread>
 #include <vector>
 
+#include "hip_host.hpp"
 #include "hnswio.hpp"
 #include "search_device.hpp"
 #include "search_kernels.hpp"
@@ -103,15 +104,6 @@ void reload_knobs() {  // (the previous set stays allocated: a call in flight ma
 
 namespace {
 
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            err = std::string(#expr) + ": " + hipGetErrorString(e_);                           \
-            return ERR_DEVICE;                                                                 \
-        }                                                                                      \
-    } while (0)
-
 // A search call ends with one read-back of the counters.  The kernels of this path run for milliseconds, and a blocking
 // wait costs ~0.1 ms of wake-up latency per call: poll first, block only when the work is long.
 hipError_t wait_stream(hipStream_t s) {
@@ -130,27 +122,6 @@ hipError_t wait_event(hipEvent_t ev) {
         if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) return hipEventSynchronize(ev);
     }
 }
-
-// Every entry point works on the replica's device and leaves the CALLER's current HIP device as it found it (a host
-// thread shared with PyTorch, a Rust or a Julia runtime keeps allocating and launching where it did before the call).
-class DeviceGuard {
-public:
-    explicit DeviceGuard(int device) {
-        if (device < 0) return;
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-        if (cur == device) return;
-        status_ = hipSetDevice(device);
-        if (status_ == hipSuccess && cur >= 0) prev_ = cur;
-    }
-    ~DeviceGuard() { if (prev_ >= 0) (void)hipSetDevice(prev_); }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-    hipError_t status() const { return status_; }
-private:
-    int prev_ = -1;
-    hipError_t status_ = hipSuccess;
-};
 
 constexpr uint64_t PAIR_SEARCH_AUTO_MIN_QUERIES = 40000;  // hnsw_search_pair_kernel as the first pass of a strict DistCosine / DistDot batch (rows of one 128-byte line) of at least this many queries
 constexpr int STRICT_WG_PER_CU = 16;  // resident workgroups per CU of a strict launch: four waves per SIMD (see search_device)

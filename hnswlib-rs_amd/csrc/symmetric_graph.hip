@@ -30,44 +30,11 @@
 
 #include "capi_index.hpp"
 #include "graph_internal.hpp"
+#include "hip_host.hpp"
 #include "hnswio.hpp"
 
 namespace hnswgpu {
 namespace {
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            err = std::string(#expr) + ": " + hipGetErrorString(e_);                           \
-            return ERR_DEVICE;                                                                 \
-        }                                                                                      \
-    } while (0)
-
-// the caller's current HIP device is left as it was found
-class OnDevice {
-public:
-    explicit OnDevice(int device) {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-        if (cur == device) return;
-        status_ = hipSetDevice(device);
-        if (status_ == hipSuccess && cur >= 0) prev_ = cur;
-    }
-    ~OnDevice() { if (prev_ >= 0) (void)hipSetDevice(prev_); }
-    OnDevice(const OnDevice&) = delete;
-    OnDevice& operator=(const OnDevice&) = delete;
-    hipError_t status() const { return status_; }
-private:
-    int prev_ = -1;
-    hipError_t status_ = hipSuccess;
-};
-struct DevMem {
-    void* p = nullptr;
-    ~DevMem() { release(); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-};
-uint64_t round_up(uint64_t x, uint64_t m) { return (x + m - 1) / m * m; }
 
 // A record's key: the row above bit 33, the col in bits 1 .. 32, the flag in bit 0 (rows and cols are below 2^30: n k <= 2^30)
 constexpr uint64_t FLAG_REV = 1ull;
@@ -179,7 +146,7 @@ int symmetric_graph(DeviceIndex* dev_p, const std::vector<uint64_t>& origin_id, 
     }
     DeviceIndex& dev = *dev_p;
     const DeviceIndexView& v = dev.view();
-    OnDevice on(dev.device());
+    DeviceGuard on(dev.device());
     HIP_TRY(on.status());
     const uint64_t n = v.n, k = a.k;
     const uint64_t slots = n * k, records = 2 * slots;  // (n k <= 2^30: checked by the entries)
