@@ -784,14 +784,27 @@ def f16_representable(x):
     return bad, (first.value if bad else None)
 
 
-def eval_distance_matrix(dist, queries, rows, batch, arithmetic="scalar", storage="f32"):
+EVAL_VARIANT = {"plain": 0, "deep": N.HEADER.constants["HNSWGPU_EVAL_DEEP"], "pipe": N.HEADER.constants["HNSWGPU_EVAL_PIPE"],
+                "r128": N.HEADER.constants["HNSWGPU_EVAL_R128"],
+                "deep+r128": N.HEADER.constants["HNSWGPU_EVAL_DEEP"] | N.HEADER.constants["HNSWGPU_EVAL_R128"]}
+
+
+def eval_distance_matrix(dist, queries, rows, batch, arithmetic="scalar", storage="f32", variant="plain"):
     """out[q][r] = Distance<f32>::eval(queries[q], rows[r]) on the device, by the search kernel's own distance routine with
     the rows taken in batches of `batch` (1..64) -- the lane-group branches the search takes for that many neighbours.
     arithmetic: "scalar" (the crate's default build) or "simd8" (the summation order of its simdeez_f build).
-    storage: "f16" = the rows (representable ones only) narrowed to binary16 before the kernel reads them (scalar arithmetic)."""
+    storage: "f16" = the rows (representable ones only) narrowed to binary16 before the kernel reads them (scalar arithmetic).
+    variant: "plain", or the row loop a search kernel's expansion compiles -- "deep" (strict, ef <= 128), "pipe" (strict, ef 129..256),
+    "r128" / "deep+r128" (the fixed row stride of DistL2 / f32 / 97 <= d <= 128, lean / strict); scalar arithmetic."""
     q = np.ascontiguousarray(queries, dtype=np.float32)
     r = np.ascontiguousarray(rows, dtype=np.float32)
     out = np.zeros((q.shape[0], r.shape[0]), np.float32)
+    if variant != "plain":
+        if arithmetic != "scalar":
+            raise HnswError(N.ERR_ARG, "the variants of the row loop exist in the scalar arithmetic only")
+        _check(N.lib().hnswgpu_eval_distance_matrix_variant(N.DIST[dist], STORAGE[storage], EVAL_VARIANT[variant], _p(q), q.shape[0], _p(r),
+                                                            r.shape[0], q.shape[1], batch, _p(out)))
+        return out
     if storage != "f32":
         if arithmetic != "scalar":
             raise HnswError(N.ERR_ARG, "half-precision rows are read in the scalar arithmetic only")

@@ -1397,14 +1397,14 @@ extern "C++" {
 namespace hnswgpu {
 __attribute__((weak)) int eval_distance_matrix_storage_device(int, int, const float*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, float*,
                                                               std::string&);
+__attribute__((weak)) int eval_distance_matrix_variant_device(int, int, int, const float*, uint64_t, const float*, uint64_t, uint64_t, uint32_t,
+                                                              float*, std::string&);
 }  // namespace hnswgpu
 }  // extern "C++"
-int hnswgpu_eval_distance_matrix_storage(int dist, int storage, const float* queries, uint64_t nq, const float* rows, uint64_t n,
-                                         uint64_t d, uint32_t batch, float* out) {
-    CAPI_GUARD_BEGIN
-    if (!queries || !rows || !out || dist < 0 || dist >= DIST_COUNT) return fail(HNSWGPU_ERR_ARG, "bad argument");
+// the storage of an eval call's rows (the one place these are checked: the device side converts what it is handed)
+static int check_eval_storage(int dist, int storage, const float* rows, uint64_t n, uint64_t d) {
     if (storage != HNSWGPU_STORAGE_F32 && storage != HNSWGPU_STORAGE_F16) return fail(HNSWGPU_ERR_ARG, "unknown storage");
-    if (storage == HNSWGPU_STORAGE_F16) {  // (the one place these two are checked: the device side converts what it is handed)
+    if (storage == HNSWGPU_STORAGE_F16) {
         if (dist != DIST_L2 && dist != DIST_COSINE && dist != DIST_DOT && dist != DIST_L1)
             return fail(HNSWGPU_ERR_ARG, "HNSWGPU_STORAGE_F16 serves DistL2, DistCosine, DistDot and DistL1 only");
         uint64_t first = 0;
@@ -1413,9 +1413,36 @@ int hnswgpu_eval_distance_matrix_storage(int dist, int storage, const float* que
             return fail(HNSWGPU_ERR_ARG, std::to_string(bad) + " row elements are not representable as binary16; the first is element " +
                                          std::to_string(first % d) + " of row " + std::to_string(first / d));
     }
+    return HNSWGPU_OK;
+}
+int hnswgpu_eval_distance_matrix_storage(int dist, int storage, const float* queries, uint64_t nq, const float* rows, uint64_t n,
+                                         uint64_t d, uint32_t batch, float* out) {
+    CAPI_GUARD_BEGIN
+    if (!queries || !rows || !out || dist < 0 || dist >= DIST_COUNT) return fail(HNSWGPU_ERR_ARG, "bad argument");
+    if (const int rc = check_eval_storage(dist, storage, rows, n, d)) return rc;
     if (!hnswgpu::eval_distance_matrix_storage_device) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     std::string err;
     return finish(hnswgpu::eval_distance_matrix_storage_device(dist, storage, queries, nq, rows, n, d, batch, out, err), err);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+int hnswgpu_eval_distance_matrix_variant(int dist, int storage, int variant, const float* queries, uint64_t nq, const float* rows,
+                                         uint64_t n, uint64_t d, uint32_t batch, float* out) {
+    CAPI_GUARD_BEGIN
+    if (!queries || !rows || !out || dist < 0 || dist >= DIST_COUNT) return fail(HNSWGPU_ERR_ARG, "bad argument");
+    // a variant names a row loop some search kernel compiles; a combination none has is refused, never served by the plain routine
+    if ((variant & ~(HNSWGPU_EVAL_DEEP | HNSWGPU_EVAL_PIPE | HNSWGPU_EVAL_R128)) != 0)
+        return fail(HNSWGPU_ERR_ARG, "unknown variant bits: HNSWGPU_EVAL_DEEP, HNSWGPU_EVAL_PIPE and HNSWGPU_EVAL_R128 are defined");
+    if ((variant & HNSWGPU_EVAL_DEEP) != 0 && (variant & HNSWGPU_EVAL_PIPE) != 0)
+        return fail(HNSWGPU_ERR_ARG, "HNSWGPU_EVAL_DEEP with HNSWGPU_EVAL_PIPE: no search kernel has both");
+    if ((variant & HNSWGPU_EVAL_R128) != 0) {
+        if ((variant & HNSWGPU_EVAL_PIPE) != 0) return fail(HNSWGPU_ERR_ARG, "HNSWGPU_EVAL_R128 with HNSWGPU_EVAL_PIPE: no search kernel has both");
+        if (dist != DIST_L2 || storage != HNSWGPU_STORAGE_F32 || d < 97 || d > 128)
+            return fail(HNSWGPU_ERR_ARG, "HNSWGPU_EVAL_R128 serves DistL2 on HNSWGPU_STORAGE_F32 rows of 97 .. 128 elements only");
+    }
+    if (const int rc = check_eval_storage(dist, storage, rows, n, d)) return rc;
+    if (!hnswgpu::eval_distance_matrix_variant_device) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    std::string err;
+    return finish(hnswgpu::eval_distance_matrix_variant_device(dist, storage, variant, queries, nq, rows, n, d, batch, out, err), err);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 

@@ -1727,7 +1727,7 @@ std::unique_ptr<BuildSearchBackend> make_device_build_backend(int device) {
 
 namespace {
 int eval_distance_matrix_impl(int dist, const float* queries, uint64_t nq, const float* rows, uint64_t n, uint64_t d,
-                              uint32_t nf, bool pairs, float* out, std::string& err, int arithmetic, int storage);
+                              uint32_t nf, bool pairs, float* out, std::string& err, int arithmetic, int storage, int variant = 0);
 }
 int eval_distance_matrix_device(int dist, const float* queries, uint64_t nq, const float* rows, uint64_t n, uint64_t d,
                                 uint32_t nf, bool pairs, float* out, std::string& err, int arithmetic) {
@@ -1737,9 +1737,13 @@ int eval_distance_matrix_storage_device(int dist, int storage, const float* quer
                                         uint32_t nf, float* out, std::string& err) {
     return eval_distance_matrix_impl(dist, queries, nq, rows, n, d, nf, false, out, err, ARITH_SCALAR, storage);
 }
+int eval_distance_matrix_variant_device(int dist, int storage, int variant, const float* queries, uint64_t nq, const float* rows, uint64_t n,
+                                        uint64_t d, uint32_t nf, float* out, std::string& err) {
+    return eval_distance_matrix_impl(dist, queries, nq, rows, n, d, nf, false, out, err, ARITH_SCALAR, storage, variant);
+}
 namespace {
 int eval_distance_matrix_impl(int dist, const float* queries, uint64_t nq, const float* rows, uint64_t n, uint64_t d,
-                              uint32_t nf, bool pairs, float* out, std::string& err, int arithmetic, int storage) {
+                              uint32_t nf, bool pairs, float* out, std::string& err, int arithmetic, int storage, int variant) {
     if (nq == 0 || n == 0) return OK;
     // half rows (eval_distance_matrix_storage_device): scalar arithmetic, one of the four metrics, every element representable --
     // the C ABI's entry has checked all of it
@@ -1749,6 +1753,13 @@ int eval_distance_matrix_impl(int dist, const float* queries, uint64_t nq, const
     if (arithmetic == ARITH_SIMD8) {
         km = simd8_kernel_metric(dist);
         if (km < 0) { err = "this distance has no SIMD-order variant"; return ERR_ARG; }
+    }
+    // a variant of the row loop (eval_distance_matrix_variant_device): matrix mode, scalar arithmetic, a kernel that exists, and
+    // for the fixed stride rows of exactly that stride -- the C ABI's entry has checked it; never the plain routine in its place
+    if (variant != 0 && (pairs || arithmetic != ARITH_SCALAR || !eval_variant_built(km, variant) ||
+                         ((variant & EVAL_R128) != 0 && (d < 97 || d > 128)))) {
+        err = "no distance routine of this variant for this metric, storage and dimension";
+        return ERR_ARG;
     }
     if (!pairs && (nf < 1 || nf > 64)) { err = "nf must be in 1..64"; return ERR_ARG; }
     if (pairs && nq != n) { err = "pair mode needs as many queries as rows"; return ERR_ARG; }
@@ -1790,11 +1801,11 @@ int eval_distance_matrix_impl(int dist, const float* queries, uint64_t nq, const
             const uint32_t cnt = (uint32_t)std::min<uint64_t>(32768, n - q0);
             const float* rows_q0 = reinterpret_cast<const float*>(dr.as<unsigned char>() + q0 * rs * elem);
             HIP_TRY(kernel_set(km).launch_eval_matrix(nullptr, dq.as<float>() + q0 * rs, cnt, rows_q0, cnt,
-                                                      dn.p ? dn.as<double>() + q0 : nullptr, dout.as<float>() + q0, rs, (uint32_t)d, 1, true));
+                                                      dn.p ? dn.as<double>() + q0 : nullptr, dout.as<float>() + q0, rs, (uint32_t)d, 1, true, 0));
         }
     } else {
         HIP_TRY(kernel_set(km).launch_eval_matrix(nullptr, dq.as<float>(), (uint32_t)nq, dr.as<float>(), (uint32_t)n, dn.as<double>(),
-                                                  dout.as<float>(), rs, (uint32_t)d, nf, false));
+                                                  dout.as<float>(), rs, (uint32_t)d, nf, false, variant));
     }
     HIP_TRY(hipMemcpy(out, dout.p, n_out * sizeof(float), hipMemcpyDeviceToHost));
     return OK;

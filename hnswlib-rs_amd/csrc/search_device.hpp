@@ -299,6 +299,10 @@ int eval_distance_matrix_device(int dist, const float* queries, uint64_t nq, con
                                 uint32_t nf, bool pairs, float* out, std::string& err, int arithmetic = 0);
 int eval_distance_matrix_storage_device(int dist, int storage, const float* queries, uint64_t nq, const float* rows, uint64_t n, uint64_t d,
                                         uint32_t nf, float* out, std::string& err);
+// the same through one of the row loops that only the search kernel's expansion loop compiles (variant: EVAL_* of
+// search_kernels.hpp, a combination that exists -- else ERR_ARG, never the plain routine); referred to weakly by capi.cpp too
+int eval_distance_matrix_variant_device(int dist, int storage, int variant, const float* queries, uint64_t nq, const float* rows, uint64_t n,
+                                        uint64_t d, uint32_t nf, float* out, std::string& err);
 
 // The lane lab (search_kernels.hpp, lane_lab.inc): runs a script of wave-level operations of the search kernels on `device`
 // (host buffers in, host buffer out; out[0] = words produced).  Test entry.

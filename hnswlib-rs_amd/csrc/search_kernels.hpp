@@ -44,6 +44,20 @@ constexpr int f16_base_metric(int km) {  // the Dist id whose arithmetic a half-
     return km == KM_L2_F16 ? DIST_L2 : km == KM_COSINE_F16 ? DIST_COSINE : km == KM_DOT_F16 ? DIST_DOT : DIST_L1;
 }
 
+// The row loops of the distance routine that only the search kernel's expansion loop compiles, for the arithmetic test kernel
+// (eval_matrix_kernel; a bit set, the values of HNSWGPU_EVAL_* in the C header):
+//   EVAL_DEEP  batch_dist<DEEP>: what a strict search with 1 or 2 result slots per lane (ef <= 128) runs
+//   EVAL_PIPE  batch_dist<PIPE>: what a strict search with 4 result slots per lane (ef 129 .. 256) runs
+//   EVAL_R128  batch_dist<RS = 128>: the SHAPE_R128_EF kernels (lean); with EVAL_DEEP, their strict form
+// Built for the scalar metrics and the half-storage ones (DEEP, PIPE) and for DistL2 on f32 rows (R128), as the search kernels are.
+constexpr int EVAL_DEEP = 1, EVAL_PIPE = 2, EVAL_R128 = 4;
+inline bool eval_variant_built(int kernel_metric, int variant) {
+    if (variant == 0) return true;
+    if (kernel_metric >= KM_SIMD8_FIRST && kernel_metric < KM_F16_FIRST) return false;  // group_dist_simd8 has no variants
+    if (variant == EVAL_DEEP || variant == EVAL_PIPE) return true;
+    return (variant == EVAL_R128 || variant == (EVAL_DEEP | EVAL_R128)) && kernel_metric == DIST_L2;
+}
+
 constexpr uint32_t IDS_BYTES = 64 * 4;  // LDS: the compacted ids of one batch of neighbours
 
 typedef unsigned long long hent_t;  // heap / log entry: {key f32 (high), id u32 (low)}
@@ -215,9 +229,10 @@ struct KernelSet {
     hipError_t (*descend_occupancy)(size_t lds, bool pair, int* per_cu);
     hipError_t (*launch_order)(hipStream_t stream, const PreDescent* pre, uint32_t n, uint32_t* order);
     // arithmetic tests: out[q][r] = dist(queries[q], rows[r]) through batch_dist, rows in batches of nf; or, pairs:
-    // out[q] = dist(queries[q], rows[q])
+    // out[q] = dist(queries[q], rows[q]).  variant: 0, or EVAL_* where eval_variant_built() (else hipErrorInvalidDeviceFunction:
+    // never the plain routine in a variant's place); EVAL_R128 needs row_stride == 128
     hipError_t (*launch_eval_matrix)(hipStream_t stream, const float* queries, uint32_t nq, const float* rows, uint32_t n_rows,
-                                     const double* nrm2, float* out, uint32_t row_stride, uint32_t d, uint32_t nf, bool pairs);
+                                     const double* nrm2, float* out, uint32_t row_stride, uint32_t d, uint32_t nf, bool pairs, int variant);
     // construction: the searches of insert_slice for a window of points (hnsw_build_search_kernel)
     hipError_t (*launch_build_search)(int slots, uint32_t grid, size_t lds, hipStream_t stream, const BuildArgs& a);
     hipError_t (*build_occupancy)(int slots, size_t lds, int* per_cu);

@@ -3064,7 +3064,9 @@ __global__ void filter_group_kernel(const uint32_t* __restrict__ filter_of, uint
 // Distance<f32>::eval through the search's own routine (batch_dist: lane groups, DPP chain, G = 4 and G = 2 branches).
 // Matrix mode: out[q][r] = dist(queries[q], rows[r]), one workgroup per (query, batch of `nf` consecutive rows).
 // Pair mode (pairs != 0): out[q] = dist(queries[q0 + q], rows[q0 + q]), one workgroup per pair.  Arithmetic tests.
-template <int METRIC>
+// DEEP / PIPE / RS: batch_dist's own template arguments, handed on -- the row loops the expansion loop of hnsw_search_kernel
+// compiles (EVAL_* in search_kernels.hpp says which kernels); RS != 0 needs row_stride == RS (the host side checks it).
+template <int METRIC, bool DEEP = false, bool PIPE = false, int RS = 0>
 __global__ __launch_bounds__(64) void eval_matrix_kernel(const float* __restrict__ queries, const float* __restrict__ rows,
                                                          const double* __restrict__ nrm2, float* __restrict__ out, uint32_t n_rows,
                                                          uint32_t row_stride, uint32_t nf, uint32_t tile_bytes, uint32_t pairs, uint32_t d) {
@@ -3078,7 +3080,7 @@ __global__ __launch_bounds__(64) void eval_matrix_kernel(const float* __restrict
     stage_query<METRIC>(tile, queries + (size_t)q * row_stride, row_stride, lane, d);
     if ((uint32_t)lane < cnt) ids_lds[lane] = r0 + (uint32_t)lane;
     __syncthreads();
-    const float v = batch_dist<METRIC>(rows, row_stride, d, (nrm_ptr_t)nrm2, tile, ids_lds, cnt, lane);
+    const float v = batch_dist<METRIC, DEEP, PIPE, RS>(rows, row_stride, d, (nrm_ptr_t)nrm2, tile, ids_lds, cnt, lane, NoOverlap());
     if ((uint32_t)lane < cnt) out[pairs ? (size_t)q : (size_t)q * n_rows + r0 + (uint32_t)lane] = v;
 }
 

@@ -132,9 +132,21 @@ hipError_t launch_order(hipStream_t stream, const PreDescent* pre, uint32_t n, u
     return hipGetLastError();
 }
 hipError_t launch_eval_matrix(hipStream_t stream, const float* queries, uint32_t nq, const float* rows, uint32_t n_rows,
-                              const double* nrm2, float* out, uint32_t row_stride, uint32_t d, uint32_t nf, bool pairs) {
+                              const double* nrm2, float* out, uint32_t row_stride, uint32_t d, uint32_t nf, bool pairs, int variant) {
+    using EvalFn = void (*)(const float*, const float*, const double*, float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t);
+    EvalFn fn = nullptr;
+    if (variant == 0) fn = eval_matrix_kernel<M>;
+#if HNSW_THIS_METRIC < 7 || HNSW_THIS_METRIC >= 11  // (eval_variant_built: the SIMD-order routine has no variants)
+    else if (variant == EVAL_DEEP) fn = eval_matrix_kernel<M, true, false, 0>;
+    else if (variant == EVAL_PIPE) fn = eval_matrix_kernel<M, false, true, 0>;
+#endif
+#if HNSW_THIS_METRIC == 0  // DistL2 on f32 rows, as shape_r128_ef_built
+    else if (variant == EVAL_R128 && row_stride == 128u) fn = eval_matrix_kernel<M, false, false, 128>;
+    else if (variant == (EVAL_DEEP | EVAL_R128) && row_stride == 128u) fn = eval_matrix_kernel<M, true, false, 128>;
+#endif
+    if (fn == nullptr) return hipErrorInvalidDeviceFunction;
     const uint32_t tile_bytes = tile_bytes_for(M, row_stride);
-    hipLaunchKernelGGL(eval_matrix_kernel<M>, dim3(pairs ? 1u : (n_rows + nf - 1) / nf, nq), dim3(64), tile_bytes + IDS_BYTES, stream,
+    hipLaunchKernelGGL(fn, dim3(pairs ? 1u : (n_rows + nf - 1) / nf, nq), dim3(64), tile_bytes + IDS_BYTES, stream,
                        queries, rows, nrm2, out, n_rows, row_stride, nf, tile_bytes, pairs ? 1u : 0u, d);
     return hipGetLastError();
 }

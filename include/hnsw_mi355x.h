@@ -390,6 +390,21 @@ int hnswgpu_eval_distance_matrix_arith(int dist, int arithmetic, const float* qu
  * kernel reads them, as a replica's are -- every element of rows must be representable, else HNSWGPU_ERR_ARG                      */
 int hnswgpu_eval_distance_matrix_storage(int dist, int storage, const float* queries, uint64_t nq, const float* rows,
                                          uint64_t n, uint64_t d, uint32_t batch, float* out);
+/* the same through one of the row loops of the distance routine that only the search kernel's expansion loop compiles -- the same
+ * left-to-right sum, so the same bits -- `variant` a bit set:
+ *   HNSWGPU_EVAL_DEEP  sixteen row loads per lane at two lanes per row: a strict search with ef <= 128
+ *   HNSWGPU_EVAL_PIPE  two register sets that take turns, the next round's loads ahead of this round's chain: a strict search with
+ *                      ef 129 .. 256
+ *   HNSWGPU_EVAL_R128  the row stride 128 as a compile-time fact: a search of ef 64 or 128 on DistL2 / F32 rows of 97 .. 128
+ *                      elements, lean; with HNSWGPU_EVAL_DEEP its strict form
+ * 0 is hnswgpu_eval_distance_matrix_storage.  DEEP and PIPE exist for the seven distances on F32 rows and the four of F16 rows.
+ * HNSWGPU_ERR_ARG, never the plain routine in a variant's place: DEEP with PIPE; R128 with PIPE; R128 with another distance,
+ * storage or dimension; unknown bits; and what hnswgpu_eval_distance_matrix_storage refuses.                                      */
+#define HNSWGPU_EVAL_DEEP 1
+#define HNSWGPU_EVAL_PIPE 2
+#define HNSWGPU_EVAL_R128 4
+int hnswgpu_eval_distance_matrix_variant(int dist, int storage, int variant, const float* queries, uint64_t nq, const float* rows,
+                                         uint64_t n, uint64_t d, uint32_t batch, float* out);
 
 /* ---------------------------------------------------------------- exact k-NN ---------- */
 /* Exhaustive exact k-NN over EVERY point of the index (all layers), on the device: the ground truth a recall measurement

@@ -321,6 +321,66 @@ def test_eval_hook_refuses_what_a_half_cannot_hold(native):
     assert native.lib().hnswgpu_eval_distance_matrix_storage(N.DIST["DistL2"], 3, _p(q), 2, _p(good), 4, 8, 4, _p(out)) == N.ERR_ARG
 
 
+R128_ONLY = "HNSWGPU_EVAL_R128 serves DistL2 on HNSWGPU_STORAGE_F32 rows of 97 .. 128 elements only"
+VARIANT_REFUSALS = [  # dist, storage, variant bits, d, the complete message
+    ("DistL2", 0, 1 | 2, 128, "HNSWGPU_EVAL_DEEP with HNSWGPU_EVAL_PIPE: no search kernel has both"),
+    ("DistL2", 0, 1 | 2 | 4, 128, "HNSWGPU_EVAL_DEEP with HNSWGPU_EVAL_PIPE: no search kernel has both"),
+    ("DistL2", 0, 2 | 4, 128, "HNSWGPU_EVAL_R128 with HNSWGPU_EVAL_PIPE: no search kernel has both"),
+    ("DistL2", 0, 8, 128, "unknown variant bits: HNSWGPU_EVAL_DEEP, HNSWGPU_EVAL_PIPE and HNSWGPU_EVAL_R128 are defined"),
+    ("DistL2", 0, 8 | 1, 128, "unknown variant bits: HNSWGPU_EVAL_DEEP, HNSWGPU_EVAL_PIPE and HNSWGPU_EVAL_R128 are defined"),
+    ("DistL2", 0, -1, 128, "unknown variant bits: HNSWGPU_EVAL_DEEP, HNSWGPU_EVAL_PIPE and HNSWGPU_EVAL_R128 are defined"),
+    ("DistL2", 0, 4, 96, R128_ONLY),
+    ("DistL2", 0, 4, 129, R128_ONLY),
+    ("DistL2", 0, 4 | 1, 96, R128_ONLY),
+    ("DistL2", 1, 4, 128, R128_ONLY),
+    ("DistL1", 0, 4, 128, R128_ONLY),
+    ("DistCosine", 0, 4 | 1, 100, R128_ONLY),
+    ("DistL2", 3, 1, 128, "unknown storage"),
+    ("DistHellinger", 1, 2, 128, "HNSWGPU_STORAGE_F16 serves DistL2, DistCosine, DistDot and DistL1 only"),
+]
+
+
+@pytest.mark.parametrize("dist, storage, variant, d, msg", VARIANT_REFUSALS)
+def test_eval_variant_refusals(native, dist, storage, variant, d, msg):
+    """hnswgpu_eval_distance_matrix_variant: the combinations no search kernel has are HNSWGPU_ERR_ARG with their message -- checked in
+    front of the device, so without one too -- and the output is not touched: never the plain routine in a variant's place"""
+    N = _N()
+    q = np.ones((2, d), np.float32)
+    rows = _api().round_to_f16(np.random.default_rng(3).random((4, d), dtype=np.float32))
+    out = np.full((2, 4), np.float32(-7.0))
+    rc = native.lib().hnswgpu_eval_distance_matrix_variant(N.DIST[dist], storage, variant, _p(q), 2, _p(rows), 4, d, 4, _p(out))
+    assert rc == N.ERR_ARG and N.last_error() == msg
+    assert np.all(out == np.float32(-7.0))
+
+
+def test_eval_variant_argument_checks_and_python_names(native):
+    N, A = _N(), _api()
+    assert A.EVAL_VARIANT == {"plain": 0, "deep": 1, "pipe": 2, "r128": 4, "deep+r128": 5}
+    assert (N.HEADER.constants["HNSWGPU_EVAL_DEEP"], N.HEADER.constants["HNSWGPU_EVAL_PIPE"], N.HEADER.constants["HNSWGPU_EVAL_R128"]) == (1, 2, 4)
+    q, rows, out = np.ones((2, 128), np.float32), np.ones((4, 128), np.float32), np.zeros((2, 4), np.float32)
+    call = native.lib().hnswgpu_eval_distance_matrix_variant
+    for args in ((None, 2, _p(rows), 4, 128, 4, _p(out)), (_p(q), 2, None, 4, 128, 4, _p(out)), (_p(q), 2, _p(rows), 4, 128, 4, None)):
+        assert call(N.DIST["DistL2"], 0, 1, *args) == N.ERR_ARG and N.last_error() == "bad argument"
+    assert call(7, 0, 1, _p(q), 2, _p(rows), 4, 128, 4, _p(out)) == N.ERR_ARG
+    # the half-storage scan runs for a variant as it does without one
+    rows[2, 3] = np.float32(0.1)
+    with pytest.raises(native.HnswError) as e:
+        native.eval_distance_matrix("DistL2", q, rows, 4, storage="f16", variant="pipe")
+    assert e.value.code == N.ERR_ARG and "element 3 of row 2" in str(e.value)
+    # the Python wrapper: scalar arithmetic only, the names of the table only
+    with pytest.raises(native.HnswError) as e:
+        native.eval_distance_matrix("DistL2", q, np.ones((4, 128), np.float32), 4, arithmetic="simd8", variant="deep")
+    assert e.value.code == N.ERR_ARG
+    with pytest.raises(KeyError):
+        native.eval_distance_matrix("DistL2", q, np.ones((4, 128), np.float32), 4, variant="deep+pipe")
+    # a well-formed variant call gets as far as the device: with none it answers "no device", it does not compute on the host
+    if native.lib().hnswgpu_device_count() == 0:
+        for variant in ("deep", "pipe", "r128", "deep+r128"):
+            with pytest.raises(native.HnswError) as e:
+                native.eval_distance_matrix("DistL2", q, np.ones((4, 128), np.float32), 4, variant=variant)
+            assert e.value.code == N.ERR_DEVICE
+
+
 def test_file_dump_of_an_f16_index_is_the_f32_dump(native, tmp_path):
     X, h = _built(native, "DistCosine", n=80, d=9)
     h.file_dump(tmp_path, "a32")
