@@ -154,6 +154,40 @@ class GraphCsrResult:
         return out
 
 
+class ComponentsResult:
+    """The connected components of a graph (Hnsw.knn_graph_components, csr_components): labels[v] is the component of vertex v,
+    components numbered 0 .. n_components - 1 by their smallest vertex, ascending; sizes[c] is the number of vertices of c."""
+
+    def __init__(self, labels, sizes, n_components):
+        self.labels, self.sizes, self.n_components = labels, sizes, n_components
+
+
+def _cut(max_dist):
+    """the one f32 behind the max_dist pointer (the caller keeps it alive over the call), or None"""
+    return None if max_dist is None else np.array([max_dist], np.float32)
+
+
+def csr_components(offsets, cols, dists=None, max_dist=None, device=0):
+    """The connected components of ANY graph given in CSR (offsets u64[n + 1], cols u32[offsets[n]]), labelled on `device`: every
+    entry (r, c) joins r and c, whichever row names it, so a directed CSR gets its weakly connected components.  With max_dist an
+    entry counts iff its f32 in dists is <= max_dist (a NaN never is).  Returns a ComponentsResult."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    cols = np.ascontiguousarray(cols, dtype=np.uint32)
+    if dists is not None:
+        dists = np.ascontiguousarray(dists, dtype=np.float32)
+        if len(dists) != len(cols):
+            raise HnswError(N.ERR_ARG, f"dists has {len(dists)} entries, cols has {len(cols)}")
+    if len(offsets) == 0 or int(offsets[-1]) > len(cols):
+        raise HnswError(N.ERR_ARG, "offsets must hold n + 1 entries, the last one at most len(cols)")
+    n = len(offsets) - 1
+    labels, sizes, c = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(1, np.uint64)
+    cut = _cut(max_dist)
+    if dists is not None and len(dists) == 0:
+        dists = np.zeros(1, np.float32)  # (never read: there is no entry)
+    _check(N.lib().hnswgpu_csr_components(device, n, _p(offsets), _p(cols) if len(cols) else None, _p(dists), _p(cut), _p(labels), _p(sizes), _p(c)))
+    return ComponentsResult(labels, sizes[:int(c[0])].copy(), int(c[0]))
+
+
 class Hnsw:
     """Hnsw<f32, D>: owns a hnswgpu_index handle (flat host graph + its HBM replica)."""
 
@@ -606,6 +640,28 @@ class Hnsw:
     def symmetric_knn_graph(self, knbn, ef=None, mode="union"):
         """symmetric_knn_graph_flat as Vec<Vec<Neighbour>>, row i being the point at position i."""
         return self.symmetric_knn_graph_flat(knbn, ef, mode).to_neighbours()
+
+    def knn_graph_components(self, knbn, ef=None, mode="union", max_dist=None):
+        """The connected components of the graph symmetric_knn_graph_flat(knbn, ef, mode) would build, labelled on the device without
+        building it.  Vertices are POSITIONS (the rows of that graph).  With max_dist the directed graph is cut first: an entry i -> j
+        counts iff its stored f32 distance is <= max_dist (a NaN never is); "union" then joins i and j iff either direction is left,
+        "mutual" iff both are.  Returns a ComponentsResult."""
+        modes = {"union": N.HEADER.constants["HNSWGPU_SYM_UNION"], "mutual": N.HEADER.constants["HNSWGPU_SYM_MUTUAL"]}
+        if mode not in modes:
+            raise HnswError(N.ERR_ARG, f"mode must be 'union' or 'mutual', not {mode!r}")
+        if ef is not None and ef < 1:
+            raise HnswError(N.ERR_ARG, "ef must be >= 1 (ef=None: the exact graph)")
+        if max_dist is not None and np.isnan(np.float32(max_dist)):
+            raise HnswError(N.ERR_ARG, "max_dist is NaN")
+        n = self.get_nb_point()
+        labels, sizes, c = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(1, np.uint64)
+        if self._h is None:
+            if knbn < 1:
+                raise HnswError(N.ERR_ARG, "knbn must be > 0")
+            return ComponentsResult(labels, sizes, 0)
+        cut = _cut(max_dist)
+        _check(self._lib.hnswgpu_graph_components(self._h, knbn, 0 if ef is None else ef, modes[mode], _p(cut), _p(labels), _p(sizes), _p(c)))
+        return ComponentsResult(labels, sizes[:int(c[0])].copy(), int(c[0]))
 
     def knn_graph_recall(self, knbn, ef, point_ids=None):
         """The recall by id of knn_graph_flat against exact_knn_graph_flat over the named points: the share of the exact

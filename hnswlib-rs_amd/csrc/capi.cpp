@@ -1199,23 +1199,33 @@ namespace hnswgpu {
 __attribute__((weak)) int symmetric_graph(DeviceIndex*, const std::vector<uint64_t>&, const SymGraphArgs&, bool, void*, std::string&);
 }  // namespace hnswgpu
 }  // extern "C++"
-// the checks both entries share; the handle's lock is held (shared).  What the source call of D refuses is refused here.
-static int symmetric_graph_call(const hnswgpu_index* idx, const SymGraphArgs& a) {
+// The checks of the directed graph D that the symmetrised graph and the components share, in two halves (the symmetrised graph
+// looks at its capacity in between); the handle's lock is held (shared).  What the source call of D refuses is refused here.
+static int directed_graph_shape(uint64_t k, uint32_t mode) {
+    if (k == 0) return fail(HNSWGPU_ERR_ARG, "knbn must be > 0");
+    if (mode != HNSWGPU_SYM_UNION && mode != HNSWGPU_SYM_MUTUAL)
+        return fail(HNSWGPU_ERR_ARG, "unknown mode " + std::to_string(mode) + ": HNSWGPU_SYM_UNION or HNSWGPU_SYM_MUTUAL");
+    return HNSWGPU_OK;
+}
+static int directed_graph_source(const hnswgpu_index* idx, const char* what, uint64_t k, uint64_t ef) {
     const uint64_t n = index_nb_point(idx);
-    if (!a.out_offsets) return fail(HNSWGPU_ERR_ARG, "null out_offsets: the offsets are written by every call");
-    if (a.k == 0) return fail(HNSWGPU_ERR_ARG, "knbn must be > 0");
-    if (a.mode != HNSWGPU_SYM_UNION && a.mode != HNSWGPU_SYM_MUTUAL)
-        return fail(HNSWGPU_ERR_ARG, "unknown mode " + std::to_string(a.mode) + ": HNSWGPU_SYM_UNION or HNSWGPU_SYM_MUTUAL");
-    if (a.cap != 0 && (!a.out_pos || !a.out_dists))
-        return fail(HNSWGPU_ERR_ARG, "cap > 0 with null out_pos or out_dists (the count-only call is cap == 0)");
-    if (n != 0 && a.k > (1ull << 30) / n)
-        return fail(HNSWGPU_ERR_ARG, "symmetric graph: nb_point x knbn = " + std::to_string(n) + " x " + std::to_string(a.k) +
-                                         (a.k <= ~0ull / n ? " = " + std::to_string(n * a.k) : std::string()) + " slots, above 2^30 = 1073741824");
-    if (a.ef != 0) return capi_refuse_f16(idx, "the graph search (its gather kernel copies stored rows)");
-    if (a.k > 4096) return fail(HNSWGPU_ERR_ARG, "exact graph: knbn above 4096");
+    if (n != 0 && k > (1ull << 30) / n)
+        return fail(HNSWGPU_ERR_ARG, std::string(what) + ": nb_point x knbn = " + std::to_string(n) + " x " + std::to_string(k) +
+                                         (k <= ~0ull / n ? " = " + std::to_string(n * k) : std::string()) + " slots, above 2^30 = 1073741824");
+    if (ef != 0) return capi_refuse_f16(idx, "the graph search (its gather kernel copies stored rows)");
+    if (k > 4096) return fail(HNSWGPU_ERR_ARG, "exact graph: knbn above 4096");
     if (idx->arithmetic != HNSWGPU_ARITH_SCALAR)
         return fail(HNSWGPU_ERR_ARG, "exact graph answers in the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
     return capi_refuse_f16(idx, "exact graph");
+}
+// the checks both entries share
+static int symmetric_graph_call(const hnswgpu_index* idx, const SymGraphArgs& a) {
+    if (!a.out_offsets) return fail(HNSWGPU_ERR_ARG, "null out_offsets: the offsets are written by every call");
+    const int rc = directed_graph_shape(a.k, a.mode);
+    if (rc != HNSWGPU_OK) return rc;
+    if (a.cap != 0 && (!a.out_pos || !a.out_dists))
+        return fail(HNSWGPU_ERR_ARG, "cap > 0 with null out_pos or out_dists (the count-only call is cap == 0)");
+    return directed_graph_source(idx, "symmetric graph", a.k, a.ef);
 }
 
 int hnswgpu_symmetric_graph(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t cap, uint64_t* out_offsets, uint32_t* out_pos,
@@ -1259,6 +1269,127 @@ int hnswgpu_symmetric_graph_device(const hnswgpu_index* cidx, uint64_t k, uint64
     rc = resident_replica(idx, true, &dev);
     if (rc != HNSWGPU_OK) return rc;
     return finish(hnswgpu::symmetric_graph(dev, idx->flat->origin_id, a, false, stream, err), err);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+// ---- connected components: of the k-NN graph of the indexed points, and of any CSR (graph_components.hip holds the device side)
+extern "C++" {
+namespace hnswgpu {
+__attribute__((weak)) int graph_components(DeviceIndex&, const std::vector<uint64_t>&, const ComponentsArgs&, bool, void*, std::string&);
+__attribute__((weak)) int csr_components(const CsrComponentsArgs&, bool, void*, std::string&);
+}  // namespace hnswgpu
+}  // extern "C++"
+// what all four entries check of the answer's slots and of the cut (n: the number of vertices)
+static int components_answer_check(uint64_t n, const float* max_dist, const uint32_t* out_label, const uint64_t* out_n_components) {
+    if (!out_n_components) return fail(HNSWGPU_ERR_ARG, "null out_n_components: the number of components is written by every call");
+    if (n != 0 && !out_label) return fail(HNSWGPU_ERR_ARG, "null out_label");
+    if (max_dist && *max_dist != *max_dist) return fail(HNSWGPU_ERR_ARG, "max_dist is NaN: no distance compares to it (NULL is the call without a cut)");
+    return HNSWGPU_OK;
+}
+// the checks both index entries share; the handle's lock is held (shared)
+static int graph_components_call(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, const float* max_dist, const uint32_t* out_label,
+                                 const uint64_t* out_n_components) {
+    int rc = components_answer_check(index_nb_point(idx), max_dist, out_label, out_n_components);
+    if (rc != HNSWGPU_OK) return rc;
+    rc = directed_graph_shape(k, mode);
+    if (rc != HNSWGPU_OK) return rc;
+    return directed_graph_source(idx, "graph components", k, ef);
+}
+
+int hnswgpu_graph_components(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, const float* max_dist, uint32_t* out_label,
+                             uint32_t* out_sizes, uint64_t* out_n_components) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    int rc = graph_components_call(idx, k, ef, mode, max_dist, out_label, out_n_components);
+    if (rc != HNSWGPU_OK) return rc;
+    if (index_empty(idx)) {  // no vertex: no component, nothing else written
+        *out_n_components = 0;
+        return HNSWGPU_OK;
+    }
+    if (!hnswgpu::graph_components) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = primary_f32_replica(idx, sl, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    const ComponentsArgs a{k, ef, mode, max_dist != nullptr, max_dist ? *max_dist : 0.0f, out_label, out_sizes, out_n_components};
+    std::string err;
+    return finish(hnswgpu::graph_components(*dev, idx->flat->origin_id, a, true, nullptr, err), err);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswgpu_graph_components_device(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, const float* max_dist, uint32_t* d_out_label,
+                                    uint32_t* d_out_sizes, uint64_t* out_n_components, void* stream) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    int rc = graph_components_call(idx, k, ef, mode, max_dist, d_out_label, out_n_components);
+    if (rc != HNSWGPU_OK) return rc;
+    if (index_empty(idx)) {
+        *out_n_components = 0;
+        return HNSWGPU_OK;
+    }
+    if (!hnswgpu::graph_components) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = resident_replica(idx, true, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    const ComponentsArgs a{k, ef, mode, max_dist != nullptr, max_dist ? *max_dist : 0.0f, d_out_label, d_out_sizes, out_n_components};
+    std::string err;
+    return finish(hnswgpu::graph_components(*dev, idx->flat->origin_id, a, false, stream, err), err);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+// what both CSR entries can check without reading an array
+static int csr_components_call(uint64_t n, const void* offsets, const void* dists, const float* max_dist, const uint32_t* out_label,
+                               const uint64_t* out_n_components) {
+    const int rc = components_answer_check(n, max_dist, out_label, out_n_components);
+    if (rc != HNSWGPU_OK) return rc;
+    if (n > 0x7FFFFFFFull) return fail(HNSWGPU_ERR_ARG, "csr components: n = " + std::to_string(n) + " vertices, above 2^31 - 1");
+    if (n != 0 && !offsets) return fail(HNSWGPU_ERR_ARG, "null offsets");
+    if (max_dist && !dists) return fail(HNSWGPU_ERR_ARG, "max_dist without dists: a cut needs the entries' distances");
+    return HNSWGPU_OK;
+}
+
+int hnswgpu_csr_components(int device, uint64_t n, const uint64_t* offsets, const uint32_t* cols, const float* dists, const float* max_dist,
+                           uint32_t* out_label, uint32_t* out_sizes, uint64_t* out_n_components) {
+    CAPI_GUARD_BEGIN
+    int rc = csr_components_call(n, offsets, dists, max_dist, out_label, out_n_components);
+    if (rc != HNSWGPU_OK) return rc;
+    if (n == 0) {
+        *out_n_components = 0;
+        return HNSWGPU_OK;
+    }
+    // the graph itself, as the device form's validation kernels check it
+    if (offsets[0] != 0) return fail(HNSWGPU_ERR_ARG, "csr components: offsets[0] is not 0");
+    for (uint64_t r = 0; r < n; ++r)
+        if (offsets[r] > offsets[r + 1]) return fail(HNSWGPU_ERR_ARG, "csr components: the offsets descend at row " + std::to_string(r));
+    const uint64_t total = offsets[n];
+    if (total >= (1ull << 32)) return fail(HNSWGPU_ERR_ARG, "csr components: offsets[n] = " + std::to_string(total) + " is 2^32 or more");
+    if (total != 0 && !cols) return fail(HNSWGPU_ERR_ARG, "csr components: null cols with entries");
+    for (uint64_t e = 0; e < total; ++e)
+        if (cols[e] >= n) return fail(HNSWGPU_ERR_ARG, "csr components: col " + std::to_string(cols[e]) + " at entry " + std::to_string(e) + " is not below n");
+    if (!hnswgpu::csr_components) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    const CsrComponentsArgs a{device, n, offsets, cols, dists, max_dist != nullptr, max_dist ? *max_dist : 0.0f, out_label, out_sizes, out_n_components};
+    std::string err;
+    return finish(hnswgpu::csr_components(a, true, nullptr, err), err);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswgpu_csr_components_device(int device, uint64_t n, const uint64_t* d_offsets, const uint32_t* d_cols, const float* d_dists, const float* max_dist,
+                                  uint32_t* d_out_label, uint32_t* d_out_sizes, uint64_t* out_n_components, void* stream) {
+    CAPI_GUARD_BEGIN
+    const int rc = csr_components_call(n, d_offsets, d_dists, max_dist, d_out_label, out_n_components);
+    if (rc != HNSWGPU_OK) return rc;
+    if (n == 0) {
+        *out_n_components = 0;
+        return HNSWGPU_OK;
+    }
+    if (!hnswgpu::csr_components) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    const CsrComponentsArgs a{device, n, d_offsets, d_cols, d_dists, max_dist != nullptr, max_dist ? *max_dist : 0.0f, d_out_label, d_out_sizes,
+                              out_n_components};
+    std::string err;
+    return finish(hnswgpu::csr_components(a, false, stream, err), err);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 

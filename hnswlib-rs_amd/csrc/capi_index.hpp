@@ -1,5 +1,5 @@
 // capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h, for the translation units
-// that implement entry points of the C ABI (capi.cpp; exact_knn.hip; range_search.hip; symmetric_graph.hip).  Private: not installed, not part of the ABI.
+// that implement entry points of the C ABI (capi.cpp; exact_knn.hip; range_search.hip; symmetric_graph.hip; graph_components.hip).  Private: not installed, not part of the ABI.
 // The checks that entries share (empty index, resident replica, sorted filter, the shape and contents of a filter set, the limits of
 // an exact call, the zeroed k-NN answer, the tail) live once, in capi.cpp; what an entry outside capi.cpp needs of them is declared
 // below as capi_*.  A new pair of entries calls them.  The HIP host helpers of the .hip units (HIP_TRY, DeviceGuard, DevMem,
@@ -142,6 +142,33 @@ struct SymGraphArgs {
     int32_t* out_rank;      // may be nullptr
 };
 int symmetric_graph(DeviceIndex* dev, const std::vector<uint64_t>& origin_id, const SymGraphArgs& a, bool host, void* stream, std::string& err);
+// the device side of hnswgpu_graph_components(_device) and hnswgpu_csr_components(_device), defined in graph_components.hip and
+// referred to weakly in the same way (the arguments have been checked; at least one vertex).  host: the arrays are plain host memory;
+// else device memory and `stream` is the caller's.  out_n is host memory either way.  csr_components returns ERR_ARG, no out slot
+// written, when its validation kernels refuse the graph.
+struct ComponentsArgs {
+    uint64_t k, ef;
+    uint32_t mode;        // HNSWGPU_SYM_*
+    bool has_cut;
+    float max_dist;
+    uint32_t* out_label;  // [n]
+    uint32_t* out_sizes;  // [n], may be nullptr
+    uint64_t* out_n;
+};
+int graph_components(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ComponentsArgs& a, bool host, void* stream, std::string& err);
+struct CsrComponentsArgs {
+    int device;
+    uint64_t n;
+    const uint64_t* offsets;  // [n + 1]
+    const uint32_t* cols;     // [offsets[n]]
+    const float* dists;       // [offsets[n]], read only under a cut
+    bool has_cut;
+    float max_dist;
+    uint32_t* out_label;
+    uint32_t* out_sizes;
+    uint64_t* out_n;
+};
+int csr_components(const CsrComponentsArgs& a, bool host, void* stream, std::string& err);
 }  // namespace hnswgpu
 
 // No C++ exception may cross the C ABI: every entry point is `try { ... HNSWGPU_CAPI_GUARD_END(ret)`

@@ -1,0 +1,339 @@
+// graph_components.hip -- connected components on the device (gfx950 only): the device side of hnswgpu_graph_components(_device)
+// and hnswgpu_csr_components(_device) of include/hnsw_mi355x.h (the entries and every check that needs no device are in capi.cpp).
+// DESIGN.md "Connected components".
+//
+// A lock-free union-find over u32 parents (ECL-CC: Jaiganesh & Burtscher, HPDC 2018), one thread per ENTRY of the graph:
+//   cc_check_offsets_kernel  (CSR) one thread per row: offsets[0] == 0, no descent, offsets[n] < 2^32 -- flags and the total in one word
+//   cc_check_cols_kernel     (CSR) a fixed grid strides over the offsets[n] cols: every col < n.  The word is read back BEFORE any
+//                            kernel below runs: no kernel follows a col that was not checked.
+//   cc_init_kernel           parent[v] = v
+//   cc_hook_csr_kernel       one thread per entry e: its row by a binary search in the offsets, the cut, unite(row, col)
+//   cc_hook_slots_kernel     (index, UNION) one thread per slot of D: the neighbour's position through the rank array as in
+//                            sym_expand_kernel, the cut, unite(i, j).  No sort: every surviving slot is an edge.
+//   cc_hook_records_kernel   (index, MUTUAL) one thread per sorted edge record of symmetric_graph.hip: a forward record (i, j) whose
+//                            successor is the reverse record (i, j) is a pair named both ways; the two records carry d(i->j) and
+//                            d(j->i), the cut looks at both, unite(i, j)
+//   cc_compress_kernel       one thread per vertex: parent[v] = its root; mark[v] = (v is a root)
+//   (rocPRIM)                an exclusive scan of the marks: a root's dense number in ascending root order, and the count c
+//   cc_label_kernel          one thread per vertex: label[v] = number of parent[v]; sizes[label] += 1 (integer atomics, one per
+//                            wavefront where the wavefront agrees on the label)
+// The invariant behind every loop: parent[v] <= v at all times, and a write to parent[v] only ever lowers it (a compare-and-swap of a
+// root v to a smaller root, an atomic min with an ancestor).  So the links have no cycle, a walk up strictly descends, and a root is
+// the smallest vertex of its tree.  Once the hooks are done the trees are the components whatever the timing was: the answer is a
+// function of the graph alone.  No wavefront waits on another; no kernel walks a row.
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_scan.hpp>
+
+#include <algorithm>
+#include <string>
+
+#include "capi_index.hpp"
+#include "graph_internal.hpp"
+#include "hip_host.hpp"
+#include "hnswio.hpp"
+
+namespace hnswgpu {
+namespace {
+
+// the validation word of the CSR form: the total in the low half, the flags above it
+constexpr uint64_t BAD_FIRST = 1ull << 32, BAD_DESCENT = 1ull << 33, BAD_TOTAL = 1ull << 34, BAD_COL = 1ull << 35, BAD_NO_COLS = 1ull << 36;
+constexpr uint32_t CHECK_BLOCKS = 2048;  // the grid of cc_check_cols_kernel
+
+__device__ __forceinline__ uint32_t parent_of(const uint32_t* parent, uint32_t v) {
+    return __hip_atomic_load(parent + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the root of v's tree as far as this thread sees it, halving the path on the way.  Ends: v takes the value of its parent, which is
+// smaller, until it is its own parent -- at most v steps.
+__device__ __forceinline__ uint32_t cc_find(uint32_t* parent, uint32_t v) {
+    uint32_t p = parent_of(parent, v);
+    while (p != v) {
+        const uint32_t g = parent_of(parent, p);
+        if (g != p) atomicMin(parent + v, g);  // (an ancestor of v, below its parent)
+        v = p;
+        p = g;
+    }
+    return v;
+}
+
+// a and b into one tree: the larger root under the smaller.  Ends: a round that does not hook replaces the larger of (ra, rb) by its
+// parent, which is smaller -- ra + rb falls every round and is never negative.
+__device__ __forceinline__ void cc_unite(uint32_t* parent, uint32_t a, uint32_t b) {
+    uint32_t ra = cc_find(parent, a), rb = cc_find(parent, b);
+    while (ra != rb) {
+        const uint32_t hi = ra > rb ? ra : rb, lo = ra > rb ? rb : ra;
+        const uint32_t old = atomicCAS(parent + hi, hi, lo);
+        if (old == hi) return;  // hi was a root and hangs under lo now
+        ra = old;               // somebody hooked hi first: old < hi is an ancestor of it
+        rb = lo;
+    }
+}
+
+// d <= cut as an ordered comparison: false for a NaN, -0 equals +0
+__device__ __forceinline__ bool survives(float d, uint32_t has_cut, float cut) { return has_cut == 0u || d <= cut; }
+
+// one thread per r of 0 .. n
+__global__ __launch_bounds__(256) void cc_check_offsets_kernel(const uint64_t* __restrict__ offsets, uint32_t n, unsigned long long* __restrict__ word) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r > n) return;
+    const uint64_t here = offsets[r];
+    unsigned long long bad = 0ull;
+    if (r == 0u && here != 0ull) bad |= BAD_FIRST;
+    if (r < n && here > offsets[r + 1u]) bad |= BAD_DESCENT;
+    if (r == n) bad |= here >= (1ull << 32) ? BAD_TOTAL : here;  // (the total itself, below the flags)
+    if (bad != 0ull) atomicOr(word, bad);
+}
+
+// CHECK_BLOCKS x 256 threads over the offsets[n] cols (the caller's array holds that many, whatever else the offsets say)
+__global__ __launch_bounds__(256) void cc_check_cols_kernel(const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ cols, uint32_t n,
+                                                           unsigned long long* __restrict__ word) {
+    const uint64_t total = offsets[n];
+    if (total >= (1ull << 32) || total == 0ull) return;
+    if (cols == nullptr) {
+        if (blockIdx.x == 0u && threadIdx.x == 0u) atomicOr(word, (unsigned long long)BAD_NO_COLS);
+        return;
+    }
+    bool bad = false;
+    for (uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x; e < total; e += (uint64_t)CHECK_BLOCKS * 256u) bad |= cols[e] >= n;
+    if (bad) atomicOr(word, (unsigned long long)BAD_COL);
+}
+
+__global__ __launch_bounds__(256) void cc_init_kernel(uint32_t* __restrict__ parent, uint32_t n) {
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    if (v < n) parent[v] = v;
+}
+
+// one thread per entry e of a checked CSR: offsets[0] = 0 <= e < total = offsets[n], the offsets ascend, every col < n
+__global__ __launch_bounds__(256) void cc_hook_csr_kernel(const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ cols,
+                                                         const float* __restrict__ dists, uint32_t n, uint32_t total, uint32_t has_cut, float cut,
+                                                         uint32_t* parent) {
+    const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+    if (e >= total) return;
+    if (has_cut != 0u && !(dists[e] <= cut)) return;
+    uint32_t lo = 0u, hi = n;  // offsets[lo] <= e < offsets[hi]; ends: hi - lo halves
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (offsets[mid] <= (uint64_t)e) lo = mid; else hi = mid;
+    }
+    const uint32_t c = cols[e];
+    if (c != lo) cc_unite(parent, lo, c);
+}
+
+// one thread per slot t = i k + s of D
+__global__ __launch_bounds__(256) void cc_hook_slots_kernel(DeviceIndexView ix, const uint32_t* __restrict__ rank_of, const uint8_t* __restrict__ layer,
+                                                           const int32_t* __restrict__ rank, const float* __restrict__ dists,
+                                                           const uint32_t* __restrict__ counts, uint32_t k, uint32_t slots, uint32_t has_cut, float cut,
+                                                           uint32_t* parent) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= slots) return;
+    const uint32_t i = t / k, s = t - i * k;
+    if (s >= counts[i] || !survives(dists[t], has_cut, cut)) return;
+    const uint32_t l = layer[t] < NB_LAYER_MAX ? layer[t] : NB_LAYER_MAX;
+    const uint32_t flat = ix.layer_offset[l] + (uint32_t)rank[t];
+    if (flat >= ix.n) return;  // (a p_id of the index, whatever the slot holds)
+    const uint32_t j = rank_of[flat];
+    if (j < ix.n && j != i) cc_unite(parent, i, j);
+}
+
+// one thread per sorted record: the forward record of a pair that has its reverse record too
+__global__ __launch_bounds__(256) void cc_hook_records_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t records,
+                                                             uint32_t n, uint32_t has_cut, float cut, uint32_t* parent) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t + 1u >= records) return;
+    const uint64_t key = keys[t];
+    const uint32_t row = (uint32_t)(key >> 33), col = (uint32_t)(key >> 1);
+    if (row >= n || col >= n || (key & FLAG_REV) != 0ull || keys[t + 1u] != (key | FLAG_REV)) return;
+    if (!survives(__uint_as_float(vals[t]), has_cut, cut) || !survives(__uint_as_float(vals[t + 1u]), has_cut, cut)) return;
+    if (row != col) cc_unite(parent, row, col);
+}
+
+// one thread per vertex.  Roots stay roots here: nothing hooks any more.
+__global__ __launch_bounds__(256) void cc_compress_kernel(uint32_t* parent, uint32_t n, uint32_t* __restrict__ mark) {
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    if (v >= n) return;
+    const uint32_t r = cc_find(parent, v);
+    if (r != v) atomicMin(parent + v, r);
+    mark[v] = r == v ? 1u : 0u;
+}
+
+// one thread per vertex; parent[v] is v's root, number_of[r] the dense number of root r
+__global__ __launch_bounds__(256) void cc_label_kernel(const uint32_t* __restrict__ parent, const uint32_t* __restrict__ number_of, uint32_t n,
+                                                      uint32_t* __restrict__ label, uint32_t* __restrict__ sizes) {
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    const bool live = v < n;
+    uint32_t lab = 0u;
+    if (live) {
+        lab = number_of[parent[v]];
+        label[v] = lab;
+    }
+    if (sizes == nullptr) return;
+    // lane 0 of a wavefront holds its smallest v: it is live whenever any lane is
+    const uint32_t first = __builtin_amdgcn_readfirstlane(lab);
+    const uint64_t all = __ballot(live), same = __ballot(live && lab == first);
+    if (same == all) {
+        if ((threadIdx.x & 63u) == 0u && live) atomicAdd(sizes + first, (uint32_t)__popcll(all));
+    } else if (live) {
+        atomicAdd(sizes + lab, 1u);
+    }
+}
+
+dim3 grid_of(uint64_t threads) { return dim3((uint32_t)((threads + 255) / 256)); }
+
+struct Drain {
+    hipStream_t s;
+    ~Drain() { (void)hipStreamSynchronize(s); }
+};
+
+// what every form keeps for the length of a call: parent, mark and the scan of the marks (4 n, 4 n + 4, 4 n + 4 bytes)
+struct Forest {
+    DevMem mem;
+    uint32_t* parent = nullptr;
+    uint32_t* mark = nullptr;
+    uint32_t* number_of = nullptr;
+};
+int forest_init(Forest& f, uint64_t n, hipStream_t stream, std::string& err) {
+    HIP_TRY(hipMalloc(&f.mem.p, 3 * round_up((n + 1) * 4, 256)));
+    unsigned char* p = static_cast<unsigned char*>(f.mem.p);
+    f.parent = reinterpret_cast<uint32_t*>(p); p += round_up((n + 1) * 4, 256);
+    f.mark = reinterpret_cast<uint32_t*>(p); p += round_up((n + 1) * 4, 256);
+    f.number_of = reinterpret_cast<uint32_t*>(p);
+    hipLaunchKernelGGL(cc_init_kernel, grid_of(n), dim3(256), 0, stream, f.parent, (uint32_t)n);
+    HIP_TRY(hipGetLastError());
+    return OK;
+}
+
+// the hooks are on the stream: roots, their numbers, the labels and the sizes.  host: out_label / out_sizes are host memory.
+int forest_answer(Forest& f, uint64_t n, bool host, uint32_t* out_label, uint32_t* out_sizes, uint64_t* out_n, hipStream_t stream, std::string& err) {
+    DevMem m_temp, m_out;
+    HIP_TRY(hipMemsetAsync(f.mark + n, 0, 4, stream));
+    hipLaunchKernelGGL(cc_compress_kernel, grid_of(n), dim3(256), 0, stream, f.parent, (uint32_t)n, f.mark);
+    HIP_TRY(hipGetLastError());
+    size_t temp_bytes = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, f.mark, f.number_of, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), stream));
+    HIP_TRY(hipMalloc(&m_temp.p, std::max<size_t>(temp_bytes, 256)));
+    HIP_TRY(rocprim::exclusive_scan(m_temp.p, temp_bytes, f.mark, f.number_of, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), stream));
+    uint32_t c = 0;
+    HIP_TRY(hipMemcpyAsync(&c, f.number_of + n, 4, hipMemcpyDeviceToHost, stream));  // the read-back of the device entries
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (c == 0 || c > n) {
+        err = "components: " + std::to_string(c) + " roots among " + std::to_string(n) + " vertices";
+        return ERR_FORMAT;
+    }
+    uint32_t* d_label = out_label;
+    uint32_t* d_sizes = out_sizes;
+    if (host) {
+        HIP_TRY(hipMalloc(&m_out.p, round_up(n * 4, 256) + (uint64_t)c * 4));
+        d_label = static_cast<uint32_t*>(m_out.p);
+        d_sizes = out_sizes ? d_label + round_up(n * 4, 256) / 4 : nullptr;
+    }
+    if (d_sizes) HIP_TRY(hipMemsetAsync(d_sizes, 0, (uint64_t)c * 4, stream));
+    hipLaunchKernelGGL(cc_label_kernel, grid_of(n), dim3(256), 0, stream, f.parent, f.number_of, (uint32_t)n, d_label, d_sizes);
+    HIP_TRY(hipGetLastError());
+    if (host) {
+        HIP_TRY(hipMemcpyAsync(out_label, d_label, n * 4, hipMemcpyDeviceToHost, stream));
+        if (out_sizes) HIP_TRY(hipMemcpyAsync(out_sizes, d_sizes, (uint64_t)c * 4, hipMemcpyDeviceToHost, stream));
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    *out_n = c;
+    return OK;
+}
+
+}  // namespace
+
+// Both index entries (capi.cpp refers to it weakly, capi_index.hpp): n >= 1.  Waits for `stream` before it returns.
+int graph_components(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ComponentsArgs& a, bool host, void* stream_v, std::string& err) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    const DeviceIndexView& v = dev.view();
+    DeviceGuard on(dev.device());
+    HIP_TRY(on.status());
+    const uint64_t n = v.n, k = a.k, slots = n * k;  // (n k <= 2^30: checked by the entries)
+    StagedGraph d;
+    SortedRecords rec;
+    Forest f;
+    Drain drain{stream};  // (destroyed first: nothing of this call is running when its memory is freed)
+    GraphOrder ord;
+    int rc = graph_order(dev, origin_id, ord, err);
+    if (rc != OK) return rc;
+    const uint32_t has_cut = a.has_cut ? 1u : 0u;
+    if (a.mode == HNSWGPU_SYM_UNION) {
+        rc = stage_directed_graph(dev, origin_id, k, a.ef, stream_v, d, err);
+        if (rc != OK) return rc;
+        rc = forest_init(f, n, stream, err);
+        if (rc != OK) return rc;
+        hipLaunchKernelGGL(cc_hook_slots_kernel, grid_of(slots), dim3(256), 0, stream, v, ord.d_rank, d.layer, d.rank, d.dists, d.counts, (uint32_t)k,
+                           (uint32_t)slots, has_cut, a.max_dist, f.parent);
+    } else {
+        rc = sorted_edge_records(dev, origin_id, ord, k, a.ef, stream_v, rec, err);
+        if (rc != OK) return rc;
+        rec.keys_a.release();  // (the sort's other half: not needed here)
+        rec.vals_a.release();
+        rc = forest_init(f, n, stream, err);
+        if (rc != OK) return rc;
+        hipLaunchKernelGGL(cc_hook_records_kernel, grid_of(rec.records), dim3(256), 0, stream, static_cast<const uint64_t*>(rec.keys_b.p),
+                           static_cast<const uint32_t*>(rec.vals_b.p), (uint32_t)rec.records, (uint32_t)n, has_cut, a.max_dist, f.parent);
+    }
+    HIP_TRY(hipGetLastError());
+    return forest_answer(f, n, host, a.out_label, a.out_sizes, a.out_n, stream, err);
+}
+
+// Both CSR entries: 1 <= n < 2^31.  host: every array is host memory and has passed the same checks on the host (capi.cpp).
+int csr_components(const CsrComponentsArgs& a, bool host, void* stream_v, std::string& err) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || a.device < 0 || a.device >= count) {
+        (void)hipGetLastError();
+        err = "csr components: no device " + std::to_string(a.device);
+        return ERR_DEVICE;
+    }
+    DeviceGuard on(a.device);
+    HIP_TRY(on.status());
+    const uint64_t n = a.n;
+    DevMem m_in, m_word;
+    Forest f;
+    Drain drain{stream};
+    const uint64_t* d_offsets = a.offsets;
+    const uint32_t* d_cols = a.cols;
+    const float* d_dists = a.dists;
+    if (host) {
+        const uint64_t total = a.offsets[n];
+        const uint64_t b_offs = round_up((n + 1) * 8, 256), b_cols = round_up(total * 4, 256);
+        HIP_TRY(hipMalloc(&m_in.p, b_offs + b_cols * (a.has_cut ? 2 : 1) + 256));
+        unsigned char* p = static_cast<unsigned char*>(m_in.p);
+        HIP_TRY(hipMemcpyAsync(p, a.offsets, (n + 1) * 8, hipMemcpyHostToDevice, stream));
+        d_offsets = reinterpret_cast<const uint64_t*>(p); p += b_offs;
+        if (total != 0) HIP_TRY(hipMemcpyAsync(p, a.cols, total * 4, hipMemcpyHostToDevice, stream));
+        d_cols = reinterpret_cast<const uint32_t*>(p); p += b_cols;
+        if (a.has_cut && total != 0) HIP_TRY(hipMemcpyAsync(p, a.dists, total * 4, hipMemcpyHostToDevice, stream));
+        d_dists = reinterpret_cast<const float*>(p);
+    }
+    // the checks, and the one word that says how they went
+    HIP_TRY(hipMalloc(&m_word.p, 256));
+    unsigned long long* d_word = static_cast<unsigned long long*>(m_word.p);
+    HIP_TRY(hipMemsetAsync(d_word, 0, 8, stream));
+    hipLaunchKernelGGL(cc_check_offsets_kernel, grid_of(n + 1), dim3(256), 0, stream, d_offsets, (uint32_t)n, d_word);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cc_check_cols_kernel, dim3(CHECK_BLOCKS), dim3(256), 0, stream, d_offsets, d_cols, (uint32_t)n, d_word);
+    HIP_TRY(hipGetLastError());
+    unsigned long long word = 0;
+    HIP_TRY(hipMemcpyAsync(&word, d_word, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if ((word >> 32) != 0ull) {
+        err = std::string("csr components: ") + ((word & BAD_FIRST)     ? "offsets[0] is not 0"
+                                                 : (word & BAD_DESCENT) ? "the offsets descend"
+                                                 : (word & BAD_TOTAL)   ? "offsets[n] is 2^32 or more"
+                                                 : (word & BAD_NO_COLS) ? "null cols with entries"
+                                                                        : "a col is not below n");
+        return ERR_ARG;
+    }
+    const uint64_t total = word & 0xFFFFFFFFull;
+    int rc = forest_init(f, n, stream, err);
+    if (rc != OK) return rc;
+    if (total != 0) {
+        hipLaunchKernelGGL(cc_hook_csr_kernel, grid_of(total), dim3(256), 0, stream, d_offsets, d_cols, d_dists, (uint32_t)n, (uint32_t)total,
+                           a.has_cut ? 1u : 0u, a.max_dist, f.parent);
+        HIP_TRY(hipGetLastError());
+    }
+    return forest_answer(f, n, host, a.out_label, a.out_sizes, a.out_n, stream, err);
+}
+
+}  // namespace hnswgpu

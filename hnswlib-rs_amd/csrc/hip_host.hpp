@@ -1,5 +1,5 @@
-// hip_host.hpp -- the HIP host helpers of the four host units (search_device.hip, exact_knn.hip, range_search.hip,
-// symmetric_graph.hip), once.  Needs the HIP runtime: nothing that a host-only build compiles (capi.cpp, the builder, the stand-ins
+// hip_host.hpp -- the HIP host helpers of the five host units (search_device.hip, exact_knn.hip, range_search.hip,
+// symmetric_graph.hip, graph_components.hip), once.  Needs the HIP runtime: nothing that a host-only build compiles (capi.cpp, the builder, the stand-ins
 // of tests/cpp) may include it, and the kernel units do not see it.  Private: not installed, not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>

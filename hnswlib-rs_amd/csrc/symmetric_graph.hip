@@ -19,6 +19,9 @@
 //   sym_decode_kernel   one thread per entry: position, DataId, distance bits as stored, p_id
 // No atomics and no write whose place depends on timing: the answer is a function of D alone.  No kernel walks a row: a row of
 // n - 1 entries costs what n - 1 entries of short rows cost.
+// The first half -- D staged (stage_directed_graph), expanded and sorted (sorted_edge_records) -- is shared with
+// graph_components.hip through graph_internal.hpp: the components of the UNION graph hook D's slots, those of the MUTUAL graph the
+// sorted records.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -36,10 +39,7 @@
 namespace hnswgpu {
 namespace {
 
-// A record's key: the row above bit 33, the col in bits 1 .. 32, the flag in bit 0 (rows and cols are below 2^30: n k <= 2^30)
-constexpr uint64_t FLAG_REV = 1ull;
-__host__ __device__ inline uint64_t rec_key(uint32_t row, uint32_t col, uint64_t flag) { return ((uint64_t)row << 33) | ((uint64_t)col << 1) | flag; }
-
+// (a record's key, rec_key and FLAG_REV, is in graph_internal.hpp: graph_components.hip reads the sorted records too)
 // one thread per slot t = i k + s of D; records 2 t and 2 t + 1
 __global__ __launch_bounds__(256) void sym_expand_kernel(DeviceIndexView ix, const uint32_t* __restrict__ rank_of, const uint8_t* __restrict__ layer,
                                                         const int32_t* __restrict__ rank, const float* __restrict__ dists,
@@ -133,7 +133,66 @@ typedef rocprim::transform_iterator<const uint64_t*, SegBound, unsigned int> seg
 
 dim3 grid_of(uint64_t threads) { return dim3((uint32_t)((threads + 255) / 256)); }
 
+// declared behind a call's device memory, so destroyed first: nothing of the call is running when its memory is freed
+struct Drain {
+    hipStream_t s;
+    ~Drain() { (void)hipStreamSynchronize(s); }
+};
+
 }  // namespace
+
+// D staged for every point: the graph path's own call into one allocation (graph_internal.hpp)
+int stage_directed_graph(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, uint64_t k, uint64_t ef, void* stream_v, StagedGraph& out,
+                         std::string& err) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    const uint64_t n = dev.view().n, slots = n * k;
+    HIP_TRY(hipMalloc(&out.mem.p, round_up(slots * 8, 256) + 2 * round_up(slots * 4, 256) + round_up(n * 4, 256) + round_up(slots, 256)));
+    unsigned char* p = static_cast<unsigned char*>(out.mem.p);
+    uint64_t* d_ids = reinterpret_cast<uint64_t*>(p); p += round_up(slots * 8, 256);
+    out.dists = reinterpret_cast<float*>(p); p += round_up(slots * 4, 256);
+    out.rank = reinterpret_cast<int32_t*>(p); p += round_up(slots * 4, 256);
+    out.counts = reinterpret_cast<uint32_t*>(p); p += round_up(n * 4, 256);
+    out.layer = p;
+    return ef == 0 ? exact_graph(dev, origin_id, false, nullptr, n, k, nullptr, 0, d_ids, out.dists, out.layer, out.rank, out.counts, stream, err)
+                   : graph_search(dev, origin_id, false, nullptr, n, k, ef, d_ids, out.dists, out.layer, out.rank, out.counts, stream, err);
+}
+
+// D's edge records, sorted (graph_internal.hpp)
+int sorted_edge_records(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphOrder& ord, uint64_t k, uint64_t ef, void* stream_v,
+                        SortedRecords& out, std::string& err) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    const DeviceIndexView& v = dev.view();
+    const uint64_t n = v.n;
+    const uint64_t slots = n * k, records = 2 * slots;  // (n k <= 2^30: checked by the entries)
+    out.records = records;
+    StagedGraph d;
+    DevMem m_temp;
+    Drain drain{stream};
+    // D, staged: the graph path's own answer for every point, row i the point at position i
+    int rc = stage_directed_graph(dev, origin_id, k, ef, stream_v, d, err);
+    if (rc != OK) return rc;
+
+    // the records, and their sort.  keys_a has room for one word more per half: it holds the marks and their scan afterwards.
+    HIP_TRY(hipMalloc(&out.keys_a.p, records * 8 + 256));
+    HIP_TRY(hipMalloc(&out.keys_b.p, records * 8));
+    HIP_TRY(hipMalloc(&out.vals_a.p, records * 4));
+    HIP_TRY(hipMalloc(&out.vals_b.p, records * 4));
+    uint64_t* keys_a = static_cast<uint64_t*>(out.keys_a.p);
+    uint64_t* keys_b = static_cast<uint64_t*>(out.keys_b.p);
+    uint32_t* vals_a = static_cast<uint32_t*>(out.vals_a.p);
+    uint32_t* vals_b = static_cast<uint32_t*>(out.vals_b.p);
+    hipLaunchKernelGGL(sym_expand_kernel, grid_of(slots), dim3(256), 0, stream, v, ord.d_rank, d.layer, d.rank, d.dists, d.counts, (uint32_t)k, (uint32_t)slots,
+                       keys_a, vals_a);
+    HIP_TRY(hipGetLastError());
+    unsigned end_bit = 34;  // the flag, the col, and the bits of a row number 0 .. n
+    while (end_bit < 64 && (n >> (end_bit - 33)) != 0) ++end_bit;
+    size_t temp_bytes = 0;
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_a, keys_b, vals_a, vals_b, (uint32_t)records, 0u, end_bit, stream));
+    HIP_TRY(hipMalloc(&m_temp.p, std::max<size_t>(temp_bytes, 256)));
+    HIP_TRY(rocprim::radix_sort_pairs(m_temp.p, temp_bytes, keys_a, keys_b, vals_a, vals_b, (uint32_t)records, 0u, end_bit, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return OK;  // (D is in the records: it and the sort's temporary storage are released here)
+}
 
 // Both entries (capi.cpp refers to it weakly, capi_index.hpp).  host: the out arrays are plain host memory, else device memory.
 // Waits for `stream` before it returns.  dev_p == nullptr (device entry on an empty index): the one offset is zeroed.
@@ -149,50 +208,21 @@ int symmetric_graph(DeviceIndex* dev_p, const std::vector<uint64_t>& origin_id, 
     DeviceGuard on(dev.device());
     HIP_TRY(on.status());
     const uint64_t n = v.n, k = a.k;
-    const uint64_t slots = n * k, records = 2 * slots;  // (n k <= 2^30: checked by the entries)
-    struct Drain {
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    };
-    DevMem m_d, m_keys_a, m_keys_b, m_vals_a, m_vals_b, m_temp, m_offs, m_row;
+    const uint64_t records = 2 * n * k;  // (n k <= 2^30: checked by the entries)
+    SortedRecords rec;
+    DevMem m_temp, m_offs, m_row;
     Drain drain{stream};  // (destroyed first: nothing of this call is running when its memory is freed)
     GraphOrder ord;
     int rc = graph_order(dev, origin_id, ord, err);
     if (rc != OK) return rc;
-
-    // D, staged: the graph path's own answer for every point, row i the point at position i
-    HIP_TRY(hipMalloc(&m_d.p, round_up(slots * 8, 256) + 2 * round_up(slots * 4, 256) + round_up(n * 4, 256) + round_up(slots, 256)));
-    unsigned char* p = static_cast<unsigned char*>(m_d.p);
-    uint64_t* d_ids = reinterpret_cast<uint64_t*>(p); p += round_up(slots * 8, 256);
-    float* d_dists = reinterpret_cast<float*>(p); p += round_up(slots * 4, 256);
-    int32_t* d_rank = reinterpret_cast<int32_t*>(p); p += round_up(slots * 4, 256);
-    uint32_t* d_counts = reinterpret_cast<uint32_t*>(p); p += round_up(n * 4, 256);
-    uint8_t* d_layer = p;
-    rc = a.ef == 0 ? exact_graph(dev, origin_id, false, nullptr, n, k, nullptr, 0, d_ids, d_dists, d_layer, d_rank, d_counts, stream, err)
-                   : graph_search(dev, origin_id, false, nullptr, n, k, a.ef, d_ids, d_dists, d_layer, d_rank, d_counts, stream, err);
+    rc = sorted_edge_records(dev, origin_id, ord, k, a.ef, stream_v, rec, err);
     if (rc != OK) return rc;
-
-    // the records, and their sort.  keys_a has room for one word more per half: it holds the marks and their scan afterwards.
-    HIP_TRY(hipMalloc(&m_keys_a.p, records * 8 + 256));
-    HIP_TRY(hipMalloc(&m_keys_b.p, records * 8));
-    HIP_TRY(hipMalloc(&m_vals_a.p, records * 4));
-    HIP_TRY(hipMalloc(&m_vals_b.p, records * 4));
-    uint64_t* keys_a = static_cast<uint64_t*>(m_keys_a.p);
-    uint64_t* keys_b = static_cast<uint64_t*>(m_keys_b.p);
-    uint32_t* vals_a = static_cast<uint32_t*>(m_vals_a.p);
-    uint32_t* vals_b = static_cast<uint32_t*>(m_vals_b.p);
-    hipLaunchKernelGGL(sym_expand_kernel, grid_of(slots), dim3(256), 0, stream, v, ord.d_rank, d_layer, d_rank, d_dists, d_counts, (uint32_t)k, (uint32_t)slots,
-                       keys_a, vals_a);
-    HIP_TRY(hipGetLastError());
-    unsigned end_bit = 34;  // the flag, the col, and the bits of a row number 0 .. n
-    while (end_bit < 64 && (n >> (end_bit - 33)) != 0) ++end_bit;
+    uint64_t* keys_a = static_cast<uint64_t*>(rec.keys_a.p);
+    uint64_t* keys_b = static_cast<uint64_t*>(rec.keys_b.p);
+    uint32_t* vals_a = static_cast<uint32_t*>(rec.vals_a.p);
+    uint32_t* vals_b = static_cast<uint32_t*>(rec.vals_b.p);
     size_t temp_bytes = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_a, keys_b, vals_a, vals_b, (uint32_t)records, 0u, end_bit, stream));
-    HIP_TRY(hipMalloc(&m_temp.p, std::max<size_t>(temp_bytes, 256)));
-    HIP_TRY(rocprim::radix_sort_pairs(m_temp.p, temp_bytes, keys_a, keys_b, vals_a, vals_b, (uint32_t)records, 0u, end_bit, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    m_d.release();  // (D is in the records)
-    m_temp.release();
+    unsigned char* p = nullptr;
 
     // marks, their scan, the offsets, the total
     uint32_t* mark = reinterpret_cast<uint32_t*>(keys_a);

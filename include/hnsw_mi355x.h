@@ -654,6 +654,63 @@ int hnswgpu_symmetric_graph_device(const hnswgpu_index* idx, uint64_t k, uint64_
                                    uint64_t* d_out_offsets, uint32_t* d_out_pos, uint64_t* d_out_ids, float* d_out_dists,
                                    uint8_t* d_out_layer, int32_t* d_out_rank, void* stream);
 
+/* ---------------------------------------------------------------- connected components, cut optional --- */
+/* The connected components of the undirected k-NN graph of the section above, labelled on the device WITHOUT building that graph:
+ * what an embedder asks before it normalises a Laplacian (is the graph connected?), what a mutual-neighbour outlier test is
+ * (components of size 1 of the MUTUAL graph), and -- with the longer edges cut -- single-linkage clusters at a radius.  The
+ * answer is all integers and every correct algorithm gives the same bytes.
+ *   vertices  POSITIONS: vertex i, i in 0 .. n = hnswgpu_nb_point, is row i of hnswgpu_symmetric_graph, the point at position i
+ *             of the ascending (DataId, dump order) order -- the row numbering of the graph calls with point_ids == NULL.
+ *   D         the directed graph, exactly as hnswgpu_symmetric_graph takes it: k, ef and mode mean what they mean there (ef == 0:
+ *             the exact graph; ef >= 1: the graph search at this ef).  What that call refuses this one refuses the same way,
+ *             HNSWGPU_ERR_ARG before any output is written: k == 0; for ef == 0, k above 4096 and an index set to
+ *             HNSWGPU_ARITH_SIMD8; an index set to HNSWGPU_STORAGE_F16; n k above 2^30; a mode that is neither HNSWGPU_SYM_UNION nor
+ *             HNSWGPU_SYM_MUTUAL.
+ *   cut       max_dist is a HOST pointer to one f32, in all four entries.  NULL: every entry of D counts, whatever its distance,
+ *             a NaN included.  Otherwise the entry i -> j counts iff d(i->j) <= *max_dist, an ordered f32 comparison of the STORED
+ *             bits: a NaN distance never counts, -0 equals +0.  *max_dist NaN is HNSWGPU_ERR_ARG.  The cut is applied to D FIRST;
+ *             the definitions of the section above then apply to what is left -- HNSWGPU_SYM_UNION: i and j are joined iff i -> j
+ *             or j -> i survives; HNSWGPU_SYM_MUTUAL: iff both survive (for DistJeffreys and DistJensenShannon, whose two directions
+ *             differ in their bits, a cut may keep one direction of a pair and drop the other).
+ *   answer    two vertices share a label iff a path of such joins connects them.  Components are numbered 0 .. c - 1 by their
+ *             smallest position, ascending: out_label[0] == 0 and the first occurrences of the labels ascend.  out_label has n
+ *             slots.  out_sizes may be NULL and has n slots: the first c are written (vertices per component), the rest are not
+ *             touched.  *out_n_components = c.  An empty index: c = 0, nothing else written, HNSWGPU_OK.  A NULL out_label with
+ *             n > 0 and a NULL out_n_components are HNSWGPU_ERR_ARG.  On any error no out slot is touched.
+ *   memory    no record sort under UNION: every surviving slot of D is an edge.  With S = n k: D is staged as the section above
+ *             stages it (17 S + 4 n bytes, besides what its own call takes) and stays until its slots are hooked; the forest takes
+ *             12 n bytes (parents, root marks, their scan) and rocPRIM's temporary storage of one scan of n words.  MUTUAL needs the
+ *             pairs named both ways and sorts the section above's 2 S edge records for them (D and the records held twice, 65 S
+ *             bytes, and rocPRIM's temporary storage at the peak; 24 S while the forest is built).  The host forms add 4 n + 4 c
+ *             bytes of staged answer.
+ * The labels are the fixed point of a lock-free union-find over integer atomics (a root is the smallest position of its tree): the
+ * answer is a function of D alone, two calls give the same bytes.  Takes the handle's lock shared, like a search, and is legal from
+ * several host threads at once.  Host buffers; uploads the index on first use.
+ * Out of scope: a filter or a subset of points; labels by DataId; sharding over GPUs; F16 storage; a hierarchy over all radii
+ * (single-linkage dendrogram); strongly connected components of D.                                                           */
+int hnswgpu_graph_components(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, const float* max_dist,
+                             uint32_t* out_label, uint32_t* out_sizes, uint64_t* out_n_components);
+/* The same with out_label and out_sizes in HBM, on HIP stream `stream`, waited for; max_dist and out_n_components stay host
+ * pointers.  The index must be uploaded (else HNSWGPU_ERR_DEVICE).  Only c is read back.                                      */
+int hnswgpu_graph_components_device(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, const float* max_dist,
+                                    uint32_t* d_out_label, uint32_t* d_out_sizes, uint64_t* out_n_components, void* stream);
+/* The components of ANY graph given in CSR on `device`: offsets u64[n + 1], cols u32[offsets[n]], optionally dists f32[offsets[n]].
+ * Every entry (r, c) joins r and c, whichever row names it: a directed CSR gets its WEAKLY connected components.  Self-loops and
+ * repeated entries are legal and change nothing.  The cut, the numbering and the outputs are those above (an entry counts iff
+ * dists[e] <= *max_dist); dists is read under a cut only, and dists == NULL with a non-NULL max_dist is HNSWGPU_ERR_ARG.
+ * HNSWGPU_ERR_ARG, nothing written: offsets[0] != 0; offsets that descend; a col >= n; n > 2^31 - 1; offsets[n] >= 2^32 (and a NULL
+ * offsets, or a NULL cols with offsets[n] > 0).  n == 0: c = 0, HNSWGPU_OK.  The outputs of hnswgpu_symmetric_graph_device
+ * (offsets, pos, dists) are valid inputs as they stand.  Scratch: 12 n bytes and one scan's temporary storage; the host form
+ * stages its arrays (8 n + 4 or 8 bytes per entry) and its answer.  Needs no index; legal from several host threads at once.    */
+int hnswgpu_csr_components(int device, uint64_t n, const uint64_t* offsets, const uint32_t* cols, const float* dists,
+                           const float* max_dist, uint32_t* out_label, uint32_t* out_sizes, uint64_t* out_n_components);
+/* The same with the graph and out_label / out_sizes in HBM of `device`, on HIP stream `stream`, waited for.  The graph is checked
+ * by a validation kernel and ONE word read back before any kernel that follows a col runs: a bad graph is HNSWGPU_ERR_ARG, never a
+ * fault.  Only that word and c are read back.                                                                                */
+int hnswgpu_csr_components_device(int device, uint64_t n, const uint64_t* d_offsets, const uint32_t* d_cols, const float* d_dists,
+                                  const float* max_dist, uint32_t* d_out_label, uint32_t* d_out_sizes, uint64_t* out_n_components,
+                                  void* stream);
+
 /* Test entry: the lane lab. The wave-level algorithms the search kernels are made of -- the reference's BinaryHeap (src/hnsw.rs:940,
  * :958-973, :1035-1053, :1544; std's push / pop / into_sorted_vec) as a memory heap and as a register heap, the sorted result set
  * with its accept rule (:1028-1053), the exact visited table (:955-956, :1016-1017) -- run on `device` by ONE wavefront from a

@@ -54,6 +54,30 @@ struct AnnT {
     virtual std::string file_dump(const std::string& path, const std::string& file_basename) const = 0;
 };
 
+// Connected components (an extension: hnswgpu_graph_components, hnswgpu_csr_components): labels[v] is the component of vertex v,
+// components numbered 0 .. sizes.size() - 1 by their smallest vertex, ascending; sizes[c] is the number of vertices of c.
+struct Components {
+    std::vector<uint32_t> labels;
+    std::vector<uint32_t> sizes;
+    size_t n_components() const { return sizes.size(); }
+};
+// The components of ANY graph given in CSR (offsets.size() == n + 1, cols.size() >= offsets[n]), labelled on `device`: every entry
+// (r, c) joins r and c, whichever row names it.  max_dist (needs dists): an entry counts iff its distance is <= *max_dist.
+inline Components csr_components(const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& cols, const std::vector<float>* dists = nullptr,
+                                 const float* max_dist = nullptr, int device = 0) {
+    Components c;
+    if (offsets.empty() || offsets.back() > cols.size() || (dists && dists->size() < cols.size()))
+        throw Error(HNSWGPU_ERR_ARG, "csr_components: offsets must hold n + 1 entries, cols and dists offsets[n]");
+    const size_t n = offsets.size() - 1;
+    c.labels.assign(n, 0);
+    c.sizes.assign(n, 0);
+    uint64_t count = 0;
+    check(hnswgpu_csr_components(device, n, offsets.data(), cols.data(), dists ? dists->data() : nullptr, max_dist, c.labels.data(), c.sizes.data(),
+                                 &count));
+    c.sizes.resize(count);
+    return c;
+}
+
 template <class T, class D>
 class Hnsw;
 
@@ -155,6 +179,21 @@ public:
         g.neighbours.reserve(total);
         for (size_t e = 0; e < total; ++e) g.neighbours.push_back(Neighbour{(size_t)ids[e], dists[e], PointId{layers[e], ranks[e]}});
         return g;
+    }
+    // The connected components of the graph symmetric_knn_graph(knbn, ef, mutual) would build, labelled on the device without
+    // building it; vertices are POSITIONS.  max_dist: the directed graph is cut first -- an entry counts iff its stored distance is
+    // <= *max_dist --, then joined (mutual: iff both directions are left).
+    Components knn_graph_components(size_t knbn, size_t ef = 0, bool mutual = false, const float* max_dist = nullptr) const {
+        Components c;
+        if (!idx_) return c;
+        const size_t n = get_nb_point();
+        c.labels.assign(n, 0);
+        c.sizes.assign(n, 0);
+        uint64_t count = 0;
+        check(hnswgpu_graph_components(idx_, knbn, ef, mutual ? HNSWGPU_SYM_MUTUAL : HNSWGPU_SYM_UNION, max_dist, c.labels.data(), c.sizes.data(),
+                                       &count));
+        c.sizes.resize(count);
+        return c;
     }
     hnswgpu_index* handle() const { return idx_; }
 
