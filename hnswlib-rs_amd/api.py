@@ -188,6 +188,66 @@ def csr_components(offsets, cols, dists=None, max_dist=None, device=0):
     return ComponentsResult(labels, sizes[:int(c[0])].copy(), int(c[0]))
 
 
+class SpanningForestResult:
+    """The minimum spanning forest of a graph (Hnsw.knn_graph_spanning_forest, csr_spanning_forest): n_edges edges, edge e joining
+    vertices a[e] < b[e] with weight weights[e] (f32, the bits as the graph stores them), ascending by (weight, a, b).  Read in this
+    order the edges are the merges of the single-linkage hierarchy; labels_at cuts it at a radius."""
+
+    def __init__(self, a, b, weights, n_edges, n_vertices=None):
+        self.a, self.b, self.weights, self.n_edges = a, b, weights, n_edges
+        self.n_vertices = n_vertices if n_vertices is not None else (int(max(a.max(), b.max())) + 1 if n_edges else 0)
+
+    def labels_at(self, max_dist=None):
+        """The components of the forest edges whose weight is <= max_dist (None: every edge, a NaN weight included; otherwise an
+        ordered f32 comparison, which a NaN never passes), as a ComponentsResult: a host union-find, components numbered by
+        their smallest position."""
+        n = self.n_vertices
+        keep = np.ones(self.n_edges, bool) if max_dist is None else (self.weights[:self.n_edges] <= np.float32(max_dist))
+        parent = list(range(n))
+
+        def find(v):
+            while parent[v] != v:
+                parent[v] = parent[parent[v]]
+                v = parent[v]
+            return v
+        for x, y in zip(self.a[:self.n_edges][keep].tolist(), self.b[:self.n_edges][keep].tolist()):
+            rx, ry = find(x), find(y)
+            if rx != ry:
+                parent[max(rx, ry)] = min(rx, ry)
+        labels, sizes, number = np.zeros(n, np.uint32), [], {}
+        for v in range(n):
+            r = find(v)
+            if r not in number:  # (r == v: a root is the smallest vertex of its tree)
+                number[r] = len(sizes)
+                sizes.append(0)
+            labels[v] = number[r]
+            sizes[number[r]] += 1
+        return ComponentsResult(labels, np.array(sizes, np.uint32), len(sizes))
+
+
+def csr_spanning_forest(offsets, cols, dists=None, device=0):
+    """The minimum spanning forest of ANY graph given in CSR (offsets u64[n + 1], cols u32[offsets[n]], dists f32 per entry or None:
+    every weight 0), taken on `device`: every entry (r, c) is the undirected pair {r, c}, self-loops are ignored, a repeated pair
+    has the min of its weights.  Weights are ordered by value, -0 equal to +0, every NaN behind +inf; ties go by (lo, hi).  Returns
+    a SpanningForestResult."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    cols = np.ascontiguousarray(cols, dtype=np.uint32)
+    if dists is not None:
+        dists = np.ascontiguousarray(dists, dtype=np.float32)
+        if len(dists) != len(cols):
+            raise HnswError(N.ERR_ARG, f"dists has {len(dists)} entries, cols has {len(cols)}")
+        if len(dists) == 0:
+            dists = None  # (there is no entry)
+    if len(offsets) == 0 or int(offsets[-1]) > len(cols):
+        raise HnswError(N.ERR_ARG, "offsets must hold n + 1 entries, the last one at most len(cols)")
+    n = len(offsets) - 1
+    slots = max(n - 1, 1)
+    a, b, w, m = np.zeros(slots, np.uint32), np.zeros(slots, np.uint32), np.zeros(slots, np.float32), np.zeros(1, np.uint64)
+    _check(N.lib().hnswgpu_csr_spanning_forest(device, n, _p(offsets), _p(cols) if len(cols) else None, _p(dists), _p(a), _p(b), _p(w), _p(m)))
+    m = int(m[0])
+    return SpanningForestResult(a[:m].copy(), b[:m].copy(), w[:m].copy(), m, n)
+
+
 class Hnsw:
     """Hnsw<f32, D>: owns a hnswgpu_index handle (flat host graph + its HBM replica)."""
 
@@ -662,6 +722,32 @@ class Hnsw:
         cut = _cut(max_dist)
         _check(self._lib.hnswgpu_graph_components(self._h, knbn, 0 if ef is None else ef, modes[mode], _p(cut), _p(labels), _p(sizes), _p(c)))
         return ComponentsResult(labels, sizes[:int(c[0])].copy(), int(c[0]))
+
+    def knn_graph_spanning_forest(self, knbn, ef=None, mode="union", core_k=0):
+        """The minimum spanning forest of the graph symmetric_knn_graph_flat(knbn, ef, mode) would build, taken on the device without
+        building it.  Vertices are POSITIONS.  "union": a pair weighs the min of its directions in the directed graph; "mutual": the
+        max of the two.  core_k >= 1: mutual-reachability weights, max(pair, core(a), core(b)) with core(v) the distance to v's
+        core_k-th neighbour in the directed graph (the last one of a shorter row).  Returns a SpanningForestResult whose
+        labels_at(r) equals knn_graph_components(knbn, ef, mode, max_dist=r) when core_k == 0."""
+        modes = {"union": N.HEADER.constants["HNSWGPU_SYM_UNION"], "mutual": N.HEADER.constants["HNSWGPU_SYM_MUTUAL"]}
+        if mode not in modes:
+            raise HnswError(N.ERR_ARG, f"mode must be 'union' or 'mutual', not {mode!r}")
+        if ef is not None and ef < 1:
+            raise HnswError(N.ERR_ARG, "ef must be >= 1 (ef=None: the exact graph)")
+        if core_k < 0:
+            raise HnswError(N.ERR_ARG, "core_k must be >= 0")
+        n = self.get_nb_point()
+        slots = max(n - 1, 1)
+        a, b, w, m = np.zeros(slots, np.uint32), np.zeros(slots, np.uint32), np.zeros(slots, np.float32), np.zeros(1, np.uint64)
+        if self._h is None:
+            if knbn < 1:
+                raise HnswError(N.ERR_ARG, "knbn must be > 0")
+            if core_k > knbn:
+                raise HnswError(N.ERR_ARG, "core_k is above knbn")
+            return SpanningForestResult(a[:0], b[:0], w[:0], 0, 0)
+        _check(self._lib.hnswgpu_graph_spanning_forest(self._h, knbn, 0 if ef is None else ef, modes[mode], core_k, _p(a), _p(b), _p(w), _p(m)))
+        m = int(m[0])
+        return SpanningForestResult(a[:m].copy(), b[:m].copy(), w[:m].copy(), m, n)
 
     def knn_graph_recall(self, knbn, ef, point_ids=None):
         """The recall by id of knn_graph_flat against exact_knn_graph_flat over the named points: the share of the exact

@@ -1351,6 +1351,20 @@ static int csr_components_call(uint64_t n, const void* offsets, const void* dist
     return HNSWGPU_OK;
 }
 
+// the graph itself as a host form reads it (n >= 1, offsets not NULL), as the device forms' validation kernels check it
+static int csr_graph_check(const char* what, uint64_t n, const uint64_t* offsets, const uint32_t* cols) {
+    const std::string w = std::string(what) + ": ";
+    if (offsets[0] != 0) return fail(HNSWGPU_ERR_ARG, w + "offsets[0] is not 0");
+    for (uint64_t r = 0; r < n; ++r)
+        if (offsets[r] > offsets[r + 1]) return fail(HNSWGPU_ERR_ARG, w + "the offsets descend at row " + std::to_string(r));
+    const uint64_t total = offsets[n];
+    if (total >= (1ull << 32)) return fail(HNSWGPU_ERR_ARG, w + "offsets[n] = " + std::to_string(total) + " is 2^32 or more");
+    if (total != 0 && !cols) return fail(HNSWGPU_ERR_ARG, w + "null cols with entries");
+    for (uint64_t e = 0; e < total; ++e)
+        if (cols[e] >= n) return fail(HNSWGPU_ERR_ARG, w + "col " + std::to_string(cols[e]) + " at entry " + std::to_string(e) + " is not below n");
+    return HNSWGPU_OK;
+}
+
 int hnswgpu_csr_components(int device, uint64_t n, const uint64_t* offsets, const uint32_t* cols, const float* dists, const float* max_dist,
                            uint32_t* out_label, uint32_t* out_sizes, uint64_t* out_n_components) {
     CAPI_GUARD_BEGIN
@@ -1360,15 +1374,8 @@ int hnswgpu_csr_components(int device, uint64_t n, const uint64_t* offsets, cons
         *out_n_components = 0;
         return HNSWGPU_OK;
     }
-    // the graph itself, as the device form's validation kernels check it
-    if (offsets[0] != 0) return fail(HNSWGPU_ERR_ARG, "csr components: offsets[0] is not 0");
-    for (uint64_t r = 0; r < n; ++r)
-        if (offsets[r] > offsets[r + 1]) return fail(HNSWGPU_ERR_ARG, "csr components: the offsets descend at row " + std::to_string(r));
-    const uint64_t total = offsets[n];
-    if (total >= (1ull << 32)) return fail(HNSWGPU_ERR_ARG, "csr components: offsets[n] = " + std::to_string(total) + " is 2^32 or more");
-    if (total != 0 && !cols) return fail(HNSWGPU_ERR_ARG, "csr components: null cols with entries");
-    for (uint64_t e = 0; e < total; ++e)
-        if (cols[e] >= n) return fail(HNSWGPU_ERR_ARG, "csr components: col " + std::to_string(cols[e]) + " at entry " + std::to_string(e) + " is not below n");
+    rc = csr_graph_check("csr components", n, offsets, cols);
+    if (rc != HNSWGPU_OK) return rc;
     if (!hnswgpu::csr_components) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     const CsrComponentsArgs a{device, n, offsets, cols, dists, max_dist != nullptr, max_dist ? *max_dist : 0.0f, out_label, out_sizes, out_n_components};
     std::string err;
@@ -1390,6 +1397,117 @@ int hnswgpu_csr_components_device(int device, uint64_t n, const uint64_t* d_offs
                               out_n_components};
     std::string err;
     return finish(hnswgpu::csr_components(a, false, stream, err), err);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+// ---- minimum spanning forest: of the k-NN graph of the indexed points, and of any CSR (spanning_forest.hip holds the device side)
+extern "C++" {
+namespace hnswgpu {
+__attribute__((weak)) int graph_spanning_forest(DeviceIndex&, const std::vector<uint64_t>&, const ForestArgs&, bool, void*, std::string&);
+__attribute__((weak)) int csr_spanning_forest(const CsrForestArgs&, bool, void*, std::string&);
+}  // namespace hnswgpu
+}  // extern "C++"
+// what all four entries check of the answer's slots (n: the number of vertices)
+static int forest_answer_check(uint64_t n, const void* out_a, const void* out_b, const void* out_w, const uint64_t* out_n_edges) {
+    if (!out_n_edges) return fail(HNSWGPU_ERR_ARG, "null out_n_edges: the number of edges is written by every call");
+    if (n >= 2 && (!out_a || !out_b || !out_w)) return fail(HNSWGPU_ERR_ARG, "null out_a, out_b or out_w");
+    return HNSWGPU_OK;
+}
+// the checks both index entries share; the handle's lock is held (shared)
+static int graph_spanning_forest_call(const hnswgpu_index* idx, const ForestArgs& a) {
+    int rc = forest_answer_check(index_nb_point(idx), a.out_a, a.out_b, a.out_w, a.out_n);
+    if (rc != HNSWGPU_OK) return rc;
+    rc = directed_graph_shape(a.k, a.mode);
+    if (rc != HNSWGPU_OK) return rc;
+    if (a.core_k > a.k)
+        return fail(HNSWGPU_ERR_ARG, "core_k = " + std::to_string(a.core_k) + " is above knbn = " + std::to_string(a.k) + ": a row of D has knbn slots");
+    return directed_graph_source(idx, "graph spanning forest", a.k, a.ef);
+}
+
+int hnswgpu_graph_spanning_forest(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k, uint32_t* out_a, uint32_t* out_b,
+                                  float* out_w, uint64_t* out_n_edges) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    const ForestArgs a{k, ef, mode, core_k, out_a, out_b, out_w, out_n_edges};
+    int rc = graph_spanning_forest_call(idx, a);
+    if (rc != HNSWGPU_OK) return rc;
+    if (index_nb_point(idx) <= 1) {  // no vertex, or one: no edge, nothing else written
+        *out_n_edges = 0;
+        return HNSWGPU_OK;
+    }
+    if (!hnswgpu::graph_spanning_forest) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = primary_f32_replica(idx, sl, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    return finish(hnswgpu::graph_spanning_forest(*dev, idx->flat->origin_id, a, true, nullptr, err), err);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswgpu_graph_spanning_forest_device(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k, uint32_t* d_out_a,
+                                         uint32_t* d_out_b, float* d_out_w, uint64_t* out_n_edges, void* stream) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    const ForestArgs a{k, ef, mode, core_k, d_out_a, d_out_b, d_out_w, out_n_edges};
+    int rc = graph_spanning_forest_call(idx, a);
+    if (rc != HNSWGPU_OK) return rc;
+    if (index_nb_point(idx) <= 1) {
+        *out_n_edges = 0;
+        return HNSWGPU_OK;
+    }
+    if (!hnswgpu::graph_spanning_forest) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = resident_replica(idx, true, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    return finish(hnswgpu::graph_spanning_forest(*dev, idx->flat->origin_id, a, false, stream, err), err);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+// what both CSR entries can check without reading an array
+static int csr_spanning_forest_call(const CsrForestArgs& a) {
+    const int rc = forest_answer_check(a.n, a.out_a, a.out_b, a.out_w, a.out_n);
+    if (rc != HNSWGPU_OK) return rc;
+    if (a.n > 0x7FFFFFFFull) return fail(HNSWGPU_ERR_ARG, "csr spanning forest: n = " + std::to_string(a.n) + " vertices, above 2^31 - 1");
+    if (a.n != 0 && !a.offsets) return fail(HNSWGPU_ERR_ARG, "null offsets");
+    return HNSWGPU_OK;
+}
+
+int hnswgpu_csr_spanning_forest(int device, uint64_t n, const uint64_t* offsets, const uint32_t* cols, const float* dists, uint32_t* out_a, uint32_t* out_b,
+                                float* out_w, uint64_t* out_n_edges) {
+    CAPI_GUARD_BEGIN
+    const CsrForestArgs a{device, n, offsets, cols, dists, out_a, out_b, out_w, out_n_edges};
+    int rc = csr_spanning_forest_call(a);
+    if (rc != HNSWGPU_OK) return rc;
+    if (n <= 1) {  // no vertex, or one: no edge (a self-loop is none); no array is read
+        *out_n_edges = 0;
+        return HNSWGPU_OK;
+    }
+    rc = csr_graph_check("csr spanning forest", n, offsets, cols);
+    if (rc != HNSWGPU_OK) return rc;
+    if (!hnswgpu::csr_spanning_forest) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    std::string err;
+    return finish(hnswgpu::csr_spanning_forest(a, true, nullptr, err), err);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswgpu_csr_spanning_forest_device(int device, uint64_t n, const uint64_t* d_offsets, const uint32_t* d_cols, const float* d_dists, uint32_t* d_out_a,
+                                       uint32_t* d_out_b, float* d_out_w, uint64_t* out_n_edges, void* stream) {
+    CAPI_GUARD_BEGIN
+    const CsrForestArgs a{device, n, d_offsets, d_cols, d_dists, d_out_a, d_out_b, d_out_w, out_n_edges};
+    const int rc = csr_spanning_forest_call(a);
+    if (rc != HNSWGPU_OK) return rc;
+    if (n <= 1) {
+        *out_n_edges = 0;
+        return HNSWGPU_OK;
+    }
+    if (!hnswgpu::csr_spanning_forest) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    std::string err;
+    return finish(hnswgpu::csr_spanning_forest(a, false, stream, err), err);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 

@@ -1,5 +1,5 @@
 // capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h, for the translation units
-// that implement entry points of the C ABI (capi.cpp; exact_knn.hip; range_search.hip; symmetric_graph.hip; graph_components.hip).  Private: not installed, not part of the ABI.
+// that implement entry points of the C ABI (capi.cpp; exact_knn.hip; range_search.hip; symmetric_graph.hip; graph_components.hip; spanning_forest.hip).  Private: not installed, not part of the ABI.
 // The checks that entries share (empty index, resident replica, sorted filter, the shape and contents of a filter set, the limits of
 // an exact call, the zeroed k-NN answer, the tail) live once, in capi.cpp; what an entry outside capi.cpp needs of them is declared
 // below as capi_*.  A new pair of entries calls them.  The HIP host helpers of the .hip units (HIP_TRY, DeviceGuard, DevMem,
@@ -169,6 +169,32 @@ struct CsrComponentsArgs {
     uint64_t* out_n;
 };
 int csr_components(const CsrComponentsArgs& a, bool host, void* stream, std::string& err);
+// the device side of hnswgpu_graph_spanning_forest(_device) and hnswgpu_csr_spanning_forest(_device), defined in spanning_forest.hip
+// and referred to weakly in the same way (the arguments have been checked; at least two vertices).  host: the arrays are plain host
+// memory; else device memory and `stream` is the caller's.  out_n is host memory either way.  csr_spanning_forest returns ERR_ARG,
+// no out slot written, when its validation kernels refuse the graph.
+struct ForestArgs {
+    uint64_t k, ef;
+    uint32_t mode;    // HNSWGPU_SYM_*
+    uint64_t core_k;  // 0 .. k
+    uint32_t* out_a;  // [n - 1]
+    uint32_t* out_b;  // [n - 1]
+    float* out_w;     // [n - 1]
+    uint64_t* out_n;
+};
+int graph_spanning_forest(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ForestArgs& a, bool host, void* stream, std::string& err);
+struct CsrForestArgs {
+    int device;
+    uint64_t n;
+    const uint64_t* offsets;  // [n + 1]
+    const uint32_t* cols;     // [offsets[n]]
+    const float* dists;       // [offsets[n]], may be nullptr: every weight +0
+    uint32_t* out_a;
+    uint32_t* out_b;
+    float* out_w;
+    uint64_t* out_n;
+};
+int csr_spanning_forest(const CsrForestArgs& a, bool host, void* stream, std::string& err);
 }  // namespace hnswgpu
 
 // No C++ exception may cross the C ABI: every entry point is `try { ... HNSWGPU_CAPI_GUARD_END(ret)`

@@ -1,5 +1,6 @@
 // graph_internal.hpp -- what exact_knn.hip shares with symmetric_graph.hip, the unit that turns the k-NN graph of the indexed points
-// into an undirected one, and what that unit shares with graph_components.hip, which labels the graph's connected components: the
+// into an undirected one, and what that unit shares with graph_components.hip, which labels the graph's connected components, and
+// with spanning_forest.hip, which takes the graph's minimum spanning forest: the
 // order of the exact k-NN key, the DataId ranks a replica keeps on the device, the directed graph D staged on the device, and D's
 // edge records sorted.  Private, like capi_index.hpp; the graph calls themselves (graph_search, exact_graph) are declared there.
 #pragma once
@@ -56,10 +57,13 @@ struct SortedRecords {
     uint64_t records = 0;
 };
 // defined in symmetric_graph.hip, on `stream`; the device of `dev` is current.  OK, or the graph call's own status with `err` set.
-// sorted_edge_records waits for the stream and has released D when it returns.
+// sorted_edge_records waits for the stream and has released D when it returns; sorted_edge_records_keeping leaves D in `d` for a
+// caller that reads it afterwards (spanning_forest.hip: the core distances).
 int stage_directed_graph(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, uint64_t k, uint64_t ef, void* stream, StagedGraph& out,
                          std::string& err);
 int sorted_edge_records(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphOrder& ord, uint64_t k, uint64_t ef, void* stream,
                         SortedRecords& out, std::string& err);
+int sorted_edge_records_keeping(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphOrder& ord, uint64_t k, uint64_t ef, void* stream,
+                                SortedRecords& out, StagedGraph& d, std::string& err);
 
 }  // namespace hnswgpu

@@ -160,12 +160,18 @@ int stage_directed_graph(DeviceIndex& dev, const std::vector<uint64_t>& origin_i
 // D's edge records, sorted (graph_internal.hpp)
 int sorted_edge_records(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphOrder& ord, uint64_t k, uint64_t ef, void* stream_v,
                         SortedRecords& out, std::string& err) {
+    StagedGraph d;
+    return sorted_edge_records_keeping(dev, origin_id, ord, k, ef, stream_v, out, d, err);  // (D is in the records: released here)
+}
+
+// the same, D left in `d`
+int sorted_edge_records_keeping(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphOrder& ord, uint64_t k, uint64_t ef, void* stream_v,
+                                SortedRecords& out, StagedGraph& d, std::string& err) {
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     const DeviceIndexView& v = dev.view();
     const uint64_t n = v.n;
     const uint64_t slots = n * k, records = 2 * slots;  // (n k <= 2^30: checked by the entries)
     out.records = records;
-    StagedGraph d;
     DevMem m_temp;
     Drain drain{stream};
     // D, staged: the graph path's own answer for every point, row i the point at position i
@@ -191,7 +197,7 @@ int sorted_edge_records(DeviceIndex& dev, const std::vector<uint64_t>& origin_id
     HIP_TRY(hipMalloc(&m_temp.p, std::max<size_t>(temp_bytes, 256)));
     HIP_TRY(rocprim::radix_sort_pairs(m_temp.p, temp_bytes, keys_a, keys_b, vals_a, vals_b, (uint32_t)records, 0u, end_bit, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    return OK;  // (D is in the records: it and the sort's temporary storage are released here)
+    return OK;  // (the sort's temporary storage is released here)
 }
 
 // Both entries (capi.cpp refers to it weakly, capi_index.hpp).  host: the out arrays are plain host memory, else device memory.

@@ -687,7 +687,7 @@ int hnswgpu_symmetric_graph_device(const hnswgpu_index* idx, uint64_t k, uint64_
  * answer is a function of D alone, two calls give the same bytes.  Takes the handle's lock shared, like a search, and is legal from
  * several host threads at once.  Host buffers; uploads the index on first use.
  * Out of scope: a filter or a subset of points; labels by DataId; sharding over GPUs; F16 storage; a hierarchy over all radii
- * (single-linkage dendrogram); strongly connected components of D.                                                           */
+ * (single-linkage dendrogram); strongly connected components of D.  (The hierarchy's merge order: the section below.)        */
 int hnswgpu_graph_components(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, const float* max_dist,
                              uint32_t* out_label, uint32_t* out_sizes, uint64_t* out_n_components);
 /* The same with out_label and out_sizes in HBM, on HIP stream `stream`, waited for; max_dist and out_n_components stay host
@@ -710,6 +710,69 @@ int hnswgpu_csr_components(int device, uint64_t n, const uint64_t* offsets, cons
 int hnswgpu_csr_components_device(int device, uint64_t n, const uint64_t* d_offsets, const uint32_t* d_cols, const float* d_dists,
                                   const float* max_dist, uint32_t* d_out_label, uint32_t* d_out_sizes, uint64_t* out_n_components,
                                   void* stream);
+
+/* ---------------------------------------------------------------- minimum spanning forest --- */
+/* The minimum spanning forest (MSF) of the undirected k-NN graph of the two sections above, on the device WITHOUT building that
+ * graph: the single-linkage clusters at EVERY radius in one call.  The forest's edges in ascending order are the merge order of the
+ * single-linkage hierarchy; the components at a cut r are the components of the forest edges of weight <= r, and they are what
+ * hnswgpu_graph_components answers at max_dist = r; with core_k >= 1 the weights are mutual-reachability distances and the forest
+ * is what HDBSCAN starts from.  Under a strict total order on the edges the forest is unique: every correct algorithm gives the
+ * same bytes.
+ *   vertices  POSITIONS, exactly as in hnswgpu_graph_components: vertex i is the point at position i of the ascending (DataId, dump
+ *             order) order, row i of hnswgpu_symmetric_graph.
+ *   D         the directed graph: k, ef and mode mean what they mean in hnswgpu_graph_components, and what that call refuses of
+ *             them this one refuses with the same words, HNSWGPU_ERR_ARG before any output is written.
+ *   order     weights are compared as the exact k-NN key compares distances: by f32 value, -0 equal to +0, every NaN equal to
+ *             every other NaN and behind +inf.  min and max below are min and max in this order.
+ *   weight    of the pair {i, j}.  HNSWGPU_SYM_UNION: the pair exists iff i -> j or j -> i is in D, and weighs the min of the
+ *             directions present.  HNSWGPU_SYM_MUTUAL: iff both are in D, and weighs the max of the two.  The weight carries the
+ *             STORED bits of the direction chosen; when the two tie in the order, those of lo -> hi (lo < hi the two positions).
+ *             ("Either direction survives a cut" is the min, "both survive" is the max: for DistJeffreys and DistJensenShannon,
+ *             whose two directions differ in their bits, this is what makes the forest agree with the components at every cut.)
+ *   core_k    0: the weights above.  core_k >= 1: weight = max(pair weight, core(lo), core(hi)), where core(v) is the stored
+ *             distance in slot min(core_k, counts[v]) - 1 of row v of D (rows of D ascend; +0 for an empty row).  When values tie
+ *             in the order the bits are the pair weight's first, then core(lo)'s, then core(hi)'s.  core_k > k is HNSWGPU_ERR_ARG.
+ *   answer    the unique minimum spanning forest under the strict total order (weight, lo, hi) on pairs: n - c edges, c the number
+ *             of components hnswgpu_graph_components reports with a NULL cut, written ascending by (weight, lo, hi).  Edge e:
+ *             out_a[e] = lo, out_b[e] = hi > lo, out_w[e] = the weight's bits.  *out_n_edges = n - c.  The out arrays have
+ *             max(n - 1, 0) slots; slots behind the answer are not touched.  n <= 1 (an empty index too): 0 edges, HNSWGPU_OK,
+ *             nothing else written.  A NULL out_n_edges, and with n >= 2 a NULL out_a, out_b or out_w, are HNSWGPU_ERR_ARG.  On any
+ *             error no out slot is touched.
+ *   memory    with S = n k and m <= S pairs: the 2 S sorted edge records of the section above (D and the records held twice, 65 S
+ *             bytes, and rocPRIM's temporary storage at the peak; D stays 17 S + 4 n bytes longer when core_k >= 1, for the 4 n
+ *             bytes of core distances), then 24 S + 12 m while the pairs are taken out of the records, then the edge list alone:
+ *             36 m + 12 n bytes (lo, hi, bits; order keys twice -- the flags and their scan afterwards --, two permutation halves,
+ *             the ranked ends; parents, best edges, root marks) and rocPRIM's temporary storage of one sort of m pairs of words.
+ *             The host forms add 12 (n - c) bytes of staged answer.
+ * Boruvka rounds over the lock-free union-find of the components, integer atomics only: the edges are sorted into the total order
+ * once, an edge's index is its rank, and every later comparison is a u32 atomic min.  A round is three kernels and one word read
+ * back; there are at most ceil(log2 n) + 1 rounds, and the bound is hard (a round past it would be HNSWGPU_ERR_FORMAT, an internal
+ * error).  The answer is a function of D alone, two calls give the same bytes.  Takes the handle's lock shared, like a search, and
+ * is legal from several host threads at once.  Host buffers; uploads the index on first use.
+ * Out of scope: the dendrogram itself (cluster sizes, condensed tree, stability); a filter or a subset of points; F16 storage;
+ * sharding over GPUs; weights other than stored distances and their core maxima.                                              */
+int hnswgpu_graph_spanning_forest(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k,
+                                  uint32_t* out_a, uint32_t* out_b, float* out_w, uint64_t* out_n_edges);
+/* The same with out_a, out_b and out_w in HBM, on HIP stream `stream`, waited for; out_n_edges stays a host pointer.  The index
+ * must be uploaded (else HNSWGPU_ERR_DEVICE).  Only the pair count, one word per round and n - c are read back.               */
+int hnswgpu_graph_spanning_forest_device(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k,
+                                         uint32_t* d_out_a, uint32_t* d_out_b, float* d_out_w, uint64_t* out_n_edges, void* stream);
+/* The minimum spanning forest of ANY graph given in CSR on `device`: offsets u64[n + 1], cols u32[offsets[n]], optionally dists
+ * f32[offsets[n]] (dists == NULL: every weight is +0).  Every entry (r, c) is the undirected pair {r, c} with weight dists[e],
+ * whichever row names it; self-loops are ignored; a pair that several entries name has the min of their weights (among entries that tie,
+ * the bits of the lowest-numbered one).  The order, the answer and the outputs are those above, c being what
+ * hnswgpu_csr_components reports with a NULL cut.  HNSWGPU_ERR_ARG, nothing written, exactly as hnswgpu_csr_components refuses:
+ * offsets[0] != 0; offsets that descend; a col >= n; n > 2^31 - 1; offsets[n] >= 2^32 (and a NULL offsets, or a NULL cols with
+ * offsets[n] > 0).  n <= 1: 0 edges, HNSWGPU_OK, no array is read.  The outputs of hnswgpu_symmetric_graph_device (offsets, pos,
+ * dists) are valid inputs as they stand.  Scratch: 20 bytes per entry while the entries are sorted by (lo, hi), then 36 per entry
+ * and 12 n as above; the host form stages its arrays and its answer.  Needs no index; legal from several host threads at once.   */
+int hnswgpu_csr_spanning_forest(int device, uint64_t n, const uint64_t* offsets, const uint32_t* cols, const float* dists,
+                                uint32_t* out_a, uint32_t* out_b, float* out_w, uint64_t* out_n_edges);
+/* The same with the graph and out_a / out_b / out_w in HBM of `device`, on HIP stream `stream`, waited for.  The graph is checked
+ * by the validation kernels of hnswgpu_csr_components_device and ONE word read back first, before any kernel that follows a col
+ * runs: a bad graph is HNSWGPU_ERR_ARG, never a fault.                                                                        */
+int hnswgpu_csr_spanning_forest_device(int device, uint64_t n, const uint64_t* d_offsets, const uint32_t* d_cols, const float* d_dists,
+                                       uint32_t* d_out_a, uint32_t* d_out_b, float* d_out_w, uint64_t* out_n_edges, void* stream);
 
 /* Test entry: the lane lab. The wave-level algorithms the search kernels are made of -- the reference's BinaryHeap (src/hnsw.rs:940,
  * :958-973, :1035-1053, :1544; std's push / pop / into_sorted_vec) as a memory heap and as a register heap, the sorted result set

@@ -78,6 +78,35 @@ inline Components csr_components(const std::vector<uint64_t>& offsets, const std
     return c;
 }
 
+// The minimum spanning forest (an extension: hnswgpu_graph_spanning_forest, hnswgpu_csr_spanning_forest): edge e joins vertices
+// a[e] < b[e] with weight weights[e] (the bits as the graph stores them); the edges ascend by (weight, a, b), weights ordered by
+// value, -0 equal to +0, every NaN behind +inf.  Read in this order they are the merges of the single-linkage hierarchy.
+struct SpanningForest {
+    std::vector<uint32_t> a;
+    std::vector<uint32_t> b;
+    std::vector<float> weights;
+    size_t n_edges() const { return a.size(); }
+};
+// The forest of ANY graph given in CSR (offsets.size() == n + 1, cols.size() >= offsets[n]), taken on `device`: every entry (r, c) is
+// the undirected pair {r, c} with weight (*dists)[e] (no dists: +0), self-loops are ignored, a repeated pair has the min of its weights.
+inline SpanningForest csr_spanning_forest(const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& cols, const std::vector<float>* dists = nullptr,
+                                          int device = 0) {
+    SpanningForest f;
+    if (offsets.empty() || offsets.back() > cols.size() || (dists && dists->size() < cols.size()))
+        throw Error(HNSWGPU_ERR_ARG, "csr_spanning_forest: offsets must hold n + 1 entries, cols and dists offsets[n]");
+    const size_t n = offsets.size() - 1, slots = n > 1 ? n - 1 : 1;
+    f.a.assign(slots, 0);
+    f.b.assign(slots, 0);
+    f.weights.assign(slots, 0.0f);
+    uint64_t count = 0;
+    check(hnswgpu_csr_spanning_forest(device, n, offsets.data(), cols.data(), dists ? dists->data() : nullptr, f.a.data(), f.b.data(), f.weights.data(),
+                                      &count));
+    f.a.resize(count);
+    f.b.resize(count);
+    f.weights.resize(count);
+    return f;
+}
+
 template <class T, class D>
 class Hnsw;
 
@@ -194,6 +223,24 @@ public:
                                        &count));
         c.sizes.resize(count);
         return c;
+    }
+    // The minimum spanning forest of the graph symmetric_knn_graph(knbn, ef, mutual) would build, taken on the device without
+    // building it; vertices are POSITIONS.  A pair weighs the min of its directions in the directed graph (mutual: the max of the
+    // two); core_k >= 1: mutual-reachability weights, max(pair, core(a), core(b)), core(v) the distance to v's core_k-th neighbour.
+    SpanningForest knn_graph_spanning_forest(size_t knbn, size_t ef = 0, bool mutual = false, size_t core_k = 0) const {
+        SpanningForest f;
+        if (!idx_) return f;
+        const size_t n = get_nb_point(), slots = n > 1 ? n - 1 : 1;
+        f.a.assign(slots, 0);
+        f.b.assign(slots, 0);
+        f.weights.assign(slots, 0.0f);
+        uint64_t count = 0;
+        check(hnswgpu_graph_spanning_forest(idx_, knbn, ef, mutual ? HNSWGPU_SYM_MUTUAL : HNSWGPU_SYM_UNION, core_k, f.a.data(), f.b.data(),
+                                            f.weights.data(), &count));
+        f.a.resize(count);
+        f.b.resize(count);
+        f.weights.resize(count);
+        return f;
     }
     hnswgpu_index* handle() const { return idx_; }
 
