@@ -461,6 +461,9 @@ int DeviceIndex::upload(const FlatIndex& x, int device, std::string& err) {
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     num_cu_ = prop.multiProcessorCount;
+    int lds_limit = 0;
+    HIP_TRY(hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+    lds_limit_ = (size_t)std::max(0, lds_limit);
     device_ = device;
     dist_ = x.dist;
     bytes_ = 0;
@@ -714,11 +717,10 @@ int DeviceIndex::SearchCall::run_exact(const uint32_t* d_qlist, uint32_t n, cons
         const uint64_t per_block = bm_slice + heap_stride * sizeof(hent_t);
         ExactArgs x{};
         // LDS: [query][ids][return_points: ef + 2 entries, or what fits][top of candidate_points]
-        const uint64_t lds_fixed = tile_bytes + IDS_BYTES;
-        const uint64_t lds_budget = std::max<uint64_t>(10 * 1024, lds_fixed + 4096) - lds_fixed;
-        x.r_lds_cap = (uint32_t)std::min<uint64_t>(ef + 2, lds_budget / 2 / sizeof(hent_t));
-        x.cand_lds = (uint32_t)std::min<uint64_t>(cand_cap, (lds_budget - (uint64_t)x.r_lds_cap * sizeof(hent_t)) / sizeof(hent_t));
-        const size_t lds = lds_fixed + ((size_t)x.r_lds_cap + x.cand_lds) * sizeof(hent_t);
+        const ExactLds xl = exact_lds(tile_bytes, ef, cand_cap);
+        x.r_lds_cap = xl.r_lds_cap;
+        x.cand_lds = xl.cand_lds;
+        const size_t lds = xl.lds;
         int per_cu = 0;
         HIP_TRY(ks.exact_occupancy(ns, lds, &per_cu));
         per_cu = std::max(1, per_cu);
@@ -822,6 +824,9 @@ int DeviceIndex::search_device_impl(const float* d_queries, uint64_t nq, uint64_
                                     void* stream_v, const CallFilter& filter, CallInfo* info_out, std::string& err, const RowFeed* feed) {
     if (!ready_) { err = "index is not resident on a device: call hnswgpu_upload first"; return ERR_DEVICE; }
     if (d != v_.d) { err = "query dimension differs from the index dimension"; return ERR_ARG; }
+    // rows whose tile fits no launch on this device: refused here, before the first launch, no output touched
+    err = lds_refusal(v_.d, tile_bytes_for(kernel_metric(), v_.row_stride), lds_limit_);
+    if (!err.empty()) return ERR_ARG;
     auto publish = [&](const CallInfo& info) {
         if (info_out) *info_out = info;
         std::lock_guard<std::mutex> g(meta_mu_);
@@ -882,11 +887,16 @@ int DeviceIndex::search_device_impl(const float* d_queries, uint64_t nq, uint64_
 // first kernel of the call: rows padded to the row stride, the greedy descent of every query (pre[]), counters zeroed
 int DeviceIndex::SearchCall::descend(const float* d_queries, const RowFeed* feed) {
     // two queries per wavefront where every list above the search layer fits a half's 16 row slots (hnsw_descend_pair_kernel)
-    const bool pair = ix.up_deg_max_ <= 16u && metric < KM_SIMD8_FIRST && !kn.no_pair_descent;
-    const size_t descend_lds = (pair ? 2u : 1u) * (size_t)tile_bytes + IDS_BYTES;
+    // (... and two query tiles fit a workgroup's LDS: else one query per wavefront, as the pair pass of the search does)
+    bool pair = ix.up_deg_max_ <= 16u && metric < KM_SIMD8_FIRST && !kn.no_pair_descent && descend_lds_bytes(tile_bytes, true) <= ix.lds_limit_;
     int per_cu = ix.descend_per_cu_[pair].load();
     if (per_cu <= 0) {
-        HIP_TRY(ks.descend_occupancy(descend_lds, pair, &per_cu));
+        HIP_TRY(ks.descend_occupancy(descend_lds_bytes(tile_bytes, pair), pair, &per_cu));
+        if (pair && per_cu < 1) {  // (no workgroup of the two-query kernel is resident at this size)
+            pair = false;
+            per_cu = ix.descend_per_cu_[0].load();
+            if (per_cu <= 0) HIP_TRY(ks.descend_occupancy(descend_lds_bytes(tile_bytes, false), false, &per_cu));
+        }
         per_cu = std::max(1, per_cu);
         ix.descend_per_cu_[pair].store(per_cu);
     }
@@ -1048,30 +1058,23 @@ hipError_t DeviceIndex::SearchCall::search_occupancy(int shape, bool strict, siz
 // LDS, visited table and resident workgroups of one launch of the one-query kernels: sets the table's kind (`table`) and the
 // fields of `a` that size the workgroup's LDS.
 int DeviceIndex::SearchCall::shape_launch(SearchArgs& a, LaunchShape& s) {
-    s.lds = tile_bytes + IDS_BYTES;
+    s.strict_kernel = strict_ties && table != TABLE_GLOBAL_BITMAP && !kn.no_inkernel;
+    a.merge_entries = merge_entries_for(slots, s.strict_kernel);  // merge_list's scatter buffer
+    size_t table_bytes = 0;
     if (table != TABLE_GLOBAL_BITMAP) {
-        // buckets of 8 cells: the id's top (tb - 3) bits select the bucket, the cell keeps the other restbits bits
-        // next to a 2-bit bucket displacement and the valid bit (16-bit cells: restbits <= 13)
-        uint32_t tb = std::max(3u, std::min(tbits, idbits + 3u));
-        if (idbits - (tb - 3u) <= 13u) {
-            table = TABLE_LDS_CELL16;
-            a.restbits = idbits - (tb - 3u);
-            s.lds += (size_t)2 << tb;
-        } else {
-            table = TABLE_LDS_CELL32;
-            s.lds += (size_t)4 << tb;
-        }
-        a.tbits = tb;
+        // (the largest table the device's LDS limit leaves room for: the one asked for at every shape of 64 KiB and less)
+        const size_t behind = ((size_t)a.merge_entries + (s.strict_kernel ? CAND_LDS_MIN : 0u)) * sizeof(hent_t);
+        const VisitedTable t = fit_visited_table(tile_bytes, tbits, idbits, behind, ix.lds_limit_);
+        table = t.table;
+        if (t.table == TABLE_LDS_CELL16) a.restbits = t.restbits;
+        a.tbits = t.tb;
+        table_bytes = t.bytes;
     }
     a.idbits = idbits;
-    s.strict_kernel = strict_ties && table != TABLE_GLOBAL_BITMAP && !kn.no_inkernel;
     // the kernel that knows its row stride and ef, where the replica and the call have that shape and it was built (HNSWGPU_NO_SHAPE:
     // never -- the A/B switch and test hook; answers and work counters are the same either way)
     s.shape = !kn.no_shape && v.row_stride == 128u && ef == 64u * (uint64_t)slots && shape_r128_ef_built(metric, slots, table) ? SHAPE_R128_EF : SHAPE_ANY;
-    if (slots <= (s.strict_kernel ? HNSW_MERGE_SMAX : HNSW_MERGE_LEAN_SMAX)) {  // merge_list's scatter buffer
-        a.merge_entries = (uint32_t)slots * 64u + 64u;
-        s.lds += (size_t)a.merge_entries * sizeof(hent_t);
-    }
+    s.lds = search_lds_bytes(tile_bytes, table_bytes, a.merge_entries, 0);
     s.per_cu = 0;
     s.strict_cap = STRICT_WG_PER_CU;
     if (kn.strict_wg_per_cu > 0) s.strict_cap = kn.strict_wg_per_cu;  // tuning hook (reported by HNSWGPU_TRACE_LAUNCH)
@@ -1079,10 +1082,11 @@ int DeviceIndex::SearchCall::shape_launch(SearchArgs& a, LaunchShape& s) {
         // top levels of the (lazy) literal candidate heap, for the few pops that need it: 512 entries when that costs no
         // resident wave (the strict kernel sits at 4 waves per SIMD by its registers, which leaves ~10 KB of LDS per
         // wave), else 256 -- a replay touches the heap ~800 times per query, every level out of LDS is an L2 round trip
-        a.cand_lds = 256;
+        a.cand_lds = CAND_LDS_MIN;
+        const uint32_t room = (uint32_t)std::min<size_t>(4096, (ix.lds_limit_ - std::min(ix.lds_limit_, s.lds)) / sizeof(hent_t));  // entries the limit leaves
         if (kn.cand_lds >= 0) {
-            a.cand_lds = (uint32_t)std::min(4096, kn.cand_lds);  // tuning hook
-        } else {
+            a.cand_lds = std::min((uint32_t)std::min(4096, kn.cand_lds), room);  // tuning hook
+        } else if (room >= 512u) {
             int occ256 = 0, occ512 = 0;
             HIP_TRY(search_occupancy(s.shape, true, s.lds + 256 * sizeof(hent_t), &occ256));
             HIP_TRY(search_occupancy(s.shape, true, s.lds + 512 * sizeof(hent_t), &occ512));
@@ -1159,8 +1163,12 @@ int DeviceIndex::SearchCall::relaunch_loop() {
         qlist = w.retry[pingpong].as<uint32_t>();
         pingpong ^= 1;
         if (table == TABLE_GLOBAL_BITMAP) { err = "internal error: bitmap visited set reported an overflow"; return ERR_DEVICE; }
-        if (!grown && tbits < 14u) {
-            tbits = std::min<uint32_t>(14u, tbits + 2u);
+        // (a grown table that the LDS limit clamps back to this launch's size answers nothing new: the bitmap is next)
+        const uint32_t grown_bits = std::min<uint32_t>(14u, tbits + 2u);
+        const size_t behind = ((size_t)a.merge_entries + (s.strict_kernel ? CAND_LDS_MIN : 0u)) * sizeof(hent_t);
+        const VisitedTable g = fit_visited_table(tile_bytes, grown_bits, idbits, behind, ix.lds_limit_);
+        if (!grown && tbits < 14u && (!g.clamped || g.tb > a.tbits)) {
+            tbits = grown_bits;
             grown = true;
         } else {
             table = TABLE_GLOBAL_BITMAP;
@@ -1502,6 +1510,11 @@ public:
         hipDeviceProp_t prop;
         HIP_TRY(hipGetDeviceProperties(&prop, device_));
         num_cu_ = prop.multiProcessorCount;
+        int lds_limit = 0;
+        HIP_TRY(hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device_));
+        lds_limit_ = (size_t)std::max(0, lds_limit);
+        err = lds_refusal(d, tile_bytes_for(dist, (uint32_t)((d + 31) / 32 * 32)), lds_limit_);
+        if (!err.empty()) return ERR_ARG;
         n_ = n;
         dist_ = dist;
         ef_c_ = (uint32_t)ef_construction;
@@ -1611,7 +1624,18 @@ public:
         a.idbits = idbits;
         a.restbits = idbits - (tbits - 3u);
         a.tile_bytes = tile_bytes_for(dist_, row_stride_);
-        const size_t lds = a.tile_bytes + IDS_BYTES + ((size_t)2 << tbits);
+        // (the LDS limit: a smaller table where 16-bit cells allow it -- the searches that outgrow it migrate to their bitmap slice)
+        while (build_search_lds_bytes(a.tile_bytes, tbits) > lds_limit_ && tbits > 3u && idbits - (tbits - 1u - 3u) <= 13u) {
+            --tbits;
+            a.tbits = tbits;
+            a.restbits = idbits - (tbits - 3u);
+        }
+        const size_t lds = build_search_lds_bytes(a.tile_bytes, tbits);
+        if (lds > lds_limit_) {
+            err = "GPU-assisted construction: rows of " + std::to_string(row_stride_) + " elements and " + std::to_string(n_) + " points need " +
+                  std::to_string(lds) + " bytes of LDS per workgroup, the device's limit is " + std::to_string(lds_limit_);
+            return ERR_ARG;
+        }
         const KernelSet& ks = kernel_set(dist_);
         int per_cu = 0;
         HIP_TRY(ks.build_occupancy(slots_per_lane, lds, &per_cu));
@@ -1673,7 +1697,7 @@ public:
             sa.sel_n = sel_n_.as<uint32_t>();
             sa.work_counter = static_cast<uint32_t*>(d_ctrl_);
             HIP_TRY(hipMemset(d_ctrl_, 0, 8));
-            const size_t sel_lds = a.tile_bytes + IDS_BYTES + (size_t)sel_stride * 8u;
+            const size_t sel_lds = build_select_lds_bytes(a.tile_bytes, sel_stride);
             uint32_t sgrid = (uint32_t)std::min<uint64_t>((uint64_t)num_cu_ * 24u, slots);
             if (kn.build_wg > 0) sgrid = std::min<uint32_t>(sgrid, (uint32_t)kn.build_wg);
             HIP_TRY(ks.launch_build_select(sgrid, sel_lds, nullptr, sa));
@@ -1707,6 +1731,7 @@ public:
 private:
     int device_;
     int num_cu_ = 0;
+    size_t lds_limit_ = 0;  // hipDeviceAttributeMaxSharedMemoryPerBlock of the build device
     int dist_ = DIST_L2;
     uint64_t n_ = 0;
     uint32_t ef_c_ = 0, row_stride_ = 0, max_window_ = 1, max_stride_ = 0;
@@ -1767,6 +1792,13 @@ int eval_distance_matrix_impl(int dist, const float* queries, uint64_t nq, const
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { err = "no HIP device visible"; return ERR_DEVICE; }
     const uint32_t rs = (uint32_t)((d + 31) / 32 * 32);
+    {   // rows whose tile fits no launch on the current device: refused as the search refuses them, before anything is launched
+        int dev = 0, lds_limit = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        HIP_TRY(hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+        err = lds_refusal(d, tile_bytes_for(km, rs), (size_t)std::max(0, lds_limit));
+        if (!err.empty()) return ERR_ARG;
+    }
     const size_t elem = half_rows ? sizeof(uint16_t) : sizeof(float);  // of a stored row
     std::vector<float> pq((size_t)nq * rs, 0.f);
     std::vector<unsigned char> pr((size_t)n * rs * elem, (unsigned char)0);

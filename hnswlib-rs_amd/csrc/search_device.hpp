@@ -251,6 +251,7 @@ private:
     int dist_ = DIST_L2;
     int storage_ = STORAGE_F32;   // of the rows at d_vec_ (fixed by upload())
     int num_cu_ = 0;
+    size_t lds_limit_ = 0;  // hipDeviceAttributeMaxSharedMemoryPerBlock of the replica's device: what a workgroup's LDS may add up to
     uint64_t bytes_ = 0;
     // the replica (read-only after upload)
     void* d_vec_ = nullptr;

@@ -256,6 +256,88 @@ inline uint32_t tile_bytes_for(int metric, uint32_t row_stride) {
 inline size_t pair_lds_bytes(uint32_t tile_bytes, uint32_t tb, uint32_t ef) {
     return 2u * (size_t)tile_bytes + 2u * IDS_BYTES + 2u * ((size_t)2 << tb) + 2u * (size_t)((ef + 2u) & ~1u) * sizeof(hent_t) + 2u * 16u * sizeof(hent_t) + 2u * 16u * 4u;
 }
+// ---- The LDS of a workgroup, launch by launch.  Pure host arithmetic -- no allocation, no HIP call -- so that the driver, the
+// builder's backend and the tests add up the same bytes.  `limit` is hipDeviceAttributeMaxSharedMemoryPerBlock of the replica's
+// device (DeviceIndex::lds_limit_): a launch that asks for more does not start.
+// the greedy descent: one query tile, or two (hnsw_descend_pair_kernel), and the id buffer
+inline size_t descend_lds_bytes(uint32_t tile_bytes, bool pair) { return (pair ? 2u : 1u) * (size_t)tile_bytes + IDS_BYTES; }
+// merge_list's scatter buffer behind the visited table: 64 S + 64 entries up to HNSW_MERGE_SMAX (lean: HNSW_MERGE_LEAN_SMAX) slots
+inline uint32_t merge_entries_for(int slots, bool strict_kernel) {
+    return slots <= (strict_kernel ? HNSW_MERGE_SMAX : HNSW_MERGE_LEAN_SMAX) ? (uint32_t)slots * 64u + 64u : 0u;
+}
+// the visited table of a one-query launch: buckets of 8 cells, the id's top (tb - 3) bits select the bucket, the cell keeps the other
+// restbits bits next to a 2-bit bucket displacement and the valid bit -- 16-bit cells where restbits <= 13, else 32-bit cells
+struct VisitedTable {
+    int table;          // TABLE_LDS_CELL16 / TABLE_LDS_CELL32
+    uint32_t tb;        // 2^tb cells
+    uint32_t restbits;  // (16-bit cells)
+    size_t bytes;
+    bool clamped;       // fit_visited_table: smaller than asked for, because of the limit
+};
+inline VisitedTable visited_table_for(uint32_t tbits, uint32_t idbits) {
+    VisitedTable t{};
+    t.tb = tbits < idbits + 3u ? tbits : idbits + 3u;
+    if (t.tb < 3u) t.tb = 3u;
+    if (idbits - (t.tb - 3u) <= 13u) {
+        t.table = TABLE_LDS_CELL16;
+        t.restbits = idbits - (t.tb - 3u);
+        t.bytes = (size_t)2 << t.tb;
+    } else {
+        t.table = TABLE_LDS_CELL32;
+        t.bytes = (size_t)4 << t.tb;
+    }
+    return t;
+}
+// one-query search kernels (SearchCall::shape_launch): tile, ids, visited table (0 bytes: TABLE_GLOBAL_BITMAP), merge_list's buffer,
+// and in a strict launch the top cand_lds entries of the literal candidate heap
+inline size_t search_lds_bytes(uint32_t tile_bytes, size_t table_bytes, uint32_t merge_entries, uint32_t cand_lds) {
+    return (size_t)tile_bytes + IDS_BYTES + table_bytes + ((size_t)merge_entries + cand_lds) * sizeof(hent_t);
+}
+constexpr uint32_t CAND_LDS_MIN = 256;  // what a strict launch keeps of its literal heap in LDS at the least
+// the largest table of at most 2^tbits cells with which a launch fits the limit: the table of visited_table_for(tbits, idbits) wherever
+// that fits (every shape of 64 KiB and less); else tb goes down -- the queries that outgrow the smaller table move to the bitmap
+// inside the launch, as they do from any table.  behind_bytes: what the launch keeps behind the table (merge buffer, CAND_LDS_MIN
+// entries of the literal heap).  (A replica whose tile leaves no room for the smallest table is refused before: lds_refusal.)
+inline VisitedTable fit_visited_table(uint32_t tile_bytes, uint32_t tbits, uint32_t idbits, size_t behind_bytes, size_t limit) {
+    VisitedTable t = visited_table_for(tbits, idbits);
+    const uint32_t asked = t.tb;
+    while (t.tb > 3u && (size_t)tile_bytes + IDS_BYTES + t.bytes + behind_bytes > limit) t = visited_table_for(t.tb - 1u, idbits);
+    t.clamped = t.tb != asked;
+    return t;
+}
+// the literal-heap kernel (SearchCall::run_exact): [query][ids][return_points: ef + 2 entries, or what fits][top of candidate_points]
+// in max(10 KiB, tile + ids + 4 KiB) -- resident workgroups are what that kernel lives on
+struct ExactLds {
+    uint32_t r_lds_cap, cand_lds;
+    size_t lds;
+};
+inline ExactLds exact_lds(uint32_t tile_bytes, uint64_t ef, uint64_t cand_cap) {
+    const uint64_t fixed = (uint64_t)tile_bytes + IDS_BYTES;
+    const uint64_t budget = (fixed + 4096 > 10 * 1024 ? fixed + 4096 : 10 * 1024) - fixed;
+    ExactLds x{};
+    const uint64_t r = budget / 2 / sizeof(hent_t);
+    x.r_lds_cap = (uint32_t)(ef + 2 < r ? ef + 2 : r);
+    const uint64_t c = (budget - (uint64_t)x.r_lds_cap * sizeof(hent_t)) / sizeof(hent_t);
+    x.cand_lds = (uint32_t)(cand_cap < c ? cand_cap : c);
+    x.lds = (size_t)(fixed + ((uint64_t)x.r_lds_cap + x.cand_lds) * sizeof(hent_t));
+    return x;
+}
+// construction: the searches of a window (tile, ids, a table of 2^tbits 16-bit cells) and select_neighbours (tile, ids, the selection)
+inline size_t build_search_lds_bytes(uint32_t tile_bytes, uint32_t tbits) { return (size_t)tile_bytes + IDS_BYTES + ((size_t)2 << tbits); }
+inline size_t build_select_lds_bytes(uint32_t tile_bytes, uint32_t sel_stride) { return (size_t)tile_bytes + IDS_BYTES + (size_t)sel_stride * 8u; }
+// What a replica must be able to launch whatever the call asks for: the tile and its ids with the parts no clamp can shrink -- the
+// smallest visited table (8 cells of 32 bits), merge_list's buffer at four slots and CAND_LDS_MIN entries of the literal heap.  The
+// literal-heap kernel (+ 4096), a selection of 512 entries (+ 4096) and the descent of one query per wavefront need less.
+inline size_t min_workgroup_lds_bytes(uint32_t tile_bytes) {
+    return search_lds_bytes(tile_bytes, 32, merge_entries_for(HNSW_MERGE_SMAX, true), CAND_LDS_MIN);
+}
+// Rows too long for this device: the message of the refusal (HNSWGPU_ERR_ARG), empty where the tile fits
+inline std::string lds_refusal(uint64_t d, uint32_t tile_bytes, size_t limit) {
+    const size_t need = min_workgroup_lds_bytes(tile_bytes);
+    if (need <= limit) return std::string();
+    return "rows of d = " + std::to_string(d) + " elements are too long for this device: a workgroup needs " + std::to_string(need) +
+           " bytes of LDS for the query tile and the smallest search state, the device's limit is " + std::to_string(limit) + " bytes per workgroup";
+}
 // kernels_for<METRIC>(): defined in part 2 of that metric's translation units (search_kernels_tu.hip)
 template <int METRIC> const KernelSet& kernels_for();
 template <> const KernelSet& kernels_for<DIST_L2>();

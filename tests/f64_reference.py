@@ -370,6 +370,10 @@ def common_reachable_set(h):
 # every dimension 1..130 (every residue mod 8, 32 and 64 of the lane groups) and the larger residues the device sweeps use
 SWEEP_D = tuple(sorted(set(list(range(1, 131)) + [159, 160, 161, 191, 192, 193, 255, 256, 257, 300, 383, 384, 385, 511, 512, 513,
                                                   640, 767, 768, 769, 783, 784, 785, 799, 800])))
+# rows as long as the ones people index (1024 .. 4096 wide) and up to where U_EFF is stated: the powers of two with their neighbours,
+# 1054 / 1055 / 1056 for DistCosine (the norm in the last two floats of a stride of 1056, then beside the row).  A tuple of its own:
+# the tests parametrised on SWEEP_D stay as quick as they are
+LONG_D = (801, 832, 1023, 1024, 1025, 1054, 1055, 1056, 1536, 2047, 2048, 3072, 4095, 4096, 4097, 6144, 7999, 8000)
 
 
 def _mixed(rng, shape, lo, hi, signed=True):
