@@ -224,6 +224,56 @@ class SpanningForestResult:
             sizes[number[r]] += 1
         return ComponentsResult(labels, np.array(sizes, np.uint32), len(sizes))
 
+    def dendrogram(self, device=0):
+        """The single-linkage dendrogram of this forest's edges in their order (forest_dendrogram), with the edges and weights
+        carried along: a DendrogramResult."""
+        m = self.n_edges
+        d = forest_dendrogram(self.n_vertices, self.a[:m], self.b[:m], device)
+        return DendrogramResult(d.left, d.right, d.sizes, m, self.n_vertices, self.a[:m], self.b[:m], self.weights[:m])
+
+
+class DendrogramResult:
+    """The single-linkage dendrogram of a forest (forest_dendrogram, SpanningForestResult.dendrogram, Hnsw.knn_graph_dendrogram):
+    merge e joins the clusters left[e] and right[e] into cluster n_vertices + e of sizes[e] vertices.  Cluster ids are scipy's: an
+    id below n_vertices is that vertex alone.  a, b, weights: the forest's edges where the call had them, else None."""
+
+    def __init__(self, left, right, sizes, n_edges, n_vertices, a=None, b=None, weights=None):
+        self.left, self.right, self.sizes, self.n_edges, self.n_vertices = left, right, sizes, n_edges, n_vertices
+        self.a, self.b, self.weights = a, b, weights
+
+    def linkage(self):
+        """scipy's linkage matrix, float64[n_edges, 4]: left, right, weight, size.  (scipy itself accepts it when the forest is
+        connected and the weights ascend, which a minimum spanning forest's do.)"""
+        if self.weights is None:
+            raise HnswError(N.ERR_ARG, "linkage() needs the merges' heights: this dendrogram was made without weights")
+        m = self.n_edges
+        z = np.empty((m, 4), np.float64)
+        z[:, 0], z[:, 1], z[:, 2], z[:, 3] = self.left[:m], self.right[:m], self.weights[:m], self.sizes[:m]
+        return z
+
+    def roots(self):
+        """The ids of the clusters that are nobody's child, ascending: one per component of the forest."""
+        m = self.n_edges
+        child = np.zeros(self.n_vertices + m, bool)
+        child[self.left[:m]] = True
+        child[self.right[:m]] = True
+        return np.flatnonzero(~child).astype(np.uint32)
+
+
+def forest_dendrogram(n, a, b, device=0):
+    """The dendrogram of the forest whose edge e joins vertices a[e] and b[e] of 0 .. n - 1, built on `device`: the edges' order is
+    the merge order.  Refuses (HnswError, ERR_ARG) an end >= n, a self-loop, more than n - 1 edges and a cycle.  Returns a
+    DendrogramResult without a, b and weights."""
+    a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
+    b = np.ascontiguousarray(b, dtype=np.uint32).reshape(-1)
+    if len(a) != len(b):
+        raise HnswError(N.ERR_ARG, f"a has {len(a)} entries, b has {len(b)}")
+    m = len(a)
+    left, right, sizes = np.zeros(m, np.uint32), np.zeros(m, np.uint32), np.zeros(m, np.uint32)
+    _check(N.lib().hnswgpu_forest_dendrogram(device, n, m, _p(a) if m else None, _p(b) if m else None, _p(left) if m else None,
+                                             _p(right) if m else None, _p(sizes) if m else None))
+    return DendrogramResult(left, right, sizes, m, n)
+
 
 def csr_spanning_forest(offsets, cols, dists=None, device=0):
     """The minimum spanning forest of ANY graph given in CSR (offsets u64[n + 1], cols u32[offsets[n]], dists f32 per entry or None:
@@ -748,6 +798,31 @@ class Hnsw:
         _check(self._lib.hnswgpu_graph_spanning_forest(self._h, knbn, 0 if ef is None else ef, modes[mode], core_k, _p(a), _p(b), _p(w), _p(m)))
         m = int(m[0])
         return SpanningForestResult(a[:m].copy(), b[:m].copy(), w[:m].copy(), m, n)
+
+    def knn_graph_dendrogram(self, knbn, ef=None, mode="union", core_k=0):
+        """knn_graph_spanning_forest(knbn, ef, mode, core_k) and the single-linkage dendrogram of that forest in one call, the forest
+        staying on the device in between.  Returns a DendrogramResult whose a, b and weights are that forest's, byte for byte."""
+        modes = {"union": N.HEADER.constants["HNSWGPU_SYM_UNION"], "mutual": N.HEADER.constants["HNSWGPU_SYM_MUTUAL"]}
+        if mode not in modes:
+            raise HnswError(N.ERR_ARG, f"mode must be 'union' or 'mutual', not {mode!r}")
+        if ef is not None and ef < 1:
+            raise HnswError(N.ERR_ARG, "ef must be >= 1 (ef=None: the exact graph)")
+        if core_k < 0:
+            raise HnswError(N.ERR_ARG, "core_k must be >= 0")
+        n = self.get_nb_point()
+        slots = max(n - 1, 1)
+        a, b, w, m = np.zeros(slots, np.uint32), np.zeros(slots, np.uint32), np.zeros(slots, np.float32), np.zeros(1, np.uint64)
+        left, right, sizes = np.zeros(slots, np.uint32), np.zeros(slots, np.uint32), np.zeros(slots, np.uint32)
+        if self._h is None:
+            if knbn < 1:
+                raise HnswError(N.ERR_ARG, "knbn must be > 0")
+            if core_k > knbn:
+                raise HnswError(N.ERR_ARG, "core_k is above knbn")
+            return DendrogramResult(left[:0], right[:0], sizes[:0], 0, 0, a[:0], b[:0], w[:0])
+        _check(self._lib.hnswgpu_graph_dendrogram(self._h, knbn, 0 if ef is None else ef, modes[mode], core_k, _p(a), _p(b), _p(w), _p(left),
+                                                  _p(right), _p(sizes), _p(m)))
+        m = int(m[0])
+        return DendrogramResult(left[:m].copy(), right[:m].copy(), sizes[:m].copy(), m, n, a[:m].copy(), b[:m].copy(), w[:m].copy())
 
     def knn_graph_recall(self, knbn, ef, point_ids=None):
         """The recall by id of knn_graph_flat against exact_knn_graph_flat over the named points: the share of the exact

@@ -1511,6 +1511,110 @@ int hnswgpu_csr_spanning_forest_device(int device, uint64_t n, const uint64_t* d
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
+// ---- dendrogram: of a forest given as an edge list, and of the k-NN graph's own forest (dendrogram.hip holds the device side)
+extern "C++" {
+namespace hnswgpu {
+__attribute__((weak)) int forest_dendrogram(const DendrogramArgs&, bool, void*, std::string&);
+__attribute__((weak)) int graph_dendrogram(DeviceIndex&, const std::vector<uint64_t>&, const GraphDendrogramArgs&, bool, void*, std::string&);
+}  // namespace hnswgpu
+}  // extern "C++"
+// what both forest entries can check without reading an array
+static int forest_dendrogram_call(const DendrogramArgs& a) {
+    if (a.n > 0x7FFFFFFFull) return fail(HNSWGPU_ERR_ARG, "forest dendrogram: n = " + std::to_string(a.n) + " vertices, above 2^31 - 1");
+    if (a.m > std::max<uint64_t>(a.n, 1) - 1)
+        return fail(HNSWGPU_ERR_ARG, "forest dendrogram: m = " + std::to_string(a.m) + " edges among n = " + std::to_string(a.n) +
+                                         " vertices: a forest has at most n - 1");
+    if (a.m != 0 && (!a.a || !a.b)) return fail(HNSWGPU_ERR_ARG, "null a or b");
+    if (a.m != 0 && (!a.out_left || !a.out_right || !a.out_size)) return fail(HNSWGPU_ERR_ARG, "null out_left, out_right or out_size");
+    return HNSWGPU_OK;
+}
+
+int hnswgpu_forest_dendrogram(int device, uint64_t n, uint64_t m, const uint32_t* a, const uint32_t* b, uint32_t* out_left, uint32_t* out_right,
+                              uint32_t* out_size) {
+    CAPI_GUARD_BEGIN
+    const DendrogramArgs args{device, n, m, a, b, out_left, out_right, out_size};
+    const int rc = forest_dendrogram_call(args);
+    if (rc != HNSWGPU_OK) return rc;
+    if (m == 0) return HNSWGPU_OK;  // no merge: no array is read or written
+    // the ends as the device form's kernel checks them (a cycle is the device's to find)
+    for (uint64_t e = 0; e < m; ++e) {
+        if (a[e] >= n || b[e] >= n)
+            return fail(HNSWGPU_ERR_ARG, "forest dendrogram: edge " + std::to_string(e) + " has an end that is not below n");
+        if (a[e] == b[e]) return fail(HNSWGPU_ERR_ARG, "forest dendrogram: edge " + std::to_string(e) + " joins a vertex to itself");
+    }
+    if (!hnswgpu::forest_dendrogram) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    std::string err;
+    return finish(hnswgpu::forest_dendrogram(args, true, nullptr, err), err);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswgpu_forest_dendrogram_device(int device, uint64_t n, uint64_t m, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out_left,
+                                     uint32_t* d_out_right, uint32_t* d_out_size, void* stream) {
+    CAPI_GUARD_BEGIN
+    const DendrogramArgs args{device, n, m, d_a, d_b, d_out_left, d_out_right, d_out_size};
+    const int rc = forest_dendrogram_call(args);
+    if (rc != HNSWGPU_OK) return rc;
+    if (m == 0) return HNSWGPU_OK;
+    if (!hnswgpu::forest_dendrogram) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    std::string err;
+    return finish(hnswgpu::forest_dendrogram(args, false, stream, err), err);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+// the checks both index entries share: the forest call's own, then the three new arrays; the handle's lock is held (shared)
+static int graph_dendrogram_call(const hnswgpu_index* idx, const GraphDendrogramArgs& a) {
+    const int rc = graph_spanning_forest_call(idx, a.forest);
+    if (rc != HNSWGPU_OK) return rc;
+    if (index_nb_point(idx) >= 2 && (!a.out_left || !a.out_right || !a.out_size))
+        return fail(HNSWGPU_ERR_ARG, "null out_left, out_right or out_size");
+    return HNSWGPU_OK;
+}
+
+int hnswgpu_graph_dendrogram(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k, uint32_t* out_a, uint32_t* out_b,
+                             float* out_w, uint32_t* out_left, uint32_t* out_right, uint32_t* out_size, uint64_t* out_n_edges) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    const GraphDendrogramArgs a{ForestArgs{k, ef, mode, core_k, out_a, out_b, out_w, out_n_edges}, out_left, out_right, out_size};
+    int rc = graph_dendrogram_call(idx, a);
+    if (rc != HNSWGPU_OK) return rc;
+    if (index_nb_point(idx) <= 1) {  // no vertex, or one: no edge, nothing else written
+        *out_n_edges = 0;
+        return HNSWGPU_OK;
+    }
+    if (!hnswgpu::graph_dendrogram) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = primary_f32_replica(idx, sl, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    return finish(hnswgpu::graph_dendrogram(*dev, idx->flat->origin_id, a, true, nullptr, err), err);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswgpu_graph_dendrogram_device(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k, uint32_t* d_out_a,
+                                    uint32_t* d_out_b, float* d_out_w, uint32_t* d_out_left, uint32_t* d_out_right, uint32_t* d_out_size,
+                                    uint64_t* out_n_edges, void* stream) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    const GraphDendrogramArgs a{ForestArgs{k, ef, mode, core_k, d_out_a, d_out_b, d_out_w, out_n_edges}, d_out_left, d_out_right, d_out_size};
+    int rc = graph_dendrogram_call(idx, a);
+    if (rc != HNSWGPU_OK) return rc;
+    if (index_nb_point(idx) <= 1) {
+        *out_n_edges = 0;
+        return HNSWGPU_OK;
+    }
+    if (!hnswgpu::graph_dendrogram) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = resident_replica(idx, true, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    return finish(hnswgpu::graph_dendrogram(*dev, idx->flat->origin_id, a, false, stream, err), err);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
 static DeviceIndex* any_replica(hnswgpu_index* idx) {
     if (idx->primary >= 0 && idx->replica(idx->primary)) return idx->replica(idx->primary);
     return nullptr;

@@ -1,5 +1,5 @@
 // capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h, for the translation units
-// that implement entry points of the C ABI (capi.cpp; exact_knn.hip; range_search.hip; symmetric_graph.hip; graph_components.hip; spanning_forest.hip).  Private: not installed, not part of the ABI.
+// that implement entry points of the C ABI (capi.cpp; exact_knn.hip; range_search.hip; symmetric_graph.hip; graph_components.hip; spanning_forest.hip; dendrogram.hip).  Private: not installed, not part of the ABI.
 // The checks that entries share (empty index, resident replica, sorted filter, the shape and contents of a filter set, the limits of
 // an exact call, the zeroed k-NN answer, the tail) live once, in capi.cpp; what an entry outside capi.cpp needs of them is declared
 // below as capi_*.  A new pair of entries calls them.  The HIP host helpers of the .hip units (HIP_TRY, DeviceGuard, DevMem,
@@ -195,6 +195,28 @@ struct CsrForestArgs {
     uint64_t* out_n;
 };
 int csr_spanning_forest(const CsrForestArgs& a, bool host, void* stream, std::string& err);
+// the device side of hnswgpu_forest_dendrogram(_device) and hnswgpu_graph_dendrogram(_device), defined in dendrogram.hip and referred
+// to weakly in the same way (the arguments have been checked; forest form: 1 <= m <= n - 1; index form: at least two vertices).
+// host: the arrays are plain host memory -- a forest form's ends have then passed their checks on the host --; else device memory
+// and `stream` is the caller's.  forest_dendrogram returns ERR_ARG, no out slot written, when an end is not below n, an edge joins a
+// vertex to itself or the edges hold a cycle.  graph_dendrogram runs graph_spanning_forest into device memory and goes on from there.
+struct DendrogramArgs {
+    int device;
+    uint64_t n, m;
+    const uint32_t* a;    // [m]
+    const uint32_t* b;    // [m]
+    uint32_t* out_left;   // [m]
+    uint32_t* out_right;  // [m]
+    uint32_t* out_size;   // [m]
+};
+int forest_dendrogram(const DendrogramArgs& a, bool host, void* stream, std::string& err);
+struct GraphDendrogramArgs {
+    ForestArgs forest;    // out_n is host memory either way
+    uint32_t* out_left;   // [n - 1]
+    uint32_t* out_right;  // [n - 1]
+    uint32_t* out_size;   // [n - 1]
+};
+int graph_dendrogram(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphDendrogramArgs& a, bool host, void* stream, std::string& err);
 }  // namespace hnswgpu
 
 // No C++ exception may cross the C ABI: every entry point is `try { ... HNSWGPU_CAPI_GUARD_END(ret)`

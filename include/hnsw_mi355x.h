@@ -749,7 +749,7 @@ int hnswgpu_csr_components_device(int device, uint64_t n, const uint64_t* d_offs
  * back; there are at most ceil(log2 n) + 1 rounds, and the bound is hard (a round past it would be HNSWGPU_ERR_FORMAT, an internal
  * error).  The answer is a function of D alone, two calls give the same bytes.  Takes the handle's lock shared, like a search, and
  * is legal from several host threads at once.  Host buffers; uploads the index on first use.
- * Out of scope: the dendrogram itself (cluster sizes, condensed tree, stability); a filter or a subset of points; F16 storage;
+ * Out of scope: the condensed tree and stabilities (the dendrogram itself is the next section); a filter or a subset of points; F16 storage;
  * sharding over GPUs; weights other than stored distances and their core maxima.                                              */
 int hnswgpu_graph_spanning_forest(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k,
                                   uint32_t* out_a, uint32_t* out_b, float* out_w, uint64_t* out_n_edges);
@@ -773,6 +773,55 @@ int hnswgpu_csr_spanning_forest(int device, uint64_t n, const uint64_t* offsets,
  * runs: a bad graph is HNSWGPU_ERR_ARG, never a fault.                                                                        */
 int hnswgpu_csr_spanning_forest_device(int device, uint64_t n, const uint64_t* d_offsets, const uint32_t* d_cols, const float* d_dists,
                                        uint32_t* d_out_a, uint32_t* d_out_b, float* d_out_w, uint64_t* out_n_edges, void* stream);
+
+/* ---------------------------------------------------------------- dendrogram of a forest --- */
+/* The single-linkage dendrogram that a forest's edges, read in their order, encode: for every edge the two clusters it merges and
+ * the size of the result -- the table scipy.cluster.hierarchy, HDBSCAN's condensed tree and every "cut into K clusters" start from.
+ *   input     m edges over the vertices 0 .. n - 1 on `device`; edge e joins a[e] and b[e].  The order given IS the merge order:
+ *             edge e is merge number e.  Weights are no argument: the height of merge e is whatever weight the caller holds for
+ *             edge e.  out_a, out_b and *out_n_edges of hnswgpu_graph_spanning_forest(_device) and
+ *             hnswgpu_csr_spanning_forest(_device) are valid inputs as they stand.
+ *   ids       scipy's convention: id v < n is the vertex v alone, id n + i the cluster made by edge i.
+ *   answer    out_left[e]: the id of the cluster that holds a[e] just before merge e, i.e. the component of a[e] under the edges
+ *             0 .. e - 1 -- a[e] itself if no earlier edge touches it, else n + the largest edge index inside it.  out_right[e]: the
+ *             same for b[e].  out_size[e]: the number of vertices of cluster n + e = size(left) + size(right), a vertex counting 1.
+ *             Nothing is written behind slot m - 1.  m == 0: HNSWGPU_OK, no array is read or written.
+ *   refused   HNSWGPU_ERR_ARG, no out slot touched: n > 2^31 - 1; m > max(n, 1) - 1 (a forest has at most n - 1 edges); with
+ *             m >= 1 a NULL a, b, out_left, out_right or out_size; an end >= n; a[e] == b[e]; a cycle, i.e. an edge whose ends
+ *             earlier edges already join (a repeated pair is one).  Ends and self-loops are checked on the host first, so those
+ *             refusals need no device; a cycle is the device's to find.
+ *   memory    16 (n + m) + 8 m bytes (and padding to 256 per array, and one word): the edges' two current labels, and per cluster
+ *             id a parent, a last edge, a sum and a size.  The host form uploads its ends into the labels and downloads its answer
+ *             from that scratch: it stages nothing more.
+ * ceil(log2 m) levels of eight small launches over the lock-free union-find of the components, integer atomics only: level by level
+ * the upper half of every aligned block of edge indices learns what the lower half merged.  The bound is hard; no wavefront waits
+ * on another and nothing is read back inside the loop -- one word, at the end, before any out slot is written.  The answer is a
+ * function of the edge list alone: two calls give the same bytes.  Needs no index; legal from several host threads at once.
+ * Out of scope: the condensed tree, stabilities and cluster selection of HDBSCAN; a dendrogram of anything that is not a forest;
+ * reordering of the rows (scipy wants ascending heights: an edge list sorted by weight gives them).                            */
+int hnswgpu_forest_dendrogram(int device, uint64_t n, uint64_t m, const uint32_t* a, const uint32_t* b,
+                              uint32_t* out_left, uint32_t* out_right, uint32_t* out_size);
+/* The same with the five arrays in HBM of `device`, on HIP stream `stream`, waited for.  Ends and self-loops are checked by a kernel
+ * of its own, which hands the levels scratch copies that are in range: a bad edge list is HNSWGPU_ERR_ARG, never a fault.  That
+ * check and the cycle flag share ONE word, the only thing read back.                                                           */
+int hnswgpu_forest_dendrogram_device(int device, uint64_t n, uint64_t m, const uint32_t* d_a, const uint32_t* d_b,
+                                     uint32_t* d_out_left, uint32_t* d_out_right, uint32_t* d_out_size, void* stream);
+/* hnswgpu_graph_spanning_forest followed by the dendrogram of its forest, which never leaves HBM in between.  out_a, out_b, out_w
+ * and *out_n_edges are what hnswgpu_graph_spanning_forest writes with the same arguments, byte for byte; out_left, out_right and
+ * out_size are the dendrogram of those edges in that order (ascending weight: the rows are scipy's linkage rows in scipy's order),
+ * with the same max(n - 1, 0) slots, those behind the answer not touched.  Every refusal is that call's, with the same words; with
+ * n >= 2 a NULL out_left, out_right or out_size is HNSWGPU_ERR_ARG too.  n <= 1: 0 edges, HNSWGPU_OK, nothing else written.  On
+ * any error no out slot is touched.  Memory: the forest call's, then 12 (n - 1) bytes of forest and the dendrogram's
+ * 16 (n + m) + 8 m.  Takes the handle's lock shared; host buffers; uploads the index on first use.                               */
+int hnswgpu_graph_dendrogram(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k,
+                             uint32_t* out_a, uint32_t* out_b, float* out_w,
+                             uint32_t* out_left, uint32_t* out_right, uint32_t* out_size, uint64_t* out_n_edges);
+/* The same with the six arrays in HBM, on HIP stream `stream`, waited for; out_n_edges stays a host pointer.  The index must be
+ * uploaded (else HNSWGPU_ERR_DEVICE).  The forest is written into the caller's arrays directly: nothing is staged.              */
+int hnswgpu_graph_dendrogram_device(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k,
+                                    uint32_t* d_out_a, uint32_t* d_out_b, float* d_out_w,
+                                    uint32_t* d_out_left, uint32_t* d_out_right, uint32_t* d_out_size, uint64_t* out_n_edges,
+                                    void* stream);
 
 /* Test entry: the lane lab. The wave-level algorithms the search kernels are made of -- the reference's BinaryHeap (src/hnsw.rs:940,
  * :958-973, :1035-1053, :1544; std's push / pop / into_sorted_vec) as a memory heap and as a register heap, the sorted result set

@@ -107,6 +107,40 @@ inline SpanningForest csr_spanning_forest(const std::vector<uint64_t>& offsets, 
     return f;
 }
 
+// The single-linkage dendrogram of a forest (an extension: hnswgpu_forest_dendrogram, hnswgpu_graph_dendrogram): merge e joins the
+// clusters left[e] and right[e] into cluster n_vertices + e of sizes[e] vertices.  Cluster ids are scipy's: an id below n_vertices
+// is that vertex alone.  forest: the edges and weights where the call had them (knn_graph_dendrogram), else empty.
+struct Dendrogram {
+    std::vector<uint32_t> left;
+    std::vector<uint32_t> right;
+    std::vector<uint32_t> sizes;
+    size_t n_vertices = 0;
+    SpanningForest forest;
+    size_t n_edges() const { return left.size(); }
+    // the ids of the clusters that are nobody's child, ascending: one per component of the forest
+    std::vector<uint32_t> roots() const {
+        std::vector<char> child(n_vertices + n_edges(), 0);
+        for (size_t e = 0; e < n_edges(); ++e) child[left[e]] = child[right[e]] = 1;
+        std::vector<uint32_t> r;
+        for (size_t x = 0; x < child.size(); ++x)
+            if (!child[x]) r.push_back((uint32_t)x);
+        return r;
+    }
+};
+// The dendrogram of the forest whose edge e joins vertices a[e] and b[e] of 0 .. n - 1, built on `device`: the edges' order is the
+// merge order.  An end >= n, a self-loop, more than n - 1 edges and a cycle are HNSWGPU_ERR_ARG.
+inline Dendrogram forest_dendrogram(size_t n, const std::vector<uint32_t>& a, const std::vector<uint32_t>& b, int device = 0) {
+    if (a.size() != b.size()) throw Error(HNSWGPU_ERR_ARG, "forest_dendrogram: a and b must hold one entry per edge");
+    Dendrogram d;
+    const size_t m = a.size();
+    d.n_vertices = n;
+    d.left.assign(m, 0);
+    d.right.assign(m, 0);
+    d.sizes.assign(m, 0);
+    check(hnswgpu_forest_dendrogram(device, n, m, a.data(), b.data(), d.left.data(), d.right.data(), d.sizes.data()));
+    return d;
+}
+
 template <class T, class D>
 class Hnsw;
 
@@ -241,6 +275,30 @@ public:
         f.b.resize(count);
         f.weights.resize(count);
         return f;
+    }
+    // knn_graph_spanning_forest(knbn, ef, mutual, core_k) and the dendrogram of that forest in one call, the forest staying on the
+    // device in between: .forest is that call's answer, byte for byte.
+    Dendrogram knn_graph_dendrogram(size_t knbn, size_t ef = 0, bool mutual = false, size_t core_k = 0) const {
+        Dendrogram d;
+        if (!idx_) return d;
+        const size_t n = get_nb_point(), slots = n > 1 ? n - 1 : 1;
+        d.n_vertices = n;
+        d.forest.a.assign(slots, 0);
+        d.forest.b.assign(slots, 0);
+        d.forest.weights.assign(slots, 0.0f);
+        d.left.assign(slots, 0);
+        d.right.assign(slots, 0);
+        d.sizes.assign(slots, 0);
+        uint64_t count = 0;
+        check(hnswgpu_graph_dendrogram(idx_, knbn, ef, mutual ? HNSWGPU_SYM_MUTUAL : HNSWGPU_SYM_UNION, core_k, d.forest.a.data(), d.forest.b.data(),
+                                       d.forest.weights.data(), d.left.data(), d.right.data(), d.sizes.data(), &count));
+        d.forest.a.resize(count);
+        d.forest.b.resize(count);
+        d.forest.weights.resize(count);
+        d.left.resize(count);
+        d.right.resize(count);
+        d.sizes.resize(count);
+        return d;
     }
     hnswgpu_index* handle() const { return idx_; }
 
