@@ -240,6 +240,9 @@ int hnswgpu_gather_sharded_answers(const int* devices, int n_shards, const uint6
 /* Same with every buffer already resident in HBM (device pointers), launched on HIP stream
  * `stream` (hipStream_t as void*; NULL = default stream).  Synchronises `stream` once
  * before returning (the visited-set overflow check needs one 4-byte read-back).
+ * The stream contract, of this and of every other entry that takes a `stream` (the `_device` forms, _begin / _end, the gather): device
+ * inputs are read and device outputs written in the order of `stream`, so work queued on `stream` before the call needs no host
+ * wait, and when the call returns the stream has been waited for (tests/test_gpu_stream_order.py).
  * d_stats may be NULL, else uint32[nq*8] per query = {n_dist, n_expand, n_ids_read, status,
  * t_start, t_end (device wall clock, 10 ns ticks), used_hbm_bitmap, flags | (lists scanned by the greedy descent << 8) | (its n_dist << 16)}
  * (flags: 1 equal distances met, 2 a pop was taken from the literal candidate heap).  The work counters are the reference's,
