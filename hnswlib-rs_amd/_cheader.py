@@ -27,13 +27,14 @@ def _norm(t):
 
 class Header:
     """structs: name -> ctypes.Structure subclass (complete types only); opaque: names of opaque struct typedefs;
-    prototypes: name -> (restype, [argtypes], [arg names], 'C text')."""
+    prototypes: name -> (restype, [argtypes], [arg names], 'C text').
+    base: the Header of a file that this one #includes: its types are known here too (an extension header's prototypes name them)."""
 
-    def __init__(self, text):
+    def __init__(self, text, base=None):
         self.text = strip_comments(text)
-        self.structs = {}
-        self.opaque = set()
-        self.fnptr = set()
+        self.structs = dict(base.structs) if base else {}
+        self.opaque = set(base.opaque) if base else set()
+        self.fnptr = set(base.fnptr) if base else set()
         self.prototypes = {}
         self.constants = {}
         self._parse_typedefs()
@@ -105,6 +106,6 @@ class Header:
             self.prototypes[name] = (self.ctype(ret, for_return=True), argtypes, names, f"{' '.join(ret.split())} {name}({args})")
 
 
-def load(path):
+def load(path, base=None):
     with open(path) as f:
-        return Header(f.read())
+        return Header(f.read(), base)

@@ -22,6 +22,12 @@ _PKG_HEADER = os.path.join(PKG_DIR, "hnsw_mi355x.h")
 HEADER_PATH = _TREE_HEADER if os.path.exists(_TREE_HEADER) else _PKG_HEADER
 # The header is the one description of the C ABI; structures, prototypes and codes below are READ FROM IT (._cheader).
 HEADER = _cheader.load(HEADER_PATH)
+# the HDBSCAN entries are an extension with a header of its own (hnswhdb_*), found and read in the same way.  It includes
+# hnsw_mi355x.h, whose types its prototypes name: it is read with that header as its base.
+_TREE_HDBSCAN_HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "hnsw_mi355x_hdbscan.h")
+_PKG_HDBSCAN_HEADER = os.path.join(PKG_DIR, "hnsw_mi355x_hdbscan.h")
+HDBSCAN_HEADER_PATH = _TREE_HDBSCAN_HEADER if os.path.exists(_TREE_HDBSCAN_HEADER) else _PKG_HDBSCAN_HEADER
+HDBSCAN_HEADER = _cheader.load(HDBSCAN_HEADER_PATH, HEADER)
 OK, ERR_ARG, ERR_IO, ERR_FORMAT, ERR_DISTANCE, ERR_TYPE, ERR_DEVICE, ERR_EMPTY, ERR_REF_PANIC, ERR_CAPACITY = (
     HEADER.constants["HNSWGPU_" + n] for n in ("OK", "ERR_ARG", "ERR_IO", "ERR_FORMAT", "ERR_DISTANCE", "ERR_TYPE", "ERR_DEVICE",
                                                "ERR_EMPTY", "ERR_REF_PANIC", "ERR_CAPACITY"))
@@ -36,20 +42,21 @@ def build_native(force=False, verbose=False):
     """Compile every HIP/C++ source for gfx950 into libhnsw_mi355x.so (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC_DIR, f) for f in os.listdir(CSRC_DIR)
             if f.endswith((".cpp", ".hip", ".hpp", ".inc")) or f == "Makefile"]
-    srcs.append(HEADER_PATH)
+    srcs += [HEADER_PATH, HDBSCAN_HEADER_PATH]
 
     def fresh():
         return (os.path.exists(LIB_PATH)
                 and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs))
 
-    def ship_header():  # the package's own copy of the header (what a relocated package binds from)
-        if os.path.exists(_TREE_HEADER):
-            try:
-                if not os.path.exists(_PKG_HEADER) or open(_PKG_HEADER, "rb").read() != open(_TREE_HEADER, "rb").read():
-                    with open(_PKG_HEADER, "wb") as f:
-                        f.write(open(_TREE_HEADER, "rb").read())
-            except OSError:
-                pass
+    def ship_header():  # the package's own copies of the headers (what a relocated package binds from)
+        for tree, pkg in ((_TREE_HEADER, _PKG_HEADER), (_TREE_HDBSCAN_HEADER, _PKG_HDBSCAN_HEADER)):
+            if os.path.exists(tree):
+                try:
+                    if not os.path.exists(pkg) or open(pkg, "rb").read() != open(tree, "rb").read():
+                        with open(pkg, "wb") as f:
+                            f.write(open(tree, "rb").read())
+                except OSError:
+                    pass
 
     if not force and fresh():
         ship_header()
@@ -85,6 +92,8 @@ DescriptionFFI = HEADER.structs["DescriptionFFI"]                  # src/libext.
 
 # every symbol include/hnsw_mi355x.h declares: name -> (restype, argtypes)
 SYMBOLS = {name: (res, args) for name, (res, args, _names, _text) in HEADER.prototypes.items()}
+# every symbol include/hnsw_mi355x_hdbscan.h declares
+HDBSCAN_SYMBOLS = {name: (res, args) for name, (res, args, _names, _text) in HDBSCAN_HEADER.prototypes.items()}
 
 _lib = None
 
@@ -99,7 +108,7 @@ def lib():
                 f"{path} is missing: build it with hnsw_rs_amd.build_native() "
                 "(python -c 'import __graft_entry__ as g; g.build()').  There is no CPU fallback.")
         L = C.CDLL(path)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(HDBSCAN_SYMBOLS.items()):
             fn = getattr(L, name)  # AttributeError if the library does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -231,6 +231,11 @@ class SpanningForestResult:
         d = forest_dendrogram(self.n_vertices, self.a[:m], self.b[:m], device)
         return DendrogramResult(d.left, d.right, d.sizes, m, self.n_vertices, self.a[:m], self.b[:m], self.weights[:m])
 
+    def hdbscan(self, min_cluster_size, method="eom", device=0):
+        """HDBSCAN's clusters of this forest's edges in their order (forest_hdbscan): an HdbscanResult."""
+        m = self.n_edges
+        return forest_hdbscan(self.n_vertices, self.a[:m], self.b[:m], self.weights[:m], min_cluster_size, method, device)
+
 
 class DendrogramResult:
     """The single-linkage dendrogram of a forest (forest_dendrogram, SpanningForestResult.dendrogram, Hnsw.knn_graph_dendrogram):
@@ -273,6 +278,101 @@ def forest_dendrogram(n, a, b, device=0):
     _check(N.lib().hnswgpu_forest_dendrogram(device, n, m, _p(a) if m else None, _p(b) if m else None, _p(left) if m else None,
                                              _p(right) if m else None, _p(sizes) if m else None))
     return DendrogramResult(left, right, sizes, m, n)
+
+
+def _lambda_of(w):
+    """HDBSCAN's lambda of f32 weights, f64: 1 / w; 0 for +inf and NaN; +inf for w <= 0"""
+    w = np.asarray(w, np.float32)
+    lam = np.zeros(w.shape, np.float64)
+    pos = np.isfinite(w) & (w > 0)
+    lam[pos] = 1.0 / w[pos].astype(np.float64)
+    lam[w <= 0] = np.inf
+    return lam
+
+
+class HdbscanResult:
+    """HDBSCAN's answer (forest_hdbscan, SpanningForestResult.hdbscan, Hnsw.hdbscan), as include/hnsw_mi355x_hdbscan.h defines it.  Per
+    vertex: labels (i32, -1: noise), probabilities (f32), point_cluster and point_w (the cluster of the condensed tree that the
+    vertex leaves, and the f32 weight at which it does).  Per cluster of the condensed tree, n_clusters of them, cluster 0 the
+    root: cluster_parent (0xFFFFFFFF for cluster 0), cluster_birth_w, cluster_size, stability (f64), selected (bool).  n_labels
+    selected clusters, numbered by ascending cluster index.  forest (a SpanningForestResult) and dendrogram (a DendrogramResult)
+    are there where the call produced them (Hnsw.hdbscan), else None."""
+
+    def __init__(self, labels, probabilities, point_cluster, point_w, cluster_parent, cluster_birth_w, cluster_size, stability, selected,
+                 n_clusters, n_labels, forest=None, dendrogram=None):
+        self.labels, self.probabilities, self.point_cluster, self.point_w = labels, probabilities, point_cluster, point_w
+        self.cluster_parent, self.cluster_birth_w, self.cluster_size = cluster_parent, cluster_birth_w, cluster_size
+        self.stability, self.selected, self.n_clusters, self.n_labels = stability, selected, n_clusters, n_labels
+        self.forest, self.dendrogram = forest, dendrogram
+
+    def condensed_tree(self):
+        """The condensed tree as rows (parent, child, lambda, child_size) in sklearn's CONDENSED_dtype layout ('parent' and 'child'
+        intp, 'value' f64, 'cluster_size' intp): cluster c is numbered n + c; first the clusters 1 .. n_clusters - 1 as children of
+        their parents, then the vertices."""
+        n, k = len(self.labels), self.n_clusters
+        dtype = np.dtype([("parent", np.intp), ("child", np.intp), ("value", np.float64), ("cluster_size", np.intp)])
+        rows = np.zeros(max(k - 1, 0) + n, dtype)
+        c = np.arange(1, max(k, 1))
+        rows["parent"][:len(c)] = n + self.cluster_parent[1:k].astype(np.intp)
+        rows["child"][:len(c)] = n + c
+        rows["value"][:len(c)] = _lambda_of(self.cluster_birth_w[1:k])
+        rows["cluster_size"][:len(c)] = self.cluster_size[1:k]
+        rows["parent"][len(c):] = n + self.point_cluster.astype(np.intp)
+        rows["child"][len(c):] = np.arange(n)
+        rows["value"][len(c):] = _lambda_of(self.point_w)
+        rows["cluster_size"][len(c):] = 1
+        return rows
+
+
+_METHODS = {"eom": "HNSWGPU_SELECT_EOM", "leaf": "HNSWGPU_SELECT_LEAF"}
+
+
+def _hdbscan_method(method):
+    if method not in _METHODS:
+        raise HnswError(N.ERR_ARG, f"method must be 'eom' or 'leaf', not {method!r}")
+    return N.HDBSCAN_HEADER.constants[_METHODS[method]]
+
+
+class _HdbscanArrays:
+    """the out arrays of one hdbscan call over n vertices"""
+
+    def __init__(self, n, min_cluster_size):
+        if min_cluster_size != int(min_cluster_size) or not 2 <= min_cluster_size <= 0x7FFFFFFF:
+            raise HnswError(N.ERR_ARG, f"min_cluster_size = {min_cluster_size}: it must be in 2 .. 2^31 - 1")
+        k = max(int(N.lib().hnswhdb_max_clusters(n, int(min_cluster_size))), 1)
+        self.labels, self.prob = np.full(max(n, 1), -1, np.int32), np.zeros(max(n, 1), np.float32)
+        self.point_cluster, self.point_w = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.float32)
+        self.parent, self.birth, self.size = np.zeros(k, np.uint32), np.zeros(k, np.float32), np.zeros(k, np.uint32)
+        self.stability, self.selected = np.zeros(k, np.float64), np.zeros(k, np.uint8)
+        self.n_clusters, self.n_labels = np.zeros(1, np.uint64), np.zeros(1, np.uint64)
+        self.n = n
+
+    def pointers(self):
+        return (_p(self.labels), _p(self.prob), _p(self.point_cluster), _p(self.point_w), _p(self.parent), _p(self.birth), _p(self.size),
+                _p(self.stability), _p(self.selected), _p(self.n_clusters), _p(self.n_labels))
+
+    def result(self, forest=None, dendrogram=None):
+        n, k = self.n, int(self.n_clusters[0])
+        return HdbscanResult(self.labels[:n].copy(), self.prob[:n].copy(), self.point_cluster[:n].copy(), self.point_w[:n].copy(),
+                             self.parent[:k].copy(), self.birth[:k].copy(), self.size[:k].copy(), self.stability[:k].copy(),
+                             self.selected[:k].astype(bool), k, int(self.n_labels[0]), forest, dendrogram)
+
+
+def forest_hdbscan(n, a, b, weights, min_cluster_size, method="eom", device=0):
+    """HDBSCAN's clusters of the forest whose edge e joins vertices a[e] and b[e] of 0 .. n - 1 with weight weights[e] (f32), on
+    `device`: the edges' order is the merge order and the weights must not descend.  method: "eom" (excess of mass) or "leaf".
+    Refuses (HnswError, ERR_ARG) what forest_dendrogram refuses, weights that descend and a min_cluster_size outside 2 .. 2^31 - 1.
+    Returns an HdbscanResult."""
+    a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
+    b = np.ascontiguousarray(b, dtype=np.uint32).reshape(-1)
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    if len(a) != len(b) or len(a) != len(w):
+        raise HnswError(N.ERR_ARG, f"a has {len(a)} entries, b has {len(b)}, weights has {len(w)}")
+    m, code = len(a), _hdbscan_method(method)
+    o = _HdbscanArrays(n, min_cluster_size)
+    _check(N.lib().hnswhdb_forest(device, n, m, _p(a) if m else None, _p(b) if m else None, _p(w) if m else None, int(min_cluster_size), code,
+                                          *o.pointers()))
+    return o.result()
 
 
 def csr_spanning_forest(offsets, cols, dists=None, device=0):
@@ -823,6 +923,39 @@ class Hnsw:
                                                   _p(right), _p(sizes), _p(m)))
         m = int(m[0])
         return DendrogramResult(left[:m].copy(), right[:m].copy(), sizes[:m].copy(), m, n, a[:m].copy(), b[:m].copy(), w[:m].copy())
+
+    def hdbscan(self, min_cluster_size, knbn, ef=None, mode="union", core_k=None, method="eom"):
+        """HDBSCAN of the indexed points in one call: knn_graph_dendrogram(knbn, ef, mode, core_k), the condensed tree of that
+        dendrogram for min_cluster_size, the stabilities, the selection ("eom": excess of mass, "leaf": the leaves) and the labels,
+        the forest and the dendrogram staying on the device throughout.  Vertices are POSITIONS.  core_k=None means
+        min(min_cluster_size - 1, knbn): sklearn's default min_samples = min_cluster_size, which counts the point itself.  Returns
+        an HdbscanResult whose forest and dendrogram are knn_graph_dendrogram's, byte for byte."""
+        modes = {"union": N.HEADER.constants["HNSWGPU_SYM_UNION"], "mutual": N.HEADER.constants["HNSWGPU_SYM_MUTUAL"]}
+        if mode not in modes:
+            raise HnswError(N.ERR_ARG, f"mode must be 'union' or 'mutual', not {mode!r}")
+        if ef is not None and ef < 1:
+            raise HnswError(N.ERR_ARG, "ef must be >= 1 (ef=None: the exact graph)")
+        code = _hdbscan_method(method)
+        n = self.get_nb_point()
+        o = _HdbscanArrays(n, min_cluster_size)
+        if core_k is None:
+            core_k = max(min(int(min_cluster_size) - 1, knbn), 0)
+        if core_k < 0:
+            raise HnswError(N.ERR_ARG, "core_k must be >= 0")
+        slots = max(n - 1, 1)
+        a, b, w, m = np.zeros(slots, np.uint32), np.zeros(slots, np.uint32), np.zeros(slots, np.float32), np.zeros(1, np.uint64)
+        left, right, sizes = np.zeros(slots, np.uint32), np.zeros(slots, np.uint32), np.zeros(slots, np.uint32)
+        if self._h is None:
+            if knbn < 1:
+                raise HnswError(N.ERR_ARG, "knbn must be > 0")
+            if core_k > knbn:
+                raise HnswError(N.ERR_ARG, "core_k is above knbn")
+            return o.result(SpanningForestResult(a[:0], b[:0], w[:0], 0, 0), DendrogramResult(left[:0], right[:0], sizes[:0], 0, 0, a[:0], b[:0], w[:0]))
+        _check(self._lib.hnswhdb_graph(self._h, knbn, 0 if ef is None else ef, modes[mode], core_k, int(min_cluster_size), code, _p(a), _p(b),
+                                               _p(w), _p(left), _p(right), _p(sizes), *o.pointers(), _p(m)))
+        m = int(m[0])
+        a, b, w = a[:m].copy(), b[:m].copy(), w[:m].copy()
+        return o.result(SpanningForestResult(a, b, w, m, n), DendrogramResult(left[:m].copy(), right[:m].copy(), sizes[:m].copy(), m, n, a, b, w))
 
     def knn_graph_recall(self, knbn, ef, point_ids=None):
         """The recall by id of knn_graph_flat against exact_knn_graph_flat over the named points: the share of the exact

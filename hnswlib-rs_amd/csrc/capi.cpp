@@ -1414,14 +1414,18 @@ static int forest_answer_check(uint64_t n, const void* out_a, const void* out_b,
     return HNSWGPU_OK;
 }
 // the checks both index entries share; the handle's lock is held (shared)
-static int graph_spanning_forest_call(const hnswgpu_index* idx, const ForestArgs& a) {
-    int rc = forest_answer_check(index_nb_point(idx), a.out_a, a.out_b, a.out_w, a.out_n);
-    if (rc != HNSWGPU_OK) return rc;
-    rc = directed_graph_shape(a.k, a.mode);
+// (the part behind the answer's slots: what hnswhdb_graph, whose forest arrays are optional, checks too)
+static int graph_spanning_forest_source(const hnswgpu_index* idx, const ForestArgs& a) {
+    const int rc = directed_graph_shape(a.k, a.mode);
     if (rc != HNSWGPU_OK) return rc;
     if (a.core_k > a.k)
         return fail(HNSWGPU_ERR_ARG, "core_k = " + std::to_string(a.core_k) + " is above knbn = " + std::to_string(a.k) + ": a row of D has knbn slots");
     return directed_graph_source(idx, "graph spanning forest", a.k, a.ef);
+}
+static int graph_spanning_forest_call(const hnswgpu_index* idx, const ForestArgs& a) {
+    const int rc = forest_answer_check(index_nb_point(idx), a.out_a, a.out_b, a.out_w, a.out_n);
+    if (rc != HNSWGPU_OK) return rc;
+    return graph_spanning_forest_source(idx, a);
 }
 
 int hnswgpu_graph_spanning_forest(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k, uint32_t* out_a, uint32_t* out_b,
@@ -1612,6 +1616,166 @@ int hnswgpu_graph_dendrogram_device(const hnswgpu_index* cidx, uint64_t k, uint6
     if (rc != HNSWGPU_OK) return rc;
     std::string err;
     return finish(hnswgpu::graph_dendrogram(*dev, idx->flat->origin_id, a, false, stream, err), err);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+// ---- HDBSCAN: condensed tree, stabilities and flat clusters of a forest in merge order, and of the k-NN graph's own forest
+// (condensed_tree.hip holds the device side)
+extern "C++" {
+namespace hnswgpu {
+__attribute__((weak)) int forest_hdbscan(const ForestHdbscanArgs&, bool, void*, std::string&);
+__attribute__((weak)) int graph_hdbscan(DeviceIndex&, const std::vector<uint64_t>&, const GraphHdbscanArgs&, bool, void*, std::string&);
+}  // namespace hnswgpu
+}  // extern "C++"
+
+uint64_t hnswhdb_max_clusters(uint64_t n, uint64_t min_cluster_size) {
+    if (min_cluster_size == 0) return 0;
+    const uint64_t q = n / min_cluster_size;
+    return q == 0 ? 1 : q > (~0ull >> 1) ? ~0ull : 2 * q - 1;
+}
+
+// what all four entries check of the clustering's own arguments (n: the number of vertices)
+static int hdbscan_answer_check(uint64_t n, uint64_t mcs, uint32_t method, const HdbscanOut& o) {
+    if (!o.n_clusters || !o.n_labels) return fail(HNSWGPU_ERR_ARG, "null out_n_clusters or out_n_labels: the two counts are written by every call");
+    if (mcs < 2 || mcs > 0x7FFFFFFFull)
+        return fail(HNSWGPU_ERR_ARG, "min_cluster_size = " + std::to_string(mcs) + ": it must be in 2 .. 2^31 - 1");
+    if (method != HNSWGPU_SELECT_EOM && method != HNSWGPU_SELECT_LEAF)
+        return fail(HNSWGPU_ERR_ARG, "unknown method " + std::to_string(method) + ": HNSWGPU_SELECT_EOM or HNSWGPU_SELECT_LEAF");
+    if (n != 0 && !o.labels) return fail(HNSWGPU_ERR_ARG, "null out_labels");
+    return HNSWGPU_OK;
+}
+// what both forest entries can check without reading an array: the dendrogram's, in its words, then the clustering's
+static int forest_hdbscan_call(const ForestHdbscanArgs& a) {
+    if (a.n > 0x7FFFFFFFull) return fail(HNSWGPU_ERR_ARG, "forest dendrogram: n = " + std::to_string(a.n) + " vertices, above 2^31 - 1");
+    if (a.m > std::max<uint64_t>(a.n, 1) - 1)
+        return fail(HNSWGPU_ERR_ARG, "forest dendrogram: m = " + std::to_string(a.m) + " edges among n = " + std::to_string(a.n) +
+                                         " vertices: a forest has at most n - 1");
+    if (a.m != 0 && (!a.a || !a.b || !a.w)) return fail(HNSWGPU_ERR_ARG, "null a, b or w");
+    return hdbscan_answer_check(a.n, a.min_cluster_size, a.method, a.out);
+}
+// the order of the spanning forest's weights (graph_internal.hpp: dist_order_bits), on the host
+static uint32_t weight_order_bits(float v) {
+    uint32_t b;
+    std::memcpy(&b, &v, 4);
+    if (v != v) return 0xFFFFFFFFu;
+    if (b == 0x80000000u) b = 0u;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+int hnswhdb_forest(int device, uint64_t n, uint64_t m, const uint32_t* a, const uint32_t* b, const float* w, uint64_t min_cluster_size,
+                           uint32_t method, int32_t* out_labels, float* out_prob, uint32_t* out_point_cluster, float* out_point_w,
+                           uint32_t* out_cluster_parent, float* out_cluster_birth_w, uint32_t* out_cluster_size, double* out_stability,
+                           uint8_t* out_selected, uint64_t* out_n_clusters, uint64_t* out_n_labels) {
+    CAPI_GUARD_BEGIN
+    const ForestHdbscanArgs args{device, n, m, a, b, w, min_cluster_size, method,
+                                 HdbscanOut{out_labels, out_prob, out_point_cluster, out_point_w, out_cluster_parent, out_cluster_birth_w,
+                                            out_cluster_size, out_stability, out_selected, out_n_clusters, out_n_labels}};
+    const int rc = forest_hdbscan_call(args);
+    if (rc != HNSWGPU_OK) return rc;
+    if (n == 0) {  // no vertex: the two counts, no array is read or written
+        *out_n_clusters = 0;
+        *out_n_labels = 0;
+        return HNSWGPU_OK;
+    }
+    // the ends as the dendrogram's kernel checks them, the weights as this call's kernel does (a cycle is the device's to find)
+    for (uint64_t e = 0; e < m; ++e) {
+        if (a[e] >= n || b[e] >= n)
+            return fail(HNSWGPU_ERR_ARG, "forest dendrogram: edge " + std::to_string(e) + " has an end that is not below n");
+        if (a[e] == b[e]) return fail(HNSWGPU_ERR_ARG, "forest dendrogram: edge " + std::to_string(e) + " joins a vertex to itself");
+    }
+    for (uint64_t e = 1; e < m; ++e)
+        if (weight_order_bits(w[e - 1]) > weight_order_bits(w[e]))
+            return fail(HNSWGPU_ERR_ARG, "forest hdbscan: the weights descend at edge " + std::to_string(e) +
+                                             ": the edges' order is the merge order, ascending by weight");
+    if (!hnswgpu::forest_hdbscan) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    std::string err;
+    return finish(hnswgpu::forest_hdbscan(args, true, nullptr, err), err);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswhdb_forest_device(int device, uint64_t n, uint64_t m, const uint32_t* d_a, const uint32_t* d_b, const float* d_w,
+                                  uint64_t min_cluster_size, uint32_t method, int32_t* d_out_labels, float* d_out_prob,
+                                  uint32_t* d_out_point_cluster, float* d_out_point_w, uint32_t* d_out_cluster_parent, float* d_out_cluster_birth_w,
+                                  uint32_t* d_out_cluster_size, double* d_out_stability, uint8_t* d_out_selected, uint64_t* out_n_clusters,
+                                  uint64_t* out_n_labels, void* stream) {
+    CAPI_GUARD_BEGIN
+    const ForestHdbscanArgs args{device, n, m, d_a, d_b, d_w, min_cluster_size, method,
+                                 HdbscanOut{d_out_labels, d_out_prob, d_out_point_cluster, d_out_point_w, d_out_cluster_parent,
+                                            d_out_cluster_birth_w, d_out_cluster_size, d_out_stability, d_out_selected, out_n_clusters, out_n_labels}};
+    const int rc = forest_hdbscan_call(args);
+    if (rc != HNSWGPU_OK) return rc;
+    if (n == 0) {
+        *out_n_clusters = 0;
+        *out_n_labels = 0;
+        return HNSWGPU_OK;
+    }
+    if (!hnswgpu::forest_hdbscan) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    std::string err;
+    return finish(hnswgpu::forest_hdbscan(args, false, stream, err), err);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+// the checks both index entries share: the dendrogram call's own in its words -- the six arrays of the forest and the dendrogram are
+// optional here --, then the clustering's; the handle's lock is held (shared)
+static int graph_hdbscan_call(const hnswgpu_index* idx, const GraphHdbscanArgs& a) {
+    if (!a.forest.out_n) return fail(HNSWGPU_ERR_ARG, "null out_n_edges: the number of edges is written by every call");
+    const int rc = graph_spanning_forest_source(idx, a.forest);
+    if (rc != HNSWGPU_OK) return rc;
+    return hdbscan_answer_check(index_nb_point(idx), a.min_cluster_size, a.method, a.out);
+}
+
+int hnswhdb_graph(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k, uint64_t min_cluster_size, uint32_t method,
+                          uint32_t* out_a, uint32_t* out_b, float* out_w, uint32_t* out_left, uint32_t* out_right, uint32_t* out_size,
+                          int32_t* out_labels, float* out_prob, uint32_t* out_point_cluster, float* out_point_w, uint32_t* out_cluster_parent,
+                          float* out_cluster_birth_w, uint32_t* out_cluster_size, double* out_stability, uint8_t* out_selected,
+                          uint64_t* out_n_clusters, uint64_t* out_n_labels, uint64_t* out_n_edges) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    const GraphHdbscanArgs a{ForestArgs{k, ef, mode, core_k, out_a, out_b, out_w, out_n_edges}, out_left, out_right, out_size, min_cluster_size, method,
+                             HdbscanOut{out_labels, out_prob, out_point_cluster, out_point_w, out_cluster_parent, out_cluster_birth_w,
+                                        out_cluster_size, out_stability, out_selected, out_n_clusters, out_n_labels}};
+    int rc = graph_hdbscan_call(idx, a);
+    if (rc != HNSWGPU_OK) return rc;
+    if (index_nb_point(idx) == 0) {  // no vertex: the three counts, nothing else written
+        *out_n_edges = *out_n_clusters = *out_n_labels = 0;
+        return HNSWGPU_OK;
+    }
+    if (!hnswgpu::graph_hdbscan) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = primary_f32_replica(idx, sl, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    return finish(hnswgpu::graph_hdbscan(*dev, idx->flat->origin_id, a, true, nullptr, err), err);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswhdb_graph_device(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k, uint64_t min_cluster_size,
+                                 uint32_t method, uint32_t* d_out_a, uint32_t* d_out_b, float* d_out_w, uint32_t* d_out_left, uint32_t* d_out_right,
+                                 uint32_t* d_out_size, int32_t* d_out_labels, float* d_out_prob, uint32_t* d_out_point_cluster, float* d_out_point_w,
+                                 uint32_t* d_out_cluster_parent, float* d_out_cluster_birth_w, uint32_t* d_out_cluster_size, double* d_out_stability,
+                                 uint8_t* d_out_selected, uint64_t* out_n_clusters, uint64_t* out_n_labels, uint64_t* out_n_edges, void* stream) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    const GraphHdbscanArgs a{ForestArgs{k, ef, mode, core_k, d_out_a, d_out_b, d_out_w, out_n_edges}, d_out_left, d_out_right, d_out_size,
+                             min_cluster_size, method,
+                             HdbscanOut{d_out_labels, d_out_prob, d_out_point_cluster, d_out_point_w, d_out_cluster_parent, d_out_cluster_birth_w,
+                                        d_out_cluster_size, d_out_stability, d_out_selected, out_n_clusters, out_n_labels}};
+    int rc = graph_hdbscan_call(idx, a);
+    if (rc != HNSWGPU_OK) return rc;
+    if (index_nb_point(idx) == 0) {
+        *out_n_edges = *out_n_clusters = *out_n_labels = 0;
+        return HNSWGPU_OK;
+    }
+    if (!hnswgpu::graph_hdbscan) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = resident_replica(idx, true, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    return finish(hnswgpu::graph_hdbscan(*dev, idx->flat->origin_id, a, false, stream, err), err);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 

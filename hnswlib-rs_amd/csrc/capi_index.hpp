@@ -1,5 +1,5 @@
-// capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h, for the translation units
-// that implement entry points of the C ABI (capi.cpp; exact_knn.hip; range_search.hip; symmetric_graph.hip; graph_components.hip; spanning_forest.hip; dendrogram.hip).  Private: not installed, not part of the ABI.
+// capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h (and its extension hnsw_mi355x_hdbscan.h), for the translation units
+// that implement entry points of the C ABI (capi.cpp; exact_knn.hip; range_search.hip; symmetric_graph.hip; graph_components.hip; spanning_forest.hip; dendrogram.hip; condensed_tree.hip).  Private: not installed, not part of the ABI.
 // The checks that entries share (empty index, resident replica, sorted filter, the shape and contents of a filter set, the limits of
 // an exact call, the zeroed k-NN answer, the tail) live once, in capi.cpp; what an entry outside capi.cpp needs of them is declared
 // below as capi_*.  A new pair of entries calls them.  The HIP host helpers of the .hip units (HIP_TRY, DeviceGuard, DevMem,
@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/hnsw_mi355x.h"
+#include "../../include/hnsw_mi355x_hdbscan.h"
 #include "builder.hpp"
 #include "flat_index.hpp"
 #include "search_device.hpp"
@@ -217,6 +218,46 @@ struct GraphDendrogramArgs {
     uint32_t* out_size;   // [n - 1]
 };
 int graph_dendrogram(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphDendrogramArgs& a, bool host, void* stream, std::string& err);
+// the device side of hnswhdb_forest(_device) and hnswhdb_graph(_device), defined in condensed_tree.hip and referred
+// to weakly in the same way (the arguments have been checked; forest form: n >= 1, m <= n - 1; index form: at least one point;
+// 2 <= min_cluster_size <= 2^31 - 1, a known method).  host: the arrays are plain host memory -- a forest form's ends and weights
+// have then passed their checks on the host --; else device memory and `stream` is the caller's.  The two counts are host memory
+// either way.  forest_hdbscan runs forest_dendrogram on device buffers and returns what it refuses, and ERR_ARG, no out slot
+// written, when the weights descend.  graph_hdbscan runs graph_dendrogram into device scratch and goes on from there.
+struct HdbscanOut {
+    int32_t* labels;           // [n]
+    float* prob;               // [n], may be nullptr, like every array below
+    uint32_t* point_cluster;   // [n]
+    float* point_w;            // [n]
+    uint32_t* cluster_parent;  // [hnswhdb_max_clusters(n, min_cluster_size)], like the four below
+    float* cluster_birth_w;
+    uint32_t* cluster_size;
+    double* stability;
+    uint8_t* selected;
+    uint64_t* n_clusters;
+    uint64_t* n_labels;
+};
+struct ForestHdbscanArgs {
+    int device;
+    uint64_t n, m;
+    const uint32_t* a;  // [m]
+    const uint32_t* b;  // [m]
+    const float* w;     // [m]
+    uint64_t min_cluster_size;
+    uint32_t method;    // HNSWGPU_SELECT_*
+    HdbscanOut out;
+};
+int forest_hdbscan(const ForestHdbscanArgs& a, bool host, void* stream, std::string& err);
+struct GraphHdbscanArgs {
+    ForestArgs forest;    // out_a, out_b, out_w may be nullptr; out_n is host memory either way
+    uint32_t* out_left;   // [n - 1], may be nullptr, like the two below
+    uint32_t* out_right;
+    uint32_t* out_size;
+    uint64_t min_cluster_size;
+    uint32_t method;
+    HdbscanOut out;
+};
+int graph_hdbscan(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphHdbscanArgs& a, bool host, void* stream, std::string& err);
 }  // namespace hnswgpu
 
 // No C++ exception may cross the C ABI: every entry point is `try { ... HNSWGPU_CAPI_GUARD_END(ret)`

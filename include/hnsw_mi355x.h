@@ -752,7 +752,7 @@ int hnswgpu_csr_components_device(int device, uint64_t n, const uint64_t* d_offs
  * back; there are at most ceil(log2 n) + 1 rounds, and the bound is hard (a round past it would be HNSWGPU_ERR_FORMAT, an internal
  * error).  The answer is a function of D alone, two calls give the same bytes.  Takes the handle's lock shared, like a search, and
  * is legal from several host threads at once.  Host buffers; uploads the index on first use.
- * Out of scope: the condensed tree and stabilities (the dendrogram itself is the next section); a filter or a subset of points; F16 storage;
+ * Out of scope: a filter or a subset of points; F16 storage; (the dendrogram is the next section, HDBSCAN's clusters hnsw_mi355x_hdbscan.h)
  * sharding over GPUs; weights other than stored distances and their core maxima.                                              */
 int hnswgpu_graph_spanning_forest(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k,
                                   uint32_t* out_a, uint32_t* out_b, float* out_w, uint64_t* out_n_edges);
@@ -800,7 +800,7 @@ int hnswgpu_csr_spanning_forest_device(int device, uint64_t n, const uint64_t* d
  * the upper half of every aligned block of edge indices learns what the lower half merged.  The bound is hard; no wavefront waits
  * on another and nothing is read back inside the loop -- one word, at the end, before any out slot is written.  The answer is a
  * function of the edge list alone: two calls give the same bytes.  Needs no index; legal from several host threads at once.
- * Out of scope: the condensed tree, stabilities and cluster selection of HDBSCAN; a dendrogram of anything that is not a forest;
+ * Out of scope: a dendrogram of anything that is not a forest (HDBSCAN's condensed tree, stabilities and selection: hnsw_mi355x_hdbscan.h);
  * reordering of the rows (scipy wants ascending heights: an edge list sorted by weight gives them).                            */
 int hnswgpu_forest_dendrogram(int device, uint64_t n, uint64_t m, const uint32_t* a, const uint32_t* b,
                               uint32_t* out_left, uint32_t* out_right, uint32_t* out_size);

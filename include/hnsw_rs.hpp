@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "hnsw_mi355x.h"
+#include "hnsw_mi355x_hdbscan.h"
 
 namespace hnsw_rs {
 
@@ -139,6 +140,66 @@ inline Dendrogram forest_dendrogram(size_t n, const std::vector<uint32_t>& a, co
     d.sizes.assign(m, 0);
     check(hnswgpu_forest_dendrogram(device, n, m, a.data(), b.data(), d.left.data(), d.right.data(), d.sizes.data()));
     return d;
+}
+
+// HDBSCAN's answer (an extension: hnswhdb_forest, hnswhdb_graph; the definitions are hnsw_mi355x_hdbscan.h's).  Per vertex:
+// labels (-1: noise), probabilities, point_cluster and point_w (the cluster of the condensed tree that the vertex leaves, and the
+// weight at which it does).  Per cluster, cluster 0 the root: cluster_parent (UINT32_MAX for cluster 0), cluster_birth_w, cluster_size,
+// stability, selected.  n_labels selected clusters, numbered by ascending cluster index.  dendrogram (with its forest): where the
+// call produced it (Hnsw::hdbscan), else empty.
+struct Hdbscan {
+    std::vector<int32_t> labels;
+    std::vector<float> probabilities;
+    std::vector<uint32_t> point_cluster;
+    std::vector<float> point_w;
+    std::vector<uint32_t> cluster_parent;
+    std::vector<float> cluster_birth_w;
+    std::vector<uint32_t> cluster_size;
+    std::vector<double> stability;
+    std::vector<uint8_t> selected;
+    size_t n_labels = 0;
+    Dendrogram dendrogram;
+    size_t n_clusters() const { return cluster_parent.size(); }
+    // the out arrays of a call over n vertices (at least one slot each: no NULL goes to the C entry)
+    void prepare(size_t n, size_t min_cluster_size) {
+        const size_t k = (size_t)hnswhdb_max_clusters(n, min_cluster_size);
+        labels.assign(n ? n : 1, -1);
+        probabilities.assign(n ? n : 1, 0.0f);
+        point_cluster.assign(n ? n : 1, 0);
+        point_w.assign(n ? n : 1, 0.0f);
+        cluster_parent.assign(k ? k : 1, 0);
+        cluster_birth_w.assign(k ? k : 1, 0.0f);
+        cluster_size.assign(k ? k : 1, 0);
+        stability.assign(k ? k : 1, 0.0);
+        selected.assign(k ? k : 1, 0);
+    }
+    void finish(size_t n, uint64_t clusters, uint64_t n_lab) {
+        labels.resize(n);
+        probabilities.resize(n);
+        point_cluster.resize(n);
+        point_w.resize(n);
+        cluster_parent.resize(clusters);
+        cluster_birth_w.resize(clusters);
+        cluster_size.resize(clusters);
+        stability.resize(clusters);
+        selected.resize(clusters);
+        n_labels = (size_t)n_lab;
+    }
+};
+// HDBSCAN's clusters of the forest whose edge e joins vertices a[e] and b[e] of 0 .. n - 1 with weight weights[e], on `device`: the
+// edges' order is the merge order and the weights must not descend.  leaf: select the leaves of the condensed tree instead of by
+// excess of mass.  What forest_dendrogram refuses, weights that descend and a min_cluster_size outside 2 .. 2^31 - 1 are HNSWGPU_ERR_ARG.
+inline Hdbscan forest_hdbscan(size_t n, const std::vector<uint32_t>& a, const std::vector<uint32_t>& b, const std::vector<float>& weights,
+                              size_t min_cluster_size, bool leaf = false, int device = 0) {
+    if (a.size() != b.size() || a.size() != weights.size()) throw Error(HNSWGPU_ERR_ARG, "forest_hdbscan: a, b and weights must hold one entry per edge");
+    Hdbscan r;
+    r.prepare(n, min_cluster_size);
+    uint64_t clusters = 0, n_lab = 0;
+    check(hnswhdb_forest(device, n, a.size(), a.data(), b.data(), weights.data(), min_cluster_size, leaf ? HNSWGPU_SELECT_LEAF : HNSWGPU_SELECT_EOM,
+                                 r.labels.data(), r.probabilities.data(), r.point_cluster.data(), r.point_w.data(), r.cluster_parent.data(),
+                                 r.cluster_birth_w.data(), r.cluster_size.data(), r.stability.data(), r.selected.data(), &clusters, &n_lab));
+    r.finish(n, clusters, n_lab);
+    return r;
 }
 
 template <class T, class D>
@@ -299,6 +360,39 @@ public:
         d.right.resize(count);
         d.sizes.resize(count);
         return d;
+    }
+    // HDBSCAN of the indexed points in one call: knn_graph_dendrogram(knbn, ef, mutual, core_k), then the condensed tree for
+    // min_cluster_size, the stabilities, the selection and the labels, all on the device; vertices are POSITIONS.  core_k ==
+    // SIZE_MAX means min(min_cluster_size - 1, knbn): sklearn's default min_samples = min_cluster_size, which counts the point
+    // itself.  .dendrogram (and its .forest) is knn_graph_dendrogram's answer, byte for byte.
+    Hdbscan hdbscan(size_t min_cluster_size, size_t knbn, size_t ef = 0, bool mutual = false, size_t core_k = SIZE_MAX, bool leaf = false) const {
+        Hdbscan r;
+        if (!idx_) return r;
+        if (core_k == SIZE_MAX) core_k = min_cluster_size == 0 ? 0 : (min_cluster_size - 1 < knbn ? min_cluster_size - 1 : knbn);
+        const size_t n = get_nb_point(), slots = n > 1 ? n - 1 : 1;
+        r.prepare(n, min_cluster_size);
+        Dendrogram& d = r.dendrogram;
+        d.n_vertices = n;
+        d.forest.a.assign(slots, 0);
+        d.forest.b.assign(slots, 0);
+        d.forest.weights.assign(slots, 0.0f);
+        d.left.assign(slots, 0);
+        d.right.assign(slots, 0);
+        d.sizes.assign(slots, 0);
+        uint64_t count = 0, clusters = 0, n_lab = 0;
+        check(hnswhdb_graph(idx_, knbn, ef, mutual ? HNSWGPU_SYM_MUTUAL : HNSWGPU_SYM_UNION, core_k, min_cluster_size,
+                                    leaf ? HNSWGPU_SELECT_LEAF : HNSWGPU_SELECT_EOM, d.forest.a.data(), d.forest.b.data(), d.forest.weights.data(),
+                                    d.left.data(), d.right.data(), d.sizes.data(), r.labels.data(), r.probabilities.data(), r.point_cluster.data(),
+                                    r.point_w.data(), r.cluster_parent.data(), r.cluster_birth_w.data(), r.cluster_size.data(), r.stability.data(),
+                                    r.selected.data(), &clusters, &n_lab, &count));
+        d.forest.a.resize(count);
+        d.forest.b.resize(count);
+        d.forest.weights.resize(count);
+        d.left.resize(count);
+        d.right.resize(count);
+        d.sizes.resize(count);
+        r.finish(n, clusters, n_lab);
+        return r;
     }
     hnswgpu_index* handle() const { return idx_; }
 
