@@ -357,7 +357,7 @@ int scan_u32(const uint32_t* in, uint32_t* out, uint64_t count, hipStream_t stre
     size_t temp_bytes = 0;
     DevMem temp;
     HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, in, out, 0u, (size_t)count, rocprim::plus<uint32_t>(), stream));
-    HIP_TRY(hipMalloc(&temp.p, std::max<size_t>(temp_bytes, 256)));
+    HIP_TRY(temp.alloc(std::max<size_t>(temp_bytes, 256)));
     HIP_TRY(rocprim::exclusive_scan(temp.p, temp_bytes, in, out, 0u, (size_t)count, rocprim::plus<uint32_t>(), stream));
     HIP_TRY(hipStreamSynchronize(stream));  // (the temporary storage goes when this returns)
     return OK;
@@ -380,7 +380,7 @@ int clusters_of_dendrogram(const char* what, uint64_t n, uint64_t m, const float
     bytes += 4 * round_up(n * 4, 256);                            // point_cluster, point_w, labels, prob
     bytes += 2 * round_up(rows_max * 4, 256) + 2 * round_up(rows_max * 8, 256);  // the rows, twice
     bytes += 9 * round_up(slots * 4, 256) + 2 * round_up((slots + 1) * 4, 256) + 5 * round_up(slots * 8, 256) + round_up(slots, 256);  // per cluster
-    HIP_TRY(hipMalloc(&mem.p, bytes));
+    HIP_TRY(mem.alloc(bytes));
     unsigned char* p = static_cast<unsigned char*>(mem.p);
     uint32_t* words = carve<uint32_t>(p, 64);
     uint32_t* par = carve<uint32_t>(p, nodes);
@@ -467,7 +467,7 @@ int clusters_of_dendrogram(const char* what, uint64_t n, uint64_t m, const float
         size_t temp_bytes = 0;
         DevMem temp;
         HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, key_in, key_out, term_in, term_out, (size_t)rows, 0u, end_bit, stream));
-        HIP_TRY(hipMalloc(&temp.p, std::max<size_t>(temp_bytes, 256)));
+        HIP_TRY(temp.alloc(std::max<size_t>(temp_bytes, 256)));
         HIP_TRY(rocprim::radix_sort_pairs(temp.p, temp_bytes, key_in, key_out, term_in, term_out, (size_t)rows, 0u, end_bit, stream));
         HIP_TRY(hipStreamSynchronize(stream));
     }
@@ -531,7 +531,7 @@ int forest_hdbscan(const ForestHdbscanArgs& a, bool host, void* stream_v, std::s
     const float* d_w = a.w;
     uint32_t *left = nullptr, *right = nullptr, *size = nullptr;
     if (a.m != 0) {
-        HIP_TRY(hipMalloc(&mem.p, (host ? 6 : 3) * bm));
+        HIP_TRY(mem.alloc((host ? 6 : 3) * bm));
         left = static_cast<uint32_t*>(mem.p);
         right = left + bm / 4;
         size = right + bm / 4;
@@ -565,7 +565,7 @@ int graph_hdbscan(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, cons
     const uint64_t slots = round_up((std::max<uint64_t>(n, 2) - 1) * 4, 256);
     DevMem mem;
     Drain drain{stream};
-    HIP_TRY(hipMalloc(&mem.p, 6 * slots));
+    HIP_TRY(mem.alloc(6 * slots));
     uint32_t* base = static_cast<uint32_t*>(mem.p);
     uint32_t *f_a = base, *f_b = base + slots / 4, *left = base + 3 * (slots / 4), *right = base + 4 * (slots / 4), *size = base + 5 * (slots / 4);
     float* f_w = reinterpret_cast<float*>(base + 2 * (slots / 4));

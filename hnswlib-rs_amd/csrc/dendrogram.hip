@@ -233,7 +233,7 @@ int dendrogram_of_edges(uint64_t n, uint64_t m, const uint32_t* a, const uint32_
     DevMem mem;
     Drain drain{stream};
     // la, lb (m words each), parent, top, wsum, w (n + m words each), the word
-    HIP_TRY(hipMalloc(&mem.p, 2 * bm + 4 * bl + 256));
+    HIP_TRY(mem.alloc(2 * bm + 4 * bl + 256));
     unsigned char* p = static_cast<unsigned char*>(mem.p);
     uint32_t* la = reinterpret_cast<uint32_t*>(p); p += bm;
     uint32_t* lb = reinterpret_cast<uint32_t*>(p); p += bm;
@@ -321,7 +321,7 @@ int graph_dendrogram(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, c
     uint64_t edges = 0;
     f.out_n = &edges;
     if (host) {
-        HIP_TRY(hipMalloc(&m_forest.p, 3 * slots));
+        HIP_TRY(m_forest.alloc(3 * slots));
         f.out_a = static_cast<uint32_t*>(m_forest.p);
         f.out_b = f.out_a + slots / 4;
         f.out_w = reinterpret_cast<float*>(f.out_b + slots / 4);

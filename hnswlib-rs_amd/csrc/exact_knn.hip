@@ -430,14 +430,15 @@ struct ScratchLease {
             std::lock_guard<std::mutex> g(st->mu);
             if (!st->pool.empty()) { p = st->pool.back().first; bytes = st->pool.back().second; st->pool.pop_back(); }
         }
-        if (bytes >= need) return hipSuccess;
+        // (HNSWGPU_POISON_SCRATCH: the block a call takes, reused or new, is nobody's over its whole size)
+        if (bytes >= need) return poison_scratch(p, bytes);
         if (p) (void)hipFree(p);
         p = nullptr;
         bytes = 0;
         const hipError_t e = hipMalloc(&p, need);
         if (e != hipSuccess) { p = nullptr; return e; }
         bytes = need;
-        return hipSuccess;
+        return poison_scratch(p, bytes);
     }
     ~ScratchLease() {
         if (!p) return;
@@ -937,9 +938,9 @@ int exact_range(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, 
 
     DevMem m_q, m_rad, m_off;
     if (io.host) {
-        HIP_TRY(hipMalloc(&m_q.p, block_q * d * 4));
-        HIP_TRY(hipMalloc(&m_rad.p, block_q * 4));
-        HIP_TRY(hipMalloc(&m_off.p, (block_q + 1) * 8));
+        HIP_TRY(m_q.alloc(block_q * d * 4));
+        HIP_TRY(m_rad.alloc(block_q * 4));
+        HIP_TRY(m_off.alloc((block_q + 1) * 8));
     }
     // the offsets on the host: the caller's array, or a copy of it (the plan of the fill pass is made here)
     std::vector<uint64_t> off_copy;
@@ -1146,11 +1147,11 @@ struct GraphCall {
 // searched and no output written, when an id names no point.
 int graph_resolve(const DeviceIndexView& v, const ExactState* st, const GraphCall& io, DevMem& m_flat, hipStream_t stream, std::string& err) {
     DevMem m_ids, m_ctrl;
-    HIP_TRY(hipMalloc(&m_flat.p, io.np * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&m_ctrl.p, 256));
+    HIP_TRY(m_flat.alloc(io.np * sizeof(uint32_t)));
+    HIP_TRY(m_ctrl.alloc(256));
     const uint64_t* d_ids = io.point_ids;
     if (io.host && io.point_ids != nullptr) {
-        HIP_TRY(hipMalloc(&m_ids.p, io.np * sizeof(uint64_t)));
+        HIP_TRY(m_ids.alloc(io.np * sizeof(uint64_t)));
         HIP_TRY(hipMemcpyAsync(m_ids.p, io.point_ids, io.np * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
         d_ids = static_cast<const uint64_t*>(m_ids.p);
     }
@@ -1178,7 +1179,7 @@ struct AnswerStage {
     DevMem mem;
     GraphRows rows{};
     hipError_t alloc(uint64_t chunk, uint64_t k) {
-        const hipError_t e = hipMalloc(&mem.p, round_up(chunk * k * 8, 256) + 2 * round_up(chunk * k * 4, 256) + round_up(chunk * 4, 256) + round_up(chunk * k, 256));
+        const hipError_t e = mem.alloc(round_up(chunk * k * 8, 256) + 2 * round_up(chunk * k * 4, 256) + round_up(chunk * 4, 256) + round_up(chunk * k, 256));
         if (e != hipSuccess) { mem.p = nullptr; return e; }
         unsigned char* p = static_cast<unsigned char*>(mem.p);
         rows.ids = reinterpret_cast<uint64_t*>(p); p += round_up(chunk * k * 8, 256);
@@ -1209,8 +1210,8 @@ int exact_host_chunks(const DeviceIndex& dev, const std::vector<uint64_t>& origi
     const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(nq, (64ull << 20) / per_q));
     DevMem m_q, m_of;
     AnswerStage stage;
-    HIP_TRY(hipMalloc(&m_q.p, chunk * d * 4));
-    if (d_set) HIP_TRY(hipMalloc(&m_of.p, chunk * sizeof(uint32_t)));
+    HIP_TRY(m_q.alloc(chunk * d * 4));
+    if (d_set) HIP_TRY(m_of.alloc(chunk * sizeof(uint32_t)));
     HIP_TRY(stage.alloc(chunk, k));
     const FilterSet chunk_set{d_set ? d_set->ids : nullptr, d_set ? d_set->offsets : nullptr, d_set ? d_set->n_filters : 0, static_cast<const uint32_t*>(m_of.p)};
     const SetCall call{&chunk_set, filter_set_budget()};
@@ -1233,7 +1234,7 @@ int exact_host(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, c
     HIP_TRY(on.status());
     DevMem m_allowed;  // (a filter that is empty still is a filter: a non-null pointer that is never dereferenced)
     if (allowed != nullptr) {
-        HIP_TRY(hipMalloc(&m_allowed.p, std::max<uint64_t>(1, n_allowed) * sizeof(uint64_t)));
+        HIP_TRY(m_allowed.alloc(std::max<uint64_t>(1, n_allowed) * sizeof(uint64_t)));
         if (n_allowed != 0) HIP_TRY(hipMemcpy(m_allowed.p, allowed, n_allowed * sizeof(uint64_t), hipMemcpyHostToDevice));
     }
     return exact_host_chunks(dev, origin_id, queries, nq, d, k, static_cast<const uint64_t*>(m_allowed.p), n_allowed, allowed != nullptr, nullptr, nullptr,
@@ -1261,8 +1262,8 @@ int exact_filter_set_host(const DeviceIndex& dev, const std::vector<uint64_t>& o
     HIP_TRY(on.status());
     const uint64_t n_ids = set.offsets[set.n_filters];
     DevMem m_ids, m_off;
-    HIP_TRY(hipMalloc(&m_ids.p, std::max<uint64_t>(1, n_ids) * sizeof(uint64_t)));  // (filters that are all empty: never read)
-    HIP_TRY(hipMalloc(&m_off.p, (set.n_filters + 1) * sizeof(uint64_t)));
+    HIP_TRY(m_ids.alloc(std::max<uint64_t>(1, n_ids) * sizeof(uint64_t)));  // (filters that are all empty: never read)
+    HIP_TRY(m_off.alloc((set.n_filters + 1) * sizeof(uint64_t)));
     if (n_ids != 0) HIP_TRY(hipMemcpy(m_ids.p, set.ids, n_ids * sizeof(uint64_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(m_off.p, set.offsets, (set.n_filters + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
     const FilterSet d_set{static_cast<const uint64_t*>(m_ids.p), static_cast<const uint64_t*>(m_off.p), set.n_filters, nullptr};
@@ -1288,7 +1289,7 @@ int exact_range_host(const DeviceIndex& dev, const std::vector<uint64_t>& origin
     HIP_TRY(on.status());
     DevMem m_allowed;
     if (allowed != nullptr) {
-        HIP_TRY(hipMalloc(&m_allowed.p, std::max<uint64_t>(1, n_allowed) * sizeof(uint64_t)));
+        HIP_TRY(m_allowed.alloc(std::max<uint64_t>(1, n_allowed) * sizeof(uint64_t)));
         if (n_allowed != 0) HIP_TRY(hipMemcpy(m_allowed.p, allowed, n_allowed * sizeof(uint64_t), hipMemcpyHostToDevice));
     }
     const RangeCall io{true, queries, radii, static_cast<const uint64_t*>(m_allowed.p), n_allowed, allowed != nullptr, cap, out_offsets, out_ids,
@@ -1329,7 +1330,7 @@ int graph_search(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, bool 
     const uint64_t per_point = d * 4 + k1 * 17 + 4 + (host ? k * 17 + 4 : 0);
     const int64_t knob = knobs().graph_chunk;
     const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>({np, GRAPH_SCRATCH / per_point, knob > 0 ? (uint64_t)knob : np}));
-    HIP_TRY(hipMalloc(&m_q.p, chunk * d * 4));
+    HIP_TRY(m_q.alloc(chunk * d * 4));
     float* d_q = static_cast<float*>(m_q.p);
     HIP_TRY(wide.alloc(chunk, k1));
     if (host) HIP_TRY(stage.alloc(chunk, k));
@@ -1376,7 +1377,7 @@ int exact_graph(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, 
     // (a filter that is empty still is a filter: a non-null pointer that is never dereferenced)
     const uint64_t* d_allowed = filtered ? reinterpret_cast<const uint64_t*>(m_flat.p) : nullptr;
     if (filtered && n_allowed != 0) {
-        HIP_TRY(hipMalloc(&m_allowed.p, n_allowed * sizeof(uint64_t)));
+        HIP_TRY(m_allowed.alloc(n_allowed * sizeof(uint64_t)));
         HIP_TRY(hipMemcpy(m_allowed.p, allowed, n_allowed * sizeof(uint64_t), hipMemcpyHostToDevice));
         d_allowed = static_cast<const uint64_t*>(m_allowed.p);
     }

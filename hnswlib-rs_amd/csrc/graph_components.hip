@@ -126,7 +126,7 @@ struct Forest {
     uint32_t* number_of = nullptr;
 };
 int forest_init(Forest& f, uint64_t n, hipStream_t stream, std::string& err) {
-    HIP_TRY(hipMalloc(&f.mem.p, 3 * round_up((n + 1) * 4, 256)));
+    HIP_TRY(f.mem.alloc(3 * round_up((n + 1) * 4, 256)));
     unsigned char* p = static_cast<unsigned char*>(f.mem.p);
     f.parent = reinterpret_cast<uint32_t*>(p); p += round_up((n + 1) * 4, 256);
     f.mark = reinterpret_cast<uint32_t*>(p); p += round_up((n + 1) * 4, 256);
@@ -144,7 +144,7 @@ int forest_answer(Forest& f, uint64_t n, bool host, uint32_t* out_label, uint32_
     HIP_TRY(hipGetLastError());
     size_t temp_bytes = 0;
     HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, f.mark, f.number_of, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), stream));
-    HIP_TRY(hipMalloc(&m_temp.p, std::max<size_t>(temp_bytes, 256)));
+    HIP_TRY(m_temp.alloc(std::max<size_t>(temp_bytes, 256)));
     HIP_TRY(rocprim::exclusive_scan(m_temp.p, temp_bytes, f.mark, f.number_of, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), stream));
     uint32_t c = 0;
     HIP_TRY(hipMemcpyAsync(&c, f.number_of + n, 4, hipMemcpyDeviceToHost, stream));  // the read-back of the device entries
@@ -156,7 +156,7 @@ int forest_answer(Forest& f, uint64_t n, bool host, uint32_t* out_label, uint32_
     uint32_t* d_label = out_label;
     uint32_t* d_sizes = out_sizes;
     if (host) {
-        HIP_TRY(hipMalloc(&m_out.p, round_up(n * 4, 256) + (uint64_t)c * 4));
+        HIP_TRY(m_out.alloc(round_up(n * 4, 256) + (uint64_t)c * 4));
         d_label = static_cast<uint32_t*>(m_out.p);
         d_sizes = out_sizes ? d_label + round_up(n * 4, 256) / 4 : nullptr;
     }
@@ -231,7 +231,7 @@ int csr_components(const CsrComponentsArgs& a, bool host, void* stream_v, std::s
     if (host) {
         const uint64_t total = a.offsets[n];
         const uint64_t b_offs = round_up((n + 1) * 8, 256), b_cols = round_up(total * 4, 256);
-        HIP_TRY(hipMalloc(&m_in.p, b_offs + b_cols * (a.has_cut ? 2 : 1) + 256));
+        HIP_TRY(m_in.alloc(b_offs + b_cols * (a.has_cut ? 2 : 1) + 256));
         unsigned char* p = static_cast<unsigned char*>(m_in.p);
         HIP_TRY(hipMemcpyAsync(p, a.offsets, (n + 1) * 8, hipMemcpyHostToDevice, stream));
         d_offsets = reinterpret_cast<const uint64_t*>(p); p += b_offs;
@@ -241,7 +241,7 @@ int csr_components(const CsrComponentsArgs& a, bool host, void* stream_v, std::s
         d_dists = reinterpret_cast<const float*>(p);
     }
     // the checks, and the one word that says how they went
-    HIP_TRY(hipMalloc(&m_word.p, 256));
+    HIP_TRY(m_word.alloc(256));
     unsigned long long* d_word = static_cast<unsigned long long*>(m_word.p);
     HIP_TRY(hipMemsetAsync(d_word, 0, 8, stream));
     hipLaunchKernelGGL(cc_check_offsets_kernel, grid_of(n + 1), dim3(256), 0, stream, d_offsets, (uint32_t)n, d_word);

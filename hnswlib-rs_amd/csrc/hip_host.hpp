@@ -5,9 +5,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdio>
 #include <string>
 
 #include "hnswio.hpp"  // ERR_DEVICE
+#include "search_device.hpp"  // knobs()
 
 // inside a function that returns a status code and has a `std::string& err` in scope
 #define HIP_TRY(expr)                                                                          \
@@ -21,12 +23,35 @@
 
 namespace hnswgpu {
 
+// HNSWGPU_POISON_SCRATCH (test hook, Knobs::poison_scratch): what one call filled, per host thread.  A call is the lifetime of the
+// outermost DeviceGuard of its thread -- every device entry makes one before it allocates or takes anything from a pool, and the
+// entries that call each other (the graph units down to the search) nest theirs.
+struct PoisonTally {
+    int depth = 0;
+    uint64_t blocks = 0, bytes = 0;
+};
+inline thread_local PoisonTally t_poison;
+
+// Scratch that passes from nobody's to this call's: with the knob on, `bytes` at `p` are filled with its byte and the host waits
+// for the fill before the block is handed on.  With the knob off (the default) nothing is asked of the runtime.
+inline hipError_t poison_scratch(void* p, uint64_t bytes) {
+    const int byte = knobs().poison_scratch;
+    if (byte < 0 || p == nullptr || bytes == 0) return hipSuccess;
+    hipError_t e = hipMemset(p, byte, (size_t)bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return e;
+    t_poison.blocks += 1;
+    t_poison.bytes += bytes;
+    return hipSuccess;
+}
+
 // Every entry point works on the replica's device and leaves the CALLER's current HIP device as it found it (a host
 // thread shared with PyTorch, a Rust or a Julia runtime keeps allocating and launching where it did before the call).
 // device < 0 (a state that never got a device): nothing is asked of the runtime.
 class DeviceGuard {
 public:
     explicit DeviceGuard(int device) {
+        ++t_poison.depth;
         if (device < 0) return;
         int cur = -1;
         if (hipGetDevice(&cur) != hipSuccess) cur = -1;
@@ -37,7 +62,15 @@ public:
         // unrelated launch would report it as that launch's)
         if (status_ != hipSuccess) (void)hipGetLastError();
     }
-    ~DeviceGuard() { if (prev_ >= 0) (void)hipSetDevice(prev_); }
+    ~DeviceGuard() {
+        if (prev_ >= 0) (void)hipSetDevice(prev_);
+        if (--t_poison.depth > 0 || t_poison.blocks == 0) return;
+        // the call ends: one line under HNSWGPU_TRACE_LAUNCH (the tests read it to prove that the hook ran for this entry)
+        if (knobs().trace_launch)
+            std::fprintf(stderr, "[hnswgpu poison] blocks %llu bytes %llu byte 0x%02x\n", (unsigned long long)t_poison.blocks,
+                         (unsigned long long)t_poison.bytes, (unsigned)(knobs().poison_scratch & 0xFF));
+        t_poison.blocks = t_poison.bytes = 0;
+    }
     DeviceGuard(const DeviceGuard&) = delete;
     DeviceGuard& operator=(const DeviceGuard&) = delete;
     hipError_t status() const { return status_; }
@@ -50,6 +83,12 @@ private:
 struct DevMem {
     void* p = nullptr;
     ~DevMem() { release(); }
+    // a fresh block of `bytes`, poisoned under HNSWGPU_POISON_SCRATCH: every call-scoped allocation goes through here
+    hipError_t alloc(size_t bytes) {
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        return poison_scratch(p, bytes);
+    }
     void release() { if (p) (void)hipFree(p); p = nullptr; }
 };
 

@@ -188,7 +188,7 @@ int range_search(DeviceIndex& dev, const RangeSearchArgs& a, bool host, hipStrea
     const bool keep = a.out_ids != nullptr;   // (else the count-only call)
     // the group's small arrays, one block
     const uint64_t qmat = round_up(group * d * 4, 256), w4 = round_up(group * 4, 256);
-    HIP_TRY(hipMalloc(&m_small.p, (host ? 2 : 1) * qmat + 8 * w4 + round_up(group * 8, 256) + round_up(group, 256) + 256));
+    HIP_TRY(m_small.alloc((host ? 2 : 1) * qmat + 8 * w4 + round_up(group * 8, 256) + round_up(group, 256) + 256));
     unsigned char* p = static_cast<unsigned char*>(m_small.p);
     auto take = [&](uint64_t bytes) { unsigned char* r = p; p += bytes; return r; };
     float* d_qround = reinterpret_cast<float*>(take(qmat));
@@ -204,8 +204,8 @@ int range_search(DeviceIndex& dev, const RangeSearchArgs& a, bool host, hipStrea
     uint64_t* d_offs = reinterpret_cast<uint64_t*>(take(round_up(group * 8, 256)));  // (host calls)
     uint8_t* d_flags = take(round_up(group, 256));            // (host calls)
     uint32_t* d_ctrl = reinterpret_cast<uint32_t*>(take(256));
-    HIP_TRY(hipMalloc(&m_staged.p, slots_bytes(slots)));
-    if (keep) HIP_TRY(hipMalloc(&m_held.p, slots_bytes(slots)));
+    HIP_TRY(m_staged.alloc(slots_bytes(slots)));
+    if (keep) HIP_TRY(m_held.alloc(slots_bytes(slots)));
     const RangeSlots held = keep ? carve_slots(m_held.p, slots) : RangeSlots{};
 
     if (host) a.out_offsets[0] = 0;
@@ -314,7 +314,7 @@ int range_search_host(DeviceIndex& dev, const RangeSearchArgs& a, std::string& e
     DevMem m_allowed;
     RangeSearchArgs b = a;
     if (a.filtered && a.n_allowed != 0) {
-        HIP_TRY(hipMalloc(&m_allowed.p, a.n_allowed * sizeof(uint64_t)));
+        HIP_TRY(m_allowed.alloc(a.n_allowed * sizeof(uint64_t)));
         HIP_TRY(hipMemcpy(m_allowed.p, a.allowed, a.n_allowed * sizeof(uint64_t), hipMemcpyHostToDevice));
     }
     b.allowed = static_cast<const uint64_t*>(m_allowed.p);

@@ -85,6 +85,11 @@ Knobs read_knobs() {
         const long long v = std::atoll(e);
         k.range_chunk = v < 1 ? -1 : (int64_t)std::min<long long>(v, 1ll << 31);
     }
+    if (const char* e = std::getenv("HNSWGPU_POISON_SCRATCH")) {  // a whole number 0 .. 255, nothing behind it: anything else is off
+        char* end = nullptr;
+        const long v = std::strtol(e, &end, 0);
+        if (end != e && *end == '\0' && v >= 0 && v <= 255) k.poison_scratch = (int)v;
+    }
     return k;
 }
 std::atomic<const Knobs*> g_knobs{nullptr};
@@ -174,8 +179,10 @@ struct DevBuf {
         const hipError_t e = hipMalloc(&p, bytes);
         if (e != hipSuccess) { p = nullptr; return e; }
         cap = bytes;
-        return hipSuccess;
+        return poison_scratch(p, cap);  // (growth kept nothing of the old block)
     }
+    // a pooled buffer as a call takes it: whatever an earlier call left is nobody's (HNSWGPU_POISON_SCRATCH)
+    hipError_t poison() const { return poison_scratch(p, cap); }
     void free() {
         if (p) (void)hipFree(p);
         p = nullptr;
@@ -246,12 +253,20 @@ struct DeviceIndex::Workspace {
     hipStream_t own_stream = nullptr;  // for the host-buffer entry points
     int init(std::string& err) {
         HIP_TRY(hipMalloc(&d_ctrl, 64));
+        HIP_TRY(poison_scratch(d_ctrl, 64));
         HIP_TRY(hipHostMalloc(&h_ctrl, 64, hipHostMallocDefault));
         HIP_TRY(hipEventCreate(&ev_start));
         HIP_TRY(hipEventCreate(&ev_stop));
         HIP_TRY(hipEventCreate(&ev_ks));
         HIP_TRY(hipEventCreate(&ev_ke));
         HIP_TRY(hipStreamCreateWithFlags(&own_stream, hipStreamNonBlocking));
+        return OK;
+    }
+    // HNSWGPU_POISON_SCRATCH, a pooled workspace as the next call takes it: every buffer over its whole capacity, and the counters
+    int poison(std::string& err) {
+        for (DevBuf* b : {&qpad, &tie, &pre, &order, &retry[0], &retry[1], &stats, &bitmap, &heaps, &cand, &oplog, &allow, &allowed_ids, &slot_of, &set_offsets, &set_of})
+            HIP_TRY(b->poison());
+        HIP_TRY(poison_scratch(d_ctrl, 64));
         return OK;
     }
     ~Workspace() {
@@ -280,13 +295,20 @@ private:
 };
 
 DeviceIndex::Workspace* DeviceIndex::acquire(std::string& err) {
+    Workspace* pooled = nullptr;
     {
         std::lock_guard<std::mutex> g(pool_mu_);
         if (!free_ws_.empty()) {
-            Workspace* w = free_ws_.back();
+            pooled = free_ws_.back();
             free_ws_.pop_back();
-            return w;
         }
+    }
+    if (pooled != nullptr) {
+        if (knobs().poison_scratch >= 0 && pooled->poison(err) != OK) {
+            release_ws(pooled);
+            return nullptr;
+        }
+        return pooled;
     }
     std::unique_ptr<Workspace> w(new Workspace());
     if (w->init(err) != OK) return nullptr;
@@ -1547,6 +1569,7 @@ public:
             max_stride_ = std::max(max_stride_, stride);
         }
         HIP_TRY(hipMalloc(&d_ctrl_, 64));
+        HIP_TRY(poison_scratch(d_ctrl_, 64));
         HIP_TRY(hipDeviceSynchronize());
         return OK;
     }
@@ -1568,6 +1591,7 @@ public:
         if (n_records > 0xFFFFFFFFull) { err = "too many list updates"; return ERR_ARG; }
         for (uint64_t u = 0; u < n_records; ++u)
             if (records[u * rw + 1] > top_layer_ || records[u * rw] >= n_) { err = "internal error: list update outside the snapshot"; return ERR_ARG; }
+        HIP_TRY(upd_.poison());  // (HNSWGPU_POISON_SCRATCH: the previous patch's records are nobody's)
         HIP_TRY(upd_.ensure(n_records * rw * sizeof(uint32_t)));
         HIP_TRY(hipMemcpyAsync(upd_.p, records, n_records * rw * sizeof(uint32_t), hipMemcpyHostToDevice, nullptr));  // pinned: a DMA at link speed
         HIP_TRY(launch_scatter_lists(nullptr, upd_.as<uint32_t>(), (uint32_t)n_records, rw, bl_));
@@ -1579,6 +1603,9 @@ public:
         DeviceGuard on_device(device_);
         HIP_TRY(on_device.status());
         if (entry_level > top_layer_) { err = "internal error: entry point above the snapshot's layers"; return ERR_ARG; }
+        // HNSWGPU_POISON_SCRATCH: what the previous window left in the scratch (never the vectors, levels, norms and lists)
+        for (DevBuf* b : {&slot0_, &out_ids_, &out_d_, &out_n_, &hit_ids_, &hit_d_, &bitmap_, &slot_nb_, &sel_ids_, &sel_d_, &sel_n_}) HIP_TRY(b->poison());
+        HIP_TRY(poison_scratch(d_ctrl_, 64));
         // output slots: one per (point, layer <= min(level, entry level))
         levels_h_.resize(count);
         HIP_TRY(hipMemcpy(levels_h_.data(), level_.as<uint8_t>() + first, count, hipMemcpyDeviceToHost));

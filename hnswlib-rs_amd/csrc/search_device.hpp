@@ -54,6 +54,10 @@ struct Knobs {
                                  // its 256 MiB of queries and staged answers hold)
     int64_t range_chunk = -1;    // HNSWGPU_RANGE_CHUNK (test hook): the queries one group of hnswgpu_range_search_batch serves at most (1 ..; unset: as many as
                                  // keep a round's staged answers and the group's held answers within 256 MiB each)
+    int poison_scratch = -1;     // HNSWGPU_POISON_SCRATCH (test hook, host code only): 0 .. 255 = every device scratch block is filled with this byte where it
+                                 // passes from nobody's to a call's -- a fresh allocation, a pooled workspace or exact-unit block as it is taken, the builder
+                                 // backend's scratch per window -- and the host waits for the fill (hip_host.hpp: poison_scratch).  Replica data, caller
+                                 // buffers and pinned staging are never filled.  Unset or out of range: off, no HIP call more on any path
 };
 const Knobs& knobs();
 void reload_knobs();

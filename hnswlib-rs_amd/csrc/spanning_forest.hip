@@ -237,7 +237,7 @@ int forest_of_edges(uint64_t n, uint64_t m, const uint32_t* e_lo, const uint32_t
     DevMem mem, m_temp, m_out;
     Drain drain{stream};
     // okey_in, okey_out, self, from, a, b (m words each; flag and its scan stand where the two okeys stood), parent, best, mark (n), hooked
-    HIP_TRY(hipMalloc(&mem.p, 6 * bm + 3 * bn + round_up((uint64_t)bound * 4, 256)));
+    HIP_TRY(mem.alloc(6 * bm + 3 * bn + round_up((uint64_t)bound * 4, 256)));
     unsigned char* p = static_cast<unsigned char*>(mem.p);
     uint32_t* okey_in = reinterpret_cast<uint32_t*>(p); p += bm;
     uint32_t* okey_out = reinterpret_cast<uint32_t*>(p); p += bm;
@@ -257,7 +257,7 @@ int forest_of_edges(uint64_t n, uint64_t m, const uint32_t* e_lo, const uint32_t
     HIP_TRY(hipGetLastError());
     size_t temp_bytes = 0;
     HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, okey_in, okey_out, self, from, (size_t)m, 0u, 32u, stream));
-    HIP_TRY(hipMalloc(&m_temp.p, std::max<size_t>(temp_bytes, 256)));
+    HIP_TRY(m_temp.alloc(std::max<size_t>(temp_bytes, 256)));
     HIP_TRY(rocprim::radix_sort_pairs(m_temp.p, temp_bytes, okey_in, okey_out, self, from, (size_t)m, 0u, 32u, stream));
     hipLaunchKernelGGL(msf_gather_kernel, grid_of(m + 1), dim3(256), 0, stream, from, e_lo, e_hi, (uint32_t)m, a, b, flag);
     HIP_TRY(hipGetLastError());
@@ -288,7 +288,7 @@ int forest_of_edges(uint64_t n, uint64_t m, const uint32_t* e_lo, const uint32_t
     m_temp.release();
     temp_bytes = 0;
     HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, flag, slot_of, 0u, (size_t)m + 1, rocprim::plus<uint32_t>(), stream));
-    HIP_TRY(hipMalloc(&m_temp.p, std::max<size_t>(temp_bytes, 256)));
+    HIP_TRY(m_temp.alloc(std::max<size_t>(temp_bytes, 256)));
     HIP_TRY(rocprim::exclusive_scan(m_temp.p, temp_bytes, flag, slot_of, 0u, (size_t)m + 1, rocprim::plus<uint32_t>(), stream));
     uint32_t edges = 0;
     HIP_TRY(hipMemcpyAsync(&edges, slot_of + m, 4, hipMemcpyDeviceToHost, stream));
@@ -306,7 +306,7 @@ int forest_of_edges(uint64_t n, uint64_t m, const uint32_t* e_lo, const uint32_t
     uint32_t* d_w = reinterpret_cast<uint32_t*>(out_w);
     const uint64_t be = round_up((uint64_t)edges * 4, 256);
     if (host) {
-        HIP_TRY(hipMalloc(&m_out.p, 3 * be));
+        HIP_TRY(m_out.alloc(3 * be));
         d_a = static_cast<uint32_t*>(m_out.p);
         d_b = d_a + be / 4;
         d_w = d_b + be / 4;
@@ -344,7 +344,7 @@ int graph_spanning_forest(DeviceIndex& dev, const std::vector<uint64_t>& origin_
         StagedGraph d;
         rc = sorted_edge_records_keeping(dev, origin_id, ord, k, a.ef, stream_v, rec, d, err);
         if (rc != OK) return rc;
-        HIP_TRY(hipMalloc(&m_core.p, round_up(n * 4, 256)));
+        HIP_TRY(m_core.alloc(round_up(n * 4, 256)));
         core = static_cast<uint32_t*>(m_core.p);
         hipLaunchKernelGGL(msf_core_kernel, grid_of(n), dim3(256), 0, stream, d.dists, d.counts, (uint32_t)k, (uint32_t)a.core_k, (uint32_t)n, core);
         HIP_TRY(hipGetLastError());
@@ -365,7 +365,7 @@ int graph_spanning_forest(DeviceIndex& dev, const std::vector<uint64_t>& origin_
     HIP_TRY(hipGetLastError());
     size_t temp_bytes = 0;
     HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, mark, slot_of, 0u, (size_t)records + 1, rocprim::plus<uint32_t>(), stream));
-    HIP_TRY(hipMalloc(&m_temp.p, std::max<size_t>(temp_bytes, 256)));
+    HIP_TRY(m_temp.alloc(std::max<size_t>(temp_bytes, 256)));
     HIP_TRY(rocprim::exclusive_scan(m_temp.p, temp_bytes, mark, slot_of, 0u, (size_t)records + 1, rocprim::plus<uint32_t>(), stream));
     uint32_t m32 = 0;
     HIP_TRY(hipMemcpyAsync(&m32, slot_of + records, 4, hipMemcpyDeviceToHost, stream));
@@ -377,7 +377,7 @@ int graph_spanning_forest(DeviceIndex& dev, const std::vector<uint64_t>& origin_
         return ERR_FORMAT;
     }
     const uint64_t bm = round_up(std::max<uint64_t>(m, 1) * 4, 256);
-    HIP_TRY(hipMalloc(&m_edges.p, 3 * bm));
+    HIP_TRY(m_edges.alloc(3 * bm));
     uint32_t* e_lo = static_cast<uint32_t*>(m_edges.p);
     uint32_t* e_hi = e_lo + bm / 4;
     uint32_t* e_bits = e_hi + bm / 4;
@@ -414,7 +414,7 @@ int csr_spanning_forest(const CsrForestArgs& a, bool host, void* stream_v, std::
     if (host) {
         const uint64_t total = a.offsets[n];
         const uint64_t b_offs = round_up((n + 1) * 8, 256), b_cols = round_up(total * 4, 256);
-        HIP_TRY(hipMalloc(&m_in.p, b_offs + b_cols * (a.dists ? 2 : 1) + 256));
+        HIP_TRY(m_in.alloc(b_offs + b_cols * (a.dists ? 2 : 1) + 256));
         unsigned char* p = static_cast<unsigned char*>(m_in.p);
         HIP_TRY(hipMemcpyAsync(p, a.offsets, (n + 1) * 8, hipMemcpyHostToDevice, stream));
         d_offsets = reinterpret_cast<const uint64_t*>(p); p += b_offs;
@@ -424,7 +424,7 @@ int csr_spanning_forest(const CsrForestArgs& a, bool host, void* stream_v, std::
         if (a.dists) d_dists = reinterpret_cast<const float*>(p);
     }
     // the checks, and the one word that says how they went
-    HIP_TRY(hipMalloc(&m_word.p, 256));
+    HIP_TRY(m_word.alloc(256));
     unsigned long long* d_word = static_cast<unsigned long long*>(m_word.p);
     HIP_TRY(hipMemsetAsync(d_word, 0, 8, stream));
     hipLaunchKernelGGL(cc_check_offsets_kernel, grid_of(n + 1), dim3(256), 0, stream, d_offsets, (uint32_t)n, d_word);
@@ -446,8 +446,8 @@ int csr_spanning_forest(const CsrForestArgs& a, bool host, void* stream_v, std::
     if (m == 0) return forest_of_edges(n, 0, nullptr, nullptr, nullptr, host, a.out_a, a.out_b, a.out_w, a.out_n, stream, err);
     // the entries as (lo, hi) keys with their bits, sorted by key
     const uint64_t b8 = round_up(m * 8, 256), b4 = round_up(m * 4, 256);
-    HIP_TRY(hipMalloc(&m_keys.p, 2 * b8 + b4));
-    HIP_TRY(hipMalloc(&m_edges.p, 3 * b4));
+    HIP_TRY(m_keys.alloc(2 * b8 + b4));
+    HIP_TRY(m_edges.alloc(3 * b4));
     unsigned char* p = static_cast<unsigned char*>(m_keys.p);
     uint64_t* keys_in = reinterpret_cast<uint64_t*>(p); p += b8;
     uint64_t* keys_out = reinterpret_cast<uint64_t*>(p); p += b8;
@@ -461,7 +461,7 @@ int csr_spanning_forest(const CsrForestArgs& a, bool host, void* stream_v, std::
     while (end_bit < 64 && (n >> (end_bit - 32)) != 0) ++end_bit;
     size_t temp_bytes = 0;
     HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, keys_out, bits_in, e_bits, (size_t)m, 0u, end_bit, stream));
-    HIP_TRY(hipMalloc(&m_temp.p, std::max<size_t>(temp_bytes, 256)));
+    HIP_TRY(m_temp.alloc(std::max<size_t>(temp_bytes, 256)));
     HIP_TRY(rocprim::radix_sort_pairs(m_temp.p, temp_bytes, keys_in, keys_out, bits_in, e_bits, (size_t)m, 0u, end_bit, stream));
     hipLaunchKernelGGL(msf_unpack_kernel, grid_of(m), dim3(256), 0, stream, keys_out, (uint32_t)m, e_lo, e_hi);
     HIP_TRY(hipGetLastError());

@@ -146,7 +146,7 @@ int stage_directed_graph(DeviceIndex& dev, const std::vector<uint64_t>& origin_i
                          std::string& err) {
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     const uint64_t n = dev.view().n, slots = n * k;
-    HIP_TRY(hipMalloc(&out.mem.p, round_up(slots * 8, 256) + 2 * round_up(slots * 4, 256) + round_up(n * 4, 256) + round_up(slots, 256)));
+    HIP_TRY(out.mem.alloc(round_up(slots * 8, 256) + 2 * round_up(slots * 4, 256) + round_up(n * 4, 256) + round_up(slots, 256)));
     unsigned char* p = static_cast<unsigned char*>(out.mem.p);
     uint64_t* d_ids = reinterpret_cast<uint64_t*>(p); p += round_up(slots * 8, 256);
     out.dists = reinterpret_cast<float*>(p); p += round_up(slots * 4, 256);
@@ -179,10 +179,10 @@ int sorted_edge_records_keeping(DeviceIndex& dev, const std::vector<uint64_t>& o
     if (rc != OK) return rc;
 
     // the records, and their sort.  keys_a has room for one word more per half: it holds the marks and their scan afterwards.
-    HIP_TRY(hipMalloc(&out.keys_a.p, records * 8 + 256));
-    HIP_TRY(hipMalloc(&out.keys_b.p, records * 8));
-    HIP_TRY(hipMalloc(&out.vals_a.p, records * 4));
-    HIP_TRY(hipMalloc(&out.vals_b.p, records * 4));
+    HIP_TRY(out.keys_a.alloc(records * 8 + 256));
+    HIP_TRY(out.keys_b.alloc(records * 8));
+    HIP_TRY(out.vals_a.alloc(records * 4));
+    HIP_TRY(out.vals_b.alloc(records * 4));
     uint64_t* keys_a = static_cast<uint64_t*>(out.keys_a.p);
     uint64_t* keys_b = static_cast<uint64_t*>(out.keys_b.p);
     uint32_t* vals_a = static_cast<uint32_t*>(out.vals_a.p);
@@ -194,7 +194,7 @@ int sorted_edge_records_keeping(DeviceIndex& dev, const std::vector<uint64_t>& o
     while (end_bit < 64 && (n >> (end_bit - 33)) != 0) ++end_bit;
     size_t temp_bytes = 0;
     HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_a, keys_b, vals_a, vals_b, (uint32_t)records, 0u, end_bit, stream));
-    HIP_TRY(hipMalloc(&m_temp.p, std::max<size_t>(temp_bytes, 256)));
+    HIP_TRY(m_temp.alloc(std::max<size_t>(temp_bytes, 256)));
     HIP_TRY(rocprim::radix_sort_pairs(m_temp.p, temp_bytes, keys_a, keys_b, vals_a, vals_b, (uint32_t)records, 0u, end_bit, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return OK;  // (the sort's temporary storage is released here)
@@ -239,11 +239,11 @@ int symmetric_graph(DeviceIndex* dev_p, const std::vector<uint64_t>& origin_id, 
     HIP_TRY(hipGetLastError());
     temp_bytes = 0;
     HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, mark, slot_of, 0u, (size_t)records + 1, rocprim::plus<uint32_t>(), stream));
-    HIP_TRY(hipMalloc(&m_temp.p, std::max<size_t>(temp_bytes, 256)));
+    HIP_TRY(m_temp.alloc(std::max<size_t>(temp_bytes, 256)));
     HIP_TRY(rocprim::exclusive_scan(m_temp.p, temp_bytes, mark, slot_of, 0u, (size_t)records + 1, rocprim::plus<uint32_t>(), stream));
     uint64_t* d_offs = a.out_offsets;
     if (host) {
-        HIP_TRY(hipMalloc(&m_offs.p, (n + 1) * 8));
+        HIP_TRY(m_offs.alloc((n + 1) * 8));
         d_offs = static_cast<uint64_t*>(m_offs.p);
     }
     hipLaunchKernelGGL(sym_offsets_kernel, grid_of(n + 1), dim3(256), 0, stream, keys_b, slot_of, (uint32_t)records, (uint32_t)n, d_offs);
@@ -261,7 +261,7 @@ int symmetric_graph(DeviceIndex* dev_p, const std::vector<uint64_t>& origin_id, 
     if (total == 0) return OK;
 
     // the entries at their rows, every row sorted, decoded
-    HIP_TRY(hipMalloc(&m_row.p, 2 * round_up(total * 8, 256) + round_up(total * 4, 256)));
+    HIP_TRY(m_row.alloc(2 * round_up(total * 8, 256) + round_up(total * 4, 256)));
     p = static_cast<unsigned char*>(m_row.p);
     uint64_t* row_keys_in = reinterpret_cast<uint64_t*>(p); p += round_up(total * 8, 256);
     uint64_t* row_keys = reinterpret_cast<uint64_t*>(p); p += round_up(total * 8, 256);
@@ -273,7 +273,7 @@ int symmetric_graph(DeviceIndex* dev_p, const std::vector<uint64_t>& origin_id, 
     temp_bytes = 0;
     HIP_TRY(rocprim::segmented_radix_sort_pairs(nullptr, temp_bytes, row_keys_in, row_keys, row_bits_in, row_bits, (unsigned)total, (unsigned)n, seg, seg + 1, 0u,
                                                 64u, stream));
-    HIP_TRY(hipMalloc(&m_temp.p, std::max<size_t>(temp_bytes, 256)));
+    HIP_TRY(m_temp.alloc(std::max<size_t>(temp_bytes, 256)));
     HIP_TRY(rocprim::segmented_radix_sort_pairs(m_temp.p, temp_bytes, row_keys_in, row_keys, row_bits_in, row_bits, (unsigned)total, (unsigned)n, seg, seg + 1, 0u,
                                                 64u, stream));
     SymSlots out{a.out_pos, a.out_ids, reinterpret_cast<uint32_t*>(a.out_dists), a.out_layer, a.out_rank};

@@ -311,7 +311,8 @@ int hnswgpu_last_tie_count(const hnswgpu_index* idx, uint32_t* ties);
 
 /* The HNSWGPU_* tuning and test hooks (HNSWGPU_HASH_BITS, _NO_SCHED, _NO_INKERNEL, _STRICT_WG_PER_CU, _CAND_LDS, _WAVES_PER_CU,
  * _EXACT_FIRST, _TRACE_LAUNCH, _TRACE_HOST, _HOST_THREADS, _HOST_CHUNKS, _FFI_UNPACK, _FILTER_SET_MB; the test hooks
- * HNSWGPU_BITMAP_SLICES, HNSWGPU_LITERAL_CAND_CAP, HNSWGPU_MAX_WG, HNSWGPU_RANGE_HITS_PER_PASS, HNSWGPU_GRAPH_CHUNK and HNSWGPU_RANGE_CHUNK) are read from the
+ * HNSWGPU_BITMAP_SLICES, HNSWGPU_LITERAL_CAND_CAP, HNSWGPU_MAX_WG, HNSWGPU_RANGE_HITS_PER_PASS, HNSWGPU_GRAPH_CHUNK, HNSWGPU_RANGE_CHUNK and
+ * HNSWGPU_POISON_SCRATCH) are read from the
  * environment ONCE per process, at the library's first search -- never on the launch path.  A caller that changes them afterwards (the tests do)
  * says so with this call.  Always HNSWGPU_OK.                                                                          */
 int hnswgpu_reload_env(void);

@@ -108,3 +108,18 @@ def test_the_workgroup_cap_test_hook_is_documented_as_such():
     design = open(os.path.join(root, "DESIGN.md"), encoding="utf-8").read()
     grid = design[design.index("persistent grid (`occupancy"):]
     assert f"`{name}` (test hook)" in grid[:1500]
+
+
+def test_the_scratch_poison_test_hook_is_documented_as_such():
+    """HNSWGPU_POISON_SCRATCH: held to the same rule, and DESIGN.md holds the first-writer tables it goes with (its parsing, reloading
+    and effect need a device: tests/test_gpu_scratch_poison.py)"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "hnsw_mi355x.h")).read()
+    comment = header[:header.index("int hnswgpu_reload_env(void);")].rsplit("/*", 1)[1]
+    knobs = open(os.path.join(root, "INTEGRATION.md"), encoding="utf-8").read()
+    name = "HNSWGPU_POISON_SCRATCH"
+    assert name in comment
+    assert f"`{name}=" in knobs and "test hook" in knobs[knobs.index(f"`{name}="):][:80]
+    design = open(os.path.join(root, "DESIGN.md"), encoding="utf-8").read()
+    title = "## 17. Scratch memory: who writes it first"
+    assert title in design and f"`{name}" in design[design.index(title):][:2000]

@@ -250,8 +250,8 @@ def want_of(ix, k, ef, mode, cut=None):
     key = (id(ix), k, ef, mode, None if cut is None else float(np.float32(cut)))
     if key not in _WANT:
         res, pos = ix.D(k, ef)
-        _WANT[key] = cut_and_join(ix.n, res.counts, pos, res.dists, mode, cut)
-    return _WANT[key]
+        _WANT[key] = (ix, cut_and_join(ix.n, res.counts, pos, res.dists, mode, cut))   # (ix is kept: an id is unique among LIVE objects only)
+    return _WANT[key][1]
 
 
 def check_index(ix, k, ef, mode, cut=None, what=""):

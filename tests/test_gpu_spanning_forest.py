@@ -291,8 +291,8 @@ def want_of(ix, k, ef, mode, core_k=0):
     key = (id(ix), k, ef, mode, core_k)
     if key not in _WANT:
         res, pos = ix.D(k, ef)
-        _WANT[key] = spanning_forest(ix.n, pair_weights(ix.n, res.counts, pos, res.dists, mode, core_k))
-    return _WANT[key]
+        _WANT[key] = (ix, spanning_forest(ix.n, pair_weights(ix.n, res.counts, pos, res.dists, mode, core_k)))   # (ix is kept: an id is unique among LIVE objects only)
+    return _WANT[key][1]
 
 
 def check_index(ix, k, ef, mode, core_k=0, what=""):
