@@ -39,8 +39,6 @@
 // doubling rounds are counted.  No wavefront waits on another; no floating-point atomic; everything is a function of the input.
 // Everything is computed into scratch, and the out arrays are written at the very end: a refusal touches none of them.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
 #include <string>
@@ -49,6 +47,7 @@
 #include "graph_internal.hpp"
 #include "hip_host.hpp"
 #include "hnswio.hpp"
+#include "rocprim_host.hpp"
 // (the CSR validation kernels that come with the union-find have no caller in this unit)
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunused-function"
@@ -338,28 +337,12 @@ __global__ __launch_bounds__(256) void hd_label_kernel(const uint32_t* __restric
     prob[v] = (top == 0.0 || lam >= top) ? 1.0f : (float)(lam / top);
 }
 
-dim3 grid_of(uint64_t threads) { return dim3((uint32_t)((threads + 255) / 256)); }
-
-struct Drain {
-    hipStream_t s;
-    ~Drain() { (void)hipStreamSynchronize(s); }
-};
-
-// an array of `count` T carved out of p, padded to 256 bytes
-template <typename T>
-T* carve(unsigned char*& p, uint64_t count) {
-    T* out = reinterpret_cast<T*>(p);
-    p += round_up(count * sizeof(T), 256);
-    return out;
-}
-
+// a scan that has ended when this returns (its temporary storage goes here)
 int scan_u32(const uint32_t* in, uint32_t* out, uint64_t count, hipStream_t stream, std::string& err) {
-    size_t temp_bytes = 0;
     DevMem temp;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, in, out, 0u, (size_t)count, rocprim::plus<uint32_t>(), stream));
-    HIP_TRY(temp.alloc(std::max<size_t>(temp_bytes, 256)));
-    HIP_TRY(rocprim::exclusive_scan(temp.p, temp_bytes, in, out, 0u, (size_t)count, rocprim::plus<uint32_t>(), stream));
-    HIP_TRY(hipStreamSynchronize(stream));  // (the temporary storage goes when this returns)
+    const int rc = exclusive_scan_u32(temp, in, out, count, stream, err);
+    if (rc != OK) return rc;
+    HIP_TRY(hipStreamSynchronize(stream));
     return OK;
 }
 
@@ -375,51 +358,32 @@ int clusters_of_dendrogram(const char* what, uint64_t n, uint64_t m, const float
     const uint32_t n32 = (uint32_t)n, m32 = (uint32_t)m, nodes32 = (uint32_t)nodes, mcs32 = (uint32_t)mcs;
     DevMem mem;
     Drain drain{stream};
-    uint64_t bytes = 256;                                         // the words
-    bytes += 3 * round_up(nodes * 4, 256) + 2 * round_up((nodes + 1) * 4, 256);  // par, uf, mark; headflag, hscan
-    bytes += 4 * round_up(n * 4, 256);                            // point_cluster, point_w, labels, prob
-    bytes += 2 * round_up(rows_max * 4, 256) + 2 * round_up(rows_max * 8, 256);  // the rows, twice
-    bytes += 9 * round_up(slots * 4, 256) + 2 * round_up((slots + 1) * 4, 256) + 5 * round_up(slots * 8, 256) + round_up(slots, 256);  // per cluster
-    HIP_TRY(mem.alloc(bytes));
-    unsigned char* p = static_cast<unsigned char*>(mem.p);
-    uint32_t* words = carve<uint32_t>(p, 64);
-    uint32_t* par = carve<uint32_t>(p, nodes);
-    uint32_t* uf = carve<uint32_t>(p, nodes);
-    uint32_t* mark = carve<uint32_t>(p, nodes);
-    uint32_t* headflag = carve<uint32_t>(p, nodes + 1);
-    uint32_t* hscan = carve<uint32_t>(p, nodes + 1);
-    uint32_t* point_cluster = carve<uint32_t>(p, n);
-    uint32_t* point_w = carve<uint32_t>(p, n);
-    int32_t* labels = carve<int32_t>(p, n);
-    float* prob = carve<float>(p, n);
-    uint32_t* key_in = carve<uint32_t>(p, rows_max);
-    uint32_t* key_out = carve<uint32_t>(p, rows_max);
-    double* term_in = carve<double>(p, rows_max);
-    double* term_out = carve<double>(p, rows_max);
-    // per cluster; those that are 0 before their kernels stand together: child_hi, arrive, wins, seg_begin, seg_end, maxlam
-    uint32_t* c_parent = carve<uint32_t>(p, slots);
-    uint32_t* c_birth = carve<uint32_t>(p, slots);
-    uint32_t* c_size = carve<uint32_t>(p, slots);
-    uint32_t* child_lo = carve<uint32_t>(p, slots);
-    uint32_t* zeroed = reinterpret_cast<uint32_t*>(p);
-    uint32_t* child_hi = carve<uint32_t>(p, slots);
-    uint32_t* arrive = carve<uint32_t>(p, slots);
-    uint32_t* wins = carve<uint32_t>(p, slots);
-    uint32_t* seg_begin = carve<uint32_t>(p, slots);
-    uint32_t* seg_end = carve<uint32_t>(p, slots);
-    unsigned long long* maxlam = carve<unsigned long long>(p, slots);
-    const uint64_t zeroed_bytes = (uint64_t)(p - reinterpret_cast<unsigned char*>(zeroed));
-    unsigned long long* s_of = carve<unsigned long long>(p, slots);
-    double* stability = carve<double>(p, slots);
-    uint64_t* state_a = carve<uint64_t>(p, slots);
-    uint64_t* state_b = carve<uint64_t>(p, slots);
-    uint32_t* selflag = carve<uint32_t>(p, slots + 1);
-    uint32_t* label_of = carve<uint32_t>(p, slots + 1);
-    uint8_t* selected = carve<uint8_t>(p, slots);
-    if ((uint64_t)(p - static_cast<unsigned char*>(mem.p)) != bytes) {  // (before anything is written)
-        err = std::string(what) + ": scratch layout";
-        return ERR_FORMAT;
-    }
+    // per node, per vertex, per row (twice: the sort's two sides), per cluster
+    uint32_t *words, *par, *uf, *mark, *headflag, *hscan, *point_cluster, *point_w, *key_in, *key_out;
+    int32_t* labels;
+    float* prob;
+    double *term_in, *term_out, *stability;
+    uint32_t *c_parent, *c_birth, *c_size, *child_lo, *child_hi, *arrive, *wins, *seg_begin, *seg_end, *selflag, *label_of;
+    unsigned long long *maxlam, *s_of;
+    uint64_t *state_a, *state_b;
+    uint8_t* selected;
+    ScratchLayout lay;
+    lay.array(words, 64);
+    lay.arrays(nodes, par, uf, mark);
+    lay.arrays(nodes + 1, headflag, hscan);
+    lay.arrays(n, point_cluster, point_w, labels, prob);
+    lay.arrays(rows_max, key_in, key_out, term_in, term_out);
+    lay.arrays(slots, c_parent, c_birth, c_size, child_lo);
+    // those that are 0 before their kernels stand together, from child_hi on
+    const uint64_t zeroed_from = lay.size();
+    lay.arrays(slots, child_hi, arrive, wins, seg_begin, seg_end, maxlam);
+    const uint64_t zeroed_bytes = lay.size() - zeroed_from;
+    lay.arrays(slots, s_of, stability, state_a, state_b);
+    lay.arrays(slots + 1, selflag, label_of);
+    lay.array(selected, slots);
+    int rc = alloc_layout(what, mem, lay, err);  // (before anything is written)
+    if (rc != OK) return rc;
+    uint32_t* zeroed = child_hi;
 
     HIP_TRY(hipMemsetAsync(words, 0, 256, stream));
     HIP_TRY(hipMemsetAsync(par, 0xFF, nodes * 4, stream));
@@ -439,7 +403,7 @@ int clusters_of_dendrogram(const char* what, uint64_t n, uint64_t m, const float
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(cc_compress_kernel, grid_of(nodes), dim3(256), 0, stream, uf, nodes32, mark);
     HIP_TRY(hipGetLastError());
-    int rc = scan_u32(headflag, hscan, nodes + 1, stream, err);
+    rc = scan_u32(headflag, hscan, nodes + 1, stream, err);
     if (rc != OK) return rc;
     uint32_t descent = 0, heads = 0;
     HIP_TRY(hipMemcpyAsync(&descent, words + W_DESCENT, 4, hipMemcpyDeviceToHost, stream));
@@ -464,11 +428,9 @@ int clusters_of_dendrogram(const char* what, uint64_t n, uint64_t m, const float
     {
         uint32_t end_bit = 1;
         while (end_bit < 32 && (1ull << end_bit) < clusters) ++end_bit;
-        size_t temp_bytes = 0;
         DevMem temp;
-        HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, key_in, key_out, term_in, term_out, (size_t)rows, 0u, end_bit, stream));
-        HIP_TRY(temp.alloc(std::max<size_t>(temp_bytes, 256)));
-        HIP_TRY(rocprim::radix_sort_pairs(temp.p, temp_bytes, key_in, key_out, term_in, term_out, (size_t)rows, 0u, end_bit, stream));
+        rc = radix_sort_pairs(temp, key_in, key_out, term_in, term_out, (size_t)rows, end_bit, stream, err);
+        if (rc != OK) return rc;
         HIP_TRY(hipStreamSynchronize(stream));
     }
     hipLaunchKernelGGL(hd_segment_kernel, grid_of(rows), dim3(256), 0, stream, key_out, (uint32_t)rows, k32, seg_begin, seg_end);
@@ -516,36 +478,34 @@ int clusters_of_dendrogram(const char* what, uint64_t n, uint64_t m, const float
 // host: every array is host memory, and the ends and weights have passed the same checks on the host.  Waits for `stream`.
 int forest_hdbscan(const ForestHdbscanArgs& a, bool host, void* stream_v, std::string& err) {
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || a.device < 0 || a.device >= count) {
-        (void)hipGetLastError();
-        err = "forest hdbscan: no device " + std::to_string(a.device);
-        return ERR_DEVICE;
-    }
+    int rc = use_device_ordinal("forest hdbscan", a.device, err);
+    if (rc != OK) return rc;
     DeviceGuard on(a.device);
     HIP_TRY(on.status());
-    const uint64_t bm = round_up(a.m * 4, 256);
     DevMem mem;
     Drain drain{stream};
     const uint32_t *d_a = a.a, *d_b = a.b;
     const float* d_w = a.w;
     uint32_t *left = nullptr, *right = nullptr, *size = nullptr;
     if (a.m != 0) {
-        HIP_TRY(mem.alloc((host ? 6 : 3) * bm));
-        left = static_cast<uint32_t*>(mem.p);
-        right = left + bm / 4;
-        size = right + bm / 4;
+        // the dendrogram; behind it, for the host form, the forest
+        uint32_t *up_a = nullptr, *up_b = nullptr;
+        float* up_w = nullptr;
+        ScratchLayout lay;
+        lay.arrays(a.m, left, right, size);
+        if (host) lay.arrays(a.m, up_a, up_b, up_w);
+        rc = alloc_layout("forest hdbscan", mem, lay, err);
+        if (rc != OK) return rc;
         if (host) {
-            uint32_t* up = size + bm / 4;
-            HIP_TRY(hipMemcpyAsync(up, a.a, a.m * 4, hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(up + bm / 4, a.b, a.m * 4, hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(up + 2 * (bm / 4), a.w, a.m * 4, hipMemcpyHostToDevice, stream));
-            d_a = up;
-            d_b = up + bm / 4;
-            d_w = reinterpret_cast<const float*>(up + 2 * (bm / 4));
+            HIP_TRY(hipMemcpyAsync(up_a, a.a, a.m * 4, hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(up_b, a.b, a.m * 4, hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(up_w, a.w, a.m * 4, hipMemcpyHostToDevice, stream));
+            d_a = up_a;
+            d_b = up_b;
+            d_w = up_w;
         }
         const DendrogramArgs d{a.device, a.n, a.m, d_a, d_b, left, right, size};
-        const int rc = forest_dendrogram(d, false, stream_v, err);  // a bad end, a self-loop, a cycle: its refusals, in its words
+        rc = forest_dendrogram(d, false, stream_v, err);  // a bad end, a self-loop, a cycle: its refusals, in its words
         if (rc != OK) return rc;
     }
     return clusters_of_dendrogram("forest hdbscan", a.n, a.m, d_w, left, right, size, a.min_cluster_size, a.method, a.out, host, stream, err);
@@ -562,13 +522,15 @@ int graph_hdbscan(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, cons
         err = "graph hdbscan: " + std::to_string(n) + " points, above 2^31 - 1";
         return ERR_ARG;
     }
-    const uint64_t slots = round_up((std::max<uint64_t>(n, 2) - 1) * 4, 256);
+    const uint64_t most = std::max<uint64_t>(n, 2) - 1;  // the edges of a forest at most
     DevMem mem;
     Drain drain{stream};
-    HIP_TRY(mem.alloc(6 * slots));
-    uint32_t* base = static_cast<uint32_t*>(mem.p);
-    uint32_t *f_a = base, *f_b = base + slots / 4, *left = base + 3 * (slots / 4), *right = base + 4 * (slots / 4), *size = base + 5 * (slots / 4);
-    float* f_w = reinterpret_cast<float*>(base + 2 * (slots / 4));
+    uint32_t *f_a, *f_b, *left, *right, *size;
+    float* f_w;
+    ScratchLayout lay;
+    lay.arrays(most, f_a, f_b, f_w, left, right, size);
+    int rc = alloc_layout("graph hdbscan", mem, lay, err);
+    if (rc != OK) return rc;
     uint64_t edges = 0;
     if (n >= 2) {
         GraphDendrogramArgs g{a.forest, left, right, size};
@@ -576,10 +538,10 @@ int graph_hdbscan(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, cons
         g.forest.out_b = f_b;
         g.forest.out_w = f_w;
         g.forest.out_n = &edges;
-        const int rc = graph_dendrogram(dev, origin_id, g, false, stream_v, err);
+        rc = graph_dendrogram(dev, origin_id, g, false, stream_v, err);
         if (rc != OK) return rc;
     }
-    const int rc = clusters_of_dendrogram("graph hdbscan", n, edges, f_w, left, right, size, a.min_cluster_size, a.method, a.out, host, stream, err);
+    rc = clusters_of_dendrogram("graph hdbscan", n, edges, f_w, left, right, size, a.min_cluster_size, a.method, a.out, host, stream, err);
     if (rc != OK) return rc == ERR_ARG ? ERR_FORMAT : rc;  // (a forest of this library's own: an internal error)
     const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     const struct { void* to; const void* from; } copies[] = {{a.forest.out_a, f_a}, {a.forest.out_b, f_b}, {a.forest.out_w, f_w},

@@ -210,13 +210,6 @@ __global__ __launch_bounds__(256) void dn_size_kernel(uint32_t* __restrict__ la,
     lb[e] = labels - 1u - y;
 }
 
-dim3 grid_of(uint64_t threads) { return dim3((uint32_t)((threads + 255) / 256)); }
-
-struct Drain {
-    hipStream_t s;
-    ~Drain() { (void)hipStreamSynchronize(s); }
-};
-
 // ceil(log2 m): the levels of m >= 1 edges
 uint32_t level_count(uint64_t m) {
     uint32_t bits = 0;
@@ -229,19 +222,16 @@ uint32_t level_count(uint64_t m) {
 int dendrogram_of_edges(uint64_t n, uint64_t m, const uint32_t* a, const uint32_t* b, bool host_in, bool host_out, uint32_t* out_left,
                         uint32_t* out_right, uint32_t* out_size, hipStream_t stream, std::string& err) {
     const uint64_t labels = n + m;  // below 2^32
-    const uint64_t bm = round_up(m * 4, 256), bl = round_up(labels * 4, 256);
     DevMem mem;
     Drain drain{stream};
     // la, lb (m words each), parent, top, wsum, w (n + m words each), the word
-    HIP_TRY(mem.alloc(2 * bm + 4 * bl + 256));
-    unsigned char* p = static_cast<unsigned char*>(mem.p);
-    uint32_t* la = reinterpret_cast<uint32_t*>(p); p += bm;
-    uint32_t* lb = reinterpret_cast<uint32_t*>(p); p += bm;
-    uint32_t* parent = reinterpret_cast<uint32_t*>(p); p += bl;
-    uint32_t* top = reinterpret_cast<uint32_t*>(p); p += bl;
-    uint32_t* wsum = reinterpret_cast<uint32_t*>(p); p += bl;
-    uint32_t* w = reinterpret_cast<uint32_t*>(p); p += bl;
-    uint32_t* d_word = reinterpret_cast<uint32_t*>(p);
+    uint32_t *la, *lb, *parent, *top, *wsum, *w, *d_word;
+    ScratchLayout lay;
+    lay.arrays(m, la, lb);
+    lay.arrays(labels, parent, top, wsum, w);
+    lay.array(d_word, 64);
+    const int rc = alloc_layout("forest dendrogram", mem, lay, err);
+    if (rc != OK) return rc;
     uint32_t* size = top;  // (free once the last level is done; m <= n + m words)
     const uint32_t n32 = (uint32_t)n, m32 = (uint32_t)m, l32 = (uint32_t)labels;
 
@@ -297,12 +287,8 @@ int dendrogram_of_edges(uint64_t n, uint64_t m, const uint32_t* a, const uint32_
 // memory, and the ends have passed the same checks on the host.  Waits for `stream` before it returns.
 int forest_dendrogram(const DendrogramArgs& a, bool host, void* stream_v, std::string& err) {
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || a.device < 0 || a.device >= count) {
-        (void)hipGetLastError();
-        err = "forest dendrogram: no device " + std::to_string(a.device);
-        return ERR_DEVICE;
-    }
+    const int rc = use_device_ordinal("forest dendrogram", a.device, err);
+    if (rc != OK) return rc;
     DeviceGuard on(a.device);
     HIP_TRY(on.status());
     return dendrogram_of_edges(a.n, a.m, a.a, a.b, host, host, a.out_left, a.out_right, a.out_size, stream, err);
@@ -314,19 +300,20 @@ int graph_dendrogram(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, c
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     DeviceGuard on(dev.device());
     HIP_TRY(on.status());
-    const uint64_t n = dev.view().n, slots = round_up((n - 1) * 4, 256);
+    const uint64_t n = dev.view().n;
     DevMem m_forest;
     Drain drain{stream};
     ForestArgs f = a.forest;
     uint64_t edges = 0;
     f.out_n = &edges;
+    int rc = OK;
     if (host) {
-        HIP_TRY(m_forest.alloc(3 * slots));
-        f.out_a = static_cast<uint32_t*>(m_forest.p);
-        f.out_b = f.out_a + slots / 4;
-        f.out_w = reinterpret_cast<float*>(f.out_b + slots / 4);
+        ScratchLayout lay;
+        lay.arrays(n - 1, f.out_a, f.out_b, f.out_w);
+        rc = alloc_layout("graph dendrogram", m_forest, lay, err);
+        if (rc != OK) return rc;
     }
-    int rc = graph_spanning_forest(dev, origin_id, f, false, stream_v, err);
+    rc = graph_spanning_forest(dev, origin_id, f, false, stream_v, err);
     if (rc != OK) return rc;
     if (edges != 0) {
         if (edges > n - 1) {

@@ -446,6 +446,13 @@ struct ScratchLease {
         st->pool.emplace_back(p, bytes);
     }
 };
+// a call's block from the pool, sized by the arrays that `lay` names and divided among them
+int take_layout(const char* what, ScratchLease& lease, ScratchLayout& lay, std::string& err) {
+    HIP_TRY(lease.take(lay.size()));
+    if (lay.place(lease.p, lease.bytes)) return OK;
+    err = std::string(what) + ": scratch layout";
+    return ERR_FORMAT;
+}
 
 // rank[f] = position of flat id f in ascending (origin id, flat id) order, and the inverse: once per replica, on the host
 std::shared_ptr<void> make_state(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, std::string& err) {
@@ -531,25 +538,32 @@ int exact_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id,
     const uint64_t chunk_tiles = std::min<uint64_t>({tiles_total, (SCRATCH_BUDGET - allow_bytes) / per_tile, 65535});
     if (chunk_tiles == 0) { err = "knbn too large for the exact search's scratch budget"; return ERR_ARG; }
 
+    // (a per-tile array: every tile's part padded, tile behind tile)
+    uint32_t *d_allow, *d_ctrl, *d_qlist, *d_slot_of, *d_lens, *d_tword = nullptr, *d_self_rank = nullptr;
+    float* d_qt;
+    double* d_qnorm;
+    uint64_t* d_lists;
+    ScratchLayout lay;
+    lay.array(d_allow, per_group * words);
+    lay.bytes(d_ctrl, ctrl_bytes);  // [0] entries of filter_of that name no filter, [1] queries of the group
+    lay.bytes(d_qlist, qlist_bytes);
+    lay.bytes(d_slot_of, qlist_bytes);
+    lay.bytes(d_qt, chunk_tiles * round_up(nchunk * TQ * 16, 256));
+    lay.bytes(d_qnorm, chunk_tiles * round_up(TQ * 8, 256));
+    lay.bytes(d_lists, chunk_tiles * round_up(slabs * TQ * cap * 8, 256));
+    lay.bytes(d_lens, chunk_tiles * round_up(slabs * TQ * 4, 256));
+    if (set) lay.bytes(d_tword, chunk_tiles * tword_bytes);
+    if (d_self) lay.bytes(d_self_rank, chunk_tiles * self_bytes);
+    if (lay.size() != allow_bytes + chunk_tiles * per_tile) {  // (what the budget above counted: before anything is taken)
+        err = "exact search: scratch layout";
+        return ERR_FORMAT;
+    }
     ScratchLease lease(st);
-    HIP_TRY(lease.take(allow_bytes + chunk_tiles * per_tile));
-    unsigned char* p = static_cast<unsigned char*>(lease.p);
-    uint32_t* d_allow = reinterpret_cast<uint32_t*>(p); p += round_up(per_group * slot_bytes, 256);
-    uint32_t* d_ctrl = reinterpret_cast<uint32_t*>(p); p += ctrl_bytes;  // [0] entries of filter_of that name no filter, [1] queries of the group
-    uint32_t* d_qlist = reinterpret_cast<uint32_t*>(p); p += qlist_bytes;
-    uint32_t* d_slot_of = reinterpret_cast<uint32_t*>(p); p += qlist_bytes;
-    float* d_qt = reinterpret_cast<float*>(p); p += chunk_tiles * round_up(nchunk * TQ * 16, 256);
-    double* d_qnorm = reinterpret_cast<double*>(p); p += chunk_tiles * round_up(TQ * 8, 256);
-    uint64_t* d_lists = reinterpret_cast<uint64_t*>(p); p += chunk_tiles * round_up(slabs * TQ * cap * 8, 256);
-    uint32_t* d_lens = reinterpret_cast<uint32_t*>(p); p += chunk_tiles * round_up(slabs * TQ * 4, 256);
-    uint32_t* d_tword = set ? reinterpret_cast<uint32_t*>(p) : nullptr; p += chunk_tiles * tword_bytes;
-    uint32_t* d_self_rank = d_self ? reinterpret_cast<uint32_t*>(p) : nullptr;
+    const int rc_lease = take_layout("exact search", lease, lay, err);
+    if (rc_lease != OK) return rc_lease;
 
     // whatever happens, nothing of this call is still running when the scratch block goes back to the pool
-    struct Drain {
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    } drain{stream};
+    Drain drain{stream};
 
     // `count` queries in chunks of whole tiles: slot i of the tiles is query qlist[i] (nullptr: query i) of the batch, searched
     // under the bitmap slot_of[that query] of the group (filter set only)
@@ -902,7 +916,6 @@ int exact_range(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, 
     // query's base is its offset, the counters are a chunk's
     const bool keep = slabs > 1;
     const uint64_t words = (n + 31) / 32;
-    const uint64_t allow_bytes = io.filtered ? round_up(words * 4, 256) : 0;
     const uint64_t tile_bytes = round_up(nchunk * TQ * 16, 256) + round_up(TQ * 8, 256);
     const uint64_t per_tile = tile_bytes + (keep ? 0 : TQ * 4);
     const uint64_t block_q = io.host ? std::max<uint64_t>(1, std::min<uint64_t>(nq, (64ull << 20) / (d * 4 + 12))) : nq;
@@ -918,23 +931,27 @@ int exact_range(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, 
     size_t temp_bytes = 0;
     if (key_cap != 0)
         HIP_TRY(sort_segments(nullptr, temp_bytes, nullptr, nullptr, (uint32_t)key_cap, (uint32_t)max_fill_q, nullptr, 0, stream));
-    const uint64_t keys_bytes = round_up(key_cap * 8, 256);
-    const uint64_t stage_bytes = io.host ? round_up(key_cap * 8, 256) + 2 * round_up(key_cap * 4, 256) + round_up(key_cap, 256) : 0;
 
+    // (d_qt, d_qnorm: every tile's part padded, tile behind tile; the s_ arrays: the staging of a host call)
+    uint32_t *d_allow = nullptr, *d_cnt;
+    float *d_qt, *s_dists = nullptr;
+    double* d_qnorm;
+    uint64_t *d_keys_a, *d_keys_b, *s_ids = nullptr;
+    void* d_temp;
+    int32_t* s_rank = nullptr;
+    uint8_t* s_layer = nullptr;
+    ScratchLayout lay;
+    if (io.filtered) lay.array(d_allow, words);
+    lay.bytes(d_qt, chunk_tiles * round_up(nchunk * TQ * 16, 256));
+    lay.bytes(d_qnorm, chunk_tiles * round_up(TQ * 8, 256));
+    lay.bytes(d_cnt, cnt_bytes);
+    lay.arrays(key_cap, d_keys_a, d_keys_b);
+    lay.bytes(d_temp, round_up(temp_bytes, 256));
+    if (io.host) lay.arrays(key_cap, s_ids, s_dists, s_rank, s_layer);
+    lay.skip(256);
     ScratchLease lease(st);
-    HIP_TRY(lease.take(allow_bytes + chunk_tiles * tile_bytes + cnt_bytes + 2 * keys_bytes + round_up(temp_bytes, 256) + stage_bytes + 256));
-    unsigned char* p = static_cast<unsigned char*>(lease.p);
-    uint32_t* d_allow = io.filtered ? reinterpret_cast<uint32_t*>(p) : nullptr; p += allow_bytes;
-    float* d_qt = reinterpret_cast<float*>(p); p += chunk_tiles * round_up(nchunk * TQ * 16, 256);
-    double* d_qnorm = reinterpret_cast<double*>(p); p += chunk_tiles * round_up(TQ * 8, 256);
-    uint32_t* d_cnt = reinterpret_cast<uint32_t*>(p); p += cnt_bytes;
-    uint64_t* d_keys_a = reinterpret_cast<uint64_t*>(p); p += keys_bytes;
-    uint64_t* d_keys_b = reinterpret_cast<uint64_t*>(p); p += keys_bytes;
-    void* d_temp = p; p += round_up(temp_bytes, 256);
-    uint64_t* s_ids = reinterpret_cast<uint64_t*>(p); p += io.host ? round_up(key_cap * 8, 256) : 0;
-    float* s_dists = reinterpret_cast<float*>(p); p += io.host ? round_up(key_cap * 4, 256) : 0;
-    int32_t* s_rank = reinterpret_cast<int32_t*>(p); p += io.host ? round_up(key_cap * 4, 256) : 0;
-    uint8_t* s_layer = p;
+    const int rc_lease = take_layout("exact range search", lease, lay, err);
+    if (rc_lease != OK) return rc_lease;
 
     DevMem m_q, m_rad, m_off;
     if (io.host) {
@@ -948,10 +965,7 @@ int exact_range(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, 
     uint64_t* const h_off = io.host ? io.offsets : off_copy.data();
     h_off[0] = 0;
 
-    struct Drain {
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    } drain{stream};
+    Drain drain{stream};
 
     if (io.filtered) HIP_TRY(launch_allow_bitmap(stream, v.origin_id, v.n, io.d_allowed, io.n_allowed, d_allow));
     ExactRangeArgs a{};
@@ -1179,15 +1193,13 @@ struct AnswerStage {
     DevMem mem;
     GraphRows rows{};
     hipError_t alloc(uint64_t chunk, uint64_t k) {
-        const hipError_t e = mem.alloc(round_up(chunk * k * 8, 256) + 2 * round_up(chunk * k * 4, 256) + round_up(chunk * 4, 256) + round_up(chunk * k, 256));
+        ScratchLayout lay;
+        lay.arrays(chunk * k, rows.ids, rows.dists, rows.rank);
+        lay.array(rows.counts, chunk);
+        lay.array(rows.layer, chunk * k);
+        const hipError_t e = mem.alloc(lay.size());
         if (e != hipSuccess) { mem.p = nullptr; return e; }
-        unsigned char* p = static_cast<unsigned char*>(mem.p);
-        rows.ids = reinterpret_cast<uint64_t*>(p); p += round_up(chunk * k * 8, 256);
-        rows.dists = reinterpret_cast<float*>(p); p += round_up(chunk * k * 4, 256);
-        rows.rank = reinterpret_cast<int32_t*>(p); p += round_up(chunk * k * 4, 256);
-        rows.counts = reinterpret_cast<uint32_t*>(p); p += round_up(chunk * 4, 256);
-        rows.layer = p;
-        return hipSuccess;
+        return lay.place(mem.p, lay.size()) ? hipSuccess : hipErrorInvalidValue;
     }
     hipError_t copy_out(const GraphRows& dst, uint64_t cq, uint64_t k, hipStream_t stream) const {  // (dst.layer, dst.rank may be nullptr)
         hipError_t e = hipMemcpyAsync(dst.ids, rows.ids, cq * k * 8, hipMemcpyDeviceToHost, stream);
@@ -1315,10 +1327,6 @@ int graph_search(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, bool 
     if (!ext) { err = serr.empty() ? "graph search: no device state" : serr; return ERR_DEVICE; }
     const ExactState* st = static_cast<const ExactState*>(ext.get());
     const GraphCall io{host, point_ids, np, k, {out_ids, out_dists, out_layer, out_rank, out_counts}};
-    struct Drain {
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    };
     DevMem m_flat, m_q;
     AnswerStage wide, stage;  // the search's (k + 1)-wide answers; a host call's k-wide ones
     Drain drain{stream};  // (destroyed first: nothing of this call is running when its memory is freed)

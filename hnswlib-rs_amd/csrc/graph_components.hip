@@ -22,15 +22,15 @@
 // the smallest vertex of its tree.  Once the hooks are done the trees are the components whatever the timing was: the answer is a
 // function of the graph alone.  No wavefront waits on another; no kernel walks a row.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
 
-#include <algorithm>
 #include <string>
 
 #include "capi_index.hpp"
+#include "csr_intake.hpp"
 #include "graph_internal.hpp"
 #include "hip_host.hpp"
 #include "hnswio.hpp"
+#include "rocprim_host.hpp"
 #include "union_find.hpp"
 
 namespace hnswgpu {
@@ -111,13 +111,6 @@ __global__ __launch_bounds__(256) void cc_label_kernel(const uint32_t* __restric
     }
 }
 
-dim3 grid_of(uint64_t threads) { return dim3((uint32_t)((threads + 255) / 256)); }
-
-struct Drain {
-    hipStream_t s;
-    ~Drain() { (void)hipStreamSynchronize(s); }
-};
-
 // what every form keeps for the length of a call: parent, mark and the scan of the marks (4 n, 4 n + 4, 4 n + 4 bytes)
 struct Forest {
     DevMem mem;
@@ -126,11 +119,10 @@ struct Forest {
     uint32_t* number_of = nullptr;
 };
 int forest_init(Forest& f, uint64_t n, hipStream_t stream, std::string& err) {
-    HIP_TRY(f.mem.alloc(3 * round_up((n + 1) * 4, 256)));
-    unsigned char* p = static_cast<unsigned char*>(f.mem.p);
-    f.parent = reinterpret_cast<uint32_t*>(p); p += round_up((n + 1) * 4, 256);
-    f.mark = reinterpret_cast<uint32_t*>(p); p += round_up((n + 1) * 4, 256);
-    f.number_of = reinterpret_cast<uint32_t*>(p);
+    ScratchLayout lay;
+    lay.arrays(n + 1, f.parent, f.mark, f.number_of);
+    const int rc = alloc_layout("components", f.mem, lay, err);
+    if (rc != OK) return rc;
     hipLaunchKernelGGL(cc_init_kernel, grid_of(n), dim3(256), 0, stream, f.parent, (uint32_t)n);
     HIP_TRY(hipGetLastError());
     return OK;
@@ -142,10 +134,8 @@ int forest_answer(Forest& f, uint64_t n, bool host, uint32_t* out_label, uint32_
     HIP_TRY(hipMemsetAsync(f.mark + n, 0, 4, stream));
     hipLaunchKernelGGL(cc_compress_kernel, grid_of(n), dim3(256), 0, stream, f.parent, (uint32_t)n, f.mark);
     HIP_TRY(hipGetLastError());
-    size_t temp_bytes = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, f.mark, f.number_of, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), stream));
-    HIP_TRY(m_temp.alloc(std::max<size_t>(temp_bytes, 256)));
-    HIP_TRY(rocprim::exclusive_scan(m_temp.p, temp_bytes, f.mark, f.number_of, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), stream));
+    int rc = exclusive_scan_u32(m_temp, f.mark, f.number_of, n + 1, stream, err);
+    if (rc != OK) return rc;
     uint32_t c = 0;
     HIP_TRY(hipMemcpyAsync(&c, f.number_of + n, 4, hipMemcpyDeviceToHost, stream));  // the read-back of the device entries
     HIP_TRY(hipStreamSynchronize(stream));
@@ -156,9 +146,12 @@ int forest_answer(Forest& f, uint64_t n, bool host, uint32_t* out_label, uint32_
     uint32_t* d_label = out_label;
     uint32_t* d_sizes = out_sizes;
     if (host) {
-        HIP_TRY(m_out.alloc(round_up(n * 4, 256) + (uint64_t)c * 4));
-        d_label = static_cast<uint32_t*>(m_out.p);
-        d_sizes = out_sizes ? d_label + round_up(n * 4, 256) / 4 : nullptr;
+        ScratchLayout lay;
+        lay.array(d_label, n);
+        lay.bytes(d_sizes, (uint64_t)c * 4);  // (the block ends with the c words)
+        rc = alloc_layout("components", m_out, lay, err);
+        if (rc != OK) return rc;
+        if (!out_sizes) d_sizes = nullptr;
     }
     if (d_sizes) HIP_TRY(hipMemsetAsync(d_sizes, 0, (uint64_t)c * 4, stream));
     hipLaunchKernelGGL(cc_label_kernel, grid_of(n), dim3(256), 0, stream, f.parent, f.number_of, (uint32_t)n, d_label, d_sizes);
@@ -213,57 +206,21 @@ int graph_components(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, c
 // Both CSR entries: 1 <= n < 2^31.  host: every array is host memory and has passed the same checks on the host (capi.cpp).
 int csr_components(const CsrComponentsArgs& a, bool host, void* stream_v, std::string& err) {
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || a.device < 0 || a.device >= count) {
-        (void)hipGetLastError();
-        err = "csr components: no device " + std::to_string(a.device);
-        return ERR_DEVICE;
-    }
+    int rc = use_device_ordinal("csr components", a.device, err);
+    if (rc != OK) return rc;
     DeviceGuard on(a.device);
     HIP_TRY(on.status());
     const uint64_t n = a.n;
-    DevMem m_in, m_word;
+    CsrOnDevice csr;
     Forest f;
     Drain drain{stream};
-    const uint64_t* d_offsets = a.offsets;
-    const uint32_t* d_cols = a.cols;
-    const float* d_dists = a.dists;
-    if (host) {
-        const uint64_t total = a.offsets[n];
-        const uint64_t b_offs = round_up((n + 1) * 8, 256), b_cols = round_up(total * 4, 256);
-        HIP_TRY(m_in.alloc(b_offs + b_cols * (a.has_cut ? 2 : 1) + 256));
-        unsigned char* p = static_cast<unsigned char*>(m_in.p);
-        HIP_TRY(hipMemcpyAsync(p, a.offsets, (n + 1) * 8, hipMemcpyHostToDevice, stream));
-        d_offsets = reinterpret_cast<const uint64_t*>(p); p += b_offs;
-        if (total != 0) HIP_TRY(hipMemcpyAsync(p, a.cols, total * 4, hipMemcpyHostToDevice, stream));
-        d_cols = reinterpret_cast<const uint32_t*>(p); p += b_cols;
-        if (a.has_cut && total != 0) HIP_TRY(hipMemcpyAsync(p, a.dists, total * 4, hipMemcpyHostToDevice, stream));
-        d_dists = reinterpret_cast<const float*>(p);
-    }
-    // the checks, and the one word that says how they went
-    HIP_TRY(m_word.alloc(256));
-    unsigned long long* d_word = static_cast<unsigned long long*>(m_word.p);
-    HIP_TRY(hipMemsetAsync(d_word, 0, 8, stream));
-    hipLaunchKernelGGL(cc_check_offsets_kernel, grid_of(n + 1), dim3(256), 0, stream, d_offsets, (uint32_t)n, d_word);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(cc_check_cols_kernel, dim3(CHECK_BLOCKS), dim3(256), 0, stream, d_offsets, d_cols, (uint32_t)n, d_word);
-    HIP_TRY(hipGetLastError());
-    unsigned long long word = 0;
-    HIP_TRY(hipMemcpyAsync(&word, d_word, 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if ((word >> 32) != 0ull) {
-        err = std::string("csr components: ") + ((word & BAD_FIRST)     ? "offsets[0] is not 0"
-                                                 : (word & BAD_DESCENT) ? "the offsets descend"
-                                                 : (word & BAD_TOTAL)   ? "offsets[n] is 2^32 or more"
-                                                 : (word & BAD_NO_COLS) ? "null cols with entries"
-                                                                        : "a col is not below n");
-        return ERR_ARG;
-    }
-    const uint64_t total = word & 0xFFFFFFFFull;
-    int rc = forest_init(f, n, stream, err);
+    rc = csr_intake("csr components", n, a.offsets, a.cols, a.dists, host, a.has_cut, stream, csr, err);
+    if (rc != OK) return rc;
+    const uint64_t total = csr.total;
+    rc = forest_init(f, n, stream, err);
     if (rc != OK) return rc;
     if (total != 0) {
-        hipLaunchKernelGGL(cc_hook_csr_kernel, grid_of(total), dim3(256), 0, stream, d_offsets, d_cols, d_dists, (uint32_t)n, (uint32_t)total,
+        hipLaunchKernelGGL(cc_hook_csr_kernel, grid_of(total), dim3(256), 0, stream, csr.offsets, csr.cols, csr.dists, (uint32_t)n, (uint32_t)total,
                            a.has_cut ? 1u : 0u, a.max_dist, f.parent);
         HIP_TRY(hipGetLastError());
     }

@@ -1,6 +1,7 @@
-// hip_host.hpp -- the HIP host helpers of the five host units (search_device.hip, exact_knn.hip, range_search.hip,
-// symmetric_graph.hip, graph_components.hip), once.  Needs the HIP runtime: nothing that a host-only build compiles (capi.cpp, the builder, the stand-ins
-// of tests/cpp) may include it, and the kernel units do not see it.  Private: not installed, not part of the ABI.
+// hip_host.hpp -- the HIP host helpers of every host unit (the .hip files other than search_kernels_tu.hip), once: error handling,
+// the device guard, call-scoped device memory and its layout, the grid of a one-thread-per-item launch, the wait that ends a call.
+// Needs the HIP runtime: nothing that a host-only build compiles (capi.cpp, the builder, the stand-ins of tests/cpp) may include
+// it, and the kernel units do not see it.  Private: not installed, not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +10,7 @@
 #include <string>
 
 #include "hnswio.hpp"  // ERR_DEVICE
+#include "scratch_layout.hpp"
 #include "search_device.hpp"  // knobs()
 
 // inside a function that returns a status code and has a `std::string& err` in scope
@@ -92,6 +94,37 @@ struct DevMem {
     void release() { if (p) (void)hipFree(p); p = nullptr; }
 };
 
-inline uint64_t round_up(uint64_t x, uint64_t m) { return (x + m - 1) / m * m; }
+// A call's block, sized by the arrays that `lay` names and divided among them (scratch_layout.hpp).  Nothing is written before the
+// layout is known to fit.
+inline int alloc_layout(const char* what, DevMem& mem, ScratchLayout& lay, std::string& err) {
+    const uint64_t bytes = lay.size();
+    HIP_TRY(mem.alloc(bytes));
+    if (!lay.place(mem.p, bytes)) {
+        err = std::string(what) + ": scratch layout";
+        return ERR_FORMAT;
+    }
+    return OK;
+}
+
+// one thread per item, 256 to a block
+inline dim3 grid_of(uint64_t threads) { return dim3((uint32_t)((threads + 255) / 256)); }
+
+// Declared behind a call's device memory, so destroyed first: whatever happens, nothing of the call is running when its memory is
+// freed or goes back to a pool.
+struct Drain {
+    hipStream_t s;
+    ~Drain() { (void)hipStreamSynchronize(s); }
+};
+
+// The entries that take a device ordinal instead of a replica: OK, or ERR_DEVICE and "<what>: no device <N>"
+inline int use_device_ordinal(const char* what, int device, std::string& err) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) {
+        (void)hipGetLastError();
+        err = std::string(what) + ": no device " + std::to_string(device);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
 
 }  // namespace hnswgpu

@@ -39,16 +39,22 @@ struct RangeSlots {
     uint8_t* layer;
 };
 // `slots` entries behind one another in one block: ids, distances, ranks, layers
-RangeSlots carve_slots(void* base, uint64_t slots) {
-    unsigned char* p = static_cast<unsigned char*>(base);
+ScratchLayout slots_layout(RangeSlots& s, uint64_t slots) {
+    ScratchLayout lay;
+    lay.arrays(slots, s.ids, s.dists, s.rank, s.layer);
+    return lay;
+}
+uint64_t slots_bytes(uint64_t slots) {
     RangeSlots s{};
-    s.ids = reinterpret_cast<uint64_t*>(p); p += round_up(slots * 8, 256);
-    s.dists = reinterpret_cast<float*>(p); p += round_up(slots * 4, 256);
-    s.rank = reinterpret_cast<int32_t*>(p); p += round_up(slots * 4, 256);
-    s.layer = p;
+    return slots_layout(s, slots).size();
+}
+// over a block of slots_bytes(at least `slots`): the layout only grows with the slots, so it fits
+RangeSlots carve_slots(void* base, uint64_t slots) {
+    RangeSlots s{};
+    ScratchLayout lay = slots_layout(s, slots);
+    (void)lay.place(base, lay.size());
     return s;
 }
-uint64_t slots_bytes(uint64_t slots) { return round_up(slots * 8, 256) + 2 * round_up(slots * 4, 256) + round_up(slots, 256); }
 
 enum : uint32_t { CTRL_PENDING = 0, CTRL_HELD = 1, CTRL_WORDS = 2 };  // words of the group's control block
 
@@ -176,10 +182,6 @@ int range_search(DeviceIndex& dev, const RangeSearchArgs& a, bool host, hipStrea
     const uint64_t nq = a.nq, d = a.d;
     DeviceGuard on(dev.device());
     HIP_TRY(on.status());
-    struct Drain {
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    };
     DevMem m_small, m_staged, m_held;
     Drain drain{stream};  // (destroyed first: nothing of this call is running when its memory is freed)
 
@@ -187,23 +189,18 @@ int range_search(DeviceIndex& dev, const RangeSearchArgs& a, bool host, hipStrea
     const uint64_t slots = group * a.ef_max;  // of a round's staged answers and of the group's held answers at most
     const bool keep = a.out_ids != nullptr;   // (else the count-only call)
     // the group's small arrays, one block
-    const uint64_t qmat = round_up(group * d * 4, 256), w4 = round_up(group * 4, 256);
-    HIP_TRY(m_small.alloc((host ? 2 : 1) * qmat + 8 * w4 + round_up(group * 8, 256) + round_up(group, 256) + 256));
-    unsigned char* p = static_cast<unsigned char*>(m_small.p);
-    auto take = [&](uint64_t bytes) { unsigned char* r = p; p += bytes; return r; };
-    float* d_qround = reinterpret_cast<float*>(take(qmat));
-    float* d_qgroup = host ? reinterpret_cast<float*>(take(qmat)) : nullptr;
-    float* d_radii = reinterpret_cast<float*>(take(w4));  // (host calls)
-    uint32_t* d_pend[2] = {reinterpret_cast<uint32_t*>(take(w4)), nullptr};
-    d_pend[1] = reinterpret_cast<uint32_t*>(take(w4));
-    uint32_t* d_counts = reinterpret_cast<uint32_t*>(take(w4));
-    uint32_t* d_m = reinterpret_cast<uint32_t*>(take(w4));
-    uint32_t* d_hpos = reinterpret_cast<uint32_t*>(take(w4));
-    uint32_t* d_goff = reinterpret_cast<uint32_t*>(take(w4));
-    uint32_t* d_ef = reinterpret_cast<uint32_t*>(take(w4));   // (host calls)
-    uint64_t* d_offs = reinterpret_cast<uint64_t*>(take(round_up(group * 8, 256)));  // (host calls)
-    uint8_t* d_flags = take(round_up(group, 256));            // (host calls)
-    uint32_t* d_ctrl = reinterpret_cast<uint32_t*>(take(256));
+    float *d_qround, *d_qgroup = nullptr, *d_radii;
+    uint32_t *d_pend[2], *d_counts, *d_m, *d_hpos, *d_goff, *d_ef, *d_ctrl;
+    uint64_t* d_offs;
+    uint8_t* d_flags;
+    ScratchLayout lay;
+    lay.array(d_qround, group * d);
+    if (host) lay.array(d_qgroup, group * d);
+    // (d_radii, d_ef, d_offs, d_flags: host calls)
+    lay.arrays(group, d_radii, d_pend[0], d_pend[1], d_counts, d_m, d_hpos, d_goff, d_ef, d_offs, d_flags);
+    lay.array(d_ctrl, 64);
+    const int rc_small = alloc_layout("range search", m_small, lay, err);
+    if (rc_small != OK) return rc_small;
     HIP_TRY(m_staged.alloc(slots_bytes(slots)));
     if (keep) HIP_TRY(m_held.alloc(slots_bytes(slots)));
     const RangeSlots held = keep ? carve_slots(m_held.p, slots) : RangeSlots{};

@@ -34,16 +34,16 @@
 // ceil(log2 n) rounds at most one is left, and the next round counts 0.  The bound is hard: a round past it is an internal error.
 // No wavefront waits on another; the answer is a function of the edge list alone.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
 #include <string>
 
 #include "capi_index.hpp"
+#include "csr_intake.hpp"
 #include "graph_internal.hpp"
 #include "hip_host.hpp"
 #include "hnswio.hpp"
+#include "rocprim_host.hpp"
 #include "union_find.hpp"
 
 namespace hnswgpu {
@@ -209,13 +209,6 @@ __global__ __launch_bounds__(256) void msf_answer_kernel(const uint32_t* __restr
     out_w[to] = e_bits[from[e]];  // the stored bits: a -0 or a NaN's payload comes back as the graph holds it
 }
 
-dim3 grid_of(uint64_t threads) { return dim3((uint32_t)((threads + 255) / 256)); }
-
-struct Drain {
-    hipStream_t s;
-    ~Drain() { (void)hipStreamSynchronize(s); }
-};
-
 // ceil(log2 n) + 1: the rounds a forest of n >= 2 vertices can take, the one that counts 0 included
 uint32_t round_bound(uint64_t n) {
     uint32_t bits = 0;
@@ -233,32 +226,24 @@ int forest_of_edges(uint64_t n, uint64_t m, const uint32_t* e_lo, const uint32_t
         return OK;
     }
     const uint32_t bound = round_bound(n);
-    const uint64_t bm = round_up((m + 1) * 4, 256), bn = round_up(n * 4, 256);
     DevMem mem, m_temp, m_out;
     Drain drain{stream};
-    // okey_in, okey_out, self, from, a, b (m words each; flag and its scan stand where the two okeys stood), parent, best, mark (n), hooked
-    HIP_TRY(mem.alloc(6 * bm + 3 * bn + round_up((uint64_t)bound * 4, 256)));
-    unsigned char* p = static_cast<unsigned char*>(mem.p);
-    uint32_t* okey_in = reinterpret_cast<uint32_t*>(p); p += bm;
-    uint32_t* okey_out = reinterpret_cast<uint32_t*>(p); p += bm;
-    uint32_t* self = reinterpret_cast<uint32_t*>(p); p += bm;
-    uint32_t* from = reinterpret_cast<uint32_t*>(p); p += bm;
-    uint32_t* a = reinterpret_cast<uint32_t*>(p); p += bm;
-    uint32_t* b = reinterpret_cast<uint32_t*>(p); p += bm;
-    uint32_t* parent = reinterpret_cast<uint32_t*>(p); p += bn;
-    uint32_t* best = reinterpret_cast<uint32_t*>(p); p += bn;
-    uint32_t* mark = reinterpret_cast<uint32_t*>(p); p += bn;
-    uint32_t* hooked = reinterpret_cast<uint32_t*>(p);
+    // m + 1 words each (flag and its scan stand where the two okeys stood), then n words each, then a word per round
+    uint32_t *okey_in, *okey_out, *self, *from, *a, *b, *parent, *best, *mark, *hooked;
+    ScratchLayout lay;
+    lay.arrays(m + 1, okey_in, okey_out, self, from, a, b);
+    lay.arrays(n, parent, best, mark);
+    lay.array(hooked, bound);
+    int rc = alloc_layout("spanning forest", mem, lay, err);
+    if (rc != OK) return rc;
     uint32_t* flag = okey_in;      // (free once the sort is done)
     uint32_t* slot_of = okey_out;  // (its keys are never read)
 
     // rank
     hipLaunchKernelGGL(msf_keys_kernel, grid_of(m), dim3(256), 0, stream, e_bits, (uint32_t)m, okey_in, self);
     HIP_TRY(hipGetLastError());
-    size_t temp_bytes = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, okey_in, okey_out, self, from, (size_t)m, 0u, 32u, stream));
-    HIP_TRY(m_temp.alloc(std::max<size_t>(temp_bytes, 256)));
-    HIP_TRY(rocprim::radix_sort_pairs(m_temp.p, temp_bytes, okey_in, okey_out, self, from, (size_t)m, 0u, 32u, stream));
+    rc = radix_sort_pairs(m_temp, okey_in, okey_out, self, from, (size_t)m, 32u, stream, err);
+    if (rc != OK) return rc;
     hipLaunchKernelGGL(msf_gather_kernel, grid_of(m + 1), dim3(256), 0, stream, from, e_lo, e_hi, (uint32_t)m, a, b, flag);
     HIP_TRY(hipGetLastError());
 
@@ -286,10 +271,8 @@ int forest_of_edges(uint64_t n, uint64_t m, const uint32_t* e_lo, const uint32_t
 
     // the flagged edges, in rank order
     m_temp.release();
-    temp_bytes = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, flag, slot_of, 0u, (size_t)m + 1, rocprim::plus<uint32_t>(), stream));
-    HIP_TRY(m_temp.alloc(std::max<size_t>(temp_bytes, 256)));
-    HIP_TRY(rocprim::exclusive_scan(m_temp.p, temp_bytes, flag, slot_of, 0u, (size_t)m + 1, rocprim::plus<uint32_t>(), stream));
+    rc = exclusive_scan_u32(m_temp, flag, slot_of, m + 1, stream, err);
+    if (rc != OK) return rc;
     uint32_t edges = 0;
     HIP_TRY(hipMemcpyAsync(&edges, slot_of + m, 4, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -304,12 +287,11 @@ int forest_of_edges(uint64_t n, uint64_t m, const uint32_t* e_lo, const uint32_t
     uint32_t* d_a = out_a;
     uint32_t* d_b = out_b;
     uint32_t* d_w = reinterpret_cast<uint32_t*>(out_w);
-    const uint64_t be = round_up((uint64_t)edges * 4, 256);
     if (host) {
-        HIP_TRY(m_out.alloc(3 * be));
-        d_a = static_cast<uint32_t*>(m_out.p);
-        d_b = d_a + be / 4;
-        d_w = d_b + be / 4;
+        ScratchLayout staged;
+        staged.arrays(edges, d_a, d_b, d_w);
+        rc = alloc_layout("spanning forest", m_out, staged, err);
+        if (rc != OK) return rc;
     }
     hipLaunchKernelGGL(msf_answer_kernel, grid_of(m), dim3(256), 0, stream, a, b, from, e_bits, flag, slot_of, (uint32_t)m, edges, d_a, d_b, d_w);
     HIP_TRY(hipGetLastError());
@@ -363,10 +345,8 @@ int graph_spanning_forest(DeviceIndex& dev, const std::vector<uint64_t>& origin_
     HIP_TRY(hipMemsetAsync(mark + records, 0, 4, stream));
     hipLaunchKernelGGL(msf_mark_kernel, grid_of(records), dim3(256), 0, stream, keys, (uint32_t)records, (uint32_t)n, mutual, mark);
     HIP_TRY(hipGetLastError());
-    size_t temp_bytes = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, mark, slot_of, 0u, (size_t)records + 1, rocprim::plus<uint32_t>(), stream));
-    HIP_TRY(m_temp.alloc(std::max<size_t>(temp_bytes, 256)));
-    HIP_TRY(rocprim::exclusive_scan(m_temp.p, temp_bytes, mark, slot_of, 0u, (size_t)records + 1, rocprim::plus<uint32_t>(), stream));
+    rc = exclusive_scan_u32(m_temp, mark, slot_of, records + 1, stream, err);
+    if (rc != OK) return rc;
     uint32_t m32 = 0;
     HIP_TRY(hipMemcpyAsync(&m32, slot_of + records, 4, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -376,11 +356,11 @@ int graph_spanning_forest(DeviceIndex& dev, const std::vector<uint64_t>& origin_
         err = "spanning forest: " + std::to_string(m) + " pairs out of " + std::to_string(records) + " records";
         return ERR_FORMAT;
     }
-    const uint64_t bm = round_up(std::max<uint64_t>(m, 1) * 4, 256);
-    HIP_TRY(m_edges.alloc(3 * bm));
-    uint32_t* e_lo = static_cast<uint32_t*>(m_edges.p);
-    uint32_t* e_hi = e_lo + bm / 4;
-    uint32_t* e_bits = e_hi + bm / 4;
+    uint32_t *e_lo, *e_hi, *e_bits;
+    ScratchLayout lay;
+    lay.arrays(std::max<uint64_t>(m, 1), e_lo, e_hi, e_bits);
+    rc = alloc_layout("spanning forest", m_edges, lay, err);
+    if (rc != OK) return rc;
     if (m != 0) {
         hipLaunchKernelGGL(msf_pairs_kernel, grid_of(records), dim3(256), 0, stream, keys, vals, slot_of, (uint32_t)records, (uint32_t)n, mutual, core, e_lo,
                            e_hi, e_bits);
@@ -397,78 +377,40 @@ int graph_spanning_forest(DeviceIndex& dev, const std::vector<uint64_t>& origin_
 // Both CSR entries: 2 <= n < 2^31.  host: every array is host memory and has passed the same checks on the host (capi.cpp).
 int csr_spanning_forest(const CsrForestArgs& a, bool host, void* stream_v, std::string& err) {
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || a.device < 0 || a.device >= count) {
-        (void)hipGetLastError();
-        err = "csr spanning forest: no device " + std::to_string(a.device);
-        return ERR_DEVICE;
-    }
+    int rc = use_device_ordinal("csr spanning forest", a.device, err);
+    if (rc != OK) return rc;
     DeviceGuard on(a.device);
     HIP_TRY(on.status());
     const uint64_t n = a.n;
-    DevMem m_in, m_word, m_keys, m_temp, m_edges;
+    CsrOnDevice csr;
+    DevMem m_keys, m_temp, m_edges;
     Drain drain{stream};
-    const uint64_t* d_offsets = a.offsets;
-    const uint32_t* d_cols = a.cols;
-    const float* d_dists = a.dists;
-    if (host) {
-        const uint64_t total = a.offsets[n];
-        const uint64_t b_offs = round_up((n + 1) * 8, 256), b_cols = round_up(total * 4, 256);
-        HIP_TRY(m_in.alloc(b_offs + b_cols * (a.dists ? 2 : 1) + 256));
-        unsigned char* p = static_cast<unsigned char*>(m_in.p);
-        HIP_TRY(hipMemcpyAsync(p, a.offsets, (n + 1) * 8, hipMemcpyHostToDevice, stream));
-        d_offsets = reinterpret_cast<const uint64_t*>(p); p += b_offs;
-        if (total != 0) HIP_TRY(hipMemcpyAsync(p, a.cols, total * 4, hipMemcpyHostToDevice, stream));
-        d_cols = reinterpret_cast<const uint32_t*>(p); p += b_cols;
-        if (a.dists && total != 0) HIP_TRY(hipMemcpyAsync(p, a.dists, total * 4, hipMemcpyHostToDevice, stream));
-        if (a.dists) d_dists = reinterpret_cast<const float*>(p);
-    }
-    // the checks, and the one word that says how they went
-    HIP_TRY(m_word.alloc(256));
-    unsigned long long* d_word = static_cast<unsigned long long*>(m_word.p);
-    HIP_TRY(hipMemsetAsync(d_word, 0, 8, stream));
-    hipLaunchKernelGGL(cc_check_offsets_kernel, grid_of(n + 1), dim3(256), 0, stream, d_offsets, (uint32_t)n, d_word);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(cc_check_cols_kernel, dim3(CHECK_BLOCKS), dim3(256), 0, stream, d_offsets, d_cols, (uint32_t)n, d_word);
-    HIP_TRY(hipGetLastError());
-    unsigned long long word = 0;
-    HIP_TRY(hipMemcpyAsync(&word, d_word, 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if ((word >> 32) != 0ull) {
-        err = std::string("csr spanning forest: ") + ((word & BAD_FIRST)     ? "offsets[0] is not 0"
-                                                      : (word & BAD_DESCENT) ? "the offsets descend"
-                                                      : (word & BAD_TOTAL)   ? "offsets[n] is 2^32 or more"
-                                                      : (word & BAD_NO_COLS) ? "null cols with entries"
-                                                                             : "a col is not below n");
-        return ERR_ARG;
-    }
-    const uint64_t m = word & 0xFFFFFFFFull;
+    rc = csr_intake("csr spanning forest", n, a.offsets, a.cols, a.dists, host, a.dists != nullptr, stream, csr, err);
+    if (rc != OK) return rc;
+    const uint64_t m = csr.total;
     if (m == 0) return forest_of_edges(n, 0, nullptr, nullptr, nullptr, host, a.out_a, a.out_b, a.out_w, a.out_n, stream, err);
     // the entries as (lo, hi) keys with their bits, sorted by key
-    const uint64_t b8 = round_up(m * 8, 256), b4 = round_up(m * 4, 256);
-    HIP_TRY(m_keys.alloc(2 * b8 + b4));
-    HIP_TRY(m_edges.alloc(3 * b4));
-    unsigned char* p = static_cast<unsigned char*>(m_keys.p);
-    uint64_t* keys_in = reinterpret_cast<uint64_t*>(p); p += b8;
-    uint64_t* keys_out = reinterpret_cast<uint64_t*>(p); p += b8;
-    uint32_t* bits_in = reinterpret_cast<uint32_t*>(p);
-    uint32_t* e_lo = static_cast<uint32_t*>(m_edges.p);
-    uint32_t* e_hi = e_lo + b4 / 4;
-    uint32_t* e_bits = e_hi + b4 / 4;
-    hipLaunchKernelGGL(msf_entries_kernel, grid_of(m), dim3(256), 0, stream, d_offsets, d_cols, d_dists, (uint32_t)n, (uint32_t)m, keys_in, bits_in);
+    uint64_t *keys_in, *keys_out;
+    uint32_t *bits_in, *e_lo, *e_hi, *e_bits;
+    ScratchLayout keyed, edges;
+    keyed.arrays(m, keys_in, keys_out, bits_in);
+    edges.arrays(m, e_lo, e_hi, e_bits);
+    rc = alloc_layout("csr spanning forest", m_keys, keyed, err);
+    if (rc != OK) return rc;
+    rc = alloc_layout("csr spanning forest", m_edges, edges, err);
+    if (rc != OK) return rc;
+    hipLaunchKernelGGL(msf_entries_kernel, grid_of(m), dim3(256), 0, stream, csr.offsets, csr.cols, csr.dists, (uint32_t)n, (uint32_t)m, keys_in, bits_in);
     HIP_TRY(hipGetLastError());
     unsigned end_bit = 33;  // hi below n in the low word, lo below n above it
     while (end_bit < 64 && (n >> (end_bit - 32)) != 0) ++end_bit;
-    size_t temp_bytes = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, keys_out, bits_in, e_bits, (size_t)m, 0u, end_bit, stream));
-    HIP_TRY(m_temp.alloc(std::max<size_t>(temp_bytes, 256)));
-    HIP_TRY(rocprim::radix_sort_pairs(m_temp.p, temp_bytes, keys_in, keys_out, bits_in, e_bits, (size_t)m, 0u, end_bit, stream));
+    rc = radix_sort_pairs(m_temp, keys_in, keys_out, bits_in, e_bits, (size_t)m, end_bit, stream, err);
+    if (rc != OK) return rc;
     hipLaunchKernelGGL(msf_unpack_kernel, grid_of(m), dim3(256), 0, stream, keys_out, (uint32_t)m, e_lo, e_hi);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
     m_keys.release();
     m_temp.release();
-    m_in.release();
+    csr.mem.release();
     return forest_of_edges(n, m, e_lo, e_hi, e_bits, host, a.out_a, a.out_b, a.out_w, a.out_n, stream, err);
 }
 

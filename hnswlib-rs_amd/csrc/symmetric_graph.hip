@@ -23,8 +23,6 @@
 // graph_components.hip through graph_internal.hpp: the components of the UNION graph hook D's slots, those of the MUTUAL graph the
 // sorted records.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
@@ -35,6 +33,7 @@
 #include "graph_internal.hpp"
 #include "hip_host.hpp"
 #include "hnswio.hpp"
+#include "rocprim_host.hpp"
 
 namespace hnswgpu {
 namespace {
@@ -131,14 +130,6 @@ struct SegBound {
 };
 typedef rocprim::transform_iterator<const uint64_t*, SegBound, unsigned int> seg_iter_t;
 
-dim3 grid_of(uint64_t threads) { return dim3((uint32_t)((threads + 255) / 256)); }
-
-// declared behind a call's device memory, so destroyed first: nothing of the call is running when its memory is freed
-struct Drain {
-    hipStream_t s;
-    ~Drain() { (void)hipStreamSynchronize(s); }
-};
-
 }  // namespace
 
 // D staged for every point: the graph path's own call into one allocation (graph_internal.hpp)
@@ -146,13 +137,13 @@ int stage_directed_graph(DeviceIndex& dev, const std::vector<uint64_t>& origin_i
                          std::string& err) {
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     const uint64_t n = dev.view().n, slots = n * k;
-    HIP_TRY(out.mem.alloc(round_up(slots * 8, 256) + 2 * round_up(slots * 4, 256) + round_up(n * 4, 256) + round_up(slots, 256)));
-    unsigned char* p = static_cast<unsigned char*>(out.mem.p);
-    uint64_t* d_ids = reinterpret_cast<uint64_t*>(p); p += round_up(slots * 8, 256);
-    out.dists = reinterpret_cast<float*>(p); p += round_up(slots * 4, 256);
-    out.rank = reinterpret_cast<int32_t*>(p); p += round_up(slots * 4, 256);
-    out.counts = reinterpret_cast<uint32_t*>(p); p += round_up(n * 4, 256);
-    out.layer = p;
+    uint64_t* d_ids = nullptr;
+    ScratchLayout lay;
+    lay.arrays(slots, d_ids, out.dists, out.rank);
+    lay.array(out.counts, n);
+    lay.array(out.layer, slots);
+    const int rc = alloc_layout("graph", out.mem, lay, err);
+    if (rc != OK) return rc;
     return ef == 0 ? exact_graph(dev, origin_id, false, nullptr, n, k, nullptr, 0, d_ids, out.dists, out.layer, out.rank, out.counts, stream, err)
                    : graph_search(dev, origin_id, false, nullptr, n, k, ef, d_ids, out.dists, out.layer, out.rank, out.counts, stream, err);
 }
@@ -192,10 +183,8 @@ int sorted_edge_records_keeping(DeviceIndex& dev, const std::vector<uint64_t>& o
     HIP_TRY(hipGetLastError());
     unsigned end_bit = 34;  // the flag, the col, and the bits of a row number 0 .. n
     while (end_bit < 64 && (n >> (end_bit - 33)) != 0) ++end_bit;
-    size_t temp_bytes = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_a, keys_b, vals_a, vals_b, (uint32_t)records, 0u, end_bit, stream));
-    HIP_TRY(m_temp.alloc(std::max<size_t>(temp_bytes, 256)));
-    HIP_TRY(rocprim::radix_sort_pairs(m_temp.p, temp_bytes, keys_a, keys_b, vals_a, vals_b, (uint32_t)records, 0u, end_bit, stream));
+    rc = radix_sort_pairs(m_temp, keys_a, keys_b, vals_a, vals_b, (uint32_t)records, end_bit, stream, err);
+    if (rc != OK) return rc;
     HIP_TRY(hipStreamSynchronize(stream));
     return OK;  // (the sort's temporary storage is released here)
 }
@@ -227,8 +216,6 @@ int symmetric_graph(DeviceIndex* dev_p, const std::vector<uint64_t>& origin_id, 
     uint64_t* keys_b = static_cast<uint64_t*>(rec.keys_b.p);
     uint32_t* vals_a = static_cast<uint32_t*>(rec.vals_a.p);
     uint32_t* vals_b = static_cast<uint32_t*>(rec.vals_b.p);
-    size_t temp_bytes = 0;
-    unsigned char* p = nullptr;
 
     // marks, their scan, the offsets, the total
     uint32_t* mark = reinterpret_cast<uint32_t*>(keys_a);
@@ -237,10 +224,8 @@ int symmetric_graph(DeviceIndex* dev_p, const std::vector<uint64_t>& origin_id, 
     hipLaunchKernelGGL(sym_mark_kernel, grid_of(records), dim3(256), 0, stream, keys_b, (uint32_t)records, (uint32_t)n, a.mode == HNSWGPU_SYM_MUTUAL ? 1u : 0u,
                        mark);
     HIP_TRY(hipGetLastError());
-    temp_bytes = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, mark, slot_of, 0u, (size_t)records + 1, rocprim::plus<uint32_t>(), stream));
-    HIP_TRY(m_temp.alloc(std::max<size_t>(temp_bytes, 256)));
-    HIP_TRY(rocprim::exclusive_scan(m_temp.p, temp_bytes, mark, slot_of, 0u, (size_t)records + 1, rocprim::plus<uint32_t>(), stream));
+    rc = exclusive_scan_u32(m_temp, mark, slot_of, records + 1, stream, err);
+    if (rc != OK) return rc;
     uint64_t* d_offs = a.out_offsets;
     if (host) {
         HIP_TRY(m_offs.alloc((n + 1) * 8));
@@ -261,16 +246,17 @@ int symmetric_graph(DeviceIndex* dev_p, const std::vector<uint64_t>& origin_id, 
     if (total == 0) return OK;
 
     // the entries at their rows, every row sorted, decoded
-    HIP_TRY(m_row.alloc(2 * round_up(total * 8, 256) + round_up(total * 4, 256)));
-    p = static_cast<unsigned char*>(m_row.p);
-    uint64_t* row_keys_in = reinterpret_cast<uint64_t*>(p); p += round_up(total * 8, 256);
-    uint64_t* row_keys = reinterpret_cast<uint64_t*>(p); p += round_up(total * 8, 256);
-    uint32_t* row_bits = reinterpret_cast<uint32_t*>(p);
+    uint64_t *row_keys_in, *row_keys;
+    uint32_t* row_bits;
+    ScratchLayout lay;
+    lay.arrays(total, row_keys_in, row_keys, row_bits);
+    rc = alloc_layout("symmetric graph", m_row, lay, err);
+    if (rc != OK) return rc;
     uint32_t* row_bits_in = vals_a;  // (free since the sort; total <= records)
     hipLaunchKernelGGL(sym_fill_kernel, grid_of(records), dim3(256), 0, stream, keys_b, vals_b, mark, slot_of, (uint32_t)records, row_keys_in, row_bits_in);
     HIP_TRY(hipGetLastError());
     const seg_iter_t seg(d_offs, SegBound{});
-    temp_bytes = 0;
+    size_t temp_bytes = 0;
     HIP_TRY(rocprim::segmented_radix_sort_pairs(nullptr, temp_bytes, row_keys_in, row_keys, row_bits_in, row_bits, (unsigned)total, (unsigned)n, seg, seg + 1, 0u,
                                                 64u, stream));
     HIP_TRY(m_temp.alloc(std::max<size_t>(temp_bytes, 256)));

@@ -1,8 +1,9 @@
-// union_find.hpp -- what graph_components.hip shares with spanning_forest.hip: the lock-free union-find over u32 parents (ECL-CC:
-// Jaiganesh & Burtscher, HPDC 2018) and the validation kernels of a CSR with their one word.  Private, device code only: included by
-// the two .hip units (every name here is in an unnamed namespace, so each unit gets its own copy of the kernels).  The compress
-// kernel is union_find_compress.inc: a unit includes it, inside its own unnamed namespace, where its kernels stand in their order
-// of use.
+// union_find.hpp -- the lock-free union-find over u32 parents (ECL-CC: Jaiganesh & Burtscher, HPDC 2018) of graph_components.hip,
+// spanning_forest.hip, dendrogram.hip and condensed_tree.hip, and the validation kernels of a CSR with their one word, which the
+// first two launch through csr_intake.hpp (the other two have no caller for them).  Private, device code only.  Every name here is
+// in an unnamed namespace: a unit that includes it compiles its own copy of the kernels, and host code that launches them is shared
+// the same way, as a header in an unnamed namespace.  The compress kernel is union_find_compress.inc: a unit includes it, inside
+// its own unnamed namespace, where its kernels stand in their order of use.
 // The invariant behind every loop: parent[v] <= v at all times, and a write to parent[v] only ever lowers it (a compare-and-swap of a
 // root v to a smaller root, an atomic min with an ancestor).  So the links have no cycle, a walk up strictly descends, and a root is
 // the smallest vertex of its tree.
