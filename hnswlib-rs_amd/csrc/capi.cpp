@@ -13,6 +13,8 @@
 #include <thread>
 #include <vector>
 
+// (this file's references to the device side are weak: search_device.hpp, HNSWGPU_DEVICE_SIDE)
+#define HNSWGPU_WEAK_DEVICE_SIDE
 #include "../../include/hnsw_mi355x.h"
 #include "builder.hpp"
 #include "datamap.hpp"
@@ -164,7 +166,6 @@ void capi_zero_knn_answers(uint64_t nq, uint64_t k, uint64_t* out_ids, float* ou
     zero_knn_answers(nq, k, out_ids, out_dists, out_layer, out_rank, out_counts);
 }
 int capi_primary_f32_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mutex>& sl, DeviceIndex** out) { return primary_f32_replica(idx, sl, out); }
-int capi_primary_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mutex>& sl, DeviceIndex** out) { return primary_replica(idx, sl, out); }
 int capi_refuse_f16(const hnswgpu_index* idx, const char* what) {
     if (idx->storage != HNSWGPU_STORAGE_F16) return HNSWGPU_OK;
     return fail(HNSWGPU_ERR_ARG, std::string(what) + " reads f32 rows only: the index is set to HNSWGPU_STORAGE_F16 "
@@ -751,20 +752,22 @@ int hnswgpu_search_batch_filtered_device(const hnswgpu_index* cidx, const float*
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
-// ---- filter set: every query of the batch under a filter of its own choice (search_device.hpp: FilterSet)
-// Weak references: the host-only build of this file (tools/asan_host_suite.sh links it against stand-ins for the device) has no
-// search_device.hip behind it and answers "no device" -- after the argument checks, which are the same everywhere.
-extern "C++" {
-namespace hnswgpu {
-__attribute__((weak)) int search_filter_set_device(DeviceIndex&, const float*, uint64_t, uint64_t, uint64_t, uint64_t, const FilterSet&, uint64_t*,
-                                                   float*, uint8_t*, int32_t*, uint32_t*, uint32_t*, void*, CallInfo*, std::string&);
-__attribute__((weak)) int search_filter_set_host(DeviceIndex&, const float*, uint64_t, uint64_t, uint64_t, uint64_t, const FilterSet&, uint64_t*,
-                                                 float*, uint8_t*, int32_t*, uint32_t*, uint8_t*, CallInfo*, std::string&);
-}  // namespace hnswgpu
-}  // extern "C++"
+// ---- The host / _device pairs.  A pair is ONE body, a static function that holds the pair's whole sequence -- checks, trivial
+// answers, "is there a device side", replica, call, finish -- and takes (host, stream) last: (true, nullptr) from the host-buffer
+// entry, (false, the caller's stream) from the _device entry.  Where the two forms part, the body says `if (host)`.  The two C entries
+// above it open the guard, build the arguments' struct and close the guard with their own code: an exception that gets there is
+// HNSWGPU_ERR_ARG in the host form, HNSWGPU_ERR_DEVICE in the device form.
 static const char* const kNoFilterSetDevice = "no HIP device visible (a gfx950 GPU is required; there is no CPU fallback)";
 
-// what both entries of a filter-set pair can check of the set without reading it (unfiltered: the sibling the message points to)
+// the replica a pair's call works on; the handle's lock is held (shared).  Host form: the primary one, uploaded on first use (f32: for
+// a call that reads rows outside the search path).  Device form: the one that is there; need_flat: the call reads the host view too.
+static int call_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mutex>& sl, bool host, bool f32, bool need_flat, DeviceIndex** dev) {
+    if (!host) return resident_replica(idx, need_flat, dev);
+    return f32 ? primary_f32_replica(idx, sl, dev) : primary_replica(idx, sl, dev);
+}
+
+// ---- filter set: every query of the batch under a filter of its own choice (search_device.hpp: FilterSet)
+// what both forms of a filter-set pair can check of the set without reading it (unfiltered: the sibling the message points to)
 static int check_filter_set_shape(const void* queries, uint64_t nq, const void* filter_offsets, uint64_t n_filters, const void* filter_of,
                                   const void* out_ids, const void* out_dists, const void* out_counts, const char* unfiltered) {
     if (nq != 0 && (!queries || !out_ids || !out_dists || !out_counts)) return fail(HNSWGPU_ERR_ARG, "null buffer");
@@ -775,7 +778,7 @@ static int check_filter_set_shape(const void* queries, uint64_t nq, const void* 
     if (n_filters > 0xFFFFFFFFull) return fail(HNSWGPU_ERR_ARG, "too many filters: filter_of is 32 bits wide");
     return HNSWGPU_OK;
 }
-// ... and what only a host entry can, behind the shape: the set itself
+// ... and what only a host form can, behind the shape: the set itself
 static int check_filter_set_contents(const uint64_t* filter_ids, const uint64_t* filter_offsets, uint64_t n_filters, const uint32_t* filter_of,
                                      uint64_t nq) {
     if (n_filters != 0) {
@@ -795,335 +798,264 @@ static int check_filter_set_contents(const uint64_t* filter_ids, const uint64_t*
                         std::to_string(n_filters) + ")");
     return HNSWGPU_OK;
 }
+// the set as a device form hands it on: filters that are all empty need no id array, so a null one becomes a non-null pointer that is
+// never dereferenced
+static FilterSet device_filter_set(const ExactSetArgs& a) {
+    return FilterSet{a.set.ids ? a.set.ids : reinterpret_cast<const uint64_t*>(a.queries), a.set.offsets, a.set.n_filters, a.set.filter_of};
+}
 
-int hnswgpu_search_batch_filter_set(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef,
-                                    const uint64_t* filter_ids, const uint64_t* filter_offsets, uint64_t n_filters,
-                                    const uint32_t* filter_of, uint64_t* out_ids, float* out_dists, uint8_t* out_layer,
-                                    int32_t* out_rank, uint32_t* out_counts, uint8_t* out_status) {
-    CAPI_GUARD_BEGIN
+// The search's pair (a: the exact pair's struct serves, k its knbn).  The two forms answer in different places -- out_status on the
+// host, d_stats and *n_panics with device buffers -- and the device form reads the handle later than the host form.
+static int search_filter_set_pair(const hnswgpu_index* cidx, const ExactSetArgs& a, uint64_t ef, uint8_t* out_status, uint32_t* d_stats,
+                                  uint32_t* n_panics, bool host, void* stream) {
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!host && n_panics) *n_panics = 0;  // (ahead of the null-handle check)
     if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    int rc = check_filter_set_shape(queries, nq, filter_offsets, n_filters, filter_of, out_ids, out_dists, out_counts, "hnswgpu_search_batch");
+    int rc = check_filter_set_shape(a.queries, a.nq, a.set.offsets, a.set.n_filters, a.set.filter_of, a.out_ids, a.out_dists, a.out_counts,
+                                    host ? "hnswgpu_search_batch" : "hnswgpu_search_batch_device");
     if (rc != HNSWGPU_OK) return rc;
-    rc = check_filter_set_contents(filter_ids, filter_offsets, n_filters, filter_of, nq);
-    if (rc != HNSWGPU_OK) return rc;
-    std::shared_lock<std::shared_mutex> sl(idx->mu);
-    if (index_empty(idx)) {  // empty index => every answer is empty (src/hnsw.rs:1498-1503)
-        if (out_counts) std::memset(out_counts, 0, nq * sizeof(uint32_t));
-        if (out_status) std::memset(out_status, 0, nq);
-        return HNSWGPU_OK;
+    std::shared_lock<std::shared_mutex> sl(idx->mu, std::defer_lock);
+    if (host) {
+        rc = check_filter_set_contents(a.set.ids, a.set.offsets, a.set.n_filters, a.set.filter_of, a.nq);
+        if (rc != HNSWGPU_OK) return rc;
+        sl.lock();
+        if (index_empty(idx)) {  // empty index => every answer is empty (src/hnsw.rs:1498-1503)
+            if (a.out_counts) std::memset(a.out_counts, 0, a.nq * sizeof(uint32_t));
+            if (out_status) std::memset(out_status, 0, a.nq);
+            return HNSWGPU_OK;
+        }
     }
-    if (nq == 0) return HNSWGPU_OK;
-    if (!hnswgpu::search_filter_set_host) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    if (a.nq == 0) return HNSWGPU_OK;
+    if (host ? !hnswgpu::search_filter_set_host : !hnswgpu::search_filter_set_device) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    if (!host) sl.lock();
     DeviceIndex* dev = nullptr;
-    rc = primary_replica(idx, sl, &dev);
+    rc = call_replica(idx, sl, host, false, false, &dev);
     if (rc != HNSWGPU_OK) return rc;
     std::string err;
     CallInfo info;
-    const FilterSet set{filter_ids, filter_offsets, n_filters, filter_of};
-    rc = hnswgpu::search_filter_set_host(*dev, queries, nq, d, k, ef, set, out_ids, out_dists, out_layer, out_rank, out_counts, out_status, &info, err);
+    rc = host ? hnswgpu::search_filter_set_host(*dev, a.queries, a.nq, a.d, a.k, ef, a.set, a.out_ids, a.out_dists, a.out_layer, a.out_rank, a.out_counts,
+                                                out_status, &info, err)
+              : hnswgpu::search_filter_set_device(*dev, a.queries, a.nq, a.d, a.k, ef, device_filter_set(a), a.out_ids, a.out_dists, a.out_layer, a.out_rank,
+                                                  a.out_counts, d_stats, stream, &info, err);
     if (rc != OK) return fail(rc, err);
+    if (!host) {
+        if (n_panics) *n_panics = info.panics;
+        return HNSWGPU_OK;
+    }
     if (info.panics != 0 && !out_status)
         return fail(HNSWGPU_ERR_REF_PANIC, "the reference panics on " + std::to_string(info.panics) +
                     " of these queries (return_points.peek().unwrap() on a heap the filter emptied, src/hnsw.rs:973); "
                     "pass out_status to learn which");
     return HNSWGPU_OK;
+}
+
+int hnswgpu_search_batch_filter_set(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef,
+                                    const uint64_t* filter_ids, const uint64_t* filter_offsets, uint64_t n_filters,
+                                    const uint32_t* filter_of, uint64_t* out_ids, float* out_dists, uint8_t* out_layer,
+                                    int32_t* out_rank, uint32_t* out_counts, uint8_t* out_status) {
+    CAPI_GUARD_BEGIN
+    const ExactSetArgs a{queries, nq, d, k, FilterSet{filter_ids, filter_offsets, n_filters, filter_of}, out_ids, out_dists, out_layer, out_rank, out_counts};
+    return search_filter_set_pair(idx, a, ef, out_status, nullptr, nullptr, true, nullptr);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
-int hnswgpu_search_batch_filter_set_device(const hnswgpu_index* cidx, const float* d_queries, uint64_t nq, uint64_t d, uint64_t k,
+int hnswgpu_search_batch_filter_set_device(const hnswgpu_index* idx, const float* d_queries, uint64_t nq, uint64_t d, uint64_t k,
                                            uint64_t ef, const uint64_t* d_filter_ids, const uint64_t* d_filter_offsets,
                                            uint64_t n_filters, const uint32_t* d_filter_of, uint64_t* d_out_ids, float* d_out_dists,
                                            uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, uint32_t* d_stats,
                                            void* stream, uint32_t* n_panics) {
     CAPI_GUARD_BEGIN
-    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
-    if (n_panics) *n_panics = 0;
-    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    int rc = check_filter_set_shape(d_queries, nq, d_filter_offsets, n_filters, d_filter_of, d_out_ids, d_out_dists, d_out_counts,
-                                    "hnswgpu_search_batch_device");
-    if (rc != HNSWGPU_OK) return rc;
-    if (nq == 0) return HNSWGPU_OK;
-    if (!hnswgpu::search_filter_set_device) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    std::shared_lock<std::shared_mutex> sl(idx->mu);
-    DeviceIndex* dev = nullptr;
-    rc = resident_replica(idx, false, &dev);
-    if (rc != HNSWGPU_OK) return rc;
-    std::string err;
-    CallInfo info;
-    // (filters that are all empty need no id array: hand over a non-null pointer that is never dereferenced)
-    const FilterSet set{d_filter_ids ? d_filter_ids : reinterpret_cast<const uint64_t*>(d_queries), d_filter_offsets, n_filters, d_filter_of};
-    rc = hnswgpu::search_filter_set_device(*dev, d_queries, nq, d, k, ef, set, d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts,
-                                           d_stats, stream, &info, err);
-    if (rc != OK) return fail(rc, err);
-    if (n_panics) *n_panics = info.panics;
-    return HNSWGPU_OK;
+    const ExactSetArgs a{d_queries, nq, d, k, FilterSet{d_filter_ids, d_filter_offsets, n_filters, d_filter_of}, d_out_ids, d_out_dists, d_out_layer,
+                         d_out_rank, d_out_counts};
+    return search_filter_set_pair(idx, a, ef, nullptr, d_stats, n_panics, false, stream);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
 // ---- exact k-NN under a filter set: the ground truth of hnswgpu_search_batch_filter_set (exact_knn.hip holds the device side)
-extern "C++" {
-namespace hnswgpu {
-__attribute__((weak)) int exact_filter_set_host(const DeviceIndex&, const std::vector<uint64_t>&, const float*, uint64_t, uint64_t, uint64_t,
-                                                const FilterSet&, uint64_t*, float*, uint8_t*, int32_t*, uint32_t*, std::string&);
-__attribute__((weak)) int exact_filter_set_device(const DeviceIndex&, const std::vector<uint64_t>&, const float*, uint64_t, uint64_t, uint64_t,
-                                                  const FilterSet&, uint64_t*, float*, uint8_t*, int32_t*, uint32_t*, void*, std::string&);
-}  // namespace hnswgpu
-}  // extern "C++"
+static int exact_filter_set_pair(const hnswgpu_index* cidx, const ExactSetArgs& a, bool host, void* stream) {
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    int rc = check_filter_set_shape(a.queries, a.nq, a.set.offsets, a.set.n_filters, a.set.filter_of, a.out_ids, a.out_dists, a.out_counts,
+                                    host ? "hnswgpu_exact_search_batch" : "hnswgpu_exact_search_batch_device");
+    if (rc != HNSWGPU_OK) return rc;
+    if (host) {
+        rc = check_filter_set_contents(a.set.ids, a.set.offsets, a.set.n_filters, a.set.filter_of, a.nq);
+        if (rc != HNSWGPU_OK) return rc;
+    }
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    rc = check_exact_call(idx, a.queries, a.nq, a.d, a.k, nullptr, 0, a.out_ids, a.out_dists, a.out_counts);
+    if (rc != HNSWGPU_OK) return rc;
+    if (host && index_empty(idx)) {  // no point: every answer is empty
+        zero_knn_answers(a.nq, a.k, a.out_ids, a.out_dists, a.out_layer, a.out_rank, a.out_counts);
+        return HNSWGPU_OK;
+    }
+    if (a.nq == 0) return HNSWGPU_OK;
+    if (!hnswgpu::exact_filter_set) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = call_replica(idx, sl, host, true, true, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    ExactSetArgs b = a;
+    if (!host) b.set = device_filter_set(a);
+    std::string err;
+    return finish(hnswgpu::exact_filter_set(*dev, idx->flat->origin_id, b, host, stream, err), err);
+}
 
-int hnswgpu_exact_search_batch_filter_set(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, uint64_t k,
+int hnswgpu_exact_search_batch_filter_set(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, uint64_t k,
                                           const uint64_t* filter_ids, const uint64_t* filter_offsets, uint64_t n_filters,
                                           const uint32_t* filter_of, uint64_t* out_ids, float* out_dists, uint8_t* out_layer,
                                           int32_t* out_rank, uint32_t* out_counts) {
     CAPI_GUARD_BEGIN
-    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
-    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    int rc = check_filter_set_shape(queries, nq, filter_offsets, n_filters, filter_of, out_ids, out_dists, out_counts, "hnswgpu_exact_search_batch");
-    if (rc != HNSWGPU_OK) return rc;
-    rc = check_filter_set_contents(filter_ids, filter_offsets, n_filters, filter_of, nq);
-    if (rc != HNSWGPU_OK) return rc;
-    std::shared_lock<std::shared_mutex> sl(idx->mu);
-    rc = check_exact_call(idx, queries, nq, d, k, nullptr, 0, out_ids, out_dists, out_counts);
-    if (rc != HNSWGPU_OK) return rc;
-    if (index_empty(idx)) {  // no point: every answer is empty
-        zero_knn_answers(nq, k, out_ids, out_dists, out_layer, out_rank, out_counts);
-        return HNSWGPU_OK;
-    }
-    if (nq == 0) return HNSWGPU_OK;
-    if (!hnswgpu::exact_filter_set_host) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    DeviceIndex* dev = nullptr;
-    rc = primary_f32_replica(idx, sl, &dev);
-    if (rc != HNSWGPU_OK) return rc;
-    std::string err;
-    const FilterSet set{filter_ids, filter_offsets, n_filters, filter_of};
-    return finish(hnswgpu::exact_filter_set_host(*dev, idx->flat->origin_id, queries, nq, d, k, set, out_ids, out_dists, out_layer, out_rank, out_counts, err),
-                  err);
+    const ExactSetArgs a{queries, nq, d, k, FilterSet{filter_ids, filter_offsets, n_filters, filter_of}, out_ids, out_dists, out_layer, out_rank, out_counts};
+    return exact_filter_set_pair(idx, a, true, nullptr);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
-int hnswgpu_exact_search_batch_filter_set_device(const hnswgpu_index* cidx, const float* d_queries, uint64_t nq, uint64_t d, uint64_t k,
+int hnswgpu_exact_search_batch_filter_set_device(const hnswgpu_index* idx, const float* d_queries, uint64_t nq, uint64_t d, uint64_t k,
                                                  const uint64_t* d_filter_ids, const uint64_t* d_filter_offsets, uint64_t n_filters,
                                                  const uint32_t* d_filter_of, uint64_t* d_out_ids, float* d_out_dists,
                                                  uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, void* stream) {
     CAPI_GUARD_BEGIN
-    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
-    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    int rc = check_filter_set_shape(d_queries, nq, d_filter_offsets, n_filters, d_filter_of, d_out_ids, d_out_dists, d_out_counts,
-                                    "hnswgpu_exact_search_batch_device");
-    if (rc != HNSWGPU_OK) return rc;
-    std::shared_lock<std::shared_mutex> sl(idx->mu);
-    rc = check_exact_call(idx, d_queries, nq, d, k, nullptr, 0, d_out_ids, d_out_dists, d_out_counts);
-    if (rc != HNSWGPU_OK) return rc;
-    if (nq == 0) return HNSWGPU_OK;
-    if (!hnswgpu::exact_filter_set_device) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    DeviceIndex* dev = nullptr;
-    rc = resident_replica(idx, true, &dev);
-    if (rc != HNSWGPU_OK) return rc;
-    std::string err;
-    // (filters that are all empty need no id array: hand over a non-null pointer that is never dereferenced)
-    const FilterSet set{d_filter_ids ? d_filter_ids : reinterpret_cast<const uint64_t*>(d_queries), d_filter_offsets, n_filters, d_filter_of};
-    return finish(hnswgpu::exact_filter_set_device(*dev, idx->flat->origin_id, d_queries, nq, d, k, set, d_out_ids, d_out_dists, d_out_layer, d_out_rank,
-                                                   d_out_counts, stream, err),
-                  err);
+    const ExactSetArgs a{d_queries, nq, d, k, FilterSet{d_filter_ids, d_filter_offsets, n_filters, d_filter_of}, d_out_ids, d_out_dists, d_out_layer,
+                         d_out_rank, d_out_counts};
+    return exact_filter_set_pair(idx, a, false, stream);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
 // ---- exact range search: every eligible point within a query's radius (exact_knn.hip holds the device side)
-extern "C++" {
-namespace hnswgpu {
-__attribute__((weak)) int exact_range_host(const DeviceIndex&, const std::vector<uint64_t>&, const float*, uint64_t, uint64_t, const float*,
-                                           const uint64_t*, uint64_t, uint64_t, uint64_t*, uint64_t*, float*, uint8_t*, int32_t*, std::string&);
-__attribute__((weak)) int exact_range_device(const DeviceIndex&, const std::vector<uint64_t>&, const float*, uint64_t, uint64_t, const float*,
-                                             const uint64_t*, uint64_t, uint64_t, uint64_t*, uint64_t*, float*, uint8_t*, int32_t*, void*, std::string&);
-}  // namespace hnswgpu
-}  // extern "C++"
-// the checks both entries share; the handle's lock is held (shared)
-static int exact_range_call(const hnswgpu_index* idx, const void* queries, uint64_t nq, uint64_t d, const void* radii, const void* allowed,
-                            uint64_t n_allowed, uint64_t cap, const void* out_offsets, const void* out_ids, const void* out_dists) {
+// the checks both forms share; the handle's lock is held (shared)
+static int exact_range_call(const hnswgpu_index* idx, const ExactRangeCallArgs& a) {
     const uint64_t dim = index_dimension(idx);
-    if (!out_offsets) return fail(HNSWGPU_ERR_ARG, "null out_offsets: the offsets are written by every call");
-    if (nq != 0 && !queries) return fail(HNSWGPU_ERR_ARG, "null queries");
-    if (nq != 0 && !radii) return fail(HNSWGPU_ERR_ARG, "null radii: every query names its radius");
-    if (cap != 0 && (!out_ids || !out_dists)) return fail(HNSWGPU_ERR_ARG, "cap > 0 with null out_ids or out_dists (the count-only call is cap == 0)");
-    if (nq > 0xFFFFFFF0ull) return fail(HNSWGPU_ERR_ARG, "too many queries in one batch");
-    if (dim != 0 && d != dim) return fail(HNSWGPU_ERR_ARG, "query dimension differs from the index dimension");
-    if (n_allowed != 0 && !allowed) return fail(HNSWGPU_ERR_ARG, "null filter");
+    if (!a.out_offsets) return fail(HNSWGPU_ERR_ARG, "null out_offsets: the offsets are written by every call");
+    if (a.nq != 0 && !a.queries) return fail(HNSWGPU_ERR_ARG, "null queries");
+    if (a.nq != 0 && !a.radii) return fail(HNSWGPU_ERR_ARG, "null radii: every query names its radius");
+    if (a.cap != 0 && (!a.out_ids || !a.out_dists))
+        return fail(HNSWGPU_ERR_ARG, "cap > 0 with null out_ids or out_dists (the count-only call is cap == 0)");
+    if (a.nq > 0xFFFFFFF0ull) return fail(HNSWGPU_ERR_ARG, "too many queries in one batch");
+    if (dim != 0 && a.d != dim) return fail(HNSWGPU_ERR_ARG, "query dimension differs from the index dimension");
+    if (a.n_allowed != 0 && !a.allowed) return fail(HNSWGPU_ERR_ARG, "null filter");
     if (idx->arithmetic != HNSWGPU_ARITH_SCALAR)
         return fail(HNSWGPU_ERR_ARG, "exact range search answers in the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
     return capi_refuse_f16(idx, "exact range search");
 }
 
-int hnswgpu_exact_range_search_batch(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, const float* radii,
+static int exact_range_pair(const hnswgpu_index* cidx, const ExactRangeCallArgs& a, bool host, void* stream) {
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    int rc = exact_range_call(idx, a);
+    if (rc != HNSWGPU_OK) return rc;
+    if (host) {
+        rc = check_sorted_filter(a.allowed, a.n_allowed);
+        if (rc != HNSWGPU_OK) return rc;
+        if (index_empty(idx) || a.nq == 0) {  // no point, or no query: every answer is empty (the device side's to answer in the device form)
+            std::memset(a.out_offsets, 0, (a.nq + 1) * sizeof(uint64_t));
+            return HNSWGPU_OK;
+        }
+    }
+    if (!hnswgpu::exact_range) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = call_replica(idx, sl, host, true, true, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    return finish(hnswgpu::exact_range(*dev, idx->flat->origin_id, a, host, stream, err), err);
+}
+
+int hnswgpu_exact_range_search_batch(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, const float* radii,
                                      const uint64_t* allowed_ids, uint64_t n_allowed, uint64_t cap, uint64_t* out_offsets, uint64_t* out_ids,
                                      float* out_dists, uint8_t* out_layer, int32_t* out_rank) {
     CAPI_GUARD_BEGIN
-    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
-    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    std::shared_lock<std::shared_mutex> sl(idx->mu);
-    int rc = exact_range_call(idx, queries, nq, d, radii, allowed_ids, n_allowed, cap, out_offsets, out_ids, out_dists);
-    if (rc != HNSWGPU_OK) return rc;
-    rc = check_sorted_filter(allowed_ids, n_allowed);
-    if (rc != HNSWGPU_OK) return rc;
-    if (index_empty(idx) || nq == 0) {  // no point, or no query: every answer is empty
-        std::memset(out_offsets, 0, (nq + 1) * sizeof(uint64_t));
-        return HNSWGPU_OK;
-    }
-    if (!hnswgpu::exact_range_host) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    DeviceIndex* dev = nullptr;
-    rc = primary_f32_replica(idx, sl, &dev);
-    if (rc != HNSWGPU_OK) return rc;
-    std::string err;
-    return finish(hnswgpu::exact_range_host(*dev, idx->flat->origin_id, queries, nq, d, radii, allowed_ids, n_allowed, cap, out_offsets, out_ids, out_dists,
-                                            out_layer, out_rank, err),
-                  err);
+    return exact_range_pair(idx, ExactRangeCallArgs{queries, radii, nq, d, allowed_ids, n_allowed, cap, out_offsets, out_ids, out_dists, out_layer, out_rank},
+                            true, nullptr);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
-int hnswgpu_exact_range_search_batch_device(const hnswgpu_index* cidx, const float* d_queries, uint64_t nq, uint64_t d, const float* d_radii,
+int hnswgpu_exact_range_search_batch_device(const hnswgpu_index* idx, const float* d_queries, uint64_t nq, uint64_t d, const float* d_radii,
                                             const uint64_t* d_allowed_ids, uint64_t n_allowed, uint64_t cap, uint64_t* d_out_offsets,
                                             uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, void* stream) {
     CAPI_GUARD_BEGIN
-    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
-    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    std::shared_lock<std::shared_mutex> sl(idx->mu);
-    int rc = exact_range_call(idx, d_queries, nq, d, d_radii, d_allowed_ids, n_allowed, cap, d_out_offsets, d_out_ids, d_out_dists);
-    if (rc != HNSWGPU_OK) return rc;
-    if (!hnswgpu::exact_range_device) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    DeviceIndex* dev = nullptr;
-    rc = resident_replica(idx, true, &dev);
-    if (rc != HNSWGPU_OK) return rc;
-    std::string err;
-    return finish(hnswgpu::exact_range_device(*dev, idx->flat->origin_id, d_queries, nq, d, d_radii, d_allowed_ids, n_allowed, cap, d_out_offsets, d_out_ids,
-                                              d_out_dists, d_out_layer, d_out_rank, stream, err),
-                  err);
+    return exact_range_pair(idx, ExactRangeCallArgs{d_queries, d_radii, nq, d, d_allowed_ids, n_allowed, cap, d_out_offsets, d_out_ids, d_out_dists,
+                                                    d_out_layer, d_out_rank},
+                            false, stream);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
 // ---- queries by stored point: the k-NN graph of the indexed points, approximate and exact (exact_knn.hip holds the device side)
-extern "C++" {
-namespace hnswgpu {
-__attribute__((weak)) int graph_search(DeviceIndex&, const std::vector<uint64_t>&, bool, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*, float*,
-                                       uint8_t*, int32_t*, uint32_t*, void*, std::string&);
-__attribute__((weak)) int exact_graph(const DeviceIndex&, const std::vector<uint64_t>&, bool, const uint64_t*, uint64_t, uint64_t, const uint64_t*, uint64_t,
-                                      uint64_t*, float*, uint8_t*, int32_t*, uint32_t*, void*, std::string&);
-}  // namespace hnswgpu
-}  // extern "C++"
 // the checks all four entries share; the handle's lock is held (shared).  exact: the exact call's own limits behind them.
-static int graph_call(const hnswgpu_index* idx, const void* point_ids, uint64_t np, uint64_t k, bool exact, const void* allowed, uint64_t n_allowed,
-                      const void* out_ids, const void* out_dists, const void* out_counts) {
+static int graph_call(const hnswgpu_index* idx, const GraphCallArgs& a, bool exact) {
     const uint64_t n = index_nb_point(idx);
-    if (np != 0 && (!out_ids || !out_dists || !out_counts)) return fail(HNSWGPU_ERR_ARG, "null buffer");
-    if (!point_ids && np != n)
-        return fail(HNSWGPU_ERR_ARG, "point_ids is NULL (every point): np must be nb_point = " + std::to_string(n) + ", not " + std::to_string(np));
-    if (k == 0) return fail(HNSWGPU_ERR_ARG, "knbn must be > 0");
-    if (np > 0xFFFFFFF0ull) return fail(HNSWGPU_ERR_ARG, "too many points in one batch");
+    if (a.np != 0 && (!a.out_ids || !a.out_dists || !a.out_counts)) return fail(HNSWGPU_ERR_ARG, "null buffer");
+    if (!a.point_ids && a.np != n)
+        return fail(HNSWGPU_ERR_ARG, "point_ids is NULL (every point): np must be nb_point = " + std::to_string(n) + ", not " + std::to_string(a.np));
+    if (a.k == 0) return fail(HNSWGPU_ERR_ARG, "knbn must be > 0");
+    if (a.np > 0xFFFFFFF0ull) return fail(HNSWGPU_ERR_ARG, "too many points in one batch");
     if (!exact) return capi_refuse_f16(idx, "the graph search (its gather kernel copies stored rows)");
-    if (k > 4096) return fail(HNSWGPU_ERR_ARG, "exact graph: knbn above 4096");
-    if (n_allowed != 0 && !allowed) return fail(HNSWGPU_ERR_ARG, "null filter");
+    if (a.k > 4096) return fail(HNSWGPU_ERR_ARG, "exact graph: knbn above 4096");
+    if (a.n_allowed != 0 && !a.allowed) return fail(HNSWGPU_ERR_ARG, "null filter");
     if (idx->arithmetic != HNSWGPU_ARITH_SCALAR)
         return fail(HNSWGPU_ERR_ARG, "exact graph answers in the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
     return capi_refuse_f16(idx, "exact graph");
 }
-// what the host entries do behind the checks: an empty index names no point; else the replica, uploaded on first use
-static int graph_host_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mutex>& sl, uint64_t np, bool have_device_side, DeviceIndex** dev) {
-    *dev = nullptr;
-    if (np == 0) return HNSWGPU_OK;
-    if (index_empty(idx)) return fail(HNSWGPU_ERR_ARG, std::to_string(np) + " of the " + std::to_string(np) + " point_ids name no point of the index");
-    if (!have_device_side) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    return primary_f32_replica(idx, sl, dev);
-}
-// ... and the device entries: no point asks nothing of a device; else the replica has to be there
-static int graph_device_replica(const hnswgpu_index* idx, uint64_t np, bool have_device_side, DeviceIndex** dev) {
-    *dev = nullptr;
-    if (np == 0) return HNSWGPU_OK;
-    if (!have_device_side) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    return resident_replica(idx, true, dev);
-}
 
-int hnswgpu_graph_search_batch(const hnswgpu_index* cidx, const uint64_t* point_ids, uint64_t np, uint64_t k, uint64_t ef, uint64_t* out_ids,
-                               float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts) {
-    CAPI_GUARD_BEGIN
+// both pairs: exact picks hnswgpu_exact_graph_batch(_device), else hnswgpu_graph_search_batch(_device), which hands in no filter
+static int graph_pair(const hnswgpu_index* cidx, const GraphCallArgs& a, bool exact, bool host, void* stream) {
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
     std::shared_lock<std::shared_mutex> sl(idx->mu);
-    int rc = graph_call(idx, point_ids, np, k, false, nullptr, 0, out_ids, out_dists, out_counts);
+    int rc = graph_call(idx, a, exact);
     if (rc != HNSWGPU_OK) return rc;
+    if (host) {
+        rc = check_sorted_filter(a.allowed, a.n_allowed);
+        if (rc != HNSWGPU_OK) return rc;
+    }
+    if (a.np == 0) return HNSWGPU_OK;  // no point asks nothing of a device
+    if (host && index_empty(idx))  // an empty index names no point (the device form: it cannot be resident)
+        return fail(HNSWGPU_ERR_ARG, std::to_string(a.np) + " of the " + std::to_string(a.np) + " point_ids name no point of the index");
+    if (exact ? !hnswgpu::exact_graph : !hnswgpu::graph_search) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     DeviceIndex* dev = nullptr;
-    rc = graph_host_replica(idx, sl, np, hnswgpu::graph_search != nullptr, &dev);
-    if (rc != HNSWGPU_OK || !dev) return rc;
+    rc = call_replica(idx, sl, host, true, true, &dev);
+    if (rc != HNSWGPU_OK) return rc;
     std::string err;
-    return finish(hnswgpu::graph_search(*dev, idx->flat->origin_id, true, point_ids, np, k, ef, out_ids, out_dists, out_layer, out_rank, out_counts, nullptr, err),
+    return finish(exact ? hnswgpu::exact_graph(*dev, idx->flat->origin_id, a, host, stream, err)
+                        : hnswgpu::graph_search(*dev, idx->flat->origin_id, a, host, stream, err),
                   err);
+}
+
+int hnswgpu_graph_search_batch(const hnswgpu_index* idx, const uint64_t* point_ids, uint64_t np, uint64_t k, uint64_t ef, uint64_t* out_ids,
+                               float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts) {
+    CAPI_GUARD_BEGIN
+    return graph_pair(idx, GraphCallArgs{point_ids, np, k, ef, nullptr, 0, out_ids, out_dists, out_layer, out_rank, out_counts}, false, true, nullptr);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
-int hnswgpu_graph_search_batch_device(const hnswgpu_index* cidx, const uint64_t* d_point_ids, uint64_t np, uint64_t k, uint64_t ef,
+int hnswgpu_graph_search_batch_device(const hnswgpu_index* idx, const uint64_t* d_point_ids, uint64_t np, uint64_t k, uint64_t ef,
                                       uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts,
                                       void* stream) {
     CAPI_GUARD_BEGIN
-    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
-    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    std::shared_lock<std::shared_mutex> sl(idx->mu);
-    int rc = graph_call(idx, d_point_ids, np, k, false, nullptr, 0, d_out_ids, d_out_dists, d_out_counts);
-    if (rc != HNSWGPU_OK) return rc;
-    DeviceIndex* dev = nullptr;
-    rc = graph_device_replica(idx, np, hnswgpu::graph_search != nullptr, &dev);
-    if (rc != HNSWGPU_OK || !dev) return rc;
-    std::string err;
-    return finish(hnswgpu::graph_search(*dev, idx->flat->origin_id, false, d_point_ids, np, k, ef, d_out_ids, d_out_dists, d_out_layer, d_out_rank,
-                                        d_out_counts, stream, err),
-                  err);
+    return graph_pair(idx, GraphCallArgs{d_point_ids, np, k, ef, nullptr, 0, d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts}, false, false,
+                      stream);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
-int hnswgpu_exact_graph_batch(const hnswgpu_index* cidx, const uint64_t* point_ids, uint64_t np, uint64_t k, const uint64_t* allowed_ids,
+int hnswgpu_exact_graph_batch(const hnswgpu_index* idx, const uint64_t* point_ids, uint64_t np, uint64_t k, const uint64_t* allowed_ids,
                               uint64_t n_allowed, uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts) {
     CAPI_GUARD_BEGIN
-    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
-    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    std::shared_lock<std::shared_mutex> sl(idx->mu);
-    int rc = graph_call(idx, point_ids, np, k, true, allowed_ids, n_allowed, out_ids, out_dists, out_counts);
-    if (rc != HNSWGPU_OK) return rc;
-    rc = check_sorted_filter(allowed_ids, n_allowed);
-    if (rc != HNSWGPU_OK) return rc;
-    DeviceIndex* dev = nullptr;
-    rc = graph_host_replica(idx, sl, np, hnswgpu::exact_graph != nullptr, &dev);
-    if (rc != HNSWGPU_OK || !dev) return rc;
-    std::string err;
-    return finish(hnswgpu::exact_graph(*dev, idx->flat->origin_id, true, point_ids, np, k, allowed_ids, n_allowed, out_ids, out_dists, out_layer, out_rank,
-                                       out_counts, nullptr, err),
-                  err);
+    return graph_pair(idx, GraphCallArgs{point_ids, np, k, 0, allowed_ids, n_allowed, out_ids, out_dists, out_layer, out_rank, out_counts}, true, true,
+                      nullptr);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
-int hnswgpu_exact_graph_batch_device(const hnswgpu_index* cidx, const uint64_t* d_point_ids, uint64_t np, uint64_t k, const uint64_t* d_allowed_ids,
+int hnswgpu_exact_graph_batch_device(const hnswgpu_index* idx, const uint64_t* d_point_ids, uint64_t np, uint64_t k, const uint64_t* d_allowed_ids,
                                      uint64_t n_allowed, uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank,
                                      uint32_t* d_out_counts, void* stream) {
     CAPI_GUARD_BEGIN
-    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
-    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    std::shared_lock<std::shared_mutex> sl(idx->mu);
-    int rc = graph_call(idx, d_point_ids, np, k, true, d_allowed_ids, n_allowed, d_out_ids, d_out_dists, d_out_counts);
-    if (rc != HNSWGPU_OK) return rc;
-    DeviceIndex* dev = nullptr;
-    rc = graph_device_replica(idx, np, hnswgpu::exact_graph != nullptr, &dev);
-    if (rc != HNSWGPU_OK || !dev) return rc;
-    std::string err;
-    return finish(hnswgpu::exact_graph(*dev, idx->flat->origin_id, false, d_point_ids, np, k, d_allowed_ids, n_allowed, d_out_ids, d_out_dists, d_out_layer,
-                                       d_out_rank, d_out_counts, stream, err),
-                  err);
+    return graph_pair(idx, GraphCallArgs{d_point_ids, np, k, 0, d_allowed_ids, n_allowed, d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts},
+                      true, false, stream);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
 // ---- approximate range search: the graph's answers cut at a radius, ef doubled until the result set reaches past the ball
 // (range_search.hip holds the device side)
-extern "C++" {
-namespace hnswgpu {
-__attribute__((weak)) int range_search_host(DeviceIndex&, const RangeSearchArgs&, std::string&);
-__attribute__((weak)) int range_search_device(DeviceIndex*, const RangeSearchArgs&, void*, std::string&);
-}  // namespace hnswgpu
-}  // extern "C++"
-// the checks both entries share; the handle's lock is held (shared)
+// the checks both forms share; the handle's lock is held (shared)
 static int range_search_call(const hnswgpu_index* idx, const RangeSearchArgs& a) {
     const uint64_t dim = index_dimension(idx);
     if (!a.out_offsets) return fail(HNSWGPU_ERR_ARG, "null out_offsets: the offsets are written by every call");
@@ -1142,63 +1074,55 @@ static int range_search_call(const hnswgpu_index* idx, const RangeSearchArgs& a)
     return HNSWGPU_OK;
 }
 
-int hnswgpu_range_search_batch(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, const float* radii, uint64_t ef_first,
-                               uint64_t ef_max, const uint64_t* allowed_ids, uint64_t n_allowed, uint64_t cap, uint64_t* out_offsets, uint64_t* out_ids,
-                               float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_ef, uint8_t* out_flags) {
-    CAPI_GUARD_BEGIN
+static int range_search_pair(const hnswgpu_index* cidx, const RangeSearchArgs& a, bool host, void* stream) {
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
     std::shared_lock<std::shared_mutex> sl(idx->mu);
-    const RangeSearchArgs a{queries, radii, nq, d, ef_first, ef_max, allowed_ids, n_allowed, allowed_ids != nullptr, cap, out_offsets, out_ids, out_dists,
-                            out_layer, out_rank, out_ef, out_flags};
     int rc = range_search_call(idx, a);
     if (rc != HNSWGPU_OK) return rc;
-    rc = check_sorted_filter(allowed_ids, n_allowed);
-    if (rc != HNSWGPU_OK) return rc;
-    if (index_empty(idx) || nq == 0) {  // no point, or no query: every answer is empty
-        std::memset(out_offsets, 0, (nq + 1) * sizeof(uint64_t));
-        if (out_ef && nq != 0) std::memset(out_ef, 0, nq * sizeof(uint32_t));
-        if (out_flags && nq != 0) std::memset(out_flags, 0, nq);
-        return HNSWGPU_OK;
+    const bool nothing = index_empty(idx) || a.nq == 0;  // no point, or no query: every answer is empty
+    if (host) {
+        rc = check_sorted_filter(a.allowed, a.n_allowed);
+        if (rc != HNSWGPU_OK) return rc;
+        if (nothing) {
+            std::memset(a.out_offsets, 0, (a.nq + 1) * sizeof(uint64_t));
+            if (a.out_ef && a.nq != 0) std::memset(a.out_ef, 0, a.nq * sizeof(uint32_t));
+            if (a.out_flags && a.nq != 0) std::memset(a.out_flags, 0, a.nq);
+            return HNSWGPU_OK;
+        }
     }
-    if (!hnswgpu::range_search_host) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    DeviceIndex* dev = nullptr;
-    rc = primary_replica(idx, sl, &dev);
-    if (rc != HNSWGPU_OK) return rc;
+    if (!hnswgpu::range_search) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;  // (stays so in the device form where there is nothing to answer: the offsets are zeroed on the caller's stream)
+    if (!nothing) {
+        rc = call_replica(idx, sl, host, false, true, &dev);
+        if (rc != HNSWGPU_OK) return rc;
+    }
     std::string err;
-    return finish(hnswgpu::range_search_host(*dev, a, err), err);
+    return finish(hnswgpu::range_search(dev, a, host, stream, err), err);
+}
+
+int hnswgpu_range_search_batch(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, const float* radii, uint64_t ef_first,
+                               uint64_t ef_max, const uint64_t* allowed_ids, uint64_t n_allowed, uint64_t cap, uint64_t* out_offsets, uint64_t* out_ids,
+                               float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_ef, uint8_t* out_flags) {
+    CAPI_GUARD_BEGIN
+    const RangeSearchArgs a{queries, radii, nq, d, ef_first, ef_max, allowed_ids, n_allowed, allowed_ids != nullptr, cap, out_offsets, out_ids, out_dists,
+                            out_layer, out_rank, out_ef, out_flags};
+    return range_search_pair(idx, a, true, nullptr);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
-int hnswgpu_range_search_batch_device(const hnswgpu_index* cidx, const float* d_queries, uint64_t nq, uint64_t d, const float* d_radii,
+int hnswgpu_range_search_batch_device(const hnswgpu_index* idx, const float* d_queries, uint64_t nq, uint64_t d, const float* d_radii,
                                       uint64_t ef_first, uint64_t ef_max, const uint64_t* d_allowed_ids, uint64_t n_allowed, uint64_t cap,
                                       uint64_t* d_out_offsets, uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank,
                                       uint32_t* d_out_ef, uint8_t* d_out_flags, void* stream) {
     CAPI_GUARD_BEGIN
-    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
-    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    std::shared_lock<std::shared_mutex> sl(idx->mu);
     const RangeSearchArgs a{d_queries, d_radii, nq, d, ef_first, ef_max, d_allowed_ids, n_allowed, d_allowed_ids != nullptr, cap, d_out_offsets, d_out_ids,
                             d_out_dists, d_out_layer, d_out_rank, d_out_ef, d_out_flags};
-    int rc = range_search_call(idx, a);
-    if (rc != HNSWGPU_OK) return rc;
-    if (!hnswgpu::range_search_device) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    std::string err;
-    DeviceIndex* dev = nullptr;  // (stays so where there is no point, or no query: the offsets are zeroed on the caller's stream)
-    if (!index_empty(idx) && nq != 0) {
-        rc = resident_replica(idx, true, &dev);
-        if (rc != HNSWGPU_OK) return rc;
-    }
-    return finish(hnswgpu::range_search_device(dev, a, stream, err), err);
+    return range_search_pair(idx, a, false, stream);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
 // ---- the k-NN graph of the indexed points made undirected, in CSR (symmetric_graph.hip holds the device side)
-extern "C++" {
-namespace hnswgpu {
-__attribute__((weak)) int symmetric_graph(DeviceIndex*, const std::vector<uint64_t>&, const SymGraphArgs&, bool, void*, std::string&);
-}  // namespace hnswgpu
-}  // extern "C++"
 // The checks of the directed graph D that the symmetrised graph and the components share, in two halves (the symmetrised graph
 // looks at its capacity in between); the handle's lock is held (shared).  What the source call of D refuses is refused here.
 static int directed_graph_shape(uint64_t k, uint32_t mode) {
@@ -1218,7 +1142,7 @@ static int directed_graph_source(const hnswgpu_index* idx, const char* what, uin
         return fail(HNSWGPU_ERR_ARG, "exact graph answers in the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
     return capi_refuse_f16(idx, "exact graph");
 }
-// the checks both entries share
+// the checks both forms share
 static int symmetric_graph_call(const hnswgpu_index* idx, const SymGraphArgs& a) {
     if (!a.out_offsets) return fail(HNSWGPU_ERR_ARG, "null out_offsets: the offsets are written by every call");
     const int rc = directed_graph_shape(a.k, a.mode);
@@ -1228,57 +1152,44 @@ static int symmetric_graph_call(const hnswgpu_index* idx, const SymGraphArgs& a)
     return directed_graph_source(idx, "symmetric graph", a.k, a.ef);
 }
 
-int hnswgpu_symmetric_graph(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t cap, uint64_t* out_offsets, uint32_t* out_pos,
-                            uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank) {
-    CAPI_GUARD_BEGIN
+static int symmetric_graph_pair(const hnswgpu_index* cidx, const SymGraphArgs& a, bool host, void* stream) {
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
     std::shared_lock<std::shared_mutex> sl(idx->mu);
-    const SymGraphArgs a{k, ef, mode, cap, out_offsets, out_pos, out_ids, out_dists, out_layer, out_rank};
     int rc = symmetric_graph_call(idx, a);
     if (rc != HNSWGPU_OK) return rc;
     const uint64_t n = index_nb_point(idx);
-    if (n <= 1) {  // no point, or one: no edge
-        std::memset(out_offsets, 0, (n + 1) * sizeof(uint64_t));
+    if (host && n <= 1) {  // no point, or one: no edge
+        std::memset(a.out_offsets, 0, (n + 1) * sizeof(uint64_t));
         return HNSWGPU_OK;
     }
     if (!hnswgpu::symmetric_graph) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    DeviceIndex* dev = nullptr;
-    rc = primary_f32_replica(idx, sl, &dev);
-    if (rc != HNSWGPU_OK) return rc;
     std::string err;
-    return finish(hnswgpu::symmetric_graph(dev, idx->flat->origin_id, a, true, nullptr, err), err);
+    static const std::vector<uint64_t> no_ids;
+    if (n == 0)  // (the device form) no point: the one offset is zeroed on the caller's stream
+        return finish(hnswgpu::symmetric_graph(nullptr, no_ids, a, false, stream, err), err);
+    DeviceIndex* dev = nullptr;
+    rc = call_replica(idx, sl, host, true, true, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    return finish(hnswgpu::symmetric_graph(dev, idx->flat->origin_id, a, host, stream, err), err);
+}
+
+int hnswgpu_symmetric_graph(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t cap, uint64_t* out_offsets, uint32_t* out_pos,
+                            uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank) {
+    CAPI_GUARD_BEGIN
+    return symmetric_graph_pair(idx, SymGraphArgs{k, ef, mode, cap, out_offsets, out_pos, out_ids, out_dists, out_layer, out_rank}, true, nullptr);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
-int hnswgpu_symmetric_graph_device(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t cap, uint64_t* d_out_offsets,
+int hnswgpu_symmetric_graph_device(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t cap, uint64_t* d_out_offsets,
                                    uint32_t* d_out_pos, uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, void* stream) {
     CAPI_GUARD_BEGIN
-    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
-    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    std::shared_lock<std::shared_mutex> sl(idx->mu);
-    const SymGraphArgs a{k, ef, mode, cap, d_out_offsets, d_out_pos, d_out_ids, d_out_dists, d_out_layer, d_out_rank};
-    int rc = symmetric_graph_call(idx, a);
-    if (rc != HNSWGPU_OK) return rc;
-    if (!hnswgpu::symmetric_graph) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    std::string err;
-    static const std::vector<uint64_t> no_ids;
-    if (index_empty(idx))  // no point: the one offset is zeroed on the caller's stream
-        return finish(hnswgpu::symmetric_graph(nullptr, no_ids, a, false, stream, err), err);
-    DeviceIndex* dev = nullptr;
-    rc = resident_replica(idx, true, &dev);
-    if (rc != HNSWGPU_OK) return rc;
-    return finish(hnswgpu::symmetric_graph(dev, idx->flat->origin_id, a, false, stream, err), err);
+    return symmetric_graph_pair(idx, SymGraphArgs{k, ef, mode, cap, d_out_offsets, d_out_pos, d_out_ids, d_out_dists, d_out_layer, d_out_rank}, false,
+                                stream);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
 // ---- connected components: of the k-NN graph of the indexed points, and of any CSR (graph_components.hip holds the device side)
-extern "C++" {
-namespace hnswgpu {
-__attribute__((weak)) int graph_components(DeviceIndex&, const std::vector<uint64_t>&, const ComponentsArgs&, bool, void*, std::string&);
-__attribute__((weak)) int csr_components(const CsrComponentsArgs&, bool, void*, std::string&);
-}  // namespace hnswgpu
-}  // extern "C++"
 // what all four entries check of the answer's slots and of the cut (n: the number of vertices)
 static int components_answer_check(uint64_t n, const float* max_dist, const uint32_t* out_label, const uint64_t* out_n_components) {
     if (!out_n_components) return fail(HNSWGPU_ERR_ARG, "null out_n_components: the number of components is written by every call");
@@ -1286,23 +1197,17 @@ static int components_answer_check(uint64_t n, const float* max_dist, const uint
     if (max_dist && *max_dist != *max_dist) return fail(HNSWGPU_ERR_ARG, "max_dist is NaN: no distance compares to it (NULL is the call without a cut)");
     return HNSWGPU_OK;
 }
-// the checks both index entries share; the handle's lock is held (shared)
-static int graph_components_call(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, const float* max_dist, const uint32_t* out_label,
-                                 const uint64_t* out_n_components) {
+
+static int graph_components_pair(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, const float* max_dist, uint32_t* out_label,
+                                 uint32_t* out_sizes, uint64_t* out_n_components, bool host, void* stream) {
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
     int rc = components_answer_check(index_nb_point(idx), max_dist, out_label, out_n_components);
     if (rc != HNSWGPU_OK) return rc;
     rc = directed_graph_shape(k, mode);
     if (rc != HNSWGPU_OK) return rc;
-    return directed_graph_source(idx, "graph components", k, ef);
-}
-
-int hnswgpu_graph_components(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, const float* max_dist, uint32_t* out_label,
-                             uint32_t* out_sizes, uint64_t* out_n_components) {
-    CAPI_GUARD_BEGIN
-    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
-    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    std::shared_lock<std::shared_mutex> sl(idx->mu);
-    int rc = graph_components_call(idx, k, ef, mode, max_dist, out_label, out_n_components);
+    rc = directed_graph_source(idx, "graph components", k, ef);
     if (rc != HNSWGPU_OK) return rc;
     if (index_empty(idx)) {  // no vertex: no component, nothing else written
         *out_n_components = 0;
@@ -1310,45 +1215,25 @@ int hnswgpu_graph_components(const hnswgpu_index* cidx, uint64_t k, uint64_t ef,
     }
     if (!hnswgpu::graph_components) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     DeviceIndex* dev = nullptr;
-    rc = primary_f32_replica(idx, sl, &dev);
+    rc = call_replica(idx, sl, host, true, true, &dev);
     if (rc != HNSWGPU_OK) return rc;
     const ComponentsArgs a{k, ef, mode, max_dist != nullptr, max_dist ? *max_dist : 0.0f, out_label, out_sizes, out_n_components};
     std::string err;
-    return finish(hnswgpu::graph_components(*dev, idx->flat->origin_id, a, true, nullptr, err), err);
+    return finish(hnswgpu::graph_components(*dev, idx->flat->origin_id, a, host, stream, err), err);
+}
+
+int hnswgpu_graph_components(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, const float* max_dist, uint32_t* out_label,
+                             uint32_t* out_sizes, uint64_t* out_n_components) {
+    CAPI_GUARD_BEGIN
+    return graph_components_pair(idx, k, ef, mode, max_dist, out_label, out_sizes, out_n_components, true, nullptr);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
-int hnswgpu_graph_components_device(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, const float* max_dist, uint32_t* d_out_label,
+int hnswgpu_graph_components_device(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, const float* max_dist, uint32_t* d_out_label,
                                     uint32_t* d_out_sizes, uint64_t* out_n_components, void* stream) {
     CAPI_GUARD_BEGIN
-    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
-    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    std::shared_lock<std::shared_mutex> sl(idx->mu);
-    int rc = graph_components_call(idx, k, ef, mode, max_dist, d_out_label, out_n_components);
-    if (rc != HNSWGPU_OK) return rc;
-    if (index_empty(idx)) {
-        *out_n_components = 0;
-        return HNSWGPU_OK;
-    }
-    if (!hnswgpu::graph_components) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    DeviceIndex* dev = nullptr;
-    rc = resident_replica(idx, true, &dev);
-    if (rc != HNSWGPU_OK) return rc;
-    const ComponentsArgs a{k, ef, mode, max_dist != nullptr, max_dist ? *max_dist : 0.0f, d_out_label, d_out_sizes, out_n_components};
-    std::string err;
-    return finish(hnswgpu::graph_components(*dev, idx->flat->origin_id, a, false, stream, err), err);
+    return graph_components_pair(idx, k, ef, mode, max_dist, d_out_label, d_out_sizes, out_n_components, false, stream);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
-}
-
-// what both CSR entries can check without reading an array
-static int csr_components_call(uint64_t n, const void* offsets, const void* dists, const float* max_dist, const uint32_t* out_label,
-                               const uint64_t* out_n_components) {
-    const int rc = components_answer_check(n, max_dist, out_label, out_n_components);
-    if (rc != HNSWGPU_OK) return rc;
-    if (n > 0x7FFFFFFFull) return fail(HNSWGPU_ERR_ARG, "csr components: n = " + std::to_string(n) + " vertices, above 2^31 - 1");
-    if (n != 0 && !offsets) return fail(HNSWGPU_ERR_ARG, "null offsets");
-    if (max_dist && !dists) return fail(HNSWGPU_ERR_ARG, "max_dist without dists: a cut needs the entries' distances");
-    return HNSWGPU_OK;
 }
 
 // the graph itself as a host form reads it (n >= 1, offsets not NULL), as the device forms' validation kernels check it
@@ -1365,55 +1250,49 @@ static int csr_graph_check(const char* what, uint64_t n, const uint64_t* offsets
     return HNSWGPU_OK;
 }
 
-int hnswgpu_csr_components(int device, uint64_t n, const uint64_t* offsets, const uint32_t* cols, const float* dists, const float* max_dist,
-                           uint32_t* out_label, uint32_t* out_sizes, uint64_t* out_n_components) {
-    CAPI_GUARD_BEGIN
-    int rc = csr_components_call(n, offsets, dists, max_dist, out_label, out_n_components);
+static int csr_components_pair(int device, uint64_t n, const uint64_t* offsets, const uint32_t* cols, const float* dists, const float* max_dist,
+                               uint32_t* out_label, uint32_t* out_sizes, uint64_t* out_n_components, bool host, void* stream) {
+    int rc = components_answer_check(n, max_dist, out_label, out_n_components);
     if (rc != HNSWGPU_OK) return rc;
+    if (n > 0x7FFFFFFFull) return fail(HNSWGPU_ERR_ARG, "csr components: n = " + std::to_string(n) + " vertices, above 2^31 - 1");
+    if (n != 0 && !offsets) return fail(HNSWGPU_ERR_ARG, "null offsets");
+    if (max_dist && !dists) return fail(HNSWGPU_ERR_ARG, "max_dist without dists: a cut needs the entries' distances");
     if (n == 0) {
         *out_n_components = 0;
         return HNSWGPU_OK;
     }
-    rc = csr_graph_check("csr components", n, offsets, cols);
-    if (rc != HNSWGPU_OK) return rc;
+    if (host) {  // (the device form's validation kernels read the graph)
+        rc = csr_graph_check("csr components", n, offsets, cols);
+        if (rc != HNSWGPU_OK) return rc;
+    }
     if (!hnswgpu::csr_components) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     const CsrComponentsArgs a{device, n, offsets, cols, dists, max_dist != nullptr, max_dist ? *max_dist : 0.0f, out_label, out_sizes, out_n_components};
     std::string err;
-    return finish(hnswgpu::csr_components(a, true, nullptr, err), err);
+    return finish(hnswgpu::csr_components(a, host, stream, err), err);
+}
+
+int hnswgpu_csr_components(int device, uint64_t n, const uint64_t* offsets, const uint32_t* cols, const float* dists, const float* max_dist,
+                           uint32_t* out_label, uint32_t* out_sizes, uint64_t* out_n_components) {
+    CAPI_GUARD_BEGIN
+    return csr_components_pair(device, n, offsets, cols, dists, max_dist, out_label, out_sizes, out_n_components, true, nullptr);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
 int hnswgpu_csr_components_device(int device, uint64_t n, const uint64_t* d_offsets, const uint32_t* d_cols, const float* d_dists, const float* max_dist,
                                   uint32_t* d_out_label, uint32_t* d_out_sizes, uint64_t* out_n_components, void* stream) {
     CAPI_GUARD_BEGIN
-    const int rc = csr_components_call(n, d_offsets, d_dists, max_dist, d_out_label, out_n_components);
-    if (rc != HNSWGPU_OK) return rc;
-    if (n == 0) {
-        *out_n_components = 0;
-        return HNSWGPU_OK;
-    }
-    if (!hnswgpu::csr_components) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    const CsrComponentsArgs a{device, n, d_offsets, d_cols, d_dists, max_dist != nullptr, max_dist ? *max_dist : 0.0f, d_out_label, d_out_sizes,
-                              out_n_components};
-    std::string err;
-    return finish(hnswgpu::csr_components(a, false, stream, err), err);
+    return csr_components_pair(device, n, d_offsets, d_cols, d_dists, max_dist, d_out_label, d_out_sizes, out_n_components, false, stream);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
 // ---- minimum spanning forest: of the k-NN graph of the indexed points, and of any CSR (spanning_forest.hip holds the device side)
-extern "C++" {
-namespace hnswgpu {
-__attribute__((weak)) int graph_spanning_forest(DeviceIndex&, const std::vector<uint64_t>&, const ForestArgs&, bool, void*, std::string&);
-__attribute__((weak)) int csr_spanning_forest(const CsrForestArgs&, bool, void*, std::string&);
-}  // namespace hnswgpu
-}  // extern "C++"
 // what all four entries check of the answer's slots (n: the number of vertices)
 static int forest_answer_check(uint64_t n, const void* out_a, const void* out_b, const void* out_w, const uint64_t* out_n_edges) {
     if (!out_n_edges) return fail(HNSWGPU_ERR_ARG, "null out_n_edges: the number of edges is written by every call");
     if (n >= 2 && (!out_a || !out_b || !out_w)) return fail(HNSWGPU_ERR_ARG, "null out_a, out_b or out_w");
     return HNSWGPU_OK;
 }
-// the checks both index entries share; the handle's lock is held (shared)
+// the checks the index entries share; the handle's lock is held (shared)
 // (the part behind the answer's slots: what hnswhdb_graph, whose forest arrays are optional, checks too)
 static int graph_spanning_forest_source(const hnswgpu_index* idx, const ForestArgs& a) {
     const int rc = directed_graph_shape(a.k, a.mode);
@@ -1428,206 +1307,157 @@ static int graph_spanning_forest_call(const hnswgpu_index* idx, const ForestArgs
     return graph_spanning_forest_source(idx, a);
 }
 
-int hnswgpu_graph_spanning_forest(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k, uint32_t* out_a, uint32_t* out_b,
-                                  float* out_w, uint64_t* out_n_edges) {
-    CAPI_GUARD_BEGIN
+static int graph_spanning_forest_pair(const hnswgpu_index* cidx, const ForestArgs& a, bool host, void* stream) {
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
     std::shared_lock<std::shared_mutex> sl(idx->mu);
-    const ForestArgs a{k, ef, mode, core_k, out_a, out_b, out_w, out_n_edges};
     int rc = graph_spanning_forest_call(idx, a);
     if (rc != HNSWGPU_OK) return rc;
     if (index_nb_point(idx) <= 1) {  // no vertex, or one: no edge, nothing else written
-        *out_n_edges = 0;
+        *a.out_n = 0;
         return HNSWGPU_OK;
     }
     if (!hnswgpu::graph_spanning_forest) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     DeviceIndex* dev = nullptr;
-    rc = primary_f32_replica(idx, sl, &dev);
+    rc = call_replica(idx, sl, host, true, true, &dev);
     if (rc != HNSWGPU_OK) return rc;
     std::string err;
-    return finish(hnswgpu::graph_spanning_forest(*dev, idx->flat->origin_id, a, true, nullptr, err), err);
+    return finish(hnswgpu::graph_spanning_forest(*dev, idx->flat->origin_id, a, host, stream, err), err);
+}
+
+int hnswgpu_graph_spanning_forest(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k, uint32_t* out_a, uint32_t* out_b,
+                                  float* out_w, uint64_t* out_n_edges) {
+    CAPI_GUARD_BEGIN
+    return graph_spanning_forest_pair(idx, ForestArgs{k, ef, mode, core_k, out_a, out_b, out_w, out_n_edges}, true, nullptr);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
-int hnswgpu_graph_spanning_forest_device(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k, uint32_t* d_out_a,
+int hnswgpu_graph_spanning_forest_device(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k, uint32_t* d_out_a,
                                          uint32_t* d_out_b, float* d_out_w, uint64_t* out_n_edges, void* stream) {
     CAPI_GUARD_BEGIN
-    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
-    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    std::shared_lock<std::shared_mutex> sl(idx->mu);
-    const ForestArgs a{k, ef, mode, core_k, d_out_a, d_out_b, d_out_w, out_n_edges};
-    int rc = graph_spanning_forest_call(idx, a);
-    if (rc != HNSWGPU_OK) return rc;
-    if (index_nb_point(idx) <= 1) {
-        *out_n_edges = 0;
-        return HNSWGPU_OK;
-    }
-    if (!hnswgpu::graph_spanning_forest) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    DeviceIndex* dev = nullptr;
-    rc = resident_replica(idx, true, &dev);
-    if (rc != HNSWGPU_OK) return rc;
-    std::string err;
-    return finish(hnswgpu::graph_spanning_forest(*dev, idx->flat->origin_id, a, false, stream, err), err);
+    return graph_spanning_forest_pair(idx, ForestArgs{k, ef, mode, core_k, d_out_a, d_out_b, d_out_w, out_n_edges}, false, stream);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
-// what both CSR entries can check without reading an array
-static int csr_spanning_forest_call(const CsrForestArgs& a) {
-    const int rc = forest_answer_check(a.n, a.out_a, a.out_b, a.out_w, a.out_n);
+static int csr_spanning_forest_pair(const CsrForestArgs& a, bool host, void* stream) {
+    int rc = forest_answer_check(a.n, a.out_a, a.out_b, a.out_w, a.out_n);
     if (rc != HNSWGPU_OK) return rc;
     if (a.n > 0x7FFFFFFFull) return fail(HNSWGPU_ERR_ARG, "csr spanning forest: n = " + std::to_string(a.n) + " vertices, above 2^31 - 1");
     if (a.n != 0 && !a.offsets) return fail(HNSWGPU_ERR_ARG, "null offsets");
-    return HNSWGPU_OK;
+    if (a.n <= 1) {  // no vertex, or one: no edge (a self-loop is none); no array is read
+        *a.out_n = 0;
+        return HNSWGPU_OK;
+    }
+    if (host) {  // (the device form's validation kernels read the graph)
+        rc = csr_graph_check("csr spanning forest", a.n, a.offsets, a.cols);
+        if (rc != HNSWGPU_OK) return rc;
+    }
+    if (!hnswgpu::csr_spanning_forest) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    std::string err;
+    return finish(hnswgpu::csr_spanning_forest(a, host, stream, err), err);
 }
 
 int hnswgpu_csr_spanning_forest(int device, uint64_t n, const uint64_t* offsets, const uint32_t* cols, const float* dists, uint32_t* out_a, uint32_t* out_b,
                                 float* out_w, uint64_t* out_n_edges) {
     CAPI_GUARD_BEGIN
-    const CsrForestArgs a{device, n, offsets, cols, dists, out_a, out_b, out_w, out_n_edges};
-    int rc = csr_spanning_forest_call(a);
-    if (rc != HNSWGPU_OK) return rc;
-    if (n <= 1) {  // no vertex, or one: no edge (a self-loop is none); no array is read
-        *out_n_edges = 0;
-        return HNSWGPU_OK;
-    }
-    rc = csr_graph_check("csr spanning forest", n, offsets, cols);
-    if (rc != HNSWGPU_OK) return rc;
-    if (!hnswgpu::csr_spanning_forest) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    std::string err;
-    return finish(hnswgpu::csr_spanning_forest(a, true, nullptr, err), err);
+    return csr_spanning_forest_pair(CsrForestArgs{device, n, offsets, cols, dists, out_a, out_b, out_w, out_n_edges}, true, nullptr);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
 int hnswgpu_csr_spanning_forest_device(int device, uint64_t n, const uint64_t* d_offsets, const uint32_t* d_cols, const float* d_dists, uint32_t* d_out_a,
                                        uint32_t* d_out_b, float* d_out_w, uint64_t* out_n_edges, void* stream) {
     CAPI_GUARD_BEGIN
-    const CsrForestArgs a{device, n, d_offsets, d_cols, d_dists, d_out_a, d_out_b, d_out_w, out_n_edges};
-    const int rc = csr_spanning_forest_call(a);
-    if (rc != HNSWGPU_OK) return rc;
-    if (n <= 1) {
-        *out_n_edges = 0;
-        return HNSWGPU_OK;
-    }
-    if (!hnswgpu::csr_spanning_forest) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    std::string err;
-    return finish(hnswgpu::csr_spanning_forest(a, false, stream, err), err);
+    return csr_spanning_forest_pair(CsrForestArgs{device, n, d_offsets, d_cols, d_dists, d_out_a, d_out_b, d_out_w, out_n_edges}, false, stream);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
 // ---- dendrogram: of a forest given as an edge list, and of the k-NN graph's own forest (dendrogram.hip holds the device side)
-extern "C++" {
-namespace hnswgpu {
-__attribute__((weak)) int forest_dendrogram(const DendrogramArgs&, bool, void*, std::string&);
-__attribute__((weak)) int graph_dendrogram(DeviceIndex&, const std::vector<uint64_t>&, const GraphDendrogramArgs&, bool, void*, std::string&);
-}  // namespace hnswgpu
-}  // extern "C++"
-// what both forest entries can check without reading an array
-static int forest_dendrogram_call(const DendrogramArgs& a) {
-    if (a.n > 0x7FFFFFFFull) return fail(HNSWGPU_ERR_ARG, "forest dendrogram: n = " + std::to_string(a.n) + " vertices, above 2^31 - 1");
-    if (a.m > std::max<uint64_t>(a.n, 1) - 1)
-        return fail(HNSWGPU_ERR_ARG, "forest dendrogram: m = " + std::to_string(a.m) + " edges among n = " + std::to_string(a.n) +
+// A forest given as an edge list, for the dendrogram and for HDBSCAN, which speaks of it in the dendrogram's words: its shape ...
+static int forest_shape_check(uint64_t n, uint64_t m) {
+    if (n > 0x7FFFFFFFull) return fail(HNSWGPU_ERR_ARG, "forest dendrogram: n = " + std::to_string(n) + " vertices, above 2^31 - 1");
+    if (m > std::max<uint64_t>(n, 1) - 1)
+        return fail(HNSWGPU_ERR_ARG, "forest dendrogram: m = " + std::to_string(m) + " edges among n = " + std::to_string(n) +
                                          " vertices: a forest has at most n - 1");
-    if (a.m != 0 && (!a.a || !a.b)) return fail(HNSWGPU_ERR_ARG, "null a or b");
-    if (a.m != 0 && (!a.out_left || !a.out_right || !a.out_size)) return fail(HNSWGPU_ERR_ARG, "null out_left, out_right or out_size");
     return HNSWGPU_OK;
 }
-
-int hnswgpu_forest_dendrogram(int device, uint64_t n, uint64_t m, const uint32_t* a, const uint32_t* b, uint32_t* out_left, uint32_t* out_right,
-                              uint32_t* out_size) {
-    CAPI_GUARD_BEGIN
-    const DendrogramArgs args{device, n, m, a, b, out_left, out_right, out_size};
-    const int rc = forest_dendrogram_call(args);
-    if (rc != HNSWGPU_OK) return rc;
-    if (m == 0) return HNSWGPU_OK;  // no merge: no array is read or written
-    // the ends as the device form's kernel checks them (a cycle is the device's to find)
+// ... and its ends as a host form reads them, as the device form's kernel checks them (a cycle is the device's to find)
+static int forest_ends_check(uint64_t n, uint64_t m, const uint32_t* a, const uint32_t* b) {
     for (uint64_t e = 0; e < m; ++e) {
         if (a[e] >= n || b[e] >= n)
             return fail(HNSWGPU_ERR_ARG, "forest dendrogram: edge " + std::to_string(e) + " has an end that is not below n");
         if (a[e] == b[e]) return fail(HNSWGPU_ERR_ARG, "forest dendrogram: edge " + std::to_string(e) + " joins a vertex to itself");
     }
+    return HNSWGPU_OK;
+}
+
+static int forest_dendrogram_pair(const DendrogramArgs& a, bool host, void* stream) {
+    int rc = forest_shape_check(a.n, a.m);
+    if (rc != HNSWGPU_OK) return rc;
+    if (a.m != 0 && (!a.a || !a.b)) return fail(HNSWGPU_ERR_ARG, "null a or b");
+    if (a.m != 0 && (!a.out_left || !a.out_right || !a.out_size)) return fail(HNSWGPU_ERR_ARG, "null out_left, out_right or out_size");
+    if (a.m == 0) return HNSWGPU_OK;  // no merge: no array is read or written
+    if (host) {
+        rc = forest_ends_check(a.n, a.m, a.a, a.b);
+        if (rc != HNSWGPU_OK) return rc;
+    }
     if (!hnswgpu::forest_dendrogram) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     std::string err;
-    return finish(hnswgpu::forest_dendrogram(args, true, nullptr, err), err);
+    return finish(hnswgpu::forest_dendrogram(a, host, stream, err), err);
+}
+
+int hnswgpu_forest_dendrogram(int device, uint64_t n, uint64_t m, const uint32_t* a, const uint32_t* b, uint32_t* out_left, uint32_t* out_right,
+                              uint32_t* out_size) {
+    CAPI_GUARD_BEGIN
+    return forest_dendrogram_pair(DendrogramArgs{device, n, m, a, b, out_left, out_right, out_size}, true, nullptr);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
 int hnswgpu_forest_dendrogram_device(int device, uint64_t n, uint64_t m, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out_left,
                                      uint32_t* d_out_right, uint32_t* d_out_size, void* stream) {
     CAPI_GUARD_BEGIN
-    const DendrogramArgs args{device, n, m, d_a, d_b, d_out_left, d_out_right, d_out_size};
-    const int rc = forest_dendrogram_call(args);
-    if (rc != HNSWGPU_OK) return rc;
-    if (m == 0) return HNSWGPU_OK;
-    if (!hnswgpu::forest_dendrogram) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    std::string err;
-    return finish(hnswgpu::forest_dendrogram(args, false, stream, err), err);
+    return forest_dendrogram_pair(DendrogramArgs{device, n, m, d_a, d_b, d_out_left, d_out_right, d_out_size}, false, stream);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
-// the checks both index entries share: the forest call's own, then the three new arrays; the handle's lock is held (shared)
-static int graph_dendrogram_call(const hnswgpu_index* idx, const GraphDendrogramArgs& a) {
-    const int rc = graph_spanning_forest_call(idx, a.forest);
+static int graph_dendrogram_pair(const hnswgpu_index* cidx, const GraphDendrogramArgs& a, bool host, void* stream) {
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    int rc = graph_spanning_forest_call(idx, a.forest);  // the forest call's own checks, then the three new arrays
     if (rc != HNSWGPU_OK) return rc;
     if (index_nb_point(idx) >= 2 && (!a.out_left || !a.out_right || !a.out_size))
         return fail(HNSWGPU_ERR_ARG, "null out_left, out_right or out_size");
-    return HNSWGPU_OK;
-}
-
-int hnswgpu_graph_dendrogram(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k, uint32_t* out_a, uint32_t* out_b,
-                             float* out_w, uint32_t* out_left, uint32_t* out_right, uint32_t* out_size, uint64_t* out_n_edges) {
-    CAPI_GUARD_BEGIN
-    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
-    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    std::shared_lock<std::shared_mutex> sl(idx->mu);
-    const GraphDendrogramArgs a{ForestArgs{k, ef, mode, core_k, out_a, out_b, out_w, out_n_edges}, out_left, out_right, out_size};
-    int rc = graph_dendrogram_call(idx, a);
-    if (rc != HNSWGPU_OK) return rc;
     if (index_nb_point(idx) <= 1) {  // no vertex, or one: no edge, nothing else written
-        *out_n_edges = 0;
+        *a.forest.out_n = 0;
         return HNSWGPU_OK;
     }
     if (!hnswgpu::graph_dendrogram) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     DeviceIndex* dev = nullptr;
-    rc = primary_f32_replica(idx, sl, &dev);
+    rc = call_replica(idx, sl, host, true, true, &dev);
     if (rc != HNSWGPU_OK) return rc;
     std::string err;
-    return finish(hnswgpu::graph_dendrogram(*dev, idx->flat->origin_id, a, true, nullptr, err), err);
+    return finish(hnswgpu::graph_dendrogram(*dev, idx->flat->origin_id, a, host, stream, err), err);
+}
+
+int hnswgpu_graph_dendrogram(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k, uint32_t* out_a, uint32_t* out_b,
+                             float* out_w, uint32_t* out_left, uint32_t* out_right, uint32_t* out_size, uint64_t* out_n_edges) {
+    CAPI_GUARD_BEGIN
+    const GraphDendrogramArgs a{ForestArgs{k, ef, mode, core_k, out_a, out_b, out_w, out_n_edges}, out_left, out_right, out_size};
+    return graph_dendrogram_pair(idx, a, true, nullptr);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
-int hnswgpu_graph_dendrogram_device(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k, uint32_t* d_out_a,
+int hnswgpu_graph_dendrogram_device(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k, uint32_t* d_out_a,
                                     uint32_t* d_out_b, float* d_out_w, uint32_t* d_out_left, uint32_t* d_out_right, uint32_t* d_out_size,
                                     uint64_t* out_n_edges, void* stream) {
     CAPI_GUARD_BEGIN
-    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
-    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    std::shared_lock<std::shared_mutex> sl(idx->mu);
     const GraphDendrogramArgs a{ForestArgs{k, ef, mode, core_k, d_out_a, d_out_b, d_out_w, out_n_edges}, d_out_left, d_out_right, d_out_size};
-    int rc = graph_dendrogram_call(idx, a);
-    if (rc != HNSWGPU_OK) return rc;
-    if (index_nb_point(idx) <= 1) {
-        *out_n_edges = 0;
-        return HNSWGPU_OK;
-    }
-    if (!hnswgpu::graph_dendrogram) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    DeviceIndex* dev = nullptr;
-    rc = resident_replica(idx, true, &dev);
-    if (rc != HNSWGPU_OK) return rc;
-    std::string err;
-    return finish(hnswgpu::graph_dendrogram(*dev, idx->flat->origin_id, a, false, stream, err), err);
+    return graph_dendrogram_pair(idx, a, false, stream);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
 // ---- HDBSCAN: condensed tree, stabilities and flat clusters of a forest in merge order, and of the k-NN graph's own forest
 // (condensed_tree.hip holds the device side)
-extern "C++" {
-namespace hnswgpu {
-__attribute__((weak)) int forest_hdbscan(const ForestHdbscanArgs&, bool, void*, std::string&);
-__attribute__((weak)) int graph_hdbscan(DeviceIndex&, const std::vector<uint64_t>&, const GraphHdbscanArgs&, bool, void*, std::string&);
-}  // namespace hnswgpu
-}  // extern "C++"
-
 uint64_t hnswhdb_max_clusters(uint64_t n, uint64_t min_cluster_size) {
     if (min_cluster_size == 0) return 0;
     const uint64_t q = n / min_cluster_size;
@@ -1644,15 +1474,6 @@ static int hdbscan_answer_check(uint64_t n, uint64_t mcs, uint32_t method, const
     if (n != 0 && !o.labels) return fail(HNSWGPU_ERR_ARG, "null out_labels");
     return HNSWGPU_OK;
 }
-// what both forest entries can check without reading an array: the dendrogram's, in its words, then the clustering's
-static int forest_hdbscan_call(const ForestHdbscanArgs& a) {
-    if (a.n > 0x7FFFFFFFull) return fail(HNSWGPU_ERR_ARG, "forest dendrogram: n = " + std::to_string(a.n) + " vertices, above 2^31 - 1");
-    if (a.m > std::max<uint64_t>(a.n, 1) - 1)
-        return fail(HNSWGPU_ERR_ARG, "forest dendrogram: m = " + std::to_string(a.m) + " edges among n = " + std::to_string(a.n) +
-                                         " vertices: a forest has at most n - 1");
-    if (a.m != 0 && (!a.a || !a.b || !a.w)) return fail(HNSWGPU_ERR_ARG, "null a, b or w");
-    return hdbscan_answer_check(a.n, a.min_cluster_size, a.method, a.out);
-}
 // the order of the spanning forest's weights (graph_internal.hpp: dist_order_bits), on the host
 static uint32_t weight_order_bits(float v) {
     uint32_t b;
@@ -1660,6 +1481,30 @@ static uint32_t weight_order_bits(float v) {
     if (v != v) return 0xFFFFFFFFu;
     if (b == 0x80000000u) b = 0u;
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+static int forest_hdbscan_pair(const ForestHdbscanArgs& a, bool host, void* stream) {
+    int rc = forest_shape_check(a.n, a.m);  // the dendrogram's checks, in its words, then the clustering's
+    if (rc != HNSWGPU_OK) return rc;
+    if (a.m != 0 && (!a.a || !a.b || !a.w)) return fail(HNSWGPU_ERR_ARG, "null a, b or w");
+    rc = hdbscan_answer_check(a.n, a.min_cluster_size, a.method, a.out);
+    if (rc != HNSWGPU_OK) return rc;
+    if (a.n == 0) {  // no vertex: the two counts, no array is read or written
+        *a.out.n_clusters = 0;
+        *a.out.n_labels = 0;
+        return HNSWGPU_OK;
+    }
+    if (host) {  // the ends as the dendrogram's kernel checks them, the weights as this call's kernel does
+        rc = forest_ends_check(a.n, a.m, a.a, a.b);
+        if (rc != HNSWGPU_OK) return rc;
+        for (uint64_t e = 1; e < a.m; ++e)
+            if (weight_order_bits(a.w[e - 1]) > weight_order_bits(a.w[e]))
+                return fail(HNSWGPU_ERR_ARG, "forest hdbscan: the weights descend at edge " + std::to_string(e) +
+                                                 ": the edges' order is the merge order, ascending by weight");
+    }
+    if (!hnswgpu::forest_hdbscan) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    std::string err;
+    return finish(hnswgpu::forest_hdbscan(a, host, stream, err), err);
 }
 
 int hnswhdb_forest(int device, uint64_t n, uint64_t m, const uint32_t* a, const uint32_t* b, const float* w, uint64_t min_cluster_size,
@@ -1670,26 +1515,7 @@ int hnswhdb_forest(int device, uint64_t n, uint64_t m, const uint32_t* a, const 
     const ForestHdbscanArgs args{device, n, m, a, b, w, min_cluster_size, method,
                                  HdbscanOut{out_labels, out_prob, out_point_cluster, out_point_w, out_cluster_parent, out_cluster_birth_w,
                                             out_cluster_size, out_stability, out_selected, out_n_clusters, out_n_labels}};
-    const int rc = forest_hdbscan_call(args);
-    if (rc != HNSWGPU_OK) return rc;
-    if (n == 0) {  // no vertex: the two counts, no array is read or written
-        *out_n_clusters = 0;
-        *out_n_labels = 0;
-        return HNSWGPU_OK;
-    }
-    // the ends as the dendrogram's kernel checks them, the weights as this call's kernel does (a cycle is the device's to find)
-    for (uint64_t e = 0; e < m; ++e) {
-        if (a[e] >= n || b[e] >= n)
-            return fail(HNSWGPU_ERR_ARG, "forest dendrogram: edge " + std::to_string(e) + " has an end that is not below n");
-        if (a[e] == b[e]) return fail(HNSWGPU_ERR_ARG, "forest dendrogram: edge " + std::to_string(e) + " joins a vertex to itself");
-    }
-    for (uint64_t e = 1; e < m; ++e)
-        if (weight_order_bits(w[e - 1]) > weight_order_bits(w[e]))
-            return fail(HNSWGPU_ERR_ARG, "forest hdbscan: the weights descend at edge " + std::to_string(e) +
-                                             ": the edges' order is the merge order, ascending by weight");
-    if (!hnswgpu::forest_hdbscan) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    std::string err;
-    return finish(hnswgpu::forest_hdbscan(args, true, nullptr, err), err);
+    return forest_hdbscan_pair(args, true, nullptr);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
@@ -1702,80 +1528,57 @@ int hnswhdb_forest_device(int device, uint64_t n, uint64_t m, const uint32_t* d_
     const ForestHdbscanArgs args{device, n, m, d_a, d_b, d_w, min_cluster_size, method,
                                  HdbscanOut{d_out_labels, d_out_prob, d_out_point_cluster, d_out_point_w, d_out_cluster_parent,
                                             d_out_cluster_birth_w, d_out_cluster_size, d_out_stability, d_out_selected, out_n_clusters, out_n_labels}};
-    const int rc = forest_hdbscan_call(args);
-    if (rc != HNSWGPU_OK) return rc;
-    if (n == 0) {
-        *out_n_clusters = 0;
-        *out_n_labels = 0;
-        return HNSWGPU_OK;
-    }
-    if (!hnswgpu::forest_hdbscan) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    std::string err;
-    return finish(hnswgpu::forest_hdbscan(args, false, stream, err), err);
+    return forest_hdbscan_pair(args, false, stream);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
-// the checks both index entries share: the dendrogram call's own in its words -- the six arrays of the forest and the dendrogram are
-// optional here --, then the clustering's; the handle's lock is held (shared)
-static int graph_hdbscan_call(const hnswgpu_index* idx, const GraphHdbscanArgs& a) {
+static int graph_hdbscan_pair(const hnswgpu_index* cidx, const GraphHdbscanArgs& a, bool host, void* stream) {
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    // the dendrogram call's own checks in its words -- the six arrays of the forest and the dendrogram are optional here --, then the
+    // clustering's
     if (!a.forest.out_n) return fail(HNSWGPU_ERR_ARG, "null out_n_edges: the number of edges is written by every call");
-    const int rc = graph_spanning_forest_source(idx, a.forest);
+    int rc = graph_spanning_forest_source(idx, a.forest);
     if (rc != HNSWGPU_OK) return rc;
-    return hdbscan_answer_check(index_nb_point(idx), a.min_cluster_size, a.method, a.out);
+    rc = hdbscan_answer_check(index_nb_point(idx), a.min_cluster_size, a.method, a.out);
+    if (rc != HNSWGPU_OK) return rc;
+    if (index_empty(idx)) {  // no vertex: the three counts, nothing else written
+        *a.forest.out_n = *a.out.n_clusters = *a.out.n_labels = 0;
+        return HNSWGPU_OK;
+    }
+    if (!hnswgpu::graph_hdbscan) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = call_replica(idx, sl, host, true, true, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    return finish(hnswgpu::graph_hdbscan(*dev, idx->flat->origin_id, a, host, stream, err), err);
 }
 
-int hnswhdb_graph(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k, uint64_t min_cluster_size, uint32_t method,
+int hnswhdb_graph(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k, uint64_t min_cluster_size, uint32_t method,
                           uint32_t* out_a, uint32_t* out_b, float* out_w, uint32_t* out_left, uint32_t* out_right, uint32_t* out_size,
                           int32_t* out_labels, float* out_prob, uint32_t* out_point_cluster, float* out_point_w, uint32_t* out_cluster_parent,
                           float* out_cluster_birth_w, uint32_t* out_cluster_size, double* out_stability, uint8_t* out_selected,
                           uint64_t* out_n_clusters, uint64_t* out_n_labels, uint64_t* out_n_edges) {
     CAPI_GUARD_BEGIN
-    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
-    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    std::shared_lock<std::shared_mutex> sl(idx->mu);
     const GraphHdbscanArgs a{ForestArgs{k, ef, mode, core_k, out_a, out_b, out_w, out_n_edges}, out_left, out_right, out_size, min_cluster_size, method,
                              HdbscanOut{out_labels, out_prob, out_point_cluster, out_point_w, out_cluster_parent, out_cluster_birth_w,
                                         out_cluster_size, out_stability, out_selected, out_n_clusters, out_n_labels}};
-    int rc = graph_hdbscan_call(idx, a);
-    if (rc != HNSWGPU_OK) return rc;
-    if (index_nb_point(idx) == 0) {  // no vertex: the three counts, nothing else written
-        *out_n_edges = *out_n_clusters = *out_n_labels = 0;
-        return HNSWGPU_OK;
-    }
-    if (!hnswgpu::graph_hdbscan) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    DeviceIndex* dev = nullptr;
-    rc = primary_f32_replica(idx, sl, &dev);
-    if (rc != HNSWGPU_OK) return rc;
-    std::string err;
-    return finish(hnswgpu::graph_hdbscan(*dev, idx->flat->origin_id, a, true, nullptr, err), err);
+    return graph_hdbscan_pair(idx, a, true, nullptr);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
-int hnswhdb_graph_device(const hnswgpu_index* cidx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k, uint64_t min_cluster_size,
+int hnswhdb_graph_device(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint32_t mode, uint64_t core_k, uint64_t min_cluster_size,
                                  uint32_t method, uint32_t* d_out_a, uint32_t* d_out_b, float* d_out_w, uint32_t* d_out_left, uint32_t* d_out_right,
                                  uint32_t* d_out_size, int32_t* d_out_labels, float* d_out_prob, uint32_t* d_out_point_cluster, float* d_out_point_w,
                                  uint32_t* d_out_cluster_parent, float* d_out_cluster_birth_w, uint32_t* d_out_cluster_size, double* d_out_stability,
                                  uint8_t* d_out_selected, uint64_t* out_n_clusters, uint64_t* out_n_labels, uint64_t* out_n_edges, void* stream) {
     CAPI_GUARD_BEGIN
-    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
-    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
-    std::shared_lock<std::shared_mutex> sl(idx->mu);
     const GraphHdbscanArgs a{ForestArgs{k, ef, mode, core_k, d_out_a, d_out_b, d_out_w, out_n_edges}, d_out_left, d_out_right, d_out_size,
                              min_cluster_size, method,
                              HdbscanOut{d_out_labels, d_out_prob, d_out_point_cluster, d_out_point_w, d_out_cluster_parent, d_out_cluster_birth_w,
                                         d_out_cluster_size, d_out_stability, d_out_selected, out_n_clusters, out_n_labels}};
-    int rc = graph_hdbscan_call(idx, a);
-    if (rc != HNSWGPU_OK) return rc;
-    if (index_nb_point(idx) == 0) {
-        *out_n_edges = *out_n_clusters = *out_n_labels = 0;
-        return HNSWGPU_OK;
-    }
-    if (!hnswgpu::graph_hdbscan) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
-    DeviceIndex* dev = nullptr;
-    rc = resident_replica(idx, true, &dev);
-    if (rc != HNSWGPU_OK) return rc;
-    std::string err;
-    return finish(hnswgpu::graph_hdbscan(*dev, idx->flat->origin_id, a, false, stream, err), err);
+    return graph_hdbscan_pair(idx, a, false, stream);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
@@ -1907,17 +1710,6 @@ int hnswgpu_eval_distance_matrix_arith(int dist, int arithmetic, const float* qu
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
-// Referred to weakly, like the filter-set, exact, range and graph entries: the host-only build of the C ABI (the sanitizer build, whose
-// stand-in for search_device.hip defines the device entries that existed when it was written, eval_distance_matrix_device among
-// them) links without it and answers "no device".
-extern "C++" {
-namespace hnswgpu {
-__attribute__((weak)) int eval_distance_matrix_storage_device(int, int, const float*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, float*,
-                                                              std::string&);
-__attribute__((weak)) int eval_distance_matrix_variant_device(int, int, int, const float*, uint64_t, const float*, uint64_t, uint64_t, uint32_t,
-                                                              float*, std::string&);
-}  // namespace hnswgpu
-}  // extern "C++"
 // the storage of an eval call's rows (the one place these are checked: the device side converts what it is handed)
 static int check_eval_storage(int dist, int storage, const float* rows, uint64_t n, uint64_t d) {
     if (storage != HNSWGPU_STORAGE_F32 && storage != HNSWGPU_STORAGE_F16) return fail(HNSWGPU_ERR_ARG, "unknown storage");

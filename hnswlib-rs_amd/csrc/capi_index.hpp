@@ -1,9 +1,13 @@
-// capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h (and its extension hnsw_mi355x_hdbscan.h), for the translation units
-// that implement entry points of the C ABI (capi.cpp; exact_knn.hip; range_search.hip; symmetric_graph.hip; graph_components.hip; spanning_forest.hip; dendrogram.hip; condensed_tree.hip).  Private: not installed, not part of the ABI.
-// The checks that entries share (empty index, resident replica, sorted filter, the shape and contents of a filter set, the limits of
-// an exact call, the zeroed k-NN answer, the tail) live once, in capi.cpp; what an entry outside capi.cpp needs of them is declared
-// below as capi_*.  A new pair of entries calls them.  The HIP host helpers of the .hip units (HIP_TRY, DeviceGuard, DevMem,
-// round_up) are in hip_host.hpp, which this header -- compiled by plain g++ too -- does not include.
+// capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h (and its extension hnsw_mi355x_hdbscan.h),
+// for the translation units that implement the C ABI: capi.cpp, which holds the entries, and the .hip units that hold their device
+// side (exact_knn.hip, which also holds hnswgpu_exact_search_batch(_device) itself; range_search.hip; symmetric_graph.hip;
+// graph_components.hip; spanning_forest.hip; dendrogram.hip; condensed_tree.hip).  Private: not installed, not part of the ABI.
+// Three parts: the handle; the checks that entries share (empty index, resident replica, sorted filter, the limits of an exact call,
+// the zeroed k-NN answer, the tail), which live once, in capi.cpp, and are declared here as capi_* for the entries outside it; and
+// the device side of every host / _device pair, declared ONCE, here, with its arguments' struct (HNSWGPU_DEVICE_SIDE of
+// search_device.hpp makes capi.cpp's references weak).  A pair of entries is one body in capi.cpp that calls both.  The HIP host
+// helpers of the .hip units (HIP_TRY, DeviceGuard, DevMem, round_up) are in hip_host.hpp, which this header -- compiled by plain g++
+// too -- does not include.
 #pragma once
 #include <exception>
 #include <map>
@@ -55,10 +59,9 @@ namespace hnswgpu {
 // defined in capi.cpp, for the entry points that live in other translation units:
 // sets the calling thread's hnswgpu_last_error() message and returns `code`
 int capi_fail(int code, const std::string& msg);
-// the replica a search on the primary device uses, uploaded first where need be (`sl`: the handle's lock, held shared)
-int capi_primary_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mutex>& sl, DeviceIndex** out);
-// the same for the entries that read rows outside the search path: HNSWGPU_ERR_ARG when the replica turns out to be a half one (the
-// index's storage was changed while the lock was given up for the upload)
+// the replica a call on the primary device uses, uploaded first where need be (`sl`: the handle's lock, held shared), for the entries
+// that read rows outside the search path: HNSWGPU_ERR_ARG when the replica turns out to be a half one (the index's storage was changed
+// while the lock was given up for the upload)
 int capi_primary_f32_replica(hnswgpu_index* idx, std::shared_lock<std::shared_mutex>& sl, DeviceIndex** out);
 // HNSWGPU_OK, or -- the index is set to HNSWGPU_STORAGE_F16 -- HNSWGPU_ERR_ARG with a message that names `what`: the calls that
 // read rows outside the search path (exact k-NN / range / graph, the stored-point queries) exist for f32 rows only
@@ -78,36 +81,63 @@ int capi_check_exact_call(const hnswgpu_index* idx, const void* queries, uint64_
                           const void* out_ids, const void* out_dists, const void* out_counts);
 // the k-NN answer of an index without a point: counts, ids, dists and (where given) layer and rank of nq rows zeroed
 void capi_zero_knn_answers(uint64_t nq, uint64_t k, uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts);
-// the device side of hnswgpu_exact_search_batch_filter_set(_device), defined in exact_knn.hip: the exact k-NN of every query q
-// under filter filter_of[q] of the set (the arguments have been checked).  capi.cpp refers to these two weakly, like the search's
-// own filter-set pair (search_device.hpp): a host-only build of the C ABI links without them and answers "no device".
-int exact_filter_set_host(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* queries, uint64_t nq, uint64_t d,
-                          uint64_t k, const FilterSet& set, uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank,
-                          uint32_t* out_counts, std::string& err);
-int exact_filter_set_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* d_queries, uint64_t nq, uint64_t d,
-                            uint64_t k, const FilterSet& d_set, uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer,
-                            int32_t* d_out_rank, uint32_t* d_out_counts, void* stream, std::string& err);
-// the device side of hnswgpu_exact_range_search_batch(_device), defined in exact_knn.hip and referred to weakly in the same way.
-// They return HNSWGPU_ERR_CAPACITY, the offsets complete and no out slot written, when the answers need more than cap slots.
-int exact_range_host(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* queries, uint64_t nq, uint64_t d,
-                     const float* radii, const uint64_t* allowed, uint64_t n_allowed, uint64_t cap, uint64_t* out_offsets, uint64_t* out_ids,
-                     float* out_dists, uint8_t* out_layer, int32_t* out_rank, std::string& err);
-int exact_range_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* d_queries, uint64_t nq, uint64_t d,
-                       const float* d_radii, const uint64_t* d_allowed, uint64_t n_allowed, uint64_t cap, uint64_t* d_out_offsets,
-                       uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, void* stream, std::string& err);
-// the device side of hnswgpu_graph_search_batch(_device) and hnswgpu_exact_graph_batch(_device), defined in exact_knn.hip and
-// referred to weakly in the same way.  host: every buffer (point_ids and allowed too) is plain host memory; else device memory
-// and `stream` is the caller's.  point_ids == nullptr: every point (np == the number of points, checked by the caller).  They
-// return ERR_ARG, nothing searched and no out slot written, when an id of point_ids names no point.
-int graph_search(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, bool host, const uint64_t* point_ids, uint64_t np, uint64_t k, uint64_t ef,
-                 uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts, void* stream, std::string& err);
-int exact_graph(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, bool host, const uint64_t* point_ids, uint64_t np, uint64_t k,
-                const uint64_t* allowed, uint64_t n_allowed, uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank,
-                uint32_t* out_counts, void* stream, std::string& err);
-// the device side of hnswgpu_range_search_batch(_device), defined in range_search.hip and referred to weakly in the same way: the
-// rounds of every group of queries through DeviceIndex::search_device (the arguments have been checked).  filtered: d_allowed /
-// allowed is a filter even when it is empty.  dev == nullptr (device entry on an empty index): the offsets are zeroed.  They return
-// HNSWGPU_ERR_CAPACITY, the offsets complete, when the answers need more than cap slots.
+
+// ---- The device side of the batched entries: what capi.cpp calls behind its argument checks, each defined in the .hip unit named.
+// One shape for all of them: (the replica and its DataIds, where the call reads an index; the call's arguments in a struct; host;
+// stream; err).  host: every buffer of the struct is plain host memory and `stream` is nullptr; else device memory and `stream` is
+// the caller's, waited for before the function returns.  The arguments have been checked.  Each declaration carries
+// HNSWGPU_DEVICE_SIDE (search_device.hpp): capi.cpp, and only capi.cpp, refers to these functions weakly.
+
+// hnswgpu_exact_search_batch_filter_set(_device), exact_knn.hip: the exact k-NN of every query q under filter filter_of[q] of the set
+struct ExactSetArgs {
+    const float* queries;  // nq x d
+    uint64_t nq, d, k;
+    FilterSet set;         // host: validated
+    uint64_t* out_ids;     // nq x k, like the three below
+    float* out_dists;
+    uint8_t* out_layer;    // may be nullptr
+    int32_t* out_rank;     // may be nullptr
+    uint32_t* out_counts;  // [nq]
+};
+HNSWGPU_DEVICE_SIDE int exact_filter_set(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ExactSetArgs& a, bool host, void* stream,
+                                         std::string& err);
+// hnswgpu_exact_range_search_batch(_device), exact_knn.hip.  Returns HNSWGPU_ERR_CAPACITY, the offsets complete and no out slot
+// written, when the answers need more than cap slots.
+struct ExactRangeCallArgs {
+    const float* queries;  // nq x d
+    const float* radii;    // [nq]
+    uint64_t nq, d;
+    const uint64_t* allowed;  // not nullptr: a filter, even when it is empty
+    uint64_t n_allowed;
+    uint64_t cap;
+    uint64_t* out_offsets;  // [nq + 1]
+    uint64_t* out_ids;      // cap slots each; may be nullptr with cap == 0, the count-only call
+    float* out_dists;
+    uint8_t* out_layer;     // may be nullptr
+    int32_t* out_rank;      // may be nullptr
+};
+HNSWGPU_DEVICE_SIDE int exact_range(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ExactRangeCallArgs& a, bool host, void* stream,
+                                    std::string& err);
+// hnswgpu_graph_search_batch(_device) and hnswgpu_exact_graph_batch(_device), exact_knn.hip.  They return ERR_ARG, nothing searched
+// and no out slot written, when an id of point_ids names no point.
+struct GraphCallArgs {
+    const uint64_t* point_ids;  // nullptr: every point (np == the number of points, checked by the caller)
+    uint64_t np, k;
+    uint64_t ef;                // graph_search only
+    const uint64_t* allowed;    // exact_graph only, like n_allowed; not nullptr: a filter, even when it is empty
+    uint64_t n_allowed;
+    uint64_t* out_ids;          // np x k, like the three below
+    float* out_dists;
+    uint8_t* out_layer;         // may be nullptr
+    int32_t* out_rank;          // may be nullptr
+    uint32_t* out_counts;       // [np]
+};
+HNSWGPU_DEVICE_SIDE int graph_search(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphCallArgs& a, bool host, void* stream, std::string& err);
+HNSWGPU_DEVICE_SIDE int exact_graph(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphCallArgs& a, bool host, void* stream,
+                                    std::string& err);
+// hnswgpu_range_search_batch(_device), range_search.hip: the rounds of every group of queries through DeviceIndex::search_device.
+// filtered: allowed is a filter even when it is empty.  dev == nullptr (device form on an empty index, or with no query): the offsets
+// are zeroed on the caller's stream.  Returns HNSWGPU_ERR_CAPACITY, the offsets complete, when the answers need more than cap slots.
 struct RangeSearchArgs {
     const float* queries;  // nq x d
     const float* radii;    // [nq]
@@ -124,9 +154,8 @@ struct RangeSearchArgs {
     uint32_t* out_ef;       // [nq], may be nullptr
     uint8_t* out_flags;     // [nq], may be nullptr
 };
-int range_search_host(DeviceIndex& dev, const RangeSearchArgs& a, std::string& err);
-int range_search_device(DeviceIndex* dev, const RangeSearchArgs& d_a, void* stream, std::string& err);
-// the device side of hnswgpu_symmetric_graph(_device), defined in symmetric_graph.hip and referred to weakly in the same way: the
+HNSWGPU_DEVICE_SIDE int range_search(DeviceIndex* dev, const RangeSearchArgs& a, bool host, void* stream, std::string& err);
+// the device side of hnswgpu_symmetric_graph(_device), defined in symmetric_graph.hip: the
 // directed graph of every point through exact_graph (ef == 0) or graph_search, made undirected (the arguments have been checked).
 // host: the out arrays are plain host memory; else device memory and `stream` is the caller's.  Returns HNSWGPU_ERR_CAPACITY, the
 // offsets complete and no out slot written, when the answer needs more than cap slots.  dev == nullptr (device entry on an empty
@@ -142,9 +171,9 @@ struct SymGraphArgs {
     uint8_t* out_layer;     // may be nullptr
     int32_t* out_rank;      // may be nullptr
 };
-int symmetric_graph(DeviceIndex* dev, const std::vector<uint64_t>& origin_id, const SymGraphArgs& a, bool host, void* stream, std::string& err);
-// the device side of hnswgpu_graph_components(_device) and hnswgpu_csr_components(_device), defined in graph_components.hip and
-// referred to weakly in the same way (the arguments have been checked; at least one vertex).  host: the arrays are plain host memory;
+HNSWGPU_DEVICE_SIDE int symmetric_graph(DeviceIndex* dev, const std::vector<uint64_t>& origin_id, const SymGraphArgs& a, bool host, void* stream, std::string& err);
+// the device side of hnswgpu_graph_components(_device) and hnswgpu_csr_components(_device), defined in graph_components.hip
+// (the arguments have been checked; at least one vertex).  host: the arrays are plain host memory;
 // else device memory and `stream` is the caller's.  out_n is host memory either way.  csr_components returns ERR_ARG, no out slot
 // written, when its validation kernels refuse the graph.
 struct ComponentsArgs {
@@ -156,7 +185,7 @@ struct ComponentsArgs {
     uint32_t* out_sizes;  // [n], may be nullptr
     uint64_t* out_n;
 };
-int graph_components(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ComponentsArgs& a, bool host, void* stream, std::string& err);
+HNSWGPU_DEVICE_SIDE int graph_components(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ComponentsArgs& a, bool host, void* stream, std::string& err);
 struct CsrComponentsArgs {
     int device;
     uint64_t n;
@@ -169,9 +198,9 @@ struct CsrComponentsArgs {
     uint32_t* out_sizes;
     uint64_t* out_n;
 };
-int csr_components(const CsrComponentsArgs& a, bool host, void* stream, std::string& err);
+HNSWGPU_DEVICE_SIDE int csr_components(const CsrComponentsArgs& a, bool host, void* stream, std::string& err);
 // the device side of hnswgpu_graph_spanning_forest(_device) and hnswgpu_csr_spanning_forest(_device), defined in spanning_forest.hip
-// and referred to weakly in the same way (the arguments have been checked; at least two vertices).  host: the arrays are plain host
+// (the arguments have been checked; at least two vertices).  host: the arrays are plain host
 // memory; else device memory and `stream` is the caller's.  out_n is host memory either way.  csr_spanning_forest returns ERR_ARG,
 // no out slot written, when its validation kernels refuse the graph.
 struct ForestArgs {
@@ -183,7 +212,7 @@ struct ForestArgs {
     float* out_w;     // [n - 1]
     uint64_t* out_n;
 };
-int graph_spanning_forest(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ForestArgs& a, bool host, void* stream, std::string& err);
+HNSWGPU_DEVICE_SIDE int graph_spanning_forest(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ForestArgs& a, bool host, void* stream, std::string& err);
 struct CsrForestArgs {
     int device;
     uint64_t n;
@@ -195,9 +224,9 @@ struct CsrForestArgs {
     float* out_w;
     uint64_t* out_n;
 };
-int csr_spanning_forest(const CsrForestArgs& a, bool host, void* stream, std::string& err);
-// the device side of hnswgpu_forest_dendrogram(_device) and hnswgpu_graph_dendrogram(_device), defined in dendrogram.hip and referred
-// to weakly in the same way (the arguments have been checked; forest form: 1 <= m <= n - 1; index form: at least two vertices).
+HNSWGPU_DEVICE_SIDE int csr_spanning_forest(const CsrForestArgs& a, bool host, void* stream, std::string& err);
+// the device side of hnswgpu_forest_dendrogram(_device) and hnswgpu_graph_dendrogram(_device), defined in dendrogram.hip
+// (the arguments have been checked; forest form: 1 <= m <= n - 1; index form: at least two vertices).
 // host: the arrays are plain host memory -- a forest form's ends have then passed their checks on the host --; else device memory
 // and `stream` is the caller's.  forest_dendrogram returns ERR_ARG, no out slot written, when an end is not below n, an edge joins a
 // vertex to itself or the edges hold a cycle.  graph_dendrogram runs graph_spanning_forest into device memory and goes on from there.
@@ -210,16 +239,16 @@ struct DendrogramArgs {
     uint32_t* out_right;  // [m]
     uint32_t* out_size;   // [m]
 };
-int forest_dendrogram(const DendrogramArgs& a, bool host, void* stream, std::string& err);
+HNSWGPU_DEVICE_SIDE int forest_dendrogram(const DendrogramArgs& a, bool host, void* stream, std::string& err);
 struct GraphDendrogramArgs {
     ForestArgs forest;    // out_n is host memory either way
     uint32_t* out_left;   // [n - 1]
     uint32_t* out_right;  // [n - 1]
     uint32_t* out_size;   // [n - 1]
 };
-int graph_dendrogram(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphDendrogramArgs& a, bool host, void* stream, std::string& err);
-// the device side of hnswhdb_forest(_device) and hnswhdb_graph(_device), defined in condensed_tree.hip and referred
-// to weakly in the same way (the arguments have been checked; forest form: n >= 1, m <= n - 1; index form: at least one point;
+HNSWGPU_DEVICE_SIDE int graph_dendrogram(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphDendrogramArgs& a, bool host, void* stream, std::string& err);
+// the device side of hnswhdb_forest(_device) and hnswhdb_graph(_device), defined in condensed_tree.hip
+// (the arguments have been checked; forest form: n >= 1, m <= n - 1; index form: at least one point;
 // 2 <= min_cluster_size <= 2^31 - 1, a known method).  host: the arrays are plain host memory -- a forest form's ends and weights
 // have then passed their checks on the host --; else device memory and `stream` is the caller's.  The two counts are host memory
 // either way.  forest_hdbscan runs forest_dendrogram on device buffers and returns what it refuses, and ERR_ARG, no out slot
@@ -247,7 +276,7 @@ struct ForestHdbscanArgs {
     uint32_t method;    // HNSWGPU_SELECT_*
     HdbscanOut out;
 };
-int forest_hdbscan(const ForestHdbscanArgs& a, bool host, void* stream, std::string& err);
+HNSWGPU_DEVICE_SIDE int forest_hdbscan(const ForestHdbscanArgs& a, bool host, void* stream, std::string& err);
 struct GraphHdbscanArgs {
     ForestArgs forest;    // out_a, out_b, out_w may be nullptr; out_n is host memory either way
     uint32_t* out_left;   // [n - 1], may be nullptr, like the two below
@@ -257,7 +286,7 @@ struct GraphHdbscanArgs {
     uint32_t method;
     HdbscanOut out;
 };
-int graph_hdbscan(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphHdbscanArgs& a, bool host, void* stream, std::string& err);
+HNSWGPU_DEVICE_SIDE int graph_hdbscan(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphHdbscanArgs& a, bool host, void* stream, std::string& err);
 }  // namespace hnswgpu
 
 // No C++ exception may cross the C ABI: every entry point is `try { ... HNSWGPU_CAPI_GUARD_END(ret)`

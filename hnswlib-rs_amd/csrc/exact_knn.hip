@@ -884,8 +884,8 @@ struct RangeCall {
 // Both entries.  Count pass over every query (host buffers: in blocks of at most 64 MB of queries), the offsets complete on the
 // caller's side; then, when the total fits cap, the fill pass chunk by chunk of the plan: keys, sort, decode -- into the caller's
 // arrays (device) or into a staging area that is copied out (host).  Waits for `stream` before it returns.
-int exact_range(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const RangeCall& io, uint64_t nq, uint64_t d, hipStream_t stream,
-                std::string& err) {
+int exact_range_passes(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const RangeCall& io, uint64_t nq, uint64_t d, hipStream_t stream,
+                       std::string& err) {
     const DeviceIndexView& v = dev.view();
     DeviceGuard on(dev.device());
     HIP_TRY(on.status());
@@ -1255,23 +1255,20 @@ int exact_host(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, c
 
 }  // namespace
 
-// The device side of hnswgpu_exact_search_batch_filter_set(_device); capi.cpp holds the entries and every argument check, and
-// refers to these two weakly (capi_index.hpp).
-int exact_filter_set_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* d_queries, uint64_t nq, uint64_t d,
-                            uint64_t k, const FilterSet& d_set, uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer,
-                            int32_t* d_out_rank, uint32_t* d_out_counts, void* stream, std::string& err) {
-    const SetCall set{&d_set, filter_set_budget()};
-    return exact_device(dev, origin_id, d_queries, nq, d, k, nullptr, 0, false, &set, d_out_ids, d_out_dists, d_out_layer, d_out_rank,
-                        d_out_counts, static_cast<hipStream_t>(stream), err);
-}
-
-// host buffers: the set goes to the device once; queries and answers go chunk by chunk (exact_host_chunks)
-int exact_filter_set_host(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* queries, uint64_t nq, uint64_t d,
-                          uint64_t k, const FilterSet& set, uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank,
-                          uint32_t* out_counts, std::string& err) {
-    if (nq == 0) return OK;
+// The device side of hnswgpu_exact_search_batch_filter_set(_device); capi.cpp holds the entries and every argument check
+// (capi_index.hpp).
+int exact_filter_set(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ExactSetArgs& a, bool host, void* stream, std::string& err) {
+    const GraphRows out{a.out_ids, a.out_dists, a.out_layer, a.out_rank, a.out_counts};
+    if (!host) {
+        const SetCall set{&a.set, filter_set_budget()};
+        return exact_device(dev, origin_id, a.queries, a.nq, a.d, a.k, nullptr, 0, false, &set, out.ids, out.dists, out.layer, out.rank, out.counts,
+                            static_cast<hipStream_t>(stream), err);
+    }
+    // host buffers: the set goes to the device once; queries and answers go chunk by chunk (exact_host_chunks)
+    if (a.nq == 0) return OK;
     DeviceGuard on(dev.device());
     HIP_TRY(on.status());
+    const FilterSet& set = a.set;
     const uint64_t n_ids = set.offsets[set.n_filters];
     DevMem m_ids, m_off;
     HIP_TRY(m_ids.alloc(std::max<uint64_t>(1, n_ids) * sizeof(uint64_t)));  // (filters that are all empty: never read)
@@ -1279,44 +1276,34 @@ int exact_filter_set_host(const DeviceIndex& dev, const std::vector<uint64_t>& o
     if (n_ids != 0) HIP_TRY(hipMemcpy(m_ids.p, set.ids, n_ids * sizeof(uint64_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(m_off.p, set.offsets, (set.n_filters + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
     const FilterSet d_set{static_cast<const uint64_t*>(m_ids.p), static_cast<const uint64_t*>(m_off.p), set.n_filters, nullptr};
-    return exact_host_chunks(dev, origin_id, queries, nq, d, k, nullptr, 0, false, &d_set, set.filter_of,
-                             GraphRows{out_ids, out_dists, out_layer, out_rank, out_counts}, err);
+    return exact_host_chunks(dev, origin_id, a.queries, a.nq, a.d, a.k, nullptr, 0, false, &d_set, set.filter_of, out, err);
 }
 
-// The device side of hnswgpu_exact_range_search_batch(_device); capi.cpp holds the entries and every argument check, and refers
-// to these two weakly (capi_index.hpp).
-int exact_range_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* d_queries, uint64_t nq, uint64_t d,
-                       const float* d_radii, const uint64_t* d_allowed, uint64_t n_allowed, uint64_t cap, uint64_t* d_out_offsets,
-                       uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, void* stream, std::string& err) {
+// The device side of hnswgpu_exact_range_search_batch(_device); capi.cpp holds the entries and every argument check (capi_index.hpp).
+int exact_range(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ExactRangeCallArgs& a, bool host, void* stream, std::string& err) {
     // (a filter that is empty still is a filter: a non-null pointer that is never dereferenced)
-    const RangeCall io{false, d_queries, d_radii, d_allowed, n_allowed, d_allowed != nullptr, cap, d_out_offsets, d_out_ids, d_out_dists,
-                       d_out_layer, d_out_rank};
-    return exact_range(dev, origin_id, io, nq, d, static_cast<hipStream_t>(stream), err);
-}
-
-int exact_range_host(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* queries, uint64_t nq, uint64_t d,
-                     const float* radii, const uint64_t* allowed, uint64_t n_allowed, uint64_t cap, uint64_t* out_offsets, uint64_t* out_ids,
-                     float* out_dists, uint8_t* out_layer, int32_t* out_rank, std::string& err) {
+    RangeCall io{host, a.queries, a.radii, a.allowed, a.n_allowed, a.allowed != nullptr, a.cap, a.out_offsets, a.out_ids, a.out_dists, a.out_layer,
+                 a.out_rank};
+    if (!host) return exact_range_passes(dev, origin_id, io, a.nq, a.d, static_cast<hipStream_t>(stream), err);
     DeviceGuard on(dev.device());
     HIP_TRY(on.status());
-    DevMem m_allowed;
-    if (allowed != nullptr) {
-        HIP_TRY(m_allowed.alloc(std::max<uint64_t>(1, n_allowed) * sizeof(uint64_t)));
-        if (n_allowed != 0) HIP_TRY(hipMemcpy(m_allowed.p, allowed, n_allowed * sizeof(uint64_t), hipMemcpyHostToDevice));
+    DevMem m_allowed;  // host buffers: the filter, when there is one, goes to the device once
+    if (a.allowed != nullptr) {
+        HIP_TRY(m_allowed.alloc(std::max<uint64_t>(1, a.n_allowed) * sizeof(uint64_t)));
+        if (a.n_allowed != 0) HIP_TRY(hipMemcpy(m_allowed.p, a.allowed, a.n_allowed * sizeof(uint64_t), hipMemcpyHostToDevice));
     }
-    const RangeCall io{true, queries, radii, static_cast<const uint64_t*>(m_allowed.p), n_allowed, allowed != nullptr, cap, out_offsets, out_ids,
-                       out_dists, out_layer, out_rank};
-    return exact_range(dev, origin_id, io, nq, d, nullptr, err);
+    io.d_allowed = static_cast<const uint64_t*>(m_allowed.p);
+    return exact_range_passes(dev, origin_id, io, a.nq, a.d, nullptr, err);
 }
 
 // The device side of hnswgpu_graph_search_batch(_device) and hnswgpu_exact_graph_batch(_device); capi.cpp holds the entries and
-// every argument check that needs no device, and refers to these two weakly (capi_index.hpp).  host: every buffer is plain host
-// memory, else device memory.  Both wait for `stream` before they return.
+// every argument check that needs no device (capi_index.hpp).  host: every buffer is plain host memory, else device memory.  Both wait
+// for `stream` before they return.
 
 // Approximate graph: chunk by chunk of at most HNSWGPU_GRAPH_CHUNK points (unset: what GRAPH_SCRATCH holds), the points' vectors
 // gathered on the device, searched by the batched search itself with knbn = k + 1, and compacted into the caller's rows.
-int graph_search(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, bool host, const uint64_t* point_ids, uint64_t np, uint64_t k, uint64_t ef,
-                 uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts, void* stream_v, std::string& err) {
+int graph_search(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphCallArgs& a, bool host, void* stream_v, std::string& err) {
+    const uint64_t np = a.np, k = a.k, ef = a.ef;
     if (np == 0) return OK;
     const DeviceIndexView& v = dev.view();
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
@@ -1326,7 +1313,7 @@ int graph_search(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, bool 
     std::shared_ptr<void> ext = dev.extension([&]() { return make_state(dev, origin_id, serr); });
     if (!ext) { err = serr.empty() ? "graph search: no device state" : serr; return ERR_DEVICE; }
     const ExactState* st = static_cast<const ExactState*>(ext.get());
-    const GraphCall io{host, point_ids, np, k, {out_ids, out_dists, out_layer, out_rank, out_counts}};
+    const GraphCall io{host, a.point_ids, np, k, {a.out_ids, a.out_dists, a.out_layer, a.out_rank, a.out_counts}};
     DevMem m_flat, m_q;
     AnswerStage wide, stage;  // the search's (k + 1)-wide answers; a host call's k-wide ones
     Drain drain{stream};  // (destroyed first: nothing of this call is running when its memory is freed)
@@ -1360,9 +1347,9 @@ int graph_search(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, bool 
 }
 
 // Exact graph: the exact k-NN's own chunk loop over tiles built from the rows themselves, the slab kernel's SELF variant
-int exact_graph(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, bool host, const uint64_t* point_ids, uint64_t np, uint64_t k,
-                const uint64_t* allowed, uint64_t n_allowed, uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank,
-                uint32_t* out_counts, void* stream_v, std::string& err) {
+int exact_graph(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphCallArgs& a, bool host, void* stream_v, std::string& err) {
+    const uint64_t np = a.np, k = a.k, n_allowed = a.n_allowed;
+    const uint64_t* allowed = a.allowed;
     if (np == 0) return OK;
     const DeviceIndexView& v = dev.view();
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
@@ -1372,7 +1359,7 @@ int exact_graph(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, 
     std::shared_ptr<void> ext = dev.extension([&]() { return make_state(dev, origin_id, serr); });
     if (!ext) { err = serr.empty() ? "exact graph: no device state" : serr; return ERR_DEVICE; }
     const ExactState* st = static_cast<const ExactState*>(ext.get());
-    const GraphCall io{host, point_ids, np, k, {out_ids, out_dists, out_layer, out_rank, out_counts}};
+    const GraphCall io{host, a.point_ids, np, k, {a.out_ids, a.out_dists, a.out_layer, a.out_rank, a.out_counts}};
     DevMem m_flat, m_allowed;
     AnswerStage stage;
     int rc = graph_resolve(v, st, io, m_flat, stream, err);  // (waits for the stream)
@@ -1380,8 +1367,8 @@ int exact_graph(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, 
     const uint32_t* d_flat = static_cast<const uint32_t*>(m_flat.p);
     const bool filtered = allowed != nullptr;
     if (!host)
-        return exact_device(dev, origin_id, nullptr, np, v.d, k, allowed, n_allowed, filtered, nullptr, out_ids, out_dists, out_layer, out_rank, out_counts,
-                            stream, err, d_flat);
+        return exact_device(dev, origin_id, nullptr, np, v.d, k, allowed, n_allowed, filtered, nullptr, io.out.ids, io.out.dists, io.out.layer, io.out.rank,
+                            io.out.counts, stream, err, d_flat);
     // (a filter that is empty still is a filter: a non-null pointer that is never dereferenced)
     const uint64_t* d_allowed = filtered ? reinterpret_cast<const uint64_t*>(m_flat.p) : nullptr;
     if (filtered && n_allowed != 0) {

@@ -178,7 +178,7 @@ uint64_t range_group_size(uint64_t nq, uint64_t d, uint64_t ef_max) {
 }
 
 // both entries.  host: every buffer of `a` but the filter is plain host memory (the filter has been copied); else device memory.
-int range_search(DeviceIndex& dev, const RangeSearchArgs& a, bool host, hipStream_t stream, std::string& err) {
+int range_rounds(DeviceIndex& dev, const RangeSearchArgs& a, bool host, hipStream_t stream, std::string& err) {
     const uint64_t nq = a.nq, d = a.d;
     DeviceGuard on(dev.device());
     HIP_TRY(on.status());
@@ -291,22 +291,22 @@ int range_search(DeviceIndex& dev, const RangeSearchArgs& a, bool host, hipStrea
 
 }  // namespace
 
-// The device side of hnswgpu_range_search_batch(_device); capi.cpp holds the entries and every argument check, and refers to these
-// two weakly (capi_index.hpp).  Both wait for the stream before they return.
-int range_search_device(DeviceIndex* dev, const RangeSearchArgs& d_a, void* stream_v, std::string& err) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    if (dev == nullptr || d_a.nq == 0) {  // no point, or no query: every answer is empty
-        HIP_TRY(hipMemsetAsync(d_a.out_offsets, 0, (d_a.nq + 1) * 8, stream));
-        if (d_a.out_ef && d_a.nq != 0) HIP_TRY(hipMemsetAsync(d_a.out_ef, 0, d_a.nq * 4, stream));
-        if (d_a.out_flags && d_a.nq != 0) HIP_TRY(hipMemsetAsync(d_a.out_flags, 0, d_a.nq, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        return OK;
+// The device side of hnswgpu_range_search_batch(_device); capi.cpp holds the entries and every argument check (capi_index.hpp).
+// Waits for the stream before it returns.
+int range_search(DeviceIndex* dev, const RangeSearchArgs& a, bool host, void* stream_v, std::string& err) {
+    if (!host) {
+        hipStream_t stream = static_cast<hipStream_t>(stream_v);
+        if (dev == nullptr || a.nq == 0) {  // no point, or no query: every answer is empty
+            HIP_TRY(hipMemsetAsync(a.out_offsets, 0, (a.nq + 1) * 8, stream));
+            if (a.out_ef && a.nq != 0) HIP_TRY(hipMemsetAsync(a.out_ef, 0, a.nq * 4, stream));
+            if (a.out_flags && a.nq != 0) HIP_TRY(hipMemsetAsync(a.out_flags, 0, a.nq, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            return OK;
+        }
+        return range_rounds(*dev, a, false, stream, err);
     }
-    return range_search(*dev, d_a, false, stream, err);
-}
-
-int range_search_host(DeviceIndex& dev, const RangeSearchArgs& a, std::string& err) {
-    DeviceGuard on(dev.device());
+    // host buffers (the caller has answered an empty index and an empty batch itself): the filter goes to the device once
+    DeviceGuard on(dev->device());
     HIP_TRY(on.status());
     DevMem m_allowed;
     RangeSearchArgs b = a;
@@ -315,7 +315,7 @@ int range_search_host(DeviceIndex& dev, const RangeSearchArgs& a, std::string& e
         HIP_TRY(hipMemcpy(m_allowed.p, a.allowed, a.n_allowed * sizeof(uint64_t), hipMemcpyHostToDevice));
     }
     b.allowed = static_cast<const uint64_t*>(m_allowed.p);
-    return range_search(dev, b, true, nullptr, err);
+    return range_rounds(*dev, b, true, nullptr, err);
 }
 
 }  // namespace hnswgpu

@@ -12,6 +12,17 @@
 #include "f16_storage.hpp"
 #include "flat_index.hpp"
 
+// In front of every function that capi.cpp calls but a host-only build of the C ABI does not hold (the sanitizer build, whose source list
+// is fixed, links capi.cpp against stand-ins for the device that stop at the entries that existed when they were written).  capi.cpp
+// defines HNSWGPU_WEAK_DEVICE_SIDE ahead of its includes: its references are weak, so it links without the .hip unit behind them,
+// finds the function's address null and answers "no device" -- after the argument checks, which are the same everywhere.  Everywhere
+// else (the units that define these functions, the stand-ins) this is nothing, and the definitions are strong.
+#ifdef HNSWGPU_WEAK_DEVICE_SIDE
+#define HNSWGPU_DEVICE_SIDE __attribute__((weak))
+#else
+#define HNSWGPU_DEVICE_SIDE
+#endif
+
 namespace hnswgpu {
 
 constexpr int ARITH_SCALAR = 0, ARITH_SIMD8 = 1;  // DeviceIndex::set_arithmetic
@@ -116,15 +127,15 @@ struct FilterSet {
 class DeviceIndex;
 // Hnsw::search_filter(data_q, knbn, ef, Some(&filters[filter_of[q]])) for every query q of a batch (search_device.hip).  capi.cpp
 // refers to these two weakly: a host-only build of the C ABI (the sanitizer build, whose source list is fixed) links without
-// them and answers "no device", what every device entry answers there.
+// them and answers "no device", what every device entry answers there (HNSWGPU_DEVICE_SIDE).
 // Every buffer in device memory: like DeviceIndex::search_device with a filter.  The arrays cannot be read on the host, so a kernel
 // counts the entries of filter_of that are >= n_filters and the call returns ERR_ARG, nothing written, before the search is launched;
 // the offsets and the sortedness of the vectors are the caller's promise.
-int search_filter_set_device(DeviceIndex& ix, const float* d_queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef, const FilterSet& d_set,
+HNSWGPU_DEVICE_SIDE int search_filter_set_device(DeviceIndex& ix, const float* d_queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef, const FilterSet& d_set,
                              uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts,
                              uint32_t* d_stats, void* stream, CallInfo* info, std::string& err);
 // Host buffers (the set too, already validated): like DeviceIndex::search_host.
-int search_filter_set_host(DeviceIndex& ix, const float* queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef, const FilterSet& set,
+HNSWGPU_DEVICE_SIDE int search_filter_set_host(DeviceIndex& ix, const float* queries, uint64_t nq, uint64_t d, uint64_t k, uint64_t ef, const FilterSet& set,
                            uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts,
                            uint8_t* out_status, CallInfo* info, std::string& err);
 
@@ -302,11 +313,11 @@ std::unique_ptr<BuildSearchBackend> make_device_build_backend(int device);
 // half-storage kernels, as a STORAGE_F16 replica's are (scalar arithmetic, DistL2 / DistCosine / DistDot / DistL1).
 int eval_distance_matrix_device(int dist, const float* queries, uint64_t nq, const float* rows, uint64_t n, uint64_t d,
                                 uint32_t nf, bool pairs, float* out, std::string& err, int arithmetic = 0);
-int eval_distance_matrix_storage_device(int dist, int storage, const float* queries, uint64_t nq, const float* rows, uint64_t n, uint64_t d,
+HNSWGPU_DEVICE_SIDE int eval_distance_matrix_storage_device(int dist, int storage, const float* queries, uint64_t nq, const float* rows, uint64_t n, uint64_t d,
                                         uint32_t nf, float* out, std::string& err);
 // the same through one of the row loops that only the search kernel's expansion loop compiles (variant: EVAL_* of
 // search_kernels.hpp, a combination that exists -- else ERR_ARG, never the plain routine); referred to weakly by capi.cpp too
-int eval_distance_matrix_variant_device(int dist, int storage, int variant, const float* queries, uint64_t nq, const float* rows, uint64_t n,
+HNSWGPU_DEVICE_SIDE int eval_distance_matrix_variant_device(int dist, int storage, int variant, const float* queries, uint64_t nq, const float* rows, uint64_t n,
                                         uint64_t d, uint32_t nf, float* out, std::string& err);
 
 // The lane lab (search_kernels.hpp, lane_lab.inc): runs a script of wave-level operations of the search kernels on `device`

@@ -144,8 +144,8 @@ int stage_directed_graph(DeviceIndex& dev, const std::vector<uint64_t>& origin_i
     lay.array(out.layer, slots);
     const int rc = alloc_layout("graph", out.mem, lay, err);
     if (rc != OK) return rc;
-    return ef == 0 ? exact_graph(dev, origin_id, false, nullptr, n, k, nullptr, 0, d_ids, out.dists, out.layer, out.rank, out.counts, stream, err)
-                   : graph_search(dev, origin_id, false, nullptr, n, k, ef, d_ids, out.dists, out.layer, out.rank, out.counts, stream, err);
+    const GraphCallArgs every_point{nullptr, n, k, ef, nullptr, 0, d_ids, out.dists, out.layer, out.rank, out.counts};
+    return ef == 0 ? exact_graph(dev, origin_id, every_point, false, stream, err) : graph_search(dev, origin_id, every_point, false, stream, err);
 }
 
 // D's edge records, sorted (graph_internal.hpp)
