@@ -231,10 +231,12 @@ class SpanningForestResult:
         d = forest_dendrogram(self.n_vertices, self.a[:m], self.b[:m], device)
         return DendrogramResult(d.left, d.right, d.sizes, m, self.n_vertices, self.a[:m], self.b[:m], self.weights[:m])
 
-    def hdbscan(self, min_cluster_size, method="eom", device=0):
-        """HDBSCAN's clusters of this forest's edges in their order (forest_hdbscan): an HdbscanResult."""
+    def hdbscan(self, min_cluster_size, method="eom", device=0, allow_single_cluster=False, cluster_selection_epsilon=0.0, max_cluster_size=None,
+                outlier_scores=False):
+        """HDBSCAN's clusters of this forest's edges in their order (forest_hdbscan, its options included): an HdbscanResult."""
         m = self.n_edges
-        return forest_hdbscan(self.n_vertices, self.a[:m], self.b[:m], self.weights[:m], min_cluster_size, method, device)
+        return forest_hdbscan(self.n_vertices, self.a[:m], self.b[:m], self.weights[:m], min_cluster_size, method, device, allow_single_cluster,
+                              cluster_selection_epsilon, max_cluster_size, outlier_scores)
 
 
 class DendrogramResult:
@@ -296,14 +298,44 @@ class HdbscanResult:
     vertex leaves, and the f32 weight at which it does).  Per cluster of the condensed tree, n_clusters of them, cluster 0 the
     root: cluster_parent (0xFFFFFFFF for cluster 0), cluster_birth_w, cluster_size, stability (f64), selected (bool).  n_labels
     selected clusters, numbered by ascending cluster index.  forest (a SpanningForestResult) and dendrogram (a DendrogramResult)
-    are there where the call produced them (Hnsw.hdbscan), else None."""
+    are there where the call produced them (Hnsw.hdbscan), else None.  outlier_scores (f32 per vertex, GLOSH) and
+    cluster_death_lambda (f64 per cluster) are there on results that went through select(), else None."""
 
     def __init__(self, labels, probabilities, point_cluster, point_w, cluster_parent, cluster_birth_w, cluster_size, stability, selected,
-                 n_clusters, n_labels, forest=None, dendrogram=None):
+                 n_clusters, n_labels, forest=None, dendrogram=None, outlier_scores=None, cluster_death_lambda=None):
         self.labels, self.probabilities, self.point_cluster, self.point_w = labels, probabilities, point_cluster, point_w
         self.cluster_parent, self.cluster_birth_w, self.cluster_size = cluster_parent, cluster_birth_w, cluster_size
         self.stability, self.selected, self.n_clusters, self.n_labels = stability, selected, n_clusters, n_labels
         self.forest, self.dendrogram = forest, dendrogram
+        self.outlier_scores, self.cluster_death_lambda = outlier_scores, cluster_death_lambda
+
+    def select(self, method="eom", allow_single_cluster=False, cluster_selection_epsilon=0.0, max_cluster_size=None, device=0):
+        """The selection made again on this result's condensed tree, on `device`, without the tree being made again
+        (include/hnsw_mi355x_hdbscan_select.h): method "eom" or "leaf"; allow_single_cluster: cluster 0 may be selected;
+        cluster_selection_epsilon: a weight, selected clusters born below it climb to the ancestor born above it;
+        max_cluster_size: None, or the largest size an excess-of-mass winner may have.  Returns a new HdbscanResult over the same
+        tree arrays with selected, labels, probabilities and n_labels of its own, outlier_scores (GLOSH) and
+        cluster_death_lambda."""
+        code = _hdbscan_method(method)
+        if max_cluster_size is None:
+            max_size = 0
+        elif max_cluster_size != int(max_cluster_size) or not 1 <= max_cluster_size < 1 << 64:
+            raise HnswError(N.ERR_ARG, f"max_cluster_size = {max_cluster_size}: None, or a size of 1 or more")
+        else:
+            max_size = int(max_cluster_size)
+        n, k = len(self.labels), int(self.n_clusters)
+        tree = [np.ascontiguousarray(x[:k], dtype=t) for x, t in ((self.cluster_parent, np.uint32), (self.cluster_birth_w, np.float32),
+                                                                  (self.cluster_size, np.uint32), (self.stability, np.float64))]
+        points = [np.ascontiguousarray(self.point_cluster[:n], dtype=np.uint32), np.ascontiguousarray(self.point_w[:n], dtype=np.float32)]
+        selected, death = np.zeros(max(k, 1), np.uint8), np.zeros(max(k, 1), np.float64)
+        labels, prob, score = np.full(max(n, 1), -1, np.int32), np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32)
+        n_labels = np.zeros(1, np.uint64)
+        _check(N.lib().hnswhds_select(device, n, k, *[_p(x) if len(x) else None for x in tree + points], code, int(bool(allow_single_cluster)),
+                                      float(cluster_selection_epsilon), max_size, _p(selected), _p(labels), _p(prob), _p(score), _p(death),
+                                      _p(n_labels)))
+        return HdbscanResult(labels[:n].copy(), prob[:n].copy(), self.point_cluster, self.point_w, self.cluster_parent, self.cluster_birth_w,
+                             self.cluster_size, self.stability, selected[:k].astype(bool), k, int(n_labels[0]), self.forest, self.dendrogram,
+                             score[:n].copy(), death[:k].copy())
 
     def condensed_tree(self):
         """The condensed tree as rows (parent, child, lambda, child_size) in sklearn's CONDENSED_dtype layout ('parent' and 'child'
@@ -325,6 +357,13 @@ class HdbscanResult:
 
 
 _METHODS = {"eom": "HNSWGPU_SELECT_EOM", "leaf": "HNSWGPU_SELECT_LEAF"}
+
+
+def _select_behind(result, method, device, allow_single_cluster, cluster_selection_epsilon, max_cluster_size, outlier_scores):
+    """what the hdbscan calls return: `result` as it is under the default options, else its select()"""
+    if not allow_single_cluster and cluster_selection_epsilon == 0 and max_cluster_size is None and not outlier_scores:
+        return result
+    return result.select(method, allow_single_cluster, cluster_selection_epsilon, max_cluster_size, device)
 
 
 def _hdbscan_method(method):
@@ -358,11 +397,13 @@ class _HdbscanArrays:
                              self.selected[:k].astype(bool), k, int(self.n_labels[0]), forest, dendrogram)
 
 
-def forest_hdbscan(n, a, b, weights, min_cluster_size, method="eom", device=0):
+def forest_hdbscan(n, a, b, weights, min_cluster_size, method="eom", device=0, allow_single_cluster=False, cluster_selection_epsilon=0.0,
+                   max_cluster_size=None, outlier_scores=False):
     """HDBSCAN's clusters of the forest whose edge e joins vertices a[e] and b[e] of 0 .. n - 1 with weight weights[e] (f32), on
     `device`: the edges' order is the merge order and the weights must not descend.  method: "eom" (excess of mass) or "leaf".
     Refuses (HnswError, ERR_ARG) what forest_dendrogram refuses, weights that descend and a min_cluster_size outside 2 .. 2^31 - 1.
-    Returns an HdbscanResult."""
+    Returns an HdbscanResult.  allow_single_cluster, cluster_selection_epsilon, max_cluster_size and outlier_scores are
+    HdbscanResult.select's: at their defaults the answer is hnswhdb_forest's own, otherwise select() runs behind it."""
     a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
     b = np.ascontiguousarray(b, dtype=np.uint32).reshape(-1)
     w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
@@ -372,7 +413,7 @@ def forest_hdbscan(n, a, b, weights, min_cluster_size, method="eom", device=0):
     o = _HdbscanArrays(n, min_cluster_size)
     _check(N.lib().hnswhdb_forest(device, n, m, _p(a) if m else None, _p(b) if m else None, _p(w) if m else None, int(min_cluster_size), code,
                                           *o.pointers()))
-    return o.result()
+    return _select_behind(o.result(), method, device, allow_single_cluster, cluster_selection_epsilon, max_cluster_size, outlier_scores)
 
 
 def csr_spanning_forest(offsets, cols, dists=None, device=0):
@@ -924,12 +965,15 @@ class Hnsw:
         m = int(m[0])
         return DendrogramResult(left[:m].copy(), right[:m].copy(), sizes[:m].copy(), m, n, a[:m].copy(), b[:m].copy(), w[:m].copy())
 
-    def hdbscan(self, min_cluster_size, knbn, ef=None, mode="union", core_k=None, method="eom"):
+    def hdbscan(self, min_cluster_size, knbn, ef=None, mode="union", core_k=None, method="eom", allow_single_cluster=False,
+                cluster_selection_epsilon=0.0, max_cluster_size=None, outlier_scores=False):
         """HDBSCAN of the indexed points in one call: knn_graph_dendrogram(knbn, ef, mode, core_k), the condensed tree of that
         dendrogram for min_cluster_size, the stabilities, the selection ("eom": excess of mass, "leaf": the leaves) and the labels,
         the forest and the dendrogram staying on the device throughout.  Vertices are POSITIONS.  core_k=None means
         min(min_cluster_size - 1, knbn): sklearn's default min_samples = min_cluster_size, which counts the point itself.  Returns
-        an HdbscanResult whose forest and dendrogram are knn_graph_dendrogram's, byte for byte."""
+        an HdbscanResult whose forest and dendrogram are knn_graph_dendrogram's, byte for byte.  allow_single_cluster,
+        cluster_selection_epsilon, max_cluster_size and outlier_scores are HdbscanResult.select's: at their defaults the answer is
+        hnswhdb_graph's own, otherwise select() runs behind it (on device 0; result.select(..., device=) chooses another)."""
         modes = {"union": N.HEADER.constants["HNSWGPU_SYM_UNION"], "mutual": N.HEADER.constants["HNSWGPU_SYM_MUTUAL"]}
         if mode not in modes:
             raise HnswError(N.ERR_ARG, f"mode must be 'union' or 'mutual', not {mode!r}")
@@ -950,12 +994,14 @@ class Hnsw:
                 raise HnswError(N.ERR_ARG, "knbn must be > 0")
             if core_k > knbn:
                 raise HnswError(N.ERR_ARG, "core_k is above knbn")
-            return o.result(SpanningForestResult(a[:0], b[:0], w[:0], 0, 0), DendrogramResult(left[:0], right[:0], sizes[:0], 0, 0, a[:0], b[:0], w[:0]))
+            res = o.result(SpanningForestResult(a[:0], b[:0], w[:0], 0, 0), DendrogramResult(left[:0], right[:0], sizes[:0], 0, 0, a[:0], b[:0], w[:0]))
+            return _select_behind(res, method, 0, allow_single_cluster, cluster_selection_epsilon, max_cluster_size, outlier_scores)
         _check(self._lib.hnswhdb_graph(self._h, knbn, 0 if ef is None else ef, modes[mode], core_k, int(min_cluster_size), code, _p(a), _p(b),
                                                _p(w), _p(left), _p(right), _p(sizes), *o.pointers(), _p(m)))
         m = int(m[0])
         a, b, w = a[:m].copy(), b[:m].copy(), w[:m].copy()
-        return o.result(SpanningForestResult(a, b, w, m, n), DendrogramResult(left[:m].copy(), right[:m].copy(), sizes[:m].copy(), m, n, a, b, w))
+        res = o.result(SpanningForestResult(a, b, w, m, n), DendrogramResult(left[:m].copy(), right[:m].copy(), sizes[:m].copy(), m, n, a, b, w))
+        return _select_behind(res, method, 0, allow_single_cluster, cluster_selection_epsilon, max_cluster_size, outlier_scores)
 
     def knn_graph_recall(self, knbn, ef, point_ids=None):
         """The recall by id of knn_graph_flat against exact_knn_graph_flat over the named points: the share of the exact

@@ -1582,6 +1582,83 @@ int hnswhdb_graph_device(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
+// ---- HDBSCAN, second stage: the selection under its options, labels and GLOSH scores from a condensed tree
+// (hnsw_mi355x_hdbscan_select.h; cluster_select.hip holds the device side)
+// the tree as the host form reads it, as the device form's kernels check it
+static int select_tree_check(const HdbscanSelectArgs& a) {
+    const uint64_t K = a.clusters;
+    if (a.cluster_parent[0] != 0xFFFFFFFFu) return fail(HNSWGPU_ERR_ARG, "hdbscan select: not a condensed tree: cluster_parent[0] is not UINT32_MAX");
+    std::vector<uint8_t> kids(K, 0);
+    for (uint64_t c = 0; c < K; ++c) {
+        if (!(a.stability[c] >= 0.0))
+            return fail(HNSWGPU_ERR_ARG, "hdbscan select: not a condensed tree: a stability is NaN or negative (cluster " + std::to_string(c) + ")");
+        if (c == 0) continue;
+        const uint32_t p = a.cluster_parent[c];
+        if (p >= c) return fail(HNSWGPU_ERR_ARG, "hdbscan select: not a condensed tree: a cluster_parent[c] is not below c (cluster " + std::to_string(c) + ")");
+        if (p != 0 && kids[p] < 3) ++kids[p];
+    }
+    for (uint64_t c = 1; c < K; ++c)
+        if (kids[c] != 0 && kids[c] != 2)
+            return fail(HNSWGPU_ERR_ARG, "hdbscan select: not a condensed tree: a cluster other than 0 has one child, or more than two (cluster " +
+                                             std::to_string(c) + ")");
+    for (uint64_t v = 0; v < a.n; ++v)
+        if (a.point_cluster[v] >= K)
+            return fail(HNSWGPU_ERR_ARG, "hdbscan select: not a condensed tree: a point_cluster[v] is not below K (vertex " + std::to_string(v) + ")");
+    return HNSWGPU_OK;
+}
+
+static int hdbscan_select_pair(const HdbscanSelectArgs& a, bool host, void* stream) {
+    if (a.method != HNSWGPU_SELECT_EOM && a.method != HNSWGPU_SELECT_LEAF)
+        return fail(HNSWGPU_ERR_ARG, "unknown method " + std::to_string(a.method) + ": HNSWGPU_SELECT_EOM or HNSWGPU_SELECT_LEAF");
+    if (a.allow_single_cluster > 1)
+        return fail(HNSWGPU_ERR_ARG, "allow_single_cluster = " + std::to_string(a.allow_single_cluster) + ": it must be 0 or 1");
+    if (!(a.eps >= 0.0f)) return fail(HNSWGPU_ERR_ARG, "cluster_selection_epsilon is NaN or negative: it must be a weight, 0 or more");
+    if (a.n > 0x7FFFFFFFull) return fail(HNSWGPU_ERR_ARG, "hdbscan select: n = " + std::to_string(a.n) + " vertices, above 2^31 - 1");
+    if (a.clusters > 0x7FFFFFFFull) return fail(HNSWGPU_ERR_ARG, "hdbscan select: K = " + std::to_string(a.clusters) + " clusters, above 2^31 - 1");
+    if (!a.out_n_labels) return fail(HNSWGPU_ERR_ARG, "null out_n_labels: the number of labels is written by every call");
+    if (a.n == 0) {  // no vertex: the count, no array is read or written
+        *a.out_n_labels = 0;
+        return HNSWGPU_OK;
+    }
+    if (a.clusters == 0) return fail(HNSWGPU_ERR_ARG, "hdbscan select: K = 0 clusters over " + std::to_string(a.n) + " vertices: cluster 0 is always there");
+    if (!a.cluster_parent || !a.cluster_birth_w || !a.cluster_size || !a.stability)
+        return fail(HNSWGPU_ERR_ARG, "null cluster_parent, cluster_birth_w, cluster_size or stability");
+    if (!a.point_cluster || !a.point_w) return fail(HNSWGPU_ERR_ARG, "null point_cluster or point_w");
+    if (!a.out_labels) return fail(HNSWGPU_ERR_ARG, "null out_labels");
+    if (host) {
+        const int rc = select_tree_check(a);
+        if (rc != HNSWGPU_OK) return rc;
+    }
+    if (!hnswgpu::hdbscan_select) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    std::string err;
+    return finish(hnswgpu::hdbscan_select(a, host, stream, err), err);
+}
+
+int hnswhds_select(int device, uint64_t n, uint64_t K, const uint32_t* cluster_parent, const float* cluster_birth_w, const uint32_t* cluster_size,
+                   const double* stability, const uint32_t* point_cluster, const float* point_w, uint32_t method, uint32_t allow_single_cluster,
+                   float cluster_selection_epsilon, uint64_t max_cluster_size, uint8_t* out_selected, int32_t* out_labels, float* out_prob,
+                   float* out_outlier_score, double* out_cluster_death_lambda, uint64_t* out_n_labels) {
+    CAPI_GUARD_BEGIN
+    const HdbscanSelectArgs a{device, n, K, cluster_parent, cluster_birth_w, cluster_size, stability, point_cluster, point_w, method,
+                              allow_single_cluster, cluster_selection_epsilon, max_cluster_size, out_selected, out_labels, out_prob,
+                              out_outlier_score, out_cluster_death_lambda, out_n_labels};
+    return hdbscan_select_pair(a, true, nullptr);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswhds_select_device(int device, uint64_t n, uint64_t K, const uint32_t* d_cluster_parent, const float* d_cluster_birth_w,
+                          const uint32_t* d_cluster_size, const double* d_stability, const uint32_t* d_point_cluster, const float* d_point_w,
+                          uint32_t method, uint32_t allow_single_cluster, float cluster_selection_epsilon, uint64_t max_cluster_size,
+                          uint8_t* d_out_selected, int32_t* d_out_labels, float* d_out_prob, float* d_out_outlier_score,
+                          double* d_out_cluster_death_lambda, uint64_t* out_n_labels, void* stream) {
+    CAPI_GUARD_BEGIN
+    const HdbscanSelectArgs a{device, n, K, d_cluster_parent, d_cluster_birth_w, d_cluster_size, d_stability, d_point_cluster, d_point_w, method,
+                              allow_single_cluster, cluster_selection_epsilon, max_cluster_size, d_out_selected, d_out_labels, d_out_prob,
+                              d_out_outlier_score, d_out_cluster_death_lambda, out_n_labels};
+    return hdbscan_select_pair(a, false, stream);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
 static DeviceIndex* any_replica(hnswgpu_index* idx) {
     if (idx->primary >= 0 && idx->replica(idx->primary)) return idx->replica(idx->primary);
     return nullptr;

@@ -1,7 +1,7 @@
-// capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h (and its extension hnsw_mi355x_hdbscan.h),
+// capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h (and its extensions hnsw_mi355x_hdbscan.h and hnsw_mi355x_hdbscan_select.h),
 // for the translation units that implement the C ABI: capi.cpp, which holds the entries, and the .hip units that hold their device
 // side (exact_knn.hip, which also holds hnswgpu_exact_search_batch(_device) itself; range_search.hip; symmetric_graph.hip;
-// graph_components.hip; spanning_forest.hip; dendrogram.hip; condensed_tree.hip).  Private: not installed, not part of the ABI.
+// graph_components.hip; spanning_forest.hip; dendrogram.hip; condensed_tree.hip; cluster_select.hip).  Private: not installed, not part of the ABI.
 // Three parts: the handle; the checks that entries share (empty index, resident replica, sorted filter, the limits of an exact call,
 // the zeroed k-NN answer, the tail), which live once, in capi.cpp, and are declared here as capi_* for the entries outside it; and
 // the device side of every host / _device pair, declared ONCE, here, with its arguments' struct (HNSWGPU_DEVICE_SIDE of
@@ -20,6 +20,7 @@
 
 #include "../../include/hnsw_mi355x.h"
 #include "../../include/hnsw_mi355x_hdbscan.h"
+#include "../../include/hnsw_mi355x_hdbscan_select.h"
 #include "builder.hpp"
 #include "flat_index.hpp"
 #include "search_device.hpp"
@@ -287,6 +288,31 @@ struct GraphHdbscanArgs {
     HdbscanOut out;
 };
 HNSWGPU_DEVICE_SIDE int graph_hdbscan(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphHdbscanArgs& a, bool host, void* stream, std::string& err);
+// the device side of hnswhds_select(_device), defined in cluster_select.hip (the arguments have been checked: 1 <= n, K <= 2^31 - 1,
+// a known method, allow_single_cluster 0 or 1, eps >= 0, the six input arrays and out_labels there).  host: the arrays are plain
+// host memory and have passed the tree's checks on the host; else device memory, checked by kernel before anything walks the tree,
+// and `stream` is the caller's.  out_n_labels is host memory either way.  ERR_ARG, no out slot written, when the checks refuse.
+struct HdbscanSelectArgs {
+    int device;
+    uint64_t n, clusters;
+    const uint32_t* cluster_parent;  // [clusters], like the three below
+    const float* cluster_birth_w;
+    const uint32_t* cluster_size;
+    const double* stability;
+    const uint32_t* point_cluster;   // [n]
+    const float* point_w;            // [n]
+    uint32_t method;                 // HNSWGPU_SELECT_*
+    uint32_t allow_single_cluster;
+    float eps;
+    uint64_t max_cluster_size;       // 0: no limit
+    uint8_t* out_selected;           // [clusters], may be nullptr
+    int32_t* out_labels;             // [n]
+    float* out_prob;                 // [n], may be nullptr, like the two below
+    float* out_score;                // [n]
+    double* out_death;               // [clusters]
+    uint64_t* out_n_labels;
+};
+HNSWGPU_DEVICE_SIDE int hdbscan_select(const HdbscanSelectArgs& a, bool host, void* stream, std::string& err);
 }  // namespace hnswgpu
 
 // No C++ exception may cross the C ABI: every entry point is `try { ... HNSWGPU_CAPI_GUARD_END(ret)`

@@ -4,7 +4,10 @@
   * the forest form alone on its device entry (hnswhdb_forest_device, the forest already in HBM; it builds the dendrogram
     itself) next to what a caller did before: hnswgpu_forest_dendrogram_device, the dendrogram and the weights downloaded (timed on
     their own, from HBM into pageable host arrays) and one pass of the SAME definitions on ONE host core -- compiled C++ (g++ -O2,
-    built into a temporary directory when the tool starts; without a compiler the tool says so and leaves the pass out).
+    built into a temporary directory when the tool starts; without a compiler the tool says so and leaves the pass out);
+  * the selection alone (hnswhds_select_device) on the condensed tree that the device form left in HBM: at the defaults, checked
+    byte for byte against the first stage's own selection, and with allow_single_cluster, an epsilon at the median birth weight and
+    max_cluster_size = n / 100.
 n x 128 DistL2 (clustered, the data of tools/spanning_forest_rate.py), the index built in the process (GPU-assisted, M = 16,
 ef_construction 64).
     hdbscan_rate.py --n 100000
@@ -210,9 +213,29 @@ def main():
         assert rc == 0, H._native.last_error()
     out["forest_hdbscan_device_s"] = timed(device_form, a.warmup, a.repeats)
     out["forest_dendrogram_device_s"] = timed(dendrogram_form, a.warmup, a.repeats)
+    # the selection alone on the condensed tree that the device form left in HBM (hnswhds_select_device): at the defaults, where it
+    # must give the first stage's own bytes, and with the three options set
+    kk = r.n_clusters
+    s_out = [torch.zeros(slots, dtype=torch.uint8, device="cuda")] + [torch.zeros(n, dtype=torch.int32, device="cuda") for _ in range(3)]
+    s_out += [torch.zeros(slots, dtype=torch.float64, device="cuda")]
+    n_labels = np.zeros(1, np.uint64)
+    births = r.cluster_birth_w[np.isfinite(r.cluster_birth_w)]
+    eps = float(np.float32(np.median(births)) * np.float32(1.0001)) if len(births) else 1.0
+    tree = [ptr(d_out[i]) for i in (4, 5, 6, 7, 2, 3)]
+    torch.cuda.synchronize()
+
+    def select_form(allow, e, max_size):
+        rc = L.hnswhds_select_device(0, n, kk, *tree, 0, allow, e, max_size, *[ptr(t) for t in s_out], n_labels.ctypes.data, None)
+        assert rc == 0, H._native.last_error()
+    out["select_options"] = dict(allow_single_cluster=1, cluster_selection_epsilon=eps, max_cluster_size=n // 100)
+    out["select_device_options_s"] = timed(lambda: select_form(1, eps, n // 100), a.warmup, a.repeats)
+    out["select_options_labels"] = int(n_labels[0])
+    out["select_device_s"] = timed(lambda: select_form(0, 0.0, 0), a.warmup, a.repeats)
+    sel = [t.cpu().numpy() for t in s_out]
+    assert int(n_labels[0]) == r.n_labels and sel[0][:kk].tobytes() == r.selected.astype(np.uint8).tobytes() and sel[1].tobytes() == r.labels.tobytes()
+    assert sel[2].view(np.float32).tobytes() == r.probabilities.tobytes()
     got = [t.cpu().numpy() for t in d_out]
     assert (int(counts[0]), int(counts[1])) == (r.n_clusters, r.n_labels)
-    kk = r.n_clusters
     for x, y in ((got[0], r.labels), (got[1].view(np.float32), r.probabilities), (got[2].view(np.uint32), r.point_cluster),
                  (got[3].view(np.float32), r.point_w), (got[4].view(np.uint32)[:kk], r.cluster_parent), (got[5].view(np.float32)[:kk], r.cluster_birth_w),
                  (got[6].view(np.uint32)[:kk], r.cluster_size), (got[7][:kk], r.stability), (got[8][:kk], r.selected.astype(np.uint8))):
