@@ -308,6 +308,7 @@ class HdbscanResult:
         self.stability, self.selected, self.n_clusters, self.n_labels = stability, selected, n_clusters, n_labels
         self.forest, self.dendrogram = forest, dendrogram
         self.outlier_scores, self.cluster_death_lambda = outlier_scores, cluster_death_lambda
+        self.knn_params = None  # Hnsw.hdbscan: the (knbn, ef, core_k) it ran with, what Hnsw.hdbscan_predict defaults to
 
     def select(self, method="eom", allow_single_cluster=False, cluster_selection_epsilon=0.0, max_cluster_size=None, device=0):
         """The selection made again on this result's condensed tree, on `device`, without the tree being made again
@@ -333,9 +334,11 @@ class HdbscanResult:
         _check(N.lib().hnswhds_select(device, n, k, *[_p(x) if len(x) else None for x in tree + points], code, int(bool(allow_single_cluster)),
                                       float(cluster_selection_epsilon), max_size, _p(selected), _p(labels), _p(prob), _p(score), _p(death),
                                       _p(n_labels)))
-        return HdbscanResult(labels[:n].copy(), prob[:n].copy(), self.point_cluster, self.point_w, self.cluster_parent, self.cluster_birth_w,
-                             self.cluster_size, self.stability, selected[:k].astype(bool), k, int(n_labels[0]), self.forest, self.dendrogram,
-                             score[:n].copy(), death[:k].copy())
+        res = HdbscanResult(labels[:n].copy(), prob[:n].copy(), self.point_cluster, self.point_w, self.cluster_parent, self.cluster_birth_w,
+                            self.cluster_size, self.stability, selected[:k].astype(bool), k, int(n_labels[0]), self.forest, self.dendrogram,
+                            score[:n].copy(), death[:k].copy())
+        res.knn_params = self.knn_params
+        return res
 
     def condensed_tree(self):
         """The condensed tree as rows (parent, child, lambda, child_size) in sklearn's CONDENSED_dtype layout ('parent' and 'child'
@@ -354,6 +357,70 @@ class HdbscanResult:
         rows["value"][len(c):] = _lambda_of(self.point_w)
         rows["cluster_size"][len(c):] = 1
         return rows
+
+
+class PredictResult:
+    """The assignment of nq new points to the clusters of an HdbscanResult (hdbscan_assign, Hnsw.hdbscan_predict), as
+    include/hnsw_mi355x_hdbscan_predict.h defines it.  Per query: labels (i32, the stored points' labels, -1: noise), probabilities
+    (f32), outlier_scores (f32, GLOSH; None unless the result holds cluster_death_lambda), nearest (u32, the POSITION of the nearest
+    stored point under mutual reachability, 0xFFFFFFFF for a query without a neighbour), weights (f32, that mutual-reachability
+    distance) and clusters (u32, the cluster of the condensed tree the query falls into)."""
+
+    def __init__(self, labels, probabilities, outlier_scores, nearest, weights, clusters):
+        self.labels, self.probabilities, self.outlier_scores = labels, probabilities, outlier_scores
+        self.nearest, self.weights, self.clusters = nearest, weights, clusters
+
+
+class _PredictArrays:
+    """the tree arguments and the out arrays of one hnswhdp_assign / hnswhdp_predict call over nq queries"""
+
+    def __init__(self, result, core, nq, cluster_selection_epsilon):
+        n, k = len(result.labels), int(result.n_clusters)
+        self.n, self.k, self.nq, self.eps = n, k, nq, float(cluster_selection_epsilon)
+        core = np.ascontiguousarray(core, dtype=np.float32).reshape(-1)
+        if len(core) != n:
+            raise HnswError(N.ERR_ARG, f"core has {len(core)} entries, the result has {n} vertices")
+        self.inputs = [core, np.ascontiguousarray(result.cluster_parent[:k], dtype=np.uint32),
+                       np.ascontiguousarray(result.cluster_birth_w[:k], dtype=np.float32),
+                       np.ascontiguousarray(result.point_cluster[:n], dtype=np.uint32), np.ascontiguousarray(result.point_w[:n], dtype=np.float32),
+                       np.ascontiguousarray(result.selected[:k], dtype=np.uint8)]
+        death = result.cluster_death_lambda
+        self.death = None if death is None else np.ascontiguousarray(death[:k] if k else np.zeros(1), dtype=np.float64)  # (K == 0: never read)
+        m = max(nq, 1)
+        self.labels, self.prob = np.full(m, -1, np.int32), np.zeros(m, np.float32)
+        self.score = None if self.death is None else np.zeros(m, np.float32)
+        self.nearest, self.w, self.cluster = np.zeros(m, np.uint32), np.zeros(m, np.float32), np.zeros(m, np.uint32)
+
+    def tree(self):
+        """(core, K, cluster_parent, cluster_birth_w, point_cluster, point_w, selected, eps, death): a call's arguments between core_k
+        / n and the outputs"""
+        core, parent, birth, pc, pw, sel = [_p(x) if len(x) else None for x in self.inputs]
+        return (core, self.k, parent, birth, pc, pw, sel, self.eps, None if self.death is None else _p(self.death))
+
+    def outputs(self):
+        return (_p(self.labels), _p(self.prob), None if self.score is None else _p(self.score), _p(self.nearest), _p(self.w), _p(self.cluster))
+
+    def result(self):
+        nq = self.nq
+        return PredictResult(self.labels[:nq].copy(), self.prob[:nq].copy(), None if self.score is None else self.score[:nq].copy(),
+                             self.nearest[:nq].copy(), self.w[:nq].copy(), self.cluster[:nq].copy())
+
+
+def hdbscan_assign(result, core, nbr_pos, nbr_dist, counts, core_k, cluster_selection_epsilon=0.0, device=0):
+    """New points assigned to the clusters of `result` (an HdbscanResult) from their neighbour rows, on `device`, no index needed
+    (include/hnsw_mi355x_hdbscan_predict.h, hnswhdp_assign): nbr_pos (nq, knbn) u32 POSITIONS of stored points, nbr_dist (nq, knbn)
+    f32 and counts (nq) the used slots of each row; core (n) the stored points' core distances (Hnsw.core_distances) and core_k the
+    slot of a row that is the query's own; cluster_selection_epsilon as the selection had it.  Returns a PredictResult."""
+    nbr_pos = np.ascontiguousarray(nbr_pos, dtype=np.uint32)
+    nbr_dist = np.ascontiguousarray(nbr_dist, dtype=np.float32)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    if nbr_pos.ndim != 2 or nbr_pos.shape != nbr_dist.shape or len(counts) != nbr_pos.shape[0]:
+        raise HnswError(N.ERR_ARG, "nbr_pos and nbr_dist must be (nq, knbn) matrices of one shape, counts (nq)")
+    nq, knbn = nbr_pos.shape
+    o = _PredictArrays(result, core, nq, cluster_selection_epsilon)
+    rows = [_p(x) if x.size else None for x in (nbr_pos, nbr_dist, counts)]
+    _check(N.lib().hnswhdp_assign(device, nq, knbn, *rows, core_k, o.n, *o.tree(), *o.outputs()))
+    return o.result()
 
 
 _METHODS = {"eom": "HNSWGPU_SELECT_EOM", "leaf": "HNSWGPU_SELECT_LEAF"}
@@ -995,13 +1062,71 @@ class Hnsw:
             if core_k > knbn:
                 raise HnswError(N.ERR_ARG, "core_k is above knbn")
             res = o.result(SpanningForestResult(a[:0], b[:0], w[:0], 0, 0), DendrogramResult(left[:0], right[:0], sizes[:0], 0, 0, a[:0], b[:0], w[:0]))
+            res.knn_params = (knbn, ef, core_k)
             return _select_behind(res, method, 0, allow_single_cluster, cluster_selection_epsilon, max_cluster_size, outlier_scores)
         _check(self._lib.hnswhdb_graph(self._h, knbn, 0 if ef is None else ef, modes[mode], core_k, int(min_cluster_size), code, _p(a), _p(b),
                                                _p(w), _p(left), _p(right), _p(sizes), *o.pointers(), _p(m)))
         m = int(m[0])
         a, b, w = a[:m].copy(), b[:m].copy(), w[:m].copy()
         res = o.result(SpanningForestResult(a, b, w, m, n), DendrogramResult(left[:m].copy(), right[:m].copy(), sizes[:m].copy(), m, n, a, b, w))
+        res.knn_params = (knbn, ef, core_k)
         return _select_behind(res, method, 0, allow_single_cluster, cluster_selection_epsilon, max_cluster_size, outlier_scores)
+
+    def core_distances(self, knbn, ef=None, core_k=0):
+        """The stored points' core distances, f32 per POSITION: exactly what knn_graph_spanning_forest and hdbscan use with the same
+        knbn, ef and core_k -- the distance to a point's core_k-th neighbour in the directed graph (the last one of a shorter row),
+        0 for core_k == 0 (hnswhdp_core_distances)."""
+        if ef is not None and ef < 1:
+            raise HnswError(N.ERR_ARG, "ef must be >= 1 (ef=None: the exact graph)")
+        if core_k < 0:
+            raise HnswError(N.ERR_ARG, "core_k must be >= 0")
+        n = self.get_nb_point()
+        core = np.zeros(max(n, 1), np.float32)
+        if self._h is None:
+            if knbn < 1:
+                raise HnswError(N.ERR_ARG, "knbn must be > 0")
+            if core_k > knbn:
+                raise HnswError(N.ERR_ARG, "core_k is above knbn")
+            return core[:0]
+        _check(self._lib.hnswhdp_core_distances(self._h, knbn, 0 if ef is None else ef, core_k, _p(core)))
+        return core[:n]
+
+    def hdbscan_predict(self, result, datas, knbn=None, ef=None, core_k=None, core=None, cluster_selection_epsilon=0.0):
+        """The (nq, d) new vectors `datas` assigned to the clusters of `result`, an HdbscanResult of this index's points -- what the
+        hdbscan package calls approximate_predict -- in one call on the device: the search for each vector's knbn neighbours
+        (ef=None: the exact search), their positions, and hdbscan_assign on those rows (hnswhdp_predict).  core_k and ef default to
+        what Hnsw.hdbscan ran with (result.knn_params), knbn to 2 (core_k + 1); core=None calls core_distances with that call's knbn,
+        ef and core_k first.  cluster_selection_epsilon as the selection had it.  Returns a PredictResult."""
+        datas = np.ascontiguousarray(datas, dtype=np.float32)
+        if datas.ndim != 2:
+            raise HnswError(N.ERR_ARG, "datas must be a (nq, d) matrix")
+        ran = result.knn_params
+        if core_k is None:
+            if ran is None:
+                raise HnswError(N.ERR_ARG, "core_k=None needs a result of Hnsw.hdbscan (result.knn_params)")
+            core_k = ran[2]
+        if ef is None and ran is not None:
+            ef = ran[1]
+        if ef is not None and ef < 1:
+            raise HnswError(N.ERR_ARG, "ef must be >= 1 (ef=None: the exact search)")
+        if knbn is None:
+            knbn = 2 * (core_k + 1)
+        if core is None:
+            if ran is None:
+                raise HnswError(N.ERR_ARG, "core=None needs a result of Hnsw.hdbscan (result.knn_params)")
+            core = self.core_distances(ran[0], ran[1], ran[2])
+        nq, d = datas.shape
+        o = _PredictArrays(result, core, nq, cluster_selection_epsilon)
+        if o.n != self.get_nb_point():
+            raise HnswError(N.ERR_ARG, f"the result has {o.n} vertices, the index {self.get_nb_point()} points")
+        if self._h is None:  # no point: every row is empty
+            if knbn < 1:
+                raise HnswError(N.ERR_ARG, "knbn must be > 0")
+            _check(self._lib.hnswhdp_assign(0, nq, knbn, _p(np.zeros((max(nq, 1), knbn), np.uint32)), _p(np.zeros((max(nq, 1), knbn), np.float32)),
+                                            _p(np.zeros(max(nq, 1), np.uint32)), min(core_k, knbn), 0, *o.tree(), *o.outputs()))
+            return o.result()
+        _check(self._lib.hnswhdp_predict(self._h, _p(datas) if nq else None, nq, d, knbn, 0 if ef is None else ef, core_k, *o.tree(), *o.outputs()))
+        return o.result()
 
     def knn_graph_recall(self, knbn, ef, point_ids=None):
         """The recall by id of knn_graph_flat against exact_knn_graph_flat over the named points: the share of the exact

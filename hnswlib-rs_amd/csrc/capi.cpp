@@ -1659,6 +1659,189 @@ int hnswhds_select_device(int device, uint64_t n, uint64_t K, const uint32_t* d_
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
+// ---- HDBSCAN, third stage: new points assigned to the clusters of a condensed tree
+// (hnsw_mi355x_hdbscan_predict.h; cluster_predict.hip holds the device side)
+static int core_distances_pair(const hnswgpu_index* cidx, const CoreDistancesArgs& a, bool host, void* stream) {
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    // what hnswgpu_graph_spanning_forest refuses of the same knbn, ef and core_k, in its words
+    if (a.k == 0) return fail(HNSWGPU_ERR_ARG, "knbn must be > 0");
+    if (a.core_k > a.k)
+        return fail(HNSWGPU_ERR_ARG, "core_k = " + std::to_string(a.core_k) + " is above knbn = " + std::to_string(a.k) + ": a row of D has knbn slots");
+    int rc = directed_graph_source(idx, "core distances", a.k, a.ef);
+    if (rc != HNSWGPU_OK) return rc;
+    if (index_empty(idx)) return HNSWGPU_OK;  // no point: nothing written
+    if (!a.out_core) return fail(HNSWGPU_ERR_ARG, "null out_core");
+    if (!hnswgpu::core_distances) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = call_replica(idx, sl, host, true, true, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    return finish(hnswgpu::core_distances(*dev, idx->flat->origin_id, a, host, stream, err), err);
+}
+
+int hnswhdp_core_distances(const hnswgpu_index* idx, uint64_t knbn, uint64_t ef, uint64_t core_k, float* out_core) {
+    CAPI_GUARD_BEGIN
+    return core_distances_pair(idx, CoreDistancesArgs{knbn, ef, core_k, out_core}, true, nullptr);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswhdp_core_distances_device(const hnswgpu_index* idx, uint64_t knbn, uint64_t ef, uint64_t core_k, float* d_out_core, void* stream) {
+    CAPI_GUARD_BEGIN
+    return core_distances_pair(idx, CoreDistancesArgs{knbn, ef, core_k, d_out_core}, false, stream);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+// what both forms of both pairs check without reading an array, in the header's order
+static int predict_shape_check(const PredictTree& t, uint64_t nq, uint64_t k, uint64_t core_k) {
+    if (!(t.eps >= 0.0f)) return fail(HNSWGPU_ERR_ARG, "cluster_selection_epsilon is NaN or negative: it must be a weight, 0 or more");
+    if (core_k > k)
+        return fail(HNSWGPU_ERR_ARG, "core_k = " + std::to_string(core_k) + " is above knbn = " + std::to_string(k) + ": a row has knbn slots");
+    if (k == 0 && nq != 0) return fail(HNSWGPU_ERR_ARG, "knbn must be > 0");
+    if (t.n > 0x7FFFFFFFull) return fail(HNSWGPU_ERR_ARG, "hdbscan predict: n = " + std::to_string(t.n) + " vertices, above 2^31 - 1");
+    if (t.clusters > 0x7FFFFFFFull) return fail(HNSWGPU_ERR_ARG, "hdbscan predict: K = " + std::to_string(t.clusters) + " clusters, above 2^31 - 1");
+    if (nq > 0x7FFFFFFFull) return fail(HNSWGPU_ERR_ARG, "hdbscan predict: nq = " + std::to_string(nq) + " queries, above 2^31 - 1");
+    if (k != 0 && nq > 0x7FFFFFFFull / k)
+        return fail(HNSWGPU_ERR_ARG, "hdbscan predict: nq x knbn = " + std::to_string(nq) + " x " + std::to_string(k) + " slots, above 2^31 - 1");
+    if (t.clusters == 0 && t.n != 0)
+        return fail(HNSWGPU_ERR_ARG, "hdbscan predict: K = 0 clusters over " + std::to_string(t.n) + " vertices: cluster 0 is always there");
+    return HNSWGPU_OK;
+}
+// ... and the arrays that a call with a query needs
+static int predict_arrays_check(const PredictTree& t, const PredictOut& o) {
+    if (t.n != 0 && (!t.core || !t.point_cluster || !t.point_w)) return fail(HNSWGPU_ERR_ARG, "null core, point_cluster or point_w");
+    if (t.clusters != 0 && (!t.cluster_parent || !t.cluster_birth_w || !t.selected))
+        return fail(HNSWGPU_ERR_ARG, "null cluster_parent, cluster_birth_w or selected");
+    if (!o.labels) return fail(HNSWGPU_ERR_ARG, "null out_labels");
+    if (o.score && !t.death) return fail(HNSWGPU_ERR_ARG, "out_score without cluster_death_lambda: the score is GLOSH's, from each cluster's death");
+    return HNSWGPU_OK;
+}
+// the tree as a host form reads it, as the device form's kernel checks it
+static int predict_tree_check(const PredictTree& t) {
+    if (t.clusters != 0 && t.cluster_parent[0] != 0xFFFFFFFFu) return fail(HNSWGPU_ERR_ARG, "hdbscan predict: refused: cluster_parent[0] is not UINT32_MAX");
+    for (uint64_t c = 1; c < t.clusters; ++c)
+        if (t.cluster_parent[c] >= c)
+            return fail(HNSWGPU_ERR_ARG, "hdbscan predict: refused: a cluster_parent[c] is not below c (cluster " + std::to_string(c) + ")");
+    for (uint64_t v = 0; v < t.n; ++v)
+        if (t.point_cluster[v] >= t.clusters)
+            return fail(HNSWGPU_ERR_ARG, "hdbscan predict: refused: a point_cluster[v] is not below K (vertex " + std::to_string(v) + ")");
+    return HNSWGPU_OK;
+}
+
+static int hdbscan_assign_pair(const HdbscanAssignArgs& a, bool host, void* stream) {
+    int rc = predict_shape_check(a.tree, a.nq, a.k, a.core_k);
+    if (rc != HNSWGPU_OK) return rc;
+    if (a.nq == 0) return HNSWGPU_OK;  // no query: no array is read or written
+    if (!a.nbr_pos || !a.nbr_dist || !a.counts) return fail(HNSWGPU_ERR_ARG, "null nbr_pos, nbr_dist or counts");
+    rc = predict_arrays_check(a.tree, a.out);
+    if (rc != HNSWGPU_OK) return rc;
+    if (host) {
+        rc = predict_tree_check(a.tree);
+        if (rc != HNSWGPU_OK) return rc;
+        for (uint64_t q = 0; q < a.nq; ++q) {
+            if (a.counts[q] > a.k)
+                return fail(HNSWGPU_ERR_ARG, "hdbscan predict: refused: a counts[q] is above knbn (query " + std::to_string(q) + ")");
+            for (uint64_t s = 0; s < a.counts[q]; ++s)
+                if (a.nbr_pos[q * a.k + s] >= a.tree.n)
+                    return fail(HNSWGPU_ERR_ARG, "hdbscan predict: refused: a used nbr_pos is not below n (query " + std::to_string(q) + ")");
+        }
+    }
+    if (!hnswgpu::hdbscan_assign) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    std::string err;
+    return finish(hnswgpu::hdbscan_assign(a, host, stream, err), err);
+}
+
+int hnswhdp_assign(int device, uint64_t nq, uint64_t knbn, const uint32_t* nbr_pos, const float* nbr_dist, const uint32_t* counts, uint64_t core_k,
+                   uint64_t n, const float* core, uint64_t K, const uint32_t* cluster_parent, const float* cluster_birth_w, const uint32_t* point_cluster,
+                   const float* point_w, const uint8_t* selected, float cluster_selection_epsilon, const double* cluster_death_lambda,
+                   int32_t* out_labels, float* out_prob, float* out_score, uint32_t* out_nearest, float* out_w, uint32_t* out_cluster) {
+    CAPI_GUARD_BEGIN
+    const HdbscanAssignArgs a{device, nq, knbn, nbr_pos, nbr_dist, counts, core_k,
+                              PredictTree{n, K, core, cluster_parent, cluster_birth_w, point_cluster, point_w, selected, cluster_selection_epsilon,
+                                          cluster_death_lambda},
+                              PredictOut{out_labels, out_prob, out_score, out_nearest, out_w, out_cluster}};
+    return hdbscan_assign_pair(a, true, nullptr);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswhdp_assign_device(int device, uint64_t nq, uint64_t knbn, const uint32_t* d_nbr_pos, const float* d_nbr_dist, const uint32_t* d_counts,
+                          uint64_t core_k, uint64_t n, const float* d_core, uint64_t K, const uint32_t* d_cluster_parent, const float* d_cluster_birth_w,
+                          const uint32_t* d_point_cluster, const float* d_point_w, const uint8_t* d_selected, float cluster_selection_epsilon,
+                          const double* d_cluster_death_lambda, int32_t* d_out_labels, float* d_out_prob, float* d_out_score, uint32_t* d_out_nearest,
+                          float* d_out_w, uint32_t* d_out_cluster, void* stream) {
+    CAPI_GUARD_BEGIN
+    const HdbscanAssignArgs a{device, nq, knbn, d_nbr_pos, d_nbr_dist, d_counts, core_k,
+                              PredictTree{n, K, d_core, d_cluster_parent, d_cluster_birth_w, d_point_cluster, d_point_w, d_selected,
+                                          cluster_selection_epsilon, d_cluster_death_lambda},
+                              PredictOut{d_out_labels, d_out_prob, d_out_score, d_out_nearest, d_out_w, d_out_cluster}};
+    return hdbscan_assign_pair(a, false, stream);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+// (b: the call as the entry built it; its tree's n is filled in here, from the index)
+static int hdbscan_predict_pair(const hnswgpu_index* cidx, const HdbscanPredictArgs& b, bool host, void* stream) {
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    HdbscanPredictArgs a = b;
+    a.tree.n = index_nb_point(idx);
+    int rc = capi_refuse_f16(idx, "hdbscan predict (it names positions)");
+    if (rc != HNSWGPU_OK) return rc;
+    rc = predict_shape_check(a.tree, a.nq, a.k, a.core_k);
+    if (rc != HNSWGPU_OK) return rc;
+    if (a.nq == 0) return HNSWGPU_OK;  // no query: no array is read or written
+    if (!a.queries) return fail(HNSWGPU_ERR_ARG, "null buffer");
+    rc = predict_arrays_check(a.tree, a.out);
+    if (rc != HNSWGPU_OK) return rc;
+    if (a.ef == 0) {  // the limits of the exact call, in its words (the answers are staged: no buffer of the caller's to check)
+        rc = check_exact_call(idx, a.queries, a.nq, a.d, a.k, nullptr, 0, a.queries, a.queries, a.queries);
+        if (rc != HNSWGPU_OK) return rc;
+    }
+    if (host) {
+        rc = predict_tree_check(a.tree);
+        if (rc != HNSWGPU_OK) return rc;
+    }
+    std::string err;
+    if (a.tree.n == 0) {  // no point: every row is empty, on the handle's device (host form) or the caller's current one
+        if (!hnswgpu::hdbscan_assign) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+        const HdbscanAssignArgs rows{host ? std::max(idx->primary, 0) : -1, a.nq, 0, nullptr, nullptr, nullptr, 0, a.tree, a.out};
+        return finish(hnswgpu::hdbscan_assign(rows, host, stream, err), err);
+    }
+    if (!hnswgpu::hdbscan_predict) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = call_replica(idx, sl, host, true, true, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    return finish(hnswgpu::hdbscan_predict(*dev, idx->flat->origin_id, a, host, stream, err), err);
+}
+
+int hnswhdp_predict(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, uint64_t knbn, uint64_t ef, uint64_t core_k, const float* core,
+                    uint64_t K, const uint32_t* cluster_parent, const float* cluster_birth_w, const uint32_t* point_cluster, const float* point_w,
+                    const uint8_t* selected, float cluster_selection_epsilon, const double* cluster_death_lambda, int32_t* out_labels, float* out_prob,
+                    float* out_score, uint32_t* out_nearest, float* out_w, uint32_t* out_cluster) {
+    CAPI_GUARD_BEGIN
+    const HdbscanPredictArgs a{queries, nq, d, knbn, ef, core_k,
+                               PredictTree{0, K, core, cluster_parent, cluster_birth_w, point_cluster, point_w, selected, cluster_selection_epsilon,
+                                           cluster_death_lambda},
+                               PredictOut{out_labels, out_prob, out_score, out_nearest, out_w, out_cluster}};
+    return hdbscan_predict_pair(idx, a, true, nullptr);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswhdp_predict_device(const hnswgpu_index* idx, const float* d_queries, uint64_t nq, uint64_t d, uint64_t knbn, uint64_t ef, uint64_t core_k,
+                           const float* d_core, uint64_t K, const uint32_t* d_cluster_parent, const float* d_cluster_birth_w,
+                           const uint32_t* d_point_cluster, const float* d_point_w, const uint8_t* d_selected, float cluster_selection_epsilon,
+                           const double* d_cluster_death_lambda, int32_t* d_out_labels, float* d_out_prob, float* d_out_score, uint32_t* d_out_nearest,
+                           float* d_out_w, uint32_t* d_out_cluster, void* stream) {
+    CAPI_GUARD_BEGIN
+    const HdbscanPredictArgs a{d_queries, nq, d, knbn, ef, core_k,
+                               PredictTree{0, K, d_core, d_cluster_parent, d_cluster_birth_w, d_point_cluster, d_point_w, d_selected,
+                                           cluster_selection_epsilon, d_cluster_death_lambda},
+                               PredictOut{d_out_labels, d_out_prob, d_out_score, d_out_nearest, d_out_w, d_out_cluster}};
+    return hdbscan_predict_pair(idx, a, false, stream);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
 static DeviceIndex* any_replica(hnswgpu_index* idx) {
     if (idx->primary >= 0 && idx->replica(idx->primary)) return idx->replica(idx->primary);
     return nullptr;

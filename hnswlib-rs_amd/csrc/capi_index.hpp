@@ -1,7 +1,7 @@
-// capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h (and its extensions hnsw_mi355x_hdbscan.h and hnsw_mi355x_hdbscan_select.h),
+// capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h (and its extensions hnsw_mi355x_hdbscan.h, hnsw_mi355x_hdbscan_select.h and hnsw_mi355x_hdbscan_predict.h),
 // for the translation units that implement the C ABI: capi.cpp, which holds the entries, and the .hip units that hold their device
 // side (exact_knn.hip, which also holds hnswgpu_exact_search_batch(_device) itself; range_search.hip; symmetric_graph.hip;
-// graph_components.hip; spanning_forest.hip; dendrogram.hip; condensed_tree.hip; cluster_select.hip).  Private: not installed, not part of the ABI.
+// graph_components.hip; spanning_forest.hip; dendrogram.hip; condensed_tree.hip; cluster_select.hip; cluster_predict.hip).  Private: not installed, not part of the ABI.
 // Three parts: the handle; the checks that entries share (empty index, resident replica, sorted filter, the limits of an exact call,
 // the zeroed k-NN answer, the tail), which live once, in capi.cpp, and are declared here as capi_* for the entries outside it; and
 // the device side of every host / _device pair, declared ONCE, here, with its arguments' struct (HNSWGPU_DEVICE_SIDE of
@@ -21,6 +21,7 @@
 #include "../../include/hnsw_mi355x.h"
 #include "../../include/hnsw_mi355x_hdbscan.h"
 #include "../../include/hnsw_mi355x_hdbscan_select.h"
+#include "../../include/hnsw_mi355x_hdbscan_predict.h"
 #include "builder.hpp"
 #include "flat_index.hpp"
 #include "search_device.hpp"
@@ -313,6 +314,52 @@ struct HdbscanSelectArgs {
     uint64_t* out_n_labels;
 };
 HNSWGPU_DEVICE_SIDE int hdbscan_select(const HdbscanSelectArgs& a, bool host, void* stream, std::string& err);
+// the device side of hnswhdp_core_distances(_device), hnswhdp_assign(_device) and hnswhdp_predict(_device), defined in
+// cluster_predict.hip (the arguments have been checked: what needs no device and, in the host forms, the tree and the rows on the
+// host).  host: the arrays are plain host memory; else device memory, checked by kernel before anything walks the tree or gathers, and
+// `stream` is the caller's.  ERR_ARG, no out slot written, when the checks refuse.
+struct CoreDistancesArgs {
+    uint64_t k, ef, core_k;  // core_k <= k
+    float* out_core;         // [n]
+};
+HNSWGPU_DEVICE_SIDE int core_distances(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const CoreDistancesArgs& a, bool host, void* stream, std::string& err);
+struct PredictTree {
+    uint64_t n, clusters;
+    const float* core;               // [n], like point_cluster and point_w
+    const uint32_t* cluster_parent;  // [clusters], like the two below
+    const float* cluster_birth_w;
+    const uint32_t* point_cluster;
+    const float* point_w;
+    const uint8_t* selected;
+    float eps;
+    const double* death;             // [clusters], may be nullptr
+};
+struct PredictOut {
+    int32_t* labels;    // [nq]
+    float* prob;        // [nq], may be nullptr, like every array below
+    float* score;
+    uint32_t* nearest;
+    float* w;
+    uint32_t* cluster;
+};
+struct HdbscanAssignArgs {
+    int device;               // below 0: the caller's current device (predict on an index without a point)
+    uint64_t nq, k;
+    const uint32_t* nbr_pos;  // nq x k, like nbr_dist
+    const float* nbr_dist;
+    const uint32_t* counts;   // [nq]; nullptr: every row is empty
+    uint64_t core_k;
+    PredictTree tree;
+    PredictOut out;
+};
+HNSWGPU_DEVICE_SIDE int hdbscan_assign(const HdbscanAssignArgs& a, bool host, void* stream, std::string& err);
+struct HdbscanPredictArgs {
+    const float* queries;  // nq x d
+    uint64_t nq, d, k, ef, core_k;
+    PredictTree tree;      // n: the index's points
+    PredictOut out;
+};
+HNSWGPU_DEVICE_SIDE int hdbscan_predict(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const HdbscanPredictArgs& a, bool host, void* stream, std::string& err);
 }  // namespace hnswgpu
 
 // No C++ exception may cross the C ABI: every entry point is `try { ... HNSWGPU_CAPI_GUARD_END(ret)`

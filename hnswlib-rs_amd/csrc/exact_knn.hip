@@ -1403,6 +1403,15 @@ int graph_order(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, 
     return OK;
 }
 
+// The exact k-NN of new vectors without a filter, for cluster_predict.hip (graph_internal.hpp): exact_device as
+// hnswgpu_exact_search_batch_device calls it
+int exact_queries_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* d_queries, uint64_t nq, uint64_t d, uint64_t k,
+                         uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, void* stream,
+                         std::string& err) {
+    return exact_device(dev, origin_id, d_queries, nq, d, k, nullptr, 0, false, nullptr, d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts,
+                        static_cast<hipStream_t>(stream), err);
+}
+
 }  // namespace hnswgpu
 #pragma clang diagnostic pop
 

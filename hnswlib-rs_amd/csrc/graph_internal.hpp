@@ -39,6 +39,13 @@ struct GraphOrder {
 // defined in exact_knn.hip: OK, or ERR_DEVICE with `err` set
 int graph_order(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, GraphOrder& out, std::string& err);
 
+// defined in exact_knn.hip: the exact k-NN of nq new vectors without a filter, every buffer device memory, exactly what
+// hnswgpu_exact_search_batch_device runs behind its checks (cluster_predict.hip: the rows of a prediction with ef == 0).  Waits for
+// `stream`.
+int exact_queries_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* d_queries, uint64_t nq, uint64_t d, uint64_t k,
+                         uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, void* stream,
+                         std::string& err);
+
 // D, staged: the graph path's own answer for every point (exact_graph for ef == 0, else graph_search), row i the point at position
 // i, n rows of k slots, counts[i] of them used.  One allocation of 17 n k + 4 n bytes (and padding); a slot's neighbour is the p_id
 // (layer, rank).
