@@ -18,6 +18,7 @@
 #include "../../include/hnsw_mi355x.h"
 #include "builder.hpp"
 #include "datamap.hpp"
+#include "dist_order.hpp"
 #include "flat_index.hpp"
 #include "hnswio.hpp"
 #include "search_device.hpp"
@@ -1474,15 +1475,6 @@ static int hdbscan_answer_check(uint64_t n, uint64_t mcs, uint32_t method, const
     if (n != 0 && !o.labels) return fail(HNSWGPU_ERR_ARG, "null out_labels");
     return HNSWGPU_OK;
 }
-// the order of the spanning forest's weights (graph_internal.hpp: dist_order_bits), on the host
-static uint32_t weight_order_bits(float v) {
-    uint32_t b;
-    std::memcpy(&b, &v, 4);
-    if (v != v) return 0xFFFFFFFFu;
-    if (b == 0x80000000u) b = 0u;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 static int forest_hdbscan_pair(const ForestHdbscanArgs& a, bool host, void* stream) {
     int rc = forest_shape_check(a.n, a.m);  // the dendrogram's checks, in its words, then the clustering's
     if (rc != HNSWGPU_OK) return rc;
@@ -1498,7 +1490,7 @@ static int forest_hdbscan_pair(const ForestHdbscanArgs& a, bool host, void* stre
         rc = forest_ends_check(a.n, a.m, a.a, a.b);
         if (rc != HNSWGPU_OK) return rc;
         for (uint64_t e = 1; e < a.m; ++e)
-            if (weight_order_bits(a.w[e - 1]) > weight_order_bits(a.w[e]))
+            if (hnswgpu::dist_order_bits(a.w[e - 1]) > hnswgpu::dist_order_bits(a.w[e]))  // (dist_order.hpp: the kernel's order)
                 return fail(HNSWGPU_ERR_ARG, "forest hdbscan: the weights descend at edge " + std::to_string(e) +
                                                  ": the edges' order is the merge order, ascending by weight");
     }
@@ -1584,26 +1576,24 @@ int hnswhdb_graph_device(const hnswgpu_index* idx, uint64_t k, uint64_t ef, uint
 
 // ---- HDBSCAN, second stage: the selection under its options, labels and GLOSH scores from a condensed tree
 // (hnsw_mi355x_hdbscan_select.h; cluster_select.hip holds the device side)
-// the tree as the host form reads it, as the device form's kernels check it
-static int select_tree_check(const HdbscanSelectArgs& a) {
-    const uint64_t K = a.clusters;
-    if (a.cluster_parent[0] != 0xFFFFFFFFu) return fail(HNSWGPU_ERR_ARG, "hdbscan select: not a condensed tree: cluster_parent[0] is not UINT32_MAX");
-    std::vector<uint8_t> kids(K, 0);
+// A condensed tree as a host form reads it, as the device forms' kernels check it (cluster_tree.hpp), in the words of `prefix`:
+// cluster_parent, point_cluster and, where it is there, stability -- with it, the number of children of every cluster other than 0.
+static int condensed_tree_check(const std::string& prefix, uint64_t n, uint64_t K, const uint32_t* parent, const uint32_t* point_cluster,
+                                const double* stability) {
+    if (K != 0 && parent[0] != 0xFFFFFFFFu) return fail(HNSWGPU_ERR_ARG, prefix + " cluster_parent[0] is not UINT32_MAX");
+    std::vector<uint8_t> kids(stability ? K : 0, 0);
     for (uint64_t c = 0; c < K; ++c) {
-        if (!(a.stability[c] >= 0.0))
-            return fail(HNSWGPU_ERR_ARG, "hdbscan select: not a condensed tree: a stability is NaN or negative (cluster " + std::to_string(c) + ")");
+        if (stability && !(stability[c] >= 0.0)) return fail(HNSWGPU_ERR_ARG, prefix + " a stability is NaN or negative (cluster " + std::to_string(c) + ")");
         if (c == 0) continue;
-        const uint32_t p = a.cluster_parent[c];
-        if (p >= c) return fail(HNSWGPU_ERR_ARG, "hdbscan select: not a condensed tree: a cluster_parent[c] is not below c (cluster " + std::to_string(c) + ")");
-        if (p != 0 && kids[p] < 3) ++kids[p];
+        const uint32_t p = parent[c];
+        if (p >= c) return fail(HNSWGPU_ERR_ARG, prefix + " a cluster_parent[c] is not below c (cluster " + std::to_string(c) + ")");
+        if (stability && p != 0 && kids[p] < 3) ++kids[p];
     }
-    for (uint64_t c = 1; c < K; ++c)
+    for (uint64_t c = 1; c < kids.size(); ++c)
         if (kids[c] != 0 && kids[c] != 2)
-            return fail(HNSWGPU_ERR_ARG, "hdbscan select: not a condensed tree: a cluster other than 0 has one child, or more than two (cluster " +
-                                             std::to_string(c) + ")");
-    for (uint64_t v = 0; v < a.n; ++v)
-        if (a.point_cluster[v] >= K)
-            return fail(HNSWGPU_ERR_ARG, "hdbscan select: not a condensed tree: a point_cluster[v] is not below K (vertex " + std::to_string(v) + ")");
+            return fail(HNSWGPU_ERR_ARG, prefix + " a cluster other than 0 has one child, or more than two (cluster " + std::to_string(c) + ")");
+    for (uint64_t v = 0; v < n; ++v)
+        if (point_cluster[v] >= K) return fail(HNSWGPU_ERR_ARG, prefix + " a point_cluster[v] is not below K (vertex " + std::to_string(v) + ")");
     return HNSWGPU_OK;
 }
 
@@ -1626,7 +1616,7 @@ static int hdbscan_select_pair(const HdbscanSelectArgs& a, bool host, void* stre
     if (!a.point_cluster || !a.point_w) return fail(HNSWGPU_ERR_ARG, "null point_cluster or point_w");
     if (!a.out_labels) return fail(HNSWGPU_ERR_ARG, "null out_labels");
     if (host) {
-        const int rc = select_tree_check(a);
+        const int rc = condensed_tree_check("hdbscan select: not a condensed tree:", a.n, a.clusters, a.cluster_parent, a.point_cluster, a.stability);
         if (rc != HNSWGPU_OK) return rc;
     }
     if (!hnswgpu::hdbscan_select) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
@@ -1717,16 +1707,8 @@ static int predict_arrays_check(const PredictTree& t, const PredictOut& o) {
     if (o.score && !t.death) return fail(HNSWGPU_ERR_ARG, "out_score without cluster_death_lambda: the score is GLOSH's, from each cluster's death");
     return HNSWGPU_OK;
 }
-// the tree as a host form reads it, as the device form's kernel checks it
 static int predict_tree_check(const PredictTree& t) {
-    if (t.clusters != 0 && t.cluster_parent[0] != 0xFFFFFFFFu) return fail(HNSWGPU_ERR_ARG, "hdbscan predict: refused: cluster_parent[0] is not UINT32_MAX");
-    for (uint64_t c = 1; c < t.clusters; ++c)
-        if (t.cluster_parent[c] >= c)
-            return fail(HNSWGPU_ERR_ARG, "hdbscan predict: refused: a cluster_parent[c] is not below c (cluster " + std::to_string(c) + ")");
-    for (uint64_t v = 0; v < t.n; ++v)
-        if (t.point_cluster[v] >= t.clusters)
-            return fail(HNSWGPU_ERR_ARG, "hdbscan predict: refused: a point_cluster[v] is not below K (vertex " + std::to_string(v) + ")");
-    return HNSWGPU_OK;
+    return condensed_tree_check("hdbscan predict: refused:", t.n, t.clusters, t.cluster_parent, t.point_cluster, nullptr);
 }
 
 static int hdbscan_assign_pair(const HdbscanAssignArgs& a, bool host, void* stream) {

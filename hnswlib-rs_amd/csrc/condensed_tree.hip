@@ -25,17 +25,10 @@
 //   hd_segment_kernel    where each cluster's rows begin and end
 //   hd_stability_kernel  a block per cluster: thread t sums the terms t, t + 256, .. in order, then a tree over the 256 sums in
 //                        LDS.  The shape is a function of the segment alone: two calls give the same bytes.
-//   hd_eom_kernel        one thread per leaf cluster, ONE launch: it stores S, fences, and adds 1 to its parent's arrival counter.
-//                        The first arriver leaves; the second fences, loads both children's S (agent-scope loads), decides the
-//                        parent and goes on upwards.  Nobody waits.  A cluster other than 0 has no child or two, so the sum is one
-//                        add.  Children of cluster 0 go no further.  (HNSWGPU_SELECT_LEAF: a leaf wins, nothing climbs.)
-//   hd_jump_*_kernel     pointer doubling over the K clusters, rounds counted on the host: (jump, best) with best the highest
-//                        winner among the clusters from c up to, not including, jump.  At the end jump is 0 and best[c] is the
-//                        highest winning ancestor-or-self of c other than 0: c is selected iff best[c] == c, and best[c] is the
-//                        selected ancestor-or-self of c.  Two buffers take turns: a round reads one and writes the other.
-//   rocPRIM scan         of the selected flags: the labels.  L is read back at the end.
-//   hd_label_kernel      one thread per vertex: label and probability
-// Every loop ends: cc_find / cc_unite descend strictly, the climb of hd_eom_kernel goes to a smaller cluster index each step, the
+//   select_clusters      the selection (excess of mass, or the leaves), the labels' numbers and per vertex label and probability:
+//                        cluster_select.hip's, through cluster_tree.hpp, with the options off -- no single cluster, no epsilon, no
+//                        size limit, no score.  This library's own tree needs no check.  L is read back at the end.
+// Every loop ends: cc_find / cc_unite descend strictly, the selection's climb goes to a smaller cluster index each step, its
 // doubling rounds are counted.  No wavefront waits on another; no floating-point atomic; everything is a function of the input.
 // Everything is computed into scratch, and the out arrays are written at the very end: a refusal touches none of them.
 #include <hip/hip_runtime.h>
@@ -44,6 +37,7 @@
 #include <string>
 
 #include "capi_index.hpp"
+#include "cluster_tree.hpp"
 #include "graph_internal.hpp"
 #include "hip_host.hpp"
 #include "hnswio.hpp"
@@ -57,19 +51,7 @@
 namespace hnswgpu {
 namespace {
 
-constexpr uint32_t NONE = 0xFFFFFFFFu, INF_BITS = 0x7F800000u;
 constexpr uint32_t W_DESCENT = 0, W_BIGROOTS = 1;  // the words of a call
-
-// nodes can pass 2^32 - 256: a thread's number is taken in 64 bits
-__device__ __forceinline__ uint64_t thread_number() { return (uint64_t)blockIdx.x * 256u + threadIdx.x; }
-
-// lambda of a weight's stored bits: 1 / w in f64; +0 for +inf and NaN; +inf for w <= 0, -0 included
-__device__ __forceinline__ double lambda_of(uint32_t bits) {
-    const float w = __uint_as_float(bits);
-    if (w != w || bits == INF_BITS) return 0.0;
-    if (w <= 0.0f) return __longlong_as_double(0x7FF0000000000000ll);
-    return 1.0 / (double)w;
-}
 
 // a row's term: three separate f64 operations (the unit is compiled with -ffp-contract=off); equal lambdas give 0 (inf - inf too)
 __device__ __forceinline__ double row_term(double l_row, double l_birth, uint32_t size) {
@@ -79,13 +61,6 @@ __device__ __forceinline__ double row_term(double l_row, double l_birth, uint32_
 }
 
 __device__ __forceinline__ uint32_t node_size(const uint32_t* __restrict__ size, uint32_t n, uint32_t x) { return x < n ? 1u : size[x - n]; }
-
-// lambdas are >= 0: the order of their f64 bits is their order.  The words only rise during a kernel, so a value at or above mine,
-// however old, says that mine cannot win: behind the load most threads skip the atomic.
-__device__ __forceinline__ void raise_lambda(unsigned long long* maxlam, uint32_t c, double l) {
-    const unsigned long long mine = (unsigned long long)__double_as_longlong(l);
-    if (__hip_atomic_load(maxlam + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < mine) atomicMax(maxlam + c, mine);
-}
 
 // one thread per edge from 1 on
 __global__ __launch_bounds__(256) void hd_descent_kernel(const float* __restrict__ w, uint32_t m, uint32_t* __restrict__ words) {
@@ -254,89 +229,6 @@ __global__ __launch_bounds__(256) void hd_stability_kernel(const double* __restr
     if (threadIdx.x == 0u) stability[c] = part[0];
 }
 
-__device__ __forceinline__ void publish_f64(unsigned long long* s, uint32_t c, double v) {
-    __hip_atomic_store(s + c, (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double fetch_f64(unsigned long long* s, uint32_t c) {
-    return __longlong_as_double((long long)__hip_atomic_load(s + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-
-// one thread per cluster; arrive, wins: 0 before.  The climb goes to a smaller index each step and leaves at a child of cluster 0.
-__global__ __launch_bounds__(256) void hd_eom_kernel(const uint32_t* __restrict__ parent, const uint32_t* __restrict__ child_lo,
-                                                    const uint32_t* __restrict__ child_hi, const double* __restrict__ stability, uint32_t clusters,
-                                                    uint32_t method, uint32_t* arrive, unsigned long long* s_of, uint32_t* __restrict__ wins) {
-    const uint64_t t = thread_number();
-    if (t == 0u || t >= clusters) return;
-    uint32_t cur = (uint32_t)t;
-    if (child_hi[cur] != 0u) return;  // not a leaf
-    wins[cur] = 1u;
-    if (method != HNSWGPU_SELECT_EOM) return;
-    publish_f64(s_of, cur, stability[cur]);
-    for (;;) {
-        const uint32_t p = parent[cur];
-        if (p == 0u || p >= cur) return;  // (p >= cur: never)
-        __threadfence();  // my S before my arrival
-        if (__hip_atomic_fetch_add(arrive + p, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;  // the sibling's subtree is still to come
-        __threadfence();  // the sibling's arrival before its S
-        const uint32_t lo = child_lo[p], hi = child_hi[p];
-        if (lo >= clusters || hi >= clusters) return;  // (never)
-        const double sum = fetch_f64(s_of, lo) + fetch_f64(s_of, hi), own = stability[p];
-        const bool win = own >= sum;  // a tie goes to the parent
-        wins[p] = win ? 1u : 0u;
-        publish_f64(s_of, p, win ? own : sum);
-        cur = p;
-    }
-}
-
-// (jump << 32) | best
-__global__ __launch_bounds__(256) void hd_jump_init_kernel(const uint32_t* __restrict__ parent, const uint32_t* __restrict__ wins, uint32_t clusters,
-                                                          uint64_t* __restrict__ state) {
-    const uint64_t c = thread_number();
-    if (c >= clusters) return;
-    state[c] = c == 0u ? (uint64_t)NONE : ((uint64_t)parent[c] << 32) | (wins[c] != 0u ? (uint32_t)c : NONE);
-}
-
-__global__ __launch_bounds__(256) void hd_jump_round_kernel(const uint64_t* __restrict__ from, uint32_t clusters, uint64_t* __restrict__ to) {
-    const uint64_t c = thread_number();
-    if (c >= clusters) return;
-    uint64_t mine = from[c];
-    const uint32_t j = (uint32_t)(mine >> 32);
-    if (j != 0u && j < clusters) {
-        const uint64_t above = from[j];
-        const uint32_t best = (uint32_t)above != NONE ? (uint32_t)above : (uint32_t)mine;  // the higher stretch goes first
-        mine = (above & 0xFFFFFFFF00000000ull) | best;
-    }
-    to[c] = mine;
-}
-
-// clusters + 1 threads: one per cluster, and one for the flag behind the last, which the scan reads
-__global__ __launch_bounds__(256) void hd_select_kernel(const uint64_t* __restrict__ state, uint32_t clusters, uint8_t* __restrict__ selected,
-                                                       uint32_t* __restrict__ selflag) {
-    const uint64_t c = thread_number();
-    if (c > clusters) return;
-    const bool sel = c != 0u && c < clusters && (uint32_t)state[c] == (uint32_t)c;
-    selflag[c] = sel ? 1u : 0u;
-    if (c < clusters) selected[c] = sel ? 1u : 0u;
-}
-
-// one thread per vertex
-__global__ __launch_bounds__(256) void hd_label_kernel(const uint32_t* __restrict__ point_cluster, const uint32_t* __restrict__ point_w,
-                                                      const uint64_t* __restrict__ state, const uint32_t* __restrict__ label_of,
-                                                      const unsigned long long* __restrict__ maxlam, uint32_t n, uint32_t clusters,
-                                                      int32_t* __restrict__ labels, float* __restrict__ prob) {
-    const uint64_t v = thread_number();
-    if (v >= n) return;
-    const uint32_t c = point_cluster[v], q = c < clusters ? (uint32_t)state[c] : NONE;
-    if (q == NONE || q >= clusters) {
-        labels[v] = -1;
-        prob[v] = 0.0f;
-        return;
-    }
-    labels[v] = (int32_t)label_of[q];
-    const double top = __longlong_as_double((long long)maxlam[q]), lam = lambda_of(point_w[v]);
-    prob[v] = (top == 0.0 || lam >= top) ? 1.0f : (float)(lam / top);
-}
-
 // a scan that has ended when this returns (its temporary storage goes here)
 int scan_u32(const uint32_t* in, uint32_t* out, uint64_t count, hipStream_t stream, std::string& err) {
     DevMem temp;
@@ -360,27 +252,25 @@ int clusters_of_dendrogram(const char* what, uint64_t n, uint64_t m, const float
     Drain drain{stream};
     // per node, per vertex, per row (twice: the sort's two sides), per cluster
     uint32_t *words, *par, *uf, *mark, *headflag, *hscan, *point_cluster, *point_w, *key_in, *key_out;
-    int32_t* labels;
-    float* prob;
     double *term_in, *term_out, *stability;
-    uint32_t *c_parent, *c_birth, *c_size, *child_lo, *child_hi, *arrive, *wins, *seg_begin, *seg_end, *selflag, *label_of;
-    unsigned long long *maxlam, *s_of;
-    uint64_t *state_a, *state_b;
-    uint8_t* selected;
+    uint32_t *c_parent, *c_birth, *c_size, *child_lo, *child_hi, *seg_begin, *seg_end;
+    unsigned long long* maxlam;
+    const SelectOptions opt{method, 0u, 0.0f, 0u};  // the first selection: no single cluster, no epsilon, no size limit
+    SelectScratch sel;
     ScratchLayout lay;
     lay.array(words, 64);
     lay.arrays(nodes, par, uf, mark);
     lay.arrays(nodes + 1, headflag, hscan);
-    lay.arrays(n, point_cluster, point_w, labels, prob);
+    lay.arrays(n, point_cluster, point_w);
     lay.arrays(rows_max, key_in, key_out, term_in, term_out);
     lay.arrays(slots, c_parent, c_birth, c_size, child_lo);
     // those that are 0 before their kernels stand together, from child_hi on
     const uint64_t zeroed_from = lay.size();
-    lay.arrays(slots, child_hi, arrive, wins, seg_begin, seg_end, maxlam);
+    lay.arrays(slots, child_hi, seg_begin, seg_end, maxlam);
+    sel.zeroed(lay, slots);
     const uint64_t zeroed_bytes = lay.size() - zeroed_from;
-    lay.arrays(slots, s_of, stability, state_a, state_b);
-    lay.arrays(slots + 1, selflag, label_of);
-    lay.array(selected, slots);
+    lay.array(stability, slots);
+    sel.rest(lay, n, slots, opt, false);
     int rc = alloc_layout(what, mem, lay, err);  // (before anything is written)
     if (rc != OK) return rc;
     uint32_t* zeroed = child_hi;
@@ -437,36 +327,15 @@ int clusters_of_dendrogram(const char* what, uint64_t n, uint64_t m, const float
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(hd_stability_kernel, dim3(k32), dim3(256), 0, stream, term_out, seg_begin, seg_end, stability);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(hd_eom_kernel, grid_of(clusters), dim3(256), 0, stream, c_parent, child_lo, child_hi, stability, k32, method, arrive, s_of, wins);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(hd_jump_init_kernel, grid_of(clusters), dim3(256), 0, stream, c_parent, wins, k32, state_a);
-    HIP_TRY(hipGetLastError());
-    for (uint64_t reach = 1; reach < clusters; reach *= 2) {  // a cluster's depth is below K
-        hipLaunchKernelGGL(hd_jump_round_kernel, grid_of(clusters), dim3(256), 0, stream, state_a, k32, state_b);
-        HIP_TRY(hipGetLastError());
-        std::swap(state_a, state_b);
-    }
-    hipLaunchKernelGGL(hd_select_kernel, grid_of(clusters + 1), dim3(256), 0, stream, state_a, k32, selected, selflag);
-    HIP_TRY(hipGetLastError());
-    rc = scan_u32(selflag, label_of, clusters + 1, stream, err);
-    if (rc != OK) return rc;
-    hipLaunchKernelGGL(hd_label_kernel, grid_of(n), dim3(256), 0, stream, point_cluster, point_w, state_a, label_of, maxlam, n32, k32, labels, prob);
-    HIP_TRY(hipGetLastError());
+    const ClusterTree tree{c_parent, c_birth, c_size, stability, point_cluster, point_w, n32, k32};
     uint32_t n_labels = 0;
-    HIP_TRY(hipMemcpyAsync(&n_labels, label_of + clusters, 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-
-    const hipMemcpyKind kind = host_out ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    const struct { void* to; const void* from; uint64_t bytes; } copies[] = {
-        {out.labels, labels, n * 4},          {out.prob, prob, n * 4},
-        {out.point_cluster, point_cluster, n * 4}, {out.point_w, point_w, n * 4},
-        {out.cluster_parent, c_parent, clusters * 4}, {out.cluster_birth_w, c_birth, clusters * 4},
-        {out.cluster_size, c_size, clusters * 4},     {out.stability, stability, clusters * 8},
-        {out.selected, selected, clusters},
-    };
-    for (const auto& c : copies)
-        if (c.to) HIP_TRY(hipMemcpyAsync(c.to, c.from, c.bytes, kind, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
+    rc = select_clusters(tree, ClusterKids{child_lo, child_hi, maxlam}, opt, sel, &n_labels, stream, err);
+    if (rc != OK) return rc;
+    rc = copy_out({{out.labels, sel.labels, n * 4}, {out.prob, sel.prob, n * 4}, {out.point_cluster, point_cluster, n * 4}, {out.point_w, point_w, n * 4},
+                   {out.cluster_parent, c_parent, clusters * 4}, {out.cluster_birth_w, c_birth, clusters * 4}, {out.cluster_size, c_size, clusters * 4},
+                   {out.stability, stability, clusters * 8}, {out.selected, sel.selected, clusters}},
+                  host_out, stream, err);
+    if (rc != OK) return rc;
     *out.n_clusters = clusters;
     *out.n_labels = n_labels;
     return OK;
@@ -489,21 +358,14 @@ int forest_hdbscan(const ForestHdbscanArgs& a, bool host, void* stream_v, std::s
     uint32_t *left = nullptr, *right = nullptr, *size = nullptr;
     if (a.m != 0) {
         // the dendrogram; behind it, for the host form, the forest
-        uint32_t *up_a = nullptr, *up_b = nullptr;
-        float* up_w = nullptr;
+        Uploads ups;
         ScratchLayout lay;
         lay.arrays(a.m, left, right, size);
-        if (host) lay.arrays(a.m, up_a, up_b, up_w);
+        if (host) ups.brings(lay, a.m, d_a, d_b, d_w);
         rc = alloc_layout("forest hdbscan", mem, lay, err);
         if (rc != OK) return rc;
-        if (host) {
-            HIP_TRY(hipMemcpyAsync(up_a, a.a, a.m * 4, hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(up_b, a.b, a.m * 4, hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(up_w, a.w, a.m * 4, hipMemcpyHostToDevice, stream));
-            d_a = up_a;
-            d_b = up_b;
-            d_w = up_w;
-        }
+        rc = copy_uploads(ups, stream, err);
+        if (rc != OK) return rc;
         const DendrogramArgs d{a.device, a.n, a.m, d_a, d_b, left, right, size};
         rc = forest_dendrogram(d, false, stream_v, err);  // a bad end, a self-loop, a cycle: its refusals, in its words
         if (rc != OK) return rc;
@@ -543,12 +405,11 @@ int graph_hdbscan(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, cons
     }
     rc = clusters_of_dendrogram("graph hdbscan", n, edges, f_w, left, right, size, a.min_cluster_size, a.method, a.out, host, stream, err);
     if (rc != OK) return rc == ERR_ARG ? ERR_FORMAT : rc;  // (a forest of this library's own: an internal error)
-    const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    const struct { void* to; const void* from; } copies[] = {{a.forest.out_a, f_a}, {a.forest.out_b, f_b}, {a.forest.out_w, f_w},
-                                                              {a.out_left, left},    {a.out_right, right},  {a.out_size, size}};
-    for (const auto& c : copies)
-        if (c.to && edges != 0) HIP_TRY(hipMemcpyAsync(c.to, c.from, edges * 4, kind, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
+    const uint64_t bytes = edges * 4;
+    rc = copy_out({{a.forest.out_a, f_a, bytes}, {a.forest.out_b, f_b, bytes}, {a.forest.out_w, f_w, bytes}, {a.out_left, left, bytes},
+                   {a.out_right, right, bytes}, {a.out_size, size, bytes}},
+                  host, stream, err);
+    if (rc != OK) return rc;
     *a.forest.out_n = edges;
     return OK;
 }

@@ -9,21 +9,13 @@
 #include <string>
 #include <vector>
 
+#include "dist_order.hpp"  // dist_order_bits: the order of the exact k-NN key and of every weight
 #include "hip_host.hpp"
 #include "search_device.hpp"
 
 namespace hnswgpu {
 
 #if defined(__HIPCC__)
-// f32 -> u32 whose unsigned order is the order of the values, every NaN behind everything (distances are >= 0: then this is the
-// bit pattern with the top bit set; the other cases keep the order total whatever a distance returns)
-__device__ __forceinline__ uint32_t dist_order_bits(float v) {
-    uint32_t b = __float_as_uint(v);
-    if (v != v) return 0xFFFFFFFFu;
-    if (b == 0x80000000u) b = 0u;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 // An edge record's key: the row above bit 33, the col in bits 1 .. 32, the flag in bit 0 (rows and cols are below 2^30: n k <= 2^30)
 constexpr uint64_t FLAG_REV = 1ull;
 __host__ __device__ inline uint64_t rec_key(uint32_t row, uint32_t col, uint64_t flag) { return ((uint64_t)row << 33) | ((uint64_t)col << 1) | flag; }
@@ -45,6 +37,11 @@ int graph_order(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, 
 int exact_queries_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* d_queries, uint64_t nq, uint64_t d, uint64_t k,
                          uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, void* stream,
                          std::string& err);
+
+// defined in spanning_forest.hip, which holds the kernel: core[v] = the stored bits of slot min(core_k, counts[v]) - 1 of row v of n
+// rows of k slots (a StagedGraph's dists and counts), +0 for an empty row; one thread per row, numbered in 64 bits.  On `stream`,
+// nobody waits.
+int core_of_rows(const float* d_dists, const uint32_t* d_counts, uint64_t k, uint64_t core_k, uint64_t n, uint32_t* d_core, void* stream, std::string& err);
 
 // D, staged: the graph path's own answer for every point (exact_graph for ef == 0, else graph_search), row i the point at position
 // i, n rows of k slots, counts[i] of them used.  One allocation of 17 n k + 4 n bytes (and padding); a slot's neighbour is the p_id

@@ -7,6 +7,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 #include <string>
 
 #include "hnswio.hpp"  // ERR_DEVICE
@@ -97,12 +98,38 @@ struct DevMem {
 // A call's block, sized by the arrays that `lay` names and divided among them (scratch_layout.hpp).  Nothing is written before the
 // layout is known to fit.
 inline int alloc_layout(const char* what, DevMem& mem, ScratchLayout& lay, std::string& err) {
-    const uint64_t bytes = lay.size();
+    const uint64_t bytes = lay.size() != 0 ? lay.size() : ScratchLayout::ALIGN;  // (a layout without an array: a line that nobody uses)
     HIP_TRY(mem.alloc(bytes));
     if (!lay.place(mem.p, bytes)) {
         err = std::string(what) + ": scratch layout";
         return ERR_FORMAT;
     }
+    return OK;
+}
+
+// A host form's arrays go into its block, which alloc_layout has placed (scratch_layout.hpp: Uploads).  Nobody waits here.
+inline int copy_uploads(const Uploads& ups, hipStream_t stream, std::string& err) {
+    for (int i = 0; i < ups.count(); ++i) {
+        void* to;
+        const void* from;
+        uint64_t bytes;
+        ups.item(i, to, from, bytes);
+        if (bytes != 0) HIP_TRY(hipMemcpyAsync(to, from, bytes, hipMemcpyHostToDevice, stream));
+    }
+    return OK;
+}
+
+// The end of a call: what the caller asked for (`to` is there) goes from scratch to the out arrays, host memory for `host`, and the
+// stream is waited for.
+struct CopyOut {
+    void* to;
+    const void* from;
+    uint64_t bytes;
+};
+inline int copy_out(std::initializer_list<CopyOut> copies, bool host, hipStream_t stream, std::string& err) {
+    for (const CopyOut& c : copies)
+        if (c.to && c.bytes) HIP_TRY(hipMemcpyAsync(c.to, c.from, c.bytes, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     return OK;
 }
 

@@ -1,6 +1,7 @@
 // scratch_layout.hpp -- the one place where a block of scratch memory is divided into arrays: the host units name their arrays
 // once, the layout says how many bytes the block needs and, once the block is there, hands every array its pointer.  A byte count
-// and a carving that disagree cannot be written down.  Plain arithmetic, no HIP: hip_host.hpp includes it for the .hip units, and
+// and a carving that disagree cannot be written down.  Uploads, below it, names the arrays that a host form brings along into the
+// same block.  Plain arithmetic, no HIP: hip_host.hpp includes it for the .hip units, and
 // tests/cpp/test_scratch_layout.cpp compiles it on its own.  Private: not installed, not part of the ABI.
 #pragma once
 #include <cstdint>
@@ -56,6 +57,40 @@ private:
     int used_ = 0;
     bool broken_ = false;
     uint64_t total_ = 0;
+};
+
+// The host arrays that a host form brings to the device inside its block.  bring() takes a pointer that holds the HOST address: it
+// notes that address and names the pointer into the layout, so place() replaces it by the address of the device copy; an absent
+// array (nullptr) names nothing and stays null.  Once the block is placed, item() says what to copy where (hip_host.hpp:
+// copy_uploads).  The pointers must live as long as the list.
+class Uploads {
+public:
+    template <typename T>
+    void bring(ScratchLayout& lay, const T*& p, uint64_t count) {
+        if (p == nullptr) return;
+        // (a full list: the layout, which holds as many, is full too and refuses the block)
+        if (used_ < ScratchLayout::MAX_ARRAYS) item_[used_++] = Item{&p, p, count * sizeof(T)};
+        lay.array(p, count);
+    }
+    // arrays of `count` elements each, one behind the other
+    template <typename... Ts>
+    void brings(ScratchLayout& lay, uint64_t count, const Ts*&... ps) { (bring(lay, ps, count), ...); }
+
+    int count() const { return used_; }
+    void item(int i, void*& to, const void*& from, uint64_t& bytes) const {
+        std::memcpy(&to, item_[i].var, sizeof(to));
+        from = item_[i].from;
+        bytes = item_[i].bytes;
+    }
+
+private:
+    struct Item {
+        const void* var;  // a const T*& of the caller's: the device copy once the block is placed
+        const void* from;
+        uint64_t bytes;
+    };
+    Item item_[ScratchLayout::MAX_ARRAYS];
+    int used_ = 0;
 };
 
 }  // namespace hnswgpu

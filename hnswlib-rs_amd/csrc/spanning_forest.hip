@@ -5,6 +5,7 @@
 // Boruvka over the union-find of union_find.hpp, integer atomics only.  The edges {lo < hi, weight bits} are brought into the strict
 // total order (order bits of the weight, lo, hi) ONCE; from then on an edge's index is its rank and every comparison is a u32 min:
 //   msf_core_kernel     (index, core_k >= 1) one thread per vertex: the stored distance of slot min(core_k, counts[v]) - 1 of row v of D
+//                       (core_of_rows of graph_internal.hpp: cluster_predict.hip's core distances too)
 //   msf_mark_kernel     (index) one thread per sorted edge record of symmetric_graph.hip: the head of a run of equal (row, col) with
 //                       row < col is a pair {lo, hi}; its FWD record carries d(lo->hi), its REV record d(hi->lo).  UNION keeps every
 //                       pair, MUTUAL the pairs with both records.
@@ -54,12 +55,12 @@ constexpr uint32_t NONE = 0xFFFFFFFFu;  // no best edge (an edge's rank is below
 // one thread per vertex: core[v] = the bits of slot min(core_k, counts[v]) - 1 of row v, +0 for an empty row
 __global__ __launch_bounds__(256) void msf_core_kernel(const float* __restrict__ dists, const uint32_t* __restrict__ counts, uint32_t k, uint32_t core_k,
                                                       uint32_t n, uint32_t* __restrict__ core) {
-    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    const uint64_t v = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (v >= n) return;
     uint32_t c = counts[v];
     if (c > k) c = k;  // (a slot of the row, whatever the count holds)
     if (c > core_k) c = core_k;
-    core[v] = c == 0u ? 0u : __float_as_uint(dists[(size_t)v * k + (c - 1u)]);
+    core[v] = c == 0u ? 0u : __float_as_uint(dists[v * k + (c - 1u)]);
 }
 
 // Record t as a pair of the undirected graph: true iff it is the head of a run of equal (row, col) with row < col < n that `mutual`
@@ -307,6 +308,14 @@ int forest_of_edges(uint64_t n, uint64_t m, const uint32_t* e_lo, const uint32_t
 
 }  // namespace
 
+// graph_internal.hpp: this unit's core distances, and cluster_predict.hip's
+int core_of_rows(const float* dists, const uint32_t* counts, uint64_t k, uint64_t core_k, uint64_t n, uint32_t* core, void* stream, std::string& err) {
+    hipLaunchKernelGGL(msf_core_kernel, grid_of(n), dim3(256), 0, static_cast<hipStream_t>(stream), dists, counts, (uint32_t)k, (uint32_t)core_k, (uint32_t)n,
+                       core);
+    HIP_TRY(hipGetLastError());
+    return OK;
+}
+
 // Both index entries (capi.cpp refers to it weakly, capi_index.hpp): n >= 2, core_k <= k.  Waits for `stream` before it returns.
 int graph_spanning_forest(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ForestArgs& a, bool host, void* stream_v, std::string& err) {
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
@@ -328,8 +337,8 @@ int graph_spanning_forest(DeviceIndex& dev, const std::vector<uint64_t>& origin_
         if (rc != OK) return rc;
         HIP_TRY(m_core.alloc(round_up(n * 4, 256)));
         core = static_cast<uint32_t*>(m_core.p);
-        hipLaunchKernelGGL(msf_core_kernel, grid_of(n), dim3(256), 0, stream, d.dists, d.counts, (uint32_t)k, (uint32_t)a.core_k, (uint32_t)n, core);
-        HIP_TRY(hipGetLastError());
+        rc = core_of_rows(d.dists, d.counts, k, a.core_k, n, core, stream_v, err);
+        if (rc != OK) return rc;
         HIP_TRY(hipStreamSynchronize(stream));  // (D is released at the brace)
     } else {
         rc = sorted_edge_records(dev, origin_id, ord, k, a.ef, stream_v, rec, err);

@@ -1,7 +1,8 @@
 // ScratchLayout (csrc/scratch_layout.hpp: plain arithmetic, no HIP) over host blocks: the size and the carving agree, every array
 // starts on a 256-byte boundary and none overlaps another, a span between two marks is what lies between them, counts of 0, of 1
-// and of whole multiples of 256 bytes, a list that grew after the block was sized is refused, and three blocks of the host units
-// against the byte counts those units summed by hand before the layout existed.
+// and of whole multiples of 256 bytes, a list that grew after the block was sized is refused, the uploads of a host form with two
+// arrays absent (Uploads: the pointers turn from host to block addresses, an absent one stays null), and three blocks of the host
+// units against the byte counts those units summed by hand before the layout existed.
 // Host only: built by tests/test_scratch_layout.py with g++ -fsanitize=address,undefined, no device needed.  Every array is
 // written over its whole length, so an array that reached past its block would stop the program.
 #include <cstdint>
@@ -181,6 +182,43 @@ int main() {
         ScratchLayout small;
         small.array(a, 10);
         CHECK(small.place(big.p, big.bytes) && reinterpret_cast<unsigned char*>(a) == big.p);
+    }
+    // ---- Uploads: a host form's arrays named into the block; two of the five are absent, one is there with no element
+    {
+        const uint32_t host_parent[5] = {0xFFFFFFFFu, 0, 0, 1, 1};
+        const float host_core[70] = {};
+        const uint8_t host_selected[5] = {0, 1, 1, 0, 0};
+        const uint32_t *parent = host_parent, *point_cluster = nullptr, *empty = host_parent;
+        const float* core = host_core;
+        const uint8_t* selected = host_selected;
+        const double* death = nullptr;
+        uint32_t* scratch;
+        ScratchLayout lay;
+        Uploads ups;
+        lay.array(scratch, 10);
+        ups.brings(lay, 5, parent, point_cluster);  // (point_cluster: absent)
+        ups.bring(lay, core, 70);
+        ups.brings(lay, 5, selected, death);  // (death: absent)
+        ups.bring(lay, empty, 0);
+        CHECK(ups.count() == 4 && lay.size() == 256 + 256 + 512 + 256);
+        CHECK(parent == host_parent && core == host_core);  // (nothing moves before the block is there)
+        Block b(lay.size());
+        CHECK(lay.place(b.p, b.bytes));
+        CHECK(point_cluster == nullptr && death == nullptr);
+        CHECK(reinterpret_cast<const unsigned char*>(parent) == b.p + 256 && reinterpret_cast<const unsigned char*>(core) == b.p + 512);
+        CHECK(selected == b.p + 1024 && reinterpret_cast<const unsigned char*>(empty) == b.p + 1280);
+        check_extents(b, {{scratch, 40}, {parent, 20}, {core, 280}, {selected, 5}});
+        const struct { const void* to; const void* from; uint64_t bytes; } want[] = {
+            {parent, host_parent, 20}, {core, host_core, 280}, {selected, host_selected, 5}, {empty, host_parent, 0}};
+        for (int i = 0; i < ups.count(); ++i) {
+            void* to;
+            const void* from;
+            uint64_t bytes;
+            ups.item(i, to, from, bytes);
+            CHECK(to == want[i].to && from == want[i].from && bytes == want[i].bytes);
+            std::memcpy(to, from, (size_t)bytes);  // what copy_uploads asks of the runtime
+        }
+        CHECK(parent[0] == 0xFFFFFFFFu && parent[4] == 1 && selected[1] == 1 && selected[4] == 0);
     }
     // ---- three blocks of the host units against the sums written by hand before
     for (uint64_t n : {1, 2, 63, 64, 65, 1000}) {

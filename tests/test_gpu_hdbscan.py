@@ -244,6 +244,21 @@ def test_an_exact_tie_goes_to_the_parent(native):
     check_forest(native, 23, np.array(e2)[order], np.array(w2)[order], 3, "ties on two levels")
 
 
+def test_the_leaves_of_the_tie_under_the_shared_climb(native):
+    """the first forest of test_an_exact_tie_goes_to_the_parent under HNSWGPU_SELECT_LEAF: the selection is the one that the second
+    stage runs, and its climb runs for the leaf method too, where it carries the death lambdas and lets no cluster with children win.
+    The model's two answers differ on this forest -- the tie's parent under excess of mass, its two children as leaves --, so a climb
+    that decided the parent here would show.  Host and device form, byte for byte."""
+    e = np.array([(0, 1), (1, 2), (3, 4), (4, 5), (6, 7), (7, 8), (2, 3)], np.uint32)
+    a, b, w = np.ascontiguousarray(e[:, 0]), np.ascontiguousarray(e[:, 1]), np.array([0.5] * 6 + [1.0], np.float32)
+    leaf, eom = hdbscan_model(9, a, b, w, 3, "leaf"), hdbscan_model(9, a, b, w, 3, "eom")
+    assert (leaf.L, eom.L) == (3, 2) and leaf.selected.tolist() != eom.selected.tolist() and leaf.labels.tolist() != eom.labels.tolist()
+    for form, call in (("host", forest_host), ("device", forest_device)):
+        rc, o = call(native, 9, a, b, w, 3, "leaf")
+        assert rc == 0, (form, native._native.last_error())
+        compare(o, leaf, ("tie, leaf", form), True)
+
+
 def test_equal_and_extreme_weights(native):
     rng = np.random.default_rng(3)
     n = 257

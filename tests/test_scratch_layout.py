@@ -1,6 +1,6 @@
 """Builds and runs tests/cpp/test_scratch_layout.cpp: the layout of a call's scratch block (csrc/scratch_layout.hpp) -- size and
 carving agree, 256-byte boundaries, no overlap, spans between marks, counts of 0 and 1 and whole lines, a list that grew after the
-sizing is refused -- and the blocks of dendrogram_of_edges, forest_init and the StagedGraph against the byte counts those units
+sizing is refused, a host form's uploads with two arrays absent -- and the blocks of dendrogram_of_edges, forest_init and the StagedGraph against the byte counts those units
 summed by hand before, at n, m, k in {1, 2, 63, 64, 65, 1000}.  Plain arithmetic under AddressSanitizer and UBSan; no device."""
 import os
 import subprocess
