@@ -922,7 +922,7 @@ int hnswgpu_exact_search_batch_filter_set_device(const hnswgpu_index* idx, const
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
-// ---- exact range search: every eligible point within a query's radius (exact_knn.hip holds the device side)
+// ---- exact range search: every eligible point within a query's radius (exact_range.hip holds the device side)
 // the checks both forms share; the handle's lock is held (shared)
 static int exact_range_call(const hnswgpu_index* idx, const ExactRangeCallArgs& a) {
     const uint64_t dim = index_dimension(idx);
@@ -980,7 +980,7 @@ int hnswgpu_exact_range_search_batch_device(const hnswgpu_index* idx, const floa
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
-// ---- queries by stored point: the k-NN graph of the indexed points, approximate and exact (exact_knn.hip holds the device side)
+// ---- queries by stored point: the k-NN graph of the indexed points, approximate and exact (knn_graph.hip holds the device side)
 // the checks all four entries share; the handle's lock is held (shared).  exact: the exact call's own limits behind them.
 static int graph_call(const hnswgpu_index* idx, const GraphCallArgs& a, bool exact) {
     const uint64_t n = index_nb_point(idx);

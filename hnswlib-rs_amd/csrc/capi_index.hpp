@@ -1,6 +1,6 @@
 // capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h (and its extensions hnsw_mi355x_hdbscan.h, hnsw_mi355x_hdbscan_select.h and hnsw_mi355x_hdbscan_predict.h),
 // for the translation units that implement the C ABI: capi.cpp, which holds the entries, and the .hip units that hold their device
-// side (exact_knn.hip, which also holds hnswgpu_exact_search_batch(_device) itself; range_search.hip; symmetric_graph.hip;
+// side (exact_knn.hip, which also holds hnswgpu_exact_search_batch(_device) itself; exact_range.hip; knn_graph.hip; range_search.hip; symmetric_graph.hip;
 // graph_components.hip; spanning_forest.hip; dendrogram.hip; condensed_tree.hip; cluster_select.hip; cluster_predict.hip).  Private: not installed, not part of the ABI.
 // Three parts: the handle; the checks that entries share (empty index, resident replica, sorted filter, the limits of an exact call,
 // the zeroed k-NN answer, the tail), which live once, in capi.cpp, and are declared here as capi_* for the entries outside it; and
@@ -103,7 +103,7 @@ struct ExactSetArgs {
 };
 HNSWGPU_DEVICE_SIDE int exact_filter_set(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ExactSetArgs& a, bool host, void* stream,
                                          std::string& err);
-// hnswgpu_exact_range_search_batch(_device), exact_knn.hip.  Returns HNSWGPU_ERR_CAPACITY, the offsets complete and no out slot
+// hnswgpu_exact_range_search_batch(_device), exact_range.hip.  Returns HNSWGPU_ERR_CAPACITY, the offsets complete and no out slot
 // written, when the answers need more than cap slots.
 struct ExactRangeCallArgs {
     const float* queries;  // nq x d
@@ -120,7 +120,7 @@ struct ExactRangeCallArgs {
 };
 HNSWGPU_DEVICE_SIDE int exact_range(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ExactRangeCallArgs& a, bool host, void* stream,
                                     std::string& err);
-// hnswgpu_graph_search_batch(_device) and hnswgpu_exact_graph_batch(_device), exact_knn.hip.  They return ERR_ARG, nothing searched
+// hnswgpu_graph_search_batch(_device) and hnswgpu_exact_graph_batch(_device), knn_graph.hip.  They return ERR_ARG, nothing searched
 // and no out slot written, when an id of point_ids names no point.
 struct GraphCallArgs {
     const uint64_t* point_ids;  // nullptr: every point (np == the number of points, checked by the caller)

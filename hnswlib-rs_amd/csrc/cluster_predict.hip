@@ -26,6 +26,7 @@
 
 #include "capi_index.hpp"
 #include "cluster_tree.hpp"
+#include "exact_internal.hpp"
 #include "graph_internal.hpp"
 #include "hip_host.hpp"
 #include "hnswio.hpp"
@@ -306,7 +307,7 @@ int hdbscan_predict(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, co
     if (rc != OK) return rc;
     rc = copy_uploads(ups, stream, err);
     if (rc != OK) return rc;
-    if (a.ef == 0) rc = exact_queries_device(dev, origin_id, d_q, nq, a.d, k, ids, dists, layer, rank, counts, stream_v, err);
+    if (a.ef == 0) rc = exact_device(dev, origin_id, ExactCall{d_q, nullptr, nq, a.d, k, nullptr, 0, nullptr, {ids, dists, layer, rank, counts}}, stream, err);
     else rc = dev.search_device(d_q, nq, a.d, k, a.ef, ids, dists, layer, rank, counts, nullptr, stream_v, nullptr, 0, nullptr, err);
     if (rc != OK) return rc;
     hipLaunchKernelGGL(cp_position_kernel, grid_of(slots), dim3(256), 0, stream, v, ord.d_rank, layer, rank, counts, (uint32_t)k, (uint32_t)slots, pos);

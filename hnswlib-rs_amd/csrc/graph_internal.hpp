@@ -1,4 +1,4 @@
-// graph_internal.hpp -- what exact_knn.hip shares with symmetric_graph.hip, the unit that turns the k-NN graph of the indexed points
+// graph_internal.hpp -- what the exact units (exact_knn.hip, knn_graph.hip) share with symmetric_graph.hip, the unit that turns the k-NN graph of the indexed points
 // into an undirected one, and what that unit shares with graph_components.hip, which labels the graph's connected components, and
 // with spanning_forest.hip, which takes the graph's minimum spanning forest: the
 // order of the exact k-NN key, the DataId ranks a replica keeps on the device, the directed graph D staged on the device, and D's
@@ -28,15 +28,8 @@ struct GraphOrder {
     const uint32_t* d_rank = nullptr;
     const uint32_t* d_order = nullptr;
 };
-// defined in exact_knn.hip: OK, or ERR_DEVICE with `err` set
+// defined in knn_graph.hip: OK, or ERR_DEVICE with `err` set
 int graph_order(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, GraphOrder& out, std::string& err);
-
-// defined in exact_knn.hip: the exact k-NN of nq new vectors without a filter, every buffer device memory, exactly what
-// hnswgpu_exact_search_batch_device runs behind its checks (cluster_predict.hip: the rows of a prediction with ef == 0).  Waits for
-// `stream`.
-int exact_queries_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const float* d_queries, uint64_t nq, uint64_t d, uint64_t k,
-                         uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, void* stream,
-                         std::string& err);
 
 // defined in spanning_forest.hip, which holds the kernel: core[v] = the stored bits of slot min(core_k, counts[v]) - 1 of row v of n
 // rows of k slots (a StagedGraph's dists and counts), +0 for an empty row; one thread per row, numbered in 64 bits.  On `stream`,

@@ -96,8 +96,9 @@ struct DevMem {
 };
 
 // A call's block, sized by the arrays that `lay` names and divided among them (scratch_layout.hpp).  Nothing is written before the
-// layout is known to fit.
-inline int alloc_layout(const char* what, DevMem& mem, ScratchLayout& lay, std::string& err) {
+// layout is known to fit.  Block: DevMem, or a pooled block with the same alloc() and p (exact_internal.hpp: ScratchLease).
+template <typename Block>
+int alloc_layout(const char* what, Block& mem, ScratchLayout& lay, std::string& err) {
     const uint64_t bytes = lay.size() != 0 ? lay.size() : ScratchLayout::ALIGN;  // (a layout without an array: a line that nobody uses)
     HIP_TRY(mem.alloc(bytes));
     if (!lay.place(mem.p, bytes)) {

@@ -2,7 +2,7 @@
 // hnswgpu_symmetric_graph / hnswgpu_symmetric_graph_device of include/hnsw_mi355x.h (the entries and every check that needs no
 // device are in capi.cpp).  DESIGN.md "Symmetrised k-NN graph".
 //
-// The directed graph D is one call of the graph path itself (exact_graph or graph_search of exact_knn.hip, every point, device
+// The directed graph D is one call of the graph path itself (exact_graph or graph_search of knn_graph.hip, every point, device
 // buffers): n rows of k slots, counts[i] of them used.  Then
 //   sym_expand_kernel   one thread per slot of D: the neighbour's p_id into its position j (flat id, then the rank array of the
 //                       exact path), the forward record (i, j, FWD) and the reverse record (j, i, REV), both carrying the slot's

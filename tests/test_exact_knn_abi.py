@@ -132,7 +132,7 @@ KEY_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
 def _order_bits(d):
-    """dist_order_bits of exact_knn.hip: u32 whose unsigned order is the order of the f32 values, NaN behind everything"""
+    """dist_order_bits of dist_order.hpp: u32 whose unsigned order is the order of the f32 values, NaN behind everything"""
     b = d.view(np.uint32).copy()
     b[b == 0x80000000] = 0
     neg = (b & 0x80000000) != 0

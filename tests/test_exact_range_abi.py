@@ -1,4 +1,4 @@
-"""The exact range search entries (hnswgpu_exact_range_search_batch / _device, csrc/exact_knn.hip) as far as a box without a GPU can
+"""The exact range search entries (hnswgpu_exact_range_search_batch / _device, csrc/exact_range.hip) as far as a box without a GPU can
 see them: the ABI, every argument check with its message, the empty index, the "no device" answer, and a numpy emulation of the
 device's plan -- counters per (query, slab), the scan in query-major and slab-minor order, the write bases, the fill pass's chunks
 and the ballot-prefix compaction -- against brute force.  CPU only; tests/test_gpu_exact_range.py checks the answers."""
@@ -128,7 +128,7 @@ def test_range_result_views(native):
 
 # ----------------------------------------------------------------------------------------------------- the plan, emulated
 def _chunk_end(offs, qa, q_end, budget, max_q):
-    """range_chunk_end of exact_knn.hip: consecutive queries whose answers fit the budget, at most max_q, one at least"""
+    """range_chunk_end of exact_range.hip: consecutive queries whose answers fit the budget, at most max_q, one at least"""
     qb = qa + 1
     while qb < q_end and qb - qa < max_q and offs[qb + 1] - offs[qa] <= budget:
         qb += 1

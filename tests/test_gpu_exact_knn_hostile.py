@@ -1,6 +1,6 @@
 """Exhaustive exact k-NN on the device on HOSTILE values: the sweep of tests/f64_reference.py (magnitudes 2^-60 .. 2^60 in one
 vector, subnormals, cancellation, exact copies, sums that overflow f32, near-identical probability vectors) as rows AND queries
-of csrc/exact_knn.hip -- its own chain (chain4, scalar-operand query elements), its own DistCosine finish (norm_in_tail) and its
+of csrc/exact_knn.hip and csrc/exact_tile.hpp -- its own chain (chain4, scalar-operand query elements), its own DistCosine finish (norm_in_tail) and its
 own total order on f32 distances (dist_order_bits / make_key / dist_of_key: +inf tie groups, NaN last and canonical, ties cut
 by origin id, then dump order).
 

@@ -1,4 +1,4 @@
-"""Exact range search on the device (Hnsw.exact_range_search_flat -> hnswgpu_exact_range_search_batch, csrc/exact_knn.hip): every
+"""Exact range search on the device (Hnsw.exact_range_search_flat -> hnswgpu_exact_range_search_batch, csrc/exact_range.hip): every
 eligible point with dist(q, p) <= radii[q], ascending by (distance, origin id), in CSR form.
 The expected answer never comes from the code under test: D = oracle_lib.dist_matrix(metric, Q, X) (the CPU oracle's
 Distance::eval), the eligible rows with D[q] <= radii[q] as f32 values, ordered by np.lexsort((ids, D[q])); every comparison is

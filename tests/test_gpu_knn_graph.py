@@ -1,5 +1,5 @@
 """Queries by stored point on the device (Hnsw.knn_graph_flat / exact_knn_graph_flat -> hnswgpu_graph_search_batch /
-hnswgpu_exact_graph_batch and their _device forms, csrc/exact_knn.hip): the k-NN graph of the indexed points, the point itself
+hnswgpu_exact_graph_batch and their _device forms, csrc/knn_graph.hip): the k-NN graph of the indexed points, the point itself
 excluded by IDENTITY (its p_id) and not by id or distance.
 
 The expected answers never come from the code under test.  Exact graph: per point the lexsort of the CPU oracle's distance matrix

@@ -1,4 +1,4 @@
-"""The queries by stored point (hnswgpu_graph_search_batch / hnswgpu_exact_graph_batch and their _device forms, csrc/exact_knn.hip)
+"""The queries by stored point (hnswgpu_graph_search_batch / hnswgpu_exact_graph_batch and their _device forms, csrc/knn_graph.hip)
 as far as a box without a GPU can see them: the ABI, every argument check, the "no device" answer behind the checks, and a numpy
 emulation of the two rules the device applies -- the resolution of DataIds by binary search over the (id, dump order) table, and
 the removal of a point's own entry from a (k + 1)-wide answer -- against brute force.  CPU only; tests/test_gpu_knn_graph.py

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-kernel register / scratch / occupancy table of one kernel translation unit (cross-compiles, no GPU needed):
     tools/kres.py METRIC PART [extra -D flags ...]      e.g.  tools/kres.py 0 0
-    tools/kres.py exact [extra -D flags ...]            the kernels of exact_knn.hip (every instantiation of the slab kernel)"""
+    tools/kres.py exact [extra -D flags ...]            the kernels of exact_knn.hip, exact_range.hip and knn_graph.hip (every
+                                                        instantiation of the two slab kernels)"""
 import os
 import re
 import subprocess
@@ -11,13 +12,13 @@ root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 flags = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-pthread", "--offload-arch=gfx950",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-Rpass-analysis=kernel-resource-usage"]
 if sys.argv[1] == "exact":
-    cmd = [*flags, *sys.argv[2:], "-c", "exact_knn.hip", "-o", "/tmp/kres_exact.o"]
+    cmds = [[*flags, *sys.argv[2:], "-c", unit + ".hip", "-o", f"/tmp/kres_{unit}.o"] for unit in ("exact_knn", "exact_range", "knn_graph")]
 else:
     metric, part, extra = sys.argv[1], sys.argv[2], sys.argv[3:]
-    cmd = [*flags, *extra, f"-DHNSW_THIS_METRIC={metric}", f"-DHNSW_PART={part}", "-c", "search_kernels_tu.hip", "-o", f"/tmp/kres_{metric}_{part}.o"]
-p = subprocess.run(cmd, cwd=os.path.join(root, "hnswlib-rs_amd", "csrc"), capture_output=True, text=True)
+    cmds = [[*flags, *extra, f"-DHNSW_THIS_METRIC={metric}", f"-DHNSW_PART={part}", "-c", "search_kernels_tu.hip", "-o", f"/tmp/kres_{metric}_{part}.o"]]
+runs = [subprocess.run(cmd, cwd=os.path.join(root, "hnswlib-rs_amd", "csrc"), capture_output=True, text=True) for cmd in cmds]
 rows, cur = [], {}
-for line in p.stderr.splitlines():
+for line in "".join(p.stderr for p in runs).splitlines():
     m = re.search(r"remark:\s+(Function Name|TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\S+)", line)
     if not m:
         if "error" in line:
@@ -33,4 +34,4 @@ for r in rows:
     name = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip()
     name = re.sub(r"hnswgpu::\(anonymous namespace\)::", "", name).split("(")[0].replace("void ", "")
     print(f"{name:58s} vgpr {r.get('VGPRs', '?'):>4s} sgpr {r.get('TotalSGPRs', '?'):>4s} scratch {r.get('ScratchSize', '?'):>4s} occ {r.get('Occupancy', '?')}")
-sys.exit(p.returncode)
+sys.exit(max(p.returncode for p in runs))

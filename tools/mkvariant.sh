@@ -16,7 +16,7 @@ CXXFLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -pthread"
 HIPFLAGS="--offload-arch=gfx950 -fhip-fp32-correctly-rounded-divide-sqrt"
 if [ -n "${ONLY_METRICS:-}" ]; then
   flock .build.lock make -j8 >/dev/null   # the product's objects, up to date (one make at a time)
-  for f in hnswio builder datamap capi search_device exact_knn; do cp $f.o $OBJ/$f.o; done
+  for f in hnswio builder datamap capi search_device exact_knn exact_range knn_graph; do cp $f.o $OBJ/$f.o; done
   for m in 0 1 2 3 4 5 6 7 8 9 10; do for p in 0 1 2; do cp sk_${m}_$p.o $OBJ/sk_${m}_$p.o; done; done
   METRICS="$ONLY_METRICS"
 else
@@ -24,7 +24,9 @@ else
     g++ $CXXFLAGS $2 -c $m.cpp -o $OBJ/$m.o &
   done
   /opt/rocm/bin/hipcc $CXXFLAGS $HIPFLAGS $2 -c search_device.hip -o $OBJ/search_device.o &
-  /opt/rocm/bin/hipcc $CXXFLAGS $HIPFLAGS $2 -c exact_knn.hip -o $OBJ/exact_knn.o &
+  for u in exact_knn exact_range knn_graph; do
+    /opt/rocm/bin/hipcc $CXXFLAGS $HIPFLAGS $2 -c $u.hip -o $OBJ/$u.o &
+  done
   METRICS="0 1 2 3 4 5 6 7 8 9 10"
 fi
 for m in $METRICS; do
@@ -37,5 +39,5 @@ wait
 KOBJS=""
 for m in 0 1 2 3 4 5 6 7 8 9 10; do for p in 0 1 2; do KOBJS="$KOBJS $OBJ/sk_${m}_$p.o"; done; done
 /opt/rocm/bin/hipcc -shared -fPIC -pthread --offload-arch=gfx950 -o ../lib_$1.so $OBJ/hnswio.o $OBJ/builder.o $OBJ/datamap.o $OBJ/capi.o \
-    $OBJ/search_device.o $OBJ/exact_knn.o $KOBJS -Wl,-rpath,/opt/rocm/lib
+    $OBJ/search_device.o $OBJ/exact_knn.o $OBJ/exact_range.o $OBJ/knn_graph.o $KOBJS -Wl,-rpath,/opt/rocm/lib
 ls -la ../lib_$1.so
