@@ -7,4 +7,4 @@ from ._native import build_native, lib, LIB_PATH, DIST, DIST_NAME  # noqa: F401
 from .api import (reload_env, BatchResult, DataMap, Hnsw, HnswError, HnswIo, Neighbour, eval_distance_matrix, eval_distances,  # noqa: F401
                   load_description, GraphCsrResult, RangeResult, round_to_f16, f16_representable, ComponentsResult, csr_components,
                   SpanningForestResult, csr_spanning_forest, DendrogramResult, forest_dendrogram, HdbscanResult, forest_hdbscan,
-                  PredictResult, hdbscan_assign)
+                  PredictResult, hdbscan_assign, DbscanResult, csr_dbscan)

@@ -38,6 +38,11 @@ _TREE_PREDICT_HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "hnsw_m
 _PKG_PREDICT_HEADER = os.path.join(PKG_DIR, "hnsw_mi355x_hdbscan_predict.h")
 PREDICT_HEADER_PATH = _TREE_PREDICT_HEADER if os.path.exists(_TREE_PREDICT_HEADER) else _PKG_PREDICT_HEADER
 PREDICT_HEADER = _cheader.load(PREDICT_HEADER_PATH, SELECT_HEADER)
+# DBSCAN (hnswdbs_*) has a fifth header, which includes the prediction one: read with that as its base
+_TREE_DBSCAN_HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "hnsw_mi355x_dbscan.h")
+_PKG_DBSCAN_HEADER = os.path.join(PKG_DIR, "hnsw_mi355x_dbscan.h")
+DBSCAN_HEADER_PATH = _TREE_DBSCAN_HEADER if os.path.exists(_TREE_DBSCAN_HEADER) else _PKG_DBSCAN_HEADER
+DBSCAN_HEADER = _cheader.load(DBSCAN_HEADER_PATH, PREDICT_HEADER)
 OK, ERR_ARG, ERR_IO, ERR_FORMAT, ERR_DISTANCE, ERR_TYPE, ERR_DEVICE, ERR_EMPTY, ERR_REF_PANIC, ERR_CAPACITY = (
     HEADER.constants["HNSWGPU_" + n] for n in ("OK", "ERR_ARG", "ERR_IO", "ERR_FORMAT", "ERR_DISTANCE", "ERR_TYPE", "ERR_DEVICE",
                                                "ERR_EMPTY", "ERR_REF_PANIC", "ERR_CAPACITY"))
@@ -52,7 +57,7 @@ def build_native(force=False, verbose=False):
     """Compile every HIP/C++ source for gfx950 into libhnsw_mi355x.so (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC_DIR, f) for f in os.listdir(CSRC_DIR)
             if f.endswith((".cpp", ".hip", ".hpp", ".inc")) or f == "Makefile"]
-    srcs += [HEADER_PATH, HDBSCAN_HEADER_PATH, SELECT_HEADER_PATH, PREDICT_HEADER_PATH]
+    srcs += [HEADER_PATH, HDBSCAN_HEADER_PATH, SELECT_HEADER_PATH, PREDICT_HEADER_PATH, DBSCAN_HEADER_PATH]
 
     def fresh():
         return (os.path.exists(LIB_PATH)
@@ -60,7 +65,7 @@ def build_native(force=False, verbose=False):
 
     def ship_header():  # the package's own copies of the headers (what a relocated package binds from)
         for tree, pkg in ((_TREE_HEADER, _PKG_HEADER), (_TREE_HDBSCAN_HEADER, _PKG_HDBSCAN_HEADER), (_TREE_SELECT_HEADER, _PKG_SELECT_HEADER),
-                          (_TREE_PREDICT_HEADER, _PKG_PREDICT_HEADER)):
+                          (_TREE_PREDICT_HEADER, _PKG_PREDICT_HEADER), (_TREE_DBSCAN_HEADER, _PKG_DBSCAN_HEADER)):
             if os.path.exists(tree):
                 try:
                     if not os.path.exists(pkg) or open(pkg, "rb").read() != open(tree, "rb").read():
@@ -109,6 +114,8 @@ HDBSCAN_SYMBOLS = {name: (res, args) for name, (res, args, _names, _text) in HDB
 SELECT_SYMBOLS = {name: (res, args) for name, (res, args, _names, _text) in SELECT_HEADER.prototypes.items()}
 # every symbol include/hnsw_mi355x_hdbscan_predict.h declares
 PREDICT_SYMBOLS = {name: (res, args) for name, (res, args, _names, _text) in PREDICT_HEADER.prototypes.items()}
+# every symbol include/hnsw_mi355x_dbscan.h declares
+DBSCAN_SYMBOLS = {name: (res, args) for name, (res, args, _names, _text) in DBSCAN_HEADER.prototypes.items()}
 
 _lib = None
 
@@ -124,7 +131,7 @@ def lib():
                 "(python -c 'import __graft_entry__ as g; g.build()').  There is no CPU fallback.")
         L = C.CDLL(path)
         for name, (res, args) in (list(SYMBOLS.items()) + list(HDBSCAN_SYMBOLS.items()) + list(SELECT_SYMBOLS.items())
-                                  + list(PREDICT_SYMBOLS.items())):
+                                  + list(PREDICT_SYMBOLS.items()) + list(DBSCAN_SYMBOLS.items())):
             fn = getattr(L, name)  # AttributeError if the library does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -188,6 +188,50 @@ def csr_components(offsets, cols, dists=None, max_dist=None, device=0):
     return ComponentsResult(labels, sizes[:int(c[0])].copy(), int(c[0]))
 
 
+class DbscanResult:
+    """DBSCAN(eps, min_samples) as include/hnsw_mi355x_dbscan.h defines it (Hnsw.dbscan, csr_dbscan), indexed by POSITION like
+    ComponentsResult: labels (i32, the cluster, -1: noise), core (bool), counts (u32, the size of the point's set), anchors (u32: a
+    core point itself, otherwise the nearest core point of its own set, UINT32_MAX for noise); clusters are numbered
+    0 .. n_clusters - 1 by their smallest core position, ascending."""
+
+    def __init__(self, labels, core, counts, anchors, n_clusters):
+        self.labels, self.core, self.counts, self.anchors, self.n_clusters = labels, core, counts, anchors, n_clusters
+
+
+def _dbscan_params(eps, min_samples):
+    if np.isnan(np.float32(eps)):
+        raise HnswError(N.ERR_ARG, "eps is NaN")
+    if int(min_samples) < 1:
+        raise HnswError(N.ERR_ARG, "min_samples must be > 0")
+    return float(np.float32(eps)), int(min_samples)
+
+
+def _dbscan_arrays(n):
+    return np.zeros(n, np.int32), np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(1, np.uint64)
+
+
+def csr_dbscan(offsets, cols, dists=None, eps=float("inf"), min_samples=1, add_self=False, device=0):
+    """DBSCAN over ANY neighbour lists given in CSR by position (offsets u64[n + 1], cols u32[offsets[n]]), on `device`: entry e of
+    row i is in the set of i iff dists is None or dists[e] <= eps (a NaN never is); add_self adds the point itself to every count
+    (k-NN rows that never name their own point).  A point that is not core reads its OWN row only.  Returns a DbscanResult."""
+    eps, min_samples = _dbscan_params(eps, min_samples)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    cols = np.ascontiguousarray(cols, dtype=np.uint32)
+    if dists is not None:
+        dists = np.ascontiguousarray(dists, dtype=np.float32)
+        if len(dists) != len(cols):
+            raise HnswError(N.ERR_ARG, f"dists has {len(dists)} entries, cols has {len(cols)}")
+    if len(offsets) == 0 or int(offsets[-1]) > len(cols):
+        raise HnswError(N.ERR_ARG, "offsets must hold n + 1 entries, the last one at most len(cols)")
+    n = len(offsets) - 1
+    labels, core, counts, anchors, c = _dbscan_arrays(n)
+    if dists is not None and len(dists) == 0:
+        dists = np.zeros(1, np.float32)  # (never read: there is no entry)
+    _check(N.lib().hnswdbs_csr(device, n, _p(offsets), _p(cols) if len(cols) else None, _p(dists), eps, min_samples, 1 if add_self else 0,
+                               _p(labels), _p(core), _p(counts), _p(anchors), _p(c)))
+    return DbscanResult(labels, core.astype(bool), counts, anchors, int(c[0]))
+
+
 class SpanningForestResult:
     """The minimum spanning forest of a graph (Hnsw.knn_graph_spanning_forest, csr_spanning_forest): n_edges edges, edge e joining
     vertices a[e] < b[e] with weight weights[e] (f32, the bits as the graph stores them), ascending by (weight, a, b).  Read in this
@@ -980,6 +1024,17 @@ class Hnsw:
         cut = _cut(max_dist)
         _check(self._lib.hnswgpu_graph_components(self._h, knbn, 0 if ef is None else ef, modes[mode], _p(cut), _p(labels), _p(sizes), _p(c)))
         return ComponentsResult(labels, sizes[:int(c[0])].copy(), int(c[0]))
+
+    def dbscan(self, eps, min_samples):
+        """Exact DBSCAN(eps, min_samples) of the indexed points on the device, without a neighbour list: the set of point i is every
+        stored point j (itself included) with dist(point i as the query, j) <= eps, the bits of hnswgpu_exact_search_batch.  Vertices
+        are POSITIONS (the rows of symmetric_knn_graph_flat).  Returns a DbscanResult."""
+        eps, min_samples = _dbscan_params(eps, min_samples)
+        labels, core, counts, anchors, c = _dbscan_arrays(self.get_nb_point())
+        if self._h is None:
+            return DbscanResult(labels, core.astype(bool), counts, anchors, 0)
+        _check(self._lib.hnswdbs_exact(self._h, eps, min_samples, _p(labels), _p(core), _p(counts), _p(anchors), _p(c)))
+        return DbscanResult(labels, core.astype(bool), counts, anchors, int(c[0]))
 
     def knn_graph_spanning_forest(self, knbn, ef=None, mode="union", core_k=0):
         """The minimum spanning forest of the graph symmetric_knn_graph_flat(knbn, ef, mode) would build, taken on the device without

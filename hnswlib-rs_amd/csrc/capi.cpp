@@ -1824,6 +1824,90 @@ int hnswhdp_predict_device(const hnswgpu_index* idx, const float* d_queries, uin
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
+// ---- DBSCAN: exact over the points of the index, and over any CSR (hnsw_mi355x_dbscan.h; dbscan.hip holds the device side)
+// what all four entries check of the parameters and of the answer's slots (n: the number of vertices)
+static int dbscan_call_check(const char* what, uint64_t n, const DbscanArgs& a) {
+    if (a.min_samples == 0) return fail(HNSWGPU_ERR_ARG, "min_samples must be > 0");
+    if (a.eps != a.eps) return fail(HNSWGPU_ERR_ARG, "eps is NaN: no distance compares to it");
+    if (n > 0x7FFFFFFFull) return fail(HNSWGPU_ERR_ARG, std::string(what) + ": n = " + std::to_string(n) + " vertices, above 2^31 - 1");
+    if (n != 0 && !a.out.label) return fail(HNSWGPU_ERR_ARG, "null out_label");
+    if (!a.out.out_n) return fail(HNSWGPU_ERR_ARG, "null out_n_clusters: the number of clusters is written by every call");
+    return HNSWGPU_OK;
+}
+
+static int exact_dbscan_pair(const hnswgpu_index* cidx, const DbscanArgs& a, bool host, void* stream) {
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    int rc = dbscan_call_check("dbscan", index_nb_point(idx), a);
+    if (rc != HNSWGPU_OK) return rc;
+    if (idx->arithmetic != HNSWGPU_ARITH_SCALAR)
+        return fail(HNSWGPU_ERR_ARG, "dbscan answers in the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
+    rc = capi_refuse_f16(idx, "dbscan");
+    if (rc != HNSWGPU_OK) return rc;
+    if (index_empty(idx)) {  // no vertex: no cluster, nothing else written
+        *a.out.out_n = 0;
+        return HNSWGPU_OK;
+    }
+    if (!hnswgpu::exact_dbscan) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = call_replica(idx, sl, host, true, true, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    return finish(hnswgpu::exact_dbscan(*dev, idx->flat->origin_id, a, host, stream, err), err);
+}
+
+int hnswdbs_exact(const hnswgpu_index* idx, float eps, uint64_t min_samples, int32_t* out_label, uint8_t* out_core, uint32_t* out_count,
+                  uint32_t* out_anchor, uint64_t* out_n_clusters) {
+    CAPI_GUARD_BEGIN
+    return exact_dbscan_pair(idx, DbscanArgs{eps, min_samples, DbscanOut{out_label, out_core, out_count, out_anchor, out_n_clusters}}, true, nullptr);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswdbs_exact_device(const hnswgpu_index* idx, float eps, uint64_t min_samples, int32_t* d_out_label, uint8_t* d_out_core, uint32_t* d_out_count,
+                         uint32_t* d_out_anchor, uint64_t* out_n_clusters, void* stream) {
+    CAPI_GUARD_BEGIN
+    return exact_dbscan_pair(idx, DbscanArgs{eps, min_samples, DbscanOut{d_out_label, d_out_core, d_out_count, d_out_anchor, out_n_clusters}}, false, stream);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+static int csr_dbscan_pair(const CsrDbscanArgs& a, bool host, void* stream) {
+    int rc = dbscan_call_check("csr dbscan", a.n, a.call);
+    if (rc != HNSWGPU_OK) return rc;
+    if (a.add_self > 1) return fail(HNSWGPU_ERR_ARG, "add_self must be 0 or 1, not " + std::to_string(a.add_self));
+    if (a.n != 0 && !a.offsets) return fail(HNSWGPU_ERR_ARG, "null offsets");
+    if (a.n == 0) {
+        *a.call.out.out_n = 0;
+        return HNSWGPU_OK;
+    }
+    if (host) {  // (the device form's validation kernels read the graph)
+        rc = csr_graph_check("csr dbscan", a.n, a.offsets, a.cols);
+        if (rc != HNSWGPU_OK) return rc;
+    }
+    if (!hnswgpu::csr_dbscan) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    std::string err;
+    return finish(hnswgpu::csr_dbscan(a, host, stream, err), err);
+}
+
+int hnswdbs_csr(int device, uint64_t n, const uint64_t* offsets, const uint32_t* cols, const float* dists, float eps, uint64_t min_samples,
+                uint32_t add_self, int32_t* out_label, uint8_t* out_core, uint32_t* out_count, uint32_t* out_anchor, uint64_t* out_n_clusters) {
+    CAPI_GUARD_BEGIN
+    const CsrDbscanArgs a{device, n, offsets, cols, dists, add_self,
+                          DbscanArgs{eps, min_samples, DbscanOut{out_label, out_core, out_count, out_anchor, out_n_clusters}}};
+    return csr_dbscan_pair(a, true, nullptr);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswdbs_csr_device(int device, uint64_t n, const uint64_t* d_offsets, const uint32_t* d_cols, const float* d_dists, float eps,
+                       uint64_t min_samples, uint32_t add_self, int32_t* d_out_label, uint8_t* d_out_core, uint32_t* d_out_count,
+                       uint32_t* d_out_anchor, uint64_t* out_n_clusters, void* stream) {
+    CAPI_GUARD_BEGIN
+    const CsrDbscanArgs a{device, n, d_offsets, d_cols, d_dists, add_self,
+                          DbscanArgs{eps, min_samples, DbscanOut{d_out_label, d_out_core, d_out_count, d_out_anchor, out_n_clusters}}};
+    return csr_dbscan_pair(a, false, stream);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
 static DeviceIndex* any_replica(hnswgpu_index* idx) {
     if (idx->primary >= 0 && idx->replica(idx->primary)) return idx->replica(idx->primary);
     return nullptr;

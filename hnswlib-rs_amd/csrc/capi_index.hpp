@@ -1,7 +1,7 @@
-// capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h (and its extensions hnsw_mi355x_hdbscan.h, hnsw_mi355x_hdbscan_select.h and hnsw_mi355x_hdbscan_predict.h),
+// capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h (and its extensions hnsw_mi355x_hdbscan.h, hnsw_mi355x_hdbscan_select.h, hnsw_mi355x_hdbscan_predict.h and hnsw_mi355x_dbscan.h),
 // for the translation units that implement the C ABI: capi.cpp, which holds the entries, and the .hip units that hold their device
 // side (exact_knn.hip, which also holds hnswgpu_exact_search_batch(_device) itself; exact_range.hip; knn_graph.hip; range_search.hip; symmetric_graph.hip;
-// graph_components.hip; spanning_forest.hip; dendrogram.hip; condensed_tree.hip; cluster_select.hip; cluster_predict.hip).  Private: not installed, not part of the ABI.
+// graph_components.hip; spanning_forest.hip; dendrogram.hip; condensed_tree.hip; cluster_select.hip; cluster_predict.hip; dbscan.hip).  Private: not installed, not part of the ABI.
 // Three parts: the handle; the checks that entries share (empty index, resident replica, sorted filter, the limits of an exact call,
 // the zeroed k-NN answer, the tail), which live once, in capi.cpp, and are declared here as capi_* for the entries outside it; and
 // the device side of every host / _device pair, declared ONCE, here, with its arguments' struct (HNSWGPU_DEVICE_SIDE of
@@ -22,6 +22,7 @@
 #include "../../include/hnsw_mi355x_hdbscan.h"
 #include "../../include/hnsw_mi355x_hdbscan_select.h"
 #include "../../include/hnsw_mi355x_hdbscan_predict.h"
+#include "../../include/hnsw_mi355x_dbscan.h"
 #include "builder.hpp"
 #include "flat_index.hpp"
 #include "search_device.hpp"
@@ -360,6 +361,33 @@ struct HdbscanPredictArgs {
     PredictOut out;
 };
 HNSWGPU_DEVICE_SIDE int hdbscan_predict(DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const HdbscanPredictArgs& a, bool host, void* stream, std::string& err);
+// the device side of hnswdbs_exact(_device) and hnswdbs_csr(_device), defined in dbscan.hip (the arguments have been checked; at least
+// one vertex; 1 <= min_samples, eps no NaN).  host: the arrays are plain host memory -- a CSR form's graph has then passed its checks
+// on the host --; else device memory and `stream` is the caller's.  out_n is host memory either way.  csr_dbscan returns ERR_ARG, no
+// out slot written, when its validation kernels refuse the graph.
+struct DbscanOut {
+    int32_t* label;    // [n]
+    uint8_t* core;     // [n], may be nullptr, like the two below
+    uint32_t* count;
+    uint32_t* anchor;
+    uint64_t* out_n;
+};
+struct DbscanArgs {
+    float eps;
+    uint64_t min_samples;
+    DbscanOut out;
+};
+HNSWGPU_DEVICE_SIDE int exact_dbscan(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const DbscanArgs& a, bool host, void* stream, std::string& err);
+struct CsrDbscanArgs {
+    int device;
+    uint64_t n;
+    const uint64_t* offsets;  // [n + 1]
+    const uint32_t* cols;     // [offsets[n]]
+    const float* dists;       // [offsets[n]], may be nullptr: every entry counts, every weight +0
+    uint32_t add_self;        // 0 or 1
+    DbscanArgs call;
+};
+HNSWGPU_DEVICE_SIDE int csr_dbscan(const CsrDbscanArgs& a, bool host, void* stream, std::string& err);
 }  // namespace hnswgpu
 
 // No C++ exception may cross the C ABI: every entry point is `try { ... HNSWGPU_CAPI_GUARD_END(ret)`

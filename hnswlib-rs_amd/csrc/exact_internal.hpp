@@ -94,6 +94,11 @@ struct SlabPlan {
 // slot_of[row] * words.  On `stream`, nobody waits.
 hipError_t exact_prep_queries(hipStream_t stream, const float* d_src, uint64_t cq, uint64_t d, const SlabPlan& plan, uint32_t n_slots, float* d_qt,
                               double* d_qnorm, const uint32_t* qlist = nullptr, const uint32_t* slot_of = nullptr, uint32_t* tword = nullptr);
+// defined in exact_knn.hip too: the same tiles from the index's own rows -- slot i holds the stored point of flat id d_flat[i], its
+// bits those of the point's vector brought as a query, and self_rank[i] that point's DataId rank (its POSITION; the slots behind
+// the last: 0xFFFFFFFF).  For the exact graph and for dbscan.hip.  On `stream`, nobody waits.
+hipError_t exact_prep_rows(hipStream_t stream, const DeviceIndexView& ix, const uint32_t* d_flat, const uint32_t* d_rank, uint64_t cq, const SlabPlan& plan,
+                           uint32_t n_slots, float* d_qt, double* d_qnorm, uint32_t* d_self_rank);
 
 // The optional filter of a call with host buffers goes to the device once.  A filter that is empty still is a filter: a non-null
 // pointer that is never dereferenced.

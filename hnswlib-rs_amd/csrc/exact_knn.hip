@@ -316,6 +316,13 @@ hipError_t exact_prep_queries(hipStream_t stream, const float* d_src, uint64_t c
     return hipGetLastError();
 }
 
+hipError_t exact_prep_rows(hipStream_t stream, const DeviceIndexView& ix, const uint32_t* d_flat, const uint32_t* d_rank, uint64_t cq, const SlabPlan& plan,
+                           uint32_t n_slots, float* d_qt, double* d_qnorm, uint32_t* d_self_rank) {
+    hipLaunchKernelGGL(exact_knn_prep_rows_kernel, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, ix, d_flat, d_rank, (uint32_t)cq, (uint32_t)plan.nchunk,
+                       n_slots, d_qt, d_qnorm, d_self_rank);
+    return hipGetLastError();
+}
+
 // the device path: every pointer is device memory; waits for `stream` before it returns.
 // No set: no filter, or one for the batch (c.d_allowed).  Else query q is answered under filter set->filter_of[q]: the
 // bitmaps are built group by group -- as many consecutive filters as the bound and this unit's scratch budget hold -- and per group
@@ -403,9 +410,7 @@ int exact_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id,
             a.nq = (uint32_t)cq;
             const uint32_t n_slots = (uint32_t)(tiles * TQ);
             if (d_self) {
-                hipLaunchKernelGGL(exact_knn_prep_rows_kernel, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, v, d_self + row0, a.rank, (uint32_t)cq,
-                                   (uint32_t)nchunk, n_slots, d_qt, d_qnorm, d_self_rank);
-                HIP_TRY(hipGetLastError());
+                HIP_TRY(exact_prep_rows(stream, v, d_self + row0, a.rank, cq, plan, n_slots, d_qt, d_qnorm, d_self_rank));
             } else {
                 HIP_TRY(exact_prep_queries(stream, c.d_queries + row0 * d, cq, d, plan, n_slots, d_qt, d_qnorm, a.qlist, slot_of ? slot_of + row0 : nullptr, d_tword));
             }
