@@ -800,6 +800,42 @@ class Hnsw:
                                                     _p(layers), _p(ranks), _p(counts)))
         return BatchResult(ids, dists, layers, ranks, counts)
 
+    def exact_search_screened_flat(self, datas, knbn, allowed_ids=None):
+        """exact_search_flat through the matrix-core screen (include/hnsw_mi355x_exact_screen.h): the same BatchResult byte for byte,
+        and stats, three u64: queries certified by the screen, queries the certificate handed to the existing path, queries not
+        screened at all (a distance without a screen, knbn + 54 above 4096, a small index, very long rows).  Returns (BatchResult, stats)."""
+        datas = np.ascontiguousarray(datas, dtype=np.float32)
+        if datas.ndim != 2:
+            raise HnswError(N.ERR_ARG, "datas must be a (nq, d) matrix")
+        nq, d = datas.shape
+        ids = np.zeros((nq, knbn), np.uint64)
+        dists = np.zeros((nq, knbn), np.float32)
+        layers = np.zeros((nq, knbn), np.uint8)
+        ranks = np.zeros((nq, knbn), np.int32)
+        counts = np.zeros(nq, np.uint32)
+        stats = np.array([0, 0, nq], np.uint64)
+        if self._h is None:
+            return BatchResult(ids, dists, layers, ranks, counts), stats
+        allowed, n_allowed = None, 0
+        if allowed_ids is not None:
+            n_allowed = len(allowed_ids)
+            allowed = np.ascontiguousarray(allowed_ids, dtype=np.uint64) if n_allowed else np.zeros(1, np.uint64)
+        _check(self._lib.hnswxs_exact_search_batch(self._h, _p(datas), nq, d, knbn, _p(allowed), n_allowed, _p(ids), _p(dists),
+                                                             _p(layers), _p(ranks), _p(counts), _p(stats)))
+        return BatchResult(ids, dists, layers, ranks, counts), stats
+
+    def exact_screen_matrix(self, datas):
+        """The screen's lower bound of every (row of datas, stored point) distance, (nq, n) f32 with the points in dump order: the
+        diagnostic entry hnswxs_screen_matrix.  nq * n up to 2^24; DistL2, DistDot, DistCosine."""
+        datas = np.ascontiguousarray(datas, dtype=np.float32)
+        if datas.ndim != 2:
+            raise HnswError(N.ERR_ARG, "datas must be a (nq, d) matrix")
+        nq, d = datas.shape
+        out = np.zeros((nq, self.get_nb_point()), np.float32)
+        if self._h is not None:
+            _check(self._lib.hnswxs_screen_matrix(self._h, _p(datas), nq, d, _p(out)))
+        return out
+
     def exact_search(self, datas, knbn, allowed_ids=None):
         """exact_search_flat as Vec<Vec<Neighbour>> in input order."""
         return self.exact_search_flat(datas, knbn, allowed_ids).to_neighbours()

@@ -1871,6 +1871,71 @@ int hnswdbs_exact_device(const hnswgpu_index* idx, float eps, uint64_t min_sampl
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
+// ---- exact k-NN behind a matrix-core screen (hnsw_mi355x_exact_screen.h; exact_screen.hip holds the device side): the checks are
+// hnswgpu_exact_search_batch's own, in its order
+static int exact_screened_pair(const hnswgpu_index* cidx, const ExactScreenArgs& a, bool host, void* stream) {
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    int rc = check_exact_call(idx, a.queries, a.nq, a.d, a.k, a.allowed, a.n_allowed, a.out_ids, a.out_dists, a.out_counts);
+    if (rc != HNSWGPU_OK) return rc;
+    if (host) {
+        rc = check_sorted_filter(a.allowed, a.n_allowed);
+        if (rc != HNSWGPU_OK) return rc;
+        if (index_empty(idx)) {  // no point: every answer is empty, nothing was screened
+            zero_knn_answers(a.nq, a.k, a.out_ids, a.out_dists, a.out_layer, a.out_rank, a.out_counts);
+            if (a.out_stats) a.out_stats[0] = a.out_stats[1] = 0, a.out_stats[2] = a.nq;
+            return HNSWGPU_OK;
+        }
+    }
+    if (!hnswgpu::exact_screened) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = call_replica(idx, sl, host, true, true, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    return finish(hnswgpu::exact_screened(*dev, idx->flat->origin_id, a, host, stream, err), err);
+}
+
+int hnswxs_exact_search_batch(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, uint64_t k, const uint64_t* allowed_ids,
+                                        uint64_t n_allowed, uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank,
+                                        uint32_t* out_counts, uint64_t* out_stats) {
+    CAPI_GUARD_BEGIN
+    return exact_screened_pair(idx, ExactScreenArgs{queries, nq, d, k, allowed_ids, n_allowed, out_ids, out_dists, out_layer, out_rank, out_counts, out_stats},
+                               true, nullptr);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswxs_exact_search_batch_device(const hnswgpu_index* idx, const float* d_queries, uint64_t nq, uint64_t d, uint64_t k,
+                                               const uint64_t* d_allowed_ids, uint64_t n_allowed, uint64_t* d_out_ids, float* d_out_dists,
+                                               uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, uint64_t* out_stats, void* stream) {
+    CAPI_GUARD_BEGIN
+    return exact_screened_pair(idx, ExactScreenArgs{d_queries, nq, d, k, d_allowed_ids, n_allowed, d_out_ids, d_out_dists, d_out_layer, d_out_rank,
+                                                    d_out_counts, out_stats}, false, stream);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+int hnswxs_screen_matrix(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, float* out_lb) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    const uint64_t dim = index_dimension(idx);
+    if (nq != 0 && (!queries || !out_lb)) return fail(HNSWGPU_ERR_ARG, "null buffer");
+    if (dim != 0 && d != dim) return fail(HNSWGPU_ERR_ARG, "query dimension differs from the index dimension");
+    if (idx->arithmetic != HNSWGPU_ARITH_SCALAR)
+        return fail(HNSWGPU_ERR_ARG, "the screen bounds the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
+    int rc = capi_refuse_f16(idx, "the screen");
+    if (rc != HNSWGPU_OK) return rc;
+    if (index_empty(idx) || nq == 0) return HNSWGPU_OK;
+    if (!hnswgpu::exact_screen_matrix) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = primary_f32_replica(idx, sl, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    return finish(hnswgpu::exact_screen_matrix(*dev, idx->flat->origin_id, ScreenMatrixArgs{queries, nq, d, out_lb}, err), err);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
 static int csr_dbscan_pair(const CsrDbscanArgs& a, bool host, void* stream) {
     int rc = dbscan_call_check("csr dbscan", a.n, a.call);
     if (rc != HNSWGPU_OK) return rc;

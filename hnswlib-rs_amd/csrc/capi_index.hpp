@@ -1,7 +1,7 @@
-// capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h (and its extensions hnsw_mi355x_hdbscan.h, hnsw_mi355x_hdbscan_select.h, hnsw_mi355x_hdbscan_predict.h and hnsw_mi355x_dbscan.h),
+// capi_index.hpp -- what is behind the opaque hnswgpu_index handle of include/hnsw_mi355x.h (and its extensions hnsw_mi355x_hdbscan.h, hnsw_mi355x_hdbscan_select.h, hnsw_mi355x_hdbscan_predict.h, hnsw_mi355x_dbscan.h and hnsw_mi355x_exact_screen.h),
 // for the translation units that implement the C ABI: capi.cpp, which holds the entries, and the .hip units that hold their device
 // side (exact_knn.hip, which also holds hnswgpu_exact_search_batch(_device) itself; exact_range.hip; knn_graph.hip; range_search.hip; symmetric_graph.hip;
-// graph_components.hip; spanning_forest.hip; dendrogram.hip; condensed_tree.hip; cluster_select.hip; cluster_predict.hip; dbscan.hip).  Private: not installed, not part of the ABI.
+// graph_components.hip; spanning_forest.hip; dendrogram.hip; condensed_tree.hip; cluster_select.hip; cluster_predict.hip; dbscan.hip; exact_screen.hip).  Private: not installed, not part of the ABI.
 // Three parts: the handle; the checks that entries share (empty index, resident replica, sorted filter, the limits of an exact call,
 // the zeroed k-NN answer, the tail), which live once, in capi.cpp, and are declared here as capi_* for the entries outside it; and
 // the device side of every host / _device pair, declared ONCE, here, with its arguments' struct (HNSWGPU_DEVICE_SIDE of
@@ -23,6 +23,7 @@
 #include "../../include/hnsw_mi355x_hdbscan_select.h"
 #include "../../include/hnsw_mi355x_hdbscan_predict.h"
 #include "../../include/hnsw_mi355x_dbscan.h"
+#include "../../include/hnsw_mi355x_exact_screen.h"
 #include "builder.hpp"
 #include "flat_index.hpp"
 #include "search_device.hpp"
@@ -388,6 +389,28 @@ struct CsrDbscanArgs {
     DbscanArgs call;
 };
 HNSWGPU_DEVICE_SIDE int csr_dbscan(const CsrDbscanArgs& a, bool host, void* stream, std::string& err);
+// the device side of hnswxs_exact_search_batch(_device) and hnswxs_screen_matrix, defined in exact_screen.hip (the
+// arguments have been checked as hnswgpu_exact_search_batch checks its own; at least one point).  out_stats is host memory either way.
+struct ExactScreenArgs {
+    const float* queries;     // nq x d
+    uint64_t nq, d, k;
+    const uint64_t* allowed;  // not nullptr: a filter, even when it is empty
+    uint64_t n_allowed;
+    uint64_t* out_ids;        // nq x k, like the three below
+    float* out_dists;
+    uint8_t* out_layer;       // may be nullptr
+    int32_t* out_rank;        // may be nullptr
+    uint32_t* out_counts;     // [nq]
+    uint64_t* out_stats;      // [3], may be nullptr
+};
+HNSWGPU_DEVICE_SIDE int exact_screened(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ExactScreenArgs& a, bool host, void* stream,
+                                       std::string& err);
+struct ScreenMatrixArgs {     // host memory
+    const float* queries;     // nq x d
+    uint64_t nq, d;
+    float* out_lb;            // nq x n
+};
+HNSWGPU_DEVICE_SIDE int exact_screen_matrix(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ScreenMatrixArgs& a, std::string& err);
 }  // namespace hnswgpu
 
 // No C++ exception may cross the C ABI: every entry point is `try { ... HNSWGPU_CAPI_GUARD_END(ret)`

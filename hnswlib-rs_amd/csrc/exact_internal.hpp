@@ -1,5 +1,5 @@
-// exact_internal.hpp -- the host side that exact_knn.hip (exhaustive k-NN, the filter set), exact_range.hip (exact range search) and
-// knn_graph.hip (the queries by stored point) share, and the one declaration of exact_device for them and for cluster_predict.hip:
+// exact_internal.hpp -- the host side that exact_knn.hip (exhaustive k-NN, the filter set), exact_screen.hip (the same behind a matrix-core
+// screen), exact_range.hip (exact range search) and knn_graph.hip (the queries by stored point) share, and the one declaration of exact_device for them and for cluster_predict.hip:
 // the replica's state and its scratch pool, the plan of a call's slabs, an optional filter's way to the device, the rows of a k-NN
 // answer and their staging.  The device pieces of the two slab kernels are in exact_tile.hpp.  Private, like graph_internal.hpp.
 #pragma once
@@ -20,18 +20,21 @@ namespace hnswgpu {
 constexpr int TQ = 16;  // queries per tile: one wavefront holds an accumulator each per lane
 constexpr uint32_t MIN_SLAB_ROWS = 256;
 constexpr uint32_t MAX_SLABS = 64;  // the k-NN merge keeps one slab per lane
+constexpr uint64_t SCRATCH_BUDGET = 320ull << 20;  // bytes of scratch per exact k-NN call at most (exact_knn.hip, exact_screen.hip), whatever nq and n are
 
 // What a replica keeps for these units (DeviceIndex::extension): the DataId ranks, and scratch blocks that calls take turns with
 struct ExactState {
     int device = -1;
     void* d_rank = nullptr;   // [n] u32: position of flat id f in ascending (DataId, flat id) order
     void* d_order = nullptr;  // [n] u32: its inverse
+    void* d_xnorm = nullptr;  // [n] f32: the rows' squared norms in plain f32, made by the first screened call (exact_screen.hip, under mu)
     std::mutex mu;
     std::vector<std::pair<void*, uint64_t>> pool;  // free scratch blocks {address, bytes}
     ~ExactState() {
         DeviceGuard on(device);
         if (d_rank) (void)hipFree(d_rank);
         if (d_order) (void)hipFree(d_order);
+        if (d_xnorm) (void)hipFree(d_xnorm);
         for (auto& b : pool) (void)hipFree(b.first);
     }
     const uint32_t* rank() const { return static_cast<const uint32_t*>(d_rank); }
@@ -157,6 +160,7 @@ struct ExactCall {
     uint64_t n_allowed = 0;
     const FilterSet* set = nullptr;
     GraphRows out{};  // layer and rank may be nullptr
+    const uint32_t* d_qlist = nullptr;  // no set, no d_self: the nq queries are rows d_qlist[0 .. nq) of d_queries and of out (exact_screen.hip's fallback)
 };
 // defined in exact_knn.hip; waits for `stream` before it returns
 int exact_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ExactCall& c, hipStream_t stream, std::string& err);

@@ -30,13 +30,12 @@
 
 #include "capi_index.hpp"
 #include "exact_internal.hpp"
+#include "exact_list.hpp"
 #include "exact_tile.hpp"
 #include "hnswio.hpp"
 
 namespace hnswgpu {
 namespace {
-
-constexpr uint64_t SCRATCH_BUDGET = 320ull << 20;  // bytes of scratch per call at most, whatever nq and n are
 
 struct ExactKnnArgs : SlabArgs {
     const uint32_t* order;  // [n] the inverse of rank
@@ -49,53 +48,6 @@ struct ExactKnnArgs : SlabArgs {
     const uint32_t* tword;  // [tiles * TQ] filter set: first word of the slot's bitmap in `allow` (prep kernel)
     const uint32_t* self_rank;  // [tiles * TQ] k-NN graph: the slot's query is the stored point of this DataId rank (prep kernel), never its own answer
 };
-
-__device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int lane) {
-    return ((uint64_t)readlane_u((uint32_t)(v >> 32), lane) << 32) | readlane_u((uint32_t)v, lane);
-}
-__device__ __forceinline__ uint64_t first_lane_u64(uint64_t v) {
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) |
-           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-}
-// the lists are private to one wavefront; what one lane stored another lane loads later
-__device__ __forceinline__ void list_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
-
-struct ListState {
-    uint32_t len;
-    uint64_t thr;  // KEY_NONE until the list is full, then its last key
-};
-// the keys of the lanes in `mask` go into the sorted list (all lanes take part; everything but `key` is wave-uniform)
-__device__ __attribute__((noinline)) ListState list_insert(uint64_t* list, uint32_t cap, ListState s, uint64_t key, uint64_t mask) {
-    const uint32_t lane = threadIdx.x;
-    // (arguments arrive in vector registers: say that they are wave-uniform, the loops below are scalar control flow then)
-    mask = first_lane_u64(mask);
-    cap = (uint32_t)__builtin_amdgcn_readfirstlane((int)cap);
-    s.len = (uint32_t)__builtin_amdgcn_readfirstlane((int)s.len);
-    s.thr = first_lane_u64(s.thr);
-    while (mask != 0ull) {
-        const int b = ctz64(mask);
-        mask &= mask - 1ull;
-        const uint64_t kb = readlane_u64(key, b);
-        if (!(kb < s.thr)) continue;  // an earlier key of this mask moved the threshold
-        // the entries above kb move up one slot, chunk by chunk from the tail (a chunk is loaded whole before it is stored); the
-        // one that falls off a full list is dropped.  Sorted: the entries below kb are a prefix, the walk ends in their chunk.
-        uint32_t pos = 0;
-        for (uint32_t c = (s.len + 63u) >> 6; c-- > 0u;) {
-            const uint32_t i = (c << 6) + lane;
-            const bool have = i < s.len;
-            const uint64_t v = have ? list[i] : KEY_NONE;
-            const bool below = have && v < kb;
-            const unsigned long long bm = __ballot(below);
-            if (have && !below && i + 1u < cap) list[i + 1u] = v;
-            if (bm != 0ull) { pos = (c << 6) + popc64(bm); break; }
-        }
-        if (lane == 0u) list[pos] = kb;
-        if (s.len < cap) ++s.len;
-        list_fence();
-        if (s.len == cap) s.thr = first_lane_u64(list[cap - 1u]);
-    }
-    return s;
-}
 
 // SET: `allow` holds one bitmap of ceil(n / 32) words per filter of the group and every query of the tile names its own
 // (a.tword); else one bitmap (or none) for all.
@@ -166,7 +118,7 @@ __global__ __launch_bounds__(64, METRIC == DIST_JEFFREYS || METRIC == DIST_JENSE
                 bool mine = SET ? ((elig >> t) & 1u) != 0u : ok;
                 if constexpr (SELF) mine = mine && rk != self[t];
                 const unsigned long long m = __ballot(mine && key < st[t].thr);
-                if (m != 0ull) st[t] = list_insert(lists + (size_t)t * cap, cap, st[t], key, m);
+                if (m != 0ull) st[t] = list_insert<true>(lists + (size_t)t * cap, cap, st[t], key, m);
             }
         }
     }
@@ -423,7 +375,7 @@ int exact_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id,
 
     if (!set) {
         if (filtered) HIP_TRY(launch_allow_bitmap(stream, v.origin_id, v.n, c.d_allowed, c.n_allowed, d_allow));
-        const int rc = run(nullptr, nq, nullptr);
+        const int rc = run(c.d_qlist, nq, nullptr);
         if (rc != OK) return rc;
         HIP_TRY(hipStreamSynchronize(stream));
         return OK;

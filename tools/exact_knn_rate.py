@@ -7,6 +7,9 @@ with two comparators measured on the same box and inputs:
     tools/gpu_call.sh exact_rate OUTDIR [--shapes sift1m,glove25,mnist784] [--nq 10000]      -> OUTDIR/rate.json
 One JSON line per shape on stdout, progress on stderr.  Warm-up calls first, then the median and the spread of `--repeats` calls.
 
+--screened: the screened call (hnswxs_exact_search_batch_device) is timed beside the existing one on the same inputs, its
+answers compared with the existing call's, with the certified share from out_stats and the share of the f32 matrix rate.
+
 Filter-set mode (--filter-set): hnswgpu_exact_search_batch_filter_set through Hnsw.exact_search_filters_flat on the first shape,
 with --filters F filters of --selectivity LO[,HI] (fractions of the points, spread evenly from LO to HI) named by the queries
 --naming random | same (every query names filter 0) | own (query q names filter q: F = nq), against the host loop it replaces
@@ -39,6 +42,7 @@ SHAPES = {  # BASELINE configs 2, 3, 5
 # "fraction of the VALU bound" below is a fraction of this model, not of the issue slots of the compiled loop.
 VALU_PER_ELEMENT = {"DistL2": 3, "DistCosine": 3}
 HBM_PEAK = 8.0e12  # bytes / s, MI355X data sheet
+F32_MATRIX_PEAK = 157.3e12  # flop / s, MI355X data sheet (f32 matrix)
 
 
 def clustered(n, d, seed):
@@ -131,6 +135,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--no-torch-comparator", action="store_true")
+    ap.add_argument("--screened", action="store_true", help="also time hnswxs_exact_search_batch_device on the same inputs")
+    ap.add_argument("--no-comparator-a", action="store_true", help="skip comparator (a)")
     ap.add_argument("--filter-set", action="store_true")
     ap.add_argument("--filters", type=int, default=64)
     ap.add_argument("--selectivity", default="0.01,0.5")
@@ -170,15 +176,44 @@ def main():
                                                      C.c_void_p(dd.data_ptr()), None, None, C.c_void_p(cnt.data_ptr()), None)
             assert rc == 0, N.last_error()
         med, lo, hi = timed(call, a.warmup, a.repeats)
+        screened = None
+        if a.screened and hasattr(L, "hnswxs_exact_search_batch_device"):
+            # the screened call beside the existing one: same queries, same out arrays' shapes, and its answers compared with the
+            # existing call's (equal work); the certified share from out_stats
+            ids2, dd2, cnt2 = torch.zeros_like(ids), torch.zeros_like(dd), torch.zeros_like(cnt)
+            stats = np.zeros(3, np.uint64)
+
+            def call_screened():
+                rc = L.hnswxs_exact_search_batch_device(h.handle, C.c_void_p(dq.data_ptr()), nq, d, k, None, 0, C.c_void_p(ids2.data_ptr()),
+                                                                  C.c_void_p(dd2.data_ptr()), None, None, C.c_void_p(cnt2.data_ptr()),
+                                                                  stats.ctypes.data_as(C.c_void_p), None)
+                assert rc == 0, N.last_error()
+            smed, slo, shi = timed(call_screened, a.warmup, a.repeats)
+            same = bool(torch.equal(ids, ids2) and torch.equal(dd.view(torch.int32), dd2.view(torch.int32)) and torch.equal(cnt, cnt2))
+            dpad = (d + 31) // 32 * 32
+            screened = dict(seconds_median=smed, seconds_min=slo, seconds_max=shi, pair_evaluations_per_s=n * nq / smed,
+                            ms_per_10000_queries=smed * 1e3 * 10_000 / nq, stats=[int(x) for x in stats], certified_share=float(stats[0]) / nq,
+                            same_answers_as_existing_call=same, existing_over_screened=med / smed,
+                            # the multiply-adds the screen issues (rows padded to 32 elements) against the data sheet's f32 matrix rate
+                            fraction_of_f32_matrix_peak=2.0 * n * nq * dpad / smed / F32_MATRIX_PEAK)
         stride = (d + 31) // 32 * 32
         tiles = (nq + 15) // 16
         out = dict(shape=name, n=n, d=d, dist=dist, nq=nq, k=k, seconds_median=med, seconds_min=lo, seconds_max=hi, repeats=a.repeats,
                    pair_evaluations_per_s=n * nq / med, ms_per_10000_queries=med * 1e3 * 10_000 / nq,
                    valu_bound_pairs_per_s=cus * 64 * clock_hz / (VALU_PER_ELEMENT[dist] * 4 * ((d + 3) // 4)), clock_hz=clock_hz, cus=cus,
                    bytes_read_per_query=n * stride * 4 * tiles / nq, )
+        if screened is not None:
+            out["screened"] = screened
+            if not screened["same_answers_as_existing_call"]:
+                failed.append(name + " (screened answers differ)")
         out["fraction_of_valu_bound"] = out["pair_evaluations_per_s"] / out["valu_bound_pairs_per_s"]
         out["fraction_of_hbm_peak"] = out["bytes_read_per_query"] * nq / med / HBM_PEAK
         # (a) eval_distance_matrix in slices of rows + host selection, and the new entry (host buffers) on the same few queries
+        if a.no_comparator_a:
+            print(json.dumps(out), flush=True)
+            del h, dq, ids, dd, cnt
+            torch.cuda.empty_cache()
+            continue
         ns = min(a.nq_small, nq)
         Qs = np.ascontiguousarray(Q[:ns])
 

@@ -3,7 +3,9 @@
     tools/kres.py METRIC PART [extra -D flags ...]      e.g.  tools/kres.py 0 0
     tools/kres.py exact [extra -D flags ...]            the kernels of exact_knn.hip, exact_range.hip and knn_graph.hip (every
                                                         instantiation of the two slab kernels)
-    tools/kres.py dbscan [extra -D flags ...]           the kernels of dbscan.hip (both passes of its slab kernel per metric)"""
+    tools/kres.py dbscan [extra -D flags ...]           the kernels of dbscan.hip (both passes of its slab kernel per metric)
+    tools/kres.py screen [extra -D flags ...]           the kernels of exact_screen.hip (screen and rerank per metric; built, like the
+                                                        library's unit, without packed f32 instructions)"""
 import os
 import re
 import subprocess
@@ -12,8 +14,10 @@ import sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 flags = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-pthread", "--offload-arch=gfx950",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-Rpass-analysis=kernel-resource-usage"]
-if sys.argv[1] in ("exact", "dbscan"):
-    units = ("exact_knn", "exact_range", "knn_graph") if sys.argv[1] == "exact" else ("dbscan",)
+if sys.argv[1] in ("exact", "dbscan", "screen"):
+    units = {"exact": ("exact_knn", "exact_range", "knn_graph"), "dbscan": ("dbscan",), "screen": ("exact_screen",)}[sys.argv[1]]
+    if sys.argv[1] == "screen":
+        flags += ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
     cmds = [[*flags, *sys.argv[2:], "-c", unit + ".hip", "-o", f"/tmp/kres_{unit}.o"] for unit in units]
 else:
     metric, part, extra = sys.argv[1], sys.argv[2], sys.argv[3:]
