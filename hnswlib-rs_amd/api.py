@@ -898,6 +898,44 @@ class Hnsw:
         total = int(offsets[nq])
         return RangeResult(offsets, ids[:total], dists[:total], layers[:total], ranks[:total])
 
+    def exact_range_search_screened_flat(self, datas, radius, allowed_ids=None):
+        """exact_range_search_flat through the matrix-core screen (include/hnsw_mi355x_exact_range_screen.h): the same RangeResult
+        byte for byte, and stats, three u64: queries answered through the screen, queries answered by the existing path because a
+        buffer of the screened path was outgrown, queries not screened at all (a distance without a screen, a small index, very
+        long rows).  Returns (RangeResult, stats)."""
+        datas = np.ascontiguousarray(datas, dtype=np.float32)
+        if datas.ndim != 2:
+            raise HnswError(N.ERR_ARG, "datas must be a (nq, d) matrix")
+        nq, d = datas.shape
+        radii = np.asarray(radius, dtype=np.float32)
+        if radii.ndim == 0:
+            radii = np.full(nq, radii, np.float32)
+        if radii.shape != (nq,):
+            raise HnswError(N.ERR_ARG, "radius must be a scalar or hold one radius per query")
+        radii = np.ascontiguousarray(radii)
+        offsets = np.zeros(nq + 1, np.uint64)
+        stats = np.array([0, 0, nq], np.uint64)
+
+        def empty(cap):
+            return np.zeros(cap, np.uint64), np.zeros(cap, np.float32), np.zeros(cap, np.uint8), np.zeros(cap, np.int32)
+        if self._h is None:
+            return RangeResult(offsets, *empty(0)), stats
+        allowed, n_allowed = None, 0
+        if allowed_ids is not None:
+            n_allowed = len(allowed_ids)
+            allowed = np.ascontiguousarray(allowed_ids, dtype=np.uint64) if n_allowed else np.zeros(1, np.uint64)
+        cap = max(1024, 32 * nq)
+        for attempt in range(2):
+            ids, dists, layers, ranks = empty(cap)
+            rc = self._lib.hnswxr_exact_range_search_batch(self._h, _p(datas), nq, d, _p(radii), _p(allowed), n_allowed, cap, _p(offsets),
+                                                           _p(ids), _p(dists), _p(layers), _p(ranks), _p(stats))
+            if rc != N.ERR_CAPACITY or attempt == 1:
+                break
+            cap = int(offsets[nq])
+        _check(rc)
+        total = int(offsets[nq])
+        return RangeResult(offsets, ids[:total], dists[:total], layers[:total], ranks[:total]), stats
+
     def exact_range_search(self, datas, radius, allowed_ids=None):
         """exact_range_search_flat as Vec<Vec<Neighbour>> in input order."""
         return self.exact_range_search_flat(datas, radius, allowed_ids).to_neighbours()

@@ -1936,6 +1936,51 @@ int hnswxs_screen_matrix(const hnswgpu_index* cidx, const float* queries, uint64
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
+// ---- exact range search behind a matrix-core screen (hnsw_mi355x_exact_range_screen.h; exact_range_screen.hip holds the device
+// side): the checks are hnswgpu_exact_range_search_batch's own, in its order
+static int exact_range_screened_pair(const hnswgpu_index* cidx, const ExactRangeCallArgs& a, uint64_t* out_stats, bool host, void* stream) {
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    int rc = exact_range_call(idx, a);
+    if (rc != HNSWGPU_OK) return rc;
+    if (host) {
+        rc = check_sorted_filter(a.allowed, a.n_allowed);
+        if (rc != HNSWGPU_OK) return rc;
+        if (index_empty(idx) || a.nq == 0) {  // no point, or no query: every answer is empty, nothing was screened
+            std::memset(a.out_offsets, 0, (a.nq + 1) * sizeof(uint64_t));
+            if (out_stats) out_stats[0] = out_stats[1] = 0, out_stats[2] = a.nq;
+            return HNSWGPU_OK;
+        }
+    }
+    if (!hnswgpu::exact_range_screened) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = call_replica(idx, sl, host, true, true, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    return finish(hnswgpu::exact_range_screened(*dev, idx->flat->origin_id, a, out_stats, host, stream, err), err);
+}
+
+int hnswxr_exact_range_search_batch(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, const float* radii,
+                                    const uint64_t* allowed_ids, uint64_t n_allowed, uint64_t cap, uint64_t* out_offsets, uint64_t* out_ids,
+                                    float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint64_t* out_stats) {
+    CAPI_GUARD_BEGIN
+    return exact_range_screened_pair(idx, ExactRangeCallArgs{queries, radii, nq, d, allowed_ids, n_allowed, cap, out_offsets, out_ids, out_dists, out_layer, out_rank},
+                                     out_stats, true, nullptr);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswxr_exact_range_search_batch_device(const hnswgpu_index* idx, const float* d_queries, uint64_t nq, uint64_t d, const float* d_radii,
+                                           const uint64_t* d_allowed_ids, uint64_t n_allowed, uint64_t cap, uint64_t* d_out_offsets,
+                                           uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank,
+                                           uint64_t* out_stats, void* stream) {
+    CAPI_GUARD_BEGIN
+    return exact_range_screened_pair(idx, ExactRangeCallArgs{d_queries, d_radii, nq, d, d_allowed_ids, n_allowed, cap, d_out_offsets, d_out_ids, d_out_dists,
+                                                             d_out_layer, d_out_rank},
+                                     out_stats, false, stream);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
 static int csr_dbscan_pair(const CsrDbscanArgs& a, bool host, void* stream) {
     int rc = dbscan_call_check("csr dbscan", a.n, a.call);
     if (rc != HNSWGPU_OK) return rc;

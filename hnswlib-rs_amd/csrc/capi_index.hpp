@@ -24,6 +24,7 @@
 #include "../../include/hnsw_mi355x_hdbscan_predict.h"
 #include "../../include/hnsw_mi355x_dbscan.h"
 #include "../../include/hnsw_mi355x_exact_screen.h"
+#include "../../include/hnsw_mi355x_exact_range_screen.h"
 #include "builder.hpp"
 #include "flat_index.hpp"
 #include "search_device.hpp"
@@ -411,6 +412,10 @@ struct ScreenMatrixArgs {     // host memory
     float* out_lb;            // nq x n
 };
 HNSWGPU_DEVICE_SIDE int exact_screen_matrix(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ScreenMatrixArgs& a, std::string& err);
+// the device side of hnswxr_exact_range_search_batch(_device), defined in exact_range_screen.hip: exact_range's arguments, checked as
+// hnswgpu_exact_range_search_batch checks its own, and out_stats ([3], host memory either way, may be nullptr)
+HNSWGPU_DEVICE_SIDE int exact_range_screened(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ExactRangeCallArgs& a, uint64_t* out_stats,
+                                             bool host, void* stream, std::string& err);
 }  // namespace hnswgpu
 
 // No C++ exception may cross the C ABI: every entry point is `try { ... HNSWGPU_CAPI_GUARD_END(ret)`

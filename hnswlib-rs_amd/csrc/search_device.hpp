@@ -61,6 +61,10 @@ struct Knobs {
                                  // one-query kernels, literal kernel), applied behind every other bound (1 ..) -- a workgroup then answers many queries in turn
     int64_t range_hits_per_pass = -1;  // HNSWGPU_RANGE_HITS_PER_PASS (test hook): the answers one fill pass of the exact range search holds (1 .. 2^31; unset: 8 Mi) --
                                  // a small batch's chunk plan then takes several turns; a query with more answers still gets a pass of its own
+    int64_t range_screen_cap = -1;    // HNSWGPU_RANGE_SCREEN_CAP (test hook): both buffer capacities of the screened exact range search -- a chunk's candidates and
+                                 // the call's keys (1 .. 2^31; unset: 2 Mi and 8 Mi) -- a call that outgrows either is answered by the existing path
+    int64_t range_screen_tiles = -1;  // HNSWGPU_RANGE_SCREEN_TILES (test hook): the tiles of queries one chunk of the screened exact range search holds at most
+                                 // (1 ..; unset: what 16 MiB of padded queries hold)
     int64_t graph_chunk = -1;    // HNSWGPU_GRAPH_CHUNK (test hook): the points one chunk of hnswgpu_graph_search_batch gathers and searches at most (1 ..; unset: what
                                  // its 256 MiB of queries and staged answers hold)
     int64_t range_chunk = -1;    // HNSWGPU_RANGE_CHUNK (test hook): the queries one group of hnswgpu_range_search_batch serves at most (1 ..; unset: as many as

@@ -51,7 +51,7 @@ int hnswxs_exact_search_batch_device(const hnswgpu_index* idx, const float* d_qu
  *             written.                                                                                                             */
 int hnswxs_screen_matrix(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, float* out_lb);
 
-/* Out of scope: a set of filters; the queries by stored point; the range search; DBSCAN's passes; F16 storage; sharding.           */
+/* Out of scope: a set of filters; the queries by stored point; DBSCAN's passes; F16 storage; sharding.                             */
 
 #ifdef __cplusplus
 }

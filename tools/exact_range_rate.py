@@ -10,6 +10,15 @@ against the yardstick hnswgpu_exact_search_batch at k = 10 of the same build on 
     exact_range_rate.py --dump-dir DIR --one-filter     times the existing one-filter exact k-NN call (30 % allowed, k = 10) on the
                                                         dumped index; with --package-root DIR2 through the package of another checkout
                                                         (the parent commit, built there): the regression check
+    exact_range_rate.py --screened [--n N --dim D --dist DIST] [--package-root DIR2]
+                                                        the DEVICE entries on the null stream, device buffers made once: the existing
+                                                        call and, where the package has it, hnswxr_exact_range_search_batch_device on
+                                                        the same inputs, with its out_stats, at about 10 answers per query (each
+                                                        query's 10th-nearest distance) and at one radius for all (about
+                                                        --wide-answers answers per query, from 64 queries' pooled nearest
+                                                        distances); the bytes of both are compared.  One JSON line per case,
+                                                        `build`: what --build says.  With --package-root: the existing call of another
+                                                        checkout (the parent commit, built there)
 Warm-up calls first, then the median and the spread of --repeats calls."""
 import argparse
 import csv
@@ -58,6 +67,47 @@ def range_call(H, h, Q, radii, cap, outs):
     ptrs = [_p(o) for o in outs] if cap else [None] * 4
     rc = H.lib().hnswgpu_exact_range_search_batch(h.handle, _p(Q), nq, d, _p(radii), None, 0, cap, _p(offs), *ptrs)
     return rc, offs
+
+
+def device_range_call(L, name, h, dq, dr, nq, d, cap, outs, stats):
+    import torch
+    ptr = [C.c_void_p(t.data_ptr()) for t in outs]
+    tail = (stats.ctypes.data_as(C.c_void_p), None) if stats is not None else (None,)
+    rc = getattr(L, name)(h.handle, C.c_void_p(dq.data_ptr()), nq, d, C.c_void_p(dr.data_ptr()), None, 0, cap, ptr[0], *(ptr[1:] if cap else [None] * 4), *tail)
+    torch.cuda.synchronize()
+    return rc
+
+
+def screened_mode(H, a):
+    import torch
+    n, d, nq, L = a.n, a.dim, a.nq, H.lib()
+    X, Q = clustered(n, d, 1), clustered(nq, d, 2)
+    h = H.Hnsw(8, n, 16, 16, a.dist)
+    h.set_build_options(nthreads=0, gpu_device=0, gpu_window=0)
+    h.parallel_insert(X)
+    h.upload(0)
+    knn = h.exact_search_flat(Q, 10)
+    # one radius for all: the value below which 64 queries' 4096 nearest distances, pooled, hold 64 x --wide-answers entries
+    pooled = np.sort(h.exact_search_flat(Q[:64], 4096).dists.ravel())
+    has = hasattr(L, "hnswxr_exact_range_search_batch_device")
+    dq = torch.from_numpy(Q).cuda()
+    for case, radii in (("about 10", np.ascontiguousarray(knn.dists[:, 9])), ("one radius", np.full(nq, pooled[min(64 * a.wide_answers, len(pooled) - 1)], np.float32))):
+        dr = torch.from_numpy(radii).cuda()
+        off = torch.zeros(nq + 1, dtype=torch.int64, device="cuda")
+        assert device_range_call(L, "hnswgpu_exact_range_search_batch_device", h, dq, dr, nq, d, 0, [off] * 5, None) in (0, H._native.ERR_CAPACITY)
+        total = int(off[-1])
+        mk = lambda: [torch.zeros(nq + 1, dtype=torch.int64, device="cuda"), torch.zeros(total, dtype=torch.int64, device="cuda"),
+                      torch.zeros(total, dtype=torch.float32, device="cuda"), torch.zeros(total, dtype=torch.uint8, device="cuda"),
+                      torch.zeros(total, dtype=torch.int32, device="cuda")]
+        old, new, stats = mk(), mk(), np.zeros(3, np.uint64)
+        out = dict(mode="screened", build=a.build, n=n, d=d, dist=a.dist, nq=nq, case=case, answers=total, answers_per_query=total / nq, warmup=a.warmup,
+                   repeats=a.repeats)
+        out["existing_s"] = timed(lambda: device_range_call(L, "hnswgpu_exact_range_search_batch_device", h, dq, dr, nq, d, total, old, None), a.warmup, a.repeats)
+        if has:
+            out["screened_s"] = timed(lambda: device_range_call(L, "hnswxr_exact_range_search_batch_device", h, dq, dr, nq, d, total, new, stats), a.warmup, a.repeats)
+            out["out_stats"] = stats.tolist()
+            out["same_bytes"] = bool(all(torch.equal(x, y) for x, y in zip(old, new)))
+        print(json.dumps(out), flush=True)
 
 
 def load(H, a):
@@ -110,6 +160,12 @@ def main():
     ap.add_argument("--parse-trace")
     ap.add_argument("--one-filter", action="store_true")
     ap.add_argument("--package-root", default=None)
+    ap.add_argument("--screened", action="store_true")
+    ap.add_argument("--n", type=int, default=N_POINTS)
+    ap.add_argument("--dim", type=int, default=DIM)
+    ap.add_argument("--dist", default=DIST)
+    ap.add_argument("--wide-answers", type=int, default=2700)
+    ap.add_argument("--build", default="this tree", help="what the lines say they were measured on: the checkout, a -D variant")
     a = ap.parse_args()
     if a.parse_trace:
         calls = parse_trace(a.parse_trace)
@@ -122,6 +178,9 @@ def main():
     torch.cuda.init()
     import hnsw_rs_amd as H
     H.build_native()
+    if a.screened:
+        screened_mode(H, a)
+        return
     n, d, nq = N_POINTS, DIM, a.nq
     Q = clustered(nq, d, 2)
     if a.one_filter:
