@@ -1110,6 +1110,31 @@ class Hnsw:
         _check(self._lib.hnswdbs_exact(self._h, eps, min_samples, _p(labels), _p(core), _p(counts), _p(anchors), _p(c)))
         return DbscanResult(labels, core.astype(bool), counts, anchors, int(c[0]))
 
+    def dbscan_screened(self, eps, min_samples):
+        """dbscan(eps, min_samples) behind the two-sided matrix-core screen (hnswxd_exact): the same DbscanResult byte for byte, and the
+        four stats words -- points answered through the screen, answered by the existing path because the candidate buffer was
+        outgrown, not screened at all, pairs that went through the exact chain.  Returns (DbscanResult, stats)."""
+        eps, min_samples = _dbscan_params(eps, min_samples)
+        labels, core, counts, anchors, c = _dbscan_arrays(self.get_nb_point())
+        stats = np.zeros(4, np.uint64)
+        if self._h is None:
+            return DbscanResult(labels, core.astype(bool), counts, anchors, 0), stats
+        _check(self._lib.hnswxd_exact(self._h, eps, min_samples, _p(labels), _p(core), _p(counts), _p(anchors), _p(c), _p(stats)))
+        return DbscanResult(labels, core.astype(bool), counts, anchors, int(c[0])), stats
+
+    def dbscan_bounds_matrix(self, datas):
+        """The screen's two bounds of every (row of datas, stored point) distance, two (nq, n) f32 matrices (lb, ub) with the points in
+        dump order: the diagnostic entry hnswxd_bounds_matrix.  ub is +inf where the bound is not proved.  nq * n up to 2^24; DistL2,
+        DistDot, DistCosine."""
+        datas = np.ascontiguousarray(datas, dtype=np.float32)
+        if datas.ndim != 2:
+            raise HnswError(N.ERR_ARG, "datas must be a (nq, d) matrix")
+        nq, d = datas.shape
+        lb, ub = np.zeros((nq, self.get_nb_point()), np.float32), np.zeros((nq, self.get_nb_point()), np.float32)
+        if self._h is not None:
+            _check(self._lib.hnswxd_bounds_matrix(self._h, _p(datas), nq, d, _p(lb), _p(ub)))
+        return lb, ub
+
     def knn_graph_spanning_forest(self, knbn, ef=None, mode="union", core_k=0):
         """The minimum spanning forest of the graph symmetric_knn_graph_flat(knbn, ef, mode) would build, taken on the device without
         building it.  Vertices are POSITIONS.  "union": a pair weighs the min of its directions in the directed graph; "mutual": the

@@ -1835,7 +1835,8 @@ static int dbscan_call_check(const char* what, uint64_t n, const DbscanArgs& a) 
     return HNSWGPU_OK;
 }
 
-static int exact_dbscan_pair(const hnswgpu_index* cidx, const DbscanArgs& a, bool host, void* stream) {
+// (screened: the entries of hnsw_mi355x_dbscan_screen.h -- the same checks in the same order, then dbscan_screen.hip; out_stats is theirs)
+static int exact_dbscan_pair(const hnswgpu_index* cidx, const DbscanArgs& a, bool host, void* stream, bool screened = false, uint64_t* out_stats = nullptr) {
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
     std::shared_lock<std::shared_mutex> sl(idx->mu);
@@ -1847,13 +1848,15 @@ static int exact_dbscan_pair(const hnswgpu_index* cidx, const DbscanArgs& a, boo
     if (rc != HNSWGPU_OK) return rc;
     if (index_empty(idx)) {  // no vertex: no cluster, nothing else written
         *a.out.out_n = 0;
+        if (out_stats) out_stats[0] = out_stats[1] = out_stats[2] = out_stats[3] = 0;
         return HNSWGPU_OK;
     }
-    if (!hnswgpu::exact_dbscan) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    if (!hnswgpu::exact_dbscan || (screened && !hnswgpu::exact_dbscan_screened)) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     DeviceIndex* dev = nullptr;
     rc = call_replica(idx, sl, host, true, true, &dev);
     if (rc != HNSWGPU_OK) return rc;
     std::string err;
+    if (screened) return finish(hnswgpu::exact_dbscan_screened(*dev, idx->flat->origin_id, a, out_stats, host, stream, err), err);
     return finish(hnswgpu::exact_dbscan(*dev, idx->flat->origin_id, a, host, stream, err), err);
 }
 
@@ -1979,6 +1982,46 @@ int hnswxr_exact_range_search_batch_device(const hnswgpu_index* idx, const float
                                                              d_out_layer, d_out_rank},
                                      out_stats, false, stream);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+// ---- exact DBSCAN behind a two-sided matrix-core screen (hnsw_mi355x_dbscan_screen.h; dbscan_screen.hip holds the device side): the
+// checks are hnswdbs_exact's own (exact_dbscan_pair)
+int hnswxd_exact(const hnswgpu_index* idx, float eps, uint64_t min_samples, int32_t* out_label, uint8_t* out_core, uint32_t* out_count,
+                 uint32_t* out_anchor, uint64_t* out_n_clusters, uint64_t* out_stats) {
+    CAPI_GUARD_BEGIN
+    return exact_dbscan_pair(idx, DbscanArgs{eps, min_samples, DbscanOut{out_label, out_core, out_count, out_anchor, out_n_clusters}}, true, nullptr, true,
+                             out_stats);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswxd_exact_device(const hnswgpu_index* idx, float eps, uint64_t min_samples, int32_t* d_out_label, uint8_t* d_out_core, uint32_t* d_out_count,
+                        uint32_t* d_out_anchor, uint64_t* out_n_clusters, uint64_t* out_stats, void* stream) {
+    CAPI_GUARD_BEGIN
+    return exact_dbscan_pair(idx, DbscanArgs{eps, min_samples, DbscanOut{d_out_label, d_out_core, d_out_count, d_out_anchor, out_n_clusters}}, false, stream,
+                             true, out_stats);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+int hnswxd_bounds_matrix(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, float* out_lb, float* out_ub) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    const uint64_t dim = index_dimension(idx);
+    if (nq != 0 && (!queries || !out_lb || !out_ub)) return fail(HNSWGPU_ERR_ARG, "null buffer");
+    if (dim != 0 && d != dim) return fail(HNSWGPU_ERR_ARG, "query dimension differs from the index dimension");
+    if (idx->arithmetic != HNSWGPU_ARITH_SCALAR)
+        return fail(HNSWGPU_ERR_ARG, "the screen bounds the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
+    int rc = capi_refuse_f16(idx, "the screen");
+    if (rc != HNSWGPU_OK) return rc;
+    if (index_empty(idx) || nq == 0) return HNSWGPU_OK;
+    if (!hnswgpu::dbscan_bounds_matrix) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = primary_f32_replica(idx, sl, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    return finish(hnswgpu::dbscan_bounds_matrix(*dev, idx->flat->origin_id, DbscanBoundsArgs{queries, nq, d, out_lb, out_ub}, err), err);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 
 static int csr_dbscan_pair(const CsrDbscanArgs& a, bool host, void* stream) {

@@ -416,6 +416,17 @@ HNSWGPU_DEVICE_SIDE int exact_screen_matrix(const DeviceIndex& dev, const std::v
 // hnswgpu_exact_range_search_batch checks its own, and out_stats ([3], host memory either way, may be nullptr)
 HNSWGPU_DEVICE_SIDE int exact_range_screened(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ExactRangeCallArgs& a, uint64_t* out_stats,
                                              bool host, void* stream, std::string& err);
+// the device side of hnswxd_exact(_device) and hnswxd_bounds_matrix, defined in dbscan_screen.hip: exact_dbscan's arguments, checked as
+// hnswdbs_exact checks its own, and out_stats ([4], host memory either way, may be nullptr)
+HNSWGPU_DEVICE_SIDE int exact_dbscan_screened(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const DbscanArgs& a, uint64_t* out_stats, bool host,
+                                              void* stream, std::string& err);
+struct DbscanBoundsArgs {     // host memory
+    const float* queries;     // nq x d
+    uint64_t nq, d;
+    float* out_lb;            // nq x n, like out_ub
+    float* out_ub;
+};
+HNSWGPU_DEVICE_SIDE int dbscan_bounds_matrix(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const DbscanBoundsArgs& a, std::string& err);
 }  // namespace hnswgpu
 
 // No C++ exception may cross the C ABI: every entry point is `try { ... HNSWGPU_CAPI_GUARD_END(ret)`

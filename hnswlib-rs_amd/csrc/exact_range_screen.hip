@@ -68,22 +68,7 @@ struct RangeScreenArgs {
     uint32_t zero_tail;     // DistCosine rows that carry their norm in their last 8 bytes: those two elements are no data
 };
 
-// DistL2: the greatest f32 x with sqrt(x) <= r, the sqrt being screen_lb's (correctly rounded, so monotone): for every x in
-// [+0, +inf], sqrt(x) <= r exactly when x <= this value.  -1 where no x has it (r below -0, r NaN).  The walk starts within a few
-// units in the last place of the cut: r * r is one rounding away from r^2, and the cut lies less than two further on.
-__device__ float sqrt_cut(float r) {
-    if (!(r >= 0.f)) return -1.f;
-    float x = fminf(r * r, 3.4028234664e38f);
-    while (x > 0.f && __builtin_sqrtf(x) > r) x = __uint_as_float(__float_as_uint(x) - 1u);
-    while (x < __builtin_inff()) {
-        const float y = __uint_as_float(__float_as_uint(x) + 1u);
-        if (!(__builtin_sqrtf(y) <= r)) break;
-        x = y;
-    }
-    return x;
-}
-
-// screen_lb<METRIC>(s, nq, nx, cu) <= radius.  cut: the radius -- or, DistL2, sqrt_cut(radius), and the test is made in front of
+// screen_lb<METRIC>(s, nq, nx, cu) <= radius.  cut: the radius -- or, DistL2, sqrt_cut(radius) (exact_screen_parts.hpp), and the test is made in front of
 // screen_lb's square root on the very value it would take the root of (DESIGN.md 15.14 has the equivalence).
 template <int METRIC>
 __device__ __forceinline__ bool screen_within(float s, float nq, float nx, float cu, float cut) {

@@ -1,6 +1,7 @@
-// exact_screen_parts.hpp -- what the two units behind a matrix-core screen share: exact_screen.hip (the exact k-NN) and
-// exact_range_screen.hip (the exact range search).  The shape of a screen workgroup and its LDS, the bound itself (screen_coeff,
-// screen_lb: DESIGN.md section 15.13), the preparation of a chunk's queries, and the rows' plain f32 norms, which the replica keeps.
+// exact_screen_parts.hpp -- what the units behind a matrix-core screen share: exact_screen.hip (the exact k-NN),
+// exact_range_screen.hip (the exact range search) and dbscan_screen.hip (exact DBSCAN).  The shape of a screen workgroup and its LDS,
+// the bounds themselves (screen_coeff, screen_lb: DESIGN.md section 15.13; screen_proved, screen_ub: 15.15; sqrt_cut: 15.14), the
+// preparation of a chunk's queries, and the rows' plain f32 norms, which the replica keeps.
 // Private: not installed, not part of the ABI; a unit includes it once, behind exact_tile.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -56,6 +57,46 @@ __device__ __forceinline__ float screen_lb(float s, float nq, float nx, float cu
         lb = (float)fmax(1. - (double)(c + cu), 0.);
     }
     return ok ? lb : 0.f;
+}
+
+// The range in which screen_lb and screen_ub are proved: both norms in [NORM_LO, NORM_HI] (a NaN is outside), the screen value finite
+__device__ __forceinline__ bool screen_proved(float s, float nq, float nx) {
+    return nq >= NORM_LO && nq <= NORM_HI && nx >= NORM_LO && nx <= NORM_HI && fabsf(s) <= 3.0e38f;
+}
+
+// An upper bound, as an f32, of the same distance, from the same inputs and with the same error term as screen_lb (DESIGN.md 15.15:
+// the inequalities behind screen_lb are two-sided, and the same coefficients cover the roundings on this side).  Again the
+// reference's own monotone last step, on a bound of its argument from the other side.  ONLY inside screen_proved: outside it there
+// is no upper bound, the value returned means nothing, and a caller has to treat the pair as undecided by screen_proved itself.
+template <int METRIC>
+__device__ __forceinline__ float screen_ub(float s, float nq, float nx, float cu) {
+    if constexpr (METRIC == DIST_L2) {
+        const float w = nq + nx;
+        const float t = w - 2.f * s;
+        return __builtin_sqrtf(fmaxf(t + cu * w, 0.f));
+    } else if constexpr (METRIC == DIST_DOT) {
+        const float w = nq + nx;
+        return fmaxf(1.f - (s - cu * w), 0.f);
+    } else {
+        const float c = s / __builtin_sqrtf(nq * nx);
+        return (float)fmax(1. - (double)(c - cu), 0.);
+    }
+}
+
+// DistL2: the greatest f32 x with sqrt(x) <= r, the sqrt being screen_lb's (correctly rounded, so monotone): for every x in
+// [+0, +inf], sqrt(x) <= r exactly when x <= this value.  -1 where no x has it (r below -0, r NaN).  The walk starts within a few
+// units in the last place of the cut: r * r is one rounding away from r^2, and the cut lies less than two further on.  (The k-NN
+// screen has no radius and no caller for it.)
+[[maybe_unused]] __device__ float sqrt_cut(float r) {
+    if (!(r >= 0.f)) return -1.f;
+    float x = fminf(r * r, 3.4028234664e38f);
+    while (x > 0.f && __builtin_sqrtf(x) > r) x = __uint_as_float(__float_as_uint(x) - 1u);
+    while (x < __builtin_inff()) {
+        const float y = __uint_as_float(__float_as_uint(x) + 1u);
+        if (!(__builtin_sqrtf(y) <= r)) break;
+        x = y;
+    }
+    return x;
 }
 
 // LDS of a workgroup of `waves` wavefronts: the queries (pitch dpad + 4 floats: 16-byte reads of 8 consecutive queries cover every

@@ -85,6 +85,10 @@ Knobs read_knobs() {
         const long long v = std::atoll(e);
         k.range_screen_tiles = v < 1 ? -1 : (int64_t)std::min<long long>(v, 1ll << 31);
     }
+    if (const char* e = std::getenv("HNSWGPU_DBSCAN_SCREEN_CAP")) {
+        const long long v = std::atoll(e);
+        k.dbscan_screen_cap = v < 1 ? -1 : (int64_t)std::min<long long>(v, 1ll << 31);
+    }
     if (const char* e = std::getenv("HNSWGPU_GRAPH_CHUNK")) {
         const long long v = std::atoll(e);
         k.graph_chunk = v < 1 ? -1 : (int64_t)std::min<long long>(v, 1ll << 31);

@@ -65,6 +65,8 @@ struct Knobs {
                                  // the call's keys (1 .. 2^31; unset: 2 Mi and 8 Mi) -- a call that outgrows either is answered by the existing path
     int64_t range_screen_tiles = -1;  // HNSWGPU_RANGE_SCREEN_TILES (test hook): the tiles of queries one chunk of the screened exact range search holds at most
                                  // (1 ..; unset: what 16 MiB of padded queries hold)
+    int64_t dbscan_screen_cap = -1;   // HNSWGPU_DBSCAN_SCREEN_CAP (test hook): the candidates one chunk and pass of the screened exact DBSCAN holds (1 .. 2^31; unset:
+                                 // 2 Mi) -- a call that outgrows it is answered by the existing path
     int64_t graph_chunk = -1;    // HNSWGPU_GRAPH_CHUNK (test hook): the points one chunk of hnswgpu_graph_search_batch gathers and searches at most (1 ..; unset: what
                                  // its 256 MiB of queries and staged answers hold)
     int64_t range_chunk = -1;    // HNSWGPU_RANGE_CHUNK (test hook): the queries one group of hnswgpu_range_search_batch serves at most (1 ..; unset: as many as

@@ -6,6 +6,8 @@ index: n x 128 DistL2, clustered, GPU-assisted build, M = 16, ef_construction 64
   * hnswdbs_exact_device at min_samples = 10 and three eps: the 10th-nearest distance (the point itself included) that --core of a
     sample of the points reach -- few points core, about half, nearly all;
   * hnswdbs_csr_device on the symmetric graph at k = 10 (ef = 64, UNION, add_self 1), eps the middle one.
+--screened: hnswxd_exact_device (the same bytes behind the two-sided matrix-core screen) is timed beside hnswdbs_exact_device on the same
+inputs, its out_stats kept and its five outputs compared with the existing call's.
 One warm-up call, then the median of --repeats.  One JSON line.
     dbscan_rate.py --n 1000000
 Per-kernel times: run the tool under `rocprofv3 --kernel-trace --stats -- python tools/dbscan_rate.py --n N`."""
@@ -33,6 +35,7 @@ def main():
     ap.add_argument("--core", type=float, nargs="+", default=[0.05, 0.5, 0.98])
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--screened", action="store_true", help="also time hnswxd_exact_device on the same inputs")
     a = ap.parse_args()
     import torch
     torch.cuda.init()
@@ -80,6 +83,15 @@ def main():
         b["dbscan_exact_device_s"] = timed(dbscan_form, a.warmup, a.repeats)
         b["clusters"], b["core"], b["noise"] = int(c[0]), int(core.sum().item()), int((label < 0).sum().item())
         b["ratio_to_one_count_pass"] = b["dbscan_exact_device_s"]["median"] / b["count_pass_scaled_to_n_s"]
+        if a.screened:
+            old, stats = [t.clone() for t in (label, core, count, anchor)] + [int(c[0])], np.zeros(4, np.uint64)
+
+            def screened_form():
+                rc = L.hnswxd_exact_device(h.handle, eps, MIN_SAMPLES, ptr(label), ptr(core), ptr(count), ptr(anchor), c.ctypes.data, stats.ctypes.data, None)
+                assert rc == 0, N.last_error()
+            b["dbscan_screened_device_s"] = timed(screened_form, a.warmup, a.repeats)
+            b["out_stats"] = stats.tolist()
+            b["same_bytes"] = all(torch.equal(x, y) for x, y in zip(old[:4], (label, core, count, anchor))) and old[4] == int(c[0])
         out["cases"].append(b)
     g = h.symmetric_knn_graph_flat(K, EF, "union")
     d_offs, d_cols, d_dists = dev(g.offsets.view(np.int64)), dev(g.pos.astype(np.uint32).view(np.int32)), dev(g.dists)
