@@ -804,6 +804,15 @@ class Hnsw:
         """exact_search_flat through the matrix-core screen (include/hnsw_mi355x_exact_screen.h): the same BatchResult byte for byte,
         and stats, three u64: queries certified by the screen, queries the certificate handed to the existing path, queries not
         screened at all (a distance without a screen, knbn + 54 above 4096, a small index, very long rows).  Returns (BatchResult, stats)."""
+        return self._exact_screened("hnswxs_exact_search_batch", datas, knbn, allowed_ids)
+
+    def exact_search_long_flat(self, datas, knbn, allowed_ids=None):
+        """exact_search_screened_flat with the screen for long rows (include/hnsw_mi355x_exact_long.h): rows of 257 to 4096 elements
+        go through a kernel that streams queries and rows, shorter ones through the screen above; the same BatchResult byte for
+        byte, the same three stats.  Returns (BatchResult, stats)."""
+        return self._exact_screened("hnswxl_exact_search_batch", datas, knbn, allowed_ids)
+
+    def _exact_screened(self, entry, datas, knbn, allowed_ids):
         datas = np.ascontiguousarray(datas, dtype=np.float32)
         if datas.ndim != 2:
             raise HnswError(N.ERR_ARG, "datas must be a (nq, d) matrix")
@@ -820,20 +829,27 @@ class Hnsw:
         if allowed_ids is not None:
             n_allowed = len(allowed_ids)
             allowed = np.ascontiguousarray(allowed_ids, dtype=np.uint64) if n_allowed else np.zeros(1, np.uint64)
-        _check(self._lib.hnswxs_exact_search_batch(self._h, _p(datas), nq, d, knbn, _p(allowed), n_allowed, _p(ids), _p(dists),
-                                                             _p(layers), _p(ranks), _p(counts), _p(stats)))
+        _check(getattr(self._lib, entry)(self._h, _p(datas), nq, d, knbn, _p(allowed), n_allowed, _p(ids), _p(dists),
+                                         _p(layers), _p(ranks), _p(counts), _p(stats)))
         return BatchResult(ids, dists, layers, ranks, counts), stats
 
     def exact_screen_matrix(self, datas):
         """The screen's lower bound of every (row of datas, stored point) distance, (nq, n) f32 with the points in dump order: the
         diagnostic entry hnswxs_screen_matrix.  nq * n up to 2^24; DistL2, DistDot, DistCosine."""
+        return self._screen_matrix("hnswxs_screen_matrix", datas)
+
+    def exact_long_matrix(self, datas):
+        """exact_screen_matrix from the kernel for long rows, whatever d is (hnswxl_screen_matrix): d up to 4096."""
+        return self._screen_matrix("hnswxl_screen_matrix", datas)
+
+    def _screen_matrix(self, entry, datas):
         datas = np.ascontiguousarray(datas, dtype=np.float32)
         if datas.ndim != 2:
             raise HnswError(N.ERR_ARG, "datas must be a (nq, d) matrix")
         nq, d = datas.shape
         out = np.zeros((nq, self.get_nb_point()), np.float32)
         if self._h is not None:
-            _check(self._lib.hnswxs_screen_matrix(self._h, _p(datas), nq, d, _p(out)))
+            _check(getattr(self._lib, entry)(self._h, _p(datas), nq, d, _p(out)))
         return out
 
     def exact_search(self, datas, knbn, allowed_ids=None):

@@ -1876,7 +1876,8 @@ int hnswdbs_exact_device(const hnswgpu_index* idx, float eps, uint64_t min_sampl
 
 // ---- exact k-NN behind a matrix-core screen (hnsw_mi355x_exact_screen.h; exact_screen.hip holds the device side): the checks are
 // hnswgpu_exact_search_batch's own, in its order
-static int exact_screened_pair(const hnswgpu_index* cidx, const ExactScreenArgs& a, bool host, void* stream) {
+typedef int (*ScreenedFn)(const DeviceIndex&, const std::vector<uint64_t>&, const ExactScreenArgs&, bool, void*, std::string&);
+static int exact_screened_pair(const hnswgpu_index* cidx, const ExactScreenArgs& a, bool host, void* stream, ScreenedFn device_side = hnswgpu::exact_screened) {
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
     std::shared_lock<std::shared_mutex> sl(idx->mu);
@@ -1891,12 +1892,12 @@ static int exact_screened_pair(const hnswgpu_index* cidx, const ExactScreenArgs&
             return HNSWGPU_OK;
         }
     }
-    if (!hnswgpu::exact_screened) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    if (!device_side) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     DeviceIndex* dev = nullptr;
     rc = call_replica(idx, sl, host, true, true, &dev);
     if (rc != HNSWGPU_OK) return rc;
     std::string err;
-    return finish(hnswgpu::exact_screened(*dev, idx->flat->origin_id, a, host, stream, err), err);
+    return finish(device_side(*dev, idx->flat->origin_id, a, host, stream, err), err);
 }
 
 int hnswxs_exact_search_batch(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, uint64_t k, const uint64_t* allowed_ids,
@@ -1917,8 +1918,8 @@ int hnswxs_exact_search_batch_device(const hnswgpu_index* idx, const float* d_qu
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
-int hnswxs_screen_matrix(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, float* out_lb) {
-    CAPI_GUARD_BEGIN
+typedef int (*ScreenMatrixFn)(const DeviceIndex&, const std::vector<uint64_t>&, const ScreenMatrixArgs&, std::string&);
+static int screen_matrix_entry(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, float* out_lb, ScreenMatrixFn device_side) {
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
     std::shared_lock<std::shared_mutex> sl(idx->mu);
@@ -1930,12 +1931,43 @@ int hnswxs_screen_matrix(const hnswgpu_index* cidx, const float* queries, uint64
     int rc = capi_refuse_f16(idx, "the screen");
     if (rc != HNSWGPU_OK) return rc;
     if (index_empty(idx) || nq == 0) return HNSWGPU_OK;
-    if (!hnswgpu::exact_screen_matrix) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    if (!device_side) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     DeviceIndex* dev = nullptr;
     rc = primary_f32_replica(idx, sl, &dev);
     if (rc != HNSWGPU_OK) return rc;
     std::string err;
-    return finish(hnswgpu::exact_screen_matrix(*dev, idx->flat->origin_id, ScreenMatrixArgs{queries, nq, d, out_lb}, err), err);
+    return finish(device_side(*dev, idx->flat->origin_id, ScreenMatrixArgs{queries, nq, d, out_lb}, err), err);
+}
+
+int hnswxs_screen_matrix(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, float* out_lb) {
+    CAPI_GUARD_BEGIN
+    return screen_matrix_entry(idx, queries, nq, d, out_lb, hnswgpu::exact_screen_matrix);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+// ---- the same three behind the streamed screen for long rows (hnsw_mi355x_exact_long.h; exact_screen_long.hip holds the device side):
+// the same checks through the same functions
+int hnswxl_exact_search_batch(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, uint64_t k, const uint64_t* allowed_ids,
+                                        uint64_t n_allowed, uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank,
+                                        uint32_t* out_counts, uint64_t* out_stats) {
+    CAPI_GUARD_BEGIN
+    return exact_screened_pair(idx, ExactScreenArgs{queries, nq, d, k, allowed_ids, n_allowed, out_ids, out_dists, out_layer, out_rank, out_counts, out_stats},
+                               true, nullptr, hnswgpu::exact_screened_long);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswxl_exact_search_batch_device(const hnswgpu_index* idx, const float* d_queries, uint64_t nq, uint64_t d, uint64_t k,
+                                               const uint64_t* d_allowed_ids, uint64_t n_allowed, uint64_t* d_out_ids, float* d_out_dists,
+                                               uint8_t* d_out_layer, int32_t* d_out_rank, uint32_t* d_out_counts, uint64_t* out_stats, void* stream) {
+    CAPI_GUARD_BEGIN
+    return exact_screened_pair(idx, ExactScreenArgs{d_queries, nq, d, k, d_allowed_ids, n_allowed, d_out_ids, d_out_dists, d_out_layer, d_out_rank,
+                                                    d_out_counts, out_stats}, false, stream, hnswgpu::exact_screened_long);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+int hnswxl_screen_matrix(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, float* out_lb) {
+    CAPI_GUARD_BEGIN
+    return screen_matrix_entry(idx, queries, nq, d, out_lb, hnswgpu::exact_screen_long_matrix);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 

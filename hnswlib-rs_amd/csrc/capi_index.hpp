@@ -25,6 +25,7 @@
 #include "../../include/hnsw_mi355x_dbscan.h"
 #include "../../include/hnsw_mi355x_exact_screen.h"
 #include "../../include/hnsw_mi355x_exact_range_screen.h"
+#include "../../include/hnsw_mi355x_exact_long.h"
 #include "builder.hpp"
 #include "flat_index.hpp"
 #include "search_device.hpp"
@@ -412,6 +413,11 @@ struct ScreenMatrixArgs {     // host memory
     float* out_lb;            // nq x n
 };
 HNSWGPU_DEVICE_SIDE int exact_screen_matrix(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ScreenMatrixArgs& a, std::string& err);
+// the device side of hnswxl_exact_search_batch(_device) and hnswxl_screen_matrix, defined in exact_screen_long.hip: the arguments and
+// the checks of the two above
+HNSWGPU_DEVICE_SIDE int exact_screened_long(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ExactScreenArgs& a, bool host, void* stream,
+                                            std::string& err);
+HNSWGPU_DEVICE_SIDE int exact_screen_long_matrix(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ScreenMatrixArgs& a, std::string& err);
 // the device side of hnswxr_exact_range_search_batch(_device), defined in exact_range_screen.hip: exact_range's arguments, checked as
 // hnswgpu_exact_range_search_batch checks its own, and out_stats ([3], host memory either way, may be nullptr)
 HNSWGPU_DEVICE_SIDE int exact_range_screened(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ExactRangeCallArgs& a, uint64_t* out_stats,

@@ -167,7 +167,8 @@ int row_norms(ExactState& st, const DeviceIndexView& v, hipStream_t stream, cons
 }
 
 // wavefronts of a screen workgroup for rows of d elements on this device: as many (4 at most) as its LDS holds queries for; 0: none
-uint32_t screen_waves(int device, uint64_t dpad) {
+// (exact_screen_long.hip keeps no queries resident and does not ask)
+[[maybe_unused]] uint32_t screen_waves(int device, uint64_t dpad) {
     int limit = 0;
     if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) return 0;
     for (uint32_t w = MAX_WAVES; w > 0u; w >>= 1)

@@ -9,6 +9,8 @@ One JSON line per shape on stdout, progress on stderr.  Warm-up calls first, the
 
 --screened: the screened call (hnswxs_exact_search_batch_device) is timed beside the existing one on the same inputs, its
 answers compared with the existing call's, with the certified share from out_stats and the share of the f32 matrix rate.
+--long: the same for the screen for long rows (hnswxl_exact_search_batch_device), beside the other two: the three calls' ids,
+distance bits and counts are compared.  A package that lacks an entry (the parent commit's) leaves it out of the line.
 
 Filter-set mode (--filter-set): hnswgpu_exact_search_batch_filter_set through Hnsw.exact_search_filters_flat on the first shape,
 with --filters F filters of --selectivity LO[,HI] (fractions of the points, spread evenly from LO to HI) named by the queries
@@ -35,6 +37,9 @@ SHAPES = {  # BASELINE configs 2, 3, 5
     "sift1m": dict(n=1_000_000, d=128, dist="DistL2"),
     "glove25": dict(n=1_200_000, d=25, dist="DistCosine"),
     "mnist784": dict(n=60_000, d=784, dist="DistL2"),
+    # synthetic rows of the lengths embedding models give (0.6 GB of rows each): for --long
+    "l2_1536": dict(n=100_000, d=1536, dist="DistL2"),
+    "cos_3072": dict(n=50_000, d=3072, dist="DistCosine"),
 }
 # A NOMINAL model of the inner loop of exact_knn_slab_kernel: three vector-ALU operations per (query, element) -- DistL2: subtract,
 # multiply, add; DistCosine: multiply, widen, add in f64.  The loop as compiled for DistL2 packs the multiplies and adds of two
@@ -136,6 +141,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--no-torch-comparator", action="store_true")
     ap.add_argument("--screened", action="store_true", help="also time hnswxs_exact_search_batch_device on the same inputs")
+    ap.add_argument("--long", action="store_true", help="also time hnswxl_exact_search_batch_device (the screen for long rows) on the same inputs")
     ap.add_argument("--no-comparator-a", action="store_true", help="skip comparator (a)")
     ap.add_argument("--filter-set", action="store_true")
     ap.add_argument("--filters", type=int, default=64)
@@ -176,36 +182,38 @@ def main():
                                                      C.c_void_p(dd.data_ptr()), None, None, C.c_void_p(cnt.data_ptr()), None)
             assert rc == 0, N.last_error()
         med, lo, hi = timed(call, a.warmup, a.repeats)
-        screened = None
-        if a.screened and hasattr(L, "hnswxs_exact_search_batch_device"):
-            # the screened call beside the existing one: same queries, same out arrays' shapes, and its answers compared with the
-            # existing call's (equal work); the certified share from out_stats
+        # the screened calls beside the existing one: same queries, same out arrays' shapes, and their answers compared with the
+        # existing call's (equal work); the certified share from out_stats
+        behind_screen = {}
+        for key, entry, asked in (("screened", "hnswxs_exact_search_batch_device", a.screened), ("long", "hnswxl_exact_search_batch_device", a.long)):
+            if not asked or not hasattr(L, entry):
+                continue
             ids2, dd2, cnt2 = torch.zeros_like(ids), torch.zeros_like(dd), torch.zeros_like(cnt)
             stats = np.zeros(3, np.uint64)
 
             def call_screened():
-                rc = L.hnswxs_exact_search_batch_device(h.handle, C.c_void_p(dq.data_ptr()), nq, d, k, None, 0, C.c_void_p(ids2.data_ptr()),
-                                                                  C.c_void_p(dd2.data_ptr()), None, None, C.c_void_p(cnt2.data_ptr()),
-                                                                  stats.ctypes.data_as(C.c_void_p), None)
+                rc = getattr(L, entry)(h.handle, C.c_void_p(dq.data_ptr()), nq, d, k, None, 0, C.c_void_p(ids2.data_ptr()),
+                                       C.c_void_p(dd2.data_ptr()), None, None, C.c_void_p(cnt2.data_ptr()),
+                                       stats.ctypes.data_as(C.c_void_p), None)
                 assert rc == 0, N.last_error()
             smed, slo, shi = timed(call_screened, a.warmup, a.repeats)
             same = bool(torch.equal(ids, ids2) and torch.equal(dd.view(torch.int32), dd2.view(torch.int32)) and torch.equal(cnt, cnt2))
             dpad = (d + 31) // 32 * 32
-            screened = dict(seconds_median=smed, seconds_min=slo, seconds_max=shi, pair_evaluations_per_s=n * nq / smed,
-                            ms_per_10000_queries=smed * 1e3 * 10_000 / nq, stats=[int(x) for x in stats], certified_share=float(stats[0]) / nq,
-                            same_answers_as_existing_call=same, existing_over_screened=med / smed,
-                            # the multiply-adds the screen issues (rows padded to 32 elements) against the data sheet's f32 matrix rate
-                            fraction_of_f32_matrix_peak=2.0 * n * nq * dpad / smed / F32_MATRIX_PEAK)
+            behind_screen[key] = dict(seconds_median=smed, seconds_min=slo, seconds_max=shi, pair_evaluations_per_s=n * nq / smed,
+                                      ms_per_10000_queries=smed * 1e3 * 10_000 / nq, stats=[int(x) for x in stats], certified_share=float(stats[0]) / nq,
+                                      same_answers_as_existing_call=same, existing_over_screened=med / smed,
+                                      # the multiply-adds the screen issues (rows padded to 32 elements) against the data sheet's f32 matrix rate
+                                      fraction_of_f32_matrix_peak=2.0 * n * nq * dpad / smed / F32_MATRIX_PEAK)
         stride = (d + 31) // 32 * 32
         tiles = (nq + 15) // 16
         out = dict(shape=name, n=n, d=d, dist=dist, nq=nq, k=k, seconds_median=med, seconds_min=lo, seconds_max=hi, repeats=a.repeats,
                    pair_evaluations_per_s=n * nq / med, ms_per_10000_queries=med * 1e3 * 10_000 / nq,
                    valu_bound_pairs_per_s=cus * 64 * clock_hz / (VALU_PER_ELEMENT[dist] * 4 * ((d + 3) // 4)), clock_hz=clock_hz, cus=cus,
                    bytes_read_per_query=n * stride * 4 * tiles / nq, )
-        if screened is not None:
-            out["screened"] = screened
-            if not screened["same_answers_as_existing_call"]:
-                failed.append(name + " (screened answers differ)")
+        for key, line in behind_screen.items():
+            out[key] = line
+            if not line["same_answers_as_existing_call"]:
+                failed.append(f"{name} ({key} answers differ)")
         out["fraction_of_valu_bound"] = out["pair_evaluations_per_s"] / out["valu_bound_pairs_per_s"]
         out["fraction_of_hbm_peak"] = out["bytes_read_per_query"] * nq / med / HBM_PEAK
         # (a) eval_distance_matrix in slices of rows + host selection, and the new entry (host buffers) on the same few queries

@@ -9,7 +9,10 @@
     tools/kres.py range_screen [extra -D flags ...]     the kernels of exact_range_screen.hip (screen per metric and register tile,
                                                         rerank per metric; the same flags as screen)
     tools/kres.py dbscan_screen [extra -D flags ...]    the kernels of dbscan_screen.hip (screen per metric, pass and register tile,
-                                                        rerank per metric and pass; the same flags as screen)"""
+                                                        rerank per metric and pass; the same flags as screen)
+    tools/kres.py screen_long [extra -D flags ...]      the kernels of exact_screen_long.hip (the streamed screen per metric, the rerank
+                                                        it shares with screen; the same flags as screen; -DHNSW_LONG_NT=2,
+                                                        -DHNSW_LONG_WAVES_PER_SIMD=1 for the variants)"""
 import os
 import re
 import subprocess
@@ -18,9 +21,9 @@ import sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 flags = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-pthread", "--offload-arch=gfx950",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-Rpass-analysis=kernel-resource-usage"]
-if sys.argv[1] in ("exact", "dbscan", "screen", "range_screen", "dbscan_screen"):
-    units = {"exact": ("exact_knn", "exact_range", "knn_graph"), "dbscan": ("dbscan",), "screen": ("exact_screen",), "range_screen": ("exact_range_screen",), "dbscan_screen": ("dbscan_screen",)}[sys.argv[1]]
-    if sys.argv[1] in ("screen", "range_screen", "dbscan_screen"):
+if sys.argv[1] in ("exact", "dbscan", "screen", "range_screen", "dbscan_screen", "screen_long"):
+    units = {"exact": ("exact_knn", "exact_range", "knn_graph"), "dbscan": ("dbscan",), "screen": ("exact_screen",), "range_screen": ("exact_range_screen",), "dbscan_screen": ("dbscan_screen",), "screen_long": ("exact_screen_long",)}[sys.argv[1]]
+    if sys.argv[1] in ("screen", "range_screen", "dbscan_screen", "screen_long"):
         flags += ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
     cmds = [[*flags, *sys.argv[2:], "-c", unit + ".hip", "-o", f"/tmp/kres_{unit}.o"] for unit in units]
 else:
