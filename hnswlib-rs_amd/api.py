@@ -1015,9 +1015,9 @@ class Hnsw:
         return (found / total if total else 1.0), saturated
 
     # ---- queries by stored point: the k-NN graph of the indexed points (an extension) --------------------------------
-    def _graph_call(self, entry, knbn, point_ids, *middle):
-        """one of the two graph entries: point_ids (DataIds; None = every point, row i being the point at position i of the
-        ascending (DataId, dump order) order), the entry's own arguments, the five output arrays"""
+    def _graph_call(self, entry, knbn, point_ids, *middle, tail=()):
+        """one of the graph entries: point_ids (DataIds; None = every point, row i being the point at position i of the
+        ascending (DataId, dump order) order), the entry's own arguments, the five output arrays, what the entry takes behind them"""
         pts = None
         if point_ids is not None:
             pts = np.ascontiguousarray(point_ids, dtype=np.uint64).reshape(-1)
@@ -1033,7 +1033,7 @@ class Hnsw:
             return BatchResult(ids, dists, layers, ranks, counts)
         if pts is not None and np_ == 0:
             pts = np.zeros(1, np.uint64)  # (no point named still is a list of points: a non-null pointer, zero ids)
-        _check(entry(self._h, _p(pts), np_, knbn, *middle, _p(ids), _p(dists), _p(layers), _p(ranks), _p(counts)))
+        _check(entry(self._h, _p(pts), np_, knbn, *middle, _p(ids), _p(dists), _p(layers), _p(ranks), _p(counts), *tail))
         return BatchResult(ids, dists, layers, ranks, counts)
 
     def knn_graph_flat(self, knbn, ef, point_ids=None):
@@ -1054,6 +1054,37 @@ class Hnsw:
             n_allowed = len(allowed_ids)
             allowed = np.ascontiguousarray(allowed_ids, dtype=np.uint64) if n_allowed else np.zeros(1, np.uint64)
         return self._graph_call(self._lib.hnswgpu_exact_graph_batch, knbn, point_ids, _p(allowed), n_allowed)
+
+    def exact_knn_graph_screened_flat(self, knbn, point_ids=None, allowed_ids=None):
+        """exact_knn_graph_flat through the matrix-core screen (include/hnsw_mi355x_exact_graph_screen.h): the same BatchResult byte
+        for byte, the named points read from the replica's own rows and left out of their own answers by identity inside the
+        screen, and stats, three u64: points certified by the screen, points the certificate handed to the existing path, points
+        not screened at all (a distance without a screen, knbn + 54 above 4096, fewer than 256 points, rows above 4096 elements).
+        Returns (BatchResult, stats)."""
+        allowed, n_allowed = None, 0
+        if allowed_ids is not None:
+            n_allowed = len(allowed_ids)
+            allowed = np.ascontiguousarray(allowed_ids, dtype=np.uint64) if n_allowed else np.zeros(1, np.uint64)
+        stats = np.zeros(3, np.uint64)
+        res = self._graph_call(self._lib.hnswxg_exact_graph_batch, knbn, point_ids, _p(allowed), n_allowed, tail=(_p(stats),))
+        return res, stats
+
+    def exact_graph_screen_matrix(self, point_ids=None):
+        """The screen's lower bound of every (named point, stored point) distance, (np, n) f32 with the columns in dump order and the
+        point's own pair like any other: the diagnostic entry hnswxg_screen_matrix.  point_ids as in exact_knn_graph_flat; np * n
+        up to 2^24; DistL2, DistDot, DistCosine; rows of up to 4096 elements."""
+        pts = None if point_ids is None else np.ascontiguousarray(point_ids, dtype=np.uint64).reshape(-1)
+        n = self.get_nb_point()
+        np_ = n if pts is None else len(pts)
+        out = np.zeros((np_, n), np.float32)
+        if self._h is None:
+            if np_ != 0:
+                raise HnswError(N.ERR_ARG, f"{np_} of the {np_} point_ids name no point of the index")
+            return out
+        if pts is not None and np_ == 0:
+            pts = np.zeros(1, np.uint64)
+        _check(self._lib.hnswxg_screen_matrix(self._h, _p(pts), np_, _p(out)))
+        return out
 
     # ---- the k-NN graph of the indexed points made undirected, in CSR (an extension) ----------------------------------
     def symmetric_knn_graph_flat(self, knbn, ef=None, mode="union"):

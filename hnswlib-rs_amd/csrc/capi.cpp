@@ -997,8 +997,11 @@ static int graph_call(const hnswgpu_index* idx, const GraphCallArgs& a, bool exa
     return capi_refuse_f16(idx, "exact graph");
 }
 
-// both pairs: exact picks hnswgpu_exact_graph_batch(_device), else hnswgpu_graph_search_batch(_device), which hands in no filter
-static int graph_pair(const hnswgpu_index* cidx, const GraphCallArgs& a, bool exact, bool host, void* stream) {
+// both pairs: exact picks hnswgpu_exact_graph_batch(_device), else hnswgpu_graph_search_batch(_device), which hands in no filter.
+// screened (exact only): hnswxg_exact_graph_batch(_device) of hnsw_mi355x_exact_graph_screen.h -- the same checks in the same order,
+// the device side of exact_screen_long.hip, and out_stats (host memory, may be nullptr), written when the call succeeds
+static int graph_pair(const hnswgpu_index* cidx, const GraphCallArgs& a, bool exact, bool host, void* stream, bool screened = false,
+                      uint64_t* out_stats = nullptr) {
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
     std::shared_lock<std::shared_mutex> sl(idx->mu);
@@ -1008,14 +1011,18 @@ static int graph_pair(const hnswgpu_index* cidx, const GraphCallArgs& a, bool ex
         rc = check_sorted_filter(a.allowed, a.n_allowed);
         if (rc != HNSWGPU_OK) return rc;
     }
-    if (a.np == 0) return HNSWGPU_OK;  // no point asks nothing of a device
+    if (a.np == 0) {  // no point asks nothing of a device
+        if (screened && out_stats) out_stats[0] = out_stats[1] = out_stats[2] = 0;
+        return HNSWGPU_OK;
+    }
     if (host && index_empty(idx))  // an empty index names no point (the device form: it cannot be resident)
         return fail(HNSWGPU_ERR_ARG, std::to_string(a.np) + " of the " + std::to_string(a.np) + " point_ids name no point of the index");
-    if (exact ? !hnswgpu::exact_graph : !hnswgpu::graph_search) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    if (screened ? !hnswgpu::exact_graph_screened : exact ? !hnswgpu::exact_graph : !hnswgpu::graph_search) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     DeviceIndex* dev = nullptr;
     rc = call_replica(idx, sl, host, true, true, &dev);
     if (rc != HNSWGPU_OK) return rc;
     std::string err;
+    if (screened) return finish(hnswgpu::exact_graph_screened(*dev, idx->flat->origin_id, a, out_stats, host, stream, err), err);
     return finish(exact ? hnswgpu::exact_graph(*dev, idx->flat->origin_id, a, host, stream, err)
                         : hnswgpu::graph_search(*dev, idx->flat->origin_id, a, host, stream, err),
                   err);
@@ -1968,6 +1975,51 @@ int hnswxl_exact_search_batch_device(const hnswgpu_index* idx, const float* d_qu
 int hnswxl_screen_matrix(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, float* out_lb) {
     CAPI_GUARD_BEGIN
     return screen_matrix_entry(idx, queries, nq, d, out_lb, hnswgpu::exact_screen_long_matrix);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+// ---- the exact k-NN graph of the stored points behind the screen (hnsw_mi355x_exact_graph_screen.h; exact_screen.hip and
+// exact_screen_long.hip hold the device side): hnswgpu_exact_graph_batch(_device)'s own checks through graph_pair
+int hnswxg_exact_graph_batch(const hnswgpu_index* idx, const uint64_t* point_ids, uint64_t np, uint64_t k, const uint64_t* allowed_ids, uint64_t n_allowed,
+                             uint64_t* out_ids, float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint32_t* out_counts, uint64_t* out_stats) {
+    CAPI_GUARD_BEGIN
+    return graph_pair(idx, GraphCallArgs{point_ids, np, k, 0, allowed_ids, n_allowed, out_ids, out_dists, out_layer, out_rank, out_counts}, true, true,
+                      nullptr, true, out_stats);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswxg_exact_graph_batch_device(const hnswgpu_index* idx, const uint64_t* d_point_ids, uint64_t np, uint64_t k, const uint64_t* d_allowed_ids,
+                                    uint64_t n_allowed, uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank,
+                                    uint32_t* d_out_counts, uint64_t* out_stats, void* stream) {
+    CAPI_GUARD_BEGIN
+    return graph_pair(idx, GraphCallArgs{d_point_ids, np, k, 0, d_allowed_ids, n_allowed, d_out_ids, d_out_dists, d_out_layer, d_out_rank, d_out_counts},
+                      true, false, stream, true, out_stats);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+// the named points' own rows as the queries of the screen's matrix: hnswxs_screen_matrix's refusals, the graph calls' word for a
+// NULL point_ids, and (on the device) their word for an id that names no point
+int hnswxg_screen_matrix(const hnswgpu_index* cidx, const uint64_t* point_ids, uint64_t np, float* out_lb) {
+    CAPI_GUARD_BEGIN
+    hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
+    if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
+    std::shared_lock<std::shared_mutex> sl(idx->mu);
+    const uint64_t n = index_nb_point(idx);
+    if (np != 0 && !out_lb) return fail(HNSWGPU_ERR_ARG, "null buffer");
+    if (!point_ids && np != n)
+        return fail(HNSWGPU_ERR_ARG, "point_ids is NULL (every point): np must be nb_point = " + std::to_string(n) + ", not " + std::to_string(np));
+    if (idx->arithmetic != HNSWGPU_ARITH_SCALAR)
+        return fail(HNSWGPU_ERR_ARG, "the screen bounds the scalar arithmetic only: the index is set to HNSWGPU_ARITH_SIMD8");
+    int rc = capi_refuse_f16(idx, "the screen");
+    if (rc != HNSWGPU_OK) return rc;
+    if (np == 0) return HNSWGPU_OK;
+    if (index_empty(idx)) return fail(HNSWGPU_ERR_ARG, std::to_string(np) + " of the " + std::to_string(np) + " point_ids name no point of the index");
+    if (!hnswgpu::exact_graph_screen_matrix) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    DeviceIndex* dev = nullptr;
+    rc = primary_f32_replica(idx, sl, &dev);
+    if (rc != HNSWGPU_OK) return rc;
+    std::string err;
+    return finish(hnswgpu::exact_graph_screen_matrix(*dev, idx->flat->origin_id, ScreenMatrixArgs{nullptr, np, index_dimension(idx), out_lb, point_ids, true}, err), err);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 

@@ -26,6 +26,7 @@
 #include "../../include/hnsw_mi355x_exact_screen.h"
 #include "../../include/hnsw_mi355x_exact_range_screen.h"
 #include "../../include/hnsw_mi355x_exact_long.h"
+#include "../../include/hnsw_mi355x_exact_graph_screen.h"
 #include "builder.hpp"
 #include "flat_index.hpp"
 #include "search_device.hpp"
@@ -411,6 +412,9 @@ struct ScreenMatrixArgs {     // host memory
     const float* queries;     // nq x d
     uint64_t nq, d;
     float* out_lb;            // nq x n
+    // hnswxg_screen_matrix: the nq queries are the stored points that point_ids names (nullptr: every point), `queries` is not read
+    const uint64_t* point_ids = nullptr;
+    bool self = false;
 };
 HNSWGPU_DEVICE_SIDE int exact_screen_matrix(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ScreenMatrixArgs& a, std::string& err);
 // the device side of hnswxl_exact_search_batch(_device) and hnswxl_screen_matrix, defined in exact_screen_long.hip: the arguments and
@@ -418,6 +422,15 @@ HNSWGPU_DEVICE_SIDE int exact_screen_matrix(const DeviceIndex& dev, const std::v
 HNSWGPU_DEVICE_SIDE int exact_screened_long(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ExactScreenArgs& a, bool host, void* stream,
                                             std::string& err);
 HNSWGPU_DEVICE_SIDE int exact_screen_long_matrix(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ScreenMatrixArgs& a, std::string& err);
+// the device side of hnswxg_exact_graph_batch(_device) and hnswxg_screen_matrix (hnsw_mi355x_exact_graph_screen.h), defined in
+// exact_screen_long.hip, which routes by the rows' length: exact_graph's arguments, checked as hnswgpu_exact_graph_batch checks its
+// own, and out_stats ([3], host memory either way, may be nullptr; written on success only); the matrix with ScreenMatrixArgs::self.
+// exact_graph_screened_resident (exact_screen.hip) is the first of them for rows of up to 256 elements.
+HNSWGPU_DEVICE_SIDE int exact_graph_screened(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphCallArgs& a, uint64_t* out_stats, bool host,
+                                             void* stream, std::string& err);
+HNSWGPU_DEVICE_SIDE int exact_graph_screen_matrix(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ScreenMatrixArgs& a, std::string& err);
+int exact_graph_screened_resident(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphCallArgs& a, uint64_t* out_stats, bool host, void* stream,
+                                  std::string& err);
 // the device side of hnswxr_exact_range_search_batch(_device), defined in exact_range_screen.hip: exact_range's arguments, checked as
 // hnswgpu_exact_range_search_batch checks its own, and out_stats ([3], host memory either way, may be nullptr)
 HNSWGPU_DEVICE_SIDE int exact_range_screened(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ExactRangeCallArgs& a, uint64_t* out_stats,

@@ -99,9 +99,10 @@ hipError_t exact_prep_queries(hipStream_t stream, const float* d_src, uint64_t c
                               double* d_qnorm, const uint32_t* qlist = nullptr, const uint32_t* slot_of = nullptr, uint32_t* tword = nullptr);
 // defined in exact_knn.hip too: the same tiles from the index's own rows -- slot i holds the stored point of flat id d_flat[i], its
 // bits those of the point's vector brought as a query, and self_rank[i] that point's DataId rank (its POSITION; the slots behind
-// the last: 0xFFFFFFFF).  For the exact graph and for dbscan.hip.  On `stream`, nobody waits.
+// the last: 0xFFFFFFFF).  qlist != nullptr: slot i holds the point d_flat[qlist[i]].  For the exact graph and for dbscan.hip.  On
+// `stream`, nobody waits.
 hipError_t exact_prep_rows(hipStream_t stream, const DeviceIndexView& ix, const uint32_t* d_flat, const uint32_t* d_rank, uint64_t cq, const SlabPlan& plan,
-                           uint32_t n_slots, float* d_qt, double* d_qnorm, uint32_t* d_self_rank);
+                           uint32_t n_slots, float* d_qt, double* d_qnorm, uint32_t* d_self_rank, const uint32_t* qlist = nullptr);
 
 // The optional filter of a call with host buffers goes to the device once.  A filter that is empty still is a filter: a non-null
 // pointer that is never dereferenced.
@@ -160,7 +161,7 @@ struct ExactCall {
     uint64_t n_allowed = 0;
     const FilterSet* set = nullptr;
     GraphRows out{};  // layer and rank may be nullptr
-    const uint32_t* d_qlist = nullptr;  // no set, no d_self: the nq queries are rows d_qlist[0 .. nq) of d_queries and of out (exact_screen.hip's fallback)
+    const uint32_t* d_qlist = nullptr;  // no set: the nq queries are rows d_qlist[0 .. nq) of d_queries (or of d_self) and of out (the screens' fallback)
 };
 // defined in exact_knn.hip; waits for `stream` before it returns
 int exact_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ExactCall& c, hipStream_t stream, std::string& err);

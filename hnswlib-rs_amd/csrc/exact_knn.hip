@@ -205,13 +205,14 @@ __global__ void exact_knn_prep_kernel(const float* __restrict__ src, uint32_t nq
 
 // k-NN graph: the same tiles from the index's own rows -- slot qs holds the stored point flat[qs], its first d elements (what lies
 // behind them in the padded row, a DistCosine norm included, never reaches the tile), the squared norm summed as above, so the
-// bits are those of the point's vector brought as a query -- and the slot's own DataId rank (slots behind the last: no rank)
+// bits are those of the point's vector brought as a query -- and the slot's own DataId rank (slots behind the last: no rank).
+// Slot qs holds the point flat[qlist[qs]] (qlist == nullptr: flat[qs]), as exact_knn_prep_kernel's slots do.
 __global__ void exact_knn_prep_rows_kernel(DeviceIndexView ix, const uint32_t* __restrict__ flat, const uint32_t* __restrict__ rank, uint32_t nq,
                                            uint32_t nchunk, uint32_t n_slots, float* __restrict__ qt, double* __restrict__ qnorm,
-                                           uint32_t* __restrict__ self_rank) {
+                                           uint32_t* __restrict__ self_rank, const uint32_t* __restrict__ qlist) {
     const uint32_t qs = blockIdx.x * blockDim.x + threadIdx.x;
     if (qs >= n_slots) return;
-    const uint32_t f = qs < nq ? flat[qs] : 0u;
+    const uint32_t f = qs < nq ? flat[qlist != nullptr ? qlist[qs] : qs] : 0u;
     qnorm[qs] = prep_slot(ix.vec + (size_t)f * ix.row_stride, qs < nq ? ix.d : 0u, nchunk, qs, qt);
     self_rank[qs] = qs < nq ? rank[f] : 0xFFFFFFFFu;
 }
@@ -269,9 +270,9 @@ hipError_t exact_prep_queries(hipStream_t stream, const float* d_src, uint64_t c
 }
 
 hipError_t exact_prep_rows(hipStream_t stream, const DeviceIndexView& ix, const uint32_t* d_flat, const uint32_t* d_rank, uint64_t cq, const SlabPlan& plan,
-                           uint32_t n_slots, float* d_qt, double* d_qnorm, uint32_t* d_self_rank) {
+                           uint32_t n_slots, float* d_qt, double* d_qnorm, uint32_t* d_self_rank, const uint32_t* qlist) {
     hipLaunchKernelGGL(exact_knn_prep_rows_kernel, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, ix, d_flat, d_rank, (uint32_t)cq, (uint32_t)plan.nchunk,
-                       n_slots, d_qt, d_qnorm, d_self_rank);
+                       n_slots, d_qt, d_qnorm, d_self_rank, qlist);
     return hipGetLastError();
 }
 
@@ -280,7 +281,8 @@ hipError_t exact_prep_rows(hipStream_t stream, const DeviceIndexView& ix, const 
 // bitmaps are built group by group -- as many consecutive filters as the bound and this unit's scratch budget hold -- and per group
 // its queries are listed (launch_filter_group), tiled densely and searched; one group (the usual case): all queries in batch order.
 // c.d_self != nullptr (k-NN graph; no set): query q is the stored point of flat id d_self[q], d_queries is not read, and the point
-// itself is no candidate of its own row.
+// itself is no candidate of its own row.  c.d_qlist != nullptr (no set): the nq queries are rows d_qlist[0 .. nq) of d_queries -- or
+// of d_self -- and of the outputs.
 int exact_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ExactCall& c, hipStream_t stream, std::string& err) {
     const DeviceIndexView& v = dev.view();
     const uint64_t nq = c.nq, d = c.d, k = c.k;
@@ -362,7 +364,7 @@ int exact_device(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id,
             a.nq = (uint32_t)cq;
             const uint32_t n_slots = (uint32_t)(tiles * TQ);
             if (d_self) {
-                HIP_TRY(exact_prep_rows(stream, v, d_self + row0, a.rank, cq, plan, n_slots, d_qt, d_qnorm, d_self_rank));
+                HIP_TRY(exact_prep_rows(stream, v, d_self + row0, a.rank, cq, plan, n_slots, d_qt, d_qnorm, d_self_rank, a.qlist));
             } else {
                 HIP_TRY(exact_prep_queries(stream, c.d_queries + row0 * d, cq, d, plan, n_slots, d_qt, d_qnorm, a.qlist, slot_of ? slot_of + row0 : nullptr, d_tword));
             }

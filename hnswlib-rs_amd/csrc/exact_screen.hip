@@ -20,6 +20,9 @@
 //                              the exact chain (chain4, tile_dist: the bits of exact_knn.hip), one candidate per lane; the exact keys
 //                              sorted in LDS; the certificate; the answer written, or the query appended to the fallback list.
 //
+// The screen and the rerank have a SELF variant each, for hnswxg_exact_graph_batch(_device) and hnswxg_screen_matrix of
+// include/hnsw_mi355x_exact_graph_screen.h: the queries are stored points, gathered from the replica's own rows (no prep kernel, no
+// padded copy), and never their own candidates.
 // The queries on the fallback list are answered by exact_device (exact_knn.hip) into their own rows; the host reads back one count.
 // The rerank kernel and the driver are in exact_screen_knn.hpp, shared with exact_screen_long.hip; this unit holds the screen kernel.
 #include <hip/hip_runtime.h>
@@ -29,7 +32,11 @@
 namespace hnswgpu {
 namespace {
 
-template <int METRIC, bool MATRIX>
+// SELF (the k-NN graph of the stored points): the tile's queries are stored points.  The prologue gathers each from its own index row
+// into its LDS slot -- there is no padded copy in scratch --, its plain f32 norm is the replica's xn, and its DataId rank lies in LDS
+// beside its threshold: the one row that is the point itself is never inserted (by identity: its copies and the other points of its
+// DataId are candidates like any row).
+template <int METRIC, bool MATRIX, bool SELF>
 __global__ __launch_bounds__(64 * MAX_WAVES) void exact_screen_kernel(DeviceIndexView ix, ScreenArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, nthr = blockDim.x;
@@ -41,6 +48,7 @@ __global__ __launch_bounds__(64 * MAX_WAVES) void exact_screen_kernel(DeviceInde
     uint64_t* const thr = reinterpret_cast<uint64_t*>(rbuf + 2u * RB * RPITCH);  // [qt]
     uint32_t* const len = reinterpret_cast<uint32_t*>(thr + qt);      // [qt]
     float* const qnl = reinterpret_cast<float*>(len + qt);            // [qt]
+    [[maybe_unused]] uint32_t* const own = reinterpret_cast<uint32_t*>(qnl + qt);  // SELF: [qt] the queries' own DataId ranks
 
     const uint32_t nvalid = a.nq - tile * qt < qt ? a.nq - tile * qt : qt;
     // the tile's queries: resident from here on
@@ -49,12 +57,19 @@ __global__ __launch_bounds__(64 * MAX_WAVES) void exact_screen_kernel(DeviceInde
         const uint32_t c4n = dpad >> 2;
         for (uint32_t i = tid; i < qt * c4n; i += nthr) {
             const uint32_t q = i / c4n, c = i - q * c4n;
-            *reinterpret_cast<float4*>(qs + (size_t)q * qpitch + 4u * c) = src[i];
+            if constexpr (SELF) *reinterpret_cast<v4f*>(qs + (size_t)q * qpitch + 4u * c) = self_query4(ix, self_slot(a.self, tile * qt + q, a.nq), 4u * c);
+            else *reinterpret_cast<float4*>(qs + (size_t)q * qpitch + 4u * c) = src[i];
         }
         for (uint32_t q = tid; q < qt; q += nthr) {
             thr[q] = KEY_NONE;
             len[q] = 0u;
-            qnl[q] = a.qn[tile * qt + q];
+            if constexpr (SELF) {
+                const uint32_t f = self_slot(a.self, tile * qt + q, a.nq);
+                qnl[q] = f != NO_SELF ? a.xn[f] : 0.f;
+                own[q] = f != NO_SELF ? a.rank[f] : NO_SELF;
+            } else {
+                qnl[q] = a.qn[tile * qt + q];
+            }
         }
     }
     const uint32_t lo = slab * a.slab_rows;
@@ -143,7 +158,9 @@ __global__ __launch_bounds__(64 * MAX_WAVES) void exact_screen_kernel(DeviceInde
                             if (in && ql < nvalid) a.out_lb[(size_t)(tile * qt + ql) * ix.n + r] = lb;
                         } else {
                             const uint64_t key = make_key(lb, rk);
-                            const unsigned long long m = __ballot(elig && ql < nvalid && key < thr[ql]);
+                            bool cand = elig && ql < nvalid;
+                            if constexpr (SELF) cand = cand && rk != own[ql];
+                            const unsigned long long m = __ballot(cand && key < thr[ql]);
                             if ((m & 0xFFFFFFFFull) != 0ull)
                                 screen_insert(a.lists + (slot + q_lo) * cap, thr, len, q_lo, cap, key, m & 0xFFFFFFFFull);
                             if ((m >> 32) != 0ull)
@@ -165,8 +182,8 @@ __global__ __launch_bounds__(64 * MAX_WAVES) void exact_screen_kernel(DeviceInde
 // This unit's screen for the driver of exact_screen_knn.hpp: the tile's queries resident in LDS
 struct ResidentScreen {
     static constexpr uint64_t ROWS = RB;
-    static uint64_t waves(int device, uint64_t dpad) { return screen_waves(device, dpad); }
-    static uint64_t lds_bytes(uint64_t waves, uint64_t dpad) { return screen_lds_bytes(waves, dpad); }
+    static uint64_t waves(int device, uint64_t dpad, bool self) { return screen_waves(device, dpad, self); }
+    static uint64_t lds_bytes(uint64_t waves, uint64_t dpad, bool self) { return screen_lds_bytes(waves, dpad, self); }
     static float coeff(int metric, uint64_t d) { return screen_coeff(metric, d); }
     static const char* too_long() { return "for a query tile in LDS"; }
     template <bool MATRIX>
@@ -174,13 +191,25 @@ struct ResidentScreen {
         return for_screened_metric(metric, [&](auto m) {
             constexpr int M = decltype(m)::value;
             // (more LDS than the default limit of a launch: said once per kernel; a refusal shows in the launch itself)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&exact_screen_kernel<M, MATRIX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL((exact_screen_kernel<M, MATRIX>), grid, dim3(64u * waves), lds, stream, ix, a);
+            if (a.self != nullptr) {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&exact_screen_kernel<M, MATRIX, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                hipLaunchKernelGGL((exact_screen_kernel<M, MATRIX, true>), grid, dim3(64u * waves), lds, stream, ix, a);
+            } else {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&exact_screen_kernel<M, MATRIX, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                hipLaunchKernelGGL((exact_screen_kernel<M, MATRIX, false>), grid, dim3(64u * waves), lds, stream, ix, a);
+            }
         });
     }
 };
 
 }  // namespace
+
+// The device side of hnswxg_exact_graph_batch(_device) for rows of up to 256 elements (exact_screen_long.hip routes): the resident
+// screen's SELF variant, four wavefronts
+int exact_graph_screened_resident(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphCallArgs& a, uint64_t* out_stats, bool host, void* stream,
+                                  std::string& err) {
+    return screened_graph_call<ResidentScreen>(dev, origin_id, a, out_stats, host, stream, err);
+}
 
 // The device side of hnswxs_exact_search_batch(_device); capi.cpp holds the entries and every argument check.
 int exact_screened(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ExactScreenArgs& a, bool host, void* stream, std::string& err) {

@@ -12,7 +12,8 @@
 //                              live across the dpad / 32 steps of a row block.  Epilogue once per row block: exact_screen_kernel's.
 //
 // Rows of up to 256 elements go to exact_screen.hip's driver as they are: four wavefronts with resident queries read a query once per
-// slab, not once per row block.
+// slab, not once per row block.  The same routing serves the screened exact graph (hnswxg_*, include/hnsw_mi355x_exact_graph_screen.h),
+// whose device side is here: both screens' SELF variants, DESIGN.md section 15.17.
 #include <hip/hip_runtime.h>
 
 #include "exact_screen_knn.hpp"
@@ -46,9 +47,11 @@ float screen_coeff_long(int metric, uint64_t d) {
     return (float)(2 * d + 96) * 0x1p-24f;
 }
 
-uint64_t long_lds_bytes() { return 2ull * LONG_STAGED * RPITCH * 4 + LONG_QT * 16; }
+uint64_t long_lds_bytes(bool self) { return 2ull * LONG_STAGED * RPITCH * 4 + LONG_QT * (self ? 20 : 16); }
 
-template <int METRIC, bool MATRIX>
+// SELF (the k-NN graph of the stored points): exact_screen_kernel's, with the query fetch of every step reading 32 elements of the
+// tile's points from their own index rows (a thread keeps the flat ids of its four query rows in registers)
+template <int METRIC, bool MATRIX, bool SELF>
 __global__ __launch_bounds__(LONG_THREADS, HNSW_LONG_WAVES_PER_SIMD) void exact_screen_long_kernel(DeviceIndexView ix, ScreenArgs a) {
     constexpr uint32_t BUF = LONG_STAGED * RPITCH;  // floats of one staged step
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -60,12 +63,19 @@ __global__ __launch_bounds__(LONG_THREADS, HNSW_LONG_WAVES_PER_SIMD) void exact_
     uint64_t* const thr = reinterpret_cast<uint64_t*>(buf + 2u * BUF);       // [LONG_QT]
     uint32_t* const len = reinterpret_cast<uint32_t*>(thr + LONG_QT);        // [LONG_QT]
     float* const qnl = reinterpret_cast<float*>(len + LONG_QT);              // [LONG_QT]
+    [[maybe_unused]] uint32_t* const own = reinterpret_cast<uint32_t*>(qnl + LONG_QT);  // SELF: [LONG_QT] the queries' own DataId ranks
 
     const uint32_t nvalid = a.nq - tile * LONG_QT < LONG_QT ? a.nq - tile * LONG_QT : LONG_QT;
     if (tid < LONG_QT) {
         thr[tid] = KEY_NONE;
         len[tid] = 0u;
-        qnl[tid] = a.qn[tile * LONG_QT + tid];
+        if constexpr (SELF) {
+            const uint32_t f = self_slot(a.self, tile * LONG_QT + tid, a.nq);
+            qnl[tid] = f != NO_SELF ? a.xn[f] : 0.f;
+            own[tid] = f != NO_SELF ? a.rank[f] : NO_SELF;
+        } else {
+            qnl[tid] = a.qn[tile * LONG_QT + tid];
+        }
     }
     const uint32_t lo = slab * a.slab_rows;
     const uint32_t hi = ix.n - lo < a.slab_rows ? ix.n : lo + a.slab_rows;
@@ -79,9 +89,17 @@ __global__ __launch_bounds__(LONG_THREADS, HNSW_LONG_WAVES_PER_SIMD) void exact_
     const uint32_t srow = tid >> 3, e4 = 4u * (tid & 7u);
     const float* const qsrc = a.qpad + (size_t)(tile * LONG_QT + srow) * dpad + e4;
     v4f preq[LONG_PRE_Q], prex[LONG_NT];
+    [[maybe_unused]] uint32_t qf[LONG_PRE_Q];  // SELF: the flat ids of this thread's query rows (a slot behind the last query: none, zeros)
+    if constexpr (SELF) {
+#pragma unroll
+        for (int j = 0; j < (int)LONG_PRE_Q; ++j) qf[j] = self_slot(a.self, tile * LONG_QT + srow + 32u * (uint32_t)j, a.nq);
+    }
     auto fetch = [&](uint32_t blk, uint32_t c) {
 #pragma unroll
-        for (int j = 0; j < (int)LONG_PRE_Q; ++j) preq[j] = *reinterpret_cast<const v4f*>(qsrc + (size_t)(32u * (uint32_t)j) * dpad + c * KC);
+        for (int j = 0; j < (int)LONG_PRE_Q; ++j) {
+            if constexpr (SELF) preq[j] = self_query4(ix, qf[j], c * KC + e4);
+            else preq[j] = *reinterpret_cast<const v4f*>(qsrc + (size_t)(32u * (uint32_t)j) * dpad + c * KC);
+        }
 #pragma unroll
         for (int j = 0; j < (int)LONG_NT; ++j) {
             const uint32_t r = lo + blk * LONG_ROWS + srow + 32u * (uint32_t)j, e = c * KC + e4;
@@ -157,7 +175,9 @@ __global__ __launch_bounds__(LONG_THREADS, HNSW_LONG_WAVES_PER_SIMD) void exact_
                             if (in && ql < nvalid) a.out_lb[(size_t)(tile * LONG_QT + ql) * ix.n + r] = lb;
                         } else {
                             const uint64_t key = make_key(lb, rk);
-                            const unsigned long long m = __ballot(elig && ql < nvalid && key < thr[ql]);
+                            bool cand = elig && ql < nvalid;
+                            if constexpr (SELF) cand = cand && rk != own[ql];
+                            const unsigned long long m = __ballot(cand && key < thr[ql]);
                             if ((m & 0xFFFFFFFFull) != 0ull)
                                 screen_insert(a.lists + (slot + q_lo) * cap, thr, len, q_lo, cap, key, m & 0xFFFFFFFFull);
                             if ((m >> 32) != 0ull)
@@ -182,12 +202,12 @@ __global__ __launch_bounds__(LONG_THREADS, HNSW_LONG_WAVES_PER_SIMD) void exact_
 // This unit's screen for the driver of exact_screen_knn.hpp: queries and rows both streamed
 struct StreamedScreen {
     static constexpr uint64_t ROWS = LONG_ROWS;
-    static uint64_t waves(int device, uint64_t dpad) {
+    static uint64_t waves(int device, uint64_t dpad, bool self) {
         int limit = 0;
         if (dpad > LONG_MAX_DPAD || hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) return 0;
-        return long_lds_bytes() <= (uint64_t)limit ? MAX_WAVES : 0;
+        return long_lds_bytes(self) <= (uint64_t)limit ? MAX_WAVES : 0;
     }
-    static uint64_t lds_bytes(uint64_t, uint64_t) { return long_lds_bytes(); }
+    static uint64_t lds_bytes(uint64_t, uint64_t, bool self) { return long_lds_bytes(self); }
     static float coeff(int metric, uint64_t d) { return screen_coeff_long(metric, d); }
     static const char* too_long() { return "for the streamed screen (d above 4096)"; }
     template <bool MATRIX>
@@ -195,8 +215,13 @@ struct StreamedScreen {
         return for_screened_metric(metric, [&](auto m) {
             constexpr int M = decltype(m)::value;
             // (more LDS than the default limit of a launch: said once per kernel; a refusal shows in the launch itself)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&exact_screen_long_kernel<M, MATRIX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL((exact_screen_long_kernel<M, MATRIX>), grid, dim3(LONG_THREADS), lds, stream, ix, a);
+            if (a.self != nullptr) {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&exact_screen_long_kernel<M, MATRIX, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                hipLaunchKernelGGL((exact_screen_long_kernel<M, MATRIX, true>), grid, dim3(LONG_THREADS), lds, stream, ix, a);
+            } else {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&exact_screen_long_kernel<M, MATRIX, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                hipLaunchKernelGGL((exact_screen_long_kernel<M, MATRIX, false>), grid, dim3(LONG_THREADS), lds, stream, ix, a);
+            }
         });
     }
 };
@@ -212,6 +237,20 @@ int exact_screened_long(const DeviceIndex& dev, const std::vector<uint64_t>& ori
 
 // The device side of hnswxl_screen_matrix (host buffers): the streamed screen kernel with a store epilogue, whatever d is
 int exact_screen_long_matrix(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ScreenMatrixArgs& a, std::string& err) {
+    return screen_matrix_call<StreamedScreen>(dev, origin_id, a, err);
+}
+
+// The device side of hnswxg_exact_graph_batch(_device) (hnsw_mi355x_exact_graph_screen.h): the k-NN graph of the stored points behind
+// the SELF variant of the screen that the rows' padded length picks, as above (above 4096 elements: not screened, stats word 2)
+int exact_graph_screened(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const GraphCallArgs& a, uint64_t* out_stats, bool host, void* stream,
+                         std::string& err) {
+    if (round_up((uint64_t)dev.view().d, KC) < LONG_MIN_DPAD) return exact_graph_screened_resident(dev, origin_id, a, out_stats, host, stream, err);
+    return screened_graph_call<StreamedScreen>(dev, origin_id, a, out_stats, host, stream, err);
+}
+
+// The device side of hnswxg_screen_matrix (host buffers; a.self): the bounds of the kernel that the graph call runs at this length
+int exact_graph_screen_matrix(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ScreenMatrixArgs& a, std::string& err) {
+    if (round_up(a.d, KC) < LONG_MIN_DPAD) return exact_screen_matrix(dev, origin_id, a, err);
     return screen_matrix_call<StreamedScreen>(dev, origin_id, a, err);
 }
 

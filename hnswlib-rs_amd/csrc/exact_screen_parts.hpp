@@ -100,9 +100,10 @@ __device__ __forceinline__ float screen_ub(float s, float nq, float nx, float cu
 }
 
 // LDS of a workgroup of `waves` wavefronts: the queries (pitch dpad + 4 floats: 16-byte reads of 8 consecutive queries cover every
-// bank once), two staged row blocks, and per query the threshold, the list's length and the norm
-uint64_t screen_lds_bytes(uint64_t waves, uint64_t dpad) {
-    return waves * SQ * (dpad + 4) * 4 + 2ull * RB * RPITCH * 4 + waves * SQ * 16;
+// bank once), two staged row blocks, and per query the threshold, the list's length and the norm -- self (the queries are stored
+// points, exact_screen_knn.hpp): and the query's own DataId rank
+uint64_t screen_lds_bytes(uint64_t waves, uint64_t dpad, bool self = false) {
+    return waves * SQ * (dpad + 4) * 4 + 2ull * RB * RPITCH * 4 + waves * SQ * (self ? 20 : 16);
 }
 
 // one thread per query slot of the chunk's tiles: the padded row, the two norms (slots behind the last query: zeros)
@@ -168,11 +169,11 @@ int row_norms(ExactState& st, const DeviceIndexView& v, hipStream_t stream, cons
 
 // wavefronts of a screen workgroup for rows of d elements on this device: as many (4 at most) as its LDS holds queries for; 0: none
 // (exact_screen_long.hip keeps no queries resident and does not ask)
-[[maybe_unused]] uint32_t screen_waves(int device, uint64_t dpad) {
+[[maybe_unused]] uint32_t screen_waves(int device, uint64_t dpad, bool self = false) {
     int limit = 0;
     if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) return 0;
     for (uint32_t w = MAX_WAVES; w > 0u; w >>= 1)
-        if (screen_lds_bytes(w, dpad) <= (uint64_t)limit) return w;
+        if (screen_lds_bytes(w, dpad, self) <= (uint64_t)limit) return w;
     return 0;
 }
 

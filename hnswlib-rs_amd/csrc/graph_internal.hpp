@@ -31,6 +31,13 @@ struct GraphOrder {
 // defined in knn_graph.hip: OK, or ERR_DEVICE with `err` set
 int graph_order(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, GraphOrder& out, std::string& err);
 
+// defined in knn_graph.hip, for the graph calls there and for the screened exact graph (exact_screen_knn.hpp): the a.np points that
+// a.point_ids names (host memory for `host`; nullptr: every point, in position order) as flat ids in device memory, m_flat.  Waits
+// for `stream`.  Returns ERR_ARG, nothing searched and no output written, when an id names no point.
+struct ExactState;
+struct GraphCallArgs;
+int graph_resolve(const DeviceIndexView& v, const ExactState& st, const GraphCallArgs& a, bool host, DevMem& m_flat, hipStream_t stream, std::string& err);
+
 // defined in spanning_forest.hip, which holds the kernel: core[v] = the stored bits of slot min(core_k, counts[v]) - 1 of row v of n
 // rows of k slots (a StagedGraph's dists and counts), +0 for an empty row; one thread per row, numbered in 64 bits.  On `stream`,
 // nobody waits.

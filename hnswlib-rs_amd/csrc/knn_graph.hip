@@ -83,8 +83,10 @@ __global__ __launch_bounds__(64) void graph_compact_kernel(DeviceIndexView ix, c
     if (lane == 0u) dst.counts[row] = left;
 }
 
+}  // namespace
+
 // the points that `a` names as flat ids in device memory (m_flat; word 0 of m_ctrl counts the unknown ids); point_ids is host memory
-// for `host`.  Returns ERR_ARG, nothing searched and no output written, when an id names no point.
+// for `host`.  Returns ERR_ARG, nothing searched and no output written, when an id names no point.  (graph_internal.hpp)
 int graph_resolve(const DeviceIndexView& v, const ExactState& st, const GraphCallArgs& a, bool host, DevMem& m_flat, hipStream_t stream, std::string& err) {
     DevMem m_ids, m_ctrl;
     HIP_TRY(m_flat.alloc(a.np * sizeof(uint32_t)));
@@ -108,8 +110,6 @@ int graph_resolve(const DeviceIndexView& v, const ExactState& st, const GraphCal
     }
     return OK;
 }
-
-}  // namespace
 
 // Approximate graph: chunk by chunk of at most HNSWGPU_GRAPH_CHUNK points (unset: what GRAPH_SCRATCH holds), the points' vectors
 // gathered on the device, searched by the batched search itself with knbn = k + 1, and compacted into the caller's rows.

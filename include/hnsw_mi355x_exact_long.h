@@ -39,7 +39,8 @@ int hnswxl_exact_search_batch_device(const hnswgpu_index* idx, const float* d_qu
  *   refused   HNSWGPU_ERR_ARG: d above 4096 ("rows too long"); otherwise as hnswxs_screen_matrix refuses.                             */
 int hnswxl_screen_matrix(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, float* out_lb);
 
-/* Out of scope: the range search and DBSCAN behind this kernel; a set of filters; the queries by stored point; F16 storage; sharding. */
+/* The queries by stored point behind this kernel: hnsw_mi355x_exact_graph_screen.h (hnswxg_*).
+ * Out of scope: the range search and DBSCAN behind this kernel; a set of filters; F16 storage; sharding.                            */
 
 #ifdef __cplusplus
 }

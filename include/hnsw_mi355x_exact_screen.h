@@ -51,7 +51,8 @@ int hnswxs_exact_search_batch_device(const hnswgpu_index* idx, const float* d_qu
  *             written.                                                                                                             */
 int hnswxs_screen_matrix(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, float* out_lb);
 
-/* Out of scope: a set of filters; the queries by stored point; DBSCAN's passes; F16 storage; sharding.                             */
+/* The queries by stored point behind this screen: hnsw_mi355x_exact_graph_screen.h (hnswxg_*).
+ * Out of scope: a set of filters; DBSCAN's passes; F16 storage; sharding.                                                          */
 
 #ifdef __cplusplus
 }

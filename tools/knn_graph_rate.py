@@ -10,8 +10,16 @@
     knn_graph_rate.py --dump-dir DIR --approx         loads the dump; the approximate graph of ALL points at ef = 64 against
                                                       parallel_search_flat of the same vectors uploaded in calls of 100 000, and
                                                       its recall against the exact graph on the 10 000-point sample
+    knn_graph_rate.py --screened [--n N --d D] [--all]  no dump: a cheap index of N x D clustered rows built in the process; the exact
+                                                      graph of 10 000 named points (--all: of every point) through the DEVICE
+                                                      entries: hnswgpu_exact_graph_batch_device, the yardstick, and -- where the
+                                                      library has it -- hnswxg_exact_graph_batch_device on the same inputs, its
+                                                      out_stats and the byte comparison of the two answers.  With --package-root
+                                                      DIR2 the yardstick alone through the parent commit's package: run the two
+                                                      in alternation
 Warm-up calls first, then the median and the spread of --repeats calls.  Every mode prints one JSON line."""
 import argparse
+import ctypes as C
 import json
 import os
 import statistics
@@ -44,9 +52,47 @@ def timed(fn, warmup, repeats):
     return dict(median=statistics.median(ts), min=min(ts), max=max(ts))
 
 
+def screened_mode(a, H, out):
+    import torch
+    import hnsw_rs_amd._native as N
+    L = H.lib()
+    n, d = a.n, a.d
+    h = H.Hnsw(8, n, 16, 16, DIST)  # (the graph plays no part in an exhaustive call: a cheap one)
+    h.set_build_options(nthreads=0, gpu_device=0, gpu_window=0)
+    h.parallel_insert(clustered(n, d, 1))
+    h.upload(0)
+    pts = None if a.all else np.sort(np.random.default_rng(5).choice(n, SAMPLE, replace=False)).astype(np.uint64)
+    m = n if a.all else SAMPLE
+    dp = None if a.all else torch.from_numpy(pts.view(np.int64)).cuda()
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
+    stats = np.zeros(3, np.uint64)
+
+    def answer():
+        return [torch.zeros((m, K), dtype=torch.int64, device="cuda"), torch.zeros((m, K), dtype=torch.float32, device="cuda"),
+                torch.zeros(m, dtype=torch.int32, device="cuda")]
+
+    def call(entry, o, tail):
+        rc = getattr(L, entry)(h.handle, ptr(dp), m, K, None, 0, ptr(o[0]), ptr(o[1]), None, None, ptr(o[2]), *tail, None)
+        assert rc == 0, N.last_error()
+    old, new = answer(), answer()
+    out.update(mode="screened", n=n, d=d, points=m)
+    out["exact_graph_device_s"] = timed(lambda: call("hnswgpu_exact_graph_batch_device", old, ()), a.warmup, a.repeats)
+    if hasattr(L, "hnswxg_exact_graph_batch_device"):
+        out["screened_graph_device_s"] = timed(lambda: call("hnswxg_exact_graph_batch_device", new, (stats.ctypes.data_as(C.c_void_p),)), a.warmup, a.repeats)
+        out["out_stats"] = [int(x) for x in stats]
+        out["same_bytes_as_the_existing_call"] = bool(torch.equal(old[0], new[0]) and torch.equal(old[1].view(torch.int32), new[1].view(torch.int32)) and
+                                                      torch.equal(old[2], new[2]))
+        out["existing_over_screened"] = out["exact_graph_device_s"]["median"] / out["screened_graph_device_s"]["median"]
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--dump-dir", required=True)
+    ap.add_argument("--dump-dir", default=None)
+    ap.add_argument("--screened", action="store_true")
+    ap.add_argument("--all", action="store_true")
+    ap.add_argument("--n", type=int, default=N_POINTS)
+    ap.add_argument("--d", type=int, default=DIM)
     ap.add_argument("--build", action="store_true")
     ap.add_argument("--exact", action="store_true")
     ap.add_argument("--approx", action="store_true")
@@ -61,8 +107,12 @@ def main():
     import hnsw_rs_amd as H
     H.build_native()
     n, d = N_POINTS, DIM
-    X = clustered(n, d, 1)                                   # (ids are 0 .. n-1: point i carries id i)
     out = dict(package_root=a.package_root or "this tree", n=n, d=d, dist=DIST, k=K, repeats=a.repeats, warmup=a.warmup)
+    if a.screened:
+        return screened_mode(a, H, out)
+    if a.dump_dir is None:
+        ap.error("--dump-dir is required by --build, --exact and --approx")
+    X = clustered(n, d, 1)                                   # (ids are 0 .. n-1: point i carries id i)
     if a.build:
         h = H.Hnsw(a.m, n, 16, a.efc, DIST)
         h.set_build_options(nthreads=0, gpu_device=0, gpu_window=0)

@@ -4,14 +4,15 @@
     tools/kres.py exact [extra -D flags ...]            the kernels of exact_knn.hip, exact_range.hip and knn_graph.hip (every
                                                         instantiation of the two slab kernels)
     tools/kres.py dbscan [extra -D flags ...]           the kernels of dbscan.hip (both passes of its slab kernel per metric)
-    tools/kres.py screen [extra -D flags ...]           the kernels of exact_screen.hip (screen and rerank per metric; built, like the
-                                                        library's unit, without packed f32 instructions)
+    tools/kres.py screen [extra -D flags ...]           the kernels of exact_screen.hip (screen and rerank per metric, each with its
+                                                        SELF variant -- the last template argument -- for the screened exact graph;
+                                                        built, like the library's unit, without packed f32 instructions)
     tools/kres.py range_screen [extra -D flags ...]     the kernels of exact_range_screen.hip (screen per metric and register tile,
                                                         rerank per metric; the same flags as screen)
     tools/kres.py dbscan_screen [extra -D flags ...]    the kernels of dbscan_screen.hip (screen per metric, pass and register tile,
                                                         rerank per metric and pass; the same flags as screen)
-    tools/kres.py screen_long [extra -D flags ...]      the kernels of exact_screen_long.hip (the streamed screen per metric, the rerank
-                                                        it shares with screen; the same flags as screen; -DHNSW_LONG_NT=2,
+    tools/kres.py screen_long [extra -D flags ...]      the kernels of exact_screen_long.hip (the streamed screen per metric and its
+                                                        SELF variant, the rerank it shares with screen; the same flags as screen; -DHNSW_LONG_NT=2,
                                                         -DHNSW_LONG_WAVES_PER_SIMD=1 for the variants)"""
 import os
 import re
