@@ -919,6 +919,15 @@ class Hnsw:
         byte for byte, and stats, three u64: queries answered through the screen, queries answered by the existing path because a
         buffer of the screened path was outgrown, queries not screened at all (a distance without a screen, a small index, very
         long rows).  Returns (RangeResult, stats)."""
+        return self._exact_range_screened("hnswxr_exact_range_search_batch", datas, radius, allowed_ids)
+
+    def exact_range_search_long_flat(self, datas, radius, allowed_ids=None):
+        """exact_range_search_screened_flat with the streamed screen kernel behind rows of more than 256 elements
+        (include/hnsw_mi355x_exact_range_long.h): four wavefronts at every d up to 4096, the same RangeResult byte for byte.
+        Returns (RangeResult, stats)."""
+        return self._exact_range_screened("hnswxrl_exact_range_search_batch", datas, radius, allowed_ids)
+
+    def _exact_range_screened(self, entry, datas, radius, allowed_ids):
         datas = np.ascontiguousarray(datas, dtype=np.float32)
         if datas.ndim != 2:
             raise HnswError(N.ERR_ARG, "datas must be a (nq, d) matrix")
@@ -943,8 +952,8 @@ class Hnsw:
         cap = max(1024, 32 * nq)
         for attempt in range(2):
             ids, dists, layers, ranks = empty(cap)
-            rc = self._lib.hnswxr_exact_range_search_batch(self._h, _p(datas), nq, d, _p(radii), _p(allowed), n_allowed, cap, _p(offsets),
-                                                           _p(ids), _p(dists), _p(layers), _p(ranks), _p(stats))
+            rc = getattr(self._lib, entry)(self._h, _p(datas), nq, d, _p(radii), _p(allowed), n_allowed, cap, _p(offsets),
+                                           _p(ids), _p(dists), _p(layers), _p(ranks), _p(stats))
             if rc != N.ERR_CAPACITY or attempt == 1:
                 break
             cap = int(offsets[nq])

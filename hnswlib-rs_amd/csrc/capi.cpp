@@ -2025,7 +2025,9 @@ int hnswxg_screen_matrix(const hnswgpu_index* cidx, const uint64_t* point_ids, u
 
 // ---- exact range search behind a matrix-core screen (hnsw_mi355x_exact_range_screen.h; exact_range_screen.hip holds the device
 // side): the checks are hnswgpu_exact_range_search_batch's own, in its order
-static int exact_range_screened_pair(const hnswgpu_index* cidx, const ExactRangeCallArgs& a, uint64_t* out_stats, bool host, void* stream) {
+typedef int (*RangeScreenedFn)(const DeviceIndex&, const std::vector<uint64_t>&, const ExactRangeCallArgs&, uint64_t*, bool, void*, std::string&);
+static int exact_range_screened_pair(const hnswgpu_index* cidx, const ExactRangeCallArgs& a, uint64_t* out_stats, bool host, void* stream,
+                                     RangeScreenedFn device_side = hnswgpu::exact_range_screened) {
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
     std::shared_lock<std::shared_mutex> sl(idx->mu);
@@ -2040,12 +2042,12 @@ static int exact_range_screened_pair(const hnswgpu_index* cidx, const ExactRange
             return HNSWGPU_OK;
         }
     }
-    if (!hnswgpu::exact_range_screened) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    if (!device_side) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     DeviceIndex* dev = nullptr;
     rc = call_replica(idx, sl, host, true, true, &dev);
     if (rc != HNSWGPU_OK) return rc;
     std::string err;
-    return finish(hnswgpu::exact_range_screened(*dev, idx->flat->origin_id, a, out_stats, host, stream, err), err);
+    return finish(device_side(*dev, idx->flat->origin_id, a, out_stats, host, stream, err), err);
 }
 
 int hnswxr_exact_range_search_batch(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, const float* radii,
@@ -2065,6 +2067,28 @@ int hnswxr_exact_range_search_batch_device(const hnswgpu_index* idx, const float
     return exact_range_screened_pair(idx, ExactRangeCallArgs{d_queries, d_radii, nq, d, d_allowed_ids, n_allowed, cap, d_out_offsets, d_out_ids, d_out_dists,
                                                              d_out_layer, d_out_rank},
                                      out_stats, false, stream);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+// ---- the same two behind the streamed screen for long rows (hnsw_mi355x_exact_range_long.h; exact_range_screen_long.hip holds the
+// device side): the same checks through the same function
+int hnswxrl_exact_range_search_batch(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, const float* radii,
+                                     const uint64_t* allowed_ids, uint64_t n_allowed, uint64_t cap, uint64_t* out_offsets, uint64_t* out_ids,
+                                     float* out_dists, uint8_t* out_layer, int32_t* out_rank, uint64_t* out_stats) {
+    CAPI_GUARD_BEGIN
+    return exact_range_screened_pair(idx, ExactRangeCallArgs{queries, radii, nq, d, allowed_ids, n_allowed, cap, out_offsets, out_ids, out_dists, out_layer, out_rank},
+                                     out_stats, true, nullptr, hnswgpu::exact_range_screened_long);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswxrl_exact_range_search_batch_device(const hnswgpu_index* idx, const float* d_queries, uint64_t nq, uint64_t d, const float* d_radii,
+                                            const uint64_t* d_allowed_ids, uint64_t n_allowed, uint64_t cap, uint64_t* d_out_offsets,
+                                            uint64_t* d_out_ids, float* d_out_dists, uint8_t* d_out_layer, int32_t* d_out_rank,
+                                            uint64_t* out_stats, void* stream) {
+    CAPI_GUARD_BEGIN
+    return exact_range_screened_pair(idx, ExactRangeCallArgs{d_queries, d_radii, nq, d, d_allowed_ids, n_allowed, cap, d_out_offsets, d_out_ids, d_out_dists,
+                                                             d_out_layer, d_out_rank},
+                                     out_stats, false, stream, hnswgpu::exact_range_screened_long);
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 

@@ -27,6 +27,7 @@
 #include "../../include/hnsw_mi355x_exact_range_screen.h"
 #include "../../include/hnsw_mi355x_exact_long.h"
 #include "../../include/hnsw_mi355x_exact_graph_screen.h"
+#include "../../include/hnsw_mi355x_exact_range_long.h"
 #include "builder.hpp"
 #include "flat_index.hpp"
 #include "search_device.hpp"
@@ -435,6 +436,10 @@ int exact_graph_screened_resident(const DeviceIndex& dev, const std::vector<uint
 // hnswgpu_exact_range_search_batch checks its own, and out_stats ([3], host memory either way, may be nullptr)
 HNSWGPU_DEVICE_SIDE int exact_range_screened(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ExactRangeCallArgs& a, uint64_t* out_stats,
                                              bool host, void* stream, std::string& err);
+// the device side of hnswxrl_exact_range_search_batch(_device) (hnsw_mi355x_exact_range_long.h), defined in
+// exact_range_screen_long.hip, which routes by the rows' length: the arguments and the checks of the one above
+HNSWGPU_DEVICE_SIDE int exact_range_screened_long(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const ExactRangeCallArgs& a, uint64_t* out_stats,
+                                                  bool host, void* stream, std::string& err);
 // the device side of hnswxd_exact(_device) and hnswxd_bounds_matrix, defined in dbscan_screen.hip: exact_dbscan's arguments, checked as
 // hnswdbs_exact checks its own, and out_stats ([4], host memory either way, may be nullptr)
 HNSWGPU_DEVICE_SIDE int exact_dbscan_screened(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const DbscanArgs& a, uint64_t* out_stats, bool host,

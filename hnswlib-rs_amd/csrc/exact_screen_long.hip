@@ -33,19 +33,7 @@ constexpr uint32_t LONG_ROWS = 32u * LONG_NT;        // rows of a staged block
 constexpr uint32_t LONG_STAGED = LONG_QT + LONG_ROWS;  // staged rows of a step: the tile's queries in front, the block's rows behind
 constexpr uint32_t LONG_THREADS = 64u * MAX_WAVES;
 constexpr uint32_t LONG_PRE_Q = LONG_QT * 8u / LONG_THREADS;    // float4s of the queries' chunk per thread; of the rows': LONG_NT
-constexpr uint64_t LONG_MAX_DPAD = 4096;
-constexpr uint64_t LONG_MIN_DPAD = 288;              // below: the resident kernel with four wavefronts
 static_assert(LONG_THREADS == 256u && LONG_QT * 8u % LONG_THREADS == 0u, "a thread stages row (tid >> 3) + 32 j of the queries and of the rows");
-
-// The coefficient of the error term for the streamed screen: screen_coeff up to 1120 elements, where it was proved with the O(du)
-// factors below 1; beyond, with those factors carried for d <= 4096 and K = d + 39 >= dpad + 8.  Exact in f32: an
-// integer below 2^15 times 2^-24.
-float screen_coeff_long(int metric, uint64_t d) {
-    if (d <= 1120) return screen_coeff(metric, d);
-    if (metric == DIST_L2) return (float)(4 * d + 96) * 0x1p-24f;
-    if (metric == DIST_DOT) return (float)(d + 64) * 0x1p-24f;
-    return (float)(2 * d + 96) * 0x1p-24f;
-}
 
 uint64_t long_lds_bytes(bool self) { return 2ull * LONG_STAGED * RPITCH * 4 + LONG_QT * (self ? 20 : 16); }
 

@@ -36,6 +36,20 @@ float screen_coeff(int metric, uint64_t d) {
     return (float)(2 * d + 32) * 0x1p-24f;                           // DistCosine: absolute, on the cosine
 }
 
+// The streamed screens (exact_screen_long.hip, exact_range_screen_long.hip) by a row's padded length
+constexpr uint64_t LONG_MAX_DPAD = 4096;
+constexpr uint64_t LONG_MIN_DPAD = 288;              // below: the resident kernel with four wavefronts
+
+// The coefficient of the error term for the streamed screen: screen_coeff up to 1120 elements, where it was proved with the O(du)
+// factors below 1; beyond, with those factors carried for d <= 4096 and K = d + 39 >= dpad + 8.  Exact in f32: an
+// integer below 2^15 times 2^-24.
+[[maybe_unused]] float screen_coeff_long(int metric, uint64_t d) {
+    if (d <= 1120) return screen_coeff(metric, d);
+    if (metric == DIST_L2) return (float)(4 * d + 96) * 0x1p-24f;
+    if (metric == DIST_DOT) return (float)(d + 64) * 0x1p-24f;
+    return (float)(2 * d + 96) * 0x1p-24f;
+}
+
 // A lower bound, as an f32 that is never NaN and never below +0, of the distance exact_knn.hip computes for a pair whose inner product
 // the matrix cores gave as s; nq, nx: the two squared norms in plain f32; cu: screen_coeff.  The last step is the reference's own last
 // step (a correctly rounded sqrt; 1 - x and the clamp; DistCosine: in f64 and narrowed) applied to a bound of its argument: every

@@ -12,8 +12,8 @@ against the yardstick hnswgpu_exact_search_batch at k = 10 of the same build on 
                                                         (the parent commit, built there): the regression check
     exact_range_rate.py --screened [--n N --dim D --dist DIST] [--package-root DIR2]
                                                         the DEVICE entries on the null stream, device buffers made once: the existing
-                                                        call and, where the package has it, hnswxr_exact_range_search_batch_device on
-                                                        the same inputs, with its out_stats, at about 10 answers per query (each
+                                                        call and, where the package has them, hnswxr_ and hnswxrl_exact_range_search_batch_device
+                                                        on the same inputs, with their out_stats, at about 10 answers per query (each
                                                         query's 10th-nearest distance) and at one radius for all (about
                                                         --wide-answers answers per query, from 64 queries' pooled nearest
                                                         distances); the bytes of both are compared.  One JSON line per case,
@@ -107,6 +107,11 @@ def screened_mode(H, a):
             out["screened_s"] = timed(lambda: device_range_call(L, "hnswxr_exact_range_search_batch_device", h, dq, dr, nq, d, total, new, stats), a.warmup, a.repeats)
             out["out_stats"] = stats.tolist()
             out["same_bytes"] = bool(all(torch.equal(x, y) for x, y in zip(old, new)))
+        if hasattr(L, "hnswxrl_exact_range_search_batch_device"):   # the streamed screen for long rows, on the same inputs
+            far, stats = mk(), np.zeros(3, np.uint64)
+            out["long_s"] = timed(lambda: device_range_call(L, "hnswxrl_exact_range_search_batch_device", h, dq, dr, nq, d, total, far, stats), a.warmup, a.repeats)
+            out["long_stats"] = stats.tolist()
+            out["long_same_bytes"] = bool(all(torch.equal(x, y) for x, y in zip(old, far)))
         print(json.dumps(out), flush=True)
 
 
