@@ -74,6 +74,11 @@ _TREE_RANGE_LONG_HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "hns
 _PKG_RANGE_LONG_HEADER = os.path.join(PKG_DIR, "hnsw_mi355x_exact_range_long.h")
 RANGE_LONG_HEADER_PATH = _TREE_RANGE_LONG_HEADER if os.path.exists(_TREE_RANGE_LONG_HEADER) else _PKG_RANGE_LONG_HEADER
 RANGE_LONG_HEADER = _cheader.load(RANGE_LONG_HEADER_PATH, GRAPH_SCREEN_HEADER)
+# the screened exact DBSCAN for long rows (hnswxdl_*) has a twelfth header, which includes the eleventh: read with that as its base
+_TREE_DBSCAN_LONG_HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "hnsw_mi355x_dbscan_long.h")
+_PKG_DBSCAN_LONG_HEADER = os.path.join(PKG_DIR, "hnsw_mi355x_dbscan_long.h")
+DBSCAN_LONG_HEADER_PATH = _TREE_DBSCAN_LONG_HEADER if os.path.exists(_TREE_DBSCAN_LONG_HEADER) else _PKG_DBSCAN_LONG_HEADER
+DBSCAN_LONG_HEADER = _cheader.load(DBSCAN_LONG_HEADER_PATH, RANGE_LONG_HEADER)
 OK, ERR_ARG, ERR_IO, ERR_FORMAT, ERR_DISTANCE, ERR_TYPE, ERR_DEVICE, ERR_EMPTY, ERR_REF_PANIC, ERR_CAPACITY = (
     HEADER.constants["HNSWGPU_" + n] for n in ("OK", "ERR_ARG", "ERR_IO", "ERR_FORMAT", "ERR_DISTANCE", "ERR_TYPE", "ERR_DEVICE",
                                                "ERR_EMPTY", "ERR_REF_PANIC", "ERR_CAPACITY"))
@@ -90,7 +95,7 @@ def build_native(force=False, verbose=False):
             if f.endswith((".cpp", ".hip", ".hpp", ".inc")) or f == "Makefile"]
     srcs += [HEADER_PATH, HDBSCAN_HEADER_PATH, SELECT_HEADER_PATH, PREDICT_HEADER_PATH, DBSCAN_HEADER_PATH, SCREEN_HEADER_PATH,
              RANGE_SCREEN_HEADER_PATH, DBSCAN_SCREEN_HEADER_PATH, LONG_HEADER_PATH, GRAPH_SCREEN_HEADER_PATH,
-             RANGE_LONG_HEADER_PATH]
+             RANGE_LONG_HEADER_PATH, DBSCAN_LONG_HEADER_PATH]
 
     def fresh():
         return (os.path.exists(LIB_PATH)
@@ -101,7 +106,8 @@ def build_native(force=False, verbose=False):
                           (_TREE_PREDICT_HEADER, _PKG_PREDICT_HEADER), (_TREE_DBSCAN_HEADER, _PKG_DBSCAN_HEADER),
                           (_TREE_SCREEN_HEADER, _PKG_SCREEN_HEADER), (_TREE_RANGE_SCREEN_HEADER, _PKG_RANGE_SCREEN_HEADER),
                           (_TREE_DBSCAN_SCREEN_HEADER, _PKG_DBSCAN_SCREEN_HEADER), (_TREE_LONG_HEADER, _PKG_LONG_HEADER),
-                          (_TREE_GRAPH_SCREEN_HEADER, _PKG_GRAPH_SCREEN_HEADER), (_TREE_RANGE_LONG_HEADER, _PKG_RANGE_LONG_HEADER)):
+                          (_TREE_GRAPH_SCREEN_HEADER, _PKG_GRAPH_SCREEN_HEADER), (_TREE_RANGE_LONG_HEADER, _PKG_RANGE_LONG_HEADER),
+                          (_TREE_DBSCAN_LONG_HEADER, _PKG_DBSCAN_LONG_HEADER)):
             if os.path.exists(tree):
                 try:
                     if not os.path.exists(pkg) or open(pkg, "rb").read() != open(tree, "rb").read():
@@ -164,6 +170,8 @@ LONG_SYMBOLS = {name: (res, args) for name, (res, args, _names, _text) in LONG_H
 GRAPH_SCREEN_SYMBOLS = {name: (res, args) for name, (res, args, _names, _text) in GRAPH_SCREEN_HEADER.prototypes.items()}
 # every symbol include/hnsw_mi355x_exact_range_long.h declares
 RANGE_LONG_SYMBOLS = {name: (res, args) for name, (res, args, _names, _text) in RANGE_LONG_HEADER.prototypes.items()}
+# every symbol include/hnsw_mi355x_dbscan_long.h declares
+DBSCAN_LONG_SYMBOLS = {name: (res, args) for name, (res, args, _names, _text) in DBSCAN_LONG_HEADER.prototypes.items()}
 
 _lib = None
 
@@ -181,7 +189,8 @@ def lib():
         for name, (res, args) in (list(SYMBOLS.items()) + list(HDBSCAN_SYMBOLS.items()) + list(SELECT_SYMBOLS.items())
                                   + list(PREDICT_SYMBOLS.items()) + list(DBSCAN_SYMBOLS.items()) + list(SCREEN_SYMBOLS.items())
                                   + list(RANGE_SCREEN_SYMBOLS.items()) + list(DBSCAN_SCREEN_SYMBOLS.items()) + list(LONG_SYMBOLS.items())
-                                  + list(GRAPH_SCREEN_SYMBOLS.items()) + list(RANGE_LONG_SYMBOLS.items())):
+                                  + list(GRAPH_SCREEN_SYMBOLS.items()) + list(RANGE_LONG_SYMBOLS.items())
+                                  + list(DBSCAN_LONG_SYMBOLS.items())):
             fn = getattr(L, name)  # AttributeError if the library does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

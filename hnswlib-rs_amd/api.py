@@ -1170,25 +1170,41 @@ class Hnsw:
         """dbscan(eps, min_samples) behind the two-sided matrix-core screen (hnswxd_exact): the same DbscanResult byte for byte, and the
         four stats words -- points answered through the screen, answered by the existing path because the candidate buffer was
         outgrown, not screened at all, pairs that went through the exact chain.  Returns (DbscanResult, stats)."""
+        return self._dbscan_screened("hnswxd_exact", eps, min_samples)
+
+    def dbscan_screened_long(self, eps, min_samples):
+        """dbscan_screened with the streamed screen kernel behind rows of more than 256 elements (hnswxdl_exact,
+        include/hnsw_mi355x_dbscan_long.h): four wavefronts at every d up to 4096, the same DbscanResult byte for byte and the same
+        four stats words.  Returns (DbscanResult, stats)."""
+        return self._dbscan_screened("hnswxdl_exact", eps, min_samples)
+
+    def _dbscan_screened(self, entry, eps, min_samples):
         eps, min_samples = _dbscan_params(eps, min_samples)
         labels, core, counts, anchors, c = _dbscan_arrays(self.get_nb_point())
         stats = np.zeros(4, np.uint64)
         if self._h is None:
             return DbscanResult(labels, core.astype(bool), counts, anchors, 0), stats
-        _check(self._lib.hnswxd_exact(self._h, eps, min_samples, _p(labels), _p(core), _p(counts), _p(anchors), _p(c), _p(stats)))
+        _check(getattr(self._lib, entry)(self._h, eps, min_samples, _p(labels), _p(core), _p(counts), _p(anchors), _p(c), _p(stats)))
         return DbscanResult(labels, core.astype(bool), counts, anchors, int(c[0])), stats
 
     def dbscan_bounds_matrix(self, datas):
         """The screen's two bounds of every (row of datas, stored point) distance, two (nq, n) f32 matrices (lb, ub) with the points in
         dump order: the diagnostic entry hnswxd_bounds_matrix.  ub is +inf where the bound is not proved.  nq * n up to 2^24; DistL2,
         DistDot, DistCosine."""
+        return self._dbscan_bounds("hnswxd_bounds_matrix", datas)
+
+    def dbscan_long_bounds_matrix(self, datas):
+        """dbscan_bounds_matrix from the streamed screen kernel, whatever d is, 1 to 4096 (hnswxdl_bounds_matrix)."""
+        return self._dbscan_bounds("hnswxdl_bounds_matrix", datas)
+
+    def _dbscan_bounds(self, entry, datas):
         datas = np.ascontiguousarray(datas, dtype=np.float32)
         if datas.ndim != 2:
             raise HnswError(N.ERR_ARG, "datas must be a (nq, d) matrix")
         nq, d = datas.shape
         lb, ub = np.zeros((nq, self.get_nb_point()), np.float32), np.zeros((nq, self.get_nb_point()), np.float32)
         if self._h is not None:
-            _check(self._lib.hnswxd_bounds_matrix(self._h, _p(datas), nq, d, _p(lb), _p(ub)))
+            _check(getattr(self._lib, entry)(self._h, _p(datas), nq, d, _p(lb), _p(ub)))
         return lb, ub
 
     def knn_graph_spanning_forest(self, knbn, ef=None, mode="union", core_k=0):

@@ -1842,8 +1842,11 @@ static int dbscan_call_check(const char* what, uint64_t n, const DbscanArgs& a) 
     return HNSWGPU_OK;
 }
 
-// (screened: the entries of hnsw_mi355x_dbscan_screen.h -- the same checks in the same order, then dbscan_screen.hip; out_stats is theirs)
-static int exact_dbscan_pair(const hnswgpu_index* cidx, const DbscanArgs& a, bool host, void* stream, bool screened = false, uint64_t* out_stats = nullptr) {
+// (screened: the entries of hnsw_mi355x_dbscan_screen.h and of hnsw_mi355x_dbscan_long.h -- the same checks in the same order, then
+// their device side; out_stats is theirs)
+typedef int (*DbscanScreenedFn)(const DeviceIndex&, const std::vector<uint64_t>&, const DbscanArgs&, uint64_t*, bool, void*, std::string&);
+static int exact_dbscan_pair(const hnswgpu_index* cidx, const DbscanArgs& a, bool host, void* stream, bool screened = false, uint64_t* out_stats = nullptr,
+                             DbscanScreenedFn device_side = hnswgpu::exact_dbscan_screened) {
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
     std::shared_lock<std::shared_mutex> sl(idx->mu);
@@ -1858,12 +1861,12 @@ static int exact_dbscan_pair(const hnswgpu_index* cidx, const DbscanArgs& a, boo
         if (out_stats) out_stats[0] = out_stats[1] = out_stats[2] = out_stats[3] = 0;
         return HNSWGPU_OK;
     }
-    if (!hnswgpu::exact_dbscan || (screened && !hnswgpu::exact_dbscan_screened)) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    if (!hnswgpu::exact_dbscan || (screened && !device_side)) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     DeviceIndex* dev = nullptr;
     rc = call_replica(idx, sl, host, true, true, &dev);
     if (rc != HNSWGPU_OK) return rc;
     std::string err;
-    if (screened) return finish(hnswgpu::exact_dbscan_screened(*dev, idx->flat->origin_id, a, out_stats, host, stream, err), err);
+    if (screened) return finish(device_side(*dev, idx->flat->origin_id, a, out_stats, host, stream, err), err);
     return finish(hnswgpu::exact_dbscan(*dev, idx->flat->origin_id, a, host, stream, err), err);
 }
 
@@ -2110,8 +2113,8 @@ int hnswxd_exact_device(const hnswgpu_index* idx, float eps, uint64_t min_sample
     CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
 }
 
-int hnswxd_bounds_matrix(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, float* out_lb, float* out_ub) {
-    CAPI_GUARD_BEGIN
+typedef int (*DbscanBoundsFn)(const DeviceIndex&, const std::vector<uint64_t>&, const DbscanBoundsArgs&, std::string&);
+static int dbscan_bounds_entry(const hnswgpu_index* cidx, const float* queries, uint64_t nq, uint64_t d, float* out_lb, float* out_ub, DbscanBoundsFn device_side) {
     hnswgpu_index* idx = const_cast<hnswgpu_index*>(cidx);
     if (!idx) return fail(HNSWGPU_ERR_ARG, "null argument");
     std::shared_lock<std::shared_mutex> sl(idx->mu);
@@ -2123,12 +2126,41 @@ int hnswxd_bounds_matrix(const hnswgpu_index* cidx, const float* queries, uint64
     int rc = capi_refuse_f16(idx, "the screen");
     if (rc != HNSWGPU_OK) return rc;
     if (index_empty(idx) || nq == 0) return HNSWGPU_OK;
-    if (!hnswgpu::dbscan_bounds_matrix) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
+    if (!device_side) return fail(HNSWGPU_ERR_DEVICE, kNoFilterSetDevice);
     DeviceIndex* dev = nullptr;
     rc = primary_f32_replica(idx, sl, &dev);
     if (rc != HNSWGPU_OK) return rc;
     std::string err;
-    return finish(hnswgpu::dbscan_bounds_matrix(*dev, idx->flat->origin_id, DbscanBoundsArgs{queries, nq, d, out_lb, out_ub}, err), err);
+    return finish(device_side(*dev, idx->flat->origin_id, DbscanBoundsArgs{queries, nq, d, out_lb, out_ub}, err), err);
+}
+
+int hnswxd_bounds_matrix(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, float* out_lb, float* out_ub) {
+    CAPI_GUARD_BEGIN
+    return dbscan_bounds_entry(idx, queries, nq, d, out_lb, out_ub, hnswgpu::dbscan_bounds_matrix);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+// ---- the same three behind the streamed screen for long rows (hnsw_mi355x_dbscan_long.h; dbscan_screen_long.hip holds the device
+// side): the same checks through the same functions
+int hnswxdl_exact(const hnswgpu_index* idx, float eps, uint64_t min_samples, int32_t* out_label, uint8_t* out_core, uint32_t* out_count,
+                  uint32_t* out_anchor, uint64_t* out_n_clusters, uint64_t* out_stats) {
+    CAPI_GUARD_BEGIN
+    return exact_dbscan_pair(idx, DbscanArgs{eps, min_samples, DbscanOut{out_label, out_core, out_count, out_anchor, out_n_clusters}}, true, nullptr, true,
+                             out_stats, hnswgpu::exact_dbscan_screened_long);
+    CAPI_GUARD_END(HNSWGPU_ERR_ARG)
+}
+
+int hnswxdl_exact_device(const hnswgpu_index* idx, float eps, uint64_t min_samples, int32_t* d_out_label, uint8_t* d_out_core, uint32_t* d_out_count,
+                         uint32_t* d_out_anchor, uint64_t* out_n_clusters, uint64_t* out_stats, void* stream) {
+    CAPI_GUARD_BEGIN
+    return exact_dbscan_pair(idx, DbscanArgs{eps, min_samples, DbscanOut{d_out_label, d_out_core, d_out_count, d_out_anchor, out_n_clusters}}, false, stream,
+                             true, out_stats, hnswgpu::exact_dbscan_screened_long);
+    CAPI_GUARD_END(HNSWGPU_ERR_DEVICE)
+}
+
+int hnswxdl_bounds_matrix(const hnswgpu_index* idx, const float* queries, uint64_t nq, uint64_t d, float* out_lb, float* out_ub) {
+    CAPI_GUARD_BEGIN
+    return dbscan_bounds_entry(idx, queries, nq, d, out_lb, out_ub, hnswgpu::dbscan_bounds_matrix_long);
     CAPI_GUARD_END(HNSWGPU_ERR_ARG)
 }
 

@@ -28,6 +28,7 @@
 #include "../../include/hnsw_mi355x_exact_long.h"
 #include "../../include/hnsw_mi355x_exact_graph_screen.h"
 #include "../../include/hnsw_mi355x_exact_range_long.h"
+#include "../../include/hnsw_mi355x_dbscan_long.h"
 #include "builder.hpp"
 #include "flat_index.hpp"
 #include "search_device.hpp"
@@ -451,6 +452,11 @@ struct DbscanBoundsArgs {     // host memory
     float* out_ub;
 };
 HNSWGPU_DEVICE_SIDE int dbscan_bounds_matrix(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const DbscanBoundsArgs& a, std::string& err);
+// the device side of hnswxdl_exact(_device) and hnswxdl_bounds_matrix (hnsw_mi355x_dbscan_long.h), defined in dbscan_screen_long.hip,
+// which routes the first by the rows' length: the arguments and the checks of the two above
+HNSWGPU_DEVICE_SIDE int exact_dbscan_screened_long(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const DbscanArgs& a, uint64_t* out_stats, bool host,
+                                                   void* stream, std::string& err);
+HNSWGPU_DEVICE_SIDE int dbscan_bounds_matrix_long(const DeviceIndex& dev, const std::vector<uint64_t>& origin_id, const DbscanBoundsArgs& a, std::string& err);
 }  // namespace hnswgpu
 
 // No C++ exception may cross the C ABI: every entry point is `try { ... HNSWGPU_CAPI_GUARD_END(ret)`

@@ -7,7 +7,9 @@ index: n x 128 DistL2, clustered, GPU-assisted build, M = 16, ef_construction 64
     sample of the points reach -- few points core, about half, nearly all;
   * hnswdbs_csr_device on the symmetric graph at k = 10 (ef = 64, UNION, add_self 1), eps the middle one.
 --screened: hnswxd_exact_device (the same bytes behind the two-sided matrix-core screen) is timed beside hnswdbs_exact_device on the same
-inputs, its out_stats kept and its five outputs compared with the existing call's.
+inputs, its out_stats kept and its five outputs compared with the existing call's.  --long: hnswxdl_exact_device (the streamed screen
+for long rows) likewise.  --dim, --dist: another shape -- then on a cheap graph (M = 8), which plays no part in the exact calls, and
+without the count pass and the CSR form, which the long-row lines do not need.
 One warm-up call, then the median of --repeats.  One JSON line.
     dbscan_rate.py --n 1000000
 Per-kernel times: run the tool under `rocprofv3 --kernel-trace --stats -- python tools/dbscan_rate.py --n N`."""
@@ -36,6 +38,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--screened", action="store_true", help="also time hnswxd_exact_device on the same inputs")
+    ap.add_argument("--long", action="store_true", help="also time hnswxdl_exact_device on the same inputs")
+    ap.add_argument("--dim", type=int, default=DIM)
+    ap.add_argument("--dist", default=DIST)
+    ap.add_argument("--build", default="this tree", help="what the line says it was measured on: the checkout, a -D variant")
     a = ap.parse_args()
     import torch
     torch.cuda.init()
@@ -44,13 +50,14 @@ def main():
     L = H.lib()
     N = H._native
     n, nq = a.n, min(a.nq, a.n)
-    X = clustered(n, DIM, 1)
-    h = H.Hnsw(16, n, 16, 64, DIST)
+    dim, dist, plain = a.dim, a.dist, (a.dim, a.dist) == (DIM, DIST)
+    X = clustered(n, dim, 1)
+    h = H.Hnsw(16, n, 16, 64, dist) if plain else H.Hnsw(8, n, 16, 16, dist)
     h.set_build_options(nthreads=0, gpu_device=0, gpu_window=0)
     t0 = time.perf_counter()
     h.parallel_insert(X)
     h.upload(0)
-    out = dict(n=n, d=DIM, dist=DIST, min_samples=MIN_SAMPLES, nq_count_pass=nq, repeats=a.repeats, warmup=a.warmup,
+    out = dict(build=a.build, n=n, d=dim, dist=dist, min_samples=MIN_SAMPLES, nq_count_pass=nq, repeats=a.repeats, warmup=a.warmup,
                build_and_upload_s=time.perf_counter() - t0)
     rng = np.random.default_rng(2)
     sample = X[rng.choice(n, min(n, 2000), replace=False)]
@@ -70,29 +77,38 @@ def main():
         torch.cuda.synchronize()
 
         def count_form():
-            rc = L.hnswgpu_exact_range_search_batch_device(h.handle, ptr(d_q), nq, DIM, ptr(d_rad), None, 0, 0, ptr(d_off), None, None, None, None, None)
+            rc = L.hnswgpu_exact_range_search_batch_device(h.handle, ptr(d_q), nq, dim, ptr(d_rad), None, 0, 0, ptr(d_off), None, None, None, None, None)
             assert rc in (N.OK, N.ERR_CAPACITY), N.last_error()    # (count only: "the answers need more than 0 slots" is the answer)
 
         def dbscan_form():
             rc = L.hnswdbs_exact_device(h.handle, eps, MIN_SAMPLES, ptr(label), ptr(core), ptr(count), ptr(anchor), c.ctypes.data, None)
             assert rc == 0, N.last_error()
         b = dict(core_share_asked=share, eps=eps)
-        b["count_only_s"] = timed(count_form, a.warmup, a.repeats)
-        b["answers_per_query"] = float(d_off[-1].item()) / nq
-        b["count_pass_scaled_to_n_s"] = b["count_only_s"]["median"] * n / nq
+        if plain:
+            b["count_only_s"] = timed(count_form, a.warmup, a.repeats)
+            b["answers_per_query"] = float(d_off[-1].item()) / nq
+            b["count_pass_scaled_to_n_s"] = b["count_only_s"]["median"] * n / nq
         b["dbscan_exact_device_s"] = timed(dbscan_form, a.warmup, a.repeats)
         b["clusters"], b["core"], b["noise"] = int(c[0]), int(core.sum().item()), int((label < 0).sum().item())
-        b["ratio_to_one_count_pass"] = b["dbscan_exact_device_s"]["median"] / b["count_pass_scaled_to_n_s"]
-        if a.screened:
-            old, stats = [t.clone() for t in (label, core, count, anchor)] + [int(c[0])], np.zeros(4, np.uint64)
+        if plain:
+            b["ratio_to_one_count_pass"] = b["dbscan_exact_device_s"]["median"] / b["count_pass_scaled_to_n_s"]
+        old = [t.clone() for t in (label, core, count, anchor)] + [int(c[0])]
+        for asked, entry, key in ((a.screened, "hnswxd_exact_device", "screened"), (a.long, "hnswxdl_exact_device", "long")):
+            if not asked:
+                continue
+            stats = np.zeros(4, np.uint64)
 
             def screened_form():
-                rc = L.hnswxd_exact_device(h.handle, eps, MIN_SAMPLES, ptr(label), ptr(core), ptr(count), ptr(anchor), c.ctypes.data, stats.ctypes.data, None)
+                rc = getattr(L, entry)(h.handle, eps, MIN_SAMPLES, ptr(label), ptr(core), ptr(count), ptr(anchor), c.ctypes.data, stats.ctypes.data, None)
                 assert rc == 0, N.last_error()
-            b["dbscan_screened_device_s"] = timed(screened_form, a.warmup, a.repeats)
-            b["out_stats"] = stats.tolist()
-            b["same_bytes"] = all(torch.equal(x, y) for x, y in zip(old[:4], (label, core, count, anchor))) and old[4] == int(c[0])
+            b[f"dbscan_{key}_device_s"] = timed(screened_form, a.warmup, a.repeats)
+            b["out_stats" if key == "screened" else "out_stats_long"] = stats.tolist()
+            b["same_bytes" if key == "screened" else "same_bytes_long"] = (all(torch.equal(x, y) for x, y in zip(old[:4], (label, core, count, anchor)))
+                                                                           and old[4] == int(c[0]))
         out["cases"].append(b)
+    if not plain:
+        print(json.dumps(out), flush=True)
+        return
     g = h.symmetric_knn_graph_flat(K, EF, "union")
     d_offs, d_cols, d_dists = dev(g.offsets.view(np.int64)), dev(g.pos.astype(np.uint32).view(np.int32)), dev(g.dists)
     eps = eps_of[len(eps_of) // 2]

@@ -16,7 +16,10 @@
                                                         -DHNSW_LONG_WAVES_PER_SIMD=1 for the variants)
     tools/kres.py range_screen_long [extra -D flags ...]  the kernels of exact_range_screen_long.hip (the streamed range screen per metric
                                                         and register tile, the rerank and the scatter it shares with range_screen; the
-                                                        same flags as screen; -DHNSW_RANGE_LONG_NT=2 changes the default only)"""
+                                                        same flags as screen; -DHNSW_RANGE_LONG_NT=2 changes the default only)
+    tools/kres.py dbscan_screen_long [extra -D flags ...]  the kernels of dbscan_screen_long.hip (the streamed DBSCAN screen per metric, pass
+                                                        and register tile, the prep, cut and rerank it shares with dbscan_screen; the
+                                                        same flags as screen; -DHNSW_DBSCAN_LONG_NT=2 changes the default only)"""
 import os
 import re
 import subprocess
@@ -25,9 +28,9 @@ import sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 flags = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-pthread", "--offload-arch=gfx950",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-Rpass-analysis=kernel-resource-usage"]
-if sys.argv[1] in ("exact", "dbscan", "screen", "range_screen", "dbscan_screen", "screen_long", "range_screen_long"):
-    units = {"exact": ("exact_knn", "exact_range", "knn_graph"), "dbscan": ("dbscan",), "screen": ("exact_screen",), "range_screen": ("exact_range_screen",), "dbscan_screen": ("dbscan_screen",), "screen_long": ("exact_screen_long",), "range_screen_long": ("exact_range_screen_long",)}[sys.argv[1]]
-    if sys.argv[1] in ("screen", "range_screen", "dbscan_screen", "screen_long", "range_screen_long"):
+if sys.argv[1] in ("exact", "dbscan", "screen", "range_screen", "dbscan_screen", "screen_long", "range_screen_long", "dbscan_screen_long"):
+    units = {"exact": ("exact_knn", "exact_range", "knn_graph"), "dbscan": ("dbscan",), "screen": ("exact_screen",), "range_screen": ("exact_range_screen",), "dbscan_screen": ("dbscan_screen",), "screen_long": ("exact_screen_long",), "range_screen_long": ("exact_range_screen_long",), "dbscan_screen_long": ("dbscan_screen_long",)}[sys.argv[1]]
+    if sys.argv[1] in ("screen", "range_screen", "dbscan_screen", "screen_long", "range_screen_long", "dbscan_screen_long"):
         flags += ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
     cmds = [[*flags, *sys.argv[2:], "-c", unit + ".hip", "-o", f"/tmp/kres_{unit}.o"] for unit in units]
 else:
